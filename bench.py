@@ -3,9 +3,11 @@
 
 A step = one pass of the hot path over one block that is already resident in HBM:
     suffix sort -> BWT -> DC (GPU)  ->  distance stream D2H  ->  `dark` model + range coder (host)  -> coded stream.
-`value` is whole-job encode throughput in MB/s (MB = 10^6 input bytes) over all ranks.  Extra keys on the same JSON line:
-device-only rates (BWT forward, forward incl. DC), decode rate, the roofline of the dominant kernel measured with HIP
-events on the library's own stream, and the CPU oracle timed on a bounded sample (rank 0, N=1 only).
+`value` is whole-job encode throughput in MB/s (MB = 10^6 input bytes) over all ranks; `ms_per_step` is one timed step.
+A plain run sets up, warms up, times --steps steps, writes the coded stream of the last one (--dump-outputs DIR) and prints the line.
+With --full the timed steps carry HIP-event pairs around every kernel launch, and the same JSON line gets the legs beside the headline:
+device-only rates (BWT forward, forward incl. DC), the host_input, decode and pipelined legs, the roofline of the dominant kernel,
+the measured copy rate, and the CPU oracle on the same block (rank 0, N=1 only).
 
 Multi-GPU: one process per GPU (torch.distributed, backend nccl = RCCL), independent blocks, no data-path collective;
 RCCL only gathers the final bitstreams on rank 0 (inside the timed region).  Scaling is weak: one block per GPU.
@@ -67,7 +69,16 @@ def parse():
     ap.add_argument("--stub-exchange", action="store_true",
                     help="CPU rehearsal of the multi-rank plumbing (launcher, process group, exchange, max-over-ranks timing) with backend gloo: "
                          "the per-rank streams come from the product's host coder on seeded distances; no GPU is touched")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: per-kernel HIP-event times in the timed steps, unprofiled stage times, the host_input, "
+                         "decode, gather and pipelined legs, roofline and copy rate, the CPU baseline and the RCCL self-test (the --no-* options "
+                         "above and the --cpu-* / --pipeline-* settings apply to these legs)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the coded stream of the last one as DIR/*.npy (float32 / float64; see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def free_port():
@@ -287,6 +298,35 @@ def thread_summary(reports, plan):
             "entropy_fallback": ("ranks %s coded on fewer host threads than planned (%d): max-over-ranks is theirs" % (short, want)) if short else None}
 
 
+DUMP_SAMPLE_BYTES = 8 << 20  # stream bytes written as float32 values (32 MiB), over all ranks
+DUMP_MAX_SUMS = 1 << 20      # block sums written as float64 values (8 MiB), over all ranks
+
+
+def dump_outputs(out_dir, stream, rank, world):
+    """--dump-outputs: what a caller of the timed path receives -- the coded stream of the last timed step -- as .npy files that two
+    builds can be compared on, byte values and sums held exactly:
+      stream.npy             float32 bytes of the stream: all of them up to DUMP_SAMPLE_BYTES, else one byte from each of that many
+                             equal strata at a seeded offset (the same positions for the same stream length)
+      stream_block_sums.npy  float64 sums of consecutive runs of >= 256 bytes covering the whole stream (at most DUMP_MAX_SUMS of them)
+      stream_length.npy      float64 [length in bytes]
+    Several ranks: every rank writes its own stream under names ending in _rank<r>, the budget shared among them."""
+    s = np.asarray(stream, dtype=np.uint8).reshape(-1)
+    L = len(s)
+    cap = max(1, DUMP_SAMPLE_BYTES // world)
+    if L <= cap:
+        sample = s
+    else:
+        idx = np.arange(cap, dtype=np.int64) * L // cap + np.random.default_rng(0).integers(0, L // cap, size=cap)
+        sample = s[idx]
+    run = max(256, -(-L // max(1, DUMP_MAX_SUMS // world)))
+    sums = np.add.reduceat(s, np.arange(0, L, run), dtype=np.uint64) if L else np.zeros(0, np.uint64)
+    tag = "" if world == 1 else "_rank%d" % rank
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "stream%s.npy" % tag), sample.astype(np.float32))
+    np.save(os.path.join(out_dir, "stream_block_sums%s.npy" % tag), sums.astype(np.float64))
+    np.save(os.path.join(out_dir, "stream_length%s.npy" % tag), np.array([L], dtype=np.float64))
+
+
 def cpu_budget():
     """CPUs this container may use (cgroup quota; os.cpu_count() when unlimited)."""
     try:
@@ -385,13 +425,15 @@ def main():
     for _ in range(args.warmup):
         encode_step()
     ctx.stats_reset()
-    ctx.set_profiling(True)
+    ctx.set_profiling(args.full)  # --full: HIP-event pairs around every launch, for the per-kernel times (a plain run times the steps alone)
     stage_acc = {}
     threads_seen, groups_seen = [], []
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         stream = encode_step()
+        if not args.full:
+            continue
         st = ctx.stats()
         for k in ("ms_sa", "ms_bwt", "ms_dc", "ms_d2h", "ms_entropy", "ms_total"):
             stage_acc[k] = stage_acc.get(k, 0.0) + st[k]
@@ -403,6 +445,29 @@ def main():
     ctx.set_profiling(False)
     stats = ctx.stats()
     stream = stream.copy()
+    tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+    if use_dist:
+        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+    elapsed_max = float(tmax.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, stream, rank, world)
+    headline = {
+        "metric": "bwt_encode_MBps", "value": round(world * n * args.steps / elapsed_max / 1e6, 3), "unit": "MB/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed_max / args.steps, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8/u32/u64 integer", "data": "real" if corpus_path else ("real (text files of this image, datagen.real_text)" if args.workload == "realtext_5e7" and not args.n else "synthetic"),
+        "config": {"workload": workload_name, "block_bytes": n, "model": args.model,
+                   "blocks_per_gpu": 1, "parallelism": "block-per-gpu x%d" % world, "host_cpus_per_rank": share, "node_gpus": node_gpus,
+                   "gather": args.gather if use_dist else "none"},
+        "compressed_bytes": int(len(stream)), "ratio": round(len(stream) / n, 4),
+    }
+    if corpus_path:
+        headline["corpus"] = {"path": corpus_path, "file_bytes": os.path.getsize(corpus_path), "block_bytes": n}
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline))
+        if use_dist:
+            dist.destroy_process_group()
+        return
     # The timed steps carry a HIP event pair around every kernel launch (the per-kernel times the roofline needs); every pair costs the
     # stream about 10 us of idle (measured with rocprofv3: 78 such gaps = 1 ms per suffix sort).  The device-stage times are therefore
     # taken once more from a few steps WITHOUT events -- what a caller of the library sees -- and reported as stage_ms_unprofiled.
@@ -413,11 +478,6 @@ def main():
         st = ctx.stats()
         for k in ("ms_sa", "ms_bwt", "ms_dc", "ms_d2h", "ms_entropy", "ms_total"):
             clean_acc[k] = clean_acc.get(k, 0.0) + st[k] / clean_steps
-
-    tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
-    if use_dist:
-        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-    elapsed_max = float(tmax.item())
 
     # host_input leg: where the reference's encode starts (the block in host memory: src/main.rs:87-95 -> src/block/dc.rs:41; SURVEY 8(d)
     # "end-to-end ... including H2D/D2H").  dk_block_encode from pinned and from pageable host memory, the H2D copy inside the timed region,
@@ -663,17 +723,11 @@ def main():
                             "time_source": "t_fwd_ms: three extra steps of this run without event pairs; t_fwd_ms_timed_steps: the timed steps",
                             "traffic_source": pmc_path + " (HBM bytes: a committed rocprofv3 --pmc profile of this command, not this run)"}
         result = {
-            "metric": "bwt_encode_MBps", "value": round(world * n * k / elapsed_max / 1e6, 3), "unit": "MB/s",
-            "n_gpus": world, "steps": k, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed_max / k, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8/u32/u64 integer", "data": "real" if corpus_path else ("real (text files of this image, datagen.real_text)" if args.workload == "realtext_5e7" and not args.n else "synthetic"),
-            "config": {"workload": workload_name, "block_bytes": n, "model": args.model,
-                       "blocks_per_gpu": 1, "parallelism": "block-per-gpu x%d" % world, "host_cpus_per_rank": share, "node_gpus": node_gpus,
-                       "gather": args.gather if use_dist else "none"},
+            **headline,
             "bwt_forward_MBps_per_gpu": round(n / (fwd_ms * 1e-3) / 1e6, 1),
             "device_forward_MBps_per_gpu": round(n / ((fwd_ms + clean_acc["ms_dc"]) * 1e-3) / 1e6, 1),
             "decode_MBps": None if decode_mbps is None else round(decode_mbps, 3),
             "roundtrip_ok": roundtrip_ok,
-            "compressed_bytes": int(len(stream)), "ratio": round(len(stream) / n, 4),
             "value_host_input_MBps": None if not host_input or "pinned" not in host_input else host_input["pinned"]["MBps"],
             "host_input": host_input,
             # (ms_h2d: the H2D copy of the host_input leg's pinned form -- the timed steps of `value` start with the block in HBM and have none)
@@ -693,7 +747,6 @@ def main():
             "datagen_s": round(t_gen, 2),
         }
         if corpus_path:
-            result["corpus"] = {"path": corpus_path, "file_bytes": os.path.getsize(corpus_path), "block_bytes": n}
             if os.path.basename(corpus_path) == "book1" and n == 768771 and args.model == "dark":
                 # the one number the reference publishes for this path (README.md:20): the .dark file = 4-byte header + stream
                 result["corpus"].update({"dark_file_bytes": int(len(stream)) + 4, "reference_dark_file_bytes": BOOK1_DARK_FILE_BYTES,

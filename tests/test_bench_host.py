@@ -44,3 +44,29 @@ def test_rank_report_and_summary():
     s = bench.thread_summary(rep, 4)
     assert s["entropy_fallback_ranks"] == [1] and "fewer host threads" in s["entropy_fallback"]
     assert bench.thread_summary(rep[:1], 4)["entropy_fallback"] is None
+
+
+def test_dump_outputs(tmp_path):
+    """--dump-outputs: the coded stream as float32 bytes (all of them, or one per stratum of a long stream at seeded offsets), float64 sums of
+    runs covering the whole stream and its length; the same stream gives the same files, the budget stays under 64 MB"""
+    rng = np.random.default_rng(3)
+    short = rng.integers(0, 256, size=5000, dtype=np.uint8)
+    bench.dump_outputs(str(tmp_path / "a"), short, 0, 1)
+    assert np.array_equal(np.load(tmp_path / "a" / "stream.npy"), short.astype(np.float32))
+    sums = np.load(tmp_path / "a" / "stream_block_sums.npy")
+    assert sums.dtype == np.float64 and len(sums) == 20 and sums.sum() == short.sum() and sums[1] == short[256:512].sum()
+    assert np.load(tmp_path / "a" / "stream_length.npy").tolist() == [5000.0]
+    long = rng.integers(0, 256, size=bench.DUMP_SAMPLE_BYTES * 3 + 77, dtype=np.uint8)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), long, 0, 1)
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert files == ["stream.npy", "stream_block_sums.npy", "stream_length.npy"]
+    for f in files:
+        x, y = np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y)
+    sample = np.load(tmp_path / "b" / "stream.npy")
+    assert len(sample) == bench.DUMP_SAMPLE_BYTES and np.isin(sample, long.astype(np.float32)).all()
+    assert np.load(tmp_path / "b" / "stream_block_sums.npy").sum() == long.sum()
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in files) < 64e6
+    bench.dump_outputs(str(tmp_path / "d"), short, 1, 2)  # one rank of two: its own names
+    assert sorted(os.listdir(tmp_path / "d")) == ["stream_block_sums_rank1.npy", "stream_length_rank1.npy", "stream_rank1.npy"]

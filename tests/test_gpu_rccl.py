@@ -4,7 +4,7 @@ SURVEY section 8(e): independent blocks, one rank per GPU, RCCL only gathers the
 that code at N = 1 are driven here as child processes (the rank initialises its GPU itself, nothing of this test process is inherited):
 under the driver's launcher command line (torch.distributed.run, one rank: the N > 1 code with WORLD_SIZE=1, exchange inside the timed
 region) and as a plain `python bench.py` (the finished stream goes through init_process_group("nccl", world_size=1) + the device-buffer
-exchange once more after the timed region)."""
+exchange once more after the timed region).  Both run with --full: the gather timings and the RCCL self-test are legs of it."""
 import json
 import os
 import subprocess
@@ -15,7 +15,7 @@ import pytest
 from test_dist_gloo import ROOT, _free_port
 
 pytestmark = pytest.mark.gpu
-SMALL = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "book1_like_768771", "--no-cpu-baseline", "--pipeline-blocks", "0"]
+SMALL = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "book1_like_768771", "--full", "--no-cpu-baseline", "--pipeline-blocks", "0"]
 
 
 def _run(cmd):

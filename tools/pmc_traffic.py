@@ -5,7 +5,7 @@ reads (corrected x2 for the streaming kernels listed below, raw for kernels domi
 
 On the GPU box (run from /tmp, TMPDIR=/tmp; the program itself follows `--`):
     rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_FETCH_SIZE -- python3 bench.py --steps 2 --warmup 1 \
-              --no-cpu-baseline --no-decode --pipeline-blocks 0
+              --full --no-cpu-baseline --no-decode --pipeline-blocks 0
     rocprofv3 --pmc WRITE_SIZE ... -d gpurun_out/pmc_WRITE_SIZE -- (same)
 then here:
     python tools/pmc_traffic.py gpurun_out/pmc_FETCH_SIZE gpurun_out/pmc_WRITE_SIZE --steps 3 --workload enwik8_like_1e8 \

@@ -13,6 +13,7 @@ ERROR_NAMES = {-1: "DK_E_ARG", -2: "DK_E_NOMEM", -3: "DK_E_HIP", -4: "DK_E_CAPAC
 MODEL_IDS = {"dark": 0, "exp": 1, "ybs": 2, "simple": 3, "rawdc": 4}
 NUM_KERNEL_SLOTS = 32
 DK_FLAG_HAS_FF, DK_FLAG_SINGLE_SYMBOL = 1, 2
+DK_PACKED_MAX_BLOCKS, DK_PACKED_MAX_BLOCK_BYTES = 65536, 1 << 24
 
 
 class Stats(C.Structure):
@@ -25,7 +26,8 @@ class Stats(C.Structure):
                 ("ws_peak_bytes", C.c_uint64), ("ws_size_bytes", C.c_uint64)]
 ROUTES = {"short_prefix": 0x1, "narrow_keys": 0x2, "text_round": 0x4, "isa_windows": 0x8, "isa_marked": 0x10, "isa_buckets": 0x20,
           "general_round": 0x40, "big_groups": 0x80, "inplace_rounds": 0x100, "pair_chains": 0x200, "lfirst": 0x400,
-          "lfirst_big_round": 0x800, "lfirst_deep": 0x1000, "lfirst_fallback": 0x2000, "lfirst_giant": 0x4000, "period_round": 0x8000, "packed_pairs": 0x10000}
+          "lfirst_big_round": 0x800, "lfirst_deep": 0x1000, "lfirst_fallback": 0x2000, "lfirst_giant": 0x4000, "period_round": 0x8000, "packed_pairs": 0x10000,
+          "packed_guard": 0x20000}
 
 
 # every symbol include/dark_amd.h declares: name -> (restype, argtypes)
@@ -57,6 +59,10 @@ SIGNATURES = {
     "dk_batch_begin": (_i, [_vp, _i, _i, C.POINTER(_vp)]),
     "dk_batch_push": (_i, [_vp, _vp, _sz, _vp, _sz, _szp]),
     "dk_batch_finish": (_i, [_vp]),
+    "dk_dev_bwt_forward_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _u32p]),
+    "dk_dev_dc_encode_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _szp]),
+    "dk_batch_push_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "dk_dev_packed_encode": (_i, [_vp, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i]),
     "dk_dev_batch_decode": (_i, [_vp, _i, _sz, _vp, _vp, _vp, _vp, _i]),
     "dk_multi_block_encode": (_i, [_vp, _i, _i, _sz, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz]),
     "dk_multi_block_decode": (_i, [_vp, _i, _i, _sz, _vp, _vp, _vp, _vp, _i, _vp, _sz]),

@@ -12,6 +12,8 @@ Extensions beyond the reference (whole file = one block, read into memory, one t
              block, followed by an index footer (record offsets) so that decoding can be batched and spread over GPUs.  The reference
              reads such a file as its first block only.  Blocks are STREAMED: one block of input is in host memory at a time; each goes
              through dk_batch_push as soon as it is in HBM (file reading, upload, GPU stages and the host coding of earlier blocks overlap).
+  --packed   with -b of at most 16 MiB on one GPU: consecutive blocks go to the GPU as packs of up to 64 MiB, each through ONE segmented
+             device pass (dk_batch_push_packed); every block is still coded on its own, and the archive is byte-identical.
   --gpus G   block b -> GPU b mod G, one worker process per GPU; the parent never touches a GPU and stitches the records in order.
   --force    encode blocks that contain byte 0xFF.  The reference's header cannot carry that symbol (src/block/dc.rs:57,60,73,127):
              it writes such an archive without complaint and can never decode it.  This front end refuses unless --force is given.
@@ -211,6 +213,54 @@ def _encode_blocks(path, model, block_size, device, first_block, step, total_blo
         t.join()
 
 
+PACK_BYTES = 64 << 20
+PACKED_MAX_BLOCK_BYTES = 1 << 24  # DK_PACKED_MAX_BLOCK_BYTES  # --packed: consecutive blocks grouped into packs of at most this many bytes
+
+
+def _encode_blocks_packed(path, model, block_size, device, total_blocks, out, index, force, host_threads):
+    """--packed: consecutive blocks go to the GPU as one pack (dk_batch_push_packed: one segmented device pass per pack, every block still
+    coded as its own job); the records are byte-identical to _encode_blocks'."""
+    import torch
+    from .context import Context
+    torch.cuda.set_device(device)
+    per_pack = max(1, PACK_BYTES // block_size)
+    with open(path, "rb") as f, Context(per_pack * block_size, device) as ctx:
+        STATS["t_ready"] = time.perf_counter()
+        flush_every = int(max(2 * host_threads, min(256, (1 << 32) // max(1, block_size))))
+        batch, pending = None, []
+
+        def flush():
+            nonlocal batch, pending
+            if batch is None:
+                return
+            streams = batch.finish()
+            for (b, n), s in zip(pending, streams):
+                out.write(struct.pack("<I", n))
+                out.write(memoryview(s))
+                index.append((b, 4 + len(s)))
+            batch, pending = None, []
+
+        try:
+            for b0 in range(0, total_blocks, per_pack):
+                data = np.fromfile(f, dtype=np.uint8, count=per_pack * block_size)
+                sizes = [min(block_size, len(data) - k) for k in range(0, len(data), block_size)]
+                for j, k in enumerate(range(0, len(data), block_size)):
+                    _check_ff(data[k:k + block_size], force, "block %d" % (b0 + j))
+                    _note_single_symbol(data[k:k + block_size], "block %d" % (b0 + j))
+                d = torch.from_numpy(data).to("cuda:%d" % device)
+                if batch is None:
+                    batch = ctx.batch_begin(model, host_threads)
+                batch.push_packed(d, sizes)
+                pending.extend((b0 + j, n) for j, n in enumerate(sizes))
+                del d, data
+                if len(pending) >= flush_every:
+                    flush()
+            flush()
+        finally:
+            if batch is not None:
+                batch.close()
+
+
 def _write_footer(out, offsets):
     """index of a multi-record file: 'DKIX' u32 count, count x u64 record offsets, u64 offset of this footer, 'DKIX'"""
     start = out.tell()
@@ -262,7 +312,7 @@ def _devices(device, gpus, devices):
     return [device + r for r in range(gpus)]
 
 
-def encode_file(path, model, block_size=0, device=0, gpus=1, force=False, host_threads=0, devices=None):
+def encode_file(path, model, block_size=0, device=0, gpus=1, force=False, host_threads=0, devices=None, packed=False):
     out_path = output_name(path, EXTENSION)
     total = os.path.getsize(path)
     if total == 0:
@@ -281,10 +331,15 @@ def encode_file(path, model, block_size=0, device=0, gpus=1, force=False, host_t
                 _write_block(ctx, model, block, out, b == 0, force)
         return out_path
     threads = host_threads or max(1, _host_threads() // max(1, gpus) - 1)
+    if packed and (gpus > 1 or block_size > PACKED_MAX_BLOCK_BYTES):
+        raise SystemExit("--packed: one GPU and -b at most %d" % PACKED_MAX_BLOCK_BYTES)
     if gpus <= 1:
         index = []
         with _AtomicOutput(out_path) as out:
-            _encode_blocks(path, model, block_size, device, 0, 1, nblocks, out, index, force, threads)
+            if packed:
+                _encode_blocks_packed(path, model, block_size, device, nblocks, out, index, force, threads)
+            else:
+                _encode_blocks(path, model, block_size, device, 0, 1, nblocks, out, index, force, threads)
             offsets, pos = [], 0
             for _, ln in index:
                 offsets.append(pos)
@@ -479,6 +534,8 @@ def main(argv=None):
     ap.add_argument("--host-threads", type=int, default=0, help="host coding threads per GPU (default: CPU quota / gpus - 1)")
     ap.add_argument("--devices", default="", help="GPU ids of the workers, comma separated (default: device, device+1, ...)")
     ap.add_argument("--stats", action="store_true", help="print a JSON line with the wall time of the work and the peak RSS to stderr")
+    ap.add_argument("--packed", action="store_true", help="with -b (at most 16 MiB, one GPU): consecutive blocks share one segmented GPU pass "
+                    "per 64 MiB pack; the archive is byte-identical to the one without")
     ap.add_argument("--worker", default="", help=argparse.SUPPRESS)
     ap.add_argument("--part", default="", help=argparse.SUPPRESS)
     ap.add_argument("file")
@@ -490,7 +547,8 @@ def main(argv=None):
     if decode:
         out = decode_file(args.file, args.model, args.device, args.gpus, args.host_threads, args.devices)
     else:
-        out = encode_file(args.file, args.model, args.block_size, args.device, args.gpus, args.force, args.host_threads, args.devices)
+        out = encode_file(args.file, args.model, args.block_size, args.device, args.gpus, args.force, args.host_threads, args.devices,
+                          args.packed)
     print(out)
     if args.stats:  # wall time of the work itself (interpreter start and imports of this front end excluded) and this process's peak RSS
         import json

@@ -204,6 +204,44 @@ class Context:
                                             _ptr(d_rank) if d_rank is not None else None, C.byref(m)))
         return init, m.value
 
+    # ---- packed forward path: blocks back to back in one uint8 device tensor, `sizes` = their lengths in order ----
+    def dev_bwt_forward_packed(self, d_in, sizes, d_bwt_out):
+        """L of every block into d_bwt_out (same layout as d_in); returns the list of origins"""
+        _inputs_ready(d_in)
+        count = len(sizes)
+        ns = (C.c_size_t * count)(*[int(n) for n in sizes])
+        origin = np.zeros(max(count, 1), dtype=np.uint32)
+        self._ck(self._lib.dk_dev_bwt_forward_packed(self._h, _ptr(d_in), count, ns, _ptr(d_bwt_out),
+                                                     origin.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return [int(o) for o in origin[:count]]
+
+    def dev_dc_encode_packed(self, d_bwt, sizes, d_dist, d_sym, d_rank=None):
+        """DC arrays of a packed L: block i's entries at [off_i, off_i + m_i); returns (list of init tables, list of m)"""
+        _inputs_ready(d_bwt)
+        count = len(sizes)
+        ns = (C.c_size_t * count)(*[int(n) for n in sizes])
+        init = np.zeros((max(count, 1), 256), dtype=np.uint32)
+        m = (C.c_size_t * max(count, 1))()
+        self._ck(self._lib.dk_dev_dc_encode_packed(self._h, _ptr(d_bwt), count, ns, _ptr(init), _ptr(d_dist), _ptr(d_sym),
+                                                   _ptr(d_rank) if d_rank is not None else None, m))
+        return [init[i] for i in range(count)], [int(m[i]) for i in range(count)]
+
+    def dev_packed_encode(self, model, d_in, sizes, host_threads=8, outs=None):
+        """every block of the pack coded as by dev_block_encode; returns (list of coded streams, list of DK_FLAG_* words)"""
+        _inputs_ready(d_in)
+        count = len(sizes)
+        mid = model_id(model)
+        if outs is None:  # (rawdc: one 10-byte record per distance)
+            outs = [np.empty((10 if mid == _lib.MODEL_IDS["rawdc"] else 2) * int(n) + 4096, dtype=np.uint8) for n in sizes]
+        ns = (C.c_size_t * count)(*[int(n) for n in sizes])
+        optrs = (C.c_void_p * count)(*[_ptr(o) for o in outs])
+        caps = (C.c_size_t * count)(*[len(o) for o in outs])
+        lens = (C.c_size_t * count)()
+        flags = (C.c_uint * max(count, 1))()
+        self._ck(self._lib.dk_dev_packed_encode(self._h, mid, _ptr(d_in), count, ns, optrs, caps, lens, flags,
+                                                int(host_threads)))
+        return [o[:lens[i]] for i, o in enumerate(outs)], [int(flags[i]) for i in range(count)]
+
     def dev_block_encode(self, model, d_in, n, out=None):
         """out: optional preallocated host uint8 array; returns a view of the coded stream"""
         _inputs_ready(d_in)
@@ -275,6 +313,17 @@ class Context:
         return keys, vals
 
 
+class _LenRef:
+    """one entry of a packed push's length array, read like a c_size_t"""
+
+    def __init__(self, arr, i):
+        self._arr, self._i = arr, i
+
+    @property
+    def value(self):
+        return self._arr[self._i]
+
+
 class Batch:
     """dk_batch_begin / _push / _finish: the pipelined encoder fed one block at a time.
 
@@ -286,6 +335,8 @@ class Batch:
         self._ctx = ctx
         self._h = C.c_void_p()
         self._outs, self._lens = [], []
+        self._keep = []  # ctypes arrays the coding threads of packed pushes write into
+        self._model = model_id(model)
         ctx._ck(ctx._lib.dk_batch_begin(ctx._h, model_id(model), int(host_threads), C.byref(self._h)))
         ctx._batch = self
 
@@ -315,6 +366,29 @@ class Batch:
             text = (self._ctx._lib.dk_last_error(self._ctx._h) or b"").decode()
             self.close()  # joins the coders of the blocks already queued; only then may the buffers die with this object
             raise DarkError(rc, text)
+
+    def push_packed(self, d_in, sizes):
+        """device stages of a whole pack now (one segmented pass), every block queued as its own coding job; returns the blocks'
+        DK_FLAG_* words.  Their streams come out of finish() in push order, with those of the other pushes."""
+        if not self._h:
+            raise DarkError(_lib.DK_E_ARG, "the batch is closed")
+        _inputs_ready(d_in)
+        count = len(sizes)
+        outs = [np.empty((10 if self._model == _lib.MODEL_IDS["rawdc"] else 2) * int(n) + 4096, dtype=np.uint8) for n in sizes]
+        lens = (C.c_size_t * max(count, 1))()
+        ns = (C.c_size_t * count)(*[int(n) for n in sizes])
+        optrs = (C.c_void_p * count)(*[_ptr(o) for o in outs])
+        caps = (C.c_size_t * count)(*[len(o) for o in outs])
+        flags = (C.c_uint * max(count, 1))()
+        self._outs.extend(outs)
+        self._keep.append((lens, ns, optrs, caps))
+        self._lens.extend(_LenRef(lens, i) for i in range(count))
+        rc = self._ctx._lib.dk_batch_push_packed(self._h, _ptr(d_in), count, ns, optrs, caps, lens, flags)
+        if rc != 0:
+            text = (self._ctx._lib.dk_last_error(self._ctx._h) or b"").decode()
+            self.close()
+            raise DarkError(rc, text)
+        return [int(flags[i]) for i in range(count)]
 
     def close(self):
         """dk_batch_finish without collecting anything (idempotent); returns its code"""

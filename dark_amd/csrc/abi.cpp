@@ -396,6 +396,7 @@ struct dk_batch {
     std::condition_variable cv_job, cv_slot;
     std::deque<Job> queue;
     std::vector<int> free_slots;
+    std::vector<size_t> slot_refs;  // jobs still reading each staging slot (a packed push queues several on one slot)
     std::vector<std::thread> pool;
     bool done = false;
     size_t pushed = 0;
@@ -418,7 +419,7 @@ struct dk_batch {
             {
                 std::lock_guard<std::mutex> lk(mu);
                 if (rc != DK_OK && first_rc == DK_OK) { first_rc = rc; first_bad = job.block; }
-                free_slots.push_back(job.slot);
+                if (--slot_refs[static_cast<size_t>(job.slot)] == 0) free_slots.push_back(job.slot);
             }
             cv_slot.notify_one();
         }
@@ -438,6 +439,7 @@ int dk_batch_begin(dk_ctx *ctx, int model_id, int host_threads, dk_batch **out) 
     b->model_id = model_id;
     const size_t workers = static_cast<size_t>(std::max(1, host_threads));
     for (size_t k = 0; k < workers + 1; ++k) b->free_slots.push_back(static_cast<int>(k));
+    b->slot_refs.assign(workers + 1, 0);
     for (size_t w = 0; w < workers; ++w) b->pool.emplace_back([b] { b->worker(); });
     ctx->live_batch = b;
     *out = b;
@@ -472,6 +474,7 @@ int dk_batch_push(dk_batch *b, const uint8_t *d_in, size_t n, uint8_t *out, size
     }
     {
         std::lock_guard<std::mutex> lk(b->mu);
+        b->slot_refs[static_cast<size_t>(slot)] = 1;
         b->queue.push_back(job);
     }
     b->cv_job.notify_one();
@@ -491,6 +494,247 @@ int dk_batch_finish(dk_batch *b) {
     if (rc != DK_OK) rc = b->ctx->fail(rc, "entropy stage of block %zu failed (%d)", b->first_bad, rc);
     delete b;
     return rc;
+}
+
+}  // extern "C"
+
+// ---- packed forward path (csrc/packed.hip) ----------------------------------------------------------------------
+namespace {
+
+// Rounds of the segmented suffix sort before the blocks still unresolved leave the pack for the single-block path.  With k symbols in the
+// initial key (6 to 8 for text-sized alphabets) R rounds resolve common prefixes of k * 2^R symbols.  tools/packed_throughput.py measured
+// at most 10 rounds on its text shapes (wiki_like; english_like 2, random bytes 0), so 12 leaves two rounds of headroom.
+constexpr int PACKED_MAX_ROUNDS = 12;
+
+int check_pack(dk_ctx *ctx, size_t count, const size_t *n, std::vector<uint32_t> &off) {
+    if (!n) return ctx->fail(DK_E_ARG, "null pointer");
+    if (count == 0 || count > DK_PACKED_MAX_BLOCKS) return ctx->fail(DK_E_ARG, "a pack holds 1 .. %d blocks, not %zu", DK_PACKED_MAX_BLOCKS, count);
+    off.assign(count + 1, 0);
+    size_t total = 0;
+    for (size_t i = 0; i < count; ++i) {
+        if (n[i] == 0) return ctx->fail(DK_E_ARG, "empty block %zu in the pack (the reference panics at src/saca.rs:107)", i);
+        if (n[i] > DK_PACKED_MAX_BLOCK_BYTES) return ctx->fail(DK_E_ARG, "block %zu of %zu bytes exceeds DK_PACKED_MAX_BLOCK_BYTES", i, n[i]);
+        total += n[i];
+        if (total > ctx->max_n) return ctx->fail(DK_E_ARG, "the pack exceeds the context capacity %zu", ctx->max_n);
+        off[i + 1] = static_cast<uint32_t>(total);
+    }
+    return DK_OK;
+}
+
+// L of every block into d_bwt and the origins into h_origin (host, count): one segmented pass, then the guard's blocks one by one
+int packed_forward(dk_ctx *ctx, const uint8_t *d_in, const std::vector<uint32_t> &off, const uint32_t *d_off, uint8_t *d_bwt, uint32_t *d_origin,
+                   std::vector<std::pair<size_t, uint32_t>> *fixed) {
+    hipStream_t st = ctx->stream;
+    const size_t count = off.size() - 1, total = off.back();
+    Timer t;
+    ctx->stats.sa_route = 0;
+    uint32_t *d_guard = ctx->ws_alloc<uint32_t>(count);
+    if (!d_guard) return DK_E_NOMEM;
+    size_t unresolved = 0;
+    DK_TRY(packed_bwt_device(ctx, d_in, d_off, count, total, d_bwt, d_origin, d_guard, PACKED_MAX_ROUNDS, &unresolved));
+    fixed->clear();
+    if (unresolved) {
+        std::vector<uint32_t> guard(count);
+        DK_HIP(ctx, hipMemcpyAsync(guard.data(), d_guard, count * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        DK_HIP(ctx, hipStreamSynchronize(st));
+        const uint32_t rounds = ctx->stats.rounds;
+        for (size_t i = 0; i < count; ++i) {
+            if (!guard[i]) continue;
+            const size_t mark = ctx->ws_mark(), n = off[i + 1] - off[i];
+            uint32_t *d_sa = ctx->ws_alloc<uint32_t>(n);
+            if (!d_sa) return DK_E_NOMEM;
+            uint32_t origin = 0;
+            DK_TRY(bwt_forward_device(ctx, d_in + off[i], n, d_sa, d_bwt + off[i], &origin));
+            fixed->emplace_back(i, origin);
+            ctx->ws_release(mark);
+        }
+        ctx->stats.rounds = rounds;
+        ctx->stats.sa_route = DK_ROUTE_PACKED_GUARD;
+    }
+    DK_HIP(ctx, hipStreamSynchronize(st));
+    ctx->stats.ms_sa = t.ms();
+    ctx->stats.ms_bwt = 0;
+    return DK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dk_dev_bwt_forward_packed(dk_ctx *ctx, const uint8_t *d_in, size_t count, const size_t *n, uint8_t *d_bwt_out, uint32_t *origin) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!d_in || !n || !d_bwt_out || !origin) return ctx->fail(DK_E_ARG, "null pointer");
+    std::vector<uint32_t> off;
+    DK_TRY(check_pack(ctx, count, n, off));
+    Timer t;
+    hipStream_t st = ctx->stream;
+    uint32_t *d_off = ctx->ws_alloc<uint32_t>(count + 1), *d_origin = ctx->ws_alloc<uint32_t>(count);
+    if (!d_off || !d_origin) return DK_E_NOMEM;
+    DK_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    std::vector<std::pair<size_t, uint32_t>> fixed;
+    DK_TRY(packed_forward(ctx, d_in, off, d_off, d_bwt_out, d_origin, &fixed));
+    DK_HIP(ctx, hipMemcpyAsync(origin, d_origin, count * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    DK_HIP(ctx, hipStreamSynchronize(st));
+    for (const auto &f : fixed) origin[f.first] = f.second;
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_dev_dc_encode_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, const size_t *n, uint32_t *init, uint32_t *d_dist, uint8_t *d_sym,
+                            uint8_t *d_rank, size_t *m) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!d_bwt || !n || !init || !d_dist || !d_sym || !m) return ctx->fail(DK_E_ARG, "null pointer");
+    std::vector<uint32_t> off;
+    DK_TRY(check_pack(ctx, count, n, off));
+    Timer t;
+    hipStream_t st = ctx->stream;
+    // read-back block: m | flags | rb (count + 1) | init (count x 256)
+    const size_t words = 3 * count + 1 + 256 * count;
+    uint32_t *d_off = ctx->ws_alloc<uint32_t>(count + 1), *d_res = ctx->ws_alloc<uint32_t>(words);
+    if (!d_off || !d_res) return DK_E_NOMEM;
+    DK_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    DK_TRY(packed_dc_device(ctx, d_bwt, d_off, count, off.back(), false, d_dist, d_sym, d_rank, nullptr, d_res, d_res + count, d_res + 2 * count,
+                            d_res + 3 * count + 1));
+    std::vector<uint32_t> res(words);
+    DK_HIP(ctx, hipMemcpyAsync(res.data(), d_res, words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    DK_HIP(ctx, hipStreamSynchronize(st));
+    for (size_t i = 0; i < count; ++i) m[i] = res[i];
+    std::memcpy(init, res.data() + 3 * count + 1, 256 * count * sizeof(uint32_t));
+    ctx->stats.ms_dc = ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// device stages of a pack for an open batch: everything up to the distance streams in staging slot `slot`, then one coding job per block
+int push_packed_body(dk_batch *b, int slot, const uint8_t *d_in, const std::vector<uint32_t> &off, uint8_t *const *out, const size_t *out_cap,
+                     size_t *out_len, unsigned *flags) {
+    dk_ctx *ctx = b->ctx;
+    hipStream_t st = ctx->stream;
+    const size_t count = off.size() - 1, total = off.back();
+    const bool want = b->model_id == DK_MODEL_RAWDC;
+    // read-back block: origin | m | flags | rb (count + 1) | init (count x 256)
+    const size_t words = 4 * count + 1 + 256 * count;
+    uint32_t *d_off = ctx->ws_alloc<uint32_t>(count + 1), *d_res = ctx->ws_alloc<uint32_t>(words);
+    uint8_t *d_bwt = ctx->ws_alloc<uint8_t>(total);
+    if (!d_off || !d_res || !d_bwt) return DK_E_NOMEM;
+    DK_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    std::vector<std::pair<size_t, uint32_t>> fixed;
+    {
+        const size_t mark = ctx->ws_mark();
+        DK_TRY(packed_forward(ctx, d_in, off, d_off, d_bwt, d_res, &fixed));
+        ctx->ws_release(mark);
+    }
+    uint32_t *d_dist = ctx->ws_alloc<uint32_t>(total);
+    uint8_t *d_sym = ctx->ws_alloc<uint8_t>(total);
+    uint8_t *d_rank = want ? ctx->ws_alloc<uint8_t>(total) : nullptr;
+    uint32_t *d_run_end = want ? ctx->ws_alloc<uint32_t>(total) : nullptr;
+    if (!d_dist || !d_sym || (want && (!d_rank || !d_run_end))) return DK_E_NOMEM;
+    Timer t3;
+    uint32_t *d_m = d_res + count, *d_flags = d_res + 2 * count, *d_rb = d_res + 3 * count, *d_init = d_res + 4 * count + 1;
+    DK_TRY(packed_dc_device(ctx, d_bwt, d_off, count, total, true, d_dist, d_sym, d_rank, d_run_end, d_m, d_flags, d_rb, d_init));
+    std::vector<uint32_t> res(words);
+    DK_HIP(ctx, hipMemcpyAsync(res.data(), d_res, words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    DK_HIP(ctx, hipStreamSynchronize(st));
+    ctx->stats.ms_dc = t3.ms();
+    for (const auto &f : fixed) res[f.first] = f.second;
+    const uint32_t *h_origin = res.data(), *h_m = res.data() + count, *h_flags = res.data() + 2 * count, *h_rb = res.data() + 3 * count;
+    const uint32_t *h_init = res.data() + 4 * count + 1;
+    Timer t4;
+    const size_t m = h_rb[count];
+    const size_t off_sym = 4 * m, off_rank = off_sym + ((m + 15) & ~size_t(15)), off_end = off_rank + ((m + 15) & ~size_t(15));
+    DK_TRY(ctx->ensure_slot(static_cast<size_t>(slot), off_end + 4 * m + 64));
+    char *stage = ctx->slots[static_cast<size_t>(slot)].h;
+    DK_HIP(ctx, hipMemcpyAsync(stage, d_dist, 4 * m, hipMemcpyDeviceToHost, st));
+    DK_HIP(ctx, hipMemcpyAsync(stage + off_sym, d_sym, m, hipMemcpyDeviceToHost, st));
+    if (want) {
+        DK_HIP(ctx, hipMemcpyAsync(stage + off_rank, d_rank, m, hipMemcpyDeviceToHost, st));
+        DK_HIP(ctx, hipMemcpyAsync(stage + off_end, d_run_end, 4 * m, hipMemcpyDeviceToHost, st));
+    }
+    DK_HIP(ctx, hipStreamSynchronize(st));
+    ctx->stats.ms_d2h = t4.ms();
+    ctx->stats.dc_runs = m;
+    std::vector<dk_batch::Job> jobs(count);
+    for (size_t i = 0; i < count; ++i) {
+        dk_batch::Job &job = jobs[i];
+        job.slot = slot;
+        job.n = off[i + 1] - off[i]; job.out = out[i]; job.cap = out_cap[i]; job.out_len = &out_len[i];
+        std::memcpy(job.fr.init, h_init + 256 * i, sizeof job.fr.init);
+        job.fr.origin = h_origin[i];
+        job.fr.m = h_m[i];
+        job.fr.dist = reinterpret_cast<const uint32_t *>(stage) + h_rb[i];
+        job.fr.sym = reinterpret_cast<const uint8_t *>(stage + off_sym) + h_rb[i];
+        if (want) {
+            job.fr.rank = reinterpret_cast<const uint8_t *>(stage + off_rank) + h_rb[i];
+            job.fr.run_end = reinterpret_cast<const uint32_t *>(stage + off_end) + h_rb[i];
+        }
+        if (flags) flags[i] = h_flags[i];
+    }
+    {
+        std::lock_guard<std::mutex> lk(b->mu);
+        for (auto &job : jobs) {
+            job.block = b->pushed++;
+            b->queue.push_back(job);
+        }
+        b->slot_refs[static_cast<size_t>(slot)] = count;
+    }
+    b->cv_job.notify_all();
+    return DK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dk_batch_push_packed(dk_batch *b, const uint8_t *d_in, size_t count, const size_t *n, uint8_t *const *out, const size_t *out_cap,
+                         size_t *out_len, unsigned *flags) {
+    if (!b) return DK_E_ARG;
+    dk_ctx *ctx = b->ctx;
+    if (!d_in || !n || !out || !out_cap || !out_len) return ctx->fail(DK_E_ARG, "null pointer");
+    std::vector<uint32_t> off;
+    DK_TRY(check_pack(ctx, count, n, off));
+    for (size_t i = 0; i < count; ++i) {
+        if (!out[i]) return ctx->fail(DK_E_ARG, "null output for block %zu of the pack", i);
+        if (n[i] > model_max_block(b->model_id)) return ctx->fail(DK_E_MODEL, "model %d cannot code a block of %zu bytes", b->model_id, n[i]);
+    }
+    if (hipSetDevice(ctx->device) != hipSuccess) return ctx->fail(DK_E_HIP, "hipSetDevice(%d) failed", ctx->device);
+    int slot;
+    {
+        std::unique_lock<std::mutex> lk(b->mu);
+        b->cv_slot.wait(lk, [&] { return !b->free_slots.empty(); });
+        slot = b->free_slots.back();
+        b->free_slots.pop_back();
+    }
+    ctx->ws_reset();
+    Timer t;
+    const int rc = push_packed_body(b, slot, d_in, off, out, out_cap, out_len, flags);
+    ctx->stats.ms_total = t.ms();
+    if (ctx->profiling) ctx->prof_collect();
+    if (rc != DK_OK) {
+        std::lock_guard<std::mutex> lk(b->mu);
+        b->free_slots.push_back(slot);
+        return rc;
+    }
+    return DK_OK;
+}
+
+int dk_dev_packed_encode(dk_ctx *ctx, int model_id, const uint8_t *d_in, size_t count, const size_t *n, uint8_t *const *out, const size_t *out_cap,
+                         size_t *out_len, unsigned *flags, int host_threads) {
+    if (!ctx) return DK_E_ARG;
+    Timer t;
+    dk_batch *b = nullptr;
+    const int threads = static_cast<int>(std::max<size_t>(1, std::min<size_t>(static_cast<size_t>(std::max(1, host_threads)), std::max<size_t>(1, count))));
+    DK_TRY(dk_batch_begin(ctx, model_id, threads, &b));
+    const int rc = dk_batch_push_packed(b, d_in, count, n, out, out_cap, out_len, flags);
+    const std::string err = ctx->err;
+    const int rc2 = dk_batch_finish(b);
+    if (rc != DK_OK) ctx->err = err;  // the push's text, not the finish's
+    ctx->stats.ms_total = t.ms();
+    return rc != DK_OK ? rc : rc2;
 }
 
 int dk_dev_batch_encode(dk_ctx *ctx, int model_id, size_t count, const uint8_t *const *d_in, const size_t *n, uint8_t *const *out,

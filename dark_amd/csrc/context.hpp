@@ -198,5 +198,15 @@ int bwt_inverse_device(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t ori
 // dc.hip: d_run_end may be null
 int dc_encode_device(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t init_host[256], uint32_t *d_dist, uint8_t *d_sym,
                      uint8_t *d_rank, uint32_t *d_run_end, size_t *m);
+// packed.hip: `count` blocks back to back in d_text, block i at [d_off[i], d_off[i+1]) (d_off on the device, d_off[count] = total).
+// packed_bwt_device: L of every block at its own range of d_bwt, d_origin[i] (device) = block i's origin; rounds stop after max_rounds and
+// d_guard[i] = 1 marks the blocks that were still unresolved then (their L / origin are NOT valid: the caller re-runs them alone);
+// *guarded = the number of suffixes left unresolved (0: every block is done).
+int packed_bwt_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, size_t count, size_t total, uint8_t *d_bwt, uint32_t *d_origin,
+                      uint32_t *d_guard, int max_rounds, size_t *guarded);
+// packed_dc_device: the DC arrays of every block of a packed L.  compact: block i's entries at [rb_i, rb_i + m_i) (global run order, rb on the
+// device in d_rb[0 .. count], d_rb[count] = all runs); otherwise at [off_i, off_i + m_i).  d_m / d_flags: count words, d_init: count x 256.
+int packed_dc_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, bool compact, uint32_t *d_dist,
+                     uint8_t *d_sym, uint8_t *d_rank, uint32_t *d_run_end, uint32_t *d_m, uint32_t *d_flags, uint32_t *d_rb, uint32_t *d_init);
 
 }  // namespace dk

@@ -134,6 +134,28 @@ typedef struct dk_batch dk_batch;
 int dk_batch_begin(dk_ctx *ctx, int model_id, int host_threads, dk_batch **out);
 int dk_batch_push(dk_batch *batch, const uint8_t *d_in, size_t n, uint8_t *out, size_t out_cap, size_t *out_len);
 int dk_batch_finish(dk_batch *batch);
+/* ---- packed forward path: many blocks laid back to back in ONE device buffer, block i = d_in[off_i, off_i + n[i]) with
+ * off_i = n[0] + ... + n[i-1].  One segmented suffix sort and one segmented DC pass serve the whole pack: O(rounds) launches, not O(blocks).
+ * Per block, every result equals the single-block entry point's (src/saca.rs:368-378 for L / origin, src/block/dc.rs:41-91 for the DC arrays
+ * and the coded stream; the reference treats every block as self-contained, src/block/dc.rs:30-37,53).  A block still unresolved after the
+ * pack's round limit (long repeats, e.g. two identical halves) is re-run alone through the single-block path (DK_ROUTE_PACKED_GUARD).
+ * DK_E_ARG: count == 0, count > DK_PACKED_MAX_BLOCKS, any n[i] == 0 or > DK_PACKED_MAX_BLOCK_BYTES, sum of n > dk_capacity, null pointers. */
+#define DK_PACKED_MAX_BLOCKS 65536
+#define DK_PACKED_MAX_BLOCK_BYTES (1u << 24)
+/* L of block i at d_bwt_out[off_i, off_i + n[i]), origin[i] (host, count entries) as from dk_dev_bwt_forward */
+int dk_dev_bwt_forward_packed(dk_ctx *ctx, const uint8_t *d_in, size_t count, const size_t *n, uint8_t *d_bwt_out, uint32_t *origin);
+/* DC arrays of a packed L: block i's entries at [off_i, off_i + m[i]) of d_dist / d_sym / d_rank (device, sum of n entries each; d_rank may
+ * be NULL), init (host, count x 256: block i's table at init[256 i]) and m (host, count) as from dk_dev_dc_encode */
+int dk_dev_dc_encode_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, const size_t *n, uint32_t *init, uint32_t *d_dist, uint8_t *d_sym,
+                            uint8_t *d_rank, size_t *m);
+/* every block of the pack queued as its own coding job of an open batch (out[i] / out_len[i] as from dk_dev_block_encode); the pack's
+ * distance stream takes one staging slot, released when its last block is coded.  flags (may be NULL): flags[i] = what dk_last_block_flags
+ * gives after block i alone.  On return d_in may be reused. */
+int dk_batch_push_packed(dk_batch *batch, const uint8_t *d_in, size_t count, const size_t *n, uint8_t *const *out, const size_t *out_cap,
+                         size_t *out_len, unsigned *flags);
+/* dk_batch_begin + dk_batch_push_packed + dk_batch_finish */
+int dk_dev_packed_encode(dk_ctx *ctx, int model_id, const uint8_t *d_in, size_t count, const size_t *n, uint8_t *const *out, const size_t *out_cap,
+                         size_t *out_len, unsigned *flags, int host_threads);
 /* inverse of dk_dev_batch_encode: host threads decode the streams while the GPU inverts the BWTs that are ready */
 int dk_dev_batch_decode(dk_ctx *ctx, int model_id, size_t count, const uint8_t *const *in, const size_t *in_len, const size_t *n,
                         uint8_t *const *d_out, int host_threads);
@@ -219,6 +241,7 @@ typedef struct dk_stats {
 #define DK_ROUTE_LFIRST_FALLBACK 0x2000u  /* the L-first path gave up (giant groups / over-long common extensions): suffix-array path from the start */
 #define DK_ROUTE_PERIOD_ROUND 0x8000u    /* a period round ran: suffixes inside stretches of one short period (runs, (ab)^n, zero padding) placed by where the stretch ends */
 #define DK_ROUTE_PACKED_PAIRS 0x10000u   /* the initial sort moved packed pairs: key, carried code and position in one 64-bit word (at most 32 key bits, small alphabets) */
+#define DK_ROUTE_PACKED_GUARD 0x20000u   /* packed path: at least one block was still unresolved after the pack's round limit and went through the single-block path */
 /* enable (1) / disable (0) HIP-event bracketing of every kernel launch on the context's stream */
 int dk_set_profiling(dk_ctx *ctx, int enabled);
 int dk_stats_reset(dk_ctx *ctx);

@@ -64,6 +64,8 @@ SIGNATURES = {
     "dk_batch_push_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "dk_dev_packed_encode": (_i, [_vp, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i]),
     "dk_dev_batch_decode": (_i, [_vp, _i, _sz, _vp, _vp, _vp, _vp, _i]),
+    "dk_dev_bwt_inverse_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp]),
+    "dk_dev_packed_decode": (_i, [_vp, _i, _sz, _vp, _vp, _vp, _vp, _i]),
     "dk_multi_block_encode": (_i, [_vp, _i, _i, _sz, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz]),
     "dk_multi_block_decode": (_i, [_vp, _i, _i, _sz, _vp, _vp, _vp, _vp, _i, _vp, _sz]),
     "dk_model_encode": (_i, [_i, _vp, _vp, _sz, _vp, _sz, _szp]),

@@ -13,7 +13,9 @@ Extensions beyond the reference (whole file = one block, read into memory, one t
              reads such a file as its first block only.  Blocks are STREAMED: one block of input is in host memory at a time; each goes
              through dk_batch_push as soon as it is in HBM (file reading, upload, GPU stages and the host coding of earlier blocks overlap).
   --packed   with -b of at most 16 MiB on one GPU: consecutive blocks go to the GPU as packs of up to 64 MiB, each through ONE segmented
-             device pass (dk_batch_push_packed); every block is still coded on its own, and the archive is byte-identical.
+             device pass (dk_batch_push_packed); every block is still coded on its own, and the archive is byte-identical.  On decode
+             (one GPU, indexed archives): records of at most 16 MiB are decoded in packs of up to 64 MiB, one upload and one segmented
+             inverse BWT per pack (dk_dev_packed_decode); larger records take the batched path; the output is byte-identical.
   --gpus G   block b -> GPU b mod G, one worker process per GPU; the parent never touches a GPU and stitches the records in order.
   --force    encode blocks that contain byte 0xFF.  The reference's header cannot carry that symbol (src/block/dc.rs:57,60,73,127):
              it writes such an archive without complaint and can never decode it.  This front end refuses unless --force is given.
@@ -451,11 +453,61 @@ def _decode_records_batched(path, model, device, offsets, end, which, out_write,
                 raise werr[0]
 
 
-def decode_file(path, model, device=0, gpus=1, host_threads=0, devices=None):
+def _decode_records_packed(path, model, device, offsets, end, out_write, host_threads):
+    """--packed: runs of consecutive records of at most PACKED_MAX_BLOCK_BYTES go to the GPU as packs of up to PACK_BYTES through
+    dk_dev_packed_decode (one upload and one segmented inverse BWT per pack); larger records go through _decode_records_batched, in order"""
+    import torch
+    from .context import Context
+    torch.cuda.set_device(device)
+    bounds = offsets + [end]
+    with open(path, "rb") as f:
+        sizes = []
+        for k in range(len(offsets)):
+            f.seek(offsets[k])
+            sizes.append(struct.unpack("<I", f.read(4))[0])
+        # segments in record order: [kind, records, bytes], "pack" for small records (one pack each), "big" for a run of the others
+        segments = []
+        for k, n in enumerate(sizes):
+            kind = "pack" if n <= PACKED_MAX_BLOCK_BYTES else "big"
+            last = segments[-1] if segments else None
+            if last and last[0] == kind and (kind == "big" or last[2] + n <= PACK_BYTES):
+                last[1].append(k)
+                last[2] += n
+            else:
+                segments.append([kind, [k], n])
+        cap = max([nb for kind, _, nb in segments if kind == "pack"] or [0])
+        ctx = Context(cap, device) if cap else None
+        STATS["t_ready"] = time.perf_counter()
+        try:
+            for kind, ks, _ in segments:
+                if kind == "big":
+                    _decode_records_batched(path, model, device, offsets, end, ks, out_write, host_threads)
+                    continue
+                streams = []
+                for k in ks:
+                    f.seek(offsets[k] + 4)
+                    streams.append(np.fromfile(f, dtype=np.uint8, count=bounds[k + 1] - offsets[k] - 4))
+                ns = [sizes[k] for k in ks]
+                d_out = torch.empty(sum(ns), dtype=torch.uint8, device="cuda:%d" % device)
+                ctx.dev_packed_decode(model, streams, ns, d_out, host_threads)
+                data = d_out.cpu().numpy()
+                pos = 0
+                for k, n in zip(ks, ns):
+                    out_write(k, data[pos:pos + n].tobytes())
+                    pos += n
+                del d_out, data, streams
+        finally:
+            if ctx is not None:
+                ctx.close()
+
+
+def decode_file(path, model, device=0, gpus=1, host_threads=0, devices=None, packed=False):
     from .context import Context
     out_path = output_name(path, "orig")                    # main.rs:64-66
     if model in DUMP_MODELS:
         raise SystemExit("model %s is dump-only: there is nothing to decode (src/model/raw.rs:39-43 panics)" % model)
+    if packed and gpus > 1:
+        raise SystemExit("--packed: one GPU")
     footer = read_footer(path) if model not in RAW_CODING_MODELS else None  # bbb archives carry no index: records are walked
     threads = host_threads or max(1, _host_threads() // max(1, gpus) - 1)
     if footer is None:
@@ -488,7 +540,10 @@ def decode_file(path, model, device=0, gpus=1, host_threads=0, devices=None):
     offsets, end = footer
     if gpus <= 1:
         with open(out_path, "wb") as out:
-            _decode_records_batched(path, model, device, offsets, end, list(range(len(offsets))), lambda k, data: out.write(data), threads)
+            if packed:
+                _decode_records_packed(path, model, device, offsets, end, lambda k, data: out.write(data), threads)
+            else:
+                _decode_records_batched(path, model, device, offsets, end, list(range(len(offsets))), lambda k, data: out.write(data), threads)
         return out_path
     parts = ["%s.part%d" % (out_path, r) for r in range(gpus)]
     procs = []
@@ -535,7 +590,8 @@ def main(argv=None):
     ap.add_argument("--devices", default="", help="GPU ids of the workers, comma separated (default: device, device+1, ...)")
     ap.add_argument("--stats", action="store_true", help="print a JSON line with the wall time of the work and the peak RSS to stderr")
     ap.add_argument("--packed", action="store_true", help="with -b (at most 16 MiB, one GPU): consecutive blocks share one segmented GPU pass "
-                    "per 64 MiB pack; the archive is byte-identical to the one without")
+                    "per 64 MiB pack; the archive is byte-identical to the one without.  On decode (one GPU): records of at most 16 MiB are "
+                    "inverted in packs the same way; the output is byte-identical")
     ap.add_argument("--worker", default="", help=argparse.SUPPRESS)
     ap.add_argument("--part", default="", help=argparse.SUPPRESS)
     ap.add_argument("file")
@@ -545,7 +601,7 @@ def main(argv=None):
         return _worker_decode(args) if decode else _worker_encode(args)
     t0 = time.perf_counter()
     if decode:
-        out = decode_file(args.file, args.model, args.device, args.gpus, args.host_threads, args.devices)
+        out = decode_file(args.file, args.model, args.device, args.gpus, args.host_threads, args.devices, args.packed)
     else:
         out = encode_file(args.file, args.model, args.block_size, args.device, args.gpus, args.force, args.host_threads, args.devices,
                           args.packed)

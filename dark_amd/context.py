@@ -242,6 +242,25 @@ class Context:
                                                 int(host_threads)))
         return [o[:lens[i]] for i, o in enumerate(outs)], [int(flags[i]) for i in range(count)]
 
+    def dev_bwt_inverse_packed(self, d_bwt, sizes, origins, d_out):
+        """inverse of dev_bwt_forward_packed: block i's text into d_out (same layout as d_bwt) from its L and origins[i]"""
+        _inputs_ready(d_bwt)
+        count = len(sizes)
+        if len(origins) != count:
+            raise DarkError(_lib.DK_E_ARG, "%d origins for %d blocks" % (len(origins), count))
+        ns = (C.c_size_t * count)(*[int(n) for n in sizes])
+        org = np.array(origins, dtype=np.int64).astype(np.uint32) if count else np.zeros(1, np.uint32)
+        self._ck(self._lib.dk_dev_bwt_inverse_packed(self._h, _ptr(d_bwt), count, ns, _ptr(org), _ptr(d_out)))
+
+    def dev_packed_decode(self, model, streams, sizes, d_out, host_threads=8):
+        """inverse of dev_packed_encode: every stream decoded, the blocks back to back into the device tensor d_out"""
+        count = len(streams)
+        keep = [as_u8(x) for x in streams]
+        ins = (C.c_void_p * max(count, 1))(*[_ptr(x) for x in keep])
+        lens = (C.c_size_t * max(count, 1))(*[len(x) for x in keep])
+        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
+        self._ck(self._lib.dk_dev_packed_decode(self._h, model_id(model), count, ins, lens, ns, _ptr(d_out), int(host_threads)))
+
     def dev_block_encode(self, model, d_in, n, out=None):
         """out: optional preallocated host uint8 array; returns a view of the coded stream"""
         _inputs_ready(d_in)

@@ -60,6 +60,8 @@ size_t workspace_bytes(size_t max_n) {
     //     (its arena of deep members, the depth tables and the next-break positions live in buffers of the 62.1 n that the path does not use otherwise)
     // = 69.4 n + 23 MiB; every allocation is rounded up to 256 bytes (about forty of them: < 16 KiB).  The DC arrays (10 n) and the inverse
     // BWT's successor table (8 n) are allocated after the sort's temporaries are released and take their place.
+    // The packed inverse (dk_dev_packed_decode: L n, successor table 8 n, walk records at most 8 n, splitter arrays at most 32 n, per-block words
+    // 16 count <= 16 n) stays below 65 n; its table of every block's symbol bases (count x 1 KiB, at most 64 MiB) fits the constant term.
     // tests/test_gpu_parity.py::test_workspace_accounting checks peak <= size on contexts sized exactly to their block, and
     // tests/test_gpu_fullsize.py checks the n-proportional term where the constant is negligible (peak - 64 MiB <= 69.4 n at 1e8 bytes).
     const size_t sort_temporaries = 62 * max_n + max_n / 8, io = 6 * max_n, on_top = max_n / 4 + max_n;
@@ -844,6 +846,70 @@ int dk_dev_batch_decode(dk_ctx *ctx, int model_id, size_t count, const uint8_t *
     ctx->stats.ms_total = t.ms();
     if (rc != DK_OK && ctx->err.empty()) return ctx->fail(rc, "stream of block %zu does not decode (%d)", bad_block, rc);
     return rc;
+}
+
+// ---- packed inverse (csrc/bwt.hip packed_ibwt_device) ------------------------------------------------------------
+int dk_dev_bwt_inverse_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const uint32_t *origin, uint8_t *d_out) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!d_bwt || !n || !origin || !d_out) return ctx->fail(DK_E_ARG, "null pointer");
+    std::vector<uint32_t> off;
+    DK_TRY(check_pack(ctx, count, n, off));
+    for (size_t i = 0; i < count; ++i)
+        if (origin[i] >= n[i]) return ctx->fail(DK_E_ARG, "origin %u of block %zu is outside its %zu bytes", origin[i], i, n[i]);
+    Timer t;
+    DK_TRY(packed_ibwt_device(ctx, d_bwt, off, origin, d_out));
+    ctx->stats.ms_ibwt = ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+// Host threads decode every stream of the pack into ONE pinned slot (block i at off_i), then one upload and one packed inverse.
+int dk_dev_packed_decode(dk_ctx *ctx, int model_id, size_t count, const uint8_t *const *in, const size_t *in_len, const size_t *n,
+                         uint8_t *d_out, int host_threads) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!in || !in_len || !n || !d_out) return ctx->fail(DK_E_ARG, "null pointer");
+    if (model_id == DK_MODEL_RAWDC || model_max_block(model_id) == 0) return ctx->fail(DK_E_MODEL, "model %d cannot decode", model_id);
+    std::vector<uint32_t> off;
+    DK_TRY(check_pack(ctx, count, n, off));
+    for (size_t i = 0; i < count; ++i)
+        if (!in[i]) return ctx->fail(DK_E_ARG, "null stream for block %zu of the pack", i);
+    Timer t;
+    const size_t total = off.back();
+    DK_TRY(ctx->ensure_slot(0, total + 64));
+    uint8_t *h_bwt = reinterpret_cast<uint8_t *>(ctx->slots[0].h);
+    std::vector<uint32_t> origin(count);
+    std::vector<int> rcs(count, DK_OK);
+    std::atomic<size_t> next{0};
+    auto worker = [&] {
+        for (size_t i; (i = next.fetch_add(1, std::memory_order_relaxed)) < count;) {
+            int single = 0;
+            rcs[i] = decode_block_stream(model_id, in[i], in_len[i], n[i], h_bwt + off[i], &origin[i], &single);
+            // One-symbol block (its origin is not read: DESIGN.md quirks).  L = c^n is inverted with origin n - 1, which gives c^n back.
+            if (rcs[i] == DK_OK && single) origin[i] = static_cast<uint32_t>(n[i] - 1);
+        }
+    };
+    const size_t workers = static_cast<size_t>(std::max(1, std::min<int>(host_threads, static_cast<int>(count))));
+    std::vector<std::thread> pool;
+    for (size_t w = 0; w < workers; ++w) pool.emplace_back(worker);
+    for (auto &th : pool) th.join();
+    ctx->stats.ms_entropy = t.ms();
+    for (size_t i = 0; i < count; ++i) {
+        if (rcs[i] != DK_OK)
+            return ctx->fail(DK_E_STREAM, "stream of block %zu of the pack does not decode (%d: corrupt, truncated, wrong model/size, or a block "
+                                          "containing byte 0xFF)", i, rcs[i]);
+        if (origin[i] >= n[i]) return ctx->fail(DK_E_STREAM, "decoded origin %u is outside block %zu of the pack", origin[i], i);
+    }
+    Timer t2;
+    uint8_t *d_bwt = ctx->ws_alloc<uint8_t>(total);
+    if (!d_bwt) return DK_E_NOMEM;
+    DK_HIP(ctx, hipMemcpyAsync(d_bwt, h_bwt, total, hipMemcpyHostToDevice, ctx->stream));
+    ctx->stats.ms_h2d = t2.ms();
+    Timer t3;
+    DK_TRY(packed_ibwt_device(ctx, d_bwt, off, origin.data(), d_out));
+    ctx->stats.ms_ibwt = t3.ms();
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
 }
 
 // ---- host-pointer entry points: stage in, run the device path, stage out ---------------------------------------------

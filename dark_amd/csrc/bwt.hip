@@ -12,6 +12,9 @@
 //                        walks psi to the next splitter and records (next splitter, steps)
 //   k_ibwt_rank          pointer jumping over the reduced list -> text offset of every splitter
 //   k_ibwt_emit          one lane per splitter re-walks its sub-list and writes the text bytes
+// Packed inverse (k_pib_*): the same stages over many blocks laid back to back, segmented by the offsets table.
+#include <algorithm>
+
 #include "context.hpp"
 #include "device_util.hpp"
 
@@ -340,6 +343,263 @@ __global__ __launch_bounds__(256) void k_ibwt_copy(const uint64_t *__restrict__ 
     for (uint32_t jj = 0; jj < have; ++jj) out[k - have + jj] = static_cast<uint8_t>(acc >> (8 * jj));
 }
 
+// ---- packed inverse ------------------------------------------------------------------------------------------
+// Block i of a pack is [off_i, e_i), e_i = off_{i+1}, with origin o_i (local).  Positions, psi entries and splitter ids are pack-global.
+// G(p, c) = class_start[c] + occurrences of c in the pack before p: what k_ibwt_hist and the three scans give over the whole pack.  Block i's
+// LF is base_i[c] + G(p, c) with base_i[c] = off_i + (symbols below c in block i) - G(off_i, c): the pack-wide class start cancels, so the
+// single-block histogram and scans serve the pack unchanged and the only per-block table is base (count x 256).
+// Splitters of block i are [sb_i, sb_{i+1}): local positions j S for j < nreg_i = ceil(n_i / S), then o_i when it is no multiple of S.
+
+// largest i in [lo, hi) with off[i] <= p (off[lo] <= p < off[hi])
+__device__ __forceinline__ uint32_t pib_seg(const uint32_t *__restrict__ off, uint32_t lo, uint32_t hi, uint32_t p) {
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (off[mid] <= p) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+struct PibBlock { uint32_t blk, first, s0, n, org, nreg; };  // block of a splitter: its index, first splitter, first position, size, origin
+
+__device__ __forceinline__ PibBlock pib_block(const uint32_t *__restrict__ off, const uint32_t *__restrict__ org, const uint32_t *__restrict__ sb,
+                                              uint32_t count, uint32_t S, uint32_t s) {
+    PibBlock b;
+    b.blk = pib_seg(sb, 0, count, s);
+    b.first = sb[b.blk];
+    b.s0 = off[b.blk];
+    b.n = off[b.blk + 1] - b.s0;
+    b.org = org[b.blk];
+    b.nreg = (b.n + S - 1) / S;
+    return b;
+}
+__device__ __forceinline__ uint32_t pib_start(const PibBlock &b, uint32_t S, uint32_t s) {
+    const uint32_t j = s - b.first;
+    return b.s0 + (j == b.nreg ? b.org : j * S);
+}
+// splitter id of position p of block b, IB_END when p is none
+__device__ __forceinline__ uint32_t pib_splitter_at(const PibBlock &b, uint32_t S, uint32_t p) {
+    const uint32_t l = p - b.s0;
+    if (l % S == 0) return b.first + l / S;
+    return l == b.org ? b.first + b.nreg : IB_END;
+}
+
+// G(p, c) for c = threadIdx.x: the scanned offsets of p's tile plus an LDS histogram of the tile's bytes before p (p = total: the last tile)
+__device__ __forceinline__ uint32_t pib_occ_before(const uint8_t *__restrict__ bwt, uint32_t p, uint32_t ntiles, const uint32_t *__restrict__ tile_offs,
+                                                   uint32_t *h) {
+    const uint32_t t = min(p / IB_TILE, ntiles - 1);
+    h[threadIdx.x] = 0;
+    __syncthreads();
+    for (uint32_t q = t * IB_TILE + threadIdx.x; q < p; q += IB_BLOCK) atomicAdd(&h[bwt[q]], 1u);
+    __syncthreads();
+    const uint32_t g = tile_offs[static_cast<size_t>(t) * 256 + threadIdx.x] + h[threadIdx.x];
+    __syncthreads();
+    return g;
+}
+
+// one workgroup per block, one lane per symbol: base_i[c], and cls0_i = where block i's origin element goes (first of its class)
+__global__ __launch_bounds__(256) void k_pib_heads(const uint8_t *__restrict__ bwt, const uint32_t *__restrict__ off, const uint32_t *__restrict__ org,
+                                                    uint32_t ntiles, const uint32_t *__restrict__ tile_offs, uint32_t *__restrict__ base,
+                                                    uint32_t *__restrict__ cls0) {
+    __shared__ uint32_t h[256];
+    __shared__ uint32_t s_tmp[IB_WAVES + 1];
+    const uint32_t i = blockIdx.x, c = threadIdx.x;
+    const uint32_t s = off[i], e = off[i + 1];
+    const uint32_t g0 = pib_occ_before(bwt, s, ntiles, tile_offs, h);
+    const uint32_t g1 = pib_occ_before(bwt, e, ntiles, tile_offs, h);
+    const uint32_t below = block_excl_sum<IB_WAVES>(g1 - g0, s_tmp, nullptr);
+    base[static_cast<size_t>(i) * 256 + c] = s + below - g0;  // (mod 2^32: only base + G is ever used)
+    if (c == bwt[s + org[i]]) cls0[i] = s + below;
+}
+
+// k_ibwt_lf over the pack: the rank of every position among its symbol is the same tile/wave computation; the block of a position comes
+// from a binary search over the few blocks that meet this tile
+__global__ __launch_bounds__(IB_BLOCK) void k_pib_lf(const uint8_t *__restrict__ bwt, uint32_t total, const uint32_t *__restrict__ off, uint32_t count,
+                                                      const uint32_t *__restrict__ org, const uint32_t *__restrict__ tile_offs,
+                                                      const uint32_t *__restrict__ base, const uint32_t *__restrict__ cls0, uint64_t *__restrict__ psi) {
+    __shared__ uint32_t s_cnt[IB_WAVES][256];
+    __shared__ uint32_t s_blk[2];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t tile_base = blockIdx.x * IB_TILE;
+    for (int i = tid; i < IB_WAVES * 256; i += IB_BLOCK) (&s_cnt[0][0])[i] = 0;
+    if (tid == 0) {
+        const uint32_t lo = pib_seg(off, 0, count, tile_base);
+        s_blk[0] = lo;
+        s_blk[1] = pib_seg(off, lo, count, min(tile_base + IB_TILE, total) - 1) + 1;
+    }
+    const uint32_t wbase = static_cast<uint32_t>(wave) * (64 * IB_SPT);
+    uint32_t sym[IB_SPT], rnk[IB_SPT];
+#pragma unroll
+    for (int k = 0; k < IB_SPT; ++k) {
+        const uint32_t i = tile_base + wbase + k * 64 + lane;
+        sym[k] = i < total ? bwt[i] : 0x100u;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < IB_SPT; ++k) {
+        const uint32_t d = sym[k] & 0xFFu;
+        const bool pad = sym[k] > 0xFFu;
+        const LaneSet same = wave_match<8>(d, __ballot(!pad));
+        const uint32_t before = same.before();
+        const uint32_t old = pad ? 0u : s_cnt[wave][d];
+        __builtin_amdgcn_wave_barrier();
+        if (!pad && before == 0) s_cnt[wave][d] = old + same.count();
+        __builtin_amdgcn_wave_barrier();
+        rnk[k] = old + before;
+    }
+    __syncthreads();
+    {
+        const int d = tid;
+        uint32_t run = tile_offs[static_cast<size_t>(blockIdx.x) * 256 + d];
+#pragma unroll
+        for (int w = 0; w < IB_WAVES; ++w) {
+            const uint32_t c = s_cnt[w][d];
+            s_cnt[w][d] = run;
+            run += c;
+        }
+    }
+    __syncthreads();
+    const uint32_t blo = s_blk[0], bhi = s_blk[1];
+#pragma unroll
+    for (int k = 0; k < IB_SPT; ++k) {
+        const uint32_t i = tile_base + wbase + k * 64 + lane;
+        if (i >= total) continue;
+        const uint32_t d = sym[k];
+        const uint32_t blk = pib_seg(off, blo, bhi, i);
+        const uint32_t o = off[blk] + org[blk];
+        uint32_t dest = base[static_cast<size_t>(blk) * 256 + d] + s_cnt[wave][d] + rnk[k];
+        if (i == o) dest = cls0[blk];
+        else if (i < o && d == bwt[o]) dest += 1;
+        psi[dest] = (static_cast<uint64_t>(d) << 32) | (i == o ? IB_END : i);
+    }
+}
+
+// k_ibwt_walk per splitter of the pack; the walk stops at its block's splitters and END, and never runs past n_i steps
+__global__ __launch_bounds__(256) void k_pib_walk(const uint64_t *__restrict__ psi, const uint32_t *__restrict__ off, const uint32_t *__restrict__ org,
+                                                   const uint32_t *__restrict__ sb, uint32_t count, uint32_t S, uint32_t nsplit,
+                                                   uint32_t *__restrict__ nxt, uint32_t *__restrict__ len, uint32_t *__restrict__ len_keep,
+                                                   uint8_t *__restrict__ rec, uint32_t *__restrict__ resume) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= nsplit) return;
+    const PibBlock b = pib_block(off, org, sb, count, S, s);
+    uint32_t cur = pib_start(b, S, s);
+    uint32_t steps = 0, to = IB_END;
+    uint64_t acc = 0;
+    uint64_t *out = rec ? reinterpret_cast<uint64_t *>(rec + static_cast<size_t>(s) * IB_REC) : nullptr;
+    for (;;) {
+        const uint64_t e = psi[cur];
+        const uint32_t p = static_cast<uint32_t>(e);
+        if (rec && steps < IB_REC) {
+            acc |= (e >> 32 & 0xFFull) << (8 * (steps & 7u));
+            if ((steps & 7u) == 7u) { out[steps >> 3] = acc; acc = 0; }
+        }
+        ++steps;
+        if (p == IB_END) break;
+        if (p - b.s0 >= b.n) { steps = b.n + 1; break; }  // (LF maps a block onto itself: never taken; keeps every read inside the block)
+        const uint32_t id = pib_splitter_at(b, S, p);
+        if (id != IB_END) { to = id; break; }
+        cur = p;
+        if (rec && steps == IB_REC) resume[s] = cur;
+        if (steps > b.n) break;  // corrupt input: never spin
+    }
+    if (rec && steps < IB_REC && (steps & 7u)) out[steps >> 3] = acc;
+    nxt[s] = to;
+    len[s] = steps;
+    if (len_keep) len_keep[s] = steps;
+}
+
+// after the jumps, before anything is written: every splitter resolved, within its block, and the origin's chain covers the whole block
+// (a shorter one means a second cycle).  bad = the lowest failing block
+__global__ __launch_bounds__(256) void k_pib_check(const uint32_t *__restrict__ off, const uint32_t *__restrict__ org, const uint32_t *__restrict__ sb,
+                                                    uint32_t count, uint32_t S, uint32_t nsplit, const uint32_t *__restrict__ nxt,
+                                                    const uint32_t *__restrict__ dist, const uint32_t *__restrict__ len_keep, uint32_t *__restrict__ bad) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= nsplit) return;
+    const PibBlock b = pib_block(off, org, sb, count, S, s);
+    const uint32_t j = s - b.first, d = dist[s];
+    const bool at_origin = j == b.nreg || (b.org % S == 0 && j == b.org / S);
+    if (nxt[s] != IB_END || d > b.n || (len_keep && len_keep[s] > d) || (at_origin && d != b.n)) atomicMin(bad, b.blk);
+}
+
+// byte writer of one lane: aligned 8-byte stores where all eight bytes are this lane's, single bytes at the ragged ends
+struct PibPut {
+    uint8_t *out;
+    uint32_t k;
+    bool wide;
+    uint64_t acc = 0;
+    uint32_t have = 0;
+    __device__ PibPut(uint8_t *o, uint32_t at) : out(o), k(at), wide((reinterpret_cast<uintptr_t>(o) & 7) == 0) {}
+    __device__ __forceinline__ void put(uint8_t v) {
+        if (wide && (have > 0 || (k & 7u) == 0)) {
+            acc |= static_cast<uint64_t>(v) << (8 * have);
+            ++have;
+            ++k;
+            if (have == 8) {
+                *reinterpret_cast<uint64_t *>(out + k - 8) = acc;
+                acc = 0;
+                have = 0;
+            }
+        } else {
+            out[k++] = v;
+        }
+    }
+    __device__ __forceinline__ void flush() {
+        for (uint32_t jj = 0; jj < have; ++jj) out[k - have + jj] = static_cast<uint8_t>(acc >> (8 * jj));
+    }
+};
+
+__global__ __launch_bounds__(256) void k_pib_emit(const uint64_t *__restrict__ psi, const uint32_t *__restrict__ off, const uint32_t *__restrict__ org,
+                                                   const uint32_t *__restrict__ sb, uint32_t count, uint32_t S, uint32_t nsplit,
+                                                   const uint32_t *__restrict__ dist_to_end, uint8_t *__restrict__ out, uint32_t *__restrict__ bad) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= nsplit) return;
+    const PibBlock b = pib_block(off, org, sb, count, S, s);
+    const uint32_t d = dist_to_end[s], end = b.s0 + b.n;
+    if (d > b.n) { atomicMin(bad, b.blk); return; }
+    uint32_t cur = pib_start(b, S, s);
+    PibPut w(out, end - d);
+    for (;;) {
+        const uint64_t e = psi[cur];
+        const uint32_t p = static_cast<uint32_t>(e);
+        const uint8_t symbol = static_cast<uint8_t>(e >> 32);
+        if (p == IB_END) { if (w.k < end) w.put(symbol); else atomicMin(bad, b.blk); break; }
+        if (w.k >= end || p - b.s0 >= b.n) { atomicMin(bad, b.blk); break; }
+        w.put(symbol);
+        if (pib_splitter_at(b, S, p) != IB_END) break;
+        cur = p;
+    }
+    w.flush();
+}
+
+__global__ __launch_bounds__(256) void k_pib_copy(const uint64_t *__restrict__ psi, const uint32_t *__restrict__ off, const uint32_t *__restrict__ org,
+                                                   const uint32_t *__restrict__ sb, uint32_t count, uint32_t S, uint32_t nsplit,
+                                                   const uint32_t *__restrict__ dist_to_end, const uint32_t *__restrict__ len,
+                                                   const uint8_t *__restrict__ rec, const uint32_t *__restrict__ resume, uint8_t *__restrict__ out,
+                                                   uint32_t *__restrict__ bad) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= nsplit) return;
+    const PibBlock b = pib_block(off, org, sb, count, S, s);
+    const uint32_t d = dist_to_end[s], total = len[s];
+    if (d > b.n || total > d) { atomicMin(bad, b.blk); return; }
+    PibPut w(out, b.s0 + b.n - d);
+    const uint64_t *src = reinterpret_cast<const uint64_t *>(rec + static_cast<size_t>(s) * IB_REC);
+    const uint32_t recorded = total < IB_REC ? total : IB_REC;
+    for (uint32_t j = 0; j < recorded; j += 8) {
+        const uint64_t v = src[j >> 3];
+        const uint32_t cnt = recorded - j < 8 ? recorded - j : 8;
+        for (uint32_t q = 0; q < cnt; ++q) w.put(static_cast<uint8_t>(v >> (8 * q)));
+    }
+    if (total > IB_REC) {
+        uint32_t cur = resume[s], left = total - IB_REC;
+        while (left--) {
+            const uint64_t e = psi[cur];
+            w.put(static_cast<uint8_t>(e >> 32));
+            cur = static_cast<uint32_t>(e);
+            if ((cur == IB_END || cur - b.s0 >= b.n) && left) { atomicMin(bad, b.blk); break; }
+        }
+    }
+    w.flush();
+}
+
 }  // namespace
 
 int bwt_gather_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_sa, size_t n, uint8_t *d_bwt, uint32_t *origin) {
@@ -457,6 +717,105 @@ int bwt_inverse_device(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t ori
     DK_HIP(ctx, hipStreamSynchronize(st));
     ctx->ws_release(mark);
     if (ctx->h_mail[11]) return ctx->fail(DK_E_STREAM, "bwt_inverse: BWT/origin do not describe a single text cycle");
+    return DK_OK;
+}
+
+int packed_ibwt_device(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector<uint32_t> &off, const uint32_t *origin, uint8_t *d_out) {
+    hipStream_t st = ctx->stream;
+    const size_t count = off.size() - 1, total = off.back();
+    const uint32_t cnt = static_cast<uint32_t>(count), T = static_cast<uint32_t>(total);
+    const size_t mark = ctx->ws_mark();
+    // S = 64 as for large single blocks: a pack is one large walk problem whatever its block size
+    constexpr uint32_t S = 64;
+    // one upload: off (count + 1) | origin (count) | first splitter of every block (count + 1, the last = all splitters)
+    std::vector<uint32_t> aux(3 * count + 2);
+    std::copy(off.begin(), off.end(), aux.begin());
+    uint32_t *h_org = aux.data() + count + 1, *h_sb = h_org + count;
+    uint32_t nsplit = 0, max_split = 1;
+    for (size_t i = 0; i < count; ++i) {
+        h_org[i] = origin[i];
+        h_sb[i] = nsplit;
+        const uint32_t k = static_cast<uint32_t>(div_up(off[i + 1] - off[i], S)) + (origin[i] % S ? 1u : 0u);
+        max_split = std::max(max_split, k);
+        nsplit += k;
+    }
+    h_sb[count] = nsplit;
+    const size_t ntiles = div_up(total, IB_TILE);
+    const size_t tpc = div_up(ntiles, IB_MAX_CHUNKS);
+    const size_t nchunks = div_up(ntiles, tpc);
+    // records of the walk (IB_REC bytes per splitter) where the splitters are sparse enough that they cost at most 8 bytes per position: packs of
+    // blocks that average 2 KiB or more.  Packs of tiny blocks have walks of a few steps and take k_pib_emit.
+    const bool record = DK_KNOB("DK_IBWT_RECORD", 1) != 0 && static_cast<size_t>(nsplit) * 32 <= total;
+    uint32_t *d_aux = ctx->ws_alloc<uint32_t>(aux.size());
+    uint32_t *tile_hist = ctx->ws_alloc<uint32_t>(ntiles * 256);
+    uint32_t *chunk_sum = ctx->ws_alloc<uint32_t>(nchunks * 256);
+    uint32_t *class_start = ctx->ws_alloc<uint32_t>(256);
+    uint32_t *base = ctx->ws_alloc<uint32_t>(count * 256);
+    uint32_t *cls0 = ctx->ws_alloc<uint32_t>(count);
+    uint64_t *psi = ctx->ws_alloc<uint64_t>(total);
+    uint32_t *nxt = ctx->ws_alloc<uint32_t>(nsplit), *nxt_alt = ctx->ws_alloc<uint32_t>(nsplit);
+    uint32_t *acc = ctx->ws_alloc<uint32_t>(nsplit), *acc_alt = ctx->ws_alloc<uint32_t>(nsplit);
+    if (!d_aux || !tile_hist || !chunk_sum || !class_start || !base || !cls0 || !psi || !nxt || !nxt_alt || !acc || !acc_alt) return DK_E_NOMEM;
+    uint32_t *len_keep = record ? ctx->ws_alloc<uint32_t>(nsplit) : nullptr;
+    uint32_t *resume = record ? ctx->ws_alloc<uint32_t>(nsplit) : nullptr;
+    uint8_t *rec = record ? ctx->ws_alloc<uint8_t>(static_cast<size_t>(nsplit) * IB_REC) : nullptr;
+    if (record && (!len_keep || !resume || !rec)) return DK_E_NOMEM;
+    const uint32_t *d_off = d_aux, *d_org = d_aux + count + 1, *d_sb = d_org + count;
+    DK_HIP(ctx, hipMemcpyAsync(d_aux, aux.data(), aux.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    {
+        LaunchScope ls(ctx, K_IBWT_HIST, 1.0 * total + 2048.0 * count);
+        k_ibwt_hist<<<dim3(ntiles), dim3(IB_BLOCK), 0, st>>>(d_bwt, total, tile_hist);
+        k_ibwt_scan_a<<<dim3(nchunks), dim3(256), 0, st>>>(tile_hist, ntiles, tpc, chunk_sum);
+        k_ibwt_scan_b<<<dim3(1), dim3(256), 0, st>>>(chunk_sum, nchunks, class_start);
+        k_ibwt_scan_c<<<dim3(nchunks), dim3(256), 0, st>>>(tile_hist, ntiles, tpc, chunk_sum);
+        k_pib_heads<<<dim3(cnt), dim3(256), 0, st>>>(d_bwt, d_off, d_org, static_cast<uint32_t>(ntiles), tile_hist, base, cls0);
+    }
+    {
+        LaunchScope ls(ctx, K_IBWT_LF, 5.0 * total);
+        k_pib_lf<<<dim3(ntiles), dim3(IB_BLOCK), 0, st>>>(d_bwt, T, d_off, cnt, d_org, tile_hist, base, cls0, psi);
+    }
+    DK_HIP(ctx, hipGetLastError());
+    const unsigned sgrid = static_cast<unsigned>(div_up(nsplit, 256));
+    {
+        LaunchScope ls(ctx, K_IBWT_WALK, (record ? 5.0 : 4.0) * total);
+        k_pib_walk<<<dim3(sgrid), dim3(256), 0, st>>>(psi, d_off, d_org, d_sb, cnt, S, nsplit, nxt, acc, len_keep, rec, resume);
+    }
+    DK_HIP(ctx, hipGetLastError());
+    // every chain lies inside one block: the longest block's splitter count decides the number of jumps
+    uint32_t *d_pending = ctx->d_mail + 49, *d_bad = ctx->d_mail + 48;
+    const int steps = static_cast<int>(ceil_log2_u64(max_split)) + 1;
+    for (int it = 0; it < steps; ++it) {
+        {
+            LaunchScope ls(ctx, K_IBWT_JUMP, 24.0 * nsplit);
+            k_ibwt_jump<<<dim3(sgrid), dim3(256), 0, st>>>(nxt, acc, nxt_alt, acc_alt, nsplit, d_pending);
+        }
+        std::swap(nxt, nxt_alt);
+        std::swap(acc, acc_alt);
+    }
+    DK_HIP(ctx, hipMemsetAsync(d_bad, 0xFF, sizeof(uint32_t), st));
+    {
+        LaunchScope ls(ctx, K_IBWT_JUMP, 12.0 * nsplit);
+        k_pib_check<<<dim3(sgrid), dim3(256), 0, st>>>(d_off, d_org, d_sb, cnt, S, nsplit, nxt, acc, len_keep, d_bad);
+    }
+    DK_HIP(ctx, hipGetLastError());
+    DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 48, d_bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    DK_HIP(ctx, hipStreamSynchronize(st));
+    // nothing has been written to d_out yet: a corrupt block fails the whole call and leaves the output as it was
+    if (ctx->h_mail[48] != IB_END)
+        return ctx->fail(DK_E_STREAM, "bwt_inverse_packed: block %u of the pack: BWT/origin do not describe a single text cycle", ctx->h_mail[48]);
+    {
+        LaunchScope ls(ctx, K_IBWT_EMIT, (record ? 2.0 : 6.0) * total);
+        if (record)
+            k_pib_copy<<<dim3(sgrid), dim3(256), 0, st>>>(psi, d_off, d_org, d_sb, cnt, S, nsplit, acc, len_keep, rec, resume, d_out, d_bad);
+        else
+            k_pib_emit<<<dim3(sgrid), dim3(256), 0, st>>>(psi, d_off, d_org, d_sb, cnt, S, nsplit, acc, d_out, d_bad);
+    }
+    DK_HIP(ctx, hipGetLastError());
+    DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 48, d_bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    DK_HIP(ctx, hipStreamSynchronize(st));
+    ctx->ws_release(mark);
+    if (ctx->h_mail[48] != IB_END)
+        return ctx->fail(DK_E_STREAM, "bwt_inverse_packed: block %u of the pack: BWT/origin do not describe a single text cycle", ctx->h_mail[48]);
     return DK_OK;
 }
 

@@ -195,6 +195,9 @@ int bwt_forward_device(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d
 // bwt.hip
 int bwt_gather_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_sa, size_t n, uint8_t *d_bwt, uint32_t *origin);
 int bwt_inverse_device(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t origin, uint8_t *d_out);
+// packed inverse: block i's text at d_out[off[i], off[i+1]) from its L at d_bwt[off[i], ...) and origin[i] (host, < n_i, checked by the caller);
+// off on the host, off[count] = total.  DK_E_STREAM naming the lowest corrupt block, and then nothing is written to d_out.
+int packed_ibwt_device(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector<uint32_t> &off, const uint32_t *origin, uint8_t *d_out);
 // dc.hip: d_run_end may be null
 int dc_encode_device(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t init_host[256], uint32_t *d_dist, uint8_t *d_sym,
                      uint8_t *d_rank, uint32_t *d_run_end, size_t *m);

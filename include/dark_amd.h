@@ -156,6 +156,16 @@ int dk_batch_push_packed(dk_batch *batch, const uint8_t *d_in, size_t count, con
 /* dk_batch_begin + dk_batch_push_packed + dk_batch_finish */
 int dk_dev_packed_encode(dk_ctx *ctx, int model_id, const uint8_t *d_in, size_t count, const size_t *n, uint8_t *const *out, const size_t *out_cap,
                          size_t *out_len, unsigned *flags, int host_threads);
+/* Packed inverse, the same layout and limits: ONE segmented inverse BWT for every block of the pack (launches follow the largest block, not
+ * count).  Inverse of dk_dev_bwt_forward_packed: block i's text at d_out[off_i, off_i + n[i]) from L at d_bwt[off_i, ...) and origin[i] (host).
+ * DK_E_ARG also for origin[i] >= n[i].  DK_E_STREAM when a block's (L, origin) is not a single text cycle: dk_last_error names the block,
+ * nothing is written to d_out, and the context stays usable. */
+int dk_dev_bwt_inverse_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const uint32_t *origin, uint8_t *d_out);
+/* Inverse of dk_dev_packed_encode: up to host_threads host threads decode the streams into one pinned pack-sized slot, then ONE upload and ONE
+ * packed inverse; d_out holds the blocks back to back.  DK_E_MODEL for rawdc and unknown models; DK_E_STREAM naming the block for a stream that
+ * does not decode or a decoded origin outside its block.  One-symbol blocks are returned whole, as by dk_dev_batch_decode. */
+int dk_dev_packed_decode(dk_ctx *ctx, int model_id, size_t count, const uint8_t *const *in, const size_t *in_len, const size_t *n,
+                         uint8_t *d_out, int host_threads);
 /* inverse of dk_dev_batch_encode: host threads decode the streams while the GPU inverts the BWTs that are ready */
 int dk_dev_batch_decode(dk_ctx *ctx, int model_id, size_t count, const uint8_t *const *in, const size_t *in_len, const size_t *n,
                         uint8_t *const *d_out, int host_threads);

@@ -533,7 +533,9 @@ int packed_forward(dk_ctx *ctx, const uint8_t *d_in, const std::vector<uint32_t>
     uint32_t *d_guard = ctx->ws_alloc<uint32_t>(count);
     if (!d_guard) return DK_E_NOMEM;
     size_t unresolved = 0;
-    DK_TRY(packed_bwt_device(ctx, d_in, d_off, count, total, d_bwt, d_origin, d_guard, PACKED_MAX_ROUNDS, &unresolved));
+    // (tuning build: DK_PACKED_ROUNDS lowers the limit, clamped to [0, PACKED_MAX_ROUNDS] -- a test hook that sends blocks through the guard)
+    const int max_rounds = std::max(0, std::min(PACKED_MAX_ROUNDS, DK_KNOB("DK_PACKED_ROUNDS", PACKED_MAX_ROUNDS)));
+    DK_TRY(packed_bwt_device(ctx, d_in, d_off, count, total, d_bwt, d_origin, d_guard, max_rounds, &unresolved));
     fixed->clear();
     if (unresolved) {
         std::vector<uint32_t> guard(count);

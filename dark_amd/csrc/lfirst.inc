@@ -593,6 +593,7 @@ __global__ __launch_bounds__(LF_BLOCK) void k_lf_finish(uint32_t *__restrict__ a
             if (s < LF_TILE && static_cast<uint32_t>(a) == gs) {
                 const uint32_t at = atomicAdd(deep_count, 1u);
                 if (at < deep_cap) deep[at] = LfDeepGroup{gs, size, h, LD_LIST};
+                else *fallback = 1u;
             }
             continue;
         }
@@ -1558,6 +1559,8 @@ constexpr int LF_TAIL_SLOTS = 0;         // a big list this short (slots) would 
                                          // the bigger ones.  Off: measured on 50 MB of real text with 512 K slots, seven rounds instead of fourteen and the same 10.5 ms -- k_lf_medium runs
                                          // sixteen steps of 26 us for its slowest group where a round of a short list costs 150-350 us for everybody (profiles/NOTES.md)
 constexpr uint32_t LF_AVG_BIG = 1u << 18;  // big groups of more than this many members on average: periodic / run-dominated input, not text
+// A limit as the kernels and the host compare against it: the tuning build may lower it (test hooks, DK_KNOB), clamped to [0, hi]
+inline uint32_t lf_limit(int knob, uint32_t hi) { return knob <= 0 ? 0u : std::min(static_cast<uint32_t>(knob), hi); }
 
 // -> *done: L and the origin are complete; otherwise the caller takes the suffix-array path from the start (nothing it needs was touched
 // but scratch buffers; L and the origin word are rewritten by it)
@@ -1570,6 +1573,15 @@ int lfirst_path(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uint64_t *in
     *done = false;
     *pristine = true;  // nothing the suffix-array path reads (sorted keys, SA, L, origin) has been written yet
     hipStream_t st = ctx->stream;
+    // The limits past which the path gives up.  Tuning build (test hooks, tests/test_gpu_fallbacks.py): DK_LF_DEEP_CAP, DK_LF_ARENA, DK_LF_GIANT_CAP,
+    // DK_LF_GIANT_ARENA, DK_LF_GIANT_ROUNDS and DK_LF_ROUNDS lower them.  They lower only what the kernels and the host compare against: every buffer
+    // keeps its full size, so a site that forgets its check still writes inside its buffer (and the parity tests see the wrong L).
+    const uint32_t deep_cap = lf_limit(DK_KNOB("DK_LF_DEEP_CAP", static_cast<int>(LF_DEEP_CAP)), LF_DEEP_CAP);
+    const uint32_t arena_cap = lf_limit(DK_KNOB("DK_LF_ARENA", 0x7FFFFFFF), static_cast<uint32_t>(n));  // (every suffix leaves its list at most once)
+    const uint32_t giant_cap = lf_limit(DK_KNOB("DK_LF_GIANT_CAP", static_cast<int>(LF_GIANT_CAP)), LF_GIANT_CAP);
+    const uint32_t giant_arena = lf_limit(DK_KNOB("DK_LF_GIANT_ARENA", static_cast<int>(LF_GIANT_ARENA)), LF_GIANT_ARENA);
+    const int giant_rounds = static_cast<int>(lf_limit(DK_KNOB("DK_LF_GIANT_ROUNDS", LF_GIANT_ROUNDS), LF_GIANT_ROUNDS));
+    const int max_rounds = static_cast<int>(lf_limit(DK_KNOB("DK_LF_ROUNDS", LF_MAX_ROUNDS), LF_MAX_ROUNDS));
     const size_t mark = ctx->ws_mark();
     LfDeepGroup *deep = ctx->ws_alloc<LfDeepGroup>(LF_DEEP_CAP);
     if (!deep) return DK_E_NOMEM;
@@ -1583,7 +1595,7 @@ int lfirst_path(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uint64_t *in
     uint32_t *d_giant_count = ctx->d_mail + 983 /* [2] */, *d_giant_used = ctx->d_mail + 986 /* [2] */;
     uint32_t *d_arena_used = ctx->d_mail + 988;
     DK_HIP(ctx, hipMemsetAsync(d_deep_count, 0, 9 * sizeof(uint32_t), st));
-    const LfArena arena{b.a_idx, b.a_pos, b.a_sym, d_arena_used, static_cast<uint32_t>(n)};
+    const LfArena arena{b.a_idx, b.a_pos, b.a_sym, d_arena_used, arena_cap};
     // steps a group may take inside k_lf_finish, and steps without a split after which it leaves early (tuning build: DK_LF_STEPS, DK_LF_STUCK)
     const int max_steps = std::max(1, std::min(4096, DK_KNOB("DK_LF_STEPS", LF_STEPS))), stuck_steps = std::max(1, DK_KNOB("DK_LF_STUCK", LF_STUCK));
     // (short lists: LF_SHORT_STEPS steps for lists of at most LF_SHORT_SLOTS slots; tuning build: DK_LF_SHORT_STEPS, DK_LF_SHORT_SLOTS, 0 slots = the same everywhere)
@@ -1593,12 +1605,12 @@ int lfirst_path(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uint64_t *in
     for (int q = 0; q < 2; ++q) {
         giant[q].list = ctx->ws_alloc<LfDeepGroup>(LF_GIANT_CAP);
         giant[q].count = d_giant_count + q;
-        giant[q].cap = LF_GIANT_CAP;
+        giant[q].cap = giant_cap;
         giant[q].idx = ctx->ws_alloc<uint32_t>(LF_GIANT_ARENA);
         giant[q].pos = ctx->ws_alloc<uint32_t>(LF_GIANT_ARENA);
         giant[q].sym = ctx->ws_alloc<uint8_t>(LF_GIANT_ARENA);
         giant[q].used = d_giant_used + q;
-        giant[q].arena_cap = LF_GIANT_ARENA;
+        giant[q].arena_cap = giant_arena;
         if (!giant[q].list || !giant[q].idx || !giant[q].pos || !giant[q].sym) return DK_E_NOMEM;
     }
     uint32_t *lce_res = ctx->ws_alloc<uint32_t>(LF_GIANT_ARENA);  // per member of the listed subgroups
@@ -1667,7 +1679,13 @@ int lfirst_path(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uint64_t *in
         if (!(stalled_now || (tail_slots && nbig <= tail_slots)) || nbig == 0 || big_min == static_cast<uint32_t>(LF_DEEP_MAX)) return DK_OK;
         big_min = LF_DEEP_MAX;
         DK_TRY(classify(big_min));
-        if (trace) fprintf(stderr, "[dk] L-first: %s, groups up to %d members end inside LDS: big=%zu in %zu groups\n", stalled_now ? "stalled round" : "short big list", LF_DEEP_MAX, nbig, nbiggroups);
+        if (trace) {  // (the deep list's length: the next round lists the groups that left behind it -- tests/test_gpu_fallbacks.py caps the list there)
+            uint32_t listed = 0;
+            DK_HIP(ctx, hipMemcpyAsync(&listed, d_deep_count, sizeof listed, hipMemcpyDeviceToHost, st));
+            DK_HIP(ctx, hipStreamSynchronize(st));
+            fprintf(stderr, "[dk] L-first: %s, groups up to %d members end inside LDS: big=%zu in %zu groups, deep list at %u\n", stalled_now ? "stalled round" : "short big list",
+                    LF_DEEP_MAX, nbig, nbiggroups, listed);
+        }
         return DK_OK;
     };
     DK_TRY(let_medium_groups_go(false));
@@ -1679,14 +1697,14 @@ int lfirst_path(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uint64_t *in
         const uint32_t *end_ptr = last ? d_deep_count : nullptr;
         if (by_wave) {
             LaunchScope ls(ctx, K_CHAIN, 0.0, on);
-            k_lf_deep_wave<<<dim3(static_cast<unsigned>(std::min<size_t>(div_up(end - begin, 4), 4096))), dim3(256), 0, on>>>(arena.idx, arena.pos, arena.sym, deep, d_deep_count, begin, end, LF_DEEP_CAP,
+            k_lf_deep_wave<<<dim3(static_cast<unsigned>(std::min<size_t>(div_up(end - begin, 4), 4096))), dim3(256), 0, on>>>(arena.idx, arena.pos, arena.sym, deep, d_deep_count, begin, end, deep_cap,
                                                                                                                            d_text, static_cast<uint32_t>(n), d_bwt, d_origin, d_fallback);
         }
         {
             LaunchScope ls(ctx, K_CHAIN, 0.0, on);
-            k_lf_deep_block<LS_MAX, 256><<<dim3(1024), dim3(256), 0, on>>>(arena.idx, arena.pos, arena.sym, deep, end_ptr, begin, end, LF_DEEP_CAP, d_text, static_cast<uint32_t>(n), d_bwt,
+            k_lf_deep_block<LS_MAX, 256><<<dim3(1024), dim3(256), 0, on>>>(arena.idx, arena.pos, arena.sym, deep, end_ptr, begin, end, deep_cap, d_text, static_cast<uint32_t>(n), d_bwt,
                                                                            d_origin, d_fallback, nullptr, giant[0], by_wave ? LDM_ARENA : LDM_ALL, 0u);
-            k_lf_deep_block<LF_DEEP_MAX, 1024><<<dim3(256), dim3(1024), 0, on>>>(arena.idx, arena.pos, arena.sym, deep, end_ptr, begin, end, LF_DEEP_CAP, d_text, static_cast<uint32_t>(n),
+            k_lf_deep_block<LF_DEEP_MAX, 1024><<<dim3(256), dim3(1024), 0, on>>>(arena.idx, arena.pos, arena.sym, deep, end_ptr, begin, end, deep_cap, d_text, static_cast<uint32_t>(n),
                                                                                  d_bwt, d_origin, d_fallback, nullptr, giant[0], by_wave ? LDM_ARENA : LDM_ALL, static_cast<uint32_t>(LS_MAX));
         }
         DK_HIP(ctx, hipGetLastError());
@@ -1699,8 +1717,10 @@ int lfirst_path(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uint64_t *in
     const size_t fork_slots = static_cast<size_t>(DK_KNOB("DK_LF_FORK", 4 << 20));  // big-list size from which on the early pass may start (0: never)
     const uint32_t refork_groups = static_cast<uint32_t>(std::max(1, DK_KNOB("DK_LF_REFORK", 4096)));  // new deep groups from which on another early pass starts
     for (int round = 0; active > 0; ++round) {
-        if (nbig > 0 && (round >= LF_MAX_ROUNDS || nbig / nbiggroups > LF_AVG_BIG || stalled >= 2)) {
-            if (trace) fprintf(stderr, "[dk] L-first: giant groups (%zu slots in %zu groups, round %d): back to the suffix-array path\n", nbig, nbiggroups, round);
+        if (nbig > 0 && (round >= max_rounds || nbig / nbiggroups > LF_AVG_BIG || stalled >= 2)) {
+            if (trace)
+                fprintf(stderr, "[dk] L-first: %s (%zu slots in %zu groups, round %d): back to the suffix-array path\n",
+                        round >= max_rounds ? "round limit" : stalled >= 2 ? "two stalled rounds" : "giant groups", nbig, nbiggroups, round);
             ctx->ws_release(mark);
             return DK_OK;
         }
@@ -1740,11 +1760,11 @@ int lfirst_path(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uint64_t *in
             LaunchScope ls(ctx, K_LF_FINISH, 13.0 * active + 64.0 * active + 17.0 * nbig);
             k_lf_finish<LFS_TILE, LFS_CAP, LFS_BLOCK><<<dim3(div_up(active, LFS_TILE)), dim3(LFS_BLOCK), 0, st>>>(b.l_idx, b.l_pos, b.l_gid, b.l_sym, b.gstart, b.bigidx, b.bigoff, active, d_text,
                                                                                 static_cast<uint32_t>(n), b.gdepth, b.bigdepth, tok, kb, ls_max, big_min, b.k0, b.v0, b.bpos, d_bwt,
-                                                                                d_origin, deep, d_deep_count, LF_DEEP_CAP, arena, d_fallback, active <= short_slots ? short_steps : max_steps, stuck_steps);
+                                                                                d_origin, deep, d_deep_count, deep_cap, arena, d_fallback, active <= short_slots ? short_steps : max_steps, stuck_steps);
         }
         if (big_min != ls_max) {  // the groups the big list let go stand in the round's list: refined to their end inside LDS before the list is rewritten
             LaunchScope ls(ctx, K_CHAIN, 0.0);
-            k_lf_medium<LF_DEEP_MAX / 8><<<dim3(1024), dim3(LF_DEEP_MAX / 8), 0, st>>>(b.l_idx, b.l_pos, b.l_sym, deep, d_deep_count, d_deep_begin, LF_DEEP_CAP, d_text, static_cast<uint32_t>(n), d_bwt,
+            k_lf_medium<LF_DEEP_MAX / 8><<<dim3(1024), dim3(LF_DEEP_MAX / 8), 0, st>>>(b.l_idx, b.l_pos, b.l_sym, deep, d_deep_count, d_deep_begin, deep_cap, d_text, static_cast<uint32_t>(n), d_bwt,
                                                                             d_origin, arena, d_fallback, medium_steps, stuck_steps);
         }
         DK_HIP(ctx, hipMemcpyAsync(d_deep_begin, d_deep_count, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));  // the next round's groups start here
@@ -1772,7 +1792,7 @@ int lfirst_path(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uint64_t *in
             if (trace) fprintf(stderr, "[dk] L-first round %d: periodic groups (period %d) keyed by the tokens of their stretches' ends\n", round, period);
         }
         h += static_cast<uint32_t>(tsym_big);
-        if (fork_slots && nbig > 0 && nbig <= fork_slots && ctx->h_mail[989] <= LF_DEEP_CAP && ctx->h_mail[989] >= deep_done + (forked ? refork_groups : 1024u)) {
+        if (fork_slots && nbig > 0 && nbig <= fork_slots && ctx->h_mail[989] <= deep_cap && ctx->h_mail[989] >= deep_done + (forked ? refork_groups : 1024u)) {
             // (the count was read behind this round's k_lf_finish and k_lf_medium: every entry below it is complete -- those of the rounds by that read,
             //  those an earlier pass on the side stream handed on by the stream's order.  Again whenever enough new groups have arrived.)
             const uint32_t from_entry = deep_done;
@@ -1801,19 +1821,25 @@ int lfirst_path(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uint64_t *in
     forked = false;
     DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 980, d_deep_count, 9 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     DK_HIP(ctx, hipStreamSynchronize(st));
-    if (ctx->h_mail[980] > deep_done && ctx->h_mail[980] <= LF_DEEP_CAP && ctx->h_mail[981] == 0) {
+    if (ctx->h_mail[980] > deep_done && ctx->h_mail[980] <= deep_cap && ctx->h_mail[981] == 0) {
         if (trace) fprintf(stderr, "[dk] L-first: %u deep groups (%u of them ordered beside the rounds), %u members in the arena\n", ctx->h_mail[980], deep_done, ctx->h_mail[988]);
         DK_TRY(order_deep(st, deep_done, ctx->h_mail[980], true));
     }
     // giant common extensions: measured by the whole grid, then the subgroup goes through k_lf_deep again (and may hand on a part of itself)
     DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 980, d_deep_count, 9 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     DK_HIP(ctx, hipStreamSynchronize(st));
-    const bool any_giant = ctx->h_mail[983] != 0 && ctx->h_mail[981] == 0;
+    const bool any_giant = ctx->h_mail[983] != 0 && ctx->h_mail[981] == 0 && ctx->h_mail[980] <= deep_cap;
     if (trace && any_giant) fprintf(stderr, "[dk] L-first: %u subgroups with giant common extensions go through the grid-wide measure\n", ctx->h_mail[983]);
-    for (int r = 0; any_giant && r < LF_GIANT_ROUNDS; ++r) {
+    for (int r = 0; any_giant && r < giant_rounds; ++r) {
         const LfGiantOut &in = giant[r & 1];
         LfGiantOut out = giant[(r + 1) & 1];
-        if (r + 1 == LF_GIANT_ROUNDS) out.cap = 0;  // what is still giant after the last round makes the path give up
+        if (r + 1 == giant_rounds) out.cap = 0;  // what is still giant after the last round makes the path give up
+        if (trace) {
+            uint32_t listed = 0;
+            DK_HIP(ctx, hipMemcpyAsync(&listed, in.count, sizeof listed, hipMemcpyDeviceToHost, st));
+            DK_HIP(ctx, hipStreamSynchronize(st));
+            if (listed) fprintf(stderr, "[dk] L-first: giant round %d: %u subgroups\n", r, listed);
+        }
         DK_HIP(ctx, hipMemsetAsync(lce_res, 0xFF, static_cast<size_t>(LF_GIANT_ARENA) * sizeof(uint32_t), st));
         DK_HIP(ctx, hipMemsetAsync(out.count, 0, sizeof(uint32_t), st));
         DK_HIP(ctx, hipMemsetAsync(out.used, 0, sizeof(uint32_t), st));
@@ -1830,11 +1856,17 @@ int lfirst_path(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uint64_t *in
     DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 980, d_deep_count, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     DK_HIP(ctx, hipStreamSynchronize(st));
     deep_total = ctx->h_mail[980];
+    // Giving up: a kernel found a list full (deep list, arena, giant list or its arena) or a common extension still giant after the last giant round
+    // (the fallback word) -- or the deep list's count went past its cap where no kernel said so (the host skipped the pass at the end above, and
+    // every group listed since the early pass would stay unordered).  No giant round at all (tuning build) leaves the giant list unordered too.
+    const bool gave_up = ctx->h_mail[981] != 0 || deep_total > deep_cap || (any_giant && giant_rounds == 0);
     if (any_giant) ctx->stats.sa_route |= DK_ROUTE_LFIRST_GIANT;
-    if (trace) fprintf(stderr, "[dk] L-first: %u groups went the deep way%s\n", deep_total, ctx->h_mail[981] ? "; a common extension was too long: back to the suffix-array path" : "");
+    if (trace)
+        fprintf(stderr, "[dk] L-first: %u groups went the deep way%s\n", deep_total,
+                gave_up ? "; a list overflowed (deep groups, arena, giant list) or a common extension stayed giant: back to the suffix-array path" : "");
     ctx->ws_release(mark);
     if (deep_total) ctx->stats.sa_route |= DK_ROUTE_LFIRST_DEEP;
-    if (ctx->h_mail[981]) return DK_OK;
+    if (gave_up) return DK_OK;
     *done = true;
     return DK_OK;
 }

@@ -248,7 +248,9 @@ typedef struct dk_stats {
 #define DK_ROUTE_LFIRST_BIG_ROUND 0x800u  /* ... with at least one global-sort round of big groups */
 #define DK_ROUTE_LFIRST_DEEP 0x1000u    /* ... and groups that went the way of long repeats (common extension measured directly) */
 #define DK_ROUTE_LFIRST_GIANT 0x4000u    /* ... and common extensions longer than 64 KiB, measured by the whole grid (copies of whole files) */
-#define DK_ROUTE_LFIRST_FALLBACK 0x2000u  /* the L-first path gave up (giant groups / over-long common extensions): suffix-array path from the start */
+#define DK_ROUTE_LFIRST_FALLBACK 0x2000u  /* the L-first path gave up: most of the block in big groups, giant groups, the round limit, two stalled
+                                            rounds in a row, a full list (deep groups, their arena, the giant list or its arena) or a common
+                                            extension still giant after the last giant round.  The suffix-array path, from the start */
 #define DK_ROUTE_PERIOD_ROUND 0x8000u    /* a period round ran: suffixes inside stretches of one short period (runs, (ab)^n, zero padding) placed by where the stretch ends */
 #define DK_ROUTE_PACKED_PAIRS 0x10000u   /* the initial sort moved packed pairs: key, carried code and position in one 64-bit word (at most 32 key bits, small alphabets) */
 #define DK_ROUTE_PACKED_GUARD 0x20000u   /* packed path: at least one block was still unresolved after the pack's round limit and went through the single-block path */

@@ -267,12 +267,12 @@ int dk_ctx_create(int hip_device, size_t max_n, dk_ctx **out) {
     }
     c->ws_size = workspace_bytes(max_n);
     ok = ok && hipMalloc(reinterpret_cast<void **>(&c->ws), c->ws_size) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void **>(&c->d_mail), 1024 * sizeof(uint32_t)) == hipSuccess;
-    ok = ok && hipHostMalloc(reinterpret_cast<void **>(&c->h_mail), 1024 * sizeof(uint32_t), hipHostMallocDefault) == hipSuccess;
+    ok = ok && hipMalloc(reinterpret_cast<void **>(&c->d_mail), sizeof(dk::Mail)) == hipSuccess;
+    ok = ok && hipHostMalloc(reinterpret_cast<void **>(&c->h_mail), sizeof(dk::Mail), hipHostMallocDefault) == hipSuccess;
     // (on the context's own stream, and waited for: a memset on the null stream may still be on its way when the first call's kernels -- on a
     //  non-blocking stream, which the null stream does not order -- have written the mailbox: the first suffix sort of a fresh context then read an
     //  empty symbol histogram, one run in four of a test that starts with a tiny block)
-    ok = ok && hipMemsetAsync(c->d_mail, 0, 1024 * sizeof(uint32_t), c->stream) == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess;
+    ok = ok && hipMemsetAsync(c->d_mail, 0, sizeof(dk::Mail), c->stream) == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess;
     for (hipEvent_t &e : c->round_ev) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) == hipSuccess;

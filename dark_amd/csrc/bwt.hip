@@ -602,41 +602,39 @@ __global__ __launch_bounds__(256) void k_pib_copy(const uint64_t *__restrict__ p
 
 }  // namespace
 
+// the origin word back: some kernel has stored the slot of suffix 0 there, whichever way L was written
+static int read_origin(dk_ctx *ctx, size_t n, uint32_t *origin) {
+    DK_TRY(ctx->mail_read(&ctx->h_mail->origin));
+    *origin = ctx->h_mail->origin;
+    if (*origin >= n) return ctx->fail(DK_E_INTERNAL, "bwt_forward: no suffix 0 in the suffix array");
+    return DK_OK;
+}
+
 int bwt_gather_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_sa, size_t n, uint8_t *d_bwt, uint32_t *origin) {
     hipStream_t st = ctx->stream;
-    uint32_t *d_origin = ctx->d_mail + 8;
-    DK_HIP(ctx, hipMemsetAsync(d_origin, 0xFF, sizeof(uint32_t), st));
+    uint32_t *d_origin = &ctx->d_mail->origin;
+    DK_TRY(ctx->mail_fill(d_origin, 0xFF));
     {
         LaunchScope ls(ctx, K_BWT_GATHER, 6.0 * n);
         k_bwt_gather<<<dim3(div_up(div_up(n, BG_PER_THREAD), 256)), dim3(256), 0, st>>>(d_text, d_sa, n, d_bwt, d_origin);
     }
     DK_HIP(ctx, hipGetLastError());
-    DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 8, d_origin, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipStreamSynchronize(st));
-    *origin = ctx->h_mail[8];
-    if (*origin >= n) return ctx->fail(DK_E_INTERNAL, "bwt_forward: no suffix 0 in the suffix array");
-    return DK_OK;
+    return read_origin(ctx, n, origin);
 }
 
 // suffix sort + BWT: the gather is skipped when the sort already wrote L (suffix_array_device, short-prefix path)
 int bwt_forward_device(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d_sa, uint8_t *d_bwt, uint32_t *origin) {
     hipStream_t st = ctx->stream;
-    uint32_t *d_origin = ctx->d_mail + 8;
-    DK_HIP(ctx, hipMemsetAsync(d_origin, 0xFF, sizeof(uint32_t), st));
+    uint32_t *d_origin = &ctx->d_mail->origin;
+    DK_TRY(ctx->mail_fill(d_origin, 0xFF));
     bool written = false;
     Timer t;
     DK_TRY(suffix_array_device(ctx, d_text, n, d_sa, d_bwt, d_origin, &written));
     DK_HIP(ctx, hipStreamSynchronize(st));
     ctx->stats.ms_sa = t.ms();
     Timer t2;
-    if (!written) {
-        DK_TRY(bwt_gather_device(ctx, d_text, d_sa, n, d_bwt, origin));
-    } else {
-        DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 8, d_origin, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        DK_HIP(ctx, hipStreamSynchronize(st));
-        *origin = ctx->h_mail[8];
-        if (*origin >= n) return ctx->fail(DK_E_INTERNAL, "bwt_forward: no suffix 0 in the suffix array");
-    }
+    if (!written) DK_TRY(bwt_gather_device(ctx, d_text, d_sa, n, d_bwt, origin));
+    else DK_TRY(read_origin(ctx, n, origin));
     ctx->stats.ms_bwt = t2.ms();
     return DK_OK;
 }
@@ -686,10 +684,10 @@ int bwt_inverse_device(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t ori
     // Pointer jumping halves every chain per step: ceil(log2(nsplit)) + 1 steps finish any single path through the splitters.
     // They are enqueued back to back (no host round trip per step); only the last one reports whether something is still
     // unresolved, which can only mean a cycle (corrupt input).
-    uint32_t *d_pending = ctx->d_mail + 10;
+    uint32_t *d_pending = &ctx->d_mail->ibwt_pending;
     const int steps = static_cast<int>(ceil_log2_u64(nsplit)) + 1;
     for (int it = 0; it < steps; ++it) {
-        if (it == steps - 1) DK_HIP(ctx, hipMemsetAsync(d_pending, 0, sizeof(uint32_t), st));
+        if (it == steps - 1) DK_TRY(ctx->mail_fill(d_pending, 0));
         {
             LaunchScope ls(ctx, K_IBWT_JUMP, 24.0 * nsplit);
             k_ibwt_jump<<<dim3(div_up(nsplit, 256)), dim3(256), 0, st>>>(nxt, acc, nxt_alt, acc_alt, nsplit, d_pending);
@@ -698,11 +696,10 @@ int bwt_inverse_device(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t ori
         std::swap(acc, acc_alt);
     }
     DK_HIP(ctx, hipGetLastError());
-    DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 10, d_pending, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipStreamSynchronize(st));
-    if (ctx->h_mail[10] != 0) return ctx->fail(DK_E_STREAM, "bwt_inverse: successor table has a cycle (corrupt input)");
-    uint32_t *d_bad = ctx->d_mail + 11;
-    DK_HIP(ctx, hipMemsetAsync(d_bad, 0, sizeof(uint32_t), st));
+    DK_TRY(ctx->mail_read(&ctx->h_mail->ibwt_pending));
+    if (ctx->h_mail->ibwt_pending != 0) return ctx->fail(DK_E_STREAM, "bwt_inverse: successor table has a cycle (corrupt input)");
+    uint32_t *d_bad = &ctx->d_mail->ibwt_bad;
+    DK_TRY(ctx->mail_fill(d_bad, 0));
     {
         LaunchScope ls(ctx, K_IBWT_EMIT, (record ? 2.0 : 6.0) * n);
         if (record)
@@ -713,10 +710,9 @@ int bwt_inverse_device(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t ori
                                                                           d_out, d_bad);
     }
     DK_HIP(ctx, hipGetLastError());
-    DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 11, d_bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipStreamSynchronize(st));
+    DK_TRY(ctx->mail_read(&ctx->h_mail->ibwt_bad));
     ctx->ws_release(mark);
-    if (ctx->h_mail[11]) return ctx->fail(DK_E_STREAM, "bwt_inverse: BWT/origin do not describe a single text cycle");
+    if (ctx->h_mail->ibwt_bad) return ctx->fail(DK_E_STREAM, "bwt_inverse: BWT/origin do not describe a single text cycle");
     return DK_OK;
 }
 
@@ -782,7 +778,8 @@ int packed_ibwt_device(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector<uint
     }
     DK_HIP(ctx, hipGetLastError());
     // every chain lies inside one block: the longest block's splitter count decides the number of jumps
-    uint32_t *d_pending = ctx->d_mail + 49, *d_bad = ctx->d_mail + 48;
+    uint32_t *d_pending = &ctx->d_mail->packed.ibwt_pending, *d_bad = &ctx->d_mail->packed.ibwt_bad;
+    const uint32_t &bad = ctx->h_mail->packed.ibwt_bad;  // (valid behind every mail_read below)
     const int steps = static_cast<int>(ceil_log2_u64(max_split)) + 1;
     for (int it = 0; it < steps; ++it) {
         {
@@ -792,17 +789,15 @@ int packed_ibwt_device(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector<uint
         std::swap(nxt, nxt_alt);
         std::swap(acc, acc_alt);
     }
-    DK_HIP(ctx, hipMemsetAsync(d_bad, 0xFF, sizeof(uint32_t), st));
+    DK_TRY(ctx->mail_fill(d_bad, 0xFF));
     {
         LaunchScope ls(ctx, K_IBWT_JUMP, 12.0 * nsplit);
         k_pib_check<<<dim3(sgrid), dim3(256), 0, st>>>(d_off, d_org, d_sb, cnt, S, nsplit, nxt, acc, len_keep, d_bad);
     }
     DK_HIP(ctx, hipGetLastError());
-    DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 48, d_bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipStreamSynchronize(st));
+    DK_TRY(ctx->mail_read(&ctx->h_mail->packed.ibwt_bad));
     // nothing has been written to d_out yet: a corrupt block fails the whole call and leaves the output as it was
-    if (ctx->h_mail[48] != IB_END)
-        return ctx->fail(DK_E_STREAM, "bwt_inverse_packed: block %u of the pack: BWT/origin do not describe a single text cycle", ctx->h_mail[48]);
+    if (bad != IB_END) return ctx->fail(DK_E_STREAM, "bwt_inverse_packed: block %u of the pack: BWT/origin do not describe a single text cycle", bad);
     {
         LaunchScope ls(ctx, K_IBWT_EMIT, (record ? 2.0 : 6.0) * total);
         if (record)
@@ -811,11 +806,9 @@ int packed_ibwt_device(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector<uint
             k_pib_emit<<<dim3(sgrid), dim3(256), 0, st>>>(psi, d_off, d_org, d_sb, cnt, S, nsplit, acc, d_out, d_bad);
     }
     DK_HIP(ctx, hipGetLastError());
-    DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 48, d_bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipStreamSynchronize(st));
+    DK_TRY(ctx->mail_read(&ctx->h_mail->packed.ibwt_bad));
     ctx->ws_release(mark);
-    if (ctx->h_mail[48] != IB_END)
-        return ctx->fail(DK_E_STREAM, "bwt_inverse_packed: block %u of the pack: BWT/origin do not describe a single text cycle", ctx->h_mail[48]);
+    if (bad != IB_END) return ctx->fail(DK_E_STREAM, "bwt_inverse_packed: block %u of the pack: BWT/origin do not describe a single text cycle", bad);
     return DK_OK;
 }
 

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/dark_amd.h"
+#include "mailbox.hpp"
 
 namespace dk {
 
@@ -74,9 +75,20 @@ struct dk_ctx {
     // device workspace: one allocation, bump-allocated per API call (all stages of a call run in sequence)
     char *ws = nullptr;
     size_t ws_size = 0, ws_used = 0, ws_peak = 0;
-    // small pinned host mailbox for counters read back between rounds
-    uint32_t *h_mail = nullptr;   // 1024 words, hipHostMalloc
-    uint32_t *d_mail = nullptr;   // 1024 words on the device
+    // the mailbox (mailbox.hpp is its map): the small results of the device stages, and their pinned host twins
+    dk::Mail *h_mail = nullptr;   // hipHostMalloc
+    dk::Mail *d_mail = nullptr;
+    // All three on `stream`.  mail_fetch enqueues *h_field = its twin in d_mail (or d_src: any device address holding a T); h_field points into
+    // h_mail and is valid after the next synchronise of the stream.  mail_read synchronises at once.  mail_fill fills a member or group of d_mail.
+    template <class T> int mail_fetch(T *h_field, const void *d_src = nullptr) {
+        if (!d_src) d_src = reinterpret_cast<const char *>(d_mail) + (reinterpret_cast<const char *>(h_field) - reinterpret_cast<const char *>(h_mail));
+        return hip_ok(hipMemcpyAsync(h_field, d_src, sizeof(T), hipMemcpyDeviceToHost, stream), "mailbox copy");
+    }
+    template <class T> int mail_read(T *h_field, const void *d_src = nullptr) {
+        const int rc = mail_fetch(h_field, d_src);
+        return rc != DK_OK ? rc : hip_ok(hipStreamSynchronize(stream), "mailbox wait");
+    }
+    template <class T> int mail_fill(T *d_field, int byte) { return hip_ok(hipMemsetAsync(d_field, byte, sizeof(T), stream), "mailbox fill"); }
     // pinned staging for D2H of the DC stream
     char *h_stage = nullptr;
     size_t h_stage_size = 0;
@@ -94,13 +106,14 @@ struct dk_ctx {
     size_t last_consumed = 0;  // bytes of coded stream the last block decode read (records can be concatenated)
     dk_stats stats{};
     bool profiling = false;
-    hipEvent_t round_ev[8] = {};  // suffix sort: one per in-place round in flight (live count read back one round late)
+    hipEvent_t round_ev[dk::LIVE_RING] = {};  // suffix sort: one per in-place round in flight (live count read back one round late)
     std::vector<hipEvent_t> ev_pool;
     struct Pending { int slot; hipEvent_t a, b; double bytes; hipStream_t on; };
     std::vector<Pending> ev_pending;
     size_t ev_next = 0;
 
     int fail(int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
+    int hip_ok(hipError_t e, const char *what) { return e == hipSuccess ? DK_OK : fail(DK_E_HIP, "%s: %s", what, hipGetErrorString(e)); }
 
     void ws_reset() { ws_used = 0; }
     // 256-byte aligned bump allocation; returns nullptr (and records the error) when the workspace is exhausted

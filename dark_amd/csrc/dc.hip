@@ -124,8 +124,8 @@ __global__ __launch_bounds__(DC_BLOCK) void k_dc_summary(const uint8_t *__restri
     }
 }
 
-// one workgroup: exclusive sum over tiles of the run counts; total -> mail[0]
-__global__ __launch_bounds__(1024) void k_dc_runscan(uint32_t *__restrict__ tile_runs, size_t ntiles, uint32_t *__restrict__ mail) {
+// one workgroup: exclusive sum over tiles of the run counts; total -> *total_runs (Mail::dc_runs)
+__global__ __launch_bounds__(1024) void k_dc_runscan(uint32_t *__restrict__ tile_runs, size_t ntiles, uint32_t *__restrict__ total_runs) {
     __shared__ uint32_t s_tmp[16 + 1];
     const size_t per = (ntiles + 1023) / 1024;
     const size_t b0 = static_cast<size_t>(threadIdx.x) * per;
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(1024) void k_dc_runscan(uint32_t *__restrict__ tile
         tile_runs[b] = run;
         run += v;
     }
-    if (threadIdx.x == 0) mail[0] = total;
+    if (threadIdx.x == 0) *total_runs = total;
 }
 
 // carry scan, phase A: last non-empty entry of every symbol within a chunk of tiles.  tile_lrun is turned into a global
@@ -701,7 +701,7 @@ int dc_encode_device(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t init_
     }
     {
         LaunchScope ls(ctx, K_DC_CARRY, 3.0 * 2048.0 * ntiles);
-        k_dc_runscan<<<dim3(1), dim3(1024), 0, st>>>(tile_runs, ntiles, ctx->d_mail);
+        k_dc_runscan<<<dim3(1), dim3(1024), 0, st>>>(tile_runs, ntiles, &ctx->d_mail->dc_runs);
         k_dc_carry_a<<<dim3(nchunks), dim3(256), 0, st>>>(tile_last, tile_lrun, tile_runs, ntiles, tpc, chunk_last, chunk_lrun);
         k_dc_carry_b<<<dim3(1), dim3(1024), 0, st>>>(chunk_last, chunk_lrun, nchunks);
         k_dc_carry_c<<<dim3(nchunks), dim3(256), 0, st>>>(tile_last, tile_lrun, ntiles, tpc, chunk_last, chunk_lrun);
@@ -710,18 +710,17 @@ int dc_encode_device(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t init_
     {
         LaunchScope ls(ctx, K_DC_MAIN, 1.0 * n + 2048.0 * ntiles);
         k_dc_main<<<dim3(nblocks), dim3(DC_BLOCK), 0, st>>>(d_bwt, n, ntiles, tile_last, tile_lrun, tile_runs, tile_syms, tile_set, d_dist, d_sym, d_rank,
-                                                            d_run_end, ctx->d_mail, d_final, d_final + 256);
+                                                            d_run_end, &ctx->d_mail->dc_runs, d_final, d_final + 256);
     }
     {
         LaunchScope ls(ctx, K_DC_INIT, 2048.0);
         k_dc_init<<<dim3(1), dim3(256), 0, st>>>(d_final, static_cast<uint32_t>(n), d_init);
     }
     DK_HIP(ctx, hipGetLastError());
-    DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail, ctx->d_mail, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 16, d_init, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipStreamSynchronize(st));
-    *m = ctx->h_mail[0];
-    for (int s = 0; s < 256; ++s) init_host[s] = ctx->h_mail[16 + s];
+    DK_TRY(ctx->mail_fetch(&ctx->h_mail->dc_runs));
+    DK_TRY(ctx->mail_read(&ctx->h_mail->dc_init, d_init));
+    *m = ctx->h_mail->dc_runs;
+    for (int s = 0; s < 256; ++s) init_host[s] = ctx->h_mail->dc_init[s];
     ctx->stats.dc_runs = *m;
     ctx->ws_release(mark);
     return DK_OK;

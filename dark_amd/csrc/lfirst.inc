@@ -480,13 +480,13 @@ int lf_rerank(dk_ctx *ctx, const uint64_t *keys, int cmp_shift, const uint32_t *
         LaunchScope ls(ctx, K_RERANK_SCAN, 64.0 * ntiles);
         k_lf_straddle<<<dim3(div_up(ntiles, 4)), dim3(256), 0, st>>>(tiles, agg, static_cast<uint32_t>(ntiles));
         if (ntiles <= 4 * RSC_CHUNK) {
-            k_rerank_scan<<<dim3(1), dim3(1024), 0, st>>>(agg, ntiles, ctx->d_mail, gstart);
+            k_rerank_scan<<<dim3(1), dim3(1024), 0, st>>>(agg, ntiles, &ctx->d_mail->cls.rounds, gstart);
         } else {
             const size_t nchunks = div_up(ntiles, RSC_CHUNK);
             RerankAgg *chunk = ctx->ws_alloc<RerankAgg>(nchunks);
             if (!chunk) return DK_E_NOMEM;
             k_rerank_scan_a<<<dim3(nchunks), dim3(256), 0, st>>>(agg, ntiles, chunk);
-            k_rerank_scan<<<dim3(1), dim3(1024), 0, st>>>(chunk, nchunks, ctx->d_mail, gstart);
+            k_rerank_scan<<<dim3(1), dim3(1024), 0, st>>>(chunk, nchunks, &ctx->d_mail->cls.rounds, gstart);
             k_rerank_scan_c<<<dim3(nchunks), dim3(256), 0, st>>>(agg, ntiles, chunk);
         }
     }
@@ -1415,12 +1415,12 @@ __global__ __launch_bounds__(256) void k_lf_lce(const uint32_t *__restrict__ g_i
 // slot-rounds), which ONE workgroup sorts inside LDS (sort_groups, radix_sort.hip) at a third of the price.  So the list gets two regions: the
 // giant groups first (global sort, on their own few group bits), the medium ones behind (sorted group by group).  Same kernels as classify_and_read
 // with a size range and the bases of the class: dense index and list offset go on from where the class before stopped.
-//   mail[2] / [4]: slots / groups of the giant class; mail[12] / [13]: of the medium class
+//   Mail::Classes: rounds.big_slots / big_groups count the giant class, medium_slots / medium_groups the medium one
 // (both classes in one pass: `part` holds (giant slots, giant groups, medium slots, medium groups) per workgroup)
-__global__ __launch_bounds__(256) void k_cls_reduce(const uint32_t *__restrict__ gstart, const uint32_t *__restrict__ mail, uint4 *__restrict__ part, uint32_t lo,
+__global__ __launch_bounds__(256) void k_cls_reduce(const uint32_t *__restrict__ gstart, const Mail::Classes *__restrict__ mail, uint4 *__restrict__ part, uint32_t lo,
                                                      uint32_t mid) {
     __shared__ uint32_t s_w[4][RR_WAVES];
-    const size_t groups = mail[1];
+    const size_t groups = mail->rounds.groups;
     size_t t0, t1;
     big_stretch(groups, &t0, &t1);
     uint32_t gs = 0, gc = 0, ms = 0, mc = 0;
@@ -1450,8 +1450,8 @@ __global__ __launch_bounds__(256) void k_cls_reduce(const uint32_t *__restrict__
         part[blockIdx.x] = make_uint4(s_w[0][0] + s_w[0][1] + s_w[0][2] + s_w[0][3], s_w[1][0] + s_w[1][1] + s_w[1][2] + s_w[1][3],
                                       s_w[2][0] + s_w[2][1] + s_w[2][2] + s_w[2][3], s_w[3][0] + s_w[3][1] + s_w[3][2] + s_w[3][3]);
 }
-// exclusive over the workgroups, the medium class behind the giant one; totals -> mail[2] / [4] (giant), mail[12] / [13] (medium); sentinel behind the last group
-__global__ __launch_bounds__(BG_GRID) void k_cls_spine(uint4 *__restrict__ part, uint32_t *__restrict__ mail, uint32_t *__restrict__ bigoff) {
+// exclusive over the workgroups, the medium class behind the giant one; totals -> the mailbox; sentinel behind the last group
+__global__ __launch_bounds__(BG_GRID) void k_cls_spine(uint4 *__restrict__ part, Mail::Classes *__restrict__ mail, uint32_t *__restrict__ bigoff) {
     __shared__ uint32_t s_tmp[16 + 1];
     const uint4 v = part[threadIdx.x];
     uint32_t tg, tgc, tm, tmc;
@@ -1461,17 +1461,17 @@ __global__ __launch_bounds__(BG_GRID) void k_cls_spine(uint4 *__restrict__ part,
     const uint32_t rmc = block_excl_sum<BG_GRID / 64>(v.w, s_tmp, &tmc);
     part[threadIdx.x] = make_uint4(rg, rgc, tg + rm, tgc + rmc);
     if (threadIdx.x == 0) {
-        mail[2] = tg;
-        mail[4] = tgc;
-        mail[12] = tm;
-        mail[13] = tmc;
+        mail->rounds.big_slots = tg;
+        mail->rounds.big_groups = tgc;
+        mail->medium_slots = tm;
+        mail->medium_groups = tmc;
         bigoff[tgc + tmc] = tg + tm;
     }
 }
-__global__ __launch_bounds__(256) void k_cls_apply(const uint32_t *__restrict__ gstart, const uint32_t *__restrict__ mail, const uint4 *__restrict__ part,
+__global__ __launch_bounds__(256) void k_cls_apply(const uint32_t *__restrict__ gstart, const Mail::Classes *__restrict__ mail, const uint4 *__restrict__ part,
                                                     uint32_t *__restrict__ bigidx, uint32_t *__restrict__ bigoff, uint32_t lo, uint32_t mid) {
     __shared__ uint32_t s_tmp[RR_WAVES + 1];
-    const size_t groups = mail[1];
+    const size_t groups = mail->rounds.groups;
     size_t t0, t1;
     big_stretch(groups, &t0, &t1);
     uint4 base = part[blockIdx.x];
@@ -1519,19 +1519,19 @@ int classify_two_and_read(dk_ctx *ctx, const uint32_t *gstart, uint32_t *bigidx,
     const uint32_t mid = std::max(lo, LF_MEDIUM_MAX);
     {
         LaunchScope ls(ctx, K_BIG_CLASSIFY, 0.0);
-        k_cls_reduce<<<dim3(BG_GRID), dim3(256), 0, st>>>(gstart, ctx->d_mail, part, lo, mid);
-        k_cls_spine<<<dim3(1), dim3(BG_GRID), 0, st>>>(part, ctx->d_mail, bigoff);
-        k_cls_apply<<<dim3(BG_GRID), dim3(256), 0, st>>>(gstart, ctx->d_mail, part, bigidx, bigoff, lo, mid);
+        k_cls_reduce<<<dim3(BG_GRID), dim3(256), 0, st>>>(gstart, &ctx->d_mail->cls, part, lo, mid);
+        k_cls_spine<<<dim3(1), dim3(BG_GRID), 0, st>>>(part, &ctx->d_mail->cls, bigoff);
+        k_cls_apply<<<dim3(BG_GRID), dim3(256), 0, st>>>(gstart, &ctx->d_mail->cls, part, bigidx, bigoff, lo, mid);
     }
     DK_HIP(ctx, hipGetLastError());
-    DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail, ctx->d_mail, 14 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipStreamSynchronize(st));
-    *active = ctx->h_mail[0];
-    *groups = ctx->h_mail[1];
-    *ngiant = ctx->h_mail[2];
-    *ngiantgroups = ctx->h_mail[4];
-    *nmedium = ctx->h_mail[12];
-    *nmediumgroups = ctx->h_mail[13];
+    const Mail::Classes &c = ctx->h_mail->cls;
+    DK_TRY(ctx->mail_read(&ctx->h_mail->cls));
+    *active = c.rounds.active;
+    *groups = c.rounds.groups;
+    *ngiant = c.rounds.big_slots;
+    *ngiantgroups = c.rounds.big_groups;
+    *nmedium = c.medium_slots;
+    *nmediumgroups = c.medium_groups;
     ctx->ws_release(mark);
     return DK_OK;
 }
@@ -1586,30 +1586,31 @@ int lfirst_path(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uint64_t *in
     LfDeepGroup *deep = ctx->ws_alloc<LfDeepGroup>(LF_DEEP_CAP);
     if (!deep) return DK_E_NOMEM;
     // The list starts out as zeros (flags 0, size 0): k_lf_medium walks it up to the CURRENT count while a pass on the side stream may be handing groups
-    // on -- an entry that is reserved and not written yet must not look like a listed group (stale LD_LIST bits of an earlier call would).  Entries are
-    // written whole (one 16-byte store).  (16 bytes per entry, at most about n entries: a few microseconds.)
+    // on, so it meets entries that are reserved and not written yet, or half written.  What keeps it safe: the flags dword alone decides whether it
+    // takes an entry (LD_LIST), and what writes entries beside it -- k_lf_deep_wave on the side stream (LD_HANDED), k_lf_medium's own workgroups
+    // (flags 0) -- never stores LD_LIST: an entry in flight reads as not listed whatever the order of its stores, and no LD_LIST bits of an earlier
+    // call are left.  Nothing relies on an entry being one 16-byte store.  (16 bytes per entry, at most about n entries: a few microseconds.)
     DK_HIP(ctx, hipMemsetAsync(deep, 0, std::min<size_t>(LF_DEEP_CAP, n + 4096) * sizeof(LfDeepGroup), st));
-    // (mail words 980 .. 987: 720 .. 975 hold the bucket starts of a narrow-key sort, read by the first rerank below)
-    uint32_t *d_deep_count = ctx->d_mail + 980, *d_fallback = ctx->d_mail + 981, *d_deep_begin = ctx->d_mail + 982;
-    // giant list (subgroups whose common extension is longer than a workgroup measures): two sets, one being read, one being filled
-    uint32_t *d_giant_count = ctx->d_mail + 983 /* [2] */, *d_giant_used = ctx->d_mail + 986 /* [2] */;
-    uint32_t *d_arena_used = ctx->d_mail + 988;
-    DK_HIP(ctx, hipMemsetAsync(d_deep_count, 0, 9 * sizeof(uint32_t), st));
-    const LfArena arena{b.a_idx, b.a_pos, b.a_sym, d_arena_used, arena_cap};
+    // the path's counters, cleared before its first kernel (mailbox.hpp says who writes which of them from which stream)
+    Mail::LFirst *d_lf = &ctx->d_mail->lf;
+    const Mail::LFirst &lf = ctx->h_mail->lf;  // (valid behind every mail_read of the group below)
+    uint32_t *d_deep_count = &d_lf->deep_count, *d_fallback = &d_lf->fallback, *d_deep_begin = &d_lf->deep_begin;
+    DK_TRY(ctx->mail_fill(d_lf, 0));
+    const LfArena arena{b.a_idx, b.a_pos, b.a_sym, &d_lf->arena_used, arena_cap};
     // steps a group may take inside k_lf_finish, and steps without a split after which it leaves early (tuning build: DK_LF_STEPS, DK_LF_STUCK)
     const int max_steps = std::max(1, std::min(4096, DK_KNOB("DK_LF_STEPS", LF_STEPS))), stuck_steps = std::max(1, DK_KNOB("DK_LF_STUCK", LF_STUCK));
     // (short lists: LF_SHORT_STEPS steps for lists of at most LF_SHORT_SLOTS slots; tuning build: DK_LF_SHORT_STEPS, DK_LF_SHORT_SLOTS, 0 slots = the same everywhere)
     const int short_steps = std::max(1, std::min(4096, DK_KNOB("DK_LF_SHORT_STEPS", LF_SHORT_STEPS)));
     const size_t short_slots = static_cast<size_t>(DK_KNOB("DK_LF_SHORT_SLOTS", static_cast<int>(LF_SHORT_SLOTS)));
-    LfGiantOut giant[2];
+    LfGiantOut giant[2];  // giant list (subgroups whose common extension is longer than a workgroup measures): two sets, one being read, one being filled
     for (int q = 0; q < 2; ++q) {
         giant[q].list = ctx->ws_alloc<LfDeepGroup>(LF_GIANT_CAP);
-        giant[q].count = d_giant_count + q;
+        giant[q].count = &d_lf->giant_count[q];
         giant[q].cap = giant_cap;
         giant[q].idx = ctx->ws_alloc<uint32_t>(LF_GIANT_ARENA);
         giant[q].pos = ctx->ws_alloc<uint32_t>(LF_GIANT_ARENA);
         giant[q].sym = ctx->ws_alloc<uint8_t>(LF_GIANT_ARENA);
-        giant[q].used = d_giant_used + q;
+        giant[q].used = &d_lf->giant_used[q];
         giant[q].arena_cap = giant_arena;
         if (!giant[q].list || !giant[q].idx || !giant[q].pos || !giant[q].sym) return DK_E_NOMEM;
     }
@@ -1768,7 +1769,7 @@ int lfirst_path(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uint64_t *in
                                                                             d_origin, arena, d_fallback, medium_steps, stuck_steps);
         }
         DK_HIP(ctx, hipMemcpyAsync(d_deep_begin, d_deep_count, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));  // the next round's groups start here
-        if (fork_slots) DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 989, d_deep_count, sizeof(uint32_t), hipMemcpyDeviceToHost, st));  // (read behind the round's classification)
+        if (fork_slots) DK_TRY(ctx->mail_fetch(&ctx->h_mail->deep_seen, d_deep_count));  // (read behind the round's classification)
         DK_HIP(ctx, hipGetLastError());
         ctx->stats.rounds += 1;
         if (nbig == 0) break;
@@ -1792,11 +1793,11 @@ int lfirst_path(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uint64_t *in
             if (trace) fprintf(stderr, "[dk] L-first round %d: periodic groups (period %d) keyed by the tokens of their stretches' ends\n", round, period);
         }
         h += static_cast<uint32_t>(tsym_big);
-        if (fork_slots && nbig > 0 && nbig <= fork_slots && ctx->h_mail[989] <= deep_cap && ctx->h_mail[989] >= deep_done + (forked ? refork_groups : 1024u)) {
+        if (const uint32_t seen = ctx->h_mail->deep_seen; fork_slots && nbig > 0 && nbig <= fork_slots && seen <= deep_cap && seen >= deep_done + (forked ? refork_groups : 1024u)) {
             // (the count was read behind this round's k_lf_finish and k_lf_medium: every entry below it is complete -- those of the rounds by that read,
             //  those an earlier pass on the side stream handed on by the stream's order.  Again whenever enough new groups have arrived.)
             const uint32_t from_entry = deep_done;
-            deep_done = ctx->h_mail[989];
+            deep_done = seen;
             DK_HIP(ctx, hipEventRecord(ctx->ev_fork, st));
             DK_HIP(ctx, hipStreamWaitEvent(ctx->side_stream, ctx->ev_fork, 0));
             DK_TRY(order_deep(ctx->side_stream, from_entry, deep_done, false));
@@ -1819,17 +1820,15 @@ int lfirst_path(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uint64_t *in
     // early pass beside the rounds (order_deep above) has not taken already
     if (forked) DK_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_join, 0));
     forked = false;
-    DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 980, d_deep_count, 9 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipStreamSynchronize(st));
-    if (ctx->h_mail[980] > deep_done && ctx->h_mail[980] <= deep_cap && ctx->h_mail[981] == 0) {
-        if (trace) fprintf(stderr, "[dk] L-first: %u deep groups (%u of them ordered beside the rounds), %u members in the arena\n", ctx->h_mail[980], deep_done, ctx->h_mail[988]);
-        DK_TRY(order_deep(st, deep_done, ctx->h_mail[980], true));
+    DK_TRY(ctx->mail_read(&ctx->h_mail->lf));
+    if (lf.deep_count > deep_done && lf.deep_count <= deep_cap && lf.fallback == 0) {
+        if (trace) fprintf(stderr, "[dk] L-first: %u deep groups (%u of them ordered beside the rounds), %u members in the arena\n", lf.deep_count, deep_done, lf.arena_used);
+        DK_TRY(order_deep(st, deep_done, lf.deep_count, true));
     }
     // giant common extensions: measured by the whole grid, then the subgroup goes through k_lf_deep again (and may hand on a part of itself)
-    DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 980, d_deep_count, 9 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipStreamSynchronize(st));
-    const bool any_giant = ctx->h_mail[983] != 0 && ctx->h_mail[981] == 0 && ctx->h_mail[980] <= deep_cap;
-    if (trace && any_giant) fprintf(stderr, "[dk] L-first: %u subgroups with giant common extensions go through the grid-wide measure\n", ctx->h_mail[983]);
+    DK_TRY(ctx->mail_read(&ctx->h_mail->lf));
+    const bool any_giant = lf.giant_count[0] != 0 && lf.fallback == 0 && lf.deep_count <= deep_cap;
+    if (trace && any_giant) fprintf(stderr, "[dk] L-first: %u subgroups with giant common extensions go through the grid-wide measure\n", lf.giant_count[0]);
     for (int r = 0; any_giant && r < giant_rounds; ++r) {
         const LfGiantOut &in = giant[r & 1];
         LfGiantOut out = giant[(r + 1) & 1];
@@ -1853,13 +1852,12 @@ int lfirst_path(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uint64_t *in
         }
     }
     DK_HIP(ctx, hipGetLastError());
-    DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 980, d_deep_count, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipStreamSynchronize(st));
-    deep_total = ctx->h_mail[980];
+    DK_TRY(ctx->mail_read(&ctx->h_mail->lf));
+    deep_total = lf.deep_count;
     // Giving up: a kernel found a list full (deep list, arena, giant list or its arena) or a common extension still giant after the last giant round
     // (the fallback word) -- or the deep list's count went past its cap where no kernel said so (the host skipped the pass at the end above, and
     // every group listed since the early pass would stay unordered).  No giant round at all (tuning build) leaves the giant list unordered too.
-    const bool gave_up = ctx->h_mail[981] != 0 || deep_total > deep_cap || (any_giant && giant_rounds == 0);
+    const bool gave_up = lf.fallback != 0 || deep_total > deep_cap || (any_giant && giant_rounds == 0);
     if (any_giant) ctx->stats.sa_route |= DK_ROUTE_LFIRST_GIANT;
     if (trace)
         fprintf(stderr, "[dk] L-first: %u groups went the deep way%s\n", deep_total,

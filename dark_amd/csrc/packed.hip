@@ -452,7 +452,7 @@ int packed_bwt_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off,
     uint32_t *present = ctx->ws_alloc<uint32_t>(256);
     uint16_t *code = ctx->ws_alloc<uint16_t>(256);
     if (!keys || !keys_alt || !vals || !vals_alt || !act || !rank || !agg || !present || !code) return DK_E_NOMEM;
-    uint32_t *d_live = ctx->d_mail + 32;
+    uint32_t *d_live = &ctx->d_mail->packed.live;
     DK_HIP(ctx, hipMemsetAsync(present, 0, 256 * sizeof(uint32_t), st));
     {
         LaunchScope ls(ctx, K_SYM_HIST, 1.0 * total);
@@ -460,9 +460,8 @@ int packed_bwt_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off,
         k_pk_codes<<<dim3(1), dim3(256), 0, st>>>(present, code, d_live);
     }
     DK_HIP(ctx, hipGetLastError());
-    DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 32, d_live, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipStreamSynchronize(st));
-    const uint32_t sigma = ctx->h_mail[32];
+    DK_TRY(ctx->mail_read(&ctx->h_mail->packed.live));
+    const uint32_t sigma = ctx->h_mail->packed.live;
     const int bits = static_cast<int>(std::max(1u, ceil_log2_u64(static_cast<uint64_t>(sigma) + 1)));
     const int blk_bits = static_cast<int>(ceil_log2_u64(count));
     const int k = std::max(1, (64 - blk_bits) / bits);
@@ -490,9 +489,8 @@ int packed_bwt_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off,
             k_pk_tile_apply<<<dim3(ntiles), dim3(PK_BLOCK), 0, st>>>(keys, vals, c, rbits, agg, rank, act);
         }
         DK_HIP(ctx, hipGetLastError());
-        DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 32, d_live, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        DK_HIP(ctx, hipStreamSynchronize(st));
-        *live = ctx->h_mail[32];
+        DK_TRY(ctx->mail_read(&ctx->h_mail->packed.live));
+        *live = ctx->h_mail->packed.live;
         return DK_OK;
     };
     uint32_t live = 0;
@@ -561,9 +559,8 @@ int packed_dc_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, s
     }
     DK_HIP(ctx, hipGetLastError());
     // the run count is not read back: kernels over the runs are sized by the pack and read the count from d_rb[count]
-    DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 40, d_rb + count, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipStreamSynchronize(st));
-    const uint32_t m = ctx->h_mail[40];
+    DK_TRY(ctx->mail_read(&ctx->h_mail->packed.dc_runs, d_rb + count));
+    const uint32_t m = ctx->h_mail->packed.dc_runs;
     const uint32_t mtiles = static_cast<uint32_t>(div_up(m, PDC_TILE));
     const uint32_t nchunks = static_cast<uint32_t>(div_up(mtiles, tpc));
     DK_HIP(ctx, hipMemsetAsync(has_next, 0, m, st));

@@ -183,7 +183,6 @@ __device__ __forceinline__ uint32_t period_breaks16(const uint8_t *__restrict__ 
 // period is worth finding only for a block whose doubling rounds would run over everything anyway (giant groups hold most of it), and is used
 // once the depth has reached it.  k_period_search: PS_SAMPLES evenly spread positions, a workgroup each; thread i tests p = 9 + i, 9 + i + 256, ...
 // for 48 equal bytes and the smallest hit of a sample goes to found[sample].  k_period_count: 64-byte windows that follow a given p (any p).
-constexpr int PS_SAMPLES = 32;
 constexpr uint32_t PS_MAX = 1u << 18;
 __global__ __launch_bounds__(256) void k_period_search(const uint8_t *__restrict__ t, size_t n, uint32_t pmax, uint32_t *__restrict__ found) {
     const size_t x = (2 * static_cast<size_t>(blockIdx.x) + 1) * n / (2 * PS_SAMPLES);
@@ -288,7 +287,6 @@ __device__ __forceinline__ uint64_t text_key(const uint8_t *__restrict__ t, size
 // than a few percent of ALL suffixes share their prefix of that length with another suffix (c equal pairs: about c / 50 of them):
 // sorting by that prefix alone leaves a small active list, which one text-extension round finishes.  Text-like inputs show thousands
 // of equal pairs at every length and keep the full key.
-constexpr int PP_MAX_CAND = 4;
 struct ProbeCands { int count; int sym[PP_MAX_CAND]; };
 constexpr uint64_t PP_EMPTY = ~0ull;
 
@@ -489,8 +487,8 @@ __global__ __launch_bounds__(RR_BLOCK) void k_rerank_reduce(const K *__restrict_
     }
 }
 
-// one workgroup: exclusive scan of the per-tile aggregates (sum, sum, running max); totals -> mail[0..1]
-__global__ __launch_bounds__(1024) void k_rerank_scan(RerankAgg *__restrict__ agg, size_t ntiles, uint32_t *__restrict__ mail,
+// one workgroup: exclusive scan of the per-tile aggregates (sum, sum, running max); totals -> mail->active / groups
+__global__ __launch_bounds__(1024) void k_rerank_scan(RerankAgg *__restrict__ agg, size_t ntiles, Mail::Rounds *__restrict__ mail,
                                                       uint32_t *__restrict__ gstart) {
     __shared__ uint32_t s_tmp[16 + 1];
     const int tid = threadIdx.x;
@@ -517,7 +515,7 @@ __global__ __launch_bounds__(1024) void k_rerank_scan(RerankAgg *__restrict__ ag
         eh += r.heads;
         el = el > r.last_head ? el : r.last_head;
     }
-    if (tid == 0) { mail[0] = tot_s; mail[1] = tot_h; gstart[tot_h] = tot_s; }  // sentinel: one past the last group
+    if (tid == 0) { mail->active = tot_s; mail->groups = tot_h; gstart[tot_h] = tot_s; }  // sentinel: one past the last group
 }
 
 // The same scan for many tiles, in three phases over chunks of RS_CHUNK tiles (one workgroup reads at the rate of one CU: 524 288
@@ -699,7 +697,7 @@ struct RerankSlice { uint64_t fl, sym8; uint4 i0, i1; };
 __global__ __launch_bounds__(RR_BLOCK) void k_rerank_apply_first(const uint8_t *__restrict__ flags, const uint32_t *__restrict__ idx, size_t count,
                                                                   const RerankAgg *__restrict__ agg, uint32_t *__restrict__ out_idx,
                                                                   uint32_t *__restrict__ out_pos, uint32_t *__restrict__ out_gid,
-                                                                  uint32_t *__restrict__ gstart, const uint32_t *__restrict__ mail, BwtCarry bc,
+                                                                  uint32_t *__restrict__ gstart, const Mail::Rounds *__restrict__ mail, BwtCarry bc,
                                                                   uint32_t ntiles, uint32_t tiles_per_wg, uint32_t sparse_max) {
     __shared__ __attribute__((aligned(16))) uint32_t s_out[3 * RR_TILE];  // compacted idx | pos | gid
     __shared__ __attribute__((aligned(8))) uint8_t s_osym[RR_TILE];        // compacted symbols
@@ -709,7 +707,7 @@ __global__ __launch_bounds__(RR_BLOCK) void k_rerank_apply_first(const uint8_t *
     const uint32_t tile_first = blockIdx.x * tiles_per_wg;
     const uint32_t tile_end = tile_first + tiles_per_wg < ntiles ? tile_first + tiles_per_wg : ntiles;
     if (static_cast<uint32_t>(tid) <= tiles_per_wg)  // the aggregates in front of each of this workgroup's tiles (and of the one behind them)
-        s_agg[tid] = tile_first + tid < ntiles ? agg[tile_first + tid] : RerankAgg{mail[0], 0, 0, 0};
+        s_agg[tid] = tile_first + tid < ntiles ? agg[tile_first + tid] : RerankAgg{mail->active, 0, 0, 0};
     __syncthreads();
     auto next_with_survivors = [&](uint32_t t) {
         while (t < tile_end && s_agg[t - tile_first].surv == s_agg[t - tile_first + 1].surv) ++t;
@@ -825,13 +823,13 @@ int rerank(dk_ctx *ctx, const uint64_t *keys, const uint32_t *idx, const uint32_
     {
         LaunchScope ls(ctx, K_RERANK_SCAN, 32.0 * ntiles);
         if (ntiles <= 4 * RSC_CHUNK) {
-            k_rerank_scan<<<dim3(1), dim3(1024), 0, st>>>(agg, ntiles, ctx->d_mail, gstart);
+            k_rerank_scan<<<dim3(1), dim3(1024), 0, st>>>(agg, ntiles, &ctx->d_mail->cls.rounds, gstart);
         } else {  // phase B is the one-workgroup scan itself, over the chunk aggregates (totals -> mail, sentinel -> gstart)
             const size_t nchunks = div_up(ntiles, RSC_CHUNK);
             RerankAgg *chunk = ctx->ws_alloc<RerankAgg>(nchunks);
             if (!chunk) return DK_E_NOMEM;
             k_rerank_scan_a<<<dim3(nchunks), dim3(256), 0, st>>>(agg, ntiles, chunk);
-            k_rerank_scan<<<dim3(1), dim3(1024), 0, st>>>(chunk, nchunks, ctx->d_mail, gstart);
+            k_rerank_scan<<<dim3(1), dim3(1024), 0, st>>>(chunk, nchunks, &ctx->d_mail->cls.rounds, gstart);
             k_rerank_scan_c<<<dim3(nchunks), dim3(256), 0, st>>>(agg, ntiles, chunk);
         }
     }
@@ -843,7 +841,7 @@ int rerank(dk_ctx *ctx, const uint64_t *keys, const uint32_t *idx, const uint32_
         } else {
             if (rank) return ctx->fail(DK_E_INTERNAL, "rerank: the first rerank writes no ranks");
             const uint32_t per_wg = static_cast<uint32_t>(std::min<size_t>(std::max<size_t>(ntiles / 8192, 1), RA_FIRST_TILES));
-            k_rerank_apply_first<<<dim3(div_up(ntiles, per_wg)), dim3(RR_BLOCK), 0, st>>>(flags, idx, count, agg, out_idx, out_pos, out_gid, gstart, ctx->d_mail, fb,
+            k_rerank_apply_first<<<dim3(div_up(ntiles, per_wg)), dim3(RR_BLOCK), 0, st>>>(flags, idx, count, agg, out_idx, out_pos, out_gid, gstart, &ctx->d_mail->cls.rounds, fb,
                                                                                           static_cast<uint32_t>(ntiles), per_wg, static_cast<uint32_t>(DK_KNOB("DK_RA_SPARSE", RA_SPARSE)));
         }
     }
@@ -855,9 +853,9 @@ int rerank(dk_ctx *ctx, const uint64_t *keys, const uint32_t *idx, const uint32_
 // ---- big / small classification of the groups of the next round ---------------------------------------------------
 // A group of more than LS_MAX members goes through the global radix sort, in the BIG LIST: the slots of all big groups, group after
 // group.  bigidx[g] = number of big groups before group g (its dense index j), bigoff[j] = number of slots in big groups before it
-// (its offset in the big list); totals -> mail[2] (slots) and mail[4] (groups).  The global sort's key carries j, not the offset,
+// (its offset in the big list); totals -> Mail::Rounds big_slots and big_groups.  The global sort's key carries j, not the offset,
 // above the secondary key: j needs log2(#big groups) bits where the offset needs log2(#slots) -- two giant groups (periodic text)
-// cost ONE extra bit instead of 24, i.e. three radix passes less per round.  mail[3] = number of slots in groups of more than
+// cost ONE extra bit instead of 24, i.e. three radix passes less per round.  above_pl_slots = number of slots in groups of more than
 // PL_MAX members (those keep the sort in general rounds; zero = the in-place rounds can take over).
 constexpr int LS_MAX = 1024;  // general rounds: groups up to this size are sorted inside a workgroup's LDS
 constexpr int PL_BITS = 8;
@@ -875,7 +873,7 @@ __device__ __forceinline__ uint32_t big_size(const uint32_t *__restrict__ gstart
     const uint32_t sz = gstart[g + 1] - gstart[g];
     return sz > ls_max ? sz : 0u;
 }
-// `groups` is read from mail[1] on the device: the host does not know it yet when these kernels are enqueued.  The grid is fixed
+// `groups` is read from the mailbox on the device: the host does not know it yet when these kernels are enqueued.  The grid is fixed
 // (BG_GRID workgroups); every workgroup takes a contiguous stretch of tiles of groups, so that `part` has BG_GRID entries whatever n.
 constexpr int BG_GRID = 1024;
 __device__ __forceinline__ void big_stretch(size_t groups, size_t *t0, size_t *t1) {
@@ -884,10 +882,10 @@ __device__ __forceinline__ void big_stretch(size_t groups, size_t *t0, size_t *t
     *t0 = static_cast<size_t>(blockIdx.x) * per;
     *t1 = *t0 + per < ntiles ? *t0 + per : ntiles;
 }
-__global__ __launch_bounds__(256) void k_big_reduce(const uint32_t *__restrict__ gstart, const uint32_t *__restrict__ mail,
+__global__ __launch_bounds__(256) void k_big_reduce(const uint32_t *__restrict__ gstart, Mail::Rounds *__restrict__ mail,
                                                      uint2 *__restrict__ part, uint32_t ls_max) {
     __shared__ uint32_t s_w[2][RR_WAVES];
-    const size_t groups = mail[1];
+    const size_t groups = mail->groups;
     size_t t0, t1;
     big_stretch(groups, &t0, &t1);
     uint32_t sum = 0, cnt = 0, medium = 0;
@@ -909,28 +907,28 @@ __global__ __launch_bounds__(256) void k_big_reduce(const uint32_t *__restrict__
     cnt = wave_sum(cnt);
     medium = wave_sum(medium);
     if ((threadIdx.x & 63) == 0) { s_w[0][threadIdx.x >> 6] = sum; s_w[1][threadIdx.x >> 6] = cnt; }
-    if ((threadIdx.x & 63) == 0 && medium) atomicAdd(const_cast<uint32_t *>(mail) + 3, medium);
+    if ((threadIdx.x & 63) == 0 && medium) atomicAdd(&mail->above_pl_slots, medium);
     __syncthreads();
     if (threadIdx.x == 0) part[blockIdx.x] = make_uint2(s_w[0][0] + s_w[0][1] + s_w[0][2] + s_w[0][3], s_w[1][0] + s_w[1][1] + s_w[1][2] + s_w[1][3]);
 }
-__global__ __launch_bounds__(BG_GRID) void k_big_spine(uint2 *__restrict__ part, uint32_t *__restrict__ mail) {
+__global__ __launch_bounds__(BG_GRID) void k_big_spine(uint2 *__restrict__ part, Mail::Rounds *__restrict__ mail) {
     __shared__ uint32_t s_tmp[16 + 1];
     const uint2 v = part[threadIdx.x];
     uint32_t total, total_cnt;
     const uint32_t run = block_excl_sum<BG_GRID / 64>(v.x, s_tmp, &total);
     const uint32_t run_cnt = block_excl_sum<BG_GRID / 64>(v.y, s_tmp, &total_cnt);
     part[threadIdx.x] = make_uint2(run, run_cnt);
-    if (threadIdx.x == 0) { mail[2] = total; mail[4] = total_cnt; }
+    if (threadIdx.x == 0) { mail->big_slots = total; mail->big_groups = total_cnt; }
 }
-__global__ __launch_bounds__(256) void k_big_apply(const uint32_t *__restrict__ gstart, const uint32_t *__restrict__ mail,
+__global__ __launch_bounds__(256) void k_big_apply(const uint32_t *__restrict__ gstart, const Mail::Rounds *__restrict__ mail,
                                                     const uint2 *__restrict__ part, uint32_t *__restrict__ bigidx, uint32_t *__restrict__ bigoff,
                                                     uint32_t ls_max) {
     __shared__ uint32_t s_tmp[RR_WAVES + 1];
-    const size_t groups = mail[1];
+    const size_t groups = mail->groups;
     size_t t0, t1;
     big_stretch(groups, &t0, &t1);
     uint2 base = part[blockIdx.x];
-    if (base.x == (blockIdx.x + 1 < gridDim.x ? part[blockIdx.x + 1].x : mail[2])) return;  // no big group in this stretch
+    if (base.x == (blockIdx.x + 1 < gridDim.x ? part[blockIdx.x + 1].x : mail->big_slots)) return;  // no big group in this stretch
     for (size_t t = t0; t < t1; ++t) {
         const size_t g0 = t * BG_TILE + static_cast<size_t>(threadIdx.x) * BG_IPT;
         uint32_t v[BG_IPT], sum = 0, cnt = 0;
@@ -1567,21 +1565,22 @@ int classify_and_read(dk_ctx *ctx, size_t max_groups, uint32_t *gstart, uint32_t
     (void)max_groups;
     uint2 *part = ctx->ws_alloc<uint2>(BG_GRID);
     if (!part) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemsetAsync(ctx->d_mail + 3, 0, sizeof(uint32_t), st));
+    Mail::Rounds *d_rounds = &ctx->d_mail->cls.rounds;
+    DK_TRY(ctx->mail_fill(&d_rounds->above_pl_slots, 0));
     {
         LaunchScope ls(ctx, K_BIG_CLASSIFY, 8.0 * max_groups);
-        k_big_reduce<<<dim3(BG_GRID), dim3(256), 0, st>>>(gstart, ctx->d_mail, part, ls_max);
-        k_big_spine<<<dim3(1), dim3(BG_GRID), 0, st>>>(part, ctx->d_mail);
-        k_big_apply<<<dim3(BG_GRID), dim3(256), 0, st>>>(gstart, ctx->d_mail, part, bigidx, bigoff, ls_max);
+        k_big_reduce<<<dim3(BG_GRID), dim3(256), 0, st>>>(gstart, d_rounds, part, ls_max);
+        k_big_spine<<<dim3(1), dim3(BG_GRID), 0, st>>>(part, d_rounds);
+        k_big_apply<<<dim3(BG_GRID), dim3(256), 0, st>>>(gstart, d_rounds, part, bigidx, bigoff, ls_max);
     }
     DK_HIP(ctx, hipGetLastError());
-    DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail, ctx->d_mail, 5 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipStreamSynchronize(st));
-    *active = ctx->h_mail[0];
-    *groups = ctx->h_mail[1];
-    *nbig = ctx->h_mail[2];
-    *nmedium = ctx->h_mail[3];
-    *nbiggroups = ctx->h_mail[4];
+    const Mail::Rounds &r = ctx->h_mail->cls.rounds;
+    DK_TRY(ctx->mail_read(&ctx->h_mail->cls.rounds));
+    *active = r.active;
+    *groups = r.groups;
+    *nbig = r.big_slots;
+    *nmedium = r.above_pl_slots;
+    *nbiggroups = r.big_groups;
     ctx->ws_release(mark);
     return DK_OK;
 }
@@ -1610,28 +1609,28 @@ int suffix_array_impl(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d_
     const size_t mark = ctx->ws_mark();
 
     // 1. alphabet
-    uint32_t *d_hist = ctx->d_mail + 16;
-    DK_HIP(ctx, hipMemsetAsync(d_hist, 0, 266 * sizeof(uint32_t), st));  // (+ the run probe's two words and the period probe's eight behind the 256 counters)
+    Mail::Alphabet *d_alpha = &ctx->d_mail->alphabet;
+    const Mail::Alphabet &alpha = ctx->h_mail->alphabet;  // the host's copy: read until the end of the sort
+    DK_TRY(ctx->mail_fill(d_alpha, 0));  // (the histogram, the run probe's words and the period probe's)
     const int period_mode = DK_KNOB("DK_PERIOD", 1);  // 0 = never a period round, 1 = where the probe finds an eighth of the block periodic, 2 = wherever it finds a window (test hook)
     {
         LaunchScope ls(ctx, K_SYM_HIST, 1.0 * n);
         const size_t blocks = std::min<size_t>(div_up(n, 256 * 64), 2048);
-        k_sym_hist<<<dim3(blocks), dim3(256), 0, st>>>(d_text, n, d_hist);
-        if (d_bwt && allow_lfirst && n >= (1u << 16)) k_run_probe<<<dim3(div_up(div_up(n, 256), 256)), dim3(256), 0, st>>>(d_text, n, d_hist + 256);
-        if (period_mode != 0 && n >= (1u << 12)) k_period_probe<<<dim3(div_up(div_up(n, 64), 256)), dim3(256), 0, st>>>(d_text, n, d_hist + 258);
+        k_sym_hist<<<dim3(blocks), dim3(256), 0, st>>>(d_text, n, d_alpha->hist);
+        if (d_bwt && allow_lfirst && n >= (1u << 16)) k_run_probe<<<dim3(div_up(div_up(n, 256), 256)), dim3(256), 0, st>>>(d_text, n, d_alpha->run_probe);
+        if (period_mode != 0 && n >= (1u << 12)) k_period_probe<<<dim3(div_up(div_up(n, 64), 256)), dim3(256), 0, st>>>(d_text, n, d_alpha->period_probe);
     }
-    DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 16, d_hist, 266 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipStreamSynchronize(st));
+    DK_TRY(ctx->mail_read(&ctx->h_mail->alphabet));
     // a run of 511 bytes, or more than 1 % of the block's 16-byte pieces inside runs: not the L-first path's kind of block
-    const bool long_run = ctx->h_mail[16 + 256] != 0 || static_cast<double>(ctx->h_mail[16 + 257]) * 16.0 > 0.01 * static_cast<double>(n);
+    const bool long_run = alpha.run_probe[0] != 0 || static_cast<double>(alpha.run_probe[1]) * 16.0 > 0.01 * static_cast<double>(n);
     // ... but a block with a few long runs and next to nothing else inside runs (a zero-padded header in front of text) stays with it: the run's
     // suffixes ride in the big list until the round stalls, and one token round (k_lf_tokens) places them by where the run ends
-    const bool run_heavy = static_cast<double>(ctx->h_mail[16 + 257]) * 16.0 > 0.01 * static_cast<double>(n);
+    const bool run_heavy = static_cast<double>(alpha.run_probe[1]) * 16.0 > 0.01 * static_cast<double>(n);
     uint8_t code[256];
     unsigned sigma = 0;
     for (int s = 0; s < 256; ++s) {
         code[s] = static_cast<uint8_t>(sigma);
-        if (ctx->h_mail[16 + s]) ++sigma;
+        if (alpha.hist[s]) ++sigma;
     }
     if (sigma <= 1) {  // one distinct symbol: suffixes sort by length
         k_sa_descending<<<dim3(div_up(n, 256)), dim3(256), 0, st>>>(d_sa, n);
@@ -1649,11 +1648,11 @@ int suffix_array_impl(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d_
     uint32_t *gid = ctx->ws_alloc<uint32_t>(n), *gid_alt = ctx->ws_alloc<uint32_t>(n);
     uint32_t *gstart = ctx->ws_alloc<uint32_t>(n / 2 + 2), *bigidx = ctx->ws_alloc<uint32_t>(n / 2 + 2);
     uint32_t *bigoff = ctx->ws_alloc<uint32_t>(n / 32 + 2);  // one entry per big group (more than LS_MAX members each; the L-first path may draw the line at 32)
-    uint8_t *d_code = reinterpret_cast<uint8_t *>(ctx->d_mail + 512);
+    uint8_t *d_code = ctx->d_mail->code;
     if (!keys || !keys_alt || !keys_3 || !vals || !vals_alt || !vals_3 || !rank || !pos || !pos_alt || !gid || !gid_alt ||
         !gstart || !bigidx || !bigoff)
         return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(d_code, code, 256, hipMemcpyHostToDevice, st));
+    DK_HIP(ctx, hipMemcpyAsync(d_code, code, sizeof code, hipMemcpyHostToDevice, st));
     const bool trace = DK_KNOB("DK_TRACE", 0) != 0;
 
     // 2. how long a prefix must the initial sort cover?  DK_PREFIX: 0 = always the full key, 1 = ask the sample (default),
@@ -1676,30 +1675,29 @@ int suffix_array_impl(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d_
             uint32_t table_size = 1;
             while (table_size < 2u * cands.count * m) table_size <<= 1;
             uint64_t *table = keys_3;  // free until the first big-group sort
-            uint32_t *d_dups = ctx->d_mail + 300;
+            uint32_t *d_dups = ctx->d_mail->dups;
+            const uint32_t *dups = ctx->h_mail->dups;
             DK_HIP(ctx, hipMemsetAsync(table, 0xFF, static_cast<size_t>(table_size) * sizeof(uint64_t), st));
-            DK_HIP(ctx, hipMemsetAsync(d_dups, 0, PP_MAX_CAND * sizeof(uint32_t), st));
+            DK_TRY(ctx->mail_fill(&ctx->d_mail->dups, 0));
             {
                 LaunchScope ls(ctx, K_PREFIX_PROBE, 16.0 * m);
                 k_prefix_probe<<<dim3(div_up(m, 256)), dim3(256), 0, st>>>(d_text, n, d_code, bits, spk, m, span, cands, table, table_size - 1,
                                                                           d_dups);
             }
             DK_HIP(ctx, hipGetLastError());
-            DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 300, d_dups, PP_MAX_CAND * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            DK_HIP(ctx, hipStreamSynchronize(st));
+            DK_TRY(ctx->mail_read(&ctx->h_mail->dups));
             // m is 10 sqrt(n), so c equal pairs in the sample say that about c / 50 of ALL suffixes share their prefix with another one.
             // A radix pass over everything costs what a text round costs for about an eighth of it: up to 4 equal pairs (8 %) the
             // shorter prefix wins, its survivors go through the text round
             const uint32_t max_dups = static_cast<uint32_t>(DK_KNOB("DK_PROBE_DUPS", 4));
             for (int c = 0; c < cands.count; ++c)
-                if (ctx->h_mail[300 + c] <= max_dups) { spk_sort = cands.sym[c]; break; }
+                if (dups[c] <= max_dups) { spk_sort = cands.sym[c]; break; }
             // the deepest candidate is (about) the key of the initial sort: a sample of 10 sqrt(n) suffixes meets an equal one there about as
             // often as a suffix sits in a group of more than sqrt(n) / 10 members -- the share of the big groups
-            probe_big_share = static_cast<double>(ctx->h_mail[300 + cands.count - 1]) / m;
+            probe_big_share = static_cast<double>(dups[cands.count - 1]) / m;
             if (trace)
                 fprintf(stderr, "[dk] prefix probe: %u samples, equal pairs at %d/%d/%d/%d symbols: %u %u %u %u -> sort %d of %d symbols\n", m,
-                        cands.sym[0], cands.sym[1], cands.sym[2], cands.sym[3], ctx->h_mail[300], ctx->h_mail[301], ctx->h_mail[302],
-                        ctx->h_mail[303], spk_sort, spk);
+                        cands.sym[0], cands.sym[1], cands.sym[2], cands.sym[3], dups[0], dups[1], dups[2], dups[3], spk_sort, spk);
         }
     }
     // BWT on the way (BwtCarry): callers that want L.  The key gives up its low byte to the code of the symbol in front of the suffix, so
@@ -1711,7 +1709,7 @@ int suffix_array_impl(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d_
     // needs no more of the initial sort than the period string itself: the period round (4b) places every suffix of a stretch whatever the
     // depth, as long as the depth covers p symbols -- one or two passes instead of seven (a^n b, 1e8 bytes: 15.1 -> 7 ms).
     if (period_mode != 0 && n >= (1u << 16)) {
-        const uint32_t *pc = ctx->h_mail + 16 + 258;
+        const uint32_t *pc = alpha.period_probe;
         uint32_t cmax = 0;
         for (int q = 1; q <= 8; ++q) cmax = std::max(cmax, pc[q - 1]);
         if (static_cast<uint64_t>(cmax) * 64 * 10 >= static_cast<uint64_t>(n) * 9) {
@@ -1728,20 +1726,20 @@ int suffix_array_impl(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d_
     const bool short_prefix = spk_sort < spk;  // the probe's verdict: few suffixes will survive the initial sort
     if (carry_bwt) spk_sort = std::min(spk_sort, 56 / bits);  // (a key merely shortened to make room for the carried byte keeps the rank path)
     uint8_t *sym = nullptr, *sym_alt = nullptr;
-    uint8_t *d_inv = reinterpret_cast<uint8_t *>(ctx->d_mail + 576);
+    uint8_t *d_inv = ctx->d_mail->inv;
     if (carry_bwt) {
         sym = ctx->ws_alloc<uint8_t>(n);
         sym_alt = ctx->ws_alloc<uint8_t>(n);
         if (!sym || !sym_alt) return DK_E_NOMEM;
         uint8_t inv[256] = {0};
         for (int c = 255; c >= 0; --c)
-            if (ctx->h_mail[16 + c]) inv[code[c]] = static_cast<uint8_t>(c);
-        std::memcpy(ctx->h_mail + 576, inv, 256);
-        DK_HIP(ctx, hipMemcpyAsync(d_inv, ctx->h_mail + 576, 256, hipMemcpyHostToDevice, st));
+            if (alpha.hist[c]) inv[code[c]] = static_cast<uint8_t>(c);
+        std::memcpy(ctx->h_mail->inv, inv, sizeof inv);
+        DK_HIP(ctx, hipMemcpyAsync(d_inv, ctx->h_mail->inv, sizeof inv, hipMemcpyHostToDevice, st));
     }
     const int key_shift = carry_bwt ? 8 : 0;
     const bool narrow_keys = DK_KNOB("DK_NARROW_KEYS", 1) != 0 && bits * spk_sort <= 40;
-    uint32_t *d_starts = ctx->d_mail + 720;  // 256 words
+    uint32_t *d_starts = ctx->d_mail->narrow_starts;
 
     // 3. initial sort; its first pass builds the keys from the text (no key array is ever written unsorted)
     {
@@ -1768,7 +1766,7 @@ int suffix_array_impl(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d_
     // the block's dominant short period, if it has any periodic 64-byte window at all (k_period_probe): the smallest p with nearly the most windows
     int lf_period = 0;
     if (period_mode != 0) {
-        const uint32_t *pc = ctx->h_mail + 16 + 258;
+        const uint32_t *pc = alpha.period_probe;
         uint32_t cmax = 0;
         for (int q = 1; q <= 7; ++q) cmax = std::max(cmax, pc[q - 1]);
         for (int q = 1; q <= 7 && cmax > 0 && !lf_period; ++q)
@@ -1776,7 +1774,7 @@ int suffix_array_impl(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d_
     }
     // with tokens to settle them in one round (lfirst.inc: LfTokens), runs may hold up to a twentieth of the block (50 MB of real text -- indentation,
     // rulers -- 1.3 %: 10.9 ms this way against 12.7; 5 MB of 90 % zero bytes, 24 %, stay with prefix doubling); without, a hundredth and no long run
-    const bool lf_runs_ok = lf_period > 0 ? static_cast<double>(ctx->h_mail[16 + 257]) * 16.0 <= 0.05 * static_cast<double>(n) : !long_run;
+    const bool lf_runs_ok = lf_period > 0 ? static_cast<double>(alpha.run_probe[1]) * 16.0 <= 0.05 * static_cast<double>(n) : !long_run;
     (void)run_heavy;
     if (carry_bwt && allow_lfirst && lf_mode != 0 && n >= 64 && (lf_mode == 2 || (n >= (1u << 16) && probe_big_share <= 0.6 && !short_prefix && lf_runs_ok))) {
         // (the arena of the deep groups: the second list buffers of the suffix-array path, which this path does not use, and the upper half of the
@@ -1791,9 +1789,9 @@ int suffix_array_impl(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d_
         // (the initial keys are read by the first rerank only: their buffer holds the next-break positions of a token round later)
         // tokens in the first round (instead of after the first stalled one) where a thousandth of the block lies inside runs of one byte value or in
         // periodic 64-byte windows: indentation and rulers in real text
-        const uint32_t *pc = ctx->h_mail + 16 + 258;
+        const uint32_t *pc = alpha.period_probe;
         const bool tokens_early = lf_period > 0 && DK_KNOB("DK_LF_TOKENS_EARLY", 1) != 0 &&
-                                  (static_cast<double>(ctx->h_mail[16 + 257]) * 16.0 > 0.001 * static_cast<double>(n) || static_cast<double>(pc[lf_period - 1]) * 64.0 > 0.001 * static_cast<double>(n));
+                                  (static_cast<double>(alpha.run_probe[1]) * 16.0 > 0.001 * static_cast<double>(n) || static_cast<double>(pc[lf_period - 1]) * 64.0 > 0.001 * static_cast<double>(n));
         DK_TRY(lfirst_path(ctx, d_text, n, keys, key_shift, narrow_keys ? d_starts : nullptr, d_sa, d_bwt, d_origin, b, static_cast<uint32_t>(spk_sort), trace, lf_mode == 2, &done, &pristine,
                            nullptr, lf_period, reinterpret_cast<uint32_t *>(keys), tokens_early));
         if (done) {
@@ -1947,7 +1945,7 @@ int suffix_array_impl(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d_
     //     next-break positions (it is built later).
     bool small_period_round = false;
     if (active > 0 && period_mode != 0) {
-        const uint32_t *pc = ctx->h_mail + 16 + 258;
+        const uint32_t *pc = alpha.period_probe;
         const int pmax = static_cast<int>(std::min<uint64_t>(8, h));
         uint32_t cmax = 0;
         for (int q = 1; q <= pmax; ++q) cmax = std::max(cmax, pc[q - 1]);
@@ -2017,36 +2015,36 @@ int suffix_array_impl(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d_
     //      soon as the depth covers it: period 1000 x 8000 (8 MB) 21 -> 9 rounds.
     uint32_t long_period = 0;
     if (period_mode != 0 && !small_period_round && active > 0 && nbig * 2 > active && n >= (1u << 16)) {
-        uint32_t *d_found = ctx->d_mail + 320;  // PS_SAMPLES words + 1 counter (words 300 .. 304 are the prefix probe's)
+        uint32_t *d_found = ctx->d_mail->found, *d_windows = &ctx->d_mail->found_windows;
+        const uint32_t *found = ctx->h_mail->found;
         const uint32_t pmax = static_cast<uint32_t>(std::min<uint64_t>(PS_MAX, n / 4));
-        DK_HIP(ctx, hipMemsetAsync(d_found, 0xFF, PS_SAMPLES * sizeof(uint32_t), st));
-        DK_HIP(ctx, hipMemsetAsync(d_found + PS_SAMPLES, 0, sizeof(uint32_t), st));
+        DK_TRY(ctx->mail_fill(&ctx->d_mail->found, 0xFF));
+        DK_TRY(ctx->mail_fill(d_windows, 0));
         {
             LaunchScope ls(ctx, K_PERIOD, 0.0);
             k_period_search<<<dim3(PS_SAMPLES), dim3(256), 0, st>>>(d_text, n, pmax, d_found);
         }
-        DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 320, d_found, PS_SAMPLES * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        DK_HIP(ctx, hipStreamSynchronize(st));
+        DK_TRY(ctx->mail_read(&ctx->h_mail->found));
         uint32_t best = 0, best_votes = 0;  // the period most samples agree on
         for (int a = 0; a < PS_SAMPLES; ++a) {
-            const uint32_t v = ctx->h_mail[320 + a];
+            const uint32_t v = found[a];
             if (v == 0xFFFFFFFFu) continue;
             uint32_t votes = 0;
-            for (int b2 = 0; b2 < PS_SAMPLES; ++b2) votes += ctx->h_mail[320 + b2] == v ? 1u : 0u;
+            for (int b2 = 0; b2 < PS_SAMPLES; ++b2) votes += found[b2] == v ? 1u : 0u;
             if (votes > best_votes || (votes == best_votes && v < best)) { best = v; best_votes = votes; }
         }
         if (best_votes >= PS_SAMPLES / 4) {
             {
                 LaunchScope ls(ctx, K_PERIOD, 2.0 * n);
-                k_period_count<<<dim3(div_up(div_up(n, 64), 256)), dim3(256), 0, st>>>(d_text, n, best, d_found + PS_SAMPLES);
+                k_period_count<<<dim3(div_up(div_up(n, 64), 256)), dim3(256), 0, st>>>(d_text, n, best, d_windows);
             }
-            DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 320 + PS_SAMPLES, d_found + PS_SAMPLES, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            DK_HIP(ctx, hipStreamSynchronize(st));
+            DK_TRY(ctx->mail_read(&ctx->h_mail->found_windows));
+            const uint32_t windows = ctx->h_mail->found_windows;
             // three quarters of the block: a Fibonacci word follows "period 55" in 47 % of its windows, in stretches of a few hundred symbols that one
             // round on their ends does not settle (6.35 against 5.71 ms at 4 MB)
-            if (static_cast<uint64_t>(ctx->h_mail[320 + PS_SAMPLES]) * 64 * 4 >= static_cast<uint64_t>(n) * 3) long_period = best;
+            if (static_cast<uint64_t>(windows) * 64 * 4 >= static_cast<uint64_t>(n) * 3) long_period = best;
             if (trace)
-                fprintf(stderr, "[dk] long period: %u of %d samples say %u, %u of %zu windows follow it -> %s\n", best_votes, PS_SAMPLES, best, ctx->h_mail[320 + PS_SAMPLES], n / 64,
+                fprintf(stderr, "[dk] long period: %u of %d samples say %u, %u of %zu windows follow it -> %s\n", best_votes, PS_SAMPLES, best, windows, n / 64,
                         long_period ? "a period round once the depth covers it" : "not used");
         }
     }
@@ -2087,7 +2085,8 @@ int suffix_array_impl(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d_
         uint32_t *idx_a = vals, *idx_b = vals_alt;
         uint32_t *meta_a = gid, *meta_b = gid_alt;
         uint8_t *sym_a = sym, *sym_b = sym_alt;
-        uint32_t *d_live = ctx->d_mail + 700, *h_live = ctx->h_mail + 700;  // ring of 8 counters
+        uint32_t *d_live = ctx->d_mail->live_ring, *h_live = ctx->h_mail->live_ring;  // ring of LIVE_RING counters
+        constexpr unsigned RING = LIVE_RING - 1u;
         {
             LaunchScope ls(ctx, K_PLATEAU_RANKS, 14.0 * slots);
             k_to_inplace<<<dim3(div_up(slots, 256)), dim3(256), 0, st>>>(gid, gstart, slots, meta_b);
@@ -2103,19 +2102,19 @@ int suffix_array_impl(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d_
             const int kmax = std::min(CH_K, std::max(2, DK_KNOB("DK_CHAIN_GROUP", CH_K)));
             const int lbits = static_cast<int>(ceil_log2_u64(n));
             const uint32_t cap = static_cast<uint32_t>(std::min<size_t>(n, 0xFFFFFFF0u));  // records the buffers hold (n each); what does not fit stays with the rounds
-            uint32_t *d_cnt = ctx->d_mail + 12;  // [0] records, [1] first reservation that did not fit
-            DK_HIP(ctx, hipMemsetAsync(d_cnt, 0, sizeof(uint32_t), st));
-            DK_HIP(ctx, hipMemsetAsync(d_cnt + 1, 0xFF, sizeof(uint32_t), st));
+            uint32_t *d_cnt = ctx->d_mail->chain_cnt;  // [0] records, [1] first reservation that did not fit
+            const uint32_t *cnt = ctx->h_mail->chain_cnt;
+            DK_TRY(ctx->mail_fill(&d_cnt[0], 0));
+            DK_TRY(ctx->mail_fill(&d_cnt[1], 0xFF));
             DK_HIP(ctx, hipMemsetAsync(planes, 0, static_cast<size_t>(kmax - 1) * slots, st));
             {
                 LaunchScope ls(ctx, K_CHAIN, 16.0 * slots);
                 k_chain_extract<<<dim3(div_up(slots, 256 * CH_EXTRACT)), dim3(256), 0, st>>>(idx_a, meta_a, slots, kmax, lbits, rec_key, rec_slot, cap, d_cnt);
             }
             DK_HIP(ctx, hipGetLastError());
-            DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 12, d_cnt, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            DK_HIP(ctx, hipStreamSynchronize(st));
-            const uint32_t m = std::min(ctx->h_mail[12], ctx->h_mail[13]);
-            if (trace) fprintf(stderr, "[dk] pair chains: %u pairs inside groups of 2..%d among %zu slots%s (h = %llu)\n", m, kmax, slots, ctx->h_mail[13] != 0xFFFFFFFFu ? " (list full)" : "",
+            DK_TRY(ctx->mail_read(&ctx->h_mail->chain_cnt));
+            const uint32_t m = std::min(cnt[0], cnt[1]);
+            if (trace) fprintf(stderr, "[dk] pair chains: %u pairs inside groups of 2..%d among %zu slots%s (h = %llu)\n", m, kmax, slots, cnt[1] != 0xFFFFFFFFu ? " (list full)" : "",
                                static_cast<unsigned long long>(h));
             if (m > 0) {
                 route |= DK_ROUTE_PAIR_CHAINS;
@@ -2144,9 +2143,8 @@ int suffix_array_impl(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d_
                     k_plateau_scan<<<dim3(1), dim3(1024), 0, st>>>(tile_live, ltiles, d_cnt);
                 }
                 DK_HIP(ctx, hipGetLastError());
-                DK_HIP(ctx, hipMemcpyAsync(ctx->h_mail + 12, d_cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-                DK_HIP(ctx, hipStreamSynchronize(st));
-                settled_by_chains = slots - ctx->h_mail[12];
+                DK_TRY(ctx->mail_read(&ctx->h_mail->chain_cnt[0]));
+                settled_by_chains = slots - cnt[0];
                 if (trace) fprintf(stderr, "[dk] pair chains settled %zu of %zu slots\n", settled_by_chains, slots);
                 ctx->ws_release(mark2);
             }
@@ -2165,8 +2163,7 @@ int suffix_array_impl(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d_
                 k_plateau_compact<<<dim3(ntiles), dim3(RR_BLOCK), 0, st>>>(idx_a, meta_a, sym_a, pos, slots, tile_live, idx_b, meta_b, sym_b, pos_alt);
             }
             DK_HIP(ctx, hipGetLastError());
-            DK_HIP(ctx, hipMemcpyAsync(h_live, d_live, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            DK_HIP(ctx, hipStreamSynchronize(st));
+            DK_TRY(ctx->mail_read(&h_live[0]));
             if (h_live[0] != live) return ctx->fail(DK_E_INTERNAL, "suffix_array: live count %u after compaction, expected %zu", h_live[0], live);
             ctx->ws_release(mark2);
             std::swap(idx_a, idx_b);
@@ -2179,22 +2176,22 @@ int suffix_array_impl(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d_
         };
         auto launch_round = [&]() -> int {
             const uint32_t h_eff = static_cast<uint32_t>(std::min<uint64_t>(h, n));
-            uint32_t *cnt = d_live + (launched & 7u);
-            DK_HIP(ctx, hipMemsetAsync(cnt, 0, sizeof(uint32_t), st));
+            uint32_t *cnt = d_live + (launched & RING);
+            DK_TRY(ctx->mail_fill(cnt, 0));
             {
                 LaunchScope ls(ctx, K_PLATEAU_SORT, 6.0 * slots + 4.0 * live + 10.0 * live);
                 k_plateau_sort<<<dim3(div_up(slots, LS_TILE)), dim3(LS_BLOCK), 0, st>>>(idx_a, meta_a, sym_a, pos, rank, static_cast<uint32_t>(n), h_eff,
                                                                                       slots, idx_b, meta_b, sym_b, carry_bwt ? nullptr : d_sa, d_bwt, d_origin, cnt,
-                                                                                      launched ? d_live + ((launched - 1) & 7u) : nullptr);
+                                                                                      launched ? d_live + ((launched - 1) & RING) : nullptr);
             }
             {
                 LaunchScope ls(ctx, K_PLATEAU_RANKS, 6.0 * slots);
                 k_plateau_ranks<<<dim3(div_up(slots, 256)), dim3(256), 0, st>>>(idx_b, meta_b, pos, slots, rank,
-                                                                                launched ? d_live + ((launched - 1) & 7u) : nullptr);
+                                                                                launched ? d_live + ((launched - 1) & RING) : nullptr);
             }
             DK_HIP(ctx, hipGetLastError());
-            DK_HIP(ctx, hipMemcpyAsync(h_live + (launched & 7u), cnt, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            DK_HIP(ctx, hipEventRecord(ctx->round_ev[launched & 7u], st));
+            DK_TRY(ctx->mail_fetch(&h_live[launched & RING]));
+            DK_HIP(ctx, hipEventRecord(ctx->round_ev[launched & RING], st));
             std::swap(idx_a, idx_b);
             std::swap(meta_a, meta_b);
             std::swap(sym_a, sym_b);
@@ -2203,9 +2200,9 @@ int suffix_array_impl(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d_
             return DK_OK;
         };
         auto read_round = [&]() -> int {  // the oldest round in flight: how many slots did it leave alive?
-            DK_HIP(ctx, hipEventSynchronize(ctx->round_ev[read & 7u]));
+            DK_HIP(ctx, hipEventSynchronize(ctx->round_ev[read & RING]));
             const size_t before = live;
-            live = h_live[read & 7u];
+            live = h_live[read & RING];
             ++read;
             ctx->stats.rounds += 1;
             if (trace) fprintf(stderr, "[dk] round %u (in place) slots=%zu live %zu -> %zu\n", ctx->stats.rounds - 1, slots, before, live);

@@ -1510,8 +1510,7 @@ __global__ __launch_bounds__(256) void k_cls_apply(const uint32_t *__restrict__ 
 constexpr uint32_t LF_MEDIUM_MAX = 8192;  // largest group sort_groups takes
 // classification into (giant: above LF_MEDIUM_MAX | medium: above `lo`, at most LF_MEDIUM_MAX) and the read-back; the list offsets of both classes
 // go to bigoff (giant groups first), a group's dense index over both classes to bigidx
-int classify_two_and_read(dk_ctx *ctx, const uint32_t *gstart, uint32_t *bigidx, uint32_t *bigoff, uint32_t lo, size_t *active, size_t *groups, size_t *ngiant,
-                          size_t *ngiantgroups, size_t *nmedium, size_t *nmediumgroups) {
+int classify_two_and_read(dk_ctx *ctx, const uint32_t *gstart, uint32_t *bigidx, uint32_t *bigoff, uint32_t lo, GroupCounts *out) {
     hipStream_t st = ctx->stream;
     const size_t mark = ctx->ws_mark();
     uint4 *part = ctx->ws_alloc<uint4>(BG_GRID);
@@ -1526,12 +1525,10 @@ int classify_two_and_read(dk_ctx *ctx, const uint32_t *gstart, uint32_t *bigidx,
     DK_HIP(ctx, hipGetLastError());
     const Mail::Classes &c = ctx->h_mail->cls;
     DK_TRY(ctx->mail_read(&ctx->h_mail->cls));
-    *active = c.rounds.active;
-    *groups = c.rounds.groups;
-    *ngiant = c.rounds.big_slots;
-    *ngiantgroups = c.rounds.big_groups;
-    *nmedium = c.medium_slots;
-    *nmediumgroups = c.medium_groups;
+    *out = GroupCounts{};
+    out->active = c.rounds.active, out->groups = c.rounds.groups;
+    out->giant = c.rounds.big_slots, out->giant_groups = c.rounds.big_groups, out->medium = c.medium_slots, out->medium_groups = c.medium_groups;
+    out->big = out->giant + out->medium, out->big_groups = out->giant_groups + out->medium_groups;
     ctx->ws_release(mark);
     return DK_OK;
 }
@@ -1562,309 +1559,370 @@ constexpr uint32_t LF_AVG_BIG = 1u << 18;  // big groups of more than this many 
 // A limit as the kernels and the host compare against it: the tuning build may lower it (test hooks, DK_KNOB), clamped to [0, hi]
 inline uint32_t lf_limit(int knob, uint32_t hi) { return knob <= 0 ? 0u : std::min(static_cast<uint32_t>(knob), hi); }
 
-// -> *done: L and the origin are complete; otherwise the caller takes the suffix-array path from the start (nothing it needs was touched
-// but scratch buffers; L and the origin word are rewritten by it)
-// from != nullptr: the path takes over in the middle of the suffix-array path -- its active list (every group of more than one member, equal in
-// its first h0 symbols) is filtered down to the live groups (keys = the list's group ids) instead of the first rerank
-struct LfFrom { const uint32_t *idx, *pos, *gid; uint8_t *sym; size_t count; };
-int lfirst_path(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uint64_t *init_keys, int key_shift, const uint32_t *narrow_starts, const uint32_t *d_sa,
-                uint8_t *d_bwt, uint32_t *d_origin, LfBuffers b, uint32_t h0, bool trace, bool force, bool *done, bool *pristine, const LfFrom *from = nullptr, int period = 0,
-                uint32_t *next_break = nullptr, bool tokens_early = false) {
-    *done = false;
-    *pristine = true;  // nothing the suffix-array path reads (sorted keys, SA, L, origin) has been written yet
-    hipStream_t st = ctx->stream;
+// Where the path starts from.  Either behind the initial sort (list == nullptr): its sorted keys with the shift of their compared bits, the bucket
+// starts when the keys are narrow, and the suffix array the sort's last pass wrote.  Or taking over in the middle of the suffix-array path: its
+// active list (every group of more than one member, equal in its first h0 symbols) is filtered down to the live groups (keys = the list's group
+// ids) instead of the first rerank
+struct LfFrom {
+    const uint64_t *init_keys = nullptr; int key_shift = 0; const uint32_t *narrow_starts = nullptr, *d_sa = nullptr;  // behind the initial sort
+    const uint32_t *idx = nullptr, *pos = nullptr, *gid = nullptr; uint8_t *sym = nullptr; size_t count = 0;          // a list handed over (idx != nullptr)
+    uint32_t h0 = 0;  // symbols every group is known to be equal in
+};
+// Tokens (LfTokens): once, when the block has a dominant short period (period > 0: the probe saw at least one 64-byte window of it) and the caller
+// has room for the next-break positions (next_break: n words) -- in the first round when the probes saw runs or periodic windows worth it
+// (tokens_early: real text with its indentation and rulers; the groups inside runs are the biggest and the slowest to split on text, 17 rounds
+// instead of 9 on 50 MB of it), else in the round after the first stalled one.  A round with tokens is a text round for every group that is not periodic.
+struct LfTokenPlan { int period = 0; uint32_t *next_break = nullptr; bool tokens_early = false; };
+
+// One run of the path: what its rounds and the passes at the end share
+struct LfRun {
+    dk_ctx *ctx; hipStream_t st; const uint8_t *d_text; size_t n; uint8_t *d_bwt; uint32_t *d_origin; LfTokenPlan plan; bool trace;
+    LfBuffers b;  // (k0 / k1, v0 / v1 are swapped by the big list's sorts)
+    size_t mark;  // of the workspace, released on every way out but an error's
+    // lf_setup: the limits past which the path gives up, the knobs of its kernels, and its lists.  ls_max: groups above go the global way
+    uint32_t deep_cap, giant_cap, giant_arena, ls_max, refork_groups;
+    int giant_rounds, max_rounds, max_steps, stuck_steps, short_steps, medium_steps;
+    size_t short_slots, tail_slots, fork_slots;
+    bool two_classes, by_wave;
+    LfDeepGroup *deep;
+    LfArena arena;
+    LfGiantOut giant[2];  // giant list (subgroups whose common extension is longer than a workgroup measures): two sets, one being read, one being filled
+    uint32_t *lce_res;    // per member of the listed subgroups
+    // progress
+    GroupCounts c;       // of the active list: big = above big_min
+    uint32_t h;          // depth of the groups that were not periodic
+    int stalled;         // global-sort rounds in a row that left nearly all of their slots in big groups (runs of one symbol, periodic stretches)
+    uint32_t big_min;    // groups above this go through the global sort; after a stalled round, or once the big list is short: LF_DEEP_MAX, what the deep list takes
+    int ebits;
+    bool tokens_done, want_tokens;
+    bool pristine;       // nothing the suffix-array path reads (sorted keys, SA, L, origin) has been written yet
+    bool forked;         // a pass over the deep list is running on the side stream
+    uint32_t deep_done;  // entries [0, deep_done) of the list have been given to the early pass
+
+    Mail::LFirst *d_lf() const { return &ctx->d_mail->lf; }  // the path's counters (mailbox.hpp says who writes which of them from which stream)
+    const Mail::LFirst &lf() const { return ctx->h_mail->lf; }  // (valid behind every mail_read of the group)
+};
+
+// The limits, the knobs and the lists.  Expects the call's fields of r; leaves the deep list zeroed, the counters cleared, the giant lists allocated.
+int lf_setup(LfRun &r) {
+    const size_t n = r.n;
     // The limits past which the path gives up.  Tuning build (test hooks, tests/test_gpu_fallbacks.py): DK_LF_DEEP_CAP, DK_LF_ARENA, DK_LF_GIANT_CAP,
     // DK_LF_GIANT_ARENA, DK_LF_GIANT_ROUNDS and DK_LF_ROUNDS lower them.  They lower only what the kernels and the host compare against: every buffer
     // keeps its full size, so a site that forgets its check still writes inside its buffer (and the parity tests see the wrong L).
-    const uint32_t deep_cap = lf_limit(DK_KNOB("DK_LF_DEEP_CAP", static_cast<int>(LF_DEEP_CAP)), LF_DEEP_CAP);
+    r.deep_cap = lf_limit(DK_KNOB("DK_LF_DEEP_CAP", static_cast<int>(LF_DEEP_CAP)), LF_DEEP_CAP);
     const uint32_t arena_cap = lf_limit(DK_KNOB("DK_LF_ARENA", 0x7FFFFFFF), static_cast<uint32_t>(n));  // (every suffix leaves its list at most once)
-    const uint32_t giant_cap = lf_limit(DK_KNOB("DK_LF_GIANT_CAP", static_cast<int>(LF_GIANT_CAP)), LF_GIANT_CAP);
-    const uint32_t giant_arena = lf_limit(DK_KNOB("DK_LF_GIANT_ARENA", static_cast<int>(LF_GIANT_ARENA)), LF_GIANT_ARENA);
-    const int giant_rounds = static_cast<int>(lf_limit(DK_KNOB("DK_LF_GIANT_ROUNDS", LF_GIANT_ROUNDS), LF_GIANT_ROUNDS));
-    const int max_rounds = static_cast<int>(lf_limit(DK_KNOB("DK_LF_ROUNDS", LF_MAX_ROUNDS), LF_MAX_ROUNDS));
-    const size_t mark = ctx->ws_mark();
-    LfDeepGroup *deep = ctx->ws_alloc<LfDeepGroup>(LF_DEEP_CAP);
-    if (!deep) return DK_E_NOMEM;
+    r.giant_cap = lf_limit(DK_KNOB("DK_LF_GIANT_CAP", static_cast<int>(LF_GIANT_CAP)), LF_GIANT_CAP);
+    r.giant_arena = lf_limit(DK_KNOB("DK_LF_GIANT_ARENA", static_cast<int>(LF_GIANT_ARENA)), LF_GIANT_ARENA);
+    r.giant_rounds = static_cast<int>(lf_limit(DK_KNOB("DK_LF_GIANT_ROUNDS", LF_GIANT_ROUNDS), LF_GIANT_ROUNDS));
+    r.max_rounds = static_cast<int>(lf_limit(DK_KNOB("DK_LF_ROUNDS", LF_MAX_ROUNDS), LF_MAX_ROUNDS));
+    r.mark = r.ctx->ws_mark();
+    r.deep = r.ctx->ws_alloc<LfDeepGroup>(LF_DEEP_CAP);
+    if (!r.deep) return DK_E_NOMEM;
     // The list starts out as zeros (flags 0, size 0): k_lf_medium walks it up to the CURRENT count while a pass on the side stream may be handing groups
     // on, so it meets entries that are reserved and not written yet, or half written.  What keeps it safe: the flags dword alone decides whether it
     // takes an entry (LD_LIST), and what writes entries beside it -- k_lf_deep_wave on the side stream (LD_HANDED), k_lf_medium's own workgroups
     // (flags 0) -- never stores LD_LIST: an entry in flight reads as not listed whatever the order of its stores, and no LD_LIST bits of an earlier
     // call are left.  Nothing relies on an entry being one 16-byte store.  (16 bytes per entry, at most about n entries: a few microseconds.)
-    DK_HIP(ctx, hipMemsetAsync(deep, 0, std::min<size_t>(LF_DEEP_CAP, n + 4096) * sizeof(LfDeepGroup), st));
-    // the path's counters, cleared before its first kernel (mailbox.hpp says who writes which of them from which stream)
-    Mail::LFirst *d_lf = &ctx->d_mail->lf;
-    const Mail::LFirst &lf = ctx->h_mail->lf;  // (valid behind every mail_read of the group below)
-    uint32_t *d_deep_count = &d_lf->deep_count, *d_fallback = &d_lf->fallback, *d_deep_begin = &d_lf->deep_begin;
-    DK_TRY(ctx->mail_fill(d_lf, 0));
-    const LfArena arena{b.a_idx, b.a_pos, b.a_sym, &d_lf->arena_used, arena_cap};
+    DK_HIP(r.ctx, hipMemsetAsync(r.deep, 0, std::min<size_t>(LF_DEEP_CAP, n + 4096) * sizeof(LfDeepGroup), r.st));
+    // the path's counters, cleared before its first kernel
+    DK_TRY(r.ctx->mail_fill(r.d_lf(), 0));
+    r.arena = LfArena{r.b.a_idx, r.b.a_pos, r.b.a_sym, &r.d_lf()->arena_used, arena_cap};
     // steps a group may take inside k_lf_finish, and steps without a split after which it leaves early (tuning build: DK_LF_STEPS, DK_LF_STUCK)
-    const int max_steps = std::max(1, std::min(4096, DK_KNOB("DK_LF_STEPS", LF_STEPS))), stuck_steps = std::max(1, DK_KNOB("DK_LF_STUCK", LF_STUCK));
+    r.max_steps = std::max(1, std::min(4096, DK_KNOB("DK_LF_STEPS", LF_STEPS))), r.stuck_steps = std::max(1, DK_KNOB("DK_LF_STUCK", LF_STUCK));
     // (short lists: LF_SHORT_STEPS steps for lists of at most LF_SHORT_SLOTS slots; tuning build: DK_LF_SHORT_STEPS, DK_LF_SHORT_SLOTS, 0 slots = the same everywhere)
-    const int short_steps = std::max(1, std::min(4096, DK_KNOB("DK_LF_SHORT_STEPS", LF_SHORT_STEPS)));
-    const size_t short_slots = static_cast<size_t>(DK_KNOB("DK_LF_SHORT_SLOTS", static_cast<int>(LF_SHORT_SLOTS)));
-    LfGiantOut giant[2];  // giant list (subgroups whose common extension is longer than a workgroup measures): two sets, one being read, one being filled
+    r.short_steps = std::max(1, std::min(4096, DK_KNOB("DK_LF_SHORT_STEPS", LF_SHORT_STEPS)));
+    r.short_slots = static_cast<size_t>(DK_KNOB("DK_LF_SHORT_SLOTS", static_cast<int>(LF_SHORT_SLOTS)));
     for (int q = 0; q < 2; ++q) {
-        giant[q].list = ctx->ws_alloc<LfDeepGroup>(LF_GIANT_CAP);
-        giant[q].count = &d_lf->giant_count[q];
-        giant[q].cap = giant_cap;
-        giant[q].idx = ctx->ws_alloc<uint32_t>(LF_GIANT_ARENA);
-        giant[q].pos = ctx->ws_alloc<uint32_t>(LF_GIANT_ARENA);
-        giant[q].sym = ctx->ws_alloc<uint8_t>(LF_GIANT_ARENA);
-        giant[q].used = &d_lf->giant_used[q];
-        giant[q].arena_cap = giant_arena;
-        if (!giant[q].list || !giant[q].idx || !giant[q].pos || !giant[q].sym) return DK_E_NOMEM;
+        LfGiantOut &g = r.giant[q];
+        g.list = r.ctx->ws_alloc<LfDeepGroup>(LF_GIANT_CAP);
+        g.count = &r.d_lf()->giant_count[q];
+        g.cap = r.giant_cap;
+        g.idx = r.ctx->ws_alloc<uint32_t>(LF_GIANT_ARENA);
+        g.pos = r.ctx->ws_alloc<uint32_t>(LF_GIANT_ARENA);
+        g.sym = r.ctx->ws_alloc<uint8_t>(LF_GIANT_ARENA);
+        g.used = &r.d_lf()->giant_used[q];
+        g.arena_cap = r.giant_arena;
+        if (!g.list || !g.idx || !g.pos || !g.sym) return DK_E_NOMEM;
     }
-    uint32_t *lce_res = ctx->ws_alloc<uint32_t>(LF_GIANT_ARENA);  // per member of the listed subgroups
-    if (!lce_res) return DK_E_NOMEM;
-    size_t active = 0, groups = 0, nbig = 0, nmedium = 0, nbiggroups = 0;
-    const uint32_t ls_max = static_cast<uint32_t>(std::min(LFS_CAP, std::max(32, DK_KNOB("DK_LF_MAX", LFS_CAP))));  // groups above go the global way
+    r.lce_res = r.ctx->ws_alloc<uint32_t>(LF_GIANT_ARENA);
+    if (!r.lce_res) return DK_E_NOMEM;
+    r.ls_max = static_cast<uint32_t>(std::min(LFS_CAP, std::max(32, DK_KNOB("DK_LF_MAX", LFS_CAP))));
+    // DK_LF_MEDIUM (tuning build; default on): the big list in two regions -- giant groups through the global sort, groups of up to 8192 members sorted
+    // group by group inside LDS (classify_two_and_read)
+    r.two_classes = DK_KNOB("DK_LF_MEDIUM", 1) != 0;
+    // a short big list lets every group of up to LF_DEEP_MAX members go to k_lf_medium (tuning build: DK_LF_TAIL = slots of the big list from which on; 0: never)
+    r.tail_slots = static_cast<size_t>(DK_KNOB("DK_LF_TAIL", LF_TAIL_SLOTS));
+    r.medium_steps = std::max(1, std::min(4096, DK_KNOB("DK_LF_MEDIUM_STEPS", 16)));
+    r.by_wave = DK_KNOB("DK_LF_WAVE", 1) != 0;
+    r.fork_slots = static_cast<size_t>(DK_KNOB("DK_LF_FORK", 4 << 20));  // big-list size from which on the early pass may start (0: never)
+    r.refork_groups = static_cast<uint32_t>(std::max(1, DK_KNOB("DK_LF_REFORK", 4096)));  // new deep groups from which on another early pass starts
+    return DK_OK;
+}
+
+// classify the list the last rerank left, with the line of the big groups at `lo`
+int lf_classify(LfRun &r, uint32_t lo) {
+    if (!r.two_classes) return classify_and_read(r.ctx, 0, r.b.gstart, r.b.bigidx, r.b.bigoff, &r.c, lo);
+    return classify_two_and_read(r.ctx, r.b.gstart, r.b.bigidx, r.b.bigoff, lo, &r.c);
+}
+
+// the big groups do not split on text (a stalled round), or the big list is short: its groups of up to LF_DEEP_MAX members leave it (the next
+// k_lf_finish lists them, k_lf_medium takes them), the classification is done again with that line
+int lf_let_medium_groups_go(LfRun &r, bool stalled_now) {
+    if (!(stalled_now || (r.tail_slots && r.c.big <= r.tail_slots)) || r.c.big == 0 || r.big_min == static_cast<uint32_t>(LF_DEEP_MAX)) return DK_OK;
+    r.big_min = LF_DEEP_MAX;
+    DK_TRY(lf_classify(r, r.big_min));
+    if (r.trace) {  // (the deep list's length: the next round lists the groups that left behind it -- tests/test_gpu_fallbacks.py caps the list there)
+        uint32_t listed = 0;
+        DK_HIP(r.ctx, hipMemcpyAsync(&listed, &r.d_lf()->deep_count, sizeof listed, hipMemcpyDeviceToHost, r.st));
+        DK_HIP(r.ctx, hipStreamSynchronize(r.st));
+        fprintf(stderr, "[dk] L-first: %s, groups up to %d members end inside LDS: big=%zu in %zu groups, deep list at %u\n", stalled_now ? "stalled round" : "short big list",
+                LF_DEEP_MAX, r.c.big, r.c.big_groups, listed);
+    }
+    return DK_OK;
+}
+
+// order the deep groups [begin, end) of the list from the arena, on stream `on`: a wave per group of up to 64 members, then a workgroup per bigger
+// (or handed-on) group.
+// (last: the pass at the end -- its workgroup kernels read the list's length on the device, behind the wave kernel that has just handed groups on)
+int lf_order_deep(LfRun &r, hipStream_t on, uint32_t begin, uint32_t end, bool last) {
+    const LfArena &arena = r.arena;
+    const uint32_t n32 = static_cast<uint32_t>(r.n);
+    uint32_t *d_deep_count = &r.d_lf()->deep_count, *d_fallback = &r.d_lf()->fallback;
+    const uint32_t *end_ptr = last ? d_deep_count : nullptr;
+    if (r.by_wave) {
+        LaunchScope ls(r.ctx, K_CHAIN, 0.0, on);
+        k_lf_deep_wave<<<dim3(static_cast<unsigned>(std::min<size_t>(div_up(end - begin, 4), 4096))), dim3(256), 0, on>>>(arena.idx, arena.pos, arena.sym, r.deep, d_deep_count, begin, end, r.deep_cap,
+                                                                                                                       r.d_text, n32, r.d_bwt, r.d_origin, d_fallback);
+    }
+    {
+        LaunchScope ls(r.ctx, K_CHAIN, 0.0, on);
+        k_lf_deep_block<LS_MAX, 256><<<dim3(1024), dim3(256), 0, on>>>(arena.idx, arena.pos, arena.sym, r.deep, end_ptr, begin, end, r.deep_cap, r.d_text, n32, r.d_bwt,
+                                                                       r.d_origin, d_fallback, nullptr, r.giant[0], r.by_wave ? LDM_ARENA : LDM_ALL, 0u);
+        k_lf_deep_block<LF_DEEP_MAX, 1024><<<dim3(256), dim3(1024), 0, on>>>(arena.idx, arena.pos, arena.sym, r.deep, end_ptr, begin, end, r.deep_cap, r.d_text, n32,
+                                                                             r.d_bwt, r.d_origin, d_fallback, nullptr, r.giant[0], r.by_wave ? LDM_ARENA : LDM_ALL, static_cast<uint32_t>(LS_MAX));
+    }
+    DK_HIP(r.ctx, hipGetLastError());
+    return DK_OK;
+}
+
+// One round: k_lf_finish takes every group of the list up to ls_max members to its end inside LDS (or to the deep list) and moves the bigger ones
+// to the big list; that is sorted on its next four or five symbols (or tokens), reranked into the next list and classified.
+// Expects the list and its counts; leaves the next ones -- or, when the list had no big group, nothing active: the rounds are over.
+int lf_round(LfRun &r, int round) {
+    LfBuffers &b = r.b;
+    const size_t n = r.n, active = r.c.active, nbig = r.c.big;
+    const int period = r.plan.period;
+    uint32_t *const next_break = r.plan.next_break;
+    uint32_t *d_deep_count = &r.d_lf()->deep_count, *d_fallback = &r.d_lf()->fallback, *d_deep_begin = &r.d_lf()->deep_begin;
+    const int bsbits = r.c.big_groups > 1 ? static_cast<int>(ceil_log2_u64(r.c.big_groups)) : 1;
+    const int tsym_big = std::max(1, std::min(5, (55 - bsbits) / 8));
+    const int kb = 8 * tsym_big;
+    const bool token_round = r.want_tokens && !r.tokens_done && nbig > 0 && kb >= 1 + r.ebits + 8;
+    if (token_round) {  // next break of every position (2 n bytes read, 4 n written)
+        const size_t mark = r.ctx->ws_mark();
+        uint32_t *tile_first = r.ctx->ws_alloc<uint32_t>(div_up(n, PB_TILE));
+        if (!tile_first) return DK_E_NOMEM;
+        DK_TRY(enqueue_next_breaks(r.ctx, r.d_text, n, period, tile_first, next_break));
+        {
+            LaunchScope ls(r.ctx, K_PERIOD, 16.0 * r.c.groups);
+            k_lf_periodic_groups<<<dim3(div_up(r.c.groups, 256)), dim3(256), 0, r.st>>>(b.gstart, b.gdepth, b.l_idx, b.bigidx, r.c.groups, r.big_min, next_break, period, static_cast<uint32_t>(n), b.bigper);
+        }
+        DK_HIP(r.ctx, hipGetLastError());
+        r.ctx->ws_release(mark);
+        r.ctx->stats.sa_route |= DK_ROUTE_PERIOD_ROUND;
+    }
+    const LfTokens tok{token_round ? next_break : nullptr, period, r.ebits, b.bigper};
+    {
+        LaunchScope ls(r.ctx, K_LF_FINISH, 13.0 * active + 64.0 * active + 17.0 * nbig);
+        k_lf_finish<LFS_TILE, LFS_CAP, LFS_BLOCK><<<dim3(div_up(active, LFS_TILE)), dim3(LFS_BLOCK), 0, r.st>>>(b.l_idx, b.l_pos, b.l_gid, b.l_sym, b.gstart, b.bigidx, b.bigoff, active, r.d_text,
+                                                                            static_cast<uint32_t>(n), b.gdepth, b.bigdepth, tok, kb, r.ls_max, r.big_min, b.k0, b.v0, b.bpos, r.d_bwt,
+                                                                            r.d_origin, r.deep, d_deep_count, r.deep_cap, r.arena, d_fallback, active <= r.short_slots ? r.short_steps : r.max_steps, r.stuck_steps);
+    }
+    if (r.big_min != r.ls_max) {  // the groups the big list let go stand in the round's list: refined to their end inside LDS before the list is rewritten
+        LaunchScope ls(r.ctx, K_CHAIN, 0.0);
+        k_lf_medium<LF_DEEP_MAX / 8><<<dim3(1024), dim3(LF_DEEP_MAX / 8), 0, r.st>>>(b.l_idx, b.l_pos, b.l_sym, r.deep, d_deep_count, d_deep_begin, r.deep_cap, r.d_text, static_cast<uint32_t>(n), r.d_bwt,
+                                                                        r.d_origin, r.arena, d_fallback, r.medium_steps, r.stuck_steps);
+    }
+    DK_HIP(r.ctx, hipMemcpyAsync(d_deep_begin, d_deep_count, sizeof(uint32_t), hipMemcpyDeviceToDevice, r.st));  // the next round's groups start here
+    if (r.fork_slots) DK_TRY(r.ctx->mail_fetch(&r.ctx->h_mail->deep_seen, d_deep_count));  // (read behind the round's classification)
+    DK_HIP(r.ctx, hipGetLastError());
+    r.ctx->stats.rounds += 1;
+    if (nbig == 0) {
+        r.c.active = 0;  // (k_lf_finish has taken every group of the list: no next one)
+        return DK_OK;
+    }
+    r.ctx->stats.sa_route |= DK_ROUTE_LFIRST_BIG_ROUND;
+    if (r.two_classes) {  // (short lists too: the word-like block's last five rounds, each below 2^19 slots, 17.2 against 17.5 ms; the text block pays 0.05 ms for the second classification)
+        const uint64_t *k_src = b.k0;  // where k_lf_finish (and k_lf_tokens) left the list
+        const uint32_t *v_src = b.v0;
+        const int gbits = r.c.giant_groups > 1 ? static_cast<int>(ceil_log2_u64(r.c.giant_groups)) : 1;  // the giant groups have the lowest dense indices
+        DK_TRY(sort_pairs(r.ctx, b.k0, b.k1, b.v0, b.v1, r.c.giant, 8, 8 + kb + gbits));
+        DK_TRY(sort_groups(r.ctx, k_src, v_src, b.k0, b.v0, b.bigoff + r.c.giant_groups, r.c.medium_groups, r.c.medium, r.big_min, 8, 8 + kb));
+    } else {
+        DK_TRY(sort_pairs(r.ctx, b.k0, b.k1, b.v0, b.v1, nbig, 8, 8 + kb + bsbits));
+    }
+    const size_t big_count = nbig;
+    const LfDepthRule rule{b.gdepth, 0u, b.k0, 8 + kb, b.bigdepth, static_cast<uint32_t>(tsym_big), token_round ? next_break : nullptr, period, static_cast<uint32_t>(n), b.bigper};
+    DK_TRY(lf_rerank(r.ctx, b.k0, 8, nullptr, b.bsym, 1, b.v0, nullptr, b.bpos, big_count, b.l_idx, b.l_pos, b.l_gid, b.l_sym, b.gstart, r.d_bwt, r.d_origin, rule));
+    DK_TRY(lf_classify(r, r.big_min));
+    if (token_round) {
+        r.tokens_done = true;
+        r.want_tokens = false;
+        if (r.trace) fprintf(stderr, "[dk] L-first round %d: periodic groups (period %d) keyed by the tokens of their stretches' ends\n", round, period);
+    }
+    r.h += static_cast<uint32_t>(tsym_big);
+    // The deep groups listed so far can be ordered BESIDE the rounds that follow: they need nothing from them (their members stand in the arena, their
+    // places in L are theirs alone), and the rounds of a short big list leave the GPU nearly idle -- 50 MB of real text: 1.3 ms of deep work behind
+    // ten rounds of a few hundred microseconds each.  One early pass on the context's side stream once the big list is short; what is listed later
+    // (and what the early pass's wave kernel hands on) takes the pass at the end.
+    if (const uint32_t seen = r.ctx->h_mail->deep_seen; r.fork_slots && r.c.big > 0 && r.c.big <= r.fork_slots && seen <= r.deep_cap && seen >= r.deep_done + (r.forked ? r.refork_groups : 1024u)) {
+        // (the count was read behind this round's k_lf_finish and k_lf_medium: every entry below it is complete -- those of the rounds by that read,
+        //  those an earlier pass on the side stream handed on by the stream's order.  Again whenever enough new groups have arrived.)
+        const uint32_t from_entry = r.deep_done;
+        r.deep_done = seen;
+        DK_HIP(r.ctx, hipEventRecord(r.ctx->ev_fork, r.st));
+        DK_HIP(r.ctx, hipStreamWaitEvent(r.ctx->side_stream, r.ctx->ev_fork, 0));
+        DK_TRY(lf_order_deep(r, r.ctx->side_stream, from_entry, r.deep_done, false));
+        DK_HIP(r.ctx, hipEventRecord(r.ctx->ev_join, r.ctx->side_stream));
+        r.forked = true;
+        if (r.trace) fprintf(stderr, "[dk] L-first: deep groups %u .. %u ordered beside the rounds\n", from_entry, r.deep_done);
+    }
+    r.stalled = r.c.big * 16 > big_count * 15 ? r.stalled + 1 : 0;
+    if (r.stalled && !r.tokens_done) r.want_tokens = true;
+    const uint32_t line_before = r.big_min;
+    // (a stalled round with tokens still to come: the tokens first -- a run of 3000 zeros is placed by one token round where the arena's kernels walk
+    //  3000 bytes per member: 6.7 against 8.0 ms for the 1e8-byte block around it)
+    DK_TRY(lf_let_medium_groups_go(r, r.stalled != 0 && !(r.want_tokens && !r.tokens_done)));
+    if (r.big_min != line_before) r.stalled = 0;  // (the groups that have just left may have been the ones that did not split: count anew)
+    if (r.trace)
+        fprintf(stderr, "[dk] L-first round %d: big list %zu sorted on %d+%d bits -> depth %u (groups that were not periodic) live=%zu groups=%zu big=%zu in %zu groups\n", round, big_count, bsbits, kb, r.h,
+                r.c.active, r.c.groups, r.c.big, r.c.big_groups);
+    return DK_OK;
+}
+
+// The passes at the end.  Expects the rounds over (nothing active); leaves L complete (L_COMPLETE) or the verdict that the path gave up (START_OVER).
+int lf_last_passes(LfRun &r) {
+    const Mail::LFirst &lf = r.lf();
+    uint32_t *d_fallback = &r.d_lf()->fallback;
+    const uint32_t n32 = static_cast<uint32_t>(r.n);
+    // the deep groups of all rounds, from the arena: a wave per group of up to 64 members, then a workgroup per bigger (or handed-on) group -- what an
+    // early pass beside the rounds (lf_round) has not taken already
+    if (r.forked) DK_HIP(r.ctx, hipStreamWaitEvent(r.st, r.ctx->ev_join, 0));
+    r.forked = false;
+    DK_TRY(r.ctx->mail_read(&r.ctx->h_mail->lf));
+    if (lf.deep_count > r.deep_done && lf.deep_count <= r.deep_cap && lf.fallback == 0) {
+        if (r.trace) fprintf(stderr, "[dk] L-first: %u deep groups (%u of them ordered beside the rounds), %u members in the arena\n", lf.deep_count, r.deep_done, lf.arena_used);
+        DK_TRY(lf_order_deep(r, r.st, r.deep_done, lf.deep_count, true));
+    }
+    // giant common extensions: measured by the whole grid, then the subgroup goes through k_lf_deep again (and may hand on a part of itself)
+    DK_TRY(r.ctx->mail_read(&r.ctx->h_mail->lf));
+    const bool any_giant = lf.giant_count[0] != 0 && lf.fallback == 0 && lf.deep_count <= r.deep_cap;
+    if (r.trace && any_giant) fprintf(stderr, "[dk] L-first: %u subgroups with giant common extensions go through the grid-wide measure\n", lf.giant_count[0]);
+    for (int g = 0; any_giant && g < r.giant_rounds; ++g) {
+        const LfGiantOut &in = r.giant[g & 1];
+        LfGiantOut out = r.giant[(g + 1) & 1];
+        if (g + 1 == r.giant_rounds) out.cap = 0;  // what is still giant after the last round makes the path give up
+        if (r.trace) {
+            uint32_t listed = 0;
+            DK_HIP(r.ctx, hipMemcpyAsync(&listed, in.count, sizeof listed, hipMemcpyDeviceToHost, r.st));
+            DK_HIP(r.ctx, hipStreamSynchronize(r.st));
+            if (listed) fprintf(stderr, "[dk] L-first: giant round %d: %u subgroups\n", g, listed);
+        }
+        DK_HIP(r.ctx, hipMemsetAsync(r.lce_res, 0xFF, static_cast<size_t>(LF_GIANT_ARENA) * sizeof(uint32_t), r.st));
+        DK_HIP(r.ctx, hipMemsetAsync(out.count, 0, sizeof(uint32_t), r.st));
+        DK_HIP(r.ctx, hipMemsetAsync(out.used, 0, sizeof(uint32_t), r.st));
+        {
+            LaunchScope ls(r.ctx, K_CHAIN, 0.0);
+            k_lf_lce<<<dim3(1024), dim3(256), 0, r.st>>>(in.idx, in.list, in.count, in.cap, r.d_text, n32, r.lce_res);
+            k_lf_deep_block<LS_MAX, 256><<<dim3(256), dim3(256), 0, r.st>>>(in.idx, in.pos, in.sym, in.list, in.count, 0u, 0u, in.cap, r.d_text, n32, r.d_bwt, r.d_origin,
+                                                                          d_fallback, r.lce_res, out, LDM_ALL, 0u);
+            k_lf_deep_block<LF_DEEP_MAX, 1024><<<dim3(64), dim3(1024), 0, r.st>>>(in.idx, in.pos, in.sym, in.list, in.count, 0u, 0u, in.cap, r.d_text, n32, r.d_bwt, r.d_origin,
+                                                                                d_fallback, r.lce_res, out, LDM_ALL, static_cast<uint32_t>(LS_MAX));
+        }
+    }
+    DK_HIP(r.ctx, hipGetLastError());
+    DK_TRY(r.ctx->mail_read(&r.ctx->h_mail->lf));
+    const uint32_t deep_total = lf.deep_count;
+    // Giving up: a kernel found a list full (deep list, arena, giant list or its arena) or a common extension still giant after the last giant round
+    // (the fallback word) -- or the deep list's count went past its cap where no kernel said so (the host skipped the pass at the end above, and
+    // every group listed since the early pass would stay unordered).  No giant round at all (tuning build) leaves the giant list unordered too.
+    const bool gave_up = lf.fallback != 0 || deep_total > r.deep_cap || (any_giant && r.giant_rounds == 0);
+    if (any_giant) r.ctx->stats.sa_route |= DK_ROUTE_LFIRST_GIANT;
+    if (r.trace)
+        fprintf(stderr, "[dk] L-first: %u groups went the deep way%s\n", deep_total,
+                gave_up ? "; a list overflowed (deep groups, arena, giant list) or a common extension stayed giant: back to the suffix-array path" : "");
+    r.ctx->ws_release(r.mark);
+    if (deep_total) r.ctx->stats.sa_route |= DK_ROUTE_LFIRST_DEEP;
+    return gave_up ? START_OVER : L_COMPLETE;
+}
+
+// whatever way the path is left, the side stream's work is over before the caller goes on (the suffix-array path reuses every buffer)
+struct LfJoinSide {
+    dk_ctx *c; const bool *forked;
+    ~LfJoinSide() { if (*forked) (void)hipStreamSynchronize(c->side_stream); }
+};
+
+// The L-first path.  -> L_COMPLETE: L and the origin are complete.  Otherwise the caller takes the suffix-array path: WENT_ON: from where it stands
+// (nothing it needs was touched but scratch buffers -- only when starting behind the initial sort); START_OVER: from the start (L and the origin
+// word are rewritten by it).  Or an error.  force: go on even where the big groups hold most of the list (test hook; taking over a list)
+int lfirst_path(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint8_t *d_bwt, uint32_t *d_origin, const LfBuffers &buffers, const LfFrom &from, const LfTokenPlan &plan, bool trace,
+                bool force) {
+    LfRun r{};
+    r.ctx = ctx, r.st = ctx->stream, r.d_text = d_text, r.n = n, r.d_bwt = d_bwt, r.d_origin = d_origin, r.b = buffers, r.plan = plan, r.trace = trace;
+    const LfBuffers &b = r.b;
+    const LfJoinSide join_side{ctx, &r.forked};
+    DK_TRY(lf_setup(r));
     // first rerank: slot a is SA position a, L[a] is the symbol in front of the suffix standing there; every group is known to h0 symbols
     // (the table is filled below, once the path is sure to go on: it lies in the initial keys' buffer, which the suffix-array path reads again when it
     //  takes over from here -- "pristine")
+    const uint32_t h0 = from.h0;
     const LfDepthRule first_rule{nullptr, h0, nullptr, 0, nullptr, 0u, nullptr, 0, static_cast<uint32_t>(n), nullptr};
-    if (from) {
-        DK_TRY(lf_rerank(ctx, reinterpret_cast<const uint64_t *>(from->gid), 0, nullptr, from->sym, 0, from->idx, nullptr, from->pos, from->count, b.l_idx, b.l_pos, b.l_gid,
+    if (from.idx) {
+        DK_TRY(lf_rerank(ctx, reinterpret_cast<const uint64_t *>(from.gid), 0, nullptr, from.sym, 0, from.idx, nullptr, from.pos, from.count, b.l_idx, b.l_pos, b.l_gid,
                          b.l_sym, b.gstart, d_bwt, d_origin, first_rule, true));
-        *pristine = false;  // (finals of the filter have written L; the caller's group table has been rewritten)
     } else {
-        DK_TRY(lf_rerank(ctx, init_keys, key_shift, narrow_starts, d_bwt, 0, d_sa, d_origin, nullptr, n, b.l_idx, b.l_pos, b.l_gid, b.l_sym, b.gstart, d_bwt, d_origin, first_rule));
+        DK_TRY(lf_rerank(ctx, from.init_keys, from.key_shift, from.narrow_starts, d_bwt, 0, from.d_sa, d_origin, nullptr, n, b.l_idx, b.l_pos, b.l_gid, b.l_sym, b.gstart, d_bwt, d_origin, first_rule));
     }
-    // DK_LF_MEDIUM (tuning build; default on): the big list in two regions -- giant groups through the global sort, groups of up to 8192 members sorted
-    // group by group inside LDS (classify_two_and_read)
-    const bool two_classes = DK_KNOB("DK_LF_MEDIUM", 1) != 0;
-    size_t ngiant = 0, ngiantgroups = 0, nmed = 0, nmedgroups = 0;
-    auto classify = [&](uint32_t lo) -> int {
-        if (!two_classes) return classify_and_read(ctx, 0, b.gstart, b.bigidx, b.bigoff, &active, &groups, &nbig, &nmedium, &nbiggroups, lo);
-        DK_TRY(classify_two_and_read(ctx, b.gstart, b.bigidx, b.bigoff, lo, &active, &groups, &ngiant, &ngiantgroups, &nmed, &nmedgroups));
-        nbig = ngiant + nmed;
-        nbiggroups = ngiantgroups + nmedgroups;
-        return DK_OK;
-    };
-    DK_TRY(classify(ls_max));
-    uint32_t h = h0;
+    r.pristine = !from.idx;  // (taking over: finals of the filter have written L; the caller's group table has been rewritten)
+    DK_TRY(lf_classify(r, r.ls_max));
+    r.h = h0;
     if (trace)
-        fprintf(stderr, "[dk] L-first: %s (%u symbols) live=%zu groups=%zu big=%zu in %zu groups\n", from ? "taking over a list" : "after the initial sort", h0, active, groups,
-                nbig, nbiggroups);
+        fprintf(stderr, "[dk] L-first: %s (%u symbols) live=%zu groups=%zu big=%zu in %zu groups\n", from.idx ? "taking over a list" : "after the initial sort", h0, r.c.active, r.c.groups,
+                r.c.big, r.c.big_groups);
     // Big groups are refined four or five symbols per global sort where prefix doubling doubles.  Measured at 1e8 bytes (share of the live slots
     // in groups above 256 after the first rerank -> this way / the other): Markov text 0.5 % 6.4 / 10.0 ms; half Markov, half Zipf words 50 %
     // 13.2 / 16.6; Zipf words over 28 symbols 72 % 15.0 / 17.7; over 182 symbols, 2 M words 83 % 17.8 / 18.8; 200 K words 74 % (the most
     // frequent word 14 % of all) 20.5 / 20.7 -- never behind while the groups split on text at all.  Above 85 % the other way (nothing has
     // been written yet, the suffix-array path goes on from the same sorted keys).
-    if (nbig * 100 > active * 85 && !force) {
-        if (trace) fprintf(stderr, "[dk] L-first: %zu of %zu live slots in big groups: the suffix-array path goes on from here\n", nbig, active);
-        ctx->ws_release(mark);
-        return DK_OK;
+    if (r.c.big * 100 > r.c.active * 85 && !force) {
+        if (trace) fprintf(stderr, "[dk] L-first: %zu of %zu live slots in big groups: the suffix-array path goes on from here\n", r.c.big, r.c.active);
+        ctx->ws_release(r.mark);
+        return r.pristine ? WENT_ON : START_OVER;
     }
-    *pristine = false;
-    DK_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b.gdepth), static_cast<int>(h0), groups + 1, st));
-    uint32_t deep_total = 0;
-    int stalled = 0;  // global-sort rounds in a row that left nearly all of their slots in big groups (runs of one symbol, periodic stretches)
-    uint32_t big_min = ls_max;  // groups above this go through the global sort; after a stalled round, or once the big list is short: LF_DEEP_MAX, what the deep list takes
-    // Tokens (LfTokens): once, when the block has a dominant short period (period > 0: the probe saw at least one 64-byte window of it) and the caller
-    // has room for the next-break positions -- in the first round when the probes saw runs or periodic windows worth it (tokens_early: real text with
-    // its indentation and rulers; the groups inside runs are the biggest and the slowest to split on text, 17 rounds instead of 9 on 50 MB of it), else in
-    // the round after the first stalled one.  A round with tokens is a text round for every group that is not periodic.
-    const int ebits = static_cast<int>(ceil_log2_u64(static_cast<uint64_t>(n) + 1));
-    bool tokens_done = period <= 0 || !next_break || static_cast<uint32_t>(period) > h0;
-    bool want_tokens = !tokens_done && tokens_early;
-    // The deep groups listed so far can be ordered BESIDE the rounds that follow: they need nothing from them (their members stand in the arena, their
-    // places in L are theirs alone), and the rounds of a short big list leave the GPU nearly idle -- 50 MB of real text: 1.3 ms of deep work behind
-    // ten rounds of a few hundred microseconds each.  One early pass on the context's side stream once the big list is short; what is listed later
-    // (and what the early pass's wave kernel hands on) takes the pass at the end.
-    // a short big list lets every group of up to LF_DEEP_MAX members go to k_lf_medium (tuning build: DK_LF_TAIL = slots of the big list from which on; 0: never)
-    const size_t tail_slots = static_cast<size_t>(DK_KNOB("DK_LF_TAIL", LF_TAIL_SLOTS));
-    const int medium_steps = std::max(1, std::min(4096, DK_KNOB("DK_LF_MEDIUM_STEPS", 16)));
-    // the big groups do not split on text (a stalled round), or the big list is short: its groups of up to LF_DEEP_MAX members leave it (the next
-    // k_lf_finish lists them, k_lf_medium takes them), the classification is done again with that line
-    auto let_medium_groups_go = [&](bool stalled_now) -> int {
-        if (!(stalled_now || (tail_slots && nbig <= tail_slots)) || nbig == 0 || big_min == static_cast<uint32_t>(LF_DEEP_MAX)) return DK_OK;
-        big_min = LF_DEEP_MAX;
-        DK_TRY(classify(big_min));
-        if (trace) {  // (the deep list's length: the next round lists the groups that left behind it -- tests/test_gpu_fallbacks.py caps the list there)
-            uint32_t listed = 0;
-            DK_HIP(ctx, hipMemcpyAsync(&listed, d_deep_count, sizeof listed, hipMemcpyDeviceToHost, st));
-            DK_HIP(ctx, hipStreamSynchronize(st));
-            fprintf(stderr, "[dk] L-first: %s, groups up to %d members end inside LDS: big=%zu in %zu groups, deep list at %u\n", stalled_now ? "stalled round" : "short big list",
-                    LF_DEEP_MAX, nbig, nbiggroups, listed);
-        }
-        return DK_OK;
-    };
-    DK_TRY(let_medium_groups_go(false));
-    bool forked = false;
-    uint32_t deep_done = 0;  // entries [0, deep_done) of the list have been given to the early pass
-    const bool by_wave = DK_KNOB("DK_LF_WAVE", 1) != 0;
-    // (last: the pass at the end -- its workgroup kernels read the list's length on the device, behind the wave kernel that has just handed groups on)
-    auto order_deep = [&](hipStream_t on, uint32_t begin, uint32_t end, bool last) -> int {
-        const uint32_t *end_ptr = last ? d_deep_count : nullptr;
-        if (by_wave) {
-            LaunchScope ls(ctx, K_CHAIN, 0.0, on);
-            k_lf_deep_wave<<<dim3(static_cast<unsigned>(std::min<size_t>(div_up(end - begin, 4), 4096))), dim3(256), 0, on>>>(arena.idx, arena.pos, arena.sym, deep, d_deep_count, begin, end, deep_cap,
-                                                                                                                           d_text, static_cast<uint32_t>(n), d_bwt, d_origin, d_fallback);
-        }
-        {
-            LaunchScope ls(ctx, K_CHAIN, 0.0, on);
-            k_lf_deep_block<LS_MAX, 256><<<dim3(1024), dim3(256), 0, on>>>(arena.idx, arena.pos, arena.sym, deep, end_ptr, begin, end, deep_cap, d_text, static_cast<uint32_t>(n), d_bwt,
-                                                                           d_origin, d_fallback, nullptr, giant[0], by_wave ? LDM_ARENA : LDM_ALL, 0u);
-            k_lf_deep_block<LF_DEEP_MAX, 1024><<<dim3(256), dim3(1024), 0, on>>>(arena.idx, arena.pos, arena.sym, deep, end_ptr, begin, end, deep_cap, d_text, static_cast<uint32_t>(n),
-                                                                                 d_bwt, d_origin, d_fallback, nullptr, giant[0], by_wave ? LDM_ARENA : LDM_ALL, static_cast<uint32_t>(LS_MAX));
-        }
-        DK_HIP(ctx, hipGetLastError());
-        return DK_OK;
-    };
-    struct JoinSide {  // whatever way the path is left, the side stream's work is over before the caller goes on (the suffix-array path reuses every buffer)
-        dk_ctx *c; bool *forked;
-        ~JoinSide() { if (*forked) (void)hipStreamSynchronize(c->side_stream); }
-    } join_side{ctx, &forked};
-    const size_t fork_slots = static_cast<size_t>(DK_KNOB("DK_LF_FORK", 4 << 20));  // big-list size from which on the early pass may start (0: never)
-    const uint32_t refork_groups = static_cast<uint32_t>(std::max(1, DK_KNOB("DK_LF_REFORK", 4096)));  // new deep groups from which on another early pass starts
-    for (int round = 0; active > 0; ++round) {
-        if (nbig > 0 && (round >= max_rounds || nbig / nbiggroups > LF_AVG_BIG || stalled >= 2)) {
+    r.pristine = false;
+    DK_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b.gdepth), static_cast<int>(h0), r.c.groups + 1, r.st));
+    r.big_min = r.ls_max;
+    r.ebits = static_cast<int>(ceil_log2_u64(static_cast<uint64_t>(n) + 1));
+    r.tokens_done = plan.period <= 0 || !plan.next_break || static_cast<uint32_t>(plan.period) > h0;
+    r.want_tokens = !r.tokens_done && plan.tokens_early;
+    DK_TRY(lf_let_medium_groups_go(r, false));
+    for (int round = 0; r.c.active > 0; ++round) {
+        if (r.c.big > 0 && (round >= r.max_rounds || r.c.big / r.c.big_groups > LF_AVG_BIG || r.stalled >= 2)) {
             if (trace)
                 fprintf(stderr, "[dk] L-first: %s (%zu slots in %zu groups, round %d): back to the suffix-array path\n",
-                        round >= max_rounds ? "round limit" : stalled >= 2 ? "two stalled rounds" : "giant groups", nbig, nbiggroups, round);
-            ctx->ws_release(mark);
-            return DK_OK;
+                        round >= r.max_rounds ? "round limit" : r.stalled >= 2 ? "two stalled rounds" : "giant groups", r.c.big, r.c.big_groups, round);
+            ctx->ws_release(r.mark);
+            return START_OVER;
         }
-        if (trace && DK_KNOB("DK_LF_SIZES", 0) != 0 && nbig > 0) {  // (debug: how the big list's slots spread over group sizes)
-            size_t a2, g2, nb2, nm2, ng2;
+        if (trace && DK_KNOB("DK_LF_SIZES", 0) != 0 && r.c.big > 0) {  // (debug: how the big list's slots spread over group sizes)
+            GroupCounts above;
             for (uint32_t line : {1024u, 4096u, 8192u, 32768u, 1u << 20}) {
-                DK_TRY(classify_and_read(ctx, 0, b.gstart, b.bigidx, b.bigoff, &a2, &g2, &nb2, &nm2, &ng2, line));
-                fprintf(stderr, "[dk]    groups above %u members: %zu slots in %zu groups\n", line, nb2, ng2);
+                DK_TRY(classify_and_read(ctx, 0, b.gstart, b.bigidx, b.bigoff, &above, line));
+                fprintf(stderr, "[dk]    groups above %u members: %zu slots in %zu groups\n", line, above.big, above.big_groups);
             }
-            DK_TRY(classify(big_min));
+            DK_TRY(lf_classify(r, r.big_min));
         }
-        const int bsbits = nbiggroups > 1 ? static_cast<int>(ceil_log2_u64(nbiggroups)) : 1;
-        const int tsym_big = std::max(1, std::min(5, (55 - bsbits) / 8));
-        const int kb = 8 * tsym_big;
-        const bool token_round = want_tokens && !tokens_done && nbig > 0 && kb >= 1 + ebits + 8;
-        if (token_round) {  // next break of every position (2 n bytes read, 4 n written)
-            const size_t ptiles = div_up(n, PB_TILE);
-            const size_t mark2 = ctx->ws_mark();
-            uint32_t *tile_first = ctx->ws_alloc<uint32_t>(ptiles);
-            if (!tile_first) return DK_E_NOMEM;
-            {
-                LaunchScope ls(ctx, K_PERIOD, 2.0 * n + 4.0 * n);
-                k_period_first<<<dim3(ptiles), dim3(256), 0, st>>>(d_text, static_cast<uint32_t>(n), period, tile_first);
-                k_period_spine<<<dim3(1), dim3(1024), 0, st>>>(tile_first, ptiles);
-                k_period_fill<<<dim3(ptiles), dim3(256), 0, st>>>(d_text, static_cast<uint32_t>(n), period, tile_first, next_break);
-            }
-            {
-                LaunchScope ls(ctx, K_PERIOD, 16.0 * groups);
-                k_lf_periodic_groups<<<dim3(div_up(groups, 256)), dim3(256), 0, st>>>(b.gstart, b.gdepth, b.l_idx, b.bigidx, groups, big_min, next_break, period, static_cast<uint32_t>(n), b.bigper);
-            }
-            DK_HIP(ctx, hipGetLastError());
-            ctx->ws_release(mark2);
-            ctx->stats.sa_route |= DK_ROUTE_PERIOD_ROUND;
-        }
-        const LfTokens tok{token_round ? next_break : nullptr, period, ebits, b.bigper};
-        {
-            LaunchScope ls(ctx, K_LF_FINISH, 13.0 * active + 64.0 * active + 17.0 * nbig);
-            k_lf_finish<LFS_TILE, LFS_CAP, LFS_BLOCK><<<dim3(div_up(active, LFS_TILE)), dim3(LFS_BLOCK), 0, st>>>(b.l_idx, b.l_pos, b.l_gid, b.l_sym, b.gstart, b.bigidx, b.bigoff, active, d_text,
-                                                                                static_cast<uint32_t>(n), b.gdepth, b.bigdepth, tok, kb, ls_max, big_min, b.k0, b.v0, b.bpos, d_bwt,
-                                                                                d_origin, deep, d_deep_count, deep_cap, arena, d_fallback, active <= short_slots ? short_steps : max_steps, stuck_steps);
-        }
-        if (big_min != ls_max) {  // the groups the big list let go stand in the round's list: refined to their end inside LDS before the list is rewritten
-            LaunchScope ls(ctx, K_CHAIN, 0.0);
-            k_lf_medium<LF_DEEP_MAX / 8><<<dim3(1024), dim3(LF_DEEP_MAX / 8), 0, st>>>(b.l_idx, b.l_pos, b.l_sym, deep, d_deep_count, d_deep_begin, deep_cap, d_text, static_cast<uint32_t>(n), d_bwt,
-                                                                            d_origin, arena, d_fallback, medium_steps, stuck_steps);
-        }
-        DK_HIP(ctx, hipMemcpyAsync(d_deep_begin, d_deep_count, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));  // the next round's groups start here
-        if (fork_slots) DK_TRY(ctx->mail_fetch(&ctx->h_mail->deep_seen, d_deep_count));  // (read behind the round's classification)
-        DK_HIP(ctx, hipGetLastError());
-        ctx->stats.rounds += 1;
-        if (nbig == 0) break;
-        ctx->stats.sa_route |= DK_ROUTE_LFIRST_BIG_ROUND;
-        if (two_classes) {  // (short lists too: the word-like block's last five rounds, each below 2^19 slots, 17.2 against 17.5 ms; the text block pays 0.05 ms for the second classification)
-            const uint64_t *k_src = b.k0;  // where k_lf_finish (and k_lf_tokens) left the list
-            const uint32_t *v_src = b.v0;
-            const int gbits = ngiantgroups > 1 ? static_cast<int>(ceil_log2_u64(ngiantgroups)) : 1;  // the giant groups have the lowest dense indices
-            DK_TRY(sort_pairs(ctx, b.k0, b.k1, b.v0, b.v1, ngiant, 8, 8 + kb + gbits));
-            DK_TRY(sort_groups(ctx, k_src, v_src, b.k0, b.v0, b.bigoff + ngiantgroups, nmedgroups, nmed, big_min, 8, 8 + kb));
-        } else {
-            DK_TRY(sort_pairs(ctx, b.k0, b.k1, b.v0, b.v1, nbig, 8, 8 + kb + bsbits));
-        }
-        const size_t big_count = nbig;
-        const LfDepthRule rule{b.gdepth, 0u, b.k0, 8 + kb, b.bigdepth, static_cast<uint32_t>(tsym_big), token_round ? next_break : nullptr, period, static_cast<uint32_t>(n), b.bigper};
-        DK_TRY(lf_rerank(ctx, b.k0, 8, nullptr, b.bsym, 1, b.v0, nullptr, b.bpos, big_count, b.l_idx, b.l_pos, b.l_gid, b.l_sym, b.gstart, d_bwt, d_origin, rule));
-        DK_TRY(classify(big_min));
-        if (token_round) {
-            tokens_done = true;
-            want_tokens = false;
-            if (trace) fprintf(stderr, "[dk] L-first round %d: periodic groups (period %d) keyed by the tokens of their stretches' ends\n", round, period);
-        }
-        h += static_cast<uint32_t>(tsym_big);
-        if (const uint32_t seen = ctx->h_mail->deep_seen; fork_slots && nbig > 0 && nbig <= fork_slots && seen <= deep_cap && seen >= deep_done + (forked ? refork_groups : 1024u)) {
-            // (the count was read behind this round's k_lf_finish and k_lf_medium: every entry below it is complete -- those of the rounds by that read,
-            //  those an earlier pass on the side stream handed on by the stream's order.  Again whenever enough new groups have arrived.)
-            const uint32_t from_entry = deep_done;
-            deep_done = seen;
-            DK_HIP(ctx, hipEventRecord(ctx->ev_fork, st));
-            DK_HIP(ctx, hipStreamWaitEvent(ctx->side_stream, ctx->ev_fork, 0));
-            DK_TRY(order_deep(ctx->side_stream, from_entry, deep_done, false));
-            DK_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->side_stream));
-            forked = true;
-            if (trace) fprintf(stderr, "[dk] L-first: deep groups %u .. %u ordered beside the rounds\n", from_entry, deep_done);
-        }
-        stalled = nbig * 16 > big_count * 15 ? stalled + 1 : 0;
-        if (stalled && !tokens_done) want_tokens = true;
-        const uint32_t line_before = big_min;
-        // (a stalled round with tokens still to come: the tokens first -- a run of 3000 zeros is placed by one token round where the arena's kernels walk
-        //  3000 bytes per member: 6.7 against 8.0 ms for the 1e8-byte block around it)
-        DK_TRY(let_medium_groups_go(stalled != 0 && !(want_tokens && !tokens_done)));
-        if (big_min != line_before) stalled = 0;  // (the groups that have just left may have been the ones that did not split: count anew)
-        if (trace)
-            fprintf(stderr, "[dk] L-first round %d: big list %zu sorted on %d+%d bits -> depth %u (groups that were not periodic) live=%zu groups=%zu big=%zu in %zu groups\n", round, big_count, bsbits, kb, h,
-                    active, groups, nbig, nbiggroups);
+        DK_TRY(lf_round(r, round));
     }
-    // the deep groups of all rounds, from the arena: a wave per group of up to 64 members, then a workgroup per bigger (or handed-on) group -- what an
-    // early pass beside the rounds (order_deep above) has not taken already
-    if (forked) DK_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_join, 0));
-    forked = false;
-    DK_TRY(ctx->mail_read(&ctx->h_mail->lf));
-    if (lf.deep_count > deep_done && lf.deep_count <= deep_cap && lf.fallback == 0) {
-        if (trace) fprintf(stderr, "[dk] L-first: %u deep groups (%u of them ordered beside the rounds), %u members in the arena\n", lf.deep_count, deep_done, lf.arena_used);
-        DK_TRY(order_deep(st, deep_done, lf.deep_count, true));
-    }
-    // giant common extensions: measured by the whole grid, then the subgroup goes through k_lf_deep again (and may hand on a part of itself)
-    DK_TRY(ctx->mail_read(&ctx->h_mail->lf));
-    const bool any_giant = lf.giant_count[0] != 0 && lf.fallback == 0 && lf.deep_count <= deep_cap;
-    if (trace && any_giant) fprintf(stderr, "[dk] L-first: %u subgroups with giant common extensions go through the grid-wide measure\n", lf.giant_count[0]);
-    for (int r = 0; any_giant && r < giant_rounds; ++r) {
-        const LfGiantOut &in = giant[r & 1];
-        LfGiantOut out = giant[(r + 1) & 1];
-        if (r + 1 == giant_rounds) out.cap = 0;  // what is still giant after the last round makes the path give up
-        if (trace) {
-            uint32_t listed = 0;
-            DK_HIP(ctx, hipMemcpyAsync(&listed, in.count, sizeof listed, hipMemcpyDeviceToHost, st));
-            DK_HIP(ctx, hipStreamSynchronize(st));
-            if (listed) fprintf(stderr, "[dk] L-first: giant round %d: %u subgroups\n", r, listed);
-        }
-        DK_HIP(ctx, hipMemsetAsync(lce_res, 0xFF, static_cast<size_t>(LF_GIANT_ARENA) * sizeof(uint32_t), st));
-        DK_HIP(ctx, hipMemsetAsync(out.count, 0, sizeof(uint32_t), st));
-        DK_HIP(ctx, hipMemsetAsync(out.used, 0, sizeof(uint32_t), st));
-        {
-            LaunchScope ls(ctx, K_CHAIN, 0.0);
-            k_lf_lce<<<dim3(1024), dim3(256), 0, st>>>(in.idx, in.list, in.count, in.cap, d_text, static_cast<uint32_t>(n), lce_res);
-            k_lf_deep_block<LS_MAX, 256><<<dim3(256), dim3(256), 0, st>>>(in.idx, in.pos, in.sym, in.list, in.count, 0u, 0u, in.cap, d_text, static_cast<uint32_t>(n), d_bwt, d_origin,
-                                                                          d_fallback, lce_res, out, LDM_ALL, 0u);
-            k_lf_deep_block<LF_DEEP_MAX, 1024><<<dim3(64), dim3(1024), 0, st>>>(in.idx, in.pos, in.sym, in.list, in.count, 0u, 0u, in.cap, d_text, static_cast<uint32_t>(n), d_bwt, d_origin,
-                                                                                d_fallback, lce_res, out, LDM_ALL, static_cast<uint32_t>(LS_MAX));
-        }
-    }
-    DK_HIP(ctx, hipGetLastError());
-    DK_TRY(ctx->mail_read(&ctx->h_mail->lf));
-    deep_total = lf.deep_count;
-    // Giving up: a kernel found a list full (deep list, arena, giant list or its arena) or a common extension still giant after the last giant round
-    // (the fallback word) -- or the deep list's count went past its cap where no kernel said so (the host skipped the pass at the end above, and
-    // every group listed since the early pass would stay unordered).  No giant round at all (tuning build) leaves the giant list unordered too.
-    const bool gave_up = lf.fallback != 0 || deep_total > deep_cap || (any_giant && giant_rounds == 0);
-    if (any_giant) ctx->stats.sa_route |= DK_ROUTE_LFIRST_GIANT;
-    if (trace)
-        fprintf(stderr, "[dk] L-first: %u groups went the deep way%s\n", deep_total,
-                gave_up ? "; a list overflowed (deep groups, arena, giant list) or a common extension stayed giant: back to the suffix-array path" : "");
-    ctx->ws_release(mark);
-    if (deep_total) ctx->stats.sa_route |= DK_ROUTE_LFIRST_DEEP;
-    if (gave_up) return DK_OK;
-    *done = true;
-    return DK_OK;
+    return lf_last_passes(r);
 }

@@ -1556,13 +1556,18 @@ __global__ __launch_bounds__(RR_BLOCK) void k_plateau_compact(const uint32_t *__
     }
 }
 
-// enqueue the classification of the groups rerank() just produced and read back (active, groups, big slots, slots in groups > PL_MAX,
-// big groups)
-int classify_and_read(dk_ctx *ctx, size_t max_groups, uint32_t *gstart, uint32_t *bigidx, uint32_t *bigoff, size_t *active, size_t *groups,
-                      size_t *nbig, size_t *nmedium, size_t *nbiggroups, uint32_t ls_max = LS_MAX) {
+// what a classification reads back about the list rerank() / lf_rerank() just produced
+struct GroupCounts {
+    size_t active = 0, groups = 0;     // slots and groups of the list
+    size_t big = 0, big_groups = 0;    // slots in groups above the line, and those groups (classify_two_and_read: giant + medium)
+    size_t above_pl = 0;               // classify_and_read: slots in groups of more than PL_MAX members
+    size_t giant = 0, giant_groups = 0, medium = 0, medium_groups = 0;  // classify_two_and_read: above LF_MEDIUM_MAX | above the line, up to LF_MEDIUM_MAX
+};
+
+// enqueue the classification of the groups rerank() just produced and read the counts back
+int classify_and_read(dk_ctx *ctx, size_t max_groups, uint32_t *gstart, uint32_t *bigidx, uint32_t *bigoff, GroupCounts *out, uint32_t ls_max = LS_MAX) {
     hipStream_t st = ctx->stream;
     const size_t mark = ctx->ws_mark();
-    (void)max_groups;
     uint2 *part = ctx->ws_alloc<uint2>(BG_GRID);
     if (!part) return DK_E_NOMEM;
     Mail::Rounds *d_rounds = &ctx->d_mail->cls.rounds;
@@ -1576,91 +1581,190 @@ int classify_and_read(dk_ctx *ctx, size_t max_groups, uint32_t *gstart, uint32_t
     DK_HIP(ctx, hipGetLastError());
     const Mail::Rounds &r = ctx->h_mail->cls.rounds;
     DK_TRY(ctx->mail_read(&ctx->h_mail->cls.rounds));
-    *active = r.active;
-    *groups = r.groups;
-    *nbig = r.big_slots;
-    *nmedium = r.above_pl_slots;
-    *nbiggroups = r.big_groups;
+    *out = GroupCounts{};
+    out->active = r.active, out->groups = r.groups, out->big = r.big_slots, out->big_groups = r.big_groups, out->above_pl = r.above_pl_slots;
     ctx->ws_release(mark);
+    return DK_OK;
+}
+
+// How a stretch of the sort ends, for the functions that may end the whole call.  They return one of these or a (negative) DK_E_* code.
+enum SortStep : int {
+    WENT_ON = DK_OK,  // the suffix-array path goes on from here
+    L_COMPLETE = 1,   // the L-first path has written all of L and the origin: the call is over (the suffix array's buffer is scratch)
+    START_OVER = 2,   // the L-first path gave up half way (L has been written to): the suffix-array path, from the start, without it
+};
+
+// the block's dominant short period among 1 .. bound (k_period_probe's window counts): the smallest one with nearly (9/10) the most windows;
+// 0 when no 64-byte window is periodic at all.  *most: the largest count
+int dominant_period(const uint32_t *windows, int bound, uint32_t *most) {
+    *most = 0;
+    for (int q = 1; q <= bound; ++q) *most = std::max(*most, windows[q - 1]);
+    for (int q = 1; q <= bound && *most > 0; ++q)
+        if (static_cast<uint64_t>(windows[q - 1]) * 10 >= static_cast<uint64_t>(*most) * 9) return q;
+    return 0;
+}
+
+// enqueue the next-break position of every text position for `period` (2 n bytes read, 4 n written) into next_break (n words).  tile_first:
+// div_up(n, PB_TILE) words of scratch -- the caller's to allocate: it is the caller who knows what to do when they do not fit
+int enqueue_next_breaks(dk_ctx *ctx, const uint8_t *d_text, size_t n, int period, uint32_t *tile_first, uint32_t *next_break) {
+    const size_t ptiles = div_up(n, PB_TILE);
+    {
+        LaunchScope ls(ctx, K_PERIOD, 2.0 * n + 4.0 * n);
+        k_period_first<<<dim3(ptiles), dim3(256), 0, ctx->stream>>>(d_text, static_cast<uint32_t>(n), period, tile_first);
+        k_period_spine<<<dim3(1), dim3(1024), 0, ctx->stream>>>(tile_first, ptiles);
+        k_period_fill<<<dim3(ptiles), dim3(256), 0, ctx->stream>>>(d_text, static_cast<uint32_t>(n), period, tile_first, next_break);
+    }
+    DK_HIP(ctx, hipGetLastError());
     return DK_OK;
 }
 
 #include "lfirst.inc"
 
-int suffix_array_impl(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d_sa, uint8_t *d_bwt, uint32_t *d_origin, bool *bwt_written, bool allow_lfirst);
+// The buffers of a sort in progress: n entries each unless said otherwise, all from the context's workspace.  Which phase uses which for what:
+struct SaBuffers {
+    // initial_sort: its ping-pong pair; the sorted keys end up in `keys` and are read by the first rerank (first_rerank, or the L-first path's).
+    // general_round: keys = every slot's secondary key, keys_alt = the big list's keys.  pair_chains: the records' keys (ping-pong).
+    // The L-first path (lf_buffers_*): keys_alt = its big list's keys, and the 8 n bytes of `keys` cut up as the two functions say.
+    uint64_t *keys, *keys_alt;
+    // choose_prefix: the probe's hash table.  general_round / the L-first path: ping-pong partner of the big list's sort.  build_ranks: scratch of
+    // the inverse permutation (with keys_alt).  pair_chains: the verdict planes and a verdict byte per record.
+    uint64_t *keys_3;
+    // vals: the suffixes of the active list (from first_rerank on; a round reads it, sorts into vals_alt and reranks back into vals).  in-place
+    // rounds: the list, ping-pong.  initial_sort: ping-pong pair (the sorted suffixes themselves go to the suffix array).
+    uint32_t *vals, *vals_alt;
+    uint32_t *vals_3;  // general_round / the L-first path: the big list's suffixes.  pair_chains: the records' slots
+    // small_period_round: the next-break positions (no ranks exist yet).  build_ranks on: rank[i] = SA position of suffix i, or of the head of its
+    // group.  The L-first path: the SA position of every big-list place.
+    uint32_t *rank;
+    // pos / gid: SA position and group id of every slot of the active list; a round's rerank writes the next list's into pos_alt / gid_alt and
+    // swaps the pairs, and so does the compaction of the in-place rounds (pos).  pos_alt between reranks: a round's big-list slots (bslot),
+    // build_ranks' head positions, the pair chains' second slot buffer.  in-place rounds: gid / gid_alt hold the slots' group layout, ping-pong.
+    uint32_t *pos, *pos_alt, *gid, *gid_alt;
+    uint32_t *gstart, *bigidx;  // n / 2 + 2 each: every group's first slot (+ the end) | its index among the big groups
+    uint32_t *bigoff;           // n / 32 + 2: one entry per big group (more than LS_MAX members each; the L-first path may draw the line at 32)
+    uint8_t *sym, *sym_alt;     // callers that want L only (nullptr otherwise): the symbol in front of every slot's suffix, ping-pong like vals / vals_alt
+};
 
-}  // namespace
-
-int suffix_array_device(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d_sa, uint8_t *d_bwt, uint32_t *d_origin, bool *bwt_written) {
-    return suffix_array_impl(ctx, d_text, n, d_sa, d_bwt, d_origin, bwt_written, true);
+// today's order and sizes: the workspace is a bump allocator, so the peak (dk_stats: ws_peak_bytes) follows from them
+int alloc_buffers(dk_ctx *ctx, size_t n, bool with_sym, SaBuffers *b) {
+    b->keys = ctx->ws_alloc<uint64_t>(n), b->keys_alt = ctx->ws_alloc<uint64_t>(n), b->keys_3 = ctx->ws_alloc<uint64_t>(n);
+    b->vals = ctx->ws_alloc<uint32_t>(n), b->vals_alt = ctx->ws_alloc<uint32_t>(n);
+    b->vals_3 = ctx->ws_alloc<uint32_t>(n);
+    b->rank = ctx->ws_alloc<uint32_t>(n);
+    b->pos = ctx->ws_alloc<uint32_t>(n), b->pos_alt = ctx->ws_alloc<uint32_t>(n);
+    b->gid = ctx->ws_alloc<uint32_t>(n), b->gid_alt = ctx->ws_alloc<uint32_t>(n);
+    b->gstart = ctx->ws_alloc<uint32_t>(n / 2 + 2), b->bigidx = ctx->ws_alloc<uint32_t>(n / 2 + 2);
+    b->bigoff = ctx->ws_alloc<uint32_t>(n / 32 + 2);
+    if (!b->keys || !b->keys_alt || !b->keys_3 || !b->vals || !b->vals_alt || !b->vals_3 || !b->rank || !b->pos || !b->pos_alt || !b->gid || !b->gid_alt ||
+        !b->gstart || !b->bigidx || !b->bigoff)
+        return DK_E_NOMEM;
+    b->sym = with_sym ? ctx->ws_alloc<uint8_t>(n) : nullptr;
+    b->sym_alt = with_sym ? ctx->ws_alloc<uint8_t>(n) : nullptr;
+    return with_sym && (!b->sym || !b->sym_alt) ? DK_E_NOMEM : DK_OK;
 }
 
-namespace {
+// What both layouts of the L-first path share: the big list's keys and their sort's partner, its suffixes, its positions (the rank array's buffer:
+// no ranks exist, or none are needed any more), the group tables; and in the 8 n bytes of `keys` behind its first 5 n: the depth of every group
+// (n / 2 + 2 words) and of every big group (n / 32 + 2 words), and a byte per big group (periodic or not)
+LfBuffers lf_shared_buffers(const SaBuffers &s, size_t n) {
+    LfBuffers b;
+    b.k0 = s.keys_alt, b.k1 = s.keys_3, b.v0 = s.vals_3, b.bpos = s.rank;
+    b.gstart = s.gstart, b.bigidx = s.bigidx, b.bigoff = s.bigoff;
+    b.gdepth = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(s.keys) + ((5 * n + 15) & ~size_t(15)));
+    b.bigdepth = b.gdepth + n / 2 + 2;
+    b.bigper = reinterpret_cast<uint8_t *>(b.bigdepth + n / 32 + 2);
+    return b;
+}
+// L-first from the start (behind the initial sort).  Safe because the suffix-array path has not begun: its list buffers are all free, so the active
+// list takes the first set (vals_alt, pos, gid, sym) and the arena of the deep groups the second (pos_alt, gid_alt -- which this path does not use
+// otherwise).  The initial keys are read by the first rerank only; afterwards their buffer holds [0, 4 n) the next-break positions of a round with
+// tokens (the caller passes `keys` as such), [4 n, 5 n) the arena's symbols, then the tables of lf_shared_buffers
+LfBuffers lf_buffers_from_start(const SaBuffers &s, size_t n) {
+    LfBuffers b = lf_shared_buffers(s, n);
+    b.v1 = s.vals, b.bsym = s.sym_alt;
+    b.l_idx = s.vals_alt, b.l_pos = s.pos, b.l_gid = s.gid, b.l_sym = s.sym;
+    b.a_idx = s.pos_alt, b.a_pos = s.gid_alt, b.a_sym = reinterpret_cast<uint8_t *>(s.keys) + 4 * n;
+    return b;
+}
+// Taking over the suffix-array path's list between two rounds.  Safe because everything but the current list (vals, pos, gid, sym) is free there:
+// the new list goes to the other set (vals_alt, pos_alt, gid_alt, sym_alt); the key buffer that is not a sort's ping-pong partner holds the big
+// list's second suffix array and its symbols (4 n + n of its 8 n bytes) and the tables of lf_shared_buffers; the rank array becomes the big list's positions; and
+// the arena of the deep groups is the caller's own list, free once the first rerank has filtered it
+LfBuffers lf_buffers_take_over(const SaBuffers &s, size_t n) {
+    LfBuffers b = lf_shared_buffers(s, n);
+    b.v1 = reinterpret_cast<uint32_t *>(s.keys), b.bsym = reinterpret_cast<uint8_t *>(b.v1 + n);
+    b.l_idx = s.vals_alt, b.l_pos = s.pos_alt, b.l_gid = s.gid_alt, b.l_sym = s.sym_alt;
+    b.a_idx = s.vals, b.a_pos = s.pos, b.a_sym = s.sym;
+    return b;
+}
 
-int suffix_array_impl(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d_sa, uint8_t *d_bwt, uint32_t *d_origin, bool *bwt_written, bool allow_lfirst) {
-    if (bwt_written) *bwt_written = false;
-    if (n == 0 || n > 0x7FFFFFFEull) return ctx->fail(DK_E_ARG, "suffix_array: n out of range");
-    hipStream_t st = ctx->stream;
-    ctx->stats.rounds = 0;
-    ctx->stats.sort_passes = 0;
-    ctx->stats.sorted_elements = 0;
-    ctx->stats.sa_route = allow_lfirst ? 0u : static_cast<uint32_t>(DK_ROUTE_LFIRST_FALLBACK);
-    uint32_t &route = ctx->stats.sa_route;
-    const size_t mark = ctx->ws_mark();
+// One suffix sort in progress: what the phases below share.  A phase reads and writes this and nothing else.
+struct SaSort {
+    // the call.  d_bwt / d_origin: used where carry_bwt says that the caller wants L and the sort carries it along (BwtCarry); allow_lfirst: false
+    // in the second run, after the L-first path gave up half way
+    dk_ctx *ctx; hipStream_t st; const uint8_t *d_text; size_t n; uint32_t *d_sa; uint8_t *d_bwt; uint32_t *d_origin; bool carry_bwt, allow_lfirst, trace;
+    // read_alphabet: the code and what the probes saw (the counts themselves stay in the mailbox's host copy, alpha()).  bits per coded symbol
+    // (1..8), symbols per key: 8 (bytes) .. 32 (ACGT) .. 64 (binary); period_mode: DK_PERIOD; long_run: a run of 511 bytes, or more than 1 % of
+    // the block's 16-byte pieces inside runs: not the L-first path's kind of block
+    uint8_t code[256]; unsigned sigma; int bits, spk, period_mode; bool long_run;
+    // choose_prefix: symbols the initial sort covers; low key bits that hold the carried symbol (8 or 0); short_prefix: the probe's verdict: few
+    // suffixes will survive the initial sort; probe_big_share: its estimate of the share of the big groups
+    int spk_sort, key_shift; bool narrow_keys, short_prefix; double probe_big_share;
+    // progress.  h: symbols every group of the list is known to be equal in; have_ranks: build_ranks has run, rounds double on ranks;
+    // small_period_round: that phase took its round (find_long_period then has nothing to look for); long_period: find_long_period's, for
+    // doubling_rounds to use once h covers it (0: none); c: the counts of the active list
+    uint64_t h; bool have_ranks, small_period_round; uint32_t long_period; GroupCounts c;
+    SaBuffers b;
 
-    // 1. alphabet
-    Mail::Alphabet *d_alpha = &ctx->d_mail->alphabet;
-    const Mail::Alphabet &alpha = ctx->h_mail->alphabet;  // the host's copy: read until the end of the sort
-    DK_TRY(ctx->mail_fill(d_alpha, 0));  // (the histogram, the run probe's words and the period probe's)
-    const int period_mode = DK_KNOB("DK_PERIOD", 1);  // 0 = never a period round, 1 = where the probe finds an eighth of the block periodic, 2 = wherever it finds a window (test hook)
+    const Mail::Alphabet &alpha() const { return ctx->h_mail->alphabet; }  // the host's copy: read until the end of the sort
+    uint32_t &route() const { return ctx->stats.sa_route; }
+    uint32_t h_eff() const { return static_cast<uint32_t>(std::min<uint64_t>(h, n)); }
+    const uint32_t *narrow_starts() const { return narrow_keys ? ctx->d_mail->narrow_starts : nullptr; }
+};
+
+// 1. alphabet.  Expects nothing; leaves the code table, sigma / bits / spk and the probes' verdicts (sigma <= 1: bits and spk unset)
+int read_alphabet(SaSort &s) {
+    const size_t n = s.n;
+    Mail::Alphabet *d_alpha = &s.ctx->d_mail->alphabet;
+    DK_TRY(s.ctx->mail_fill(d_alpha, 0));  // (the histogram, the run probe's words and the period probe's)
+    s.period_mode = DK_KNOB("DK_PERIOD", 1);  // 0 = never a period round, 1 = where the probe finds an eighth of the block periodic, 2 = wherever it finds a window (test hook)
     {
-        LaunchScope ls(ctx, K_SYM_HIST, 1.0 * n);
+        LaunchScope ls(s.ctx, K_SYM_HIST, 1.0 * n);
         const size_t blocks = std::min<size_t>(div_up(n, 256 * 64), 2048);
-        k_sym_hist<<<dim3(blocks), dim3(256), 0, st>>>(d_text, n, d_alpha->hist);
-        if (d_bwt && allow_lfirst && n >= (1u << 16)) k_run_probe<<<dim3(div_up(div_up(n, 256), 256)), dim3(256), 0, st>>>(d_text, n, d_alpha->run_probe);
-        if (period_mode != 0 && n >= (1u << 12)) k_period_probe<<<dim3(div_up(div_up(n, 64), 256)), dim3(256), 0, st>>>(d_text, n, d_alpha->period_probe);
+        k_sym_hist<<<dim3(blocks), dim3(256), 0, s.st>>>(s.d_text, n, d_alpha->hist);
+        if (s.d_bwt && s.allow_lfirst && n >= (1u << 16)) k_run_probe<<<dim3(div_up(div_up(n, 256), 256)), dim3(256), 0, s.st>>>(s.d_text, n, d_alpha->run_probe);
+        if (s.period_mode != 0 && n >= (1u << 12)) k_period_probe<<<dim3(div_up(div_up(n, 64), 256)), dim3(256), 0, s.st>>>(s.d_text, n, d_alpha->period_probe);
     }
-    DK_TRY(ctx->mail_read(&ctx->h_mail->alphabet));
+    DK_TRY(s.ctx->mail_read(&s.ctx->h_mail->alphabet));
+    const Mail::Alphabet &alpha = s.alpha();
     // a run of 511 bytes, or more than 1 % of the block's 16-byte pieces inside runs: not the L-first path's kind of block
-    const bool long_run = alpha.run_probe[0] != 0 || static_cast<double>(alpha.run_probe[1]) * 16.0 > 0.01 * static_cast<double>(n);
     // ... but a block with a few long runs and next to nothing else inside runs (a zero-padded header in front of text) stays with it: the run's
-    // suffixes ride in the big list until the round stalls, and one token round (k_lf_tokens) places them by where the run ends
-    const bool run_heavy = static_cast<double>(alpha.run_probe[1]) * 16.0 > 0.01 * static_cast<double>(n);
-    uint8_t code[256];
-    unsigned sigma = 0;
-    for (int s = 0; s < 256; ++s) {
-        code[s] = static_cast<uint8_t>(sigma);
-        if (alpha.hist[s]) ++sigma;
+    // suffixes ride in the big list until the round stalls, and one token round (k_lf_tokens) places them by where the run ends (lfirst_from_start)
+    s.long_run = alpha.run_probe[0] != 0 || static_cast<double>(alpha.run_probe[1]) * 16.0 > 0.01 * static_cast<double>(n);
+    s.sigma = 0;
+    for (int c = 0; c < 256; ++c) {
+        s.code[c] = static_cast<uint8_t>(s.sigma);
+        if (alpha.hist[c]) ++s.sigma;
     }
-    if (sigma <= 1) {  // one distinct symbol: suffixes sort by length
-        k_sa_descending<<<dim3(div_up(n, 256)), dim3(256), 0, st>>>(d_sa, n);
-        DK_HIP(ctx, hipGetLastError());
-        return DK_OK;
-    }
-    const int bits = static_cast<int>(ceil_log2_u64(sigma));  // 1..8
-    const int spk = 64 / bits;                                // symbols per key: 8 (bytes) .. 32 (ACGT) .. 64 (binary)
+    if (s.sigma <= 1) return DK_OK;
+    s.bits = static_cast<int>(ceil_log2_u64(s.sigma));  // 1..8
+    s.spk = 64 / s.bits;                                // symbols per key: 8 (bytes) .. 32 (ACGT) .. 64 (binary)
+    return DK_OK;
+}
 
-    uint64_t *keys = ctx->ws_alloc<uint64_t>(n), *keys_alt = ctx->ws_alloc<uint64_t>(n), *keys_3 = ctx->ws_alloc<uint64_t>(n);
-    uint32_t *vals = ctx->ws_alloc<uint32_t>(n), *vals_alt = ctx->ws_alloc<uint32_t>(n);
-    uint32_t *vals_3 = ctx->ws_alloc<uint32_t>(n);
-    uint32_t *rank = ctx->ws_alloc<uint32_t>(n);
-    uint32_t *pos = ctx->ws_alloc<uint32_t>(n), *pos_alt = ctx->ws_alloc<uint32_t>(n);
-    uint32_t *gid = ctx->ws_alloc<uint32_t>(n), *gid_alt = ctx->ws_alloc<uint32_t>(n);
-    uint32_t *gstart = ctx->ws_alloc<uint32_t>(n / 2 + 2), *bigidx = ctx->ws_alloc<uint32_t>(n / 2 + 2);
-    uint32_t *bigoff = ctx->ws_alloc<uint32_t>(n / 32 + 2);  // one entry per big group (more than LS_MAX members each; the L-first path may draw the line at 32)
-    uint8_t *d_code = ctx->d_mail->code;
-    if (!keys || !keys_alt || !keys_3 || !vals || !vals_alt || !vals_3 || !rank || !pos || !pos_alt || !gid || !gid_alt ||
-        !gstart || !bigidx || !bigoff)
-        return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(d_code, code, sizeof code, hipMemcpyHostToDevice, st));
-    const bool trace = DK_KNOB("DK_TRACE", 0) != 0;
-
-    // 2. how long a prefix must the initial sort cover?  DK_PREFIX: 0 = always the full key, 1 = ask the sample (default),
-    //    2 / 3 = always the shortest / second candidate (test hooks: every input then takes the short-prefix path; the second one is
-    //    the five-pass sort whose narrow keys need the bucket starts)
+// 2. how long a prefix must the initial sort cover?  Expects the alphabet, carry_bwt and the buffers; leaves spk_sort, key_shift, narrow_keys,
+//    short_prefix, probe_big_share, and the code tables on the device.
+//    DK_PREFIX: 0 = always the full key, 1 = ask the sample (default),
+//    2 / 3 = always the shortest / second candidate (test hooks: every input then takes the short-prefix path; the second one is
+//    the five-pass sort whose narrow keys need the bucket starts)
+int choose_prefix(SaSort &s) {
+    const size_t n = s.n;
+    const int bits = s.bits, spk = s.spk;
+    uint8_t *d_code = s.ctx->d_mail->code;
+    DK_HIP(s.ctx, hipMemcpyAsync(d_code, s.code, sizeof s.code, hipMemcpyHostToDevice, s.st));
     const int prefix_mode = DK_KNOB("DK_PREFIX", 1);
-    int spk_sort = spk;
-    double probe_big_share = 0.0;
+    s.spk_sort = spk;
+    s.probe_big_share = 0.0;
     if (prefix_mode != 0 && (n >= (1u << 22) || prefix_mode >= 2)) {
         ProbeCands cands{0, {0, 0, 0, 0}};
         for (int passes = 4; passes <= 7 && cands.count < PP_MAX_CAND; ++passes) {
@@ -1668,568 +1772,599 @@ int suffix_array_impl(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d_
             if (k >= 1 && k < spk && (cands.count == 0 || cands.sym[cands.count - 1] != k)) cands.sym[cands.count++] = k;
         }
         if (cands.count > 0 && prefix_mode >= 2 && prefix_mode <= 4) {  // (4: the third candidate, six passes -- an experiment hook)
-            spk_sort = cands.sym[std::min(prefix_mode - 2, cands.count - 1)];
+            s.spk_sort = cands.sym[std::min(prefix_mode - 2, cands.count - 1)];
         } else if (cands.count > 0) {
             const uint32_t m = static_cast<uint32_t>(std::min<double>(n / 2.0, 10.0 * std::sqrt(static_cast<double>(n))));
             const uint32_t span = static_cast<uint32_t>(n / m);
             uint32_t table_size = 1;
             while (table_size < 2u * cands.count * m) table_size <<= 1;
-            uint64_t *table = keys_3;  // free until the first big-group sort
-            uint32_t *d_dups = ctx->d_mail->dups;
-            const uint32_t *dups = ctx->h_mail->dups;
-            DK_HIP(ctx, hipMemsetAsync(table, 0xFF, static_cast<size_t>(table_size) * sizeof(uint64_t), st));
-            DK_TRY(ctx->mail_fill(&ctx->d_mail->dups, 0));
+            uint64_t *table = s.b.keys_3;  // free until the first big-group sort
+            uint32_t *d_dups = s.ctx->d_mail->dups;
+            const uint32_t *dups = s.ctx->h_mail->dups;
+            DK_HIP(s.ctx, hipMemsetAsync(table, 0xFF, static_cast<size_t>(table_size) * sizeof(uint64_t), s.st));
+            DK_TRY(s.ctx->mail_fill(&s.ctx->d_mail->dups, 0));
             {
-                LaunchScope ls(ctx, K_PREFIX_PROBE, 16.0 * m);
-                k_prefix_probe<<<dim3(div_up(m, 256)), dim3(256), 0, st>>>(d_text, n, d_code, bits, spk, m, span, cands, table, table_size - 1,
-                                                                          d_dups);
+                LaunchScope ls(s.ctx, K_PREFIX_PROBE, 16.0 * m);
+                k_prefix_probe<<<dim3(div_up(m, 256)), dim3(256), 0, s.st>>>(s.d_text, n, d_code, bits, spk, m, span, cands, table, table_size - 1,
+                                                                            d_dups);
             }
-            DK_HIP(ctx, hipGetLastError());
-            DK_TRY(ctx->mail_read(&ctx->h_mail->dups));
+            DK_HIP(s.ctx, hipGetLastError());
+            DK_TRY(s.ctx->mail_read(&s.ctx->h_mail->dups));
             // m is 10 sqrt(n), so c equal pairs in the sample say that about c / 50 of ALL suffixes share their prefix with another one.
             // A radix pass over everything costs what a text round costs for about an eighth of it: up to 4 equal pairs (8 %) the
             // shorter prefix wins, its survivors go through the text round
             const uint32_t max_dups = static_cast<uint32_t>(DK_KNOB("DK_PROBE_DUPS", 4));
             for (int c = 0; c < cands.count; ++c)
-                if (dups[c] <= max_dups) { spk_sort = cands.sym[c]; break; }
+                if (dups[c] <= max_dups) { s.spk_sort = cands.sym[c]; break; }
             // the deepest candidate is (about) the key of the initial sort: a sample of 10 sqrt(n) suffixes meets an equal one there about as
             // often as a suffix sits in a group of more than sqrt(n) / 10 members -- the share of the big groups
-            probe_big_share = static_cast<double>(dups[cands.count - 1]) / m;
-            if (trace)
+            s.probe_big_share = static_cast<double>(dups[cands.count - 1]) / m;
+            if (s.trace)
                 fprintf(stderr, "[dk] prefix probe: %u samples, equal pairs at %d/%d/%d/%d symbols: %u %u %u %u -> sort %d of %d symbols\n", m,
-                        cands.sym[0], cands.sym[1], cands.sym[2], cands.sym[3], dups[0], dups[1], dups[2], dups[3], spk_sort, spk);
+                        cands.sym[0], cands.sym[1], cands.sym[2], cands.sym[3], dups[0], dups[1], dups[2], dups[3], s.spk_sort, spk);
         }
     }
-    // BWT on the way (BwtCarry): callers that want L.  The key gives up its low byte to the code of the symbol in front of the suffix, so
-    // the initial sort covers at most 56 bits = seven passes instead of eight; nothing is gathered from the text afterwards.
-    // DK_BWT_CARRY=0 (test hook): sort the full key and let the caller gather L from the suffix array.
-    const bool carry_enabled = DK_KNOB("DK_BWT_CARRY", 1) != 0;
-    const bool carry_bwt = carry_enabled && d_bwt && d_origin && bwt_written;
     // A block that is periodic nearly everywhere (nine tenths of its 64-byte windows follow one period p <= 8: a^n b, (ab)^n, a zeroed buffer)
     // needs no more of the initial sort than the period string itself: the period round (4b) places every suffix of a stretch whatever the
     // depth, as long as the depth covers p symbols -- one or two passes instead of seven (a^n b, 1e8 bytes: 15.1 -> 7 ms).
-    if (period_mode != 0 && n >= (1u << 16)) {
-        const uint32_t *pc = alpha.period_probe;
+    if (s.period_mode != 0 && n >= (1u << 16)) {
         uint32_t cmax = 0;
-        for (int q = 1; q <= 8; ++q) cmax = std::max(cmax, pc[q - 1]);
-        if (static_cast<uint64_t>(cmax) * 64 * 10 >= static_cast<uint64_t>(n) * 9) {
-            int q = 1;
-            while (static_cast<uint64_t>(pc[q - 1]) * 10 < static_cast<uint64_t>(cmax) * 9) ++q;
+        const int q = dominant_period(s.alpha().period_probe, 8, &cmax);
+        if (q && static_cast<uint64_t>(cmax) * 64 * 10 >= static_cast<uint64_t>(n) * 9) {
             const int passes = (q * bits + 7) / 8;
             const int k = std::min(spk, (8 * passes) / bits);
-            if (k >= q && k < spk_sort) {
-                spk_sort = k;
-                if (trace) fprintf(stderr, "[dk] period %d nearly everywhere (%u of %zu windows): the initial sort takes %d symbols\n", q, cmax, n / 64, k);
+            if (k >= q && k < s.spk_sort) {
+                s.spk_sort = k;
+                if (s.trace) fprintf(stderr, "[dk] period %d nearly everywhere (%u of %zu windows): the initial sort takes %d symbols\n", q, cmax, n / 64, k);
             }
         }
     }
-    const bool short_prefix = spk_sort < spk;  // the probe's verdict: few suffixes will survive the initial sort
-    if (carry_bwt) spk_sort = std::min(spk_sort, 56 / bits);  // (a key merely shortened to make room for the carried byte keeps the rank path)
-    uint8_t *sym = nullptr, *sym_alt = nullptr;
-    uint8_t *d_inv = ctx->d_mail->inv;
-    if (carry_bwt) {
-        sym = ctx->ws_alloc<uint8_t>(n);
-        sym_alt = ctx->ws_alloc<uint8_t>(n);
-        if (!sym || !sym_alt) return DK_E_NOMEM;
+    s.short_prefix = s.spk_sort < spk;  // the probe's verdict: few suffixes will survive the initial sort
+    if (s.carry_bwt) {
+        s.spk_sort = std::min(s.spk_sort, 56 / bits);  // (a key merely shortened to make room for the carried byte keeps the rank path)
         uint8_t inv[256] = {0};
         for (int c = 255; c >= 0; --c)
-            if (alpha.hist[c]) inv[code[c]] = static_cast<uint8_t>(c);
-        std::memcpy(ctx->h_mail->inv, inv, sizeof inv);
-        DK_HIP(ctx, hipMemcpyAsync(d_inv, ctx->h_mail->inv, sizeof inv, hipMemcpyHostToDevice, st));
+            if (s.alpha().hist[c]) inv[s.code[c]] = static_cast<uint8_t>(c);
+        std::memcpy(s.ctx->h_mail->inv, inv, sizeof inv);
+        DK_HIP(s.ctx, hipMemcpyAsync(s.ctx->d_mail->inv, s.ctx->h_mail->inv, sizeof inv, hipMemcpyHostToDevice, s.st));
     }
-    const int key_shift = carry_bwt ? 8 : 0;
-    const bool narrow_keys = DK_KNOB("DK_NARROW_KEYS", 1) != 0 && bits * spk_sort <= 40;
-    uint32_t *d_starts = ctx->d_mail->narrow_starts;
+    s.key_shift = s.carry_bwt ? 8 : 0;
+    s.narrow_keys = DK_KNOB("DK_NARROW_KEYS", 1) != 0 && bits * s.spk_sort <= 40;
+    return DK_OK;
+}
 
-    // 3. initial sort; its first pass builds the keys from the text (no key array is ever written unsorted)
-    {
-        TextKeys tk;
-        tk.t = d_text; tk.n = n; tk.code = d_code; tk.bits = bits; tk.spk = spk_sort; tk.with_prev = carry_bwt ? 1 : 0;
-        // the last pass leaves every suffix at its slot of the suffix array itself (and the symbol in front of it in L): what the first
-        // rerank finds final is final where it stands -- it stores nothing for it, and a tile without a survivor costs it nothing
-        SortFinalOut fin;
-        fin.vals = d_sa;
-        if (carry_bwt) { fin.bwt = d_bwt; fin.inv_code = d_inv; fin.origin = d_origin; }
-        // up to 40 sorted bits (short prefixes: random bytes, small alphabets): the last pass leaves 32-bit keys for the first rerank
-        if (narrow_keys) { fin.narrow_shift = key_shift; fin.bucket_starts = d_starts; }
-        DK_TRY(sort_pairs(ctx, keys, keys_alt, vals, vals_alt, n, key_shift, bits * spk_sort + key_shift, &tk, &fin));
-    }
+// 3. initial sort; its first pass builds the keys from the text (no key array is ever written unsorted).  Expects choose_prefix's verdicts; leaves
+//    the sorted keys in b.keys, every suffix at its slot of the suffix array and (carry_bwt) its symbol in L
+int initial_sort(SaSort &s) {
+    TextKeys tk;
+    tk.t = s.d_text; tk.n = s.n; tk.code = s.ctx->d_mail->code; tk.bits = s.bits; tk.spk = s.spk_sort; tk.with_prev = s.carry_bwt ? 1 : 0;
+    // the last pass leaves every suffix at its slot of the suffix array itself (and the symbol in front of it in L): what the first
+    // rerank finds final is final where it stands -- it stores nothing for it, and a tile without a survivor costs it nothing
+    SortFinalOut fin;
+    fin.vals = s.d_sa;
+    if (s.carry_bwt) { fin.bwt = s.d_bwt; fin.inv_code = s.ctx->d_mail->inv; fin.origin = s.d_origin; }
+    // up to 40 sorted bits (short prefixes: random bytes, small alphabets): the last pass leaves 32-bit keys for the first rerank
+    if (s.narrow_keys) { fin.narrow_shift = s.key_shift; fin.bucket_starts = s.ctx->d_mail->narrow_starts; }
+    DK_TRY(sort_pairs(s.ctx, s.b.keys, s.b.keys_alt, s.b.vals, s.b.vals_alt, s.n, s.key_shift, s.bits * s.spk_sort + s.key_shift, &tk, &fin));
+    if (s.short_prefix) s.route() |= DK_ROUTE_SHORT_PREFIX;
+    if (s.narrow_keys) s.route() |= DK_ROUTE_NARROW_KEYS;
+    return DK_OK;
+}
 
-    if (short_prefix) route |= DK_ROUTE_SHORT_PREFIX;
-    if (narrow_keys) route |= DK_ROUTE_NARROW_KEYS;
-    // 3b. A caller that wants L, not the suffix array: only the groups with different symbols in front are refined, from the text alone
-    //     (lfirst.inc).  DK_LFIRST: 0 = never, 1 = blocks of at least 2^16 bytes (default), 2 = always (test hook).
+// 3b. A caller that wants L, not the suffix array: only the groups with different symbols in front are refined, from the text alone
+//     (lfirst.inc).  DK_LFIRST: 0 = never, 1 = blocks of at least 2^16 bytes (default), 2 = always (test hook).
+//     Expects the initial sort's keys untouched.  WENT_ON: not taken, or it stopped before writing anything the suffix-array path reads.
+int lfirst_from_start(SaSort &s) {
+    const size_t n = s.n;
+    const Mail::Alphabet &alpha = s.alpha();
     const int lf_mode = DK_KNOB("DK_LFIRST", 1);
     // Not where the probe saw more than 60 % of its sample in big groups (lfirst_path would find the same after a rerank, see there), not
     // where runs of one byte value are common (k_run_probe), and not behind a shortened key: next to nothing survives such a sort, and the uniformity test costs the first rerank more than it saves
     // (2^30 random bytes: reduce 2.3 against 1.1 ms, nothing else differs; 2^28 {A,C,G,T}: 8.63 against 8.56 ms).
     // the block's dominant short period, if it has any periodic 64-byte window at all (k_period_probe): the smallest p with nearly the most windows
-    int lf_period = 0;
-    if (period_mode != 0) {
-        const uint32_t *pc = alpha.period_probe;
-        uint32_t cmax = 0;
-        for (int q = 1; q <= 7; ++q) cmax = std::max(cmax, pc[q - 1]);
-        for (int q = 1; q <= 7 && cmax > 0 && !lf_period; ++q)
-            if (static_cast<uint64_t>(pc[q - 1]) * 10 >= static_cast<uint64_t>(cmax) * 9) lf_period = q;
-    }
+    uint32_t most = 0;
+    const int lf_period = s.period_mode != 0 ? dominant_period(alpha.period_probe, 7, &most) : 0;
     // with tokens to settle them in one round (lfirst.inc: LfTokens), runs may hold up to a twentieth of the block (50 MB of real text -- indentation,
     // rulers -- 1.3 %: 10.9 ms this way against 12.7; 5 MB of 90 % zero bytes, 24 %, stay with prefix doubling); without, a hundredth and no long run
-    const bool lf_runs_ok = lf_period > 0 ? static_cast<double>(alpha.run_probe[1]) * 16.0 <= 0.05 * static_cast<double>(n) : !long_run;
-    (void)run_heavy;
-    if (carry_bwt && allow_lfirst && lf_mode != 0 && n >= 64 && (lf_mode == 2 || (n >= (1u << 16) && probe_big_share <= 0.6 && !short_prefix && lf_runs_ok))) {
-        // (the arena of the deep groups: the second list buffers of the suffix-array path, which this path does not use, and the upper half of the
-        //  initial keys' buffer -- the lower half holds the next-break positions of a token round)
-        //  initial keys' buffer -- 8 n bytes: [0, 4 n) the next-break positions of a round with tokens, [4 n, 5 n) the arena's symbols, then the depth of every
-        //  group (n / 2 + 2 words) and of every big group (n / 32 + 2 words), and a byte per big group (periodic or not)
-        uint8_t *kb8 = reinterpret_cast<uint8_t *>(keys);
-        uint32_t *gdepth = reinterpret_cast<uint32_t *>(kb8 + ((5 * n + 15) & ~size_t(15)));
-        const LfBuffers b{keys_alt, keys_3, vals_3, vals, rank, sym_alt, vals_alt, pos, gid, sym, gstart, bigidx, bigoff, pos_alt, gid_alt, kb8 + 4 * n, gdepth, gdepth + n / 2 + 2, reinterpret_cast<uint8_t *>(gdepth + n / 2 + 2 + n / 32 + 2)};
-        bool done = false, pristine = true;
-        route |= DK_ROUTE_LFIRST;
-        // (the initial keys are read by the first rerank only: their buffer holds the next-break positions of a token round later)
-        // tokens in the first round (instead of after the first stalled one) where a thousandth of the block lies inside runs of one byte value or in
-        // periodic 64-byte windows: indentation and rulers in real text
-        const uint32_t *pc = alpha.period_probe;
-        const bool tokens_early = lf_period > 0 && DK_KNOB("DK_LF_TOKENS_EARLY", 1) != 0 &&
-                                  (static_cast<double>(alpha.run_probe[1]) * 16.0 > 0.001 * static_cast<double>(n) || static_cast<double>(pc[lf_period - 1]) * 64.0 > 0.001 * static_cast<double>(n));
-        DK_TRY(lfirst_path(ctx, d_text, n, keys, key_shift, narrow_keys ? d_starts : nullptr, d_sa, d_bwt, d_origin, b, static_cast<uint32_t>(spk_sort), trace, lf_mode == 2, &done, &pristine,
-                           nullptr, lf_period, reinterpret_cast<uint32_t *>(keys), tokens_early));
-        if (done) {
-            ctx->ws_release(mark);
-            *bwt_written = true;
-            return DK_OK;
-        }
-        route = (route & ~static_cast<uint32_t>(DK_ROUTE_LFIRST | DK_ROUTE_LFIRST_BIG_ROUND | DK_ROUTE_LFIRST_DEEP | DK_ROUTE_PERIOD_ROUND)) | DK_ROUTE_LFIRST_FALLBACK;
-        if (!pristine) {  // it gave up half way (L has been written to): the suffix-array path, from the start
-            ctx->ws_release(mark);
-            return suffix_array_impl(ctx, d_text, n, d_sa, d_bwt, d_origin, bwt_written, false);
-        }
+    const bool lf_runs_ok = lf_period > 0 ? static_cast<double>(alpha.run_probe[1]) * 16.0 <= 0.05 * static_cast<double>(n) : !s.long_run;
+    if (!(s.carry_bwt && s.allow_lfirst && lf_mode != 0 && n >= 64 && (lf_mode == 2 || (n >= (1u << 16) && s.probe_big_share <= 0.6 && !s.short_prefix && lf_runs_ok))))
+        return WENT_ON;
+    s.route() |= DK_ROUTE_LFIRST;
+    LfFrom from;
+    from.init_keys = s.b.keys, from.key_shift = s.key_shift, from.narrow_starts = s.narrow_starts(), from.d_sa = s.d_sa;
+    from.h0 = static_cast<uint32_t>(s.spk_sort);
+    // (the initial keys are read by the first rerank only: their buffer holds the next-break positions of a token round later)
+    // tokens in the first round (instead of after the first stalled one) where a thousandth of the block lies inside runs of one byte value or in
+    // periodic 64-byte windows: indentation and rulers in real text
+    LfTokenPlan plan;
+    plan.period = lf_period, plan.next_break = reinterpret_cast<uint32_t *>(s.b.keys);
+    plan.tokens_early = lf_period > 0 && DK_KNOB("DK_LF_TOKENS_EARLY", 1) != 0 &&
+                        (static_cast<double>(alpha.run_probe[1]) * 16.0 > 0.001 * static_cast<double>(n) || static_cast<double>(alpha.period_probe[lf_period - 1]) * 64.0 > 0.001 * static_cast<double>(n));
+    const int step = lfirst_path(s.ctx, s.d_text, n, s.d_bwt, s.d_origin, lf_buffers_from_start(s.b, n), from, plan, s.trace, lf_mode == 2);
+    if (step < 0 || step == L_COMPLETE) return step;
+    s.route() = (s.route() & ~static_cast<uint32_t>(DK_ROUTE_LFIRST | DK_ROUTE_LFIRST_BIG_ROUND | DK_ROUTE_LFIRST_DEEP | DK_ROUTE_PERIOD_ROUND)) | DK_ROUTE_LFIRST_FALLBACK;
+    return step;
+}
+
+// 4. first rerank (slots are SA positions).  No rank array yet: the suffixes that survive the initial sort are first extended from
+//    the text (5a), which needs no ranks, and the rank array is built once, late, for whatever survives that (5b) -- one inverse
+//    permutation for the whole sort instead of one here plus tens of millions of random rank stores in the next round.
+//    Expects the initial sort's keys; leaves the active list in vals / pos / gid / sym, its counts, and h = the sorted prefix.
+int first_rerank(SaSort &s) {
+    SaBuffers &b = s.b;
+    const BwtCarry first_bc{s.key_shift, s.carry_bwt ? s.d_bwt : nullptr, s.ctx->d_mail->inv, s.d_origin, nullptr, b.sym};
+    DK_TRY(rerank(s.ctx, b.keys, s.d_sa, nullptr, s.n, nullptr, nullptr, s.d_sa, b.vals_alt, b.pos, b.gid, b.gstart, first_bc, s.narrow_starts()));
+    DK_TRY(classify_and_read(s.ctx, s.n / 2, b.gstart, b.bigidx, b.bigoff, &s.c));
+    std::swap(b.vals, b.vals_alt);  // vals = suffix indices of the active list
+    s.h = static_cast<uint64_t>(s.spk_sort);
+    if (s.trace)
+        fprintf(stderr, "[dk] n=%zu sigma=%u bits=%d spk=%d%s: after init sort active=%zu groups=%zu big=%zu\n", s.n, s.sigma, s.bits, s.spk_sort,
+                s.carry_bwt ? " +prev" : "", s.c.active, s.c.groups, s.c.big);
+    return DK_OK;
+}
+
+// one general round: secondary keys (ranks h further on, or the next tsym symbols of the text) -> every group sorted inside its
+// own slot range (small groups in LDS, big ones through the global sort) -> rerank.  *advanced: the symbols the round added (text
+// rounds: the big groups' keys may hold fewer symbols than the small groups' -- the depth every group is known to is the smaller).
+// Expects the active list and its counts (and the ranks when tsym == 0); leaves the next list and its counts.  h is the caller's to advance.
+int general_round(SaSort &s, int tsym, int *advanced, int period = 0, const uint32_t *next_break = nullptr) {
+    SaBuffers &b = s.b;
+    const size_t n = s.n, active = s.c.active, nbig = s.c.big;
+    const int bsbits = s.c.big_groups > 1 ? static_cast<int>(ceil_log2_u64(s.c.big_groups)) : 1;  // bits of a big group's dense index
+    int kbits, kb;
+    const bool raw_text = tsym > 0 && (s.bits >= 5 || period > 0);  // eight raw bytes per key beat the code table unless the alphabet is small
+    const int tbits = raw_text ? 8 : s.bits;
+    const int ebits = static_cast<int>(ceil_log2_u64(static_cast<uint64_t>(n) + 1));
+    if (period > 0) {
+        // the period round: tokens (direction, length to the break, bytes from the break on) in 64-bit keys; the big list takes their
+        // leading bits down to the first byte behind the break when the symbol in front still fits below them, else what fits.  The depth
+        // every group is known to stays h: equal tokens say "equal up to the break" and the break may come right behind h.
+        tsym = 8;
+        kbits = 64;
+        kb = 1 + ebits + 8;
+        if (kb + bsbits + 8 > 64) kb = std::max(1 + ebits, 56 - bsbits);
+        if (kb + bsbits > 63) kb = 63 - bsbits;
+        if (advanced) *advanced = 0;
+    } else if (tsym > 0) {
+        if (raw_text) tsym = 8;
+        kbits = tsym * tbits;
+        // the big list's key: (offset in the big list) above the leading symbols of the secondary key -- at most 32 bits of it: every
+        // digit of a list this short costs three launches, and what four more bytes leave unresolved the next round takes
+        const int tsym_big = std::min(std::min(tsym, (63 - bsbits) / tbits), std::max(1, 32 / tbits));
+        kb = tsym_big * tbits;
+        if (advanced) *advanced = nbig > 0 ? tsym_big : tsym;
+    } else {
+        kbits = kb = static_cast<int>(ceil_log2_u64(static_cast<uint64_t>(n) + s.h_eff()));
     }
-
-    // 4. first rerank (slots are SA positions).  No rank array yet: the suffixes that survive the initial sort are first extended from
-    //    the text (5a), which needs no ranks, and the rank array is built once, late, for whatever survives that (5b) -- one inverse
-    //    permutation for the whole sort instead of one here plus tens of millions of random rank stores in the next round.
-    size_t active = 0, groups = 0, nbig = 0, nmedium = 0, nbiggroups = 0;
-    bool have_ranks = false;
-    const BwtCarry first_bc{key_shift, carry_bwt ? d_bwt : nullptr, d_inv, d_origin, nullptr, sym};
-    DK_TRY(rerank(ctx, keys, d_sa, nullptr, n, nullptr, nullptr, d_sa, vals_alt, pos, gid, gstart, first_bc, narrow_keys ? d_starts : nullptr));
-    DK_TRY(classify_and_read(ctx, n / 2, gstart, bigidx, bigoff, &active, &groups, &nbig, &nmedium, &nbiggroups));
-    std::swap(vals, vals_alt);  // vals = suffix indices of the active list
-
-    uint64_t h = static_cast<uint64_t>(spk_sort);
-    if (trace)
-        fprintf(stderr, "[dk] n=%zu sigma=%u bits=%d spk=%d%s: after init sort active=%zu groups=%zu big=%zu\n", n, sigma, bits, spk_sort,
-                carry_bwt ? " +prev" : "", active, groups, nbig);
-
-    // one general round: secondary keys (ranks h further on, or the next tsym symbols of the text) -> every group sorted inside its
-    // own slot range (small groups in LDS, big ones through the global sort) -> rerank.  Returns the symbols the round added (text
-    // rounds: the big groups' keys may hold fewer symbols than the small groups' -- the depth every group is known to is the smaller).
-    auto run_round = [&](int tsym, int *advanced, int period = 0, const uint32_t *next_break = nullptr) -> int {
-        const uint32_t h_eff = static_cast<uint32_t>(std::min<uint64_t>(h, n));
-        const int bsbits = nbiggroups > 1 ? static_cast<int>(ceil_log2_u64(nbiggroups)) : 1;  // bits of a big group's dense index
-        int kbits, kb;
-        const bool raw_text = tsym > 0 && (bits >= 5 || period > 0);  // eight raw bytes per key beat the code table unless the alphabet is small
-        const int tbits = raw_text ? 8 : bits;
-        const int ebits = static_cast<int>(ceil_log2_u64(static_cast<uint64_t>(n) + 1));
-        if (period > 0) {
-            // the period round: tokens (direction, length to the break, bytes from the break on) in 64-bit keys; the big list takes their
-            // leading bits down to the first byte behind the break when the symbol in front still fits below them, else what fits.  The depth
-            // every group is known to stays h: equal tokens say "equal up to the break" and the break may come right behind h.
-            tsym = 8;
-            kbits = 64;
-            kb = 1 + ebits + 8;
-            if (kb + bsbits + 8 > 64) kb = std::max(1 + ebits, 56 - bsbits);
-            if (kb + bsbits > 63) kb = 63 - bsbits;
-            if (advanced) *advanced = 0;
-        } else if (tsym > 0) {
-            if (raw_text) tsym = 8;
-            kbits = tsym * tbits;
-            // the big list's key: (offset in the big list) above the leading symbols of the secondary key -- at most 32 bits of it: every
-            // digit of a list this short costs three launches, and what four more bytes leave unresolved the next round takes
-            const int tsym_big = std::min(std::min(tsym, (63 - bsbits) / tbits), std::max(1, 32 / tbits));
-            kb = tsym_big * tbits;
-            if (advanced) *advanced = nbig > 0 ? tsym_big : tsym;
-        } else {
-            kbits = kb = static_cast<int>(ceil_log2_u64(static_cast<uint64_t>(n) + h_eff));
-        }
-        const TextSource ts{d_text, d_code, raw_text ? 0 : bits, tsym, period > 0 ? next_break : nullptr, period, ebits};
-        route |= period > 0 ? DK_ROUTE_PERIOD_ROUND : tsym > 0 ? DK_ROUTE_TEXT_ROUND : DK_ROUTE_GENERAL_ROUND;
-        if (nbig > 0) route |= DK_ROUTE_BIG_GROUPS;
-        const int big_carry = carry_bwt && kb + bsbits + 8 <= 64 ? 1 : 0;  // the big list's keys have room for the symbol in front
-        uint32_t *bslot = pos_alt;  // written by the rerank at the end of the round only: free until k_big_back has read it
+    const TextSource ts{s.d_text, s.ctx->d_mail->code, raw_text ? 0 : s.bits, tsym, period > 0 ? next_break : nullptr, period, ebits};
+    s.route() |= period > 0 ? DK_ROUTE_PERIOD_ROUND : tsym > 0 ? DK_ROUTE_TEXT_ROUND : DK_ROUTE_GENERAL_ROUND;
+    if (nbig > 0) s.route() |= DK_ROUTE_BIG_GROUPS;
+    const int big_carry = s.carry_bwt && kb + bsbits + 8 <= 64 ? 1 : 0;  // the big list's keys have room for the symbol in front
+    uint32_t *bslot = b.pos_alt;  // written by the rerank at the end of the round only: free until k_big_back has read it
+    {
+        LaunchScope ls(s.ctx, K_ROUND_LOCAL, 8.0 * active + 4.0 * active + 12.0 * active);
+        const auto round_local = tsym > 0 ? k_round_local<true> : k_round_local<false>;
+        round_local<<<dim3(div_up(active, LS_TILE)), dim3(LS_BLOCK), 0, s.st>>>(b.vals, b.gid, b.gstart, b.bigidx, b.bigoff, b.rank, static_cast<uint32_t>(n), s.h_eff(), kbits, kb, big_carry,
+                                                                                active, b.keys, b.vals_alt, b.keys_alt, b.vals_3, bslot, ts, b.sym, b.sym_alt);
+    }
+    DK_HIP(s.ctx, hipGetLastError());
+    if (nbig > 0) {
+        uint64_t *bk = b.keys_alt, *bk_alt = b.keys_3;
+        uint32_t *bv = b.vals_3, *bv_alt = b.vals;  // the round's input list has been read (k_round_local); the rerank rewrites it below
+        DK_TRY(sort_pairs(s.ctx, bk, bk_alt, bv, bv_alt, nbig, 8 * big_carry, kb + bsbits + 8 * big_carry));
         {
-            LaunchScope ls(ctx, K_ROUND_LOCAL, 8.0 * active + 4.0 * active + 12.0 * active);
-            if (tsym > 0)
-                k_round_local<true><<<dim3(div_up(active, LS_TILE)), dim3(LS_BLOCK), 0, st>>>(
-                    vals, gid, gstart, bigidx, bigoff, rank, static_cast<uint32_t>(n), h_eff, kbits, kb, big_carry, active, keys, vals_alt, keys_alt, vals_3, bslot, ts, sym, sym_alt);
-            else
-                k_round_local<false><<<dim3(div_up(active, LS_TILE)), dim3(LS_BLOCK), 0, st>>>(
-                    vals, gid, gstart, bigidx, bigoff, rank, static_cast<uint32_t>(n), h_eff, kbits, kb, big_carry, active, keys, vals_alt, keys_alt, vals_3, bslot, ts, sym, sym_alt);
+            LaunchScope ls(s.ctx, K_BIG_BACK, 28.0 * nbig);
+            k_big_back<<<dim3(div_up(nbig, 256)), dim3(256), 0, s.st>>>(bk, bv, bslot, nbig, b.keys, b.vals_alt, s.d_text, static_cast<uint32_t>(n),
+                                                                      s.carry_bwt ? b.sym_alt : nullptr, big_carry);
         }
-        DK_HIP(ctx, hipGetLastError());
-        if (nbig > 0) {
-            uint64_t *bk = keys_alt, *bk_alt = keys_3;
-            uint32_t *bv = vals_3, *bv_alt = vals;  // the round's input list has been read (k_round_local); the rerank rewrites it below
-            DK_TRY(sort_pairs(ctx, bk, bk_alt, bv, bv_alt, nbig, 8 * big_carry, kb + bsbits + 8 * big_carry));
-            {
-                LaunchScope ls(ctx, K_BIG_BACK, 28.0 * nbig);
-                k_big_back<<<dim3(div_up(nbig, 256)), dim3(256), 0, st>>>(bk, bv, bslot, nbig, keys, vals_alt, d_text, static_cast<uint32_t>(n),
-                                                                          carry_bwt ? sym_alt : nullptr, big_carry);
-            }
-            DK_HIP(ctx, hipGetLastError());
-        }
-        // keys / vals_alt (/ sym_alt) now hold every group sorted by its secondary key in its own slot range
-        size_t next_active = 0, next_groups = 0, next_big = 0, next_medium = 0, next_biggroups = 0;
-        const BwtCarry bc{0, carry_bwt ? d_bwt : nullptr, nullptr, d_origin, sym_alt, sym};
-        // SA entries of suffixes that become final after the rank array exists are read by nobody when the caller wants L (the inverse
-        // permutation was the last reader): 84 M scattered 4-byte stores less on 1e8 bytes of word-like text
-        uint32_t *sa_out = carry_bwt && have_ranks ? nullptr : d_sa;
-        DK_TRY(rerank(ctx, keys, vals_alt, pos, active, gid, have_ranks ? rank : nullptr, sa_out, vals, pos_alt, gid_alt, gstart, bc));
-        DK_TRY(classify_and_read(ctx, active / 2, gstart, bigidx, bigoff, &next_active, &next_groups, &next_big, &next_medium, &next_biggroups));
-        std::swap(pos, pos_alt);
-        std::swap(gid, gid_alt);
-        if (trace)
-            fprintf(stderr, "[dk] round %u h=%llu%s slots=%zu big=%zu key bits=%d (big %d+%d) -> active=%zu groups=%zu big=%zu (>%d: %zu)\n", ctx->stats.rounds,
-                    (unsigned long long)h, period > 0 ? " (period tokens)" : tsym > 0 ? " (text)" : "", active, nbig, kbits, bsbits, kb, next_active, next_groups, next_big, PL_MAX, next_medium);
-        active = next_active;
-        groups = next_groups;
-        nbig = next_big;
-        nmedium = next_medium;
-        nbiggroups = next_biggroups;
-        ctx->stats.rounds += 1;
-        return DK_OK;
-    };
-
-    // A caller that wants L: once the big groups hold little of what is active (doubling has broken them up, or there never were many behind
-    // a shortened key), the rest is finished the L-first way (lfirst.inc: only the groups with different symbols in front, from the text,
-    // inside LDS) instead of more rounds on ranks, pair chains and in-place rounds.  DK_LF_SWITCH: per cent of the active slots that may
-    // still sit in big groups at the switch (0: never).  -> 1: L is complete; 0: not taken; -1: it gave up half way (start over).
-    // Measured, round 4 (1e8 bytes of word-like text, suffix-array path 20.7 ms): switch at 1 % 20.4, at 5 % 19.3-20.1, at 25 % 21.2, at 40-60 %
-    // 22.9, at 80 % (= L-first from the start) 20.5 ms -- and 5 % costs inputs whose big groups do not split on text (90 % zeros: 1.8 -> 2.9 ms
-    // at 5 MB) more than it gains here.  Off in the product; the tuning build keeps the switch and tests/test_env_variants.py the parity.
-    const int lf_switch = DK_KNOB("DK_LF_SWITCH", 0);
-    auto take_over = [&](int *outcome) -> int {
-        *outcome = 0;
-        if (!(carry_bwt && allow_lfirst && lf_mode != 0 && lf_switch > 0 && !long_run && n >= (1u << 16) && active > 0 &&
-              nbig * 100 <= active * static_cast<size_t>(lf_switch)))
-            return DK_OK;
-        if (nbig > 0 && nbig / nbiggroups > LF_AVG_BIG) return DK_OK;  // giant groups (periodic input) are doubling's business
-        // buffers: everything but the current list is free between rounds; the key buffer that is not a sort's ping-pong partner holds the
-        // big list's second suffix array and its symbols (4 n + n of its 8 n bytes); the rank array becomes the big list's positions
-        uint32_t *spare = reinterpret_cast<uint32_t *>(keys);
-        // (the arena of the deep groups: the caller's own list, free once the first rerank has filtered it)
-        uint32_t *gdepth = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(keys) + ((5 * n + 15) & ~size_t(15)));  // (behind the big list's symbols, see above)
-        const LfBuffers b{keys_alt, keys_3, vals_3, spare, rank, reinterpret_cast<uint8_t *>(spare + n), vals_alt, pos_alt, gid_alt, sym_alt, gstart, bigidx, bigoff, vals, pos, sym, gdepth, gdepth + n / 2 + 2, reinterpret_cast<uint8_t *>(gdepth + n / 2 + 2 + n / 32 + 2)};
-        const LfFrom from{vals, pos, gid, sym, active};
-        bool done = false, pristine = true;
-        if (trace) fprintf(stderr, "[dk] %zu active, %zu of them in big groups, depth %llu: the L-first path takes over\n", active, nbig, (unsigned long long)h);
-        route |= DK_ROUTE_LFIRST;
-        DK_TRY(lfirst_path(ctx, d_text, n, nullptr, 0, nullptr, nullptr, d_bwt, d_origin, b, static_cast<uint32_t>(std::min<uint64_t>(h, n)), trace, true, &done, &pristine, &from));
-        *outcome = done ? 1 : -1;
-        return DK_OK;
-    };
-#define DK_TAKE_OVER()                                                                                                      \
-    do {                                                                                                                    \
-        int outcome_ = 0;                                                                                                   \
-        DK_TRY(take_over(&outcome_));                                                                                       \
-        if (outcome_ > 0) { ctx->ws_release(mark); *bwt_written = true; return DK_OK; }                                     \
-        if (outcome_ < 0) {                                                                                                 \
-            ctx->ws_release(mark);                                                                                          \
-            return suffix_array_impl(ctx, d_text, n, d_sa, d_bwt, d_origin, bwt_written, false);                            \
-        }                                                                                                                   \
-    } while (0)
-
-    // 4b. the period round (see k_period_probe): where an eighth of the block lies in stretches of one period p <= 8 (and p <= h: the members
-    //     of a group must share the period string itself), every suffix inside such a stretch is placed by where the stretch ends -- a^n b,
-    //     (ab)^n, zero padding: one round instead of log2(length) doubling rounds over all of them.  The rank array's buffer holds the
-    //     next-break positions (it is built later).
-    bool small_period_round = false;
-    if (active > 0 && period_mode != 0) {
-        const uint32_t *pc = alpha.period_probe;
-        const int pmax = static_cast<int>(std::min<uint64_t>(8, h));
-        uint32_t cmax = 0;
-        for (int q = 1; q <= pmax; ++q) cmax = std::max(cmax, pc[q - 1]);
-        int period = 0;
-        if (cmax > 0 && (period_mode == 2 || static_cast<uint64_t>(cmax) * 64 * 8 >= n))
-            for (int q = 1; q <= pmax && !period; ++q)
-                if (static_cast<uint64_t>(pc[q - 1]) * 10 >= static_cast<uint64_t>(cmax) * 9) period = q;
-        if (period) {
-            small_period_round = true;
-            const size_t ptiles = div_up(n, PB_TILE);
-            const size_t mark2 = ctx->ws_mark();
-            uint32_t *tile_first = ctx->ws_alloc<uint32_t>(ptiles);
-            if (!tile_first) return DK_E_NOMEM;
-            {
-                LaunchScope ls(ctx, K_PERIOD, 2.0 * n + 4.0 * n);
-                k_period_first<<<dim3(ptiles), dim3(256), 0, st>>>(d_text, static_cast<uint32_t>(n), period, tile_first);
-                k_period_spine<<<dim3(1), dim3(1024), 0, st>>>(tile_first, ptiles);
-                k_period_fill<<<dim3(ptiles), dim3(256), 0, st>>>(d_text, static_cast<uint32_t>(n), period, tile_first, rank);
-            }
-            DK_HIP(ctx, hipGetLastError());
-            if (trace)
-                fprintf(stderr, "[dk] period probe: 64-byte windows of period 1..8: %u %u %u %u %u %u %u %u of %zu -> period %d\n", pc[0], pc[1], pc[2], pc[3], pc[4], pc[5],
-                        pc[6], pc[7], n / 64, period);
-            DK_TRY(run_round(8, nullptr, period, rank));
-            ctx->ws_release(mark2);
-        }
+        DK_HIP(s.ctx, hipGetLastError());
     }
-    // 5a. extend the survivors' keys from the text: up to floor(63 / bits) further symbols per round, no ranks needed.  A second
-    //     such round only when the first left a lot (otherwise what is left are long repeats, which want doubling).
-    for (int t = 0; !have_ranks && active > 0 && t < 2; ++t) {
-        if (t == 1 && !short_prefix && active * 8 < n) break;
+    // keys / vals_alt (/ sym_alt) now hold every group sorted by its secondary key in its own slot range
+    GroupCounts next;
+    const BwtCarry bc{0, s.carry_bwt ? s.d_bwt : nullptr, nullptr, s.d_origin, b.sym_alt, b.sym};
+    // SA entries of suffixes that become final after the rank array exists are read by nobody when the caller wants L (the inverse
+    // permutation was the last reader): 84 M scattered 4-byte stores less on 1e8 bytes of word-like text
+    uint32_t *sa_out = s.carry_bwt && s.have_ranks ? nullptr : s.d_sa;
+    DK_TRY(rerank(s.ctx, b.keys, b.vals_alt, b.pos, active, b.gid, s.have_ranks ? b.rank : nullptr, sa_out, b.vals, b.pos_alt, b.gid_alt, b.gstart, bc));
+    DK_TRY(classify_and_read(s.ctx, active / 2, b.gstart, b.bigidx, b.bigoff, &next));
+    std::swap(b.pos, b.pos_alt);
+    std::swap(b.gid, b.gid_alt);
+    if (s.trace)
+        fprintf(stderr, "[dk] round %u h=%llu%s slots=%zu big=%zu key bits=%d (big %d+%d) -> active=%zu groups=%zu big=%zu (>%d: %zu)\n", s.ctx->stats.rounds,
+                (unsigned long long)s.h, period > 0 ? " (period tokens)" : tsym > 0 ? " (text)" : "", active, nbig, kbits, bsbits, kb, next.active, next.groups, next.big, PL_MAX, next.above_pl);
+    s.c = next;
+    s.ctx->stats.rounds += 1;
+    return DK_OK;
+}
+
+// the rounds of the suffix-array path (general and in place) stop here instead of going on for ever on a defect
+int check_round_limit(dk_ctx *ctx) {
+    return ctx->stats.rounds > 44 ? ctx->fail(DK_E_INTERNAL, "suffix_array: no convergence after 44 rounds") : DK_OK;
+}
+
+// A caller that wants L: once the big groups hold little of what is active (doubling has broken them up, or there never were many behind
+// a shortened key), the rest is finished the L-first way (lfirst.inc: only the groups with different symbols in front, from the text,
+// inside LDS) instead of more rounds on ranks, pair chains and in-place rounds.  DK_LF_SWITCH: per cent of the active slots that may
+// still sit in big groups at the switch (0: never).  -> L_COMPLETE; WENT_ON: not taken; START_OVER: it gave up half way.
+// Measured, round 4 (1e8 bytes of word-like text, suffix-array path 20.7 ms): switch at 1 % 20.4, at 5 % 19.3-20.1, at 25 % 21.2, at 40-60 %
+// 22.9, at 80 % (= L-first from the start) 20.5 ms -- and 5 % costs inputs whose big groups do not split on text (90 % zeros: 1.8 -> 2.9 ms
+// at 5 MB) more than it gains here.  Off in the product; the tuning build keeps the switch and tests/test_env_variants.py the parity.
+// Expects the active list between two rounds.
+int take_over(SaSort &s) {
+    const size_t n = s.n, active = s.c.active, nbig = s.c.big;
+    const int lf_switch = DK_KNOB("DK_LF_SWITCH", 0);
+    if (!(s.carry_bwt && s.allow_lfirst && DK_KNOB("DK_LFIRST", 1) != 0 && lf_switch > 0 && !s.long_run && n >= (1u << 16) && active > 0 &&
+          nbig * 100 <= active * static_cast<size_t>(lf_switch)))
+        return WENT_ON;
+    if (nbig > 0 && nbig / s.c.big_groups > LF_AVG_BIG) return WENT_ON;  // giant groups (periodic input) are doubling's business
+    LfFrom from;
+    from.idx = s.b.vals, from.pos = s.b.pos, from.gid = s.b.gid, from.sym = s.b.sym, from.count = active;
+    from.h0 = s.h_eff();
+    if (s.trace) fprintf(stderr, "[dk] %zu active, %zu of them in big groups, depth %llu: the L-first path takes over\n", active, nbig, (unsigned long long)s.h);
+    s.route() |= DK_ROUTE_LFIRST;
+    return lfirst_path(s.ctx, s.d_text, n, s.d_bwt, s.d_origin, lf_buffers_take_over(s.b, n), from, LfTokenPlan{}, s.trace, true);
+}
+
+// 4b. the period round (see k_period_probe): where an eighth of the block lies in stretches of one period p <= 8 (and p <= h: the members
+//     of a group must share the period string itself), every suffix inside such a stretch is placed by where the stretch ends -- a^n b,
+//     (ab)^n, zero padding: one round instead of log2(length) doubling rounds over all of them.  The rank array's buffer holds the
+//     next-break positions (it is built later).  Expects the list of first_rerank; leaves small_period_round and, if taken, the next list.
+int small_period_round(SaSort &s) {
+    s.small_period_round = false;
+    if (s.c.active == 0 || s.period_mode == 0) return DK_OK;
+    const uint32_t *pc = s.alpha().period_probe;
+    uint32_t cmax = 0;
+    const int period = dominant_period(pc, static_cast<int>(std::min<uint64_t>(8, s.h)), &cmax);
+    if (!period || !(s.period_mode == 2 || static_cast<uint64_t>(cmax) * 64 * 8 >= s.n)) return DK_OK;
+    s.small_period_round = true;
+    const size_t mark = s.ctx->ws_mark();
+    uint32_t *tile_first = s.ctx->ws_alloc<uint32_t>(div_up(s.n, PB_TILE));
+    if (!tile_first) return DK_E_NOMEM;
+    DK_TRY(enqueue_next_breaks(s.ctx, s.d_text, s.n, period, tile_first, s.b.rank));
+    if (s.trace)
+        fprintf(stderr, "[dk] period probe: 64-byte windows of period 1..8: %u %u %u %u %u %u %u %u of %zu -> period %d\n", pc[0], pc[1], pc[2], pc[3], pc[4], pc[5],
+                pc[6], pc[7], s.n / 64, period);
+    DK_TRY(general_round(s, 8, nullptr, period, s.b.rank));
+    s.ctx->ws_release(mark);
+    return DK_OK;
+}
+
+// 5a. extend the survivors' keys from the text: up to floor(63 / bits) further symbols per round, no ranks needed.  A second
+//     such round only when the first left a lot (otherwise what is left are long repeats, which want doubling).
+//     Expects a list without ranks; leaves the list after zero to two text rounds and h advanced by what they added.
+int text_rounds(SaSort &s) {
+    for (int t = 0; !s.have_ranks && s.c.active > 0 && t < 2; ++t) {
+        if (t == 1 && !s.short_prefix && s.c.active * 8 < s.n) break;
         // mostly giant groups (periodic or run-dominated input): a text round would push them through the global sort for a few more
         // symbols each, where a doubling round doubles the depth for the same sort -- go straight to the ranks
-        if (nbig * 2 > active) break;
+        if (s.c.big * 2 > s.c.active) break;
         int adv = 0;
         // (small alphabets, coded keys: no more symbols than the depth reached so far -- the round doubles the depth like a doubling round
         // would, and its keys cost a table lookup per symbol: 2^28 ACGT took 31 symbols per survivor where 16 separate all but the repeats)
-        DK_TRY(run_round(std::min<int>(std::min(spk, 63 / bits), static_cast<int>(std::min<uint64_t>(h, 64))), &adv));
-        h += static_cast<uint64_t>(adv);
+        DK_TRY(general_round(s, std::min<int>(std::min(s.spk, 63 / s.bits), static_cast<int>(std::min<uint64_t>(s.h, 64))), &adv));
+        s.h += static_cast<uint64_t>(adv);
     }
-    DK_TAKE_OVER();
-    // 5b. survivors beyond that (long repeats): build the rank array the doubling rounds need
-    if (active > 0 && !have_ranks) {
-        // up to 2^27 suffixes the inverse permutation goes through LDS windows and can hand every active suffix the position of its
-        // group's head by itself (marked entries of SA; pos_alt is free between rounds); above, a second pass over the active list does
-        // (worth it from a quarter of all suffixes active: the marked form costs the first split 0.17 ms per 1e8 suffixes, the second pass
-        // it replaces 0.14 ms per 1e7 active ones)
-        const bool marked = inverse_through_windows(n) && active * 4 > n;
-        route |= marked ? DK_ROUTE_ISA_MARKED : 0u;
-        route |= DK_ROUTE_ISA_WINDOWS;
-        uint32_t *head_pos = marked ? pos_alt : nullptr;
-        {
-            LaunchScope ls(ctx, K_PLACE_ACTIVE, (marked ? 28.0 : 12.0) * active);
-            k_place_active<<<dim3(div_up(active, 256)), dim3(256), 0, st>>>(vals, pos, gid, gstart, active, d_sa, head_pos);
-        }
-        DK_TRY(inverse_permutation(ctx, d_sa, n, keys_alt, keys_3, rank, head_pos));  // rank[SA[p]] = p (keys_alt / keys_3: free between rounds)
-        if (!marked) {
-            LaunchScope ls(ctx, K_PLACE_ACTIVE, 16.0 * active);
-            k_rank_active<<<dim3(div_up(active, 256)), dim3(256), 0, st>>>(vals, pos, gid, gstart, active, rank);
-        }
-        DK_HIP(ctx, hipGetLastError());
-        have_ranks = true;
-    }
+    return DK_OK;
+}
 
-    // 5c'. a long period (9 .. 2^18: fixed-size records, a table of one row)?  Looked for only where giant groups hold most of what is active --
-    //      doubling would run over everything for log2(n / h) rounds -- and used by one period round (4b's, with the tokens of this period) as
-    //      soon as the depth covers it: period 1000 x 8000 (8 MB) 21 -> 9 rounds.
-    uint32_t long_period = 0;
-    if (period_mode != 0 && !small_period_round && active > 0 && nbig * 2 > active && n >= (1u << 16)) {
-        uint32_t *d_found = ctx->d_mail->found, *d_windows = &ctx->d_mail->found_windows;
-        const uint32_t *found = ctx->h_mail->found;
-        const uint32_t pmax = static_cast<uint32_t>(std::min<uint64_t>(PS_MAX, n / 4));
-        DK_TRY(ctx->mail_fill(&ctx->d_mail->found, 0xFF));
-        DK_TRY(ctx->mail_fill(d_windows, 0));
-        {
-            LaunchScope ls(ctx, K_PERIOD, 0.0);
-            k_period_search<<<dim3(PS_SAMPLES), dim3(256), 0, st>>>(d_text, n, pmax, d_found);
-        }
-        DK_TRY(ctx->mail_read(&ctx->h_mail->found));
-        uint32_t best = 0, best_votes = 0;  // the period most samples agree on
-        for (int a = 0; a < PS_SAMPLES; ++a) {
-            const uint32_t v = found[a];
-            if (v == 0xFFFFFFFFu) continue;
-            uint32_t votes = 0;
-            for (int b2 = 0; b2 < PS_SAMPLES; ++b2) votes += found[b2] == v ? 1u : 0u;
-            if (votes > best_votes || (votes == best_votes && v < best)) { best = v; best_votes = votes; }
-        }
-        if (best_votes >= PS_SAMPLES / 4) {
-            {
-                LaunchScope ls(ctx, K_PERIOD, 2.0 * n);
-                k_period_count<<<dim3(div_up(div_up(n, 64), 256)), dim3(256), 0, st>>>(d_text, n, best, d_windows);
-            }
-            DK_TRY(ctx->mail_read(&ctx->h_mail->found_windows));
-            const uint32_t windows = ctx->h_mail->found_windows;
-            // three quarters of the block: a Fibonacci word follows "period 55" in 47 % of its windows, in stretches of a few hundred symbols that one
-            // round on their ends does not settle (6.35 against 5.71 ms at 4 MB)
-            if (static_cast<uint64_t>(windows) * 64 * 4 >= static_cast<uint64_t>(n) * 3) long_period = best;
-            if (trace)
-                fprintf(stderr, "[dk] long period: %u of %d samples say %u, %u of %zu windows follow it -> %s\n", best_votes, PS_SAMPLES, best, windows, n / 64,
-                        long_period ? "a period round once the depth covers it" : "not used");
-        }
+// 5b. survivors beyond that (long repeats): build the rank array the doubling rounds need.  Expects the active list and the suffix array as the
+//     reranks left it; leaves rank[] (final suffixes: their SA position; active ones: the position of their group's head) and have_ranks.
+int build_ranks(SaSort &s) {
+    SaBuffers &b = s.b;
+    const size_t n = s.n, active = s.c.active;
+    if (active == 0 || s.have_ranks) return DK_OK;
+    // up to 2^27 suffixes the inverse permutation goes through LDS windows and can hand every active suffix the position of its
+    // group's head by itself (marked entries of SA; pos_alt is free between rounds); above, a second pass over the active list does
+    // (worth it from a quarter of all suffixes active: the marked form costs the first split 0.17 ms per 1e8 suffixes, the second pass
+    // it replaces 0.14 ms per 1e7 active ones)
+    const bool marked = inverse_through_windows(n) && active * 4 > n;
+    s.route() |= marked ? DK_ROUTE_ISA_MARKED : 0u;
+    s.route() |= DK_ROUTE_ISA_WINDOWS;
+    uint32_t *head_pos = marked ? b.pos_alt : nullptr;
+    {
+        LaunchScope ls(s.ctx, K_PLACE_ACTIVE, (marked ? 28.0 : 12.0) * active);
+        k_place_active<<<dim3(div_up(active, 256)), dim3(256), 0, s.st>>>(b.vals, b.pos, b.gid, b.gstart, active, s.d_sa, head_pos);
     }
-    // 5c. doubling rounds: the general form while big groups exist, ...
+    DK_TRY(inverse_permutation(s.ctx, s.d_sa, n, b.keys_alt, b.keys_3, b.rank, head_pos));  // rank[SA[p]] = p (keys_alt / keys_3: free between rounds)
+    if (!marked) {
+        LaunchScope ls(s.ctx, K_PLACE_ACTIVE, 16.0 * active);
+        k_rank_active<<<dim3(div_up(active, 256)), dim3(256), 0, s.st>>>(b.vals, b.pos, b.gid, b.gstart, active, b.rank);
+    }
+    DK_HIP(s.ctx, hipGetLastError());
+    s.have_ranks = true;
+    return DK_OK;
+}
+
+// 5c'. a long period (9 .. 2^18: fixed-size records, a table of one row)?  Looked for only where giant groups hold most of what is active --
+//      doubling would run over everything for log2(n / h) rounds -- and used by one period round (4b's, with the tokens of this period) as
+//      soon as the depth covers it: period 1000 x 8000 (8 MB) 21 -> 9 rounds.  Expects the counts of the list; leaves long_period (0: none).
+int find_long_period(SaSort &s) {
+    const size_t n = s.n;
+    s.long_period = 0;
+    if (!(s.period_mode != 0 && !s.small_period_round && s.c.active > 0 && s.c.big * 2 > s.c.active && n >= (1u << 16))) return DK_OK;
+    uint32_t *d_found = s.ctx->d_mail->found, *d_windows = &s.ctx->d_mail->found_windows;
+    const uint32_t *found = s.ctx->h_mail->found;
+    const uint32_t pmax = static_cast<uint32_t>(std::min<uint64_t>(PS_MAX, n / 4));
+    DK_TRY(s.ctx->mail_fill(&s.ctx->d_mail->found, 0xFF));
+    DK_TRY(s.ctx->mail_fill(d_windows, 0));
+    {
+        LaunchScope ls(s.ctx, K_PERIOD, 0.0);
+        k_period_search<<<dim3(PS_SAMPLES), dim3(256), 0, s.st>>>(s.d_text, n, pmax, d_found);
+    }
+    DK_TRY(s.ctx->mail_read(&s.ctx->h_mail->found));
+    uint32_t best = 0, best_votes = 0;  // the period most samples agree on
+    for (int a = 0; a < PS_SAMPLES; ++a) {
+        const uint32_t v = found[a];
+        if (v == 0xFFFFFFFFu) continue;
+        uint32_t votes = 0;
+        for (int b2 = 0; b2 < PS_SAMPLES; ++b2) votes += found[b2] == v ? 1u : 0u;
+        if (votes > best_votes || (votes == best_votes && v < best)) { best = v; best_votes = votes; }
+    }
+    if (best_votes < PS_SAMPLES / 4) return DK_OK;
+    {
+        LaunchScope ls(s.ctx, K_PERIOD, 2.0 * n);
+        k_period_count<<<dim3(div_up(div_up(n, 64), 256)), dim3(256), 0, s.st>>>(s.d_text, n, best, d_windows);
+    }
+    DK_TRY(s.ctx->mail_read(&s.ctx->h_mail->found_windows));
+    const uint32_t windows = s.ctx->h_mail->found_windows;
+    // three quarters of the block: a Fibonacci word follows "period 55" in 47 % of its windows, in stretches of a few hundred symbols that one
+    // round on their ends does not settle (6.35 against 5.71 ms at 4 MB)
+    if (static_cast<uint64_t>(windows) * 64 * 4 >= static_cast<uint64_t>(n) * 3) s.long_period = best;
+    if (s.trace)
+        fprintf(stderr, "[dk] long period: %u of %d samples say %u, %u of %zu windows follow it -> %s\n", best_votes, PS_SAMPLES, best, windows, n / 64,
+                s.long_period ? "a period round once the depth covers it" : "not used");
+    return DK_OK;
+}
+
+// 5c. doubling rounds: the general form while big groups exist, ... (in_place_rounds takes what they leave).  Expects the ranks; leaves a list
+//     without a group above PL_MAX (DK_PLATEAU=0: no list at all), h doubled per round.  The L-first path may take over behind any round.
+int doubling_rounds(SaSort &s) {
     const bool plateau_enabled = DK_KNOB("DK_PLATEAU", 1) != 0;
-    while (active > 0 && (nmedium > 0 || !plateau_enabled)) {
-        if (ctx->stats.rounds > 44) return ctx->fail(DK_E_INTERNAL, "suffix_array: no convergence after 44 rounds");
-        if (long_period && h >= long_period) {
+    while (s.c.active > 0 && (s.c.above_pl > 0 || !plateau_enabled)) {
+        DK_TRY(check_round_limit(s.ctx));
+        if (s.long_period && s.h >= s.long_period) {
             // (next-break positions: the suffix array's buffer when the caller wants L -- nobody reads SA once the ranks exist -- else workspace, if it has room)
-            const size_t mark2 = ctx->ws_mark();
-            uint32_t *nb = carry_bwt ? d_sa : ctx->ws_try_alloc<uint32_t>(n);
-            const size_t ptiles = div_up(n, PB_TILE);
-            uint32_t *tile_first = nb ? ctx->ws_try_alloc<uint32_t>(ptiles) : nullptr;
-            const uint32_t p_now = long_period;
-            long_period = 0;
+            const size_t mark = s.ctx->ws_mark();
+            uint32_t *nb = s.carry_bwt ? s.d_sa : s.ctx->ws_try_alloc<uint32_t>(s.n);
+            uint32_t *tile_first = nb ? s.ctx->ws_try_alloc<uint32_t>(div_up(s.n, PB_TILE)) : nullptr;
+            const int p_now = static_cast<int>(s.long_period);
+            s.long_period = 0;
             if (nb && tile_first) {
-                {
-                    LaunchScope ls(ctx, K_PERIOD, 2.0 * n + 4.0 * n);
-                    k_period_first<<<dim3(ptiles), dim3(256), 0, st>>>(d_text, static_cast<uint32_t>(n), static_cast<int>(p_now), tile_first);
-                    k_period_spine<<<dim3(1), dim3(1024), 0, st>>>(tile_first, ptiles);
-                    k_period_fill<<<dim3(ptiles), dim3(256), 0, st>>>(d_text, static_cast<uint32_t>(n), static_cast<int>(p_now), tile_first, nb);
-                }
-                DK_HIP(ctx, hipGetLastError());
-                DK_TRY(run_round(8, nullptr, static_cast<int>(p_now), nb));
-                ctx->ws_release(mark2);
+                DK_TRY(enqueue_next_breaks(s.ctx, s.d_text, s.n, p_now, tile_first, nb));
+                DK_TRY(general_round(s, 8, nullptr, p_now, nb));
+                s.ctx->ws_release(mark);
                 continue;
             }
-            ctx->ws_release(mark2);
+            s.ctx->ws_release(mark);
         }
-        DK_TRY(run_round(0, nullptr));
-        h *= 2;
-        DK_TAKE_OVER();
+        DK_TRY(general_round(s, 0, nullptr));
+        s.h *= 2;
+        const int step = take_over(s);
+        if (step != WENT_ON) return step;
     }
-    // ... then in place (k_plateau_sort): one sort kernel + one rank kernel per round, the live count read back one round late
-    if (active > 0) {
-        size_t slots = active;
-        route |= DK_ROUTE_INPLACE_ROUNDS;
-        uint32_t *idx_a = vals, *idx_b = vals_alt;
-        uint32_t *meta_a = gid, *meta_b = gid_alt;
-        uint8_t *sym_a = sym, *sym_b = sym_alt;
-        uint32_t *d_live = ctx->d_mail->live_ring, *h_live = ctx->h_mail->live_ring;  // ring of LIVE_RING counters
-        constexpr unsigned RING = LIVE_RING - 1u;
-        {
-            LaunchScope ls(ctx, K_PLATEAU_RANKS, 14.0 * slots);
-            k_to_inplace<<<dim3(div_up(slots, 256)), dim3(256), 0, st>>>(gid, gstart, slots, meta_b);
-        }
-        std::swap(meta_a, meta_b);  // gid was read, gid_alt written
-        // pair chains first: the groups of two (three, four) that long repeats leave behind are settled by one comparison per chain
-        size_t settled_by_chains = 0;
-        if (DK_KNOB("DK_PAIR_CHAINS", 1) != 0 && slots >= 2) {
-            uint64_t *rec_key = keys, *rec_key_alt = keys_alt;  // (all free at this point: nothing is sorted globally any more)
-            uint32_t *rec_slot = vals_3, *rec_slot_alt = pos_alt;
-            uint8_t *planes = reinterpret_cast<uint8_t *>(keys_3);  // CH_K - 1 planes of one verdict byte per slot (3 n of the buffer's 8 n bytes) ...
-            uint8_t *rec_verdict = planes + static_cast<size_t>(CH_K - 1) * n;  // ... and one byte per record behind them
-            const int kmax = std::min(CH_K, std::max(2, DK_KNOB("DK_CHAIN_GROUP", CH_K)));
-            const int lbits = static_cast<int>(ceil_log2_u64(n));
-            const uint32_t cap = static_cast<uint32_t>(std::min<size_t>(n, 0xFFFFFFF0u));  // records the buffers hold (n each); what does not fit stays with the rounds
-            uint32_t *d_cnt = ctx->d_mail->chain_cnt;  // [0] records, [1] first reservation that did not fit
-            const uint32_t *cnt = ctx->h_mail->chain_cnt;
-            DK_TRY(ctx->mail_fill(&d_cnt[0], 0));
-            DK_TRY(ctx->mail_fill(&d_cnt[1], 0xFF));
-            DK_HIP(ctx, hipMemsetAsync(planes, 0, static_cast<size_t>(kmax - 1) * slots, st));
-            {
-                LaunchScope ls(ctx, K_CHAIN, 16.0 * slots);
-                k_chain_extract<<<dim3(div_up(slots, 256 * CH_EXTRACT)), dim3(256), 0, st>>>(idx_a, meta_a, slots, kmax, lbits, rec_key, rec_slot, cap, d_cnt);
-            }
-            DK_HIP(ctx, hipGetLastError());
-            DK_TRY(ctx->mail_read(&ctx->h_mail->chain_cnt));
-            const uint32_t m = std::min(cnt[0], cnt[1]);
-            if (trace) fprintf(stderr, "[dk] pair chains: %u pairs inside groups of 2..%d among %zu slots%s (h = %llu)\n", m, kmax, slots, cnt[1] != 0xFFFFFFFFu ? " (list full)" : "",
-                               static_cast<unsigned long long>(h));
-            if (m > 0) {
-                route |= DK_ROUTE_PAIR_CHAINS;
-                DK_TRY(sort_pairs(ctx, rec_key, rec_key_alt, rec_slot, rec_slot_alt, m, 0, 2 * lbits));
-                const size_t mark2 = ctx->ws_mark();
-                const uint32_t ntiles = static_cast<uint32_t>(div_up(m, CH_TILE));
-                uint32_t *tile_max = ctx->ws_alloc<uint32_t>(ntiles);
-                if (!tile_max) return DK_E_NOMEM;
-                {
-                    LaunchScope ls(ctx, K_CHAIN, 22.0 * m + 14.0 * slots);
-                    k_chain_ends<<<dim3(div_up(m, 256)), dim3(256), 0, st>>>(rec_key, m, lbits, rank, static_cast<uint32_t>(n), static_cast<uint32_t>(std::min<uint64_t>(h, n)), rec_verdict);
-                    k_chain_tiles<<<dim3(ntiles), dim3(256), 0, st>>>(rec_verdict, m, tile_max);
-                    k_chain_spine<<<dim3(1), dim3(1024), 0, st>>>(tile_max, ntiles);
-                    k_chain_verdicts<<<dim3(ntiles), dim3(256), 0, st>>>(rec_verdict, rec_key, rec_slot, m, tile_max, planes, slots);
-                    k_chain_apply<<<dim3(div_up(slots, 256)), dim3(256), 0, st>>>(idx_a, meta_a, sym_a, pos, planes, slots, carry_bwt ? nullptr : d_sa, carry_bwt ? d_bwt : nullptr, d_origin, rank);
-                }
-                DK_HIP(ctx, hipGetLastError());
-                // how many slots are left?  (counted, not summed up by the kernel above: an atomic per wave on one address was 17.7 of its 18 ms on
-                // two identical halves, 1.5 of 1.6 ms on the 1e8 text block)
-                const size_t ltiles = div_up(slots, RR_TILE);
-                uint32_t *tile_live = ctx->ws_alloc<uint32_t>(ltiles);
-                if (!tile_live) return DK_E_NOMEM;
-                {
-                    LaunchScope ls(ctx, K_PLATEAU_RANKS, 4.0 * slots);
-                    k_plateau_count<<<dim3(ltiles), dim3(RR_BLOCK), 0, st>>>(idx_a, slots, tile_live);
-                    k_plateau_scan<<<dim3(1), dim3(1024), 0, st>>>(tile_live, ltiles, d_cnt);
-                }
-                DK_HIP(ctx, hipGetLastError());
-                DK_TRY(ctx->mail_read(&ctx->h_mail->chain_cnt[0]));
-                settled_by_chains = slots - cnt[0];
-                if (trace) fprintf(stderr, "[dk] pair chains settled %zu of %zu slots\n", settled_by_chains, slots);
-                ctx->ws_release(mark2);
-            }
-        }
-        unsigned launched = 0, read = 0;
-        size_t live = active - settled_by_chains;
-        auto compact = [&]() -> int {  // live slots keep their order, so groups stay contiguous
-            const size_t mark2 = ctx->ws_mark();
-            const size_t ntiles = div_up(slots, RR_TILE);
-            uint32_t *tile_live = ctx->ws_alloc<uint32_t>(ntiles);
-            if (!tile_live) return DK_E_NOMEM;
-            {
-                LaunchScope ls(ctx, K_PLATEAU_RANKS, 4.0 * slots + 22.0 * live);
-                k_plateau_count<<<dim3(ntiles), dim3(RR_BLOCK), 0, st>>>(idx_a, slots, tile_live);
-                k_plateau_scan<<<dim3(1), dim3(1024), 0, st>>>(tile_live, ntiles, d_live);
-                k_plateau_compact<<<dim3(ntiles), dim3(RR_BLOCK), 0, st>>>(idx_a, meta_a, sym_a, pos, slots, tile_live, idx_b, meta_b, sym_b, pos_alt);
-            }
-            DK_HIP(ctx, hipGetLastError());
-            DK_TRY(ctx->mail_read(&h_live[0]));
-            if (h_live[0] != live) return ctx->fail(DK_E_INTERNAL, "suffix_array: live count %u after compaction, expected %zu", h_live[0], live);
-            ctx->ws_release(mark2);
-            std::swap(idx_a, idx_b);
-            std::swap(meta_a, meta_b);
-            std::swap(sym_a, sym_b);
-            std::swap(pos, pos_alt);
-            slots = live;
-            launched = read = 0;
-            return DK_OK;
-        };
-        auto launch_round = [&]() -> int {
-            const uint32_t h_eff = static_cast<uint32_t>(std::min<uint64_t>(h, n));
-            uint32_t *cnt = d_live + (launched & RING);
-            DK_TRY(ctx->mail_fill(cnt, 0));
-            {
-                LaunchScope ls(ctx, K_PLATEAU_SORT, 6.0 * slots + 4.0 * live + 10.0 * live);
-                k_plateau_sort<<<dim3(div_up(slots, LS_TILE)), dim3(LS_BLOCK), 0, st>>>(idx_a, meta_a, sym_a, pos, rank, static_cast<uint32_t>(n), h_eff,
-                                                                                      slots, idx_b, meta_b, sym_b, carry_bwt ? nullptr : d_sa, d_bwt, d_origin, cnt,
-                                                                                      launched ? d_live + ((launched - 1) & RING) : nullptr);
-            }
-            {
-                LaunchScope ls(ctx, K_PLATEAU_RANKS, 6.0 * slots);
-                k_plateau_ranks<<<dim3(div_up(slots, 256)), dim3(256), 0, st>>>(idx_b, meta_b, pos, slots, rank,
-                                                                                launched ? d_live + ((launched - 1) & RING) : nullptr);
-            }
-            DK_HIP(ctx, hipGetLastError());
-            DK_TRY(ctx->mail_fetch(&h_live[launched & RING]));
-            DK_HIP(ctx, hipEventRecord(ctx->round_ev[launched & RING], st));
-            std::swap(idx_a, idx_b);
-            std::swap(meta_a, meta_b);
-            std::swap(sym_a, sym_b);
-            h = std::min<uint64_t>(h * 2, static_cast<uint64_t>(n) * 2);
-            ++launched;
-            return DK_OK;
-        };
-        auto read_round = [&]() -> int {  // the oldest round in flight: how many slots did it leave alive?
-            DK_HIP(ctx, hipEventSynchronize(ctx->round_ev[read & RING]));
-            const size_t before = live;
-            live = h_live[read & RING];
-            ++read;
-            ctx->stats.rounds += 1;
-            if (trace) fprintf(stderr, "[dk] round %u (in place) slots=%zu live %zu -> %zu\n", ctx->stats.rounds - 1, slots, before, live);
-            return DK_OK;
-        };
-        if (live > 0 && settled_by_chains && live * 4 <= slots && slots >= (1u << 16)) DK_TRY(compact());  // the chains left mostly dead slots behind
-        for (; live > 0;) {
-            if (ctx->stats.rounds > 44) return ctx->fail(DK_E_INTERNAL, "suffix_array: no convergence after 44 rounds");
-            DK_TRY(launch_round());
-            if (launched - read < 2) continue;  // keep one round ahead of the host
-            DK_TRY(read_round());
-            if (live == 0) break;  // the round launched since ran over dead slots only
-            if (live * 4 <= slots && slots >= (1u << 16)) {
-                // mostly dead slots: drain the round in flight, then compact (live slots keep their order: groups stay contiguous)
-                DK_TRY(read_round());
-                if (live == 0) break;
-                DK_TRY(compact());
-            }
-        }
-        active = 0;
+    return WENT_ON;
+}
+
+// The list of the in-place rounds (k_plateau_sort): slots keep their place from round to round, dead ones included, until a compaction.
+struct InPlaceList {
+    size_t slots, live;                         // slots of the list | those still alive, as far as the host has read
+    uint32_t *idx_a, *idx_b, *meta_a, *meta_b;  // suffixes (PL_DEAD: settled): vals / vals_alt | group layout of every slot: gid / gid_alt -- ping-pong
+    uint8_t *sym_a, *sym_b;                     // symbol in front: sym / sym_alt
+    unsigned launched, read;                    // rounds enqueued | rounds whose live count has been read (ring of LIVE_RING counters)
+    void flip() { std::swap(idx_a, idx_b), std::swap(meta_a, meta_b), std::swap(sym_a, sym_b); }  // a round or a compaction has written the other set
+};
+constexpr unsigned PL_RING = LIVE_RING - 1u;
+
+// pair chains first: the groups of two (three, four) that long repeats leave behind are settled by one comparison per chain.
+// Expects the in-place list before its first round; leaves the settled slots dead and *settled = how many.
+int pair_chains(SaSort &s, InPlaceList &l, size_t *settled) {
+    SaBuffers &b = s.b;
+    const size_t n = s.n, slots = l.slots;
+    *settled = 0;
+    if (DK_KNOB("DK_PAIR_CHAINS", 1) == 0 || slots < 2) return DK_OK;
+    uint64_t *rec_key = b.keys, *rec_key_alt = b.keys_alt;  // (all free at this point: nothing is sorted globally any more)
+    uint32_t *rec_slot = b.vals_3, *rec_slot_alt = b.pos_alt;
+    uint8_t *planes = reinterpret_cast<uint8_t *>(b.keys_3);  // CH_K - 1 planes of one verdict byte per slot (3 n of the buffer's 8 n bytes) ...
+    uint8_t *rec_verdict = planes + static_cast<size_t>(CH_K - 1) * n;  // ... and one byte per record behind them
+    const int kmax = std::min(CH_K, std::max(2, DK_KNOB("DK_CHAIN_GROUP", CH_K)));
+    const int lbits = static_cast<int>(ceil_log2_u64(n));
+    const uint32_t cap = static_cast<uint32_t>(std::min<size_t>(n, 0xFFFFFFF0u));  // records the buffers hold (n each); what does not fit stays with the rounds
+    uint32_t *d_cnt = s.ctx->d_mail->chain_cnt;  // [0] records, [1] first reservation that did not fit
+    const uint32_t *cnt = s.ctx->h_mail->chain_cnt;
+    DK_TRY(s.ctx->mail_fill(&d_cnt[0], 0));
+    DK_TRY(s.ctx->mail_fill(&d_cnt[1], 0xFF));
+    DK_HIP(s.ctx, hipMemsetAsync(planes, 0, static_cast<size_t>(kmax - 1) * slots, s.st));
+    {
+        LaunchScope ls(s.ctx, K_CHAIN, 16.0 * slots);
+        k_chain_extract<<<dim3(div_up(slots, 256 * CH_EXTRACT)), dim3(256), 0, s.st>>>(l.idx_a, l.meta_a, slots, kmax, lbits, rec_key, rec_slot, cap, d_cnt);
     }
-    if (carry_bwt) *bwt_written = true;
-    ctx->ws_release(mark);
+    DK_HIP(s.ctx, hipGetLastError());
+    DK_TRY(s.ctx->mail_read(&s.ctx->h_mail->chain_cnt));
+    const uint32_t m = std::min(cnt[0], cnt[1]);
+    if (s.trace) fprintf(stderr, "[dk] pair chains: %u pairs inside groups of 2..%d among %zu slots%s (h = %llu)\n", m, kmax, slots, cnt[1] != 0xFFFFFFFFu ? " (list full)" : "",
+                         static_cast<unsigned long long>(s.h));
+    if (m == 0) return DK_OK;
+    s.route() |= DK_ROUTE_PAIR_CHAINS;
+    DK_TRY(sort_pairs(s.ctx, rec_key, rec_key_alt, rec_slot, rec_slot_alt, m, 0, 2 * lbits));
+    const size_t mark = s.ctx->ws_mark();
+    const uint32_t ntiles = static_cast<uint32_t>(div_up(m, CH_TILE));
+    uint32_t *tile_max = s.ctx->ws_alloc<uint32_t>(ntiles);
+    if (!tile_max) return DK_E_NOMEM;
+    {
+        LaunchScope ls(s.ctx, K_CHAIN, 22.0 * m + 14.0 * slots);
+        k_chain_ends<<<dim3(div_up(m, 256)), dim3(256), 0, s.st>>>(rec_key, m, lbits, b.rank, static_cast<uint32_t>(n), s.h_eff(), rec_verdict);
+        k_chain_tiles<<<dim3(ntiles), dim3(256), 0, s.st>>>(rec_verdict, m, tile_max);
+        k_chain_spine<<<dim3(1), dim3(1024), 0, s.st>>>(tile_max, ntiles);
+        k_chain_verdicts<<<dim3(ntiles), dim3(256), 0, s.st>>>(rec_verdict, rec_key, rec_slot, m, tile_max, planes, slots);
+        k_chain_apply<<<dim3(div_up(slots, 256)), dim3(256), 0, s.st>>>(l.idx_a, l.meta_a, l.sym_a, b.pos, planes, slots, s.carry_bwt ? nullptr : s.d_sa, s.carry_bwt ? s.d_bwt : nullptr, s.d_origin, b.rank);
+    }
+    DK_HIP(s.ctx, hipGetLastError());
+    // how many slots are left?  (counted, not summed up by the kernel above: an atomic per wave on one address was 17.7 of its 18 ms on
+    // two identical halves, 1.5 of 1.6 ms on the 1e8 text block)
+    const size_t ltiles = div_up(slots, RR_TILE);
+    uint32_t *tile_live = s.ctx->ws_alloc<uint32_t>(ltiles);
+    if (!tile_live) return DK_E_NOMEM;
+    {
+        LaunchScope ls(s.ctx, K_PLATEAU_RANKS, 4.0 * slots);
+        k_plateau_count<<<dim3(ltiles), dim3(RR_BLOCK), 0, s.st>>>(l.idx_a, slots, tile_live);
+        k_plateau_scan<<<dim3(1), dim3(1024), 0, s.st>>>(tile_live, ltiles, d_cnt);
+    }
+    DK_HIP(s.ctx, hipGetLastError());
+    DK_TRY(s.ctx->mail_read(&s.ctx->h_mail->chain_cnt[0]));
+    *settled = slots - cnt[0];
+    if (s.trace) fprintf(stderr, "[dk] pair chains settled %zu of %zu slots\n", *settled, slots);
+    s.ctx->ws_release(mark);
     return DK_OK;
-#undef DK_TAKE_OVER
+}
+
+// compaction of the in-place list: live slots keep their order, so groups stay contiguous.  Expects no round in flight and l.live current
+int in_place_compact(SaSort &s, InPlaceList &l) {
+    uint32_t *d_live = s.ctx->d_mail->live_ring, *h_live = s.ctx->h_mail->live_ring;
+    const size_t mark = s.ctx->ws_mark();
+    const size_t ntiles = div_up(l.slots, RR_TILE);
+    uint32_t *tile_live = s.ctx->ws_alloc<uint32_t>(ntiles);
+    if (!tile_live) return DK_E_NOMEM;
+    {
+        LaunchScope ls(s.ctx, K_PLATEAU_RANKS, 4.0 * l.slots + 22.0 * l.live);
+        k_plateau_count<<<dim3(ntiles), dim3(RR_BLOCK), 0, s.st>>>(l.idx_a, l.slots, tile_live);
+        k_plateau_scan<<<dim3(1), dim3(1024), 0, s.st>>>(tile_live, ntiles, d_live);
+        k_plateau_compact<<<dim3(ntiles), dim3(RR_BLOCK), 0, s.st>>>(l.idx_a, l.meta_a, l.sym_a, s.b.pos, l.slots, tile_live, l.idx_b, l.meta_b, l.sym_b, s.b.pos_alt);
+    }
+    DK_HIP(s.ctx, hipGetLastError());
+    DK_TRY(s.ctx->mail_read(&h_live[0]));
+    if (h_live[0] != l.live) return s.ctx->fail(DK_E_INTERNAL, "suffix_array: live count %u after compaction, expected %zu", h_live[0], l.live);
+    s.ctx->ws_release(mark);
+    l.flip();
+    std::swap(s.b.pos, s.b.pos_alt);
+    l.slots = l.live;
+    l.launched = l.read = 0;
+    return DK_OK;
+}
+
+// enqueue one in-place round: one sort kernel + one rank kernel, the live count on its way to the host's ring.  Doubles h.
+int in_place_launch(SaSort &s, InPlaceList &l) {
+    uint32_t *d_live = s.ctx->d_mail->live_ring, *h_live = s.ctx->h_mail->live_ring;
+    uint32_t *cnt = d_live + (l.launched & PL_RING);
+    const uint32_t *cnt_before = l.launched ? d_live + ((l.launched - 1) & PL_RING) : nullptr;
+    DK_TRY(s.ctx->mail_fill(cnt, 0));
+    {
+        LaunchScope ls(s.ctx, K_PLATEAU_SORT, 6.0 * l.slots + 4.0 * l.live + 10.0 * l.live);
+        k_plateau_sort<<<dim3(div_up(l.slots, LS_TILE)), dim3(LS_BLOCK), 0, s.st>>>(l.idx_a, l.meta_a, l.sym_a, s.b.pos, s.b.rank, static_cast<uint32_t>(s.n), s.h_eff(),
+                                                                                  l.slots, l.idx_b, l.meta_b, l.sym_b, s.carry_bwt ? nullptr : s.d_sa, s.d_bwt, s.d_origin, cnt,
+                                                                                  cnt_before);
+    }
+    {
+        LaunchScope ls(s.ctx, K_PLATEAU_RANKS, 6.0 * l.slots);
+        k_plateau_ranks<<<dim3(div_up(l.slots, 256)), dim3(256), 0, s.st>>>(l.idx_b, l.meta_b, s.b.pos, l.slots, s.b.rank, cnt_before);
+    }
+    DK_HIP(s.ctx, hipGetLastError());
+    DK_TRY(s.ctx->mail_fetch(&h_live[l.launched & PL_RING]));
+    DK_HIP(s.ctx, hipEventRecord(s.ctx->round_ev[l.launched & PL_RING], s.st));
+    l.flip();
+    s.h = std::min<uint64_t>(s.h * 2, static_cast<uint64_t>(s.n) * 2);
+    ++l.launched;
+    return DK_OK;
+}
+
+// the oldest round in flight: how many slots did it leave alive?
+int in_place_read(SaSort &s, InPlaceList &l) {
+    DK_HIP(s.ctx, hipEventSynchronize(s.ctx->round_ev[l.read & PL_RING]));
+    const size_t before = l.live;
+    l.live = s.ctx->h_mail->live_ring[l.read & PL_RING];
+    ++l.read;
+    s.ctx->stats.rounds += 1;
+    if (s.trace) fprintf(stderr, "[dk] round %u (in place) slots=%zu live %zu -> %zu\n", s.ctx->stats.rounds - 1, l.slots, before, l.live);
+    return DK_OK;
+}
+
+// ... then in place (k_plateau_sort): one sort kernel + one rank kernel per round, the live count read back one round late.
+// Expects what doubling_rounds left: the ranks, and a list whose groups all have at most PL_MAX members; leaves every suffix placed.
+int in_place_rounds(SaSort &s) {
+    if (s.c.active == 0) return DK_OK;
+    SaBuffers &b = s.b;
+    s.route() |= DK_ROUTE_INPLACE_ROUNDS;
+    InPlaceList l;
+    l.slots = l.live = s.c.active, l.idx_a = b.vals, l.idx_b = b.vals_alt, l.meta_a = b.gid, l.meta_b = b.gid_alt, l.sym_a = b.sym, l.sym_b = b.sym_alt, l.launched = l.read = 0;
+    {
+        LaunchScope ls(s.ctx, K_PLATEAU_RANKS, 14.0 * l.slots);
+        k_to_inplace<<<dim3(div_up(l.slots, 256)), dim3(256), 0, s.st>>>(b.gid, b.gstart, l.slots, l.meta_b);
+    }
+    std::swap(l.meta_a, l.meta_b);  // gid was read, gid_alt written
+    size_t settled_by_chains = 0;
+    DK_TRY(pair_chains(s, l, &settled_by_chains));
+    l.live = s.c.active - settled_by_chains;
+    if (l.live > 0 && settled_by_chains && l.live * 4 <= l.slots && l.slots >= (1u << 16)) DK_TRY(in_place_compact(s, l));  // the chains left mostly dead slots behind
+    for (; l.live > 0;) {
+        DK_TRY(check_round_limit(s.ctx));
+        DK_TRY(in_place_launch(s, l));
+        if (l.launched - l.read < 2) continue;  // keep one round ahead of the host
+        DK_TRY(in_place_read(s, l));
+        if (l.live == 0) break;  // the round launched since ran over dead slots only
+        if (l.live * 4 <= l.slots && l.slots >= (1u << 16)) {
+            // mostly dead slots: drain the round in flight, then compact (live slots keep their order: groups stay contiguous)
+            DK_TRY(in_place_read(s, l));
+            if (l.live == 0) break;
+            DK_TRY(in_place_compact(s, l));
+        }
+    }
+    s.c.active = 0;
+    return DK_OK;
+}
+
+// The phases in order.  -> WENT_ON: the suffix-array path ran to its end (L has been written on the way if s.carry_bwt); L_COMPLETE / START_OVER
+// from the L-first path; or an error
+int run_phases(SaSort &s) {
+    DK_TRY(read_alphabet(s));
+    if (s.sigma <= 1) {  // one distinct symbol: suffixes sort by length
+        s.carry_bwt = false;  // (nothing to carry L along: the caller gathers it from the suffix array)
+        k_sa_descending<<<dim3(div_up(s.n, 256)), dim3(256), 0, s.st>>>(s.d_sa, s.n);
+        DK_HIP(s.ctx, hipGetLastError());
+        return WENT_ON;
+    }
+    DK_TRY(alloc_buffers(s.ctx, s.n, s.carry_bwt, &s.b));
+    DK_TRY(choose_prefix(s));
+    DK_TRY(initial_sort(s));
+    int step = lfirst_from_start(s);
+    if (step != WENT_ON) return step;
+    DK_TRY(first_rerank(s));
+    DK_TRY(small_period_round(s));
+    DK_TRY(text_rounds(s));
+    step = take_over(s);
+    if (step != WENT_ON) return step;
+    DK_TRY(build_ranks(s));
+    DK_TRY(find_long_period(s));
+    step = doubling_rounds(s);
+    if (step != WENT_ON) return step;
+    return in_place_rounds(s);
 }
 
 }  // namespace
+
+// runs the phases at most twice: with the L-first path allowed, and (after it gave up half way) without
+int suffix_array_device(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d_sa, uint8_t *d_bwt, uint32_t *d_origin, bool *bwt_written) {
+    if (bwt_written) *bwt_written = false;
+    if (n == 0 || n > 0x7FFFFFFEull) return ctx->fail(DK_E_ARG, "suffix_array: n out of range");
+    for (const bool allow_lfirst : {true, false}) {
+        ctx->stats.rounds = 0;
+        ctx->stats.sort_passes = 0;
+        ctx->stats.sorted_elements = 0;
+        ctx->stats.sa_route = allow_lfirst ? 0u : static_cast<uint32_t>(DK_ROUTE_LFIRST_FALLBACK);
+        SaSort s{};
+        s.ctx = ctx, s.st = ctx->stream, s.d_text = d_text, s.n = n, s.d_sa = d_sa, s.d_bwt = d_bwt, s.d_origin = d_origin, s.allow_lfirst = allow_lfirst;
+        s.trace = DK_KNOB("DK_TRACE", 0) != 0;
+        // BWT on the way (BwtCarry): callers that want L.  The key gives up its low byte to the code of the symbol in front of the suffix, so
+        // the initial sort covers at most 56 bits = seven passes instead of eight; nothing is gathered from the text afterwards.
+        // DK_BWT_CARRY=0 (test hook): sort the full key and let the caller gather L from the suffix array.
+        s.carry_bwt = DK_KNOB("DK_BWT_CARRY", 1) != 0 && d_bwt && d_origin && bwt_written;
+        const size_t mark = ctx->ws_mark();
+        const int step = run_phases(s);
+        if (step < 0) return step;  // (the workspace is left to the entry point, which resets it)
+        ctx->ws_release(mark);
+        if (step == START_OVER) continue;
+        if (step == L_COMPLETE || s.carry_bwt) *bwt_written = true;
+        return DK_OK;
+    }
+    return ctx->fail(DK_E_INTERNAL, "suffix_array: the L-first path ran where it was not allowed");
+}
 
 }  // namespace dk

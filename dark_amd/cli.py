@@ -63,7 +63,8 @@ class Refused(SystemExit):
 class _AtomicOutput:
     """The archive is written to a temporary file next to its final name and renamed over it only when it is complete (records and
     footer written, file closed): a refusal, a GPU error or a failed worker leaves an existing archive of that name untouched and never
-    leaves a truncated one behind -- a footer-less prefix of records would otherwise decode as a valid, shorter file."""
+    leaves a truncated one behind -- a footer-less prefix of records would otherwise decode as a valid, shorter file.  Decoding writes the
+    restored file the same way: a record that does not decode (DK_E_STREAM) leaves no output file, partial or otherwise."""
 
     def __init__(self, out_path):
         self.final = out_path
@@ -513,7 +514,7 @@ def decode_file(path, model, device=0, gpus=1, host_threads=0, devices=None, pac
     if footer is None:
         # no index: the reference's single-block file (main.rs:70), or concatenated records walked by the bytes each decode consumed
         size = os.path.getsize(path)
-        with open(path, "rb") as f, open(out_path, "wb") as out:
+        with open(path, "rb") as f, _AtomicOutput(out_path) as out:
             blob = np.fromfile(f, dtype=np.uint8)
             pos, ctx, records = 0, None, 0
             while pos < size:
@@ -539,7 +540,7 @@ def decode_file(path, model, device=0, gpus=1, host_threads=0, devices=None, pac
         return out_path
     offsets, end = footer
     if gpus <= 1:
-        with open(out_path, "wb") as out:
+        with _AtomicOutput(out_path) as out:  # a record that does not decode leaves no output file, partial or otherwise
             if packed:
                 _decode_records_packed(path, model, device, offsets, end, lambda k, data: out.write(data), threads)
             else:
@@ -558,9 +559,12 @@ def decode_file(path, model, device=0, gpus=1, host_threads=0, devices=None, pac
         p.wait()
         rc = rc or p.returncode
     if rc:
+        for part in parts:
+            if os.path.exists(part):
+                os.remove(part)
         raise SystemExit("a GPU worker failed (exit code %d)" % rc)
     files = [open(part, "rb") for part in parts]
-    with open(path, "rb") as f, open(out_path, "wb") as out:
+    with open(path, "rb") as f, _AtomicOutput(out_path) as out:
         for k in range(len(offsets)):
             f.seek(offsets[k])
             (n,) = struct.unpack("<I", f.read(4))

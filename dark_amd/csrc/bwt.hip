@@ -189,6 +189,8 @@ __device__ __forceinline__ bool is_splitter(uint32_t p, uint32_t S, uint32_t ori
 __device__ __forceinline__ uint32_t splitter_id(uint32_t p, uint32_t S, uint32_t origin, uint32_t nreg) {
     return (p == origin && (p % S) != 0) ? nreg : p / S;
 }
+// the splitter the text starts at: its chain to END is the whole text, n entries, exactly when (L, origin) describes one
+__device__ __forceinline__ uint32_t origin_splitter(uint32_t origin, uint32_t S, uint32_t nreg) { return splitter_id(origin, S, origin, nreg); }
 
 // Text step k visits position cur_k: cur_0 = origin, cur_{k+1} = psi[cur_k]... with the reference's convention the
 // text symbol k is L[psi[cur_k]], and the last symbol is L[origin] when psi hits END.
@@ -262,7 +264,9 @@ __global__ __launch_bounds__(256) void k_ibwt_emit(const uint8_t *__restrict__ b
     if (s == nreg) cur = origin;
     else { cur = s * S; if (cur >= n) return; }
     const uint32_t d = dist_to_end[s];
-    if (d > n) { *bad = 1; return; }  // not on the text cycle (corrupt input)
+    // not on the text cycle, or the origin's chain is shorter than the block: the rest sits in cycles that hold no splitter and that no lane
+    // visits, and text[0 .. n - d) would stay unwritten (corrupt input)
+    if (d > n || (s == origin_splitter(origin, S, nreg) && d != n)) { *bad = 1; return; }
     uint32_t k = n - d;  // text offset of the first symbol this splitter emits
     // bytes are gathered into a 64-bit word and leave as one aligned 8-byte store (single bytes only at the ragged ends)
     const bool wide = (reinterpret_cast<uintptr_t>(out) & 7) == 0;
@@ -305,7 +309,8 @@ __global__ __launch_bounds__(256) void k_ibwt_copy(const uint64_t *__restrict__ 
     if (s >= nsplit) return;
     if (s != nreg && static_cast<uint64_t>(s) * S >= n) return;
     const uint32_t d = dist_to_end[s], total = len[s];
-    if (d > n || total > d) { *bad = 1; return; }  // not on the text cycle (corrupt input)
+    // not on the text cycle, or (as in k_ibwt_emit) the origin's chain does not cover the whole block (corrupt input)
+    if (d > n || total > d || (s == origin_splitter(origin, S, nreg) && d != n)) { *bad = 1; return; }
     uint32_t k = n - d;
     const bool wide = (reinterpret_cast<uintptr_t>(out) & 7) == 0;
     uint64_t acc = 0;

@@ -62,7 +62,9 @@ int dk_suffix_array(dk_ctx *ctx, const uint8_t *in, size_t n, uint32_t *sa_out);
 /* compress::bwt::TransformIterator as driven by src/block/dc.rs:45-50: bwt_out[i] = in[SA[i]-1] (in[n-1] where
  * SA[i]==0), *origin = the i with SA[i]==0.  Known answers src/saca.rs:411-412. */
 int dk_bwt_forward(dk_ctx *ctx, const uint8_t *in, size_t n, uint8_t *bwt_out, uint32_t *origin);
-/* compress::bwt::decode as driven by src/block/dc.rs:154-156 */
+/* compress::bwt::decode as driven by src/block/dc.rs:154-156.  DK_E_STREAM when (bwt, origin) is no BWT of any text: the successor
+ * table is then a path from origin that is shorter than n plus one or more cycles, whether or not a cycle is ever visited.  DK_OK means
+ * all n bytes were written.  On DK_E_STREAM `out` is untouched. */
 int dk_bwt_inverse(dk_ctx *ctx, const uint8_t *bwt, size_t n, uint32_t origin, uint8_t *out);
 /* compress::bwt::dc::encode + EncodeIterator as driven by src/block/dc.rs:52,82-85, compacted: one entry per run
  * of the BWT, in position order.  init[s] = first position of s, or n if absent.  dist/sym/rank hold up to n
@@ -110,6 +112,8 @@ unsigned dk_last_block_flags(const dk_ctx *ctx);
 /* ---- device-resident entry points (inputs already in HBM; used by pipelines and by bench.py) ----------------- */
 int dk_dev_suffix_array(dk_ctx *ctx, const uint8_t *d_in, size_t n, uint32_t *d_sa_out);
 int dk_dev_bwt_forward(dk_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_bwt_out, uint32_t *origin);
+/* As dk_bwt_inverse.  On DK_E_STREAM parts of d_out[0, n) may already have been written (unlike the packed inverse below, which checks
+ * before it writes); nothing outside [0, n) ever is.  The same holds for the d_out of the block decoders that end in this inverse. */
 int dk_dev_bwt_inverse(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t origin, uint8_t *d_out);
 /* d_dist/d_sym/d_rank: device arrays of n entries (d_rank may be NULL); init and m are returned on the host */
 int dk_dev_dc_encode(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t init[256],

@@ -174,48 +174,48 @@ def test_errors(ctx):
 
 
 def test_corrupt_block_stays_inside(ctx, orc):
+    """two victims, one pack each: two random unequal bytes of L swapped (a long leftover cycle, which holds a splitter) and a class-e input
+    of tests/ibwt_model.py (adjacent bytes swapped: a short leftover cycle without one).  The model says which candidates are no text, and
+    the single-block inverse must reject the first such candidate; only swaps that leave a text are passed over."""
+    import ibwt_model as M
     rng = np.random.default_rng(21)
     blocks = [u8(datagen.wiki_like(int(n), seed=int(n))) for n in (5000, 70000, 300, 9000, 40000)]
     Ls, origins = zip(*[oracle_bwt(orc, b) for b in blocks])
-    Ls = [L.copy() for L in Ls]
     origins = list(origins)
-    victim = 3
-    L = Ls[victim]
-    for _ in range(500):  # swap two unequal bytes until the single-block inverse rejects the result
+    L = Ls[3]
+    for _ in range(500):
         i, j = (int(x) for x in rng.integers(0, len(L), size=2))
         if L[i] == L[j]:
             continue
         cand = L.copy()
         cand[i], cand[j] = cand[j], cand[i]
-        one = torch.empty(len(L), dtype=torch.uint8, device="cuda")
-        try:
-            ctx.dev_bwt_inverse(dev(cand), len(L), origins[victim], one)
-        except dark_amd.DarkError as e:
-            assert e.code == DK_E_STREAM
-            Ls[victim] = cand
+        if M.invert(cand, origins[3]).text is None:
             break
     else:
-        raise AssertionError("no rejected swap found")
+        raise AssertionError("every swap left a text")
+    short = M.adjacent_swaps(Ls[1], origins[1], orc.sa_sais(blocks[1]))[0]
+    assert short.verdict.text is None and not short.verdict.cycle_has_splitter and short.origin == origins[1]
     sizes, off = pack_layout(blocks)
     total = int(off[-1])
     guard = 4096
-    buf = torch.full((total + 2 * guard,), 0xA5, dtype=torch.uint8, device="cuda")
-    d_bwt = dev(np.concatenate(Ls))
-    with pytest.raises(dark_amd.DarkError) as e:
-        ctx.dev_bwt_inverse_packed(d_bwt, sizes, origins, buf[guard:guard + total])
-    assert e.value.code == DK_E_STREAM
-    assert "block %d " % victim in str(e.value), str(e.value)
-    got = buf.cpu().numpy()
-    assert (got[:guard] == 0xA5).all() and (got[guard + total:] == 0xA5).all(), "guard bytes written"
-    for i in range(len(blocks)):
-        if i != victim:
-            assert (got[guard + off[i]:guard + off[i + 1]] == 0xA5).all(), "range of block %d written" % i
-    # the same context then inverts a correct pack
-    good = [L.copy() for L in Ls]
-    good[victim] = oracle_bwt(orc, blocks[victim])[0]
-    d_out = torch.empty(total, dtype=torch.uint8, device="cuda")
-    ctx.dev_bwt_inverse_packed(dev(np.concatenate(good)), sizes, origins, d_out)
-    assert np.array_equal(d_out.cpu().numpy(), np.concatenate(blocks))
+    for victim, bad in ((3, cand), (1, short.L)):
+        one = torch.empty(len(bad), dtype=torch.uint8, device="cuda")
+        with pytest.raises(dark_amd.DarkError) as e:
+            ctx.dev_bwt_inverse(dev(bad), len(bad), origins[victim], one)
+        assert e.value.code == DK_E_STREAM
+        damaged = [L.copy() for L in Ls]
+        damaged[victim] = bad
+        buf = torch.full((total + 2 * guard,), 0xA5, dtype=torch.uint8, device="cuda")
+        with pytest.raises(dark_amd.DarkError) as e:
+            ctx.dev_bwt_inverse_packed(dev(np.concatenate(damaged)), sizes, origins, buf[guard:guard + total])
+        assert e.value.code == DK_E_STREAM
+        assert "block %d " % victim in str(e.value), str(e.value)
+        got = buf.cpu().numpy()
+        assert (got == 0xA5).all(), "a rejected pack wrote to d_out or to the guard bytes around it"
+        # the same context then inverts a correct pack
+        d_out = torch.empty(total, dtype=torch.uint8, device="cuda")
+        ctx.dev_bwt_inverse_packed(dev(np.concatenate(Ls)), sizes, origins, d_out)
+        assert np.array_equal(d_out.cpu().numpy(), np.concatenate(blocks))
 
 
 def decode_blocks():

@@ -60,6 +60,8 @@ SIGNATURES = {
     "dk_batch_push": (_i, [_vp, _vp, _sz, _vp, _sz, _szp]),
     "dk_batch_finish": (_i, [_vp]),
     "dk_dev_bwt_forward_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _u32p]),
+    "dk_dev_suffix_array_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _u32p]),
+    "dk_suffix_array_packed": (_i, [_vp, _vp, _sz, _vp, _vp]),
     "dk_dev_dc_encode_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _szp]),
     "dk_batch_push_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "dk_dev_packed_encode": (_i, [_vp, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i]),

@@ -98,6 +98,17 @@ class Context:
         self._ck(self._lib.dk_suffix_array(self._h, _ptr(t), len(t), _ptr(sa)))
         return sa
 
+    def suffix_array_packed(self, blocks):
+        """the suffix array of every block (entries local to the block), all of them from one segmented device pass"""
+        keep = [as_u8(b) for b in blocks]
+        count = len(keep)
+        ns = (C.c_size_t * max(count, 1))(*[len(b) for b in keep])
+        t = np.concatenate(keep) if count else np.zeros(0, dtype=np.uint8)
+        sa = np.empty(len(t), dtype=np.uint32)
+        self._ck(self._lib.dk_suffix_array_packed(self._h, _ptr(t), count, ns, _ptr(sa)))
+        ends = np.cumsum([len(b) for b in keep])
+        return [sa[e - len(b):e] for b, e in zip(keep, ends)]
+
     def bwt_forward(self, data):
         t = as_u8(data)
         out = np.empty(len(t), dtype=np.uint8)
@@ -213,6 +224,20 @@ class Context:
         origin = np.zeros(max(count, 1), dtype=np.uint32)
         self._ck(self._lib.dk_dev_bwt_forward_packed(self._h, _ptr(d_in), count, ns, _ptr(d_bwt_out),
                                                      origin.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return [int(o) for o in origin[:count]]
+
+    def dev_suffix_array_packed(self, d_in, sizes, d_sa_out, d_bwt_out=None):
+        """the suffix array of every block into d_sa_out (uint32, same layout as d_in, entries local to the block); with d_bwt_out also L
+        of every block, from the same pass: returns the list of origins then, else None"""
+        _inputs_ready(d_in)
+        count = len(sizes)
+        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
+        if d_bwt_out is None:
+            self._ck(self._lib.dk_dev_suffix_array_packed(self._h, _ptr(d_in), count, ns, _ptr(d_sa_out), None, None))
+            return None
+        origin = np.zeros(max(count, 1), dtype=np.uint32)
+        self._ck(self._lib.dk_dev_suffix_array_packed(self._h, _ptr(d_in), count, ns, _ptr(d_sa_out), _ptr(d_bwt_out),
+                                                      origin.ctypes.data_as(C.POINTER(C.c_uint32))))
         return [int(o) for o in origin[:count]]
 
     def dev_dc_encode_packed(self, d_bwt, sizes, d_dist, d_sym, d_rank=None):

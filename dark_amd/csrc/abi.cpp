@@ -62,6 +62,9 @@ size_t workspace_bytes(size_t max_n) {
     // BWT's successor table (8 n) are allocated after the sort's temporaries are released and take their place.
     // The packed inverse (dk_dev_packed_decode: L n, successor table 8 n, walk records at most 8 n, splitter arrays at most 32 n, per-block words
     // 16 count <= 16 n) stays below 65 n; its table of every block's symbol bases (count x 1 KiB, at most 64 MiB) fits the constant term.
+    // The packed suffix arrays (dk_suffix_array_packed: text n, SA 4 n, the pack's temporaries 32 n + the sort's 1.25 n) stay below 39 n.  Their guard
+    // runs after those temporaries are released, straight into the block's stretch of the output: text + SA 5 n and the single-block sort
+    // 63.4 n_i (no L from the sort, so the L-first path and its 23 MiB never run) = at most 68.4 n.
     // tests/test_gpu_parity.py::test_workspace_accounting checks peak <= size on contexts sized exactly to their block, and
     // tests/test_gpu_fullsize.py checks the n-proportional term where the constant is negligible (peak - 64 MiB <= 69.4 n at 1e8 bytes).
     const size_t sort_temporaries = 62 * max_n + max_n / 8, io = 6 * max_n, on_top = max_n / 4 + max_n;
@@ -523,9 +526,10 @@ int check_pack(dk_ctx *ctx, size_t count, const size_t *n, std::vector<uint32_t>
     return DK_OK;
 }
 
-// L of every block into d_bwt and the origins into h_origin (host, count): one segmented pass, then the guard's blocks one by one
+// L of every block into d_bwt and the origins into h_origin (host, count): one segmented pass, then the guard's blocks one by one.
+// d_sa (may be null): the suffix arrays too, from the same pass (dk_dev_suffix_array_packed); then d_bwt / d_origin may both be null.
 int packed_forward(dk_ctx *ctx, const uint8_t *d_in, const std::vector<uint32_t> &off, const uint32_t *d_off, uint8_t *d_bwt, uint32_t *d_origin,
-                   std::vector<std::pair<size_t, uint32_t>> *fixed) {
+                   std::vector<std::pair<size_t, uint32_t>> *fixed, uint32_t *d_sa = nullptr) {
     hipStream_t st = ctx->stream;
     const size_t count = off.size() - 1, total = off.back();
     Timer t;
@@ -535,7 +539,8 @@ int packed_forward(dk_ctx *ctx, const uint8_t *d_in, const std::vector<uint32_t>
     size_t unresolved = 0;
     // (tuning build: DK_PACKED_ROUNDS lowers the limit, clamped to [0, PACKED_MAX_ROUNDS] -- a test hook that sends blocks through the guard)
     const int max_rounds = std::max(0, std::min(PACKED_MAX_ROUNDS, DK_KNOB("DK_PACKED_ROUNDS", PACKED_MAX_ROUNDS)));
-    DK_TRY(packed_bwt_device(ctx, d_in, d_off, count, total, d_bwt, d_origin, d_guard, max_rounds, &unresolved));
+    if (d_sa) DK_TRY(packed_sa_device(ctx, d_in, d_off, count, total, d_sa, d_bwt, d_origin, d_guard, max_rounds, &unresolved));
+    else DK_TRY(packed_bwt_device(ctx, d_in, d_off, count, total, d_bwt, d_origin, d_guard, max_rounds, &unresolved));
     fixed->clear();
     if (unresolved) {
         std::vector<uint32_t> guard(count);
@@ -545,10 +550,19 @@ int packed_forward(dk_ctx *ctx, const uint8_t *d_in, const std::vector<uint32_t>
         for (size_t i = 0; i < count; ++i) {
             if (!guard[i]) continue;
             const size_t mark = ctx->ws_mark(), n = off[i + 1] - off[i];
-            uint32_t *d_sa = ctx->ws_alloc<uint32_t>(n);
-            if (!d_sa) return DK_E_NOMEM;
             uint32_t origin = 0;
-            DK_TRY(bwt_forward_device(ctx, d_in + off[i], n, d_sa, d_bwt + off[i], &origin));
+            if (d_sa) {
+                // The complete suffix array is wanted: not bwt_forward_device, whose L-first route never fills one.  The block's stretches of
+                // the text and of the output have any alignment, as the caller's own buffers of dk_dev_suffix_array do: every 16-byte access
+                // of the single-block sort and of k_bwt_gather to either checks the address first and goes element by element otherwise.
+                uint32_t *d_one = d_sa + off[i];
+                DK_TRY(suffix_array_device(ctx, d_in + off[i], n, d_one));
+                if (d_bwt) DK_TRY(bwt_gather_device(ctx, d_in + off[i], d_one, n, d_bwt + off[i], &origin));
+            } else {
+                uint32_t *d_one = ctx->ws_alloc<uint32_t>(n);
+                if (!d_one) return DK_E_NOMEM;
+                DK_TRY(bwt_forward_device(ctx, d_in + off[i], n, d_one, d_bwt + off[i], &origin));
+            }
             fixed->emplace_back(i, origin);
             ctx->ws_release(mark);
         }
@@ -581,6 +595,30 @@ int dk_dev_bwt_forward_packed(dk_ctx *ctx, const uint8_t *d_in, size_t count, co
     DK_HIP(ctx, hipMemcpyAsync(origin, d_origin, count * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     DK_HIP(ctx, hipStreamSynchronize(st));
     for (const auto &f : fixed) origin[f.first] = f.second;
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_dev_suffix_array_packed(dk_ctx *ctx, const uint8_t *d_in, size_t count, const size_t *n, uint32_t *d_sa_out, uint8_t *d_bwt_out,
+                               uint32_t *origin) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!d_in || !n || !d_sa_out) return ctx->fail(DK_E_ARG, "null pointer");
+    if ((d_bwt_out == nullptr) != (origin == nullptr)) return ctx->fail(DK_E_ARG, "d_bwt_out and origin go together: both or neither");
+    std::vector<uint32_t> off;
+    DK_TRY(check_pack(ctx, count, n, off));
+    Timer t;
+    hipStream_t st = ctx->stream;
+    uint32_t *d_off = ctx->ws_alloc<uint32_t>(count + 1), *d_origin = d_bwt_out ? ctx->ws_alloc<uint32_t>(count) : nullptr;
+    if (!d_off || (d_bwt_out && !d_origin)) return DK_E_NOMEM;
+    DK_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    std::vector<std::pair<size_t, uint32_t>> fixed;
+    DK_TRY(packed_forward(ctx, d_in, off, d_off, d_bwt_out, d_origin, &fixed, d_sa_out));
+    if (d_bwt_out) {
+        DK_HIP(ctx, hipMemcpyAsync(origin, d_origin, count * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        DK_HIP(ctx, hipStreamSynchronize(st));
+        for (const auto &f : fixed) origin[f.first] = f.second;
+    }
     ctx->stats.ms_total = t.ms();
     return DK_OK;
 }
@@ -928,6 +966,29 @@ int dk_suffix_array(dk_ctx *ctx, const uint8_t *in, size_t n, uint32_t *sa_out) 
     DK_TRY(suffix_array_device(ctx, d_text, n, d_sa));
     DK_HIP(ctx, hipMemcpyAsync(sa_out, d_sa, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_suffix_array_packed(dk_ctx *ctx, const uint8_t *in, size_t count, const size_t *n, uint32_t *sa_out) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!in || !n || !sa_out) return ctx->fail(DK_E_ARG, "null pointer");
+    std::vector<uint32_t> off;
+    DK_TRY(check_pack(ctx, count, n, off));
+    Timer t;
+    hipStream_t st = ctx->stream;
+    const size_t total = off.back();
+    uint8_t *d_text = ctx->ws_alloc<uint8_t>(total);
+    uint32_t *d_sa = ctx->ws_alloc<uint32_t>(total);
+    uint32_t *d_off = ctx->ws_alloc<uint32_t>(count + 1);
+    if (!d_text || !d_sa || !d_off) return DK_E_NOMEM;
+    DK_HIP(ctx, hipMemcpyAsync(d_text, in, total, hipMemcpyHostToDevice, st));
+    DK_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    std::vector<std::pair<size_t, uint32_t>> fixed;
+    DK_TRY(packed_forward(ctx, d_text, off, d_off, nullptr, nullptr, &fixed, d_sa));
+    DK_HIP(ctx, hipMemcpyAsync(sa_out, d_sa, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    DK_HIP(ctx, hipStreamSynchronize(st));
     ctx->stats.ms_total = t.ms();
     return DK_OK;
 }

@@ -220,6 +220,10 @@ int dc_encode_device(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t init_
 // *guarded = the number of suffixes left unresolved (0: every block is done).
 int packed_bwt_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, size_t count, size_t total, uint8_t *d_bwt, uint32_t *d_origin,
                       uint32_t *d_guard, int max_rounds, size_t *guarded);
+// packed_sa_device: the same sort, then block i's suffix array at d_sa[off_i, off_i + n_i), entries local to the block; d_bwt / d_origin (both
+// or neither) as from packed_bwt_device, written by the same kernel.  Guarded blocks' stretches are NOT valid, as above.
+int packed_sa_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, size_t count, size_t total, uint32_t *d_sa, uint8_t *d_bwt,
+                     uint32_t *d_origin, uint32_t *d_guard, int max_rounds, size_t *guarded);
 // packed_dc_device: the DC arrays of every block of a packed L.  compact: block i's entries at [rb_i, rb_i + m_i) (global run order, rb on the
 // device in d_rb[0 .. count], d_rb[count] = all runs); otherwise at [off_i, off_i + m_i).  d_m / d_flags: count words, d_init: count x 256.
 int packed_dc_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, bool compact, uint32_t *d_dist,

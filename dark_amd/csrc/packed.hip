@@ -17,6 +17,9 @@
 //                 at list index k of an old group that starts at list index ks and slot g gets the slot g + (head of its new group - ks);
 //                 singletons leave, the other members are compacted (order kept) into the next round's list.
 //   k_pk_scatter  L[rank[p]] = text[p-1] (text[e_i-1] in front of off_i), origin_i = rank[off_i] - off_i.
+//   k_pk_emit     the packed suffix arrays (packed_sa_device): after the rounds rank is the inverse suffix array of
+//                 the whole pack, so SA[rank[p]] = p - off_i; the same thread writes L and the origin when they are wanted too.  The sort
+//                 (packed_sort_device: everything up to the guard) is shared; packed_bwt_device and packed_sa_device differ in the emit alone.
 // Segmented DC over the runs of L, in L order (the single-block kernels of dc.hip walk R; the results are the same):
 //   k_pdc_count / k_pk_scan_u32 / k_pdc_runs   runs (a run never crosses a block head), their start, symbol and each block's first run rb_i
 //   k_pdc_summary / k_pdc_carry_*              per tile of 4096 runs the last run of every symbol, exclusive max-scan over tiles: the last
@@ -221,6 +224,26 @@ __global__ __launch_bounds__(256) void k_pk_scatter(const uint8_t *__restrict__ 
     const uint32_t slot = rank[p];
     L[slot] = t[p == s ? off[blk + 1] - 1 : p - 1];
     if (p == s) origin[blk] = slot - s;
+}
+
+// The suffix arrays of the pack: SA[rank[p]] = p - off_blk, entries local to the block; with L != nullptr the same thread also writes what
+// k_pk_scatter writes (rank[p] and the block search are loaded once for both).  rank[p] lies in [off_blk, e_blk) for every suffix of the
+// block, resolved or not, so no store leaves the block's own stretch of the outputs.  The members of a group still unresolved at the round
+// limit share one rank: several threads then store to the same slot with plain stores and other slots of the block stay unwritten.  That
+// is harmless: the block is marked in the guard words and the caller redoes its whole stretch alone.
+__global__ __launch_bounds__(256) void k_pk_emit(const uint8_t *__restrict__ t, const uint32_t *__restrict__ off, uint32_t count, uint32_t total,
+                                                 const uint32_t *__restrict__ rank, uint32_t *__restrict__ sa, uint8_t *__restrict__ L,
+                                                 uint32_t *__restrict__ origin) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= total) return;
+    const uint32_t blk = seg_of(off, count, p);
+    const uint32_t s = off[blk];
+    const uint32_t slot = rank[p];
+    sa[slot] = p - s;
+    if (L) {
+        L[slot] = t[p == s ? off[blk + 1] - 1 : p - 1];
+        if (p == s) origin[blk] = slot - s;
+    }
 }
 
 // ---- distance coding -------------------------------------------------------------------------------------------------------------------
@@ -438,13 +461,14 @@ __global__ __launch_bounds__(256) void k_pdc_final(const uint32_t *__restrict__ 
     }
 }
 
-}  // namespace
-
-int packed_bwt_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, size_t count, size_t total, uint8_t *d_bwt, uint32_t *d_origin,
-                      uint32_t *d_guard, int max_rounds, size_t *guarded) {
+// The segmented suffix sort, up to and including the guard: *rank_out[p] = the final slot of suffix p (the first slot of its group for the
+// members of a group still unresolved after max_rounds), d_guard[i] = 1 for the blocks that hold such a group, *guarded = their suffixes.
+// rank lives in the workspace together with the sort's temporaries: the caller takes ws_mark() before the call and releases it once it
+// has emitted what it wants from rank.
+int packed_sort_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, size_t count, size_t total, uint32_t *d_guard, int max_rounds,
+                       const uint32_t **rank_out, size_t *guarded) {
     hipStream_t st = ctx->stream;
     const uint32_t cnt = static_cast<uint32_t>(count), T = static_cast<uint32_t>(total);
-    const size_t mark = ctx->ws_mark();
     uint64_t *keys = ctx->ws_alloc<uint64_t>(total), *keys_alt = ctx->ws_alloc<uint64_t>(total);
     uint32_t *vals = ctx->ws_alloc<uint32_t>(total), *vals_alt = ctx->ws_alloc<uint32_t>(total);
     uint32_t *act = ctx->ws_alloc<uint32_t>(total), *rank = ctx->ws_alloc<uint32_t>(total);
@@ -517,12 +541,40 @@ int packed_bwt_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off,
         LaunchScope ls(ctx, K_RERANK_APPLY, 8.0 * live);
         k_pk_guard_mark<<<dim3(static_cast<unsigned>(div_up(live, 256))), dim3(256), 0, st>>>(act, live, d_off, cnt, d_guard);
     }
+    DK_HIP(ctx, hipGetLastError());
+    *rank_out = rank;
+    *guarded = live;
+    return DK_OK;
+}
+
+}  // namespace
+
+int packed_bwt_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, size_t count, size_t total, uint8_t *d_bwt, uint32_t *d_origin,
+                      uint32_t *d_guard, int max_rounds, size_t *guarded) {
+    const size_t mark = ctx->ws_mark();
+    const uint32_t *rank = nullptr;
+    DK_TRY(packed_sort_device(ctx, d_text, d_off, count, total, d_guard, max_rounds, &rank, guarded));
     {
         LaunchScope ls(ctx, K_BWT_GATHER, 6.0 * total);
-        k_pk_scatter<<<dim3(static_cast<unsigned>(div_up(total, 256))), dim3(256), 0, st>>>(d_text, d_off, cnt, T, rank, d_bwt, d_origin);
+        k_pk_scatter<<<dim3(static_cast<unsigned>(div_up(total, 256))), dim3(256), 0, ctx->stream>>>(
+            d_text, d_off, static_cast<uint32_t>(count), static_cast<uint32_t>(total), rank, d_bwt, d_origin);
     }
     DK_HIP(ctx, hipGetLastError());
-    *guarded = live;
+    ctx->ws_release(mark);
+    return DK_OK;
+}
+
+int packed_sa_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, size_t count, size_t total, uint32_t *d_sa, uint8_t *d_bwt,
+                     uint32_t *d_origin, uint32_t *d_guard, int max_rounds, size_t *guarded) {
+    const size_t mark = ctx->ws_mark();
+    const uint32_t *rank = nullptr;
+    DK_TRY(packed_sort_device(ctx, d_text, d_off, count, total, d_guard, max_rounds, &rank, guarded));
+    {
+        LaunchScope ls(ctx, K_BWT_GATHER, (d_bwt ? 10.0 : 8.0) * total);
+        k_pk_emit<<<dim3(static_cast<unsigned>(div_up(total, 256))), dim3(256), 0, ctx->stream>>>(
+            d_text, d_off, static_cast<uint32_t>(count), static_cast<uint32_t>(total), rank, d_sa, d_bwt, d_origin);
+    }
+    DK_HIP(ctx, hipGetLastError());
     ctx->ws_release(mark);
     return DK_OK;
 }

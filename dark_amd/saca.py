@@ -3,7 +3,7 @@ from .context import Context
 
 
 class Constructor:
-    """saca::Constructor: `new(max_n)`, `capacity()`, `compute(input) -> suffix array`."""
+    """saca::Constructor: `new(max_n)`, `capacity()`, `compute(input) -> suffix array`; `compute_packed(inputs)` is this library's packed form."""
 
     def __init__(self, max_n, device=0):
         self._ctx = Context(max_n, device)
@@ -16,6 +16,14 @@ class Constructor:
         if len(data) != self._n:  # src/saca.rs:369 assert_eq!(input.len(), self.n)
             raise ValueError("Constructor sized for %d bytes got %d" % (self._n, len(data)))
         return self._ctx.suffix_array(data)
+
+    def compute_packed(self, inputs):
+        """compute for many small inputs at once: a list of suffix arrays, one per input, from one segmented device pass.  The inputs
+        together must fit the capacity (each alone need not have the constructor's exact size)."""
+        total = sum(len(x) for x in inputs)
+        if total > self.capacity():
+            raise ValueError("Constructor sized for %d bytes got a pack of %d" % (self.capacity(), total))
+        return self._ctx.suffix_array_packed(inputs)
 
     def context(self):
         """the analogue of reuse(): the device workspace is lent to the later stages through the context"""

@@ -62,6 +62,27 @@ public:
         if (rc != DK_OK) throw Error(rc, ctx_.error());
         return suffixes_;
     }
+    // compute for many small inputs at once (dk_suffix_array_packed): the suffix array of inputs[i], entries local to it, at result[i].
+    // The inputs together must fit the capacity; each alone need not have the constructor's exact size.
+    std::vector<std::vector<Suffix>> compute_packed(const std::vector<std::vector<Symbol>> &inputs) {
+        std::vector<size_t> sizes;
+        std::vector<Symbol> text;
+        for (const auto &in : inputs) {
+            sizes.push_back(in.size());
+            text.insert(text.end(), in.begin(), in.end());
+        }
+        if (text.size() > capacity()) throw Error(DK_E_ARG, "assertion failed: total input length <= self.capacity()");
+        std::vector<Suffix> all(text.size());
+        int rc = dk_suffix_array_packed(ctx_.get(), text.data(), sizes.size(), sizes.data(), all.data());
+        if (rc != DK_OK) throw Error(rc, ctx_.error());
+        std::vector<std::vector<Suffix>> out;
+        size_t at = 0;
+        for (size_t n : sizes) {
+            out.emplace_back(all.begin() + static_cast<std::ptrdiff_t>(at), all.begin() + static_cast<std::ptrdiff_t>(at + n));
+            at += n;
+        }
+        return out;
+    }
     detail::Ctx &context() { return ctx_; }  // plays reuse(): later stages share the device workspace through it
 private:
     detail::Ctx ctx_;

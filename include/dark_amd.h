@@ -148,6 +148,14 @@ int dk_batch_finish(dk_batch *batch);
 #define DK_PACKED_MAX_BLOCK_BYTES (1u << 24)
 /* L of block i at d_bwt_out[off_i, off_i + n[i]), origin[i] (host, count entries) as from dk_dev_bwt_forward */
 int dk_dev_bwt_forward_packed(dk_ctx *ctx, const uint8_t *d_in, size_t count, const size_t *n, uint8_t *d_bwt_out, uint32_t *origin);
+/* saca::Constructor::compute (src/saca.rs:368-378) for every block of a pack, same layout and limits as dk_dev_bwt_forward_packed:
+ * block i's suffix array at d_sa_out[off_i, off_i + n[i]), entries LOCAL to the block (0 .. n[i]-1), equal to what dk_dev_suffix_array
+ * gives for block i alone.  d_bwt_out (may be NULL): L of block i at d_bwt_out[off_i, ...) and origin[i] (host, count entries) as from
+ * dk_dev_bwt_forward_packed, from the same pass.  origin may be NULL exactly when d_bwt_out is (DK_E_ARG otherwise). */
+int dk_dev_suffix_array_packed(dk_ctx *ctx, const uint8_t *d_in, size_t count, const size_t *n, uint32_t *d_sa_out,
+                               uint8_t *d_bwt_out, uint32_t *origin);
+/* the same from host memory (the reference's &[u8] inputs laid back to back): one upload, one pass, one download */
+int dk_suffix_array_packed(dk_ctx *ctx, const uint8_t *in, size_t count, const size_t *n, uint32_t *sa_out);
 /* DC arrays of a packed L: block i's entries at [off_i, off_i + m[i]) of d_dist / d_sym / d_rank (device, sum of n entries each; d_rank may
  * be NULL), init (host, count x 256: block i's table at init[256 i]) and m (host, count) as from dk_dev_dc_encode */
 int dk_dev_dc_encode_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, const size_t *n, uint32_t *init, uint32_t *d_dist, uint8_t *d_sym,

@@ -19,6 +19,11 @@ Extensions beyond the reference (whole file = one block, read into memory, one t
   --gpus G   block b -> GPU b mod G, one worker process per GPU; the parent never touches a GPU and stitches the records in order.
   --force    encode blocks that contain byte 0xFF.  The reference's header cannot carry that symbol (src/block/dc.rs:57,60,73,127):
              it writes such an archive without complaint and can never decode it.  This front end refuses unless --force is given.
+  --any-byte encode ANY file so that it decodes (DK_MODEL_ANYBYTE; not together with --force).  A block without byte 0xFF is
+             written as the plain record [u32 n][stream], so a file without 0xFF gives the same archive with and without the option.  A
+             block with 0xFF is written as [u32 n | 0x80000000][u32 first position of 0xFF in the BWT][stream]: the stream is still the
+             reference's, the four bytes in front are what its header leaves out.  Decoding needs no option: bit 31 of a record's n says
+             which kind it is.  The reference cannot read a record with bit 31 set.
 """
 import argparse
 import os
@@ -36,6 +41,33 @@ STATS = {}  # --stats: when the library and its context were ready (imports, wor
 FOOTER_MAGIC = b"DKIX"
 DUMP_MODELS = ("raw", "rawdc")
 RAW_CODING_MODELS = ("bbb",)  # block::raw with a coding RawModel (src/main.rs:73,104): block after block through dk_raw_block_encode
+ANY_BYTE_BIT = 0x80000000  # in a record's n: the stream starts with the any-byte prefix (n itself is at most 2^31 - 2, so the bit is free)
+ANY_BYTE_SUFFIX = "+ff"    # _lib.MODEL_IDS: the model with DK_MODEL_ANYBYTE
+
+
+def _record_head(n, stream, any_byte):
+    """-> (the record's first four bytes, the rest of the record) for a block of n bytes coded as `stream`.  Under --any-byte the stream
+    starts with the prefix the library wrote: prefix == n means "no 0xFF in this block", and the record is the plain one."""
+    if not any_byte:
+        return struct.pack("<I", n), memoryview(stream)
+    (first_ff,) = struct.unpack("<I", bytes(stream[:4]))
+    if first_ff == n:
+        return struct.pack("<I", n), memoryview(stream)[4:]
+    return struct.pack("<I", n | ANY_BYTE_BIT), memoryview(stream)
+
+
+def _split_n(word):
+    """a record's first word -> (n, the stream carries the any-byte prefix)"""
+    return word & (ANY_BYTE_BIT - 1), bool(word & ANY_BYTE_BIT)
+
+
+def _uniform_streams(model, ns, flagged, streams):
+    """A batch or pack takes ONE model id.  With at least one flagged record in it, plain records get the prefix "absent" (= n) put in
+    front -- a copy of compressed bytes only -- and the call runs with the flag; without any, everything is as it always was."""
+    if not any(flagged):
+        return model, streams
+    return model + ANY_BYTE_SUFFIX, [s if fl else np.concatenate([np.frombuffer(struct.pack("<I", n), dtype=np.uint8), s])
+                                     for n, fl, s in zip(ns, flagged, streams)]
 
 
 def set_extension(name, ext):
@@ -116,7 +148,7 @@ def _check_ff(block, force, where):
 
 
 # ---- single block: the reference's own behaviour ------------------------------------------------------------------------------------
-def _encode_single(path, model, device, force, out_path):
+def _encode_single(path, model, device, force, out_path, any_byte=False):
     from .context import Context
     data = np.fromfile(path, dtype=np.uint8)  # main.rs:87-95 reads the whole file: one block
     n = len(data)
@@ -126,8 +158,13 @@ def _encode_single(path, model, device, force, out_path):
         _check_ff(data, force, "the block")               # before the output is touched
     _note_single_symbol(data, "the input")
     with Context(n, device) as ctx, _AtomicOutput(out_path) as out:
-        out.write(struct.pack("<I", n))                   # main.rs:102
-        _write_block(ctx, model, data, out, True, force)
+        if any_byte:
+            head, body = _record_head(n, ctx.block_encode(model + ANY_BYTE_SUFFIX, data), True)
+            out.write(head)
+            out.write(body)
+        else:
+            out.write(struct.pack("<I", n))               # main.rs:102
+            _write_block(ctx, model, data, out, True, force)
     return out_path
 
 
@@ -168,7 +205,7 @@ def _reader(f, block_size, first_block, step, total_blocks, q, force, device):
         q.put(e)
 
 
-def _encode_blocks(path, model, block_size, device, first_block, step, total_blocks, out, index, force, host_threads):
+def _encode_blocks(path, model, block_size, device, first_block, step, total_blocks, out, index, force, host_threads, any_byte=False):
     """encode blocks first_block, first_block+step, ... of `path` in order into `out`; index gets (block number, record length).
     Every block goes through dk_batch_push as soon as it is in HBM: its device stages run at once, its coding on one of the host threads;
     file reading, upload, GPU stages and coding all overlap.  Records are written out every `flush_every` blocks."""
@@ -189,9 +226,10 @@ def _encode_blocks(path, model, block_size, device, first_block, step, total_blo
                 return
             streams = batch.finish()
             for (b, n), s in zip(pending, streams):
-                out.write(struct.pack("<I", n))
-                out.write(memoryview(s))
-                index.append((b, 4 + len(s)))
+                head, body = _record_head(n, s, any_byte)
+                out.write(head)
+                out.write(body)
+                index.append((b, 4 + len(body)))
             batch, pending = None, []
 
         try:
@@ -203,7 +241,7 @@ def _encode_blocks(path, model, block_size, device, first_block, step, total_blo
                     raise item
                 b, n, d = item
                 if batch is None:
-                    batch = ctx.batch_begin(model, host_threads)
+                    batch = ctx.batch_begin(model + ANY_BYTE_SUFFIX if any_byte else model, host_threads)
                 batch.push(d, n)  # a failed push closes the batch (joins the coders of the blocks before it) and raises
                 pending.append((b, n))
                 del d, item
@@ -220,7 +258,7 @@ PACK_BYTES = 64 << 20
 PACKED_MAX_BLOCK_BYTES = 1 << 24  # DK_PACKED_MAX_BLOCK_BYTES  # --packed: consecutive blocks grouped into packs of at most this many bytes
 
 
-def _encode_blocks_packed(path, model, block_size, device, total_blocks, out, index, force, host_threads):
+def _encode_blocks_packed(path, model, block_size, device, total_blocks, out, index, force, host_threads, any_byte=False):
     """--packed: consecutive blocks go to the GPU as one pack (dk_batch_push_packed: one segmented device pass per pack, every block still
     coded as its own job); the records are byte-identical to _encode_blocks'."""
     import torch
@@ -238,9 +276,10 @@ def _encode_blocks_packed(path, model, block_size, device, total_blocks, out, in
                 return
             streams = batch.finish()
             for (b, n), s in zip(pending, streams):
-                out.write(struct.pack("<I", n))
-                out.write(memoryview(s))
-                index.append((b, 4 + len(s)))
+                head, body = _record_head(n, s, any_byte)
+                out.write(head)
+                out.write(body)
+                index.append((b, 4 + len(body)))
             batch, pending = None, []
 
         try:
@@ -252,7 +291,7 @@ def _encode_blocks_packed(path, model, block_size, device, total_blocks, out, in
                     _note_single_symbol(data[k:k + block_size], "block %d" % (b0 + j))
                 d = torch.from_numpy(data).to("cuda:%d" % device)
                 if batch is None:
-                    batch = ctx.batch_begin(model, host_threads)
+                    batch = ctx.batch_begin(model + ANY_BYTE_SUFFIX if any_byte else model, host_threads)
                 batch.push_packed(d, sizes)
                 pending.extend((b0 + j, n) for j, n in enumerate(sizes))
                 del d, data
@@ -315,14 +354,23 @@ def _devices(device, gpus, devices):
     return [device + r for r in range(gpus)]
 
 
-def encode_file(path, model, block_size=0, device=0, gpus=1, force=False, host_threads=0, devices=None, packed=False):
+def encode_file(path, model, block_size=0, device=0, gpus=1, force=False, host_threads=0, devices=None, packed=False, any_byte=False):
     out_path = output_name(path, EXTENSION)
+    if any_byte:  # before any output is touched
+        if force:
+            raise SystemExit("--any-byte and --force exclude each other: one writes blocks with byte 0xFF so that they decode, the other so that they are lost")
+        if model in DUMP_MODELS:
+            raise SystemExit("--any-byte: model %s writes no stream the option could extend" % model)
+        if model in RAW_CODING_MODELS:
+            any_byte = False  # block::raw carries every byte value already
+        else:
+            force = True      # no host scan for 0xFF: whether a block holds one comes back from the library, in the prefix
     total = os.path.getsize(path)
     if total == 0:
         raise SystemExit("empty input: the reference panics on it (src/saca.rs:107)")
     _note_model(model)
     if not block_size or block_size >= total:
-        return _encode_single(path, model, device, force, out_path)
+        return _encode_single(path, model, device, force, out_path, any_byte)
     nblocks = -(-total // block_size)
     if model in DUMP_MODELS or model in RAW_CODING_MODELS:  # block after block through the host entry points
         from .context import Context
@@ -340,9 +388,9 @@ def encode_file(path, model, block_size=0, device=0, gpus=1, force=False, host_t
         index = []
         with _AtomicOutput(out_path) as out:
             if packed:
-                _encode_blocks_packed(path, model, block_size, device, nblocks, out, index, force, threads)
+                _encode_blocks_packed(path, model, block_size, device, nblocks, out, index, force, threads, any_byte)
             else:
-                _encode_blocks(path, model, block_size, device, 0, 1, nblocks, out, index, force, threads)
+                _encode_blocks(path, model, block_size, device, 0, 1, nblocks, out, index, force, threads, any_byte)
             offsets, pos = [], 0
             for _, ln in index:
                 offsets.append(pos)
@@ -355,7 +403,7 @@ def encode_file(path, model, block_size=0, device=0, gpus=1, force=False, host_t
     devs = _devices(device, gpus, devices)
     for r in range(gpus):
         cmd = [sys.executable, "-m", "dark_amd.cli", "--worker", "%d/%d" % (r, gpus), "--part", parts[r], "-m", model, "-b", str(block_size),
-               "-d", str(devs[r]), "--host-threads", str(threads)] + (["--force"] if force else []) + [path]
+               "-d", str(devs[r]), "--host-threads", str(threads)] + (["--any-byte"] if any_byte else ["--force"] if force else []) + [path]
         procs.append(subprocess.Popen(cmd, env=dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.dirname(os.path.dirname(os.path.abspath(__file__)))] +
                                                                                                os.environ.get("PYTHONPATH", "").split(os.pathsep)))))
     rc = 0
@@ -393,7 +441,8 @@ def _worker_encode(args):
     nblocks = -(-total // args.block_size)
     index = []
     with open(args.part, "wb") as out:
-        _encode_blocks(args.file, args.model, args.block_size, args.device, r, g, nblocks, out, index, args.force, args.host_threads or 1)
+        _encode_blocks(args.file, args.model, args.block_size, args.device, r, g, nblocks, out, index, args.force or args.any_byte,
+                       args.host_threads or 1, args.any_byte)
     with open(args.part + ".idx", "w") as f:
         f.write(" ".join(str(ln) for _, ln in index))
 
@@ -406,10 +455,12 @@ def _decode_records_batched(path, model, device, offsets, end, which, out_write,
     torch.cuda.set_device(device)
     bounds = offsets + [end]
     with open(path, "rb") as f:
-        sizes = []
+        sizes, flagged = [], []
         for k in which:
             f.seek(offsets[k])
-            sizes.append(struct.unpack("<I", f.read(4))[0])
+            n, fl = _split_n(struct.unpack("<I", f.read(4))[0])
+            sizes.append(n)
+            flagged.append(fl)
         if not sizes:
             return
         batch = int(max(2, min(4 * host_threads, (1 << 30) // max(sizes))))  # two batches of outputs live in HBM at a time
@@ -442,7 +493,8 @@ def _decode_records_batched(path, model, device, offsets, end, which, out_write,
                         f.seek(offsets[k] + 4)
                         streams.append(np.fromfile(f, dtype=np.uint8, count=bounds[k + 1] - offsets[k] - 4))
                     d_outs = [torch.empty(n, dtype=torch.uint8, device="cuda:%d" % device) for n in ns]
-                    ctx.dev_batch_decode(model, streams, ns, d_outs, host_threads)
+                    call_model, streams = _uniform_streams(model, ns, flagged[lo:lo + batch], streams)
+                    ctx.dev_batch_decode(call_model, streams, ns, d_outs, host_threads)
                     wq.put((ks, d_outs))
                     del d_outs, streams
                     if werr:
@@ -462,10 +514,12 @@ def _decode_records_packed(path, model, device, offsets, end, out_write, host_th
     torch.cuda.set_device(device)
     bounds = offsets + [end]
     with open(path, "rb") as f:
-        sizes = []
+        sizes, flagged = [], []
         for k in range(len(offsets)):
             f.seek(offsets[k])
-            sizes.append(struct.unpack("<I", f.read(4))[0])
+            n, fl = _split_n(struct.unpack("<I", f.read(4))[0])
+            sizes.append(n)
+            flagged.append(fl)
         # segments in record order: [kind, records, bytes], "pack" for small records (one pack each), "big" for a run of the others
         segments = []
         for k, n in enumerate(sizes):
@@ -490,7 +544,8 @@ def _decode_records_packed(path, model, device, offsets, end, out_write, host_th
                     streams.append(np.fromfile(f, dtype=np.uint8, count=bounds[k + 1] - offsets[k] - 4))
                 ns = [sizes[k] for k in ks]
                 d_out = torch.empty(sum(ns), dtype=torch.uint8, device="cuda:%d" % device)
-                ctx.dev_packed_decode(model, streams, ns, d_out, host_threads)
+                call_model, streams = _uniform_streams(model, ns, [flagged[k] for k in ks], streams)
+                ctx.dev_packed_decode(call_model, streams, ns, d_out, host_threads)
                 data = d_out.cpu().numpy()
                 pos = 0
                 for k, n in zip(ks, ns):
@@ -521,6 +576,9 @@ def decode_file(path, model, device=0, gpus=1, host_threads=0, devices=None, pac
                 if pos + 4 > size:
                     raise SystemExit("truncated record header at byte %d" % pos)
                 (n,) = struct.unpack("<I", blob[pos:pos + 4].tobytes())   # main.rs:70
+                any_byte = False
+                if model not in RAW_CODING_MODELS:
+                    n, any_byte = _split_n(n)
                 pos += 4
                 if ctx is None or ctx.capacity() < n:
                     if ctx is not None:
@@ -529,7 +587,7 @@ def decode_file(path, model, device=0, gpus=1, host_threads=0, devices=None, pac
                 if model in RAW_CODING_MODELS:
                     out.write(ctx.raw_block_decode(blob[pos:], n, 1))   # block::raw::Decoder, main.rs:73
                 else:
-                    out.write(ctx.block_decode(model, blob[pos:], n))
+                    out.write(ctx.block_decode(model + ANY_BYTE_SUFFIX if any_byte else model, blob[pos:], n))
                 pos += ctx.last_consumed()
                 records += 1
             if ctx is not None:
@@ -567,7 +625,7 @@ def decode_file(path, model, device=0, gpus=1, host_threads=0, devices=None, pac
     with open(path, "rb") as f, _AtomicOutput(out_path) as out:
         for k in range(len(offsets)):
             f.seek(offsets[k])
-            (n,) = struct.unpack("<I", f.read(4))
+            n, _ = _split_n(struct.unpack("<I", f.read(4))[0])
             out.write(files[k % gpus].read(n))
     for fobj, part in zip(files, parts):
         fobj.close()
@@ -590,6 +648,8 @@ def main(argv=None):
     ap.add_argument("-d", "--device", type=int, default=0)
     ap.add_argument("--gpus", type=int, default=1, help="block b -> GPU b mod G, one worker process per GPU (needs -b / an indexed archive)")
     ap.add_argument("--force", action="store_true", help="write archives of blocks containing byte 0xFF (undecodable in the reference format)")
+    ap.add_argument("--any-byte", action="store_true", help="encode any file so that it decodes: blocks with byte 0xFF get a flagged record with four "
+                    "more bytes (extension, DESIGN.md 4.10); files without 0xFF give the same archive as without the option.  Not with --force")
     ap.add_argument("--host-threads", type=int, default=0, help="host coding threads per GPU (default: CPU quota / gpus - 1)")
     ap.add_argument("--devices", default="", help="GPU ids of the workers, comma separated (default: device, device+1, ...)")
     ap.add_argument("--stats", action="store_true", help="print a JSON line with the wall time of the work and the peak RSS to stderr")
@@ -608,7 +668,7 @@ def main(argv=None):
         out = decode_file(args.file, args.model, args.device, args.gpus, args.host_threads, args.devices, args.packed)
     else:
         out = encode_file(args.file, args.model, args.block_size, args.device, args.gpus, args.force, args.host_threads, args.devices,
-                          args.packed)
+                          args.packed, args.any_byte)
     print(out)
     if args.stats:  # wall time of the work itself (interpreter start and imports of this front end excluded) and this process's peak RSS
         import json

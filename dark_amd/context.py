@@ -46,6 +46,16 @@ def model_id(m):
     return int(getattr(m, "MODEL_ID", m))
 
 
+def _prefix(mid):
+    """bytes the any-byte flag puts in front of a coded stream"""
+    return 4 if mid & _lib.DK_MODEL_ANYBYTE else 0
+
+
+def _stream_cap(mid, n):
+    """output bound of one coded block: 10-byte records for rawdc, else 2 n + 4096, plus the any-byte prefix"""
+    return (10 if mid == _lib.MODEL_IDS["rawdc"] else 2) * int(n) + 4096 + _prefix(mid)
+
+
 class Context:
     def __init__(self, max_n, device=0):
         self._lib = _lib.load()
@@ -146,7 +156,7 @@ class Context:
         t = as_u8(data)
         n = len(t)
         mid = model_id(model)
-        cap = 10 * (n + 600) if mid == _lib.MODEL_IDS["rawdc"] else 2 * n + 4096
+        cap = 10 * (n + 600) if mid == _lib.MODEL_IDS["rawdc"] else _stream_cap(mid, n)
         out = np.empty(cap, dtype=np.uint8)
         ln = C.c_size_t(0)
         self._ck(self._lib.dk_block_encode(self._h, mid, _ptr(t), n, _ptr(out), cap, C.byref(ln)))
@@ -257,7 +267,7 @@ class Context:
         count = len(sizes)
         mid = model_id(model)
         if outs is None:  # (rawdc: one 10-byte record per distance)
-            outs = [np.empty((10 if mid == _lib.MODEL_IDS["rawdc"] else 2) * int(n) + 4096, dtype=np.uint8) for n in sizes]
+            outs = [np.empty(_stream_cap(mid, n), dtype=np.uint8) for n in sizes]
         ns = (C.c_size_t * count)(*[int(n) for n in sizes])
         optrs = (C.c_void_p * count)(*[_ptr(o) for o in outs])
         caps = (C.c_size_t * count)(*[len(o) for o in outs])
@@ -291,7 +301,7 @@ class Context:
         _inputs_ready(d_in)
         mid = model_id(model)
         if out is None:
-            out = np.empty(2 * n + 4096, dtype=np.uint8)
+            out = np.empty(2 * n + 4096 + _prefix(mid), dtype=np.uint8)
         ln = C.c_size_t(0)
         self._ck(self._lib.dk_dev_block_encode(self._h, mid, _ptr(d_in), n, _ptr(out), len(out), C.byref(ln)))
         return out[:ln.value]
@@ -300,14 +310,15 @@ class Context:
         """d_blocks: device tensors / addresses; returns a list of coded streams (views of `outs` when given)"""
         _inputs_ready(*d_blocks[:1])
         count = len(d_blocks)
+        mid = model_id(model)
         if outs is None:
-            outs = [np.empty(2 * int(n) + 4096, dtype=np.uint8) for n in sizes]
+            outs = [np.empty(2 * int(n) + 4096 + _prefix(mid), dtype=np.uint8) for n in sizes]
         ptrs = (C.c_void_p * count)(*[_ptr(b) for b in d_blocks])
         ns = (C.c_size_t * count)(*[int(n) for n in sizes])
         optrs = (C.c_void_p * count)(*[_ptr(o) for o in outs])
         caps = (C.c_size_t * count)(*[len(o) for o in outs])
         lens = (C.c_size_t * count)()
-        self._ck(self._lib.dk_dev_batch_encode(self._h, model_id(model), count, ptrs, ns, optrs, caps, lens, int(host_threads)))
+        self._ck(self._lib.dk_dev_batch_encode(self._h, mid, count, ptrs, ns, optrs, caps, lens, int(host_threads)))
         return [o[:lens[i]] for i, o in enumerate(outs)]
 
     def batch_begin(self, model, host_threads=8):
@@ -401,7 +412,7 @@ class Batch:
         if not self._h:
             raise DarkError(_lib.DK_E_ARG, "the batch is closed")
         _inputs_ready(d_in)
-        out = np.empty(2 * int(n) + 4096, dtype=np.uint8)  # virtual until written: only the coded bytes become resident
+        out = np.empty(2 * int(n) + 4096 + _prefix(self._model), dtype=np.uint8)  # virtual until written: only the coded bytes become resident
         ln = C.c_size_t(0)
         self._outs.append(out)
         self._lens.append(ln)
@@ -418,7 +429,7 @@ class Batch:
             raise DarkError(_lib.DK_E_ARG, "the batch is closed")
         _inputs_ready(d_in)
         count = len(sizes)
-        outs = [np.empty((10 if self._model == _lib.MODEL_IDS["rawdc"] else 2) * int(n) + 4096, dtype=np.uint8) for n in sizes]
+        outs = [np.empty(_stream_cap(self._model, n), dtype=np.uint8) for n in sizes]
         lens = (C.c_size_t * max(count, 1))()
         ns = (C.c_size_t * count)(*[int(n) for n in sizes])
         optrs = (C.c_void_p * count)(*[_ptr(o) for o in outs])
@@ -455,7 +466,8 @@ def multi_block_encode(model, blocks, devices, host_threads_per_gpu=4):
     lib = _lib.load()
     keep = [as_u8(b) for b in blocks]
     count = len(keep)
-    outs = [np.empty(2 * len(b) + 4096, dtype=np.uint8) for b in keep]
+    mid = model_id(model)
+    outs = [np.empty(2 * len(b) + 4096 + _prefix(mid), dtype=np.uint8) for b in keep]
     devs = (C.c_int * len(devices))(*[int(d) for d in devices])
     ins = (C.c_void_p * count)(*[_ptr(b) for b in keep])
     ns = (C.c_size_t * count)(*[len(b) for b in keep])
@@ -463,7 +475,7 @@ def multi_block_encode(model, blocks, devices, host_threads_per_gpu=4):
     caps = (C.c_size_t * count)(*[len(o) for o in outs])
     lens = (C.c_size_t * count)()
     err = C.create_string_buffer(512)
-    rc = lib.dk_multi_block_encode(devs, len(devices), model_id(model), count, ins, ns, optrs, caps, lens, int(host_threads_per_gpu), err, 512)
+    rc = lib.dk_multi_block_encode(devs, len(devices), mid, count, ins, ns, optrs, caps, lens, int(host_threads_per_gpu), err, 512)
     if rc:
         raise DarkError(rc, err.value.decode())
     return [o[:lens[i]].tobytes() for i, o in enumerate(outs)]

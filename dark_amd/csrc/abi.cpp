@@ -182,7 +182,7 @@ int block_encode_common(dk_ctx *ctx, int model_id, const uint8_t *d_text, size_t
         return ctx->fail(DK_E_MODEL, "model %d cannot code blocks of %zu bytes without losing bits (limit %llu)", model_id, n,
                          static_cast<unsigned long long>(model_max_block(model_id)));
     ForwardResult fr;
-    DK_TRY(forward_to_stream(ctx, d_text, n, model_id == DK_MODEL_RAWDC, &fr, -1, true));
+    DK_TRY(forward_to_stream(ctx, d_text, n, dk::model_base(model_id) == DK_MODEL_RAWDC, &fr, -1, true));
     ctx->last_flags = block_flags(fr.init, n);
     Timer t;
     DcStream s;
@@ -209,7 +209,7 @@ int block_encode_common(dk_ctx *ctx, int model_id, const uint8_t *d_text, size_t
 }
 
 int block_decode_common(dk_ctx *ctx, int model_id, const uint8_t *in, size_t in_len, size_t n, uint8_t *d_out) {
-    if (model_id == DK_MODEL_RAWDC || model_max_block(model_id) == 0) return ctx->fail(DK_E_MODEL, "model %d cannot decode", model_id);
+    if (dk::model_base(model_id) == DK_MODEL_RAWDC || model_max_block(model_id) == 0) return ctx->fail(DK_E_MODEL, "model %d cannot decode", model_id);
     hipStream_t st = ctx->stream;
     DK_TRY(ctx->ensure_stage(n + 64));
     uint8_t *h_bwt = reinterpret_cast<uint8_t *>(ctx->h_stage);
@@ -219,7 +219,7 @@ int block_decode_common(dk_ctx *ctx, int model_id, const uint8_t *in, size_t in_
     int rc = decode_block_stream(model_id, in, in_len, n, h_bwt, &origin, &single, &ctx->last_consumed);
     ctx->stats.ms_entropy = t.ms();
     if (rc) return ctx->fail(rc, "stream does not decode (corrupt, truncated, wrong model/size, or a block containing byte 0xFF, "
-                                 "which the reference format cannot represent: src/block/dc.rs:57-73)");
+                                 "which the reference format cannot represent without DK_MODEL_ANYBYTE: src/block/dc.rs:57-73)");
     Timer t2;
     uint8_t *d_bwt = ctx->ws_alloc<uint8_t>(n);
     if (!d_bwt) return DK_E_NOMEM;
@@ -470,7 +470,7 @@ int dk_batch_push(dk_batch *b, const uint8_t *d_in, size_t n, uint8_t *out, size
     job.slot = slot;
     job.n = n; job.out = out; job.cap = out_cap; job.out_len = out_len;
     ctx->ws_reset();
-    const int rc = forward_to_stream(ctx, d_in, n, b->model_id == DK_MODEL_RAWDC, &job.fr, slot);
+    const int rc = forward_to_stream(ctx, d_in, n, dk::model_base(b->model_id) == DK_MODEL_RAWDC, &job.fr, slot);
     if (ctx->profiling) ctx->prof_collect();
     if (rc != DK_OK) {
         std::lock_guard<std::mutex> lk(b->mu);
@@ -658,7 +658,7 @@ int push_packed_body(dk_batch *b, int slot, const uint8_t *d_in, const std::vect
     dk_ctx *ctx = b->ctx;
     hipStream_t st = ctx->stream;
     const size_t count = off.size() - 1, total = off.back();
-    const bool want = b->model_id == DK_MODEL_RAWDC;
+    const bool want = dk::model_base(b->model_id) == DK_MODEL_RAWDC;
     // read-back block: origin | m | flags | rb (count + 1) | init (count x 256)
     const size_t words = 4 * count + 1 + 256 * count;
     uint32_t *d_off = ctx->ws_alloc<uint32_t>(count + 1), *d_res = ctx->ws_alloc<uint32_t>(words);
@@ -800,7 +800,7 @@ int dk_dev_batch_decode(dk_ctx *ctx, int model_id, size_t count, const uint8_t *
     DK_TRY(begin_call(ctx));
     ScopedCall sc(ctx);
     if (!in || !in_len || !n || !d_out || count == 0) return ctx->fail(DK_E_ARG, "null pointer or empty batch");
-    if (model_id == DK_MODEL_RAWDC || model_max_block(model_id) == 0) return ctx->fail(DK_E_MODEL, "model %d cannot decode", model_id);
+    if (dk::model_base(model_id) == DK_MODEL_RAWDC || model_max_block(model_id) == 0) return ctx->fail(DK_E_MODEL, "model %d cannot decode", model_id);
     size_t max_n = 0;
     for (size_t i = 0; i < count; ++i) {
         if (!in[i] || !d_out[i]) return ctx->fail(DK_E_ARG, "null pointer in block %zu", i);
@@ -909,7 +909,7 @@ int dk_dev_packed_decode(dk_ctx *ctx, int model_id, size_t count, const uint8_t 
     DK_TRY(begin_call(ctx));
     ScopedCall sc(ctx);
     if (!in || !in_len || !n || !d_out) return ctx->fail(DK_E_ARG, "null pointer");
-    if (model_id == DK_MODEL_RAWDC || model_max_block(model_id) == 0) return ctx->fail(DK_E_MODEL, "model %d cannot decode", model_id);
+    if (dk::model_base(model_id) == DK_MODEL_RAWDC || model_max_block(model_id) == 0) return ctx->fail(DK_E_MODEL, "model %d cannot decode", model_id);
     std::vector<uint32_t> off;
     DK_TRY(check_pack(ctx, count, n, off));
     for (size_t i = 0; i < count; ++i)

@@ -363,6 +363,10 @@ bool SimpleModel::decode(uint8_t, Decoder &d, uint32_t &dist) {  // simple.rs:66
 }
 
 uint64_t model_max_block(int model_id) {
+    if (model_any_byte(model_id)) {  // the any-byte flag belongs to the four coding models only (no header to extend in rawdc's records)
+        const int base = model_base(model_id);
+        return base >= DK_MODEL_DARK && base <= DK_MODEL_SIMPLE ? model_max_block(base) : 0;
+    }
     switch (model_id) {
     case DK_MODEL_DARK: return 0x7FFFFFFEull;         // dist + 1 must have < 32 significant bits
     case DK_MODEL_EXP: return 1ull << 24;             // 24 coded bits (exp.rs:67)
@@ -416,7 +420,8 @@ int write_stream(M &model, const DcStream &s, E &e) {
     auto fail = [&] { return e.error() ? e.error() : DK_E_MODEL; };  // the sink's own error (capacity) wins over "the model refused"
     // Init-table RLE: alternating present / absent run lengths over symbols 0..254; every present symbol is followed
     // by its first position.  The first present-run length is raw, all later lengths are len-1.  Symbol 0xFF is
-    // never visited (all loops stop at 0xFF): blocks containing byte 0xFF encode, but cannot be decoded.
+    // never visited (all loops stop at 0xFF): blocks containing byte 0xFF encode, but cannot be decoded -- unless init[0xFF] travels in
+    // front of this stream (DK_MODEL_ANYBYTE, encode_block_stream below).
     bool active = true;
     size_t i = 0;
     while (i < 0xFF) {
@@ -518,7 +523,7 @@ int dc_rebuild(uint32_t const init[256], uint8_t *out, size_t n, F &&next_dist, 
         }
     }
     if (single) *single = alpha <= 1;
-    if (alpha == 0) return DK_E_STREAM;  // no symbol at all: a block of nothing but 0xFF bytes, which the header cannot carry
+    if (alpha == 0) return DK_E_STREAM;  // no symbol at all: a block of nothing but 0xFF bytes, which the header cannot carry without DK_MODEL_ANYBYTE
     if (alpha == 1) {  // "redundant alphabet": filled without reading any distance
         std::memset(out, order[0], n);
         return DK_OK;
@@ -555,7 +560,7 @@ int dc_rebuild(uint32_t const init[256], uint8_t *out, size_t n, F &&next_dist, 
 
 // src/block/dc.rs:121-151
 template <class M>
-int read_stream(M &model, Decoder &d, size_t n, uint8_t *bwt_out, uint32_t *origin, int *single) {
+int read_stream(M &model, Decoder &d, size_t n, uint8_t *bwt_out, uint32_t *origin, int *single, const uint32_t *first_ff = nullptr) {
     uint32_t init[256];
     for (auto &v : init) v = static_cast<uint32_t>(n);
     bool active = true;
@@ -573,6 +578,7 @@ int read_stream(M &model, Decoder &d, size_t n, uint8_t *bwt_out, uint32_t *orig
         active = !active;
         i += num;
     }
+    if (first_ff) init[255] = *first_ff;  // DK_MODEL_ANYBYTE: the one entry the header never carries comes from the prefix
     int rc = dc_rebuild(init, bwt_out, n, [&](uint8_t sym, uint32_t *out) {
         return model.decode(sym, d, *out) ? DK_OK : DK_E_STREAM;
     }, single);
@@ -1693,6 +1699,17 @@ int host_l3_groups(int min_cores) {
 
 int encode_block_stream(int model_id, const DcStream &s, uint8_t *out, size_t cap, size_t *out_len, int host_threads) {
     if (!s.init || (!s.dist && s.m) || (!s.sym && s.m) || !out || !out_len) return DK_E_ARG;
+    if (model_any_byte(model_id)) {
+        // [u32 LE first position of 0xFF, n = absent][the stream of the base model, unchanged]
+        if (model_max_block(model_id) == 0) return DK_E_MODEL;
+        if (cap < 4) { *out_len = 0; return DK_E_CAPACITY; }
+        const uint32_t first_ff = s.init[255] < s.n ? s.init[255] : static_cast<uint32_t>(s.n);
+        for (int i = 0; i < 4; ++i) out[i] = static_cast<uint8_t>(first_ff >> (8 * i));
+        size_t body = 0;
+        const int rc = encode_block_stream(model_base(model_id), s, out + 4, cap - 4, &body, host_threads);
+        *out_len = body + 4;
+        return rc;
+    }
     if (model_id == DK_MODEL_RAWDC) return write_records(s, out, cap, out_len);
     if (s.n > model_max_block(model_id)) return DK_E_MODEL;
     return with_model(model_id, [&](auto &model) {
@@ -1727,11 +1744,22 @@ int encode_block_stream(int model_id, const DcStream &s, uint8_t *out, size_t ca
 int decode_block_stream(int model_id, const uint8_t *in, size_t in_len, size_t n, uint8_t *bwt_out,
                         uint32_t *origin, int *single, size_t *consumed) {
     if (!in || !bwt_out || !origin || n == 0) return DK_E_ARG;
-    return with_model(model_id, [&](auto &model) {
+    const bool any_byte = model_any_byte(model_id);
+    uint32_t first_ff = 0;
+    if (any_byte) {
+        if (model_max_block(model_id) == 0) return DK_E_MODEL;
+        if (consumed) *consumed = 0;
+        if (in_len < 4) return DK_E_STREAM;
+        for (int i = 0; i < 4; ++i) first_ff |= static_cast<uint32_t>(in[i]) << (8 * i);
+        if (first_ff > n) return DK_E_STREAM;  // == n: the block holds no 0xFF
+        in += 4;
+        in_len -= 4;
+    }
+    return with_model(model_base(model_id), [&](auto &model) {
         model.reset();  // src/block/dc.rs:108
         Decoder d(in, in_len);
-        int rc = read_stream(model, d, n, bwt_out, origin, single);
-        if (consumed) *consumed = d.consumed();
+        int rc = read_stream(model, d, n, bwt_out, origin, single, any_byte ? &first_ff : nullptr);
+        if (consumed) *consumed = d.consumed() + (any_byte ? 4 : 0);
         return rc;
     });
 }

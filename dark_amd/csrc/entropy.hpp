@@ -520,7 +520,10 @@ int bitcoder_decode(const uint8_t *in, size_t in_len, const uint16_t *flat, size
 // block::raw with the bbb model (src/block/raw.rs, src/model/bbb.rs; bbb.cpp -- gates restated after etc/bbb/main.cpp, PARITY UNPINNED)
 int raw_bbb_encode_stream(const uint8_t *bwt, size_t n, uint32_t origin, uint8_t *out, size_t cap, size_t *out_len);
 int raw_bbb_decode_stream(const uint8_t *in, size_t in_len, size_t n, uint8_t *bwt, uint32_t *origin, size_t *consumed = nullptr);
-// largest n a model can code without losing bits (0 = unknown model)
+// DK_MODEL_ANYBYTE: a coding model's id with the flag that puts init[255] in front of the stream
+inline bool model_any_byte(int model_id) { return (model_id & DK_MODEL_ANYBYTE) != 0; }
+inline int model_base(int model_id) { return model_id & ~DK_MODEL_ANYBYTE; }
+// largest n a model can code without losing bits (0 = unknown model, the any-byte flag on anything but a coding model included)
 uint64_t model_max_block(int model_id);
 
 }  // namespace dk

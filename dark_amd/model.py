@@ -8,6 +8,7 @@ from . import _lib
 from .context import DarkError, _ptr, as_u8, model_id
 
 NAMES = ("dark", "exp", "ybs", "simple", "rawdc")
+ANY_BYTE_NAMES = ("dark+ff", "exp+ff", "ybs+ff", "simple+ff")  # DK_MODEL_ANYBYTE: the stream also carries init[255], so every block decodes
 
 
 def encode(model, dist, sym):
@@ -44,7 +45,7 @@ def stream_encode(model, n, init, dist, sym, origin, rank=None, run_end=None):
     r = np.ascontiguousarray(rank, dtype=np.uint8) if rank is not None else None
     e = np.ascontiguousarray(run_end, dtype=np.uint32) if run_end is not None else None
     mid = model_id(model)
-    cap = 10 * (len(d) + 600) if mid == 4 else 8 * len(d) + 8192
+    cap = 10 * (len(d) + 600) if mid == 4 else 8 * len(d) + 8192 + (4 if mid & _lib.DK_MODEL_ANYBYTE else 0)
     out = np.empty(cap, dtype=np.uint8)
     ln = C.c_size_t(0)
     rc = lib.dk_stream_encode(mid, n, _ptr(init), _ptr(d), _ptr(s), _ptr(r) if r is not None else None,

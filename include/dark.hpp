@@ -97,32 +97,35 @@ template <class M>
 class Encoder {
 public:
     M model;  // public like the reference's field (src/block/dc.rs:25)
-    Encoder(size_t n, M m, int device = 0) : model(m), ctx_(n, device) { model.reset(); }
+    // any_byte (extension, DK_MODEL_ANYBYTE): the stream starts with four more bytes, the first position of byte 0xFF in the BWT, so that
+    // blocks with that byte decode; a Decoder must be given the same option.  The model must be one of the four coding models.
+    Encoder(size_t n, M m, int device = 0, bool any_byte = false) : model(m), ctx_(n, device), id_(M::ID | (any_byte ? DK_MODEL_ANYBYTE : 0)) { model.reset(); }
     // encode(&input, writer) -> (writer, io::Result<()>); the writer here is any byte container with insert()
     template <class W>
     std::pair<W, Result> encode(const std::vector<uint8_t> &input, W writer) {
         if (input.size() > dk_capacity(ctx_.get())) throw Error(DK_E_ARG, "assertion failed: block_size <= self.sac.capacity()");
-        std::vector<uint8_t> out(2 * input.size() + 4096);
+        std::vector<uint8_t> out(2 * input.size() + 4096 + 4);
         size_t len = 0;
-        int rc = dk_block_encode(ctx_.get(), M::ID, input.data(), input.size(), out.data(), out.size(), &len);
+        int rc = dk_block_encode(ctx_.get(), id_, input.data(), input.size(), out.data(), out.size(), &len);
         if (rc != DK_OK) return {std::move(writer), Result{false, ctx_.error()}};
         writer.insert(writer.end(), out.begin(), out.begin() + static_cast<std::ptrdiff_t>(len));
         return {std::move(writer), Result{}};
     }
 private:
     detail::Ctx ctx_;
+    int id_;
 };
 
 template <class M>
 class Decoder {
 public:
     M model;
-    Decoder(size_t n, M m, int device = 0) : model(m), ctx_(n, device), n_(n) { model.reset(); }
+    Decoder(size_t n, M m, int device = 0, bool any_byte = false) : model(m), ctx_(n, device), n_(n), id_(M::ID | (any_byte ? DK_MODEL_ANYBYTE : 0)) { model.reset(); }
     // decode(reader, writer) -> (reader, writer, io::Result<()>)
     template <class W>
     std::tuple<std::vector<uint8_t>, W, Result> decode(std::vector<uint8_t> reader, W writer) {
         std::vector<uint8_t> out(n_);
-        int rc = dk_block_decode(ctx_.get(), M::ID, reader.data(), reader.size(), n_, out.data());
+        int rc = dk_block_decode(ctx_.get(), id_, reader.data(), reader.size(), n_, out.data());
         if (rc != DK_OK) return {std::move(reader), std::move(writer), Result{false, ctx_.error()}};
         writer.insert(writer.end(), out.begin(), out.end());
         return {std::move(reader), std::move(writer), Result{}};
@@ -130,6 +133,7 @@ public:
 private:
     detail::Ctx ctx_;
     size_t n_;
+    int id_;
 };
 }  // namespace dc
 

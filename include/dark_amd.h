@@ -42,6 +42,14 @@ extern "C" {
 #define DK_MODEL_YBS 2    /* src/model/ybs.rs    (distances < 2^29) */
 #define DK_MODEL_SIMPLE 3 /* src/model/simple.rs (distances < 2^24 + 255) */
 #define DK_MODEL_RAWDC 4  /* src/model/raw.rs:12-44 DcOut: 10-byte records instead of a coded stream */
+/* Any-byte extension (nothing in the reference corresponds), OR-ed into one of the four coding models above: the stream becomes
+ * [u32 LE first_ff][the reference stream, unchanged], first_ff = init[255] = the first position of byte 0xFF in the BWT, or n when the block
+ * holds none.  Those four bytes are all the reference's init-table header leaves out (src/block/dc.rs:57,60,73,127), so with the flag EVERY
+ * block decodes, a block of nothing but 0xFF included.  The prefix is always there under the flag; out_len, out_cap, dk_last_consumed and the
+ * `consumed` of dk_stream_decode count it.  Decoding: in_len < 4 or first_ff > n is DK_E_STREAM.  Every entry point that takes a model_id takes
+ * the flag, except dk_model_encode / dk_model_decode (no header there); with those, with DK_MODEL_RAWDC or with an unknown base id: DK_E_MODEL.
+ * Without the flag nothing changes.  The DK_RAWMODEL_* ids are a different id space and carry 0xFF already. */
+#define DK_MODEL_ANYBYTE 0x100
 
 typedef struct dk_ctx dk_ctx;
 
@@ -102,7 +110,8 @@ size_t dk_last_consumed(const dk_ctx *ctx);
 /* Properties of the block the last dk_block_encode / dk_dev_block_encode on this context coded (0 after any other call):
  *   DK_FLAG_HAS_FF         the block contains byte 0xFF.  The stream is bit-exact with the reference's, and like the reference's it
  *                          cannot be decoded: the init-table header never transmits symbol 0xFF (src/block/dc.rs:57,60,73,127).
- *                          A front end should refuse or warn (dark_amd/cli.py does) instead of writing an archive that is lost.
+ *                          A front end should refuse or warn (dark_amd/cli.py does) instead of writing an archive that is lost,
+ *                          or code the block with DK_MODEL_ANYBYTE (the flag is reported with it too).
  *   DK_FLAG_SINGLE_SYMBOL  one distinct symbol: the reference's decoder mis-reads `origin` for such a block;
  *                          this library's decoder returns all n bytes. */
 #define DK_FLAG_HAS_FF 1u

@@ -367,6 +367,59 @@ class Context:
         self._ck(self._lib.dk_dbg_sort_pairs(self._h, _ptr(keys), _ptr(vals), len(keys), begin_bit, end_bit))
         return keys, vals
 
+    # ---- the sort layer's device entry points (csrc/radix_sort.hip), numpy in and out; torch only holds the device buffers ----
+    def _to_dev(self, a, dtype):
+        import torch
+        a = np.ascontiguousarray(a, dtype=dtype)
+        signed = {4: np.int32, 8: np.int64}[a.dtype.itemsize]  # (torch has no arithmetic on unsigned words, and needs none here)
+        return torch.from_numpy(a.view(signed).copy()).to("cuda:%d" % self.device)
+
+    @staticmethod
+    def _to_host(t, dtype):
+        return t.cpu().numpy().view(dtype)
+
+    def dbg_dev_sort_pairs(self, keys, vals, begin_bit=0, end_bit=64):
+        """dk_dbg_dev_sort_pairs: the stable sort on bits [begin_bit, end_bit) of device arrays, in place -> (keys, vals)"""
+        return self._dev_sort(self._lib.dk_dbg_dev_sort_pairs, keys, vals, begin_bit, end_bit)
+
+    def dbg_dev_local_sort(self, keys, vals, begin_bit=0, end_bit=64):
+        """dk_dbg_dev_local_sort: every 8192-pair tile sorted by itself -> (keys, vals)"""
+        return self._dev_sort(self._lib.dk_dbg_dev_local_sort, keys, vals, begin_bit, end_bit)
+
+    def _dev_sort(self, fn, keys, vals, begin_bit, end_bit):
+        if len(keys) != len(vals):
+            raise DarkError(_lib.DK_E_ARG, "%d keys, %d values" % (len(keys), len(vals)))
+        d_k, d_v = self._to_dev(keys, np.uint64), self._to_dev(vals, np.uint32)
+        _inputs_ready(d_k)
+        self._ck(fn(self._h, _ptr(d_k), _ptr(d_v), len(keys), int(begin_bit), int(end_bit)))
+        return self._to_host(d_k, np.uint64), self._to_host(d_v, np.uint32)
+
+    def dbg_dev_sort_groups(self, kin, vin, starts, above, begin_bit, end_bit, kout=None, vout=None):
+        """dk_dbg_dev_sort_groups: group g = the pairs [starts[g], starts[g + 1]).  kout / vout: what the output arrays hold before the call
+        (both or neither); without them the sort is in place.  -> (kout, vout) after the call"""
+        if (kout is None) != (vout is None):
+            raise DarkError(_lib.DK_E_ARG, "kout and vout: both or neither")
+        starts = np.ascontiguousarray(starts, dtype=np.uint32)
+        d_ki, d_vi = self._to_dev(kin, np.uint64), self._to_dev(vin, np.uint32)
+        d_ko, d_vo = (d_ki, d_vi) if kout is None else (self._to_dev(kout, np.uint64), self._to_dev(vout, np.uint32))
+        if not (len(d_ki) == len(d_vi) == len(d_ko) == len(d_vo)):
+            raise DarkError(_lib.DK_E_ARG, "arrays of different lengths")
+        _inputs_ready(d_ki)
+        self._ck(self._lib.dk_dbg_dev_sort_groups(self._h, _ptr(d_ki), _ptr(d_vi), _ptr(d_ko), _ptr(d_vo), _ptr(starts), len(starts) - 1, len(d_ki),
+                                                  int(above), int(begin_bit), int(end_bit)))
+        return self._to_host(d_ko, np.uint64), self._to_host(d_vo, np.uint32)
+
+    def dbg_dev_inverse_permutation(self, sa, marked_val=None):
+        """dk_dbg_dev_inverse_permutation: rank[sa[p] & 0x7FFFFFFF] = marked_val[p] if sa[p] has bit 31 set (and marked_val is given) else p"""
+        d_sa = self._to_dev(sa, np.uint32)
+        d_mv = None if marked_val is None else self._to_dev(marked_val, np.uint32)
+        if d_mv is not None and len(d_mv) != len(d_sa):
+            raise DarkError(_lib.DK_E_ARG, "%d entries, %d values for the marked ones" % (len(d_sa), len(d_mv)))
+        d_rank = self._to_dev(np.full(len(d_sa), 0xFFFFFFFF, np.uint32), np.uint32)
+        _inputs_ready(d_sa)
+        self._ck(self._lib.dk_dbg_dev_inverse_permutation(self._h, _ptr(d_sa), len(d_sa), _ptr(d_rank), _ptr(d_mv) if d_mv is not None else None))
+        return self._to_host(d_rank, np.uint32)
+
 
 class _LenRef:
     """one entry of a packed push's length array, read like a c_size_t"""

@@ -1368,6 +1368,33 @@ int dk_dbg_dev_sort_pairs(dk_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, size_
     DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return DK_OK;
 }
+int dk_dbg_dev_sort_groups(dk_ctx *ctx, const uint64_t *d_kin, const uint32_t *d_vin, uint64_t *d_kout, uint32_t *d_vout, const uint32_t *starts,
+                           size_t ngroups, size_t npairs, uint32_t above, int begin_bit, int end_bit) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!d_kin || !d_vin || !d_kout || !d_vout || !starts || ngroups == 0 || npairs == 0) return ctx->fail(DK_E_ARG, "null pointer or empty input");
+    if (npairs > 0xFFFFFFFFull || begin_bit < 0 || end_bit > 64 || begin_bit > end_bit) return ctx->fail(DK_E_ARG, "sort_groups: %zu pairs, bits [%d, %d)", npairs, begin_bit, end_bit);
+    for (size_t g = 0; g < ngroups; ++g)
+        if (starts[g] > starts[g + 1]) return ctx->fail(DK_E_ARG, "sort_groups: starts[%zu] = %u > starts[%zu] = %u", g, starts[g], g + 1, starts[g + 1]);
+    if (starts[ngroups] > npairs) return ctx->fail(DK_E_ARG, "sort_groups: the last group ends at %u of %zu pairs", starts[ngroups], npairs);
+    uint32_t *d_starts = ctx->ws_alloc<uint32_t>(ngroups + 1);
+    if (!d_starts) return DK_E_NOMEM;
+    DK_HIP(ctx, hipMemcpyAsync(d_starts, starts, (ngroups + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    DK_TRY(sort_groups(ctx, d_kin, d_vin, d_kout, d_vout, d_starts, ngroups, npairs, above, begin_bit, end_bit));
+    DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return DK_OK;
+}
+int dk_dbg_dev_inverse_permutation(dk_ctx *ctx, const uint32_t *d_sa, size_t n, uint32_t *d_rank, const uint32_t *d_marked_val) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!d_sa || !d_rank || n == 0) return ctx->fail(DK_E_ARG, "null pointer or empty input");
+    if (n > (size_t(1) << 31)) return ctx->fail(DK_E_ARG, "inverse_permutation: %zu entries (bit 31 of an entry is its mark)", n);
+    uint64_t *a = ctx->ws_alloc<uint64_t>(n), *b = a ? ctx->ws_alloc<uint64_t>(n) : nullptr;
+    if (!a || !b) return DK_E_NOMEM;
+    DK_TRY(inverse_permutation(ctx, d_sa, n, a, b, d_rank, d_marked_val));
+    DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return DK_OK;
+}
 int dk_dbg_sort_pairs(dk_ctx *ctx, uint64_t *keys, uint32_t *vals, size_t count, int begin_bit, int end_bit) {
     DK_TRY(begin_call(ctx));
     ScopedCall sc(ctx);

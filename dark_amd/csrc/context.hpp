@@ -187,6 +187,8 @@ struct SortFinalOut {
     uint32_t *vals = nullptr; uint8_t *bwt = nullptr; const uint8_t *inv_code = nullptr; uint32_t *origin = nullptr;
     int narrow_shift = -1; uint32_t *bucket_starts = nullptr;
 };
+// sort_pairs / sort_groups / local_sort_tiles: stable, on EXACTLY the key bits [begin_bit, end_bit) -- eight per pass, and a last pass of fewer when the
+// width is no multiple of eight (its digit is masked to the bits below end_bit).  Bits outside the range travel with the pair and have no say.
 // final_out (may be null; only with the sort of more than 8192 pairs): see SortFinalOut; then `vals` / `vals_alt` are both free on return
 int sort_pairs(dk_ctx *ctx, uint64_t *&keys, uint64_t *&keys_alt, uint32_t *&vals, uint32_t *&vals_alt, size_t count,
                int begin_bit, int end_bit, const TextKeys *text = nullptr, const SortFinalOut *final_out = nullptr);

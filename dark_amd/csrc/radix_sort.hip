@@ -41,7 +41,9 @@ constexpr int RS_TILE = RS_BLOCK * RS_KPT;   // 4096 pairs per workgroup
 
 constexpr int RS_TEXT_AHEAD = 64 + 16;       // TextKeys: codes staged beyond the tile (spk <= 64)
 
-__device__ __forceinline__ uint32_t digit_of(uint64_t k, int shift) { return static_cast<uint32_t>(k >> shift) & 0xFFu; }
+// The digit of a pass: eight bits from `shift` on, cut to `mask`.  mask is 0xFF in every pass but a last one that has fewer than eight bits left
+// below end_bit (digit_mask below, computed on the host, wave-uniform): the sort orders by the bits [begin_bit, end_bit) and by nothing above them.
+__device__ __forceinline__ uint32_t digit_of(uint64_t k, int shift, uint32_t mask) { return static_cast<uint32_t>(k >> shift) & mask; }
 
 // PAIRS = true: the key of element i is (hi[i] << 32) | lo[i], read from two u32 arrays, and there is no value array
 template <bool PAIRS>
@@ -182,7 +184,7 @@ __device__ __forceinline__ uint32_t hist_copies_sum(const uint32_t *h, int d) {
 
 template <int SRC>
 __global__ __launch_bounds__(RS_BLOCK) void k_radix_hist(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ hi,
-                                                          const uint32_t *__restrict__ lo, const uint8_t *__restrict__ plane, size_t n, int shift,
+                                                          const uint32_t *__restrict__ lo, const uint8_t *__restrict__ plane, size_t n, int shift, uint32_t dmask,
                                                           uint32_t ntiles, uint32_t tiles_per_chunk, uint32_t *__restrict__ tile_pre,
                                                           uint32_t *__restrict__ chunk_sum, uint32_t *__restrict__ digit_total, TextKeys tk) {
     static_assert(RS_BLOCK == 256, "one thread per digit");
@@ -227,7 +229,7 @@ __global__ __launch_bounds__(RS_BLOCK) void k_radix_hist(const uint64_t *__restr
             text_stage(tk, base, raw, s_code, s_c);
             const int p0 = tid * RS_KPT, bits = tk.bits, spk = tk.spk;
             const int last = (8 + bits - 1) / bits < spk ? (8 + bits - 1) / bits : spk;  // symbols that reach the digit (<= 8)
-            const uint32_t dmask = spk * bits >= 8 ? 0xFFu : (1u << (spk * bits)) - 1u;  // (a window shorter than the digit)
+            const uint32_t wmask = (spk * bits >= 8 ? 0xFFu : (1u << (spk * bits)) - 1u) & dmask;  // (a window shorter than the digit)
             // the 24 codes from position p0 + spk - last on, in three registers (aligned 8-byte LDS reads, a byte at a time would put the
             // 32 lanes of an LDS cycle four deep on eight banks): `last` codes prime the window, one enters per position
             const int off = p0 + spk - last;
@@ -240,7 +242,7 @@ __global__ __launch_bounds__(RS_BLOCK) void k_radix_hist(const uint64_t *__restr
             for (int j = 0; j < last; ++j) w = (w << bits) | code_at(j);
 #pragma unroll
             for (int g = 0; g < RS_KPT; ++g) {
-                if (base + p0 + g < n) atomicAdd(&mine[(w & dmask) * RS_HCOPIES], 1u);
+                if (base + p0 + g < n) atomicAdd(&mine[(w & wmask) * RS_HCOPIES], 1u);
                 w = (w << bits) | code_at(last + g);
             }
         } else if (SRC == HS_PLANE && plane_aligned && base + RS_TILE <= n) {
@@ -250,7 +252,7 @@ __global__ __launch_bounds__(RS_BLOCK) void k_radix_hist(const uint64_t *__restr
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
 #pragma unroll
-                for (int b = 0; b < 4; ++b) atomicAdd(&mine[((w[k] >> (8 * b)) & 0xFFu) * RS_HCOPIES], 1u);
+                for (int b = 0; b < 4; ++b) atomicAdd(&mine[((w[k] >> (8 * b)) & dmask) * RS_HCOPIES], 1u);
             }
         } else if (SRC == HS_KEYS && base + RS_TILE <= n) {  // full tile: two keys per 16-byte load (order inside the tile is irrelevant here)
             uint4 v[RS_KPT / 2];
@@ -260,15 +262,15 @@ __global__ __launch_bounds__(RS_BLOCK) void k_radix_hist(const uint64_t *__restr
 #pragma unroll
             for (int k = 0; k < RS_KPT / 2; ++k) {
                 const uint64_t k0 = (static_cast<uint64_t>(v[k].y) << 32) | v[k].x, k1 = (static_cast<uint64_t>(v[k].w) << 32) | v[k].z;
-                atomicAdd(&mine[digit_of(k0, shift) * RS_HCOPIES], 1u);
-                atomicAdd(&mine[digit_of(k1, shift) * RS_HCOPIES], 1u);
+                atomicAdd(&mine[digit_of(k0, shift, dmask) * RS_HCOPIES], 1u);
+                atomicAdd(&mine[digit_of(k1, shift, dmask) * RS_HCOPIES], 1u);
             }
         } else {  // pairs, a last partial tile, an unaligned plane
 #pragma unroll
             for (int k = 0; k < RS_KPT; ++k) {
                 const size_t i = base + static_cast<size_t>(k) * RS_BLOCK + tid;
                 if (i < n) {
-                    const uint32_t d = SRC == HS_PLANE ? plane[i] : digit_of(load_key<SRC == HS_PAIRS>(keys, hi, lo, i), shift);
+                    const uint32_t d = SRC == HS_PLANE ? plane[i] & dmask : digit_of(load_key<SRC == HS_PAIRS>(keys, hi, lo, i), shift, dmask);
                     atomicAdd(&mine[d * RS_HCOPIES], 1u);
                 }
             }
@@ -339,7 +341,7 @@ template <bool PAIRS = false, bool TEXT = false, int BLOCK = RS_BLOCK, bool PACK
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(3 * BLOCK / 256, 3 * BLOCK / 256))) void k_radix_scatter(const uint64_t *__restrict__ kin, const uint32_t *__restrict__ vin,
                                                              const uint32_t *__restrict__ pair_lo,
                                                              uint64_t *__restrict__ kout, uint32_t *__restrict__ vout, size_t n,
-                                                             int shift, TileOffsets offs, uint32_t xcd_tiles,
+                                                             int shift, uint32_t dmask, uint32_t next_dmask, TileOffsets offs, uint32_t xcd_tiles,
                                                              TextKeys tk, uint8_t *__restrict__ next_digit, SortFinalOut fin, PackedPairs pk = PackedPairs{}) {
     static_assert(!PACKED || !PAIRS, "packed pairs are single words already");
     constexpr int WAVES = BLOCK / 64, KPT = RS_TILE / BLOCK;
@@ -418,7 +420,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(3 * BLOCK
     uint32_t rnk[KPT];
 #pragma unroll
     for (int k = 0; k < KPT; ++k) {
-        const uint32_t d = digit_of(key[k], shift);
+        const uint32_t d = digit_of(key[k], shift, dmask);
         const LaneSet same = wave_match<8>(d, ~0ull);
         const uint32_t before = same.before();
         const uint32_t old = s_cnt[wave][d];
@@ -462,7 +464,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(3 * BLOCK
     uint32_t pos[KPT];
 #pragma unroll
     for (int k = 0; k < KPT; ++k) {
-        const uint32_t d = digit_of(key[k], shift);
+        const uint32_t d = digit_of(key[k], shift, dmask);
         pos[k] = s_start[d] + s_cnt[wave][d] + rnk[k];
         s_keys[pos[k]] = key[k];
     }
@@ -473,7 +475,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(3 * BLOCK
     for (int k = 0; k < KPT; ++k) {
         const uint32_t p = k * BLOCK + tid;
         const uint64_t kk = s_keys[p];
-        gi[k] = s_gbase[digit_of(kk, shift)] + p;
+        gi[k] = s_gbase[digit_of(kk, shift, dmask)] + p;
         if (PACKED) {
             if (p < valid) {
                 if (fin.vals) {  // the last pass: unpack
@@ -486,14 +488,14 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(3 * BLOCK
                 } else {
                     kout[gi[k]] = kk;
                 }
-                if (next_digit) next_digit[gi[k]] = static_cast<uint8_t>(digit_of(kk, shift + 8));
+                if (next_digit) next_digit[gi[k]] = static_cast<uint8_t>(digit_of(kk, shift + 8, next_dmask));
             }
             continue;
         }
         if (p < valid) {
             if (fin.narrow_shift >= 0) reinterpret_cast<uint32_t *>(kout)[gi[k]] = static_cast<uint32_t>(kk >> fin.narrow_shift);  // SortFinalOut
             else kout[gi[k]] = kk;
-            if (next_digit) next_digit[gi[k]] = static_cast<uint8_t>(digit_of(kk, shift + 8));  // what the next pass's histogram reads
+            if (next_digit) next_digit[gi[k]] = static_cast<uint8_t>(digit_of(kk, shift + 8, next_dmask));  // what the next pass's histogram reads
             if (fin.bwt) fin.bwt[gi[k]] = s_inv[kk & 0xFFu];  // last pass of the suffix sort's initial sort: L rides in the key's low byte
         }
     }
@@ -527,7 +529,7 @@ constexpr int SS_MAX = SS_BLOCK * SS_KPT;  // 8192 pairs
 // (a grid of more than one workgroup: workgroup b sorts the pairs [b * SS_MAX, (b + 1) * SS_MAX) by themselves -- the local pass of an
 // MSD-first sort, measured in round 4: dk_dbg_dev_local_sort)
 __global__ __launch_bounds__(SS_BLOCK) void k_radix_sort_small(uint64_t *__restrict__ keys, uint32_t *__restrict__ vals, uint32_t count,
-                                                               int begin_bit, int end_bit) {
+                                                               int begin_bit, int end_bit, uint32_t last_mask) {
     {
         const size_t base = static_cast<size_t>(blockIdx.x) * SS_MAX;
         keys += base;
@@ -547,16 +549,17 @@ __global__ __launch_bounds__(SS_BLOCK) void k_radix_sort_small(uint64_t *__restr
 #pragma unroll
     for (int k = 0; k < SS_KPT; ++k) {
         const uint32_t li = wbase + k * 64 + lane;
-        key[k] = li < count ? keys[li] : ~0ull;  // padding: sorts last in every pass (all-ones digits), stays behind the real pairs (stable)
+        key[k] = li < count ? keys[li] : ~0ull;  // padding: sorts last in every pass (all-ones digits, the largest under any mask), stays behind the real pairs (stable)
         val[k] = li < count ? vals[li] : 0u;
     }
     for (int shift = begin_bit; shift < end_bit; shift += 8) {
+        const uint32_t dmask = shift + 8 >= end_bit ? last_mask : 0xFFu;
         for (int i = tid; i < SS_WAVES * 256; i += SS_BLOCK) (&s_cnt[0][0])[i] = 0;
         __syncthreads();
         uint32_t rnk[SS_KPT];
 #pragma unroll
         for (int k = 0; k < SS_KPT; ++k) {
-            const uint32_t d = digit_of(key[k], shift);
+            const uint32_t d = digit_of(key[k], shift, dmask);
             const LaneSet same = wave_match<8>(d, ~0ull);
             const uint32_t before = same.before();
             const uint32_t old = s_cnt[wave][d];
@@ -583,7 +586,7 @@ __global__ __launch_bounds__(SS_BLOCK) void k_radix_sort_small(uint64_t *__restr
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < SS_KPT; ++k) {
-            const uint32_t d = digit_of(key[k], shift);
+            const uint32_t d = digit_of(key[k], shift, dmask);
             const uint32_t p = s_start[d] + s_cnt[wave][d] + rnk[k];
             s_keys[p] = key[k];
             s_vals[p] = val[k];
@@ -609,7 +612,7 @@ __global__ __launch_bounds__(SS_BLOCK) void k_radix_sort_small(uint64_t *__restr
 // The medium groups of the L-first path's big list (lfirst.inc): 257 .. 8192 members each, tens of thousands of them per round.
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void k_sort_groups(const uint64_t *kin, const uint32_t *vin, uint64_t *kout, uint32_t *vout,  // (kout may be kin: no __restrict__)
-                                                       const uint32_t *__restrict__ starts, uint32_t lo, uint32_t hi, int begin_bit, int end_bit) {
+                                                       const uint32_t *__restrict__ starts, uint32_t lo, uint32_t hi, int begin_bit, int end_bit, uint32_t last_mask) {
     constexpr int WAVES = BLOCK / 64, KPT = 8, MAXN = BLOCK * KPT;
     const uint32_t start = starts[blockIdx.x], count = starts[blockIdx.x + 1] - start;
     if (count <= lo || count > hi) return;
@@ -632,13 +635,14 @@ __global__ __launch_bounds__(BLOCK) void k_sort_groups(const uint64_t *kin, cons
         val[k] = li < count ? vin[start + li] : 0u;
     }
     for (int shift = begin_bit; shift < end_bit; shift += 8) {
+        const uint32_t dmask = shift + 8 >= end_bit ? last_mask : 0xFFu;
         for (int i = tid; i < WAVES * 256; i += BLOCK) (&s_cnt[0][0])[i] = 0;
         __syncthreads();
         uint32_t rnk[KPT];
 #pragma unroll
         for (int k = 0; k < KPT; ++k) {
             if (k >= kmax) break;
-            const uint32_t d = digit_of(key[k], shift);
+            const uint32_t d = digit_of(key[k], shift, dmask);
             const LaneSet same = wave_match<8>(d, ~0ull);
             const uint32_t before = same.before();
             const uint32_t old = s_cnt[wave][d];
@@ -666,7 +670,7 @@ __global__ __launch_bounds__(BLOCK) void k_sort_groups(const uint64_t *kin, cons
 #pragma unroll
         for (int k = 0; k < KPT; ++k) {
             if (k >= kmax) break;
-            const uint32_t d = digit_of(key[k], shift);
+            const uint32_t d = digit_of(key[k], shift, dmask);
             const uint32_t p = s_start[d] + s_cnt[wave][d] + rnk[k];
             s_keys[p] = key[k];
             s_vals[p] = val[k];
@@ -691,6 +695,12 @@ __global__ __launch_bounds__(BLOCK) void k_sort_groups(const uint64_t *kin, cons
 
 }  // namespace
 
+// the mask of the pass that starts at bit `shift` of a sort on [begin_bit, end_bit): all eight bits, or the end_bit - shift that a last pass has left
+static uint32_t digit_mask(int shift, int end_bit) { return end_bit - shift < 8 ? (1u << (end_bit - shift)) - 1u : 0xFFu; }
+static uint32_t last_digit_mask(int begin_bit, int end_bit) {  // for the kernels that run all their passes themselves (no pass at all: unused)
+    return end_bit > begin_bit ? digit_mask(begin_bit + 8 * ((end_bit - begin_bit - 1) / 8), end_bit) : 0xFFu;
+}
+
 // ngroups independent sorts on key bits [begin_bit, end_bit): group g = the pairs [starts[g], starts[g + 1]) of kin / vin, more than `above` and at
 // most 8192 of them (other sizes are left alone: nothing is written for them); the sorted group goes to the same places of kout / vout (which may be
 // kin / vin themselves).
@@ -698,9 +708,10 @@ int sort_groups(dk_ctx *ctx, const uint64_t *kin, const uint32_t *vin, uint64_t 
                 uint32_t above, int begin_bit, int end_bit) {
     if (ngroups == 0) return DK_OK;
     hipStream_t st = ctx->stream;
+    const uint32_t last_mask = last_digit_mask(begin_bit, end_bit);
     LaunchScope ls(ctx, K_RADIX_SORT_SMALL, 24.0 * npairs);
-    k_sort_groups<256><<<dim3(ngroups), dim3(256), 0, st>>>(kin, vin, kout, vout, starts, above, 2048u, begin_bit, end_bit);
-    k_sort_groups<1024><<<dim3(ngroups), dim3(1024), 0, st>>>(kin, vin, kout, vout, starts, std::max(above, 2048u), 8192u, begin_bit, end_bit);
+    k_sort_groups<256><<<dim3(ngroups), dim3(256), 0, st>>>(kin, vin, kout, vout, starts, above, 2048u, begin_bit, end_bit, last_mask);
+    k_sort_groups<1024><<<dim3(ngroups), dim3(1024), 0, st>>>(kin, vin, kout, vout, starts, std::max(above, 2048u), 8192u, begin_bit, end_bit, last_mask);
     DK_HIP(ctx, hipGetLastError());
     return DK_OK;
 }
@@ -756,6 +767,7 @@ static int sort_pairs_classic(dk_ctx *ctx, uint64_t *&keys, uint64_t *&keys_alt,
         uint8_t *emit = plane && shift + 8 < end_bit ? plane : nullptr;  // read by the next one
         const TextKeys *tk = text && shift == begin_bit ? text : nullptr;
         const bool last = shift + 8 >= end_bit;
+        const uint32_t dmask = digit_mask(shift, end_bit), next_dmask = emit ? digit_mask(shift + 8, end_bit) : 0xFFu;  // (the plane holds masked digits)
         const SortFinalOut fin = last && final_out ? *final_out : SortFinalOut{};
         uint32_t *vout = fin.vals ? fin.vals : vals_alt;
         uint32_t *totals = digit_total + static_cast<size_t>(pass) * 256;
@@ -763,11 +775,11 @@ static int sort_pairs_classic(dk_ctx *ctx, uint64_t *&keys, uint64_t *&keys_alt,
             LaunchScope ls(ctx, tk ? K_RADIX_HIST_TEXT : K_RADIX_HIST, (tk ? 1.0 : have_plane ? 1.0 : 8.0) * count + 1024.0 * ntiles);
             const dim3 grid(cp.nchunks), block(RS_BLOCK);
             if (tk)
-                k_radix_hist<HS_TEXT><<<grid, block, 0, st>>>(nullptr, nullptr, nullptr, nullptr, count, shift, cp.ntiles, cp.tiles_per_chunk, tile_pre, chunk_sum, totals, *tk);
+                k_radix_hist<HS_TEXT><<<grid, block, 0, st>>>(nullptr, nullptr, nullptr, nullptr, count, shift, dmask, cp.ntiles, cp.tiles_per_chunk, tile_pre, chunk_sum, totals, *tk);
             else if (have_plane)
-                k_radix_hist<HS_PLANE><<<grid, block, 0, st>>>(nullptr, nullptr, nullptr, plane, count, shift, cp.ntiles, cp.tiles_per_chunk, tile_pre, chunk_sum, totals, TextKeys{});
+                k_radix_hist<HS_PLANE><<<grid, block, 0, st>>>(nullptr, nullptr, nullptr, plane, count, shift, dmask, cp.ntiles, cp.tiles_per_chunk, tile_pre, chunk_sum, totals, TextKeys{});
             else
-                k_radix_hist<HS_KEYS><<<grid, block, 0, st>>>(keys, nullptr, nullptr, nullptr, count, packed ? pshift : shift, cp.ntiles, cp.tiles_per_chunk, tile_pre, chunk_sum, totals, TextKeys{});
+                k_radix_hist<HS_KEYS><<<grid, block, 0, st>>>(keys, nullptr, nullptr, nullptr, count, packed ? pshift : shift, dmask, cp.ntiles, cp.tiles_per_chunk, tile_pre, chunk_sum, totals, TextKeys{});
         }
         {
             LaunchScope ls(ctx, K_RADIX_SCAN, 2.0 * 1024.0 * cp.nchunks);
@@ -781,19 +793,19 @@ static int sort_pairs_classic(dk_ctx *ctx, uint64_t *&keys, uint64_t *&keys_alt,
             const bool xcd = DK_KNOB("DK_XCD", 1) != 0;
             const size_t grid = xcd ? 8 * div_up(ntiles, 8) : ntiles;
             if (packed && tk)
-                k_radix_scatter<false, true, RS_BLOCK, true><<<dim3(grid), dim3(RS_BLOCK), 0, st>>>(nullptr, nullptr, nullptr, keys_alt, vout, count, pshift, offs,
+                k_radix_scatter<false, true, RS_BLOCK, true><<<dim3(grid), dim3(RS_BLOCK), 0, st>>>(nullptr, nullptr, nullptr, keys_alt, vout, count, pshift, dmask, next_dmask, offs,
                                                                                                   xcd ? static_cast<uint32_t>(ntiles) : 0u, *tk, emit, fin, pk);
             else if (packed)
-                k_radix_scatter<false, false, RS_BLOCK, true><<<dim3(grid), dim3(RS_BLOCK), 0, st>>>(keys, nullptr, nullptr, keys_alt, vout, count, pshift, offs,
+                k_radix_scatter<false, false, RS_BLOCK, true><<<dim3(grid), dim3(RS_BLOCK), 0, st>>>(keys, nullptr, nullptr, keys_alt, vout, count, pshift, dmask, next_dmask, offs,
                                                                                                    xcd ? static_cast<uint32_t>(ntiles) : 0u, TextKeys{}, emit, fin, pk);
             else if (tk)
-                k_radix_scatter<false, true><<<dim3(grid), dim3(RS_BLOCK), 0, st>>>(nullptr, nullptr, nullptr, keys_alt, vout, count, shift, offs,
+                k_radix_scatter<false, true><<<dim3(grid), dim3(RS_BLOCK), 0, st>>>(nullptr, nullptr, nullptr, keys_alt, vout, count, shift, dmask, next_dmask, offs,
                                                                                    xcd ? static_cast<uint32_t>(ntiles) : 0u, *tk, emit, fin);
             else if (DK_KNOB("DK_SCATTER_BLOCK", DK_SCATTER_BLOCK_DEFAULT) == 512)
-                k_radix_scatter<false, false, 512><<<dim3(grid), dim3(512), 0, st>>>(keys, vals, nullptr, keys_alt, vout, count, shift, offs,
+                k_radix_scatter<false, false, 512><<<dim3(grid), dim3(512), 0, st>>>(keys, vals, nullptr, keys_alt, vout, count, shift, dmask, next_dmask, offs,
                                                                                     xcd ? static_cast<uint32_t>(ntiles) : 0u, TextKeys{}, emit, fin);
             else
-                k_radix_scatter<false><<<dim3(grid), dim3(RS_BLOCK), 0, st>>>(keys, vals, nullptr, keys_alt, vout, count, shift, offs,
+                k_radix_scatter<false><<<dim3(grid), dim3(RS_BLOCK), 0, st>>>(keys, vals, nullptr, keys_alt, vout, count, shift, dmask, next_dmask, offs,
                                                                              xcd ? static_cast<uint32_t>(ntiles) : 0u, TextKeys{}, emit, fin);
         }
         DK_HIP(ctx, hipGetLastError());
@@ -821,7 +833,7 @@ int sort_pairs(dk_ctx *ctx, uint64_t *&keys, uint64_t *&keys_alt, uint32_t *&val
         const int npasses = (end_bit - begin_bit + 7) / 8;
         {
             LaunchScope ls(ctx, K_RADIX_SORT_SMALL, 24.0 * count);
-            k_radix_sort_small<<<dim3(1), dim3(SS_BLOCK), 0, ctx->stream>>>(keys, vals, static_cast<uint32_t>(count), begin_bit, end_bit);
+            k_radix_sort_small<<<dim3(1), dim3(SS_BLOCK), 0, ctx->stream>>>(keys, vals, static_cast<uint32_t>(count), begin_bit, end_bit, last_digit_mask(begin_bit, end_bit));
         }
         DK_HIP(ctx, hipGetLastError());
         ctx->stats.sort_passes += static_cast<uint32_t>(npasses);
@@ -836,7 +848,7 @@ int local_sort_tiles(dk_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, size_t cou
     if (count == 0 || count > 0xFFFFFFFFull) return ctx->fail(DK_E_ARG, "local_sort_tiles: count");
     {
         LaunchScope ls(ctx, K_RADIX_SORT_SMALL, 24.0 * count);
-        k_radix_sort_small<<<dim3(static_cast<unsigned>(div_up(count, SS_MAX))), dim3(SS_BLOCK), 0, ctx->stream>>>(d_keys, d_vals, static_cast<uint32_t>(count), begin_bit, end_bit);
+        k_radix_sort_small<<<dim3(static_cast<unsigned>(div_up(count, SS_MAX))), dim3(SS_BLOCK), 0, ctx->stream>>>(d_keys, d_vals, static_cast<uint32_t>(count), begin_bit, end_bit, last_digit_mask(begin_bit, end_bit));
     }
     DK_HIP(ctx, hipGetLastError());
     DK_HIP(ctx, hipStreamSynchronize(ctx->stream));

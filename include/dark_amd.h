@@ -308,13 +308,25 @@ int dk_dbg_l3_claim_order(const int *group_numa, int ngroups, int own, int prefe
 int dk_dbg_stream_encode_gated(int model_id, size_t n, const uint32_t init[256], const uint32_t *dist, const uint8_t *sym, size_t m,
                                uint32_t origin, uint8_t *out, size_t out_cap, size_t *out_len, const size_t *ready, unsigned stall_ms,
                                int host_threads);
-/* stable LSD radix sort of (u64 key, u32 value) pairs on bits [begin_bit, end_bit) -- the workhorse of the suffix sort */
+/* stable LSD radix sort of (u64 key, u32 value) pairs on bits [begin_bit, end_bit) -- the workhorse of the suffix sort.  Exactly those bits: a
+ * width that is no multiple of eight ends in a pass with a narrower digit, and what a key holds below begin_bit or from end_bit up travels with
+ * its pair without a say in the order. */
 int dk_dbg_sort_pairs(dk_ctx *ctx, uint64_t *keys, uint32_t *vals, size_t count, int begin_bit, int end_bit);
 /* the same on device arrays, in place (measurement: tools/local_sort_bench.py) */
 int dk_dbg_dev_sort_pairs(dk_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, size_t count, int begin_bit, int end_bit);
 /* every 8192-pair tile of a device array sorted by itself inside one workgroup's LDS (the local pass an MSD-first sort would end with:
  * an experiment of round 4) */
 int dk_dbg_dev_local_sort(dk_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, size_t count, int begin_bit, int end_bit);
+/* ngroups independent stable sorts on bits [begin_bit, end_bit) in one launch per size class (the medium groups of the L-first path): group g is
+ * the pairs [starts[g], starts[g + 1]) of d_kin / d_vin.  A group of more than `above` and at most 8192 pairs goes, sorted, to the same places
+ * of d_kout / d_vout; nothing is written for any other group.  d_kout == d_kin and d_vout == d_vin (in place) are allowed.  `starts` is HOST
+ * memory, ngroups + 1 entries: DK_E_ARG unless it is non-decreasing and ends at most at npairs. */
+int dk_dbg_dev_sort_groups(dk_ctx *ctx, const uint64_t *d_kin, const uint32_t *d_vin, uint64_t *d_kout, uint32_t *d_vout, const uint32_t *starts,
+                           size_t ngroups, size_t npairs, uint32_t above, int begin_bit, int end_bit);
+/* d_rank[d_sa[p]] = p for a permutation d_sa of 0 .. n-1 (n <= 2^31), through LDS windows.  d_marked_val (may be null): an entry of d_sa with bit
+ * 31 set stands for d_sa[p] & 0x7FFFFFFF and its value is d_marked_val[p] instead of p.  The two n-u64 scratch arrays come from the context's
+ * workspace: DK_E_NOMEM when they do not fit.  What it does with an input that is no permutation is not defined beyond "no store outside d_rank". */
+int dk_dbg_dev_inverse_permutation(dk_ctx *ctx, const uint32_t *d_sa, size_t n, uint32_t *d_rank, const uint32_t *d_marked_val);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,7 @@ MODEL_IDS.update({name + "+ff": mid | DK_MODEL_ANYBYTE for name, mid in list(MOD
 NUM_KERNEL_SLOTS = 32
 DK_FLAG_HAS_FF, DK_FLAG_SINGLE_SYMBOL = 1, 2
 DK_PACKED_MAX_BLOCKS, DK_PACKED_MAX_BLOCK_BYTES = 65536, 1 << 24
+PURPOSES = {"full": 0, "decoder": 1}  # DK_CTX_FULL, DK_CTX_DECODER
 
 
 class Stats(C.Structure):
@@ -37,6 +38,9 @@ _vp, _sz, _szp, _u32p, _i = C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POI
 SIGNATURES = {
     "dk_version": (C.c_char_p, []),
     "dk_ctx_create": (_i, [_i, _sz, C.POINTER(_vp)]),
+    "dk_ctx_create_decoder": (_i, [_i, _sz, _sz, C.POINTER(_vp)]),
+    "dk_ctx_purpose": (_i, [_vp]),
+    "dk_workspace_bytes": (_sz, [_i, _sz, _sz]),
     "dk_ctx_destroy": (None, [_vp]),
     "dk_capacity": (_sz, [_vp]),
     "dk_last_consumed": (_sz, [_vp]),

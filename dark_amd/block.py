@@ -20,8 +20,12 @@ class _Dc:
         def __init__(self, n, model, device=0, ctx=None):
             self.model = model
             self._n = n
-            self._ctx = ctx or Context(n, device)
+            self._ctx = ctx or Context(n, device, purpose="decoder")  # block::dc::Decoder::new: the inverse path's workspace only
             model_id(model)
+
+        @property
+        def purpose(self):
+            return self._ctx.purpose
 
         def decode(self, stream):
             return self._ctx.block_decode(self.model, stream, self._n)
@@ -57,7 +61,11 @@ class _Raw:
             self.model = model
             self._id = RAW_MODELS[model]
             self._n = n
-            self._ctx = ctx or Context(n, device)
+            self._ctx = ctx or Context(n, device, purpose="decoder")
+
+        @property
+        def purpose(self):
+            return self._ctx.purpose
 
         def decode(self, stream):
             return self._ctx.raw_block_decode(stream, self._n, self._id)

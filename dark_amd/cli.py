@@ -129,6 +129,11 @@ def _note(key, text):
         print("dark_amd: " + text, file=sys.stderr)
 
 
+def _note_workspace(ctx):
+    """--stats on decode: the largest device workspace a context of this run took"""
+    STATS["ws_size_bytes"] = max(STATS.get("ws_size_bytes", 0), int(ctx.stats()["ws_size_bytes"]))
+
+
 def _note_model(model):
     if model in RAW_CODING_MODELS:
         _note("bbb", "-m bbb is EXPERIMENTAL here: the model's gates restate compress::entropy::ari::apm from an in-repo analogue (parity "
@@ -255,6 +260,7 @@ def _encode_blocks(path, model, block_size, device, first_block, step, total_blo
 
 
 PACK_BYTES = 64 << 20
+PACKED_MAX_BLOCKS = 65536  # DK_PACKED_MAX_BLOCKS
 PACKED_MAX_BLOCK_BYTES = 1 << 24  # DK_PACKED_MAX_BLOCK_BYTES  # --packed: consecutive blocks grouped into packs of at most this many bytes
 
 
@@ -464,8 +470,9 @@ def _decode_records_batched(path, model, device, offsets, end, which, out_write,
         if not sizes:
             return
         batch = int(max(2, min(4 * host_threads, (1 << 30) // max(sizes))))  # two batches of outputs live in HBM at a time
-        with Context(max(sizes), device) as ctx:
+        with Context(max(sizes), device, purpose="decoder") as ctx:
             STATS["t_ready"] = time.perf_counter()
+            _note_workspace(ctx)
             # a writer thread downloads and writes the blocks of one batch while the next batch is being decoded
             wq = queue.Queue(maxsize=1)
             werr = []
@@ -531,8 +538,11 @@ def _decode_records_packed(path, model, device, offsets, end, out_write, host_th
             else:
                 segments.append([kind, [k], n])
         cap = max([nb for kind, _, nb in segments if kind == "pack"] or [0])
-        ctx = Context(cap, device) if cap else None
+        most = max([len(ks) for kind, ks, _ in segments if kind == "pack"] or [0])  # the largest pack planned above decides max_blocks
+        ctx = Context(cap, device, purpose="decoder", max_blocks=min(most, PACKED_MAX_BLOCKS)) if cap else None
         STATS["t_ready"] = time.perf_counter()
+        if ctx is not None:
+            _note_workspace(ctx)
         try:
             for kind, ks, _ in segments:
                 if kind == "big":
@@ -583,7 +593,8 @@ def decode_file(path, model, device=0, gpus=1, host_threads=0, devices=None, pac
                 if ctx is None or ctx.capacity() < n:
                     if ctx is not None:
                         ctx.close()
-                    ctx = Context(n, device)
+                    ctx = Context(n, device, purpose="decoder")
+                    _note_workspace(ctx)
                 if model in RAW_CODING_MODELS:
                     out.write(ctx.raw_block_decode(blob[pos:], n, 1))   # block::raw::Decoder, main.rs:73
                 else:
@@ -674,9 +685,11 @@ def main(argv=None):
         import json
         import resource
         t1 = time.perf_counter()
-        print(json.dumps({"seconds": round(t1 - t0, 3), "seconds_after_setup": round(t1 - STATS.get("t_ready", t0), 3), "input_bytes": os.path.getsize(args.file),
-                          "output_bytes": os.path.getsize(out), "peak_rss_bytes": resource.getrusage(resource.RUSAGE_SELF).ru_maxrss * 1024}),
-              file=sys.stderr)
+        line = {"seconds": round(t1 - t0, 3), "seconds_after_setup": round(t1 - STATS.get("t_ready", t0), 3), "input_bytes": os.path.getsize(args.file),
+                "output_bytes": os.path.getsize(out), "peak_rss_bytes": resource.getrusage(resource.RUSAGE_SELF).ru_maxrss * 1024}
+        if decode and "ws_size_bytes" in STATS:  # (one GPU: with --gpus the contexts live in the worker processes)
+            line["ws_size_bytes"] = STATS["ws_size_bytes"]
+        print(json.dumps(line), file=sys.stderr)
 
 
 if __name__ == "__main__":

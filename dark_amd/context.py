@@ -56,16 +56,34 @@ def _stream_cap(mid, n):
     return (10 if mid == _lib.MODEL_IDS["rawdc"] else 2) * int(n) + 4096 + _prefix(mid)
 
 
+def workspace_bytes(purpose, n, max_blocks=1):
+    """dk_workspace_bytes: the device workspace a Context(n, purpose=purpose, max_blocks=max_blocks) allocates; needs no GPU.
+    0 for arguments no context can be made with."""
+    if purpose not in _lib.PURPOSES:
+        return 0
+    return int(_lib.load().dk_workspace_bytes(_lib.PURPOSES[purpose], int(n), int(max_blocks)))
+
+
 class Context:
-    def __init__(self, max_n, device=0):
+    def __init__(self, max_n, device=0, purpose="full", max_blocks=1):
+        """purpose="decoder": a context for the inverse path only (dk_ctx_create_decoder), about a fifth of the workspace; max_blocks = most
+        blocks one of its packed calls may hold.  A full context ignores max_blocks."""
+        if purpose not in _lib.PURPOSES:
+            raise DarkError(_lib.DK_E_ARG, "unknown context purpose %r" % (purpose,))
         self._lib = _lib.load()
         h = C.c_void_p()
-        rc = self._lib.dk_ctx_create(int(device), int(max_n), C.byref(h))
+        if purpose == "decoder":
+            rc = self._lib.dk_ctx_create_decoder(int(device), int(max_n), int(max_blocks), C.byref(h))
+            what = "dk_ctx_create_decoder(device=%d, max_n=%d, max_blocks=%d)" % (device, max_n, max_blocks)
+        else:
+            rc = self._lib.dk_ctx_create(int(device), int(max_n), C.byref(h))
+            what = "dk_ctx_create(device=%d, max_n=%d)" % (device, max_n)
         if rc != 0:
-            raise DarkError(rc, "dk_ctx_create(device=%d, max_n=%d)" % (device, max_n))
+            raise DarkError(rc, what)
         self._h = h
         self._batch = None  # the streaming Batch open on this context, if any
         self.device = device
+        self.purpose = purpose
 
     def close(self):
         if getattr(self, "_h", None):

@@ -20,8 +20,12 @@ using namespace dk;
 
 namespace {
 
-int begin_call(dk_ctx *ctx) {
+// forward_entry: the name of an entry point that needs the suffix sort's workspace (everything but the inverse path).  A decoder context
+// refuses it here, before anything is reset, allocated, launched or copied.
+int begin_call(dk_ctx *ctx, const char *forward_entry = nullptr) {
     if (!ctx) return DK_E_ARG;
+    if (forward_entry && ctx->purpose == DK_CTX_DECODER)
+        return ctx->fail(DK_E_ARG, "%s: not served by a decoder context (dk_ctx_create_decoder sizes the workspace for the inverse path only)", forward_entry);
     // a streaming batch owns the workspace and the staging slots until it is finished: any other call would pull them from under
     // the coding threads
     if (ctx->live_batch) return ctx->fail(DK_E_ARG, "a streaming batch is open on this context: call dk_batch_finish first");
@@ -69,6 +73,40 @@ size_t workspace_bytes(size_t max_n) {
     // tests/test_gpu_fullsize.py checks the n-proportional term where the constant is negligible (peak - 64 MiB <= 69.4 n at 1e8 bytes).
     const size_t sort_temporaries = 62 * max_n + max_n / 8, io = 6 * max_n, on_top = max_n / 4 + max_n;
     return sort_temporaries + io + on_top + max_n / 4 /* headroom */ + (64u << 20);
+}
+size_t decoder_workspace_bytes(size_t max_n, size_t max_blocks) {
+    // Peak of the bump allocator over the calls a decoder context serves (every term is one ws_alloc of the call, rounded up to 256 bytes):
+    //   bwt_inverse_device (bwt.hip: bwt_inverse_workspace)
+    //     tile histograms  256 counters per 4096 positions                                            n / 4
+    //     chunk sums       at most 256 chunks x 256 counters                                          256 KiB at most
+    //     class starts                                                                                1 KiB
+    //     successor table                                                                             8 n
+    //     blocks below 2^16 (S = 8):  four splitter arrays of ceil(n / 8) + 1 words, no records       2 n
+    //     blocks from 2^16 (S = 64):  four splitter arrays of ceil(n / 64) + 1 words                  n / 4
+    //                                 len_keep + resume, one word per splitter each                   n / 8
+    //                                 records, IB_REC = 256 bytes per splitter                        4 n
+    //     = 12.625 n from 2^16 bytes (10.25 n below)
+    //   around it, at most two block-sized buffers: L + the output copy (dk_bwt_inverse, dk_block_decode, dk_raw_block_decode); L alone in
+    //   dk_dev_block_decode and dk_dev_batch_decode; none in dk_dev_bwt_inverse                       2 n
+    //   = 14.625 n for a single block.
+    //   packed_ibwt_device (bwt.hip: packed_ibwt_workspace), count <= max_blocks blocks of `total` <= max_n bytes together
+    //     aux              off | origin | first splitter of every block: 3 count + 2 words
+    //     tile histograms, chunk sums, class starts, successor table over the pack                    8.25 total
+    //     base             count x 256 words                                                          1 KiB per block
+    //     cls0             count words
+    //     four splitter arrays of nsplit <= min(total, total / 64 + 2 count) words (sum of ceil(n_i / 64), + 1 per origin off the grid)
+    //     len_keep + resume + records only where nsplit * 32 <= total                                 8.25 total at most
+    //   around it the pack-sized L of dk_dev_packed_decode                                            total
+    //   = 13.625 total for one block, 33.5 total + 1 KiB per block for a pack of one-byte blocks.
+    // The larger of the two, + n / 64 + 64 KiB of headroom.  The pinned staging (ensure_stage, ensure_slot) is host memory and not part of this.
+    // tests/test_gpu_decoder_ctx.py checks peak <= size on contexts sized exactly to their block or pack, through every entry above.
+    const size_t single = 2 * ((max_n + 255) & ~size_t(255)) + bwt_inverse_workspace(max_n);
+    const size_t packed = ((max_n + 255) & ~size_t(255)) + packed_ibwt_workspace(max_n, max_blocks);
+    return std::max(single, packed) + max_n / 64 /* headroom */ + (64u << 10);
+}
+bool good_ctx_size(int purpose, size_t max_n, size_t max_blocks) {
+    if (max_n == 0 || max_n > 0x7FFFFFFEull) return false;
+    return purpose == DK_CTX_FULL || (purpose == DK_CTX_DECODER && max_blocks >= 1 && max_blocks <= DK_PACKED_MAX_BLOCKS);
 }
 struct ScopedCall {
     dk_ctx *c;
@@ -245,8 +283,11 @@ extern "C" {
 
 const char *dk_version(void) { return "dark_amd 0.1 (gfx950, HIP)"; }
 
-int dk_ctx_create(int hip_device, size_t max_n, dk_ctx **out) {
-    if (!out || max_n == 0 || max_n > 0x7FFFFFFEull) return DK_E_ARG;
+}  // extern "C"
+
+namespace {
+int ctx_create(int purpose, int hip_device, size_t max_n, size_t max_blocks, dk_ctx **out) {
+    if (!out || !good_ctx_size(purpose, max_n, max_blocks)) return DK_E_ARG;
     *out = nullptr;
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return DK_E_NODEVICE;
@@ -255,6 +296,8 @@ int dk_ctx_create(int hip_device, size_t max_n, dk_ctx **out) {
     if (!c) return DK_E_NOMEM;
     c->device = hip_device;
     c->max_n = max_n;
+    c->purpose = purpose;
+    if (purpose == DK_CTX_DECODER) c->max_blocks = max_blocks;
     bool ok = hipSetDevice(hip_device) == hipSuccess && hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess;
     {   // the GPU's memory node: the host coder claims its last-level-cache group there first (entropy.cpp: l3_claim_order)
         char bdf[32] = {0};
@@ -268,7 +311,7 @@ int dk_ctx_create(int hip_device, size_t max_n, dk_ctx **out) {
             }
         }
     }
-    c->ws_size = workspace_bytes(max_n);
+    c->ws_size = purpose == DK_CTX_DECODER ? decoder_workspace_bytes(max_n, max_blocks) : workspace_bytes(max_n);
     ok = ok && hipMalloc(reinterpret_cast<void **>(&c->ws), c->ws_size) == hipSuccess;
     ok = ok && hipMalloc(reinterpret_cast<void **>(&c->d_mail), sizeof(dk::Mail)) == hipSuccess;
     ok = ok && hipHostMalloc(reinterpret_cast<void **>(&c->h_mail), sizeof(dk::Mail), hipHostMallocDefault) == hipSuccess;
@@ -285,6 +328,19 @@ int dk_ctx_create(int hip_device, size_t max_n, dk_ctx **out) {
     }
     *out = c;
     return DK_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int dk_ctx_create(int hip_device, size_t max_n, dk_ctx **out) { return ctx_create(DK_CTX_FULL, hip_device, max_n, 0, out); }
+int dk_ctx_create_decoder(int hip_device, size_t max_n, size_t max_blocks, dk_ctx **out) {
+    return ctx_create(DK_CTX_DECODER, hip_device, max_n, max_blocks, out);
+}
+int dk_ctx_purpose(const dk_ctx *ctx) { return ctx ? ctx->purpose : DK_E_ARG; }
+size_t dk_workspace_bytes(int purpose, size_t max_n, size_t max_blocks) {
+    if (!good_ctx_size(purpose, max_n, max_blocks)) return 0;
+    return purpose == DK_CTX_DECODER ? decoder_workspace_bytes(max_n, max_blocks) : workspace_bytes(max_n);
 }
 
 void dk_ctx_destroy(dk_ctx *c) {
@@ -315,7 +371,7 @@ const char *dk_last_error(const dk_ctx *ctx) { return ctx ? ctx->err.c_str() : "
 
 // ---- device-resident entry points ------------------------------------------------------------------------------------
 int dk_dev_suffix_array(dk_ctx *ctx, const uint8_t *d_in, size_t n, uint32_t *d_sa_out) {
-    DK_TRY(begin_call(ctx));
+    DK_TRY(begin_call(ctx, "dk_dev_suffix_array"));
     ScopedCall sc(ctx);
     if (!d_in || !d_sa_out) return ctx->fail(DK_E_ARG, "null pointer");
     DK_TRY(check_n(ctx, n));
@@ -327,7 +383,7 @@ int dk_dev_suffix_array(dk_ctx *ctx, const uint8_t *d_in, size_t n, uint32_t *d_
 }
 
 int dk_dev_bwt_forward(dk_ctx *ctx, const uint8_t *d_in, size_t n, uint8_t *d_bwt_out, uint32_t *origin) {
-    DK_TRY(begin_call(ctx));
+    DK_TRY(begin_call(ctx, "dk_dev_bwt_forward"));
     ScopedCall sc(ctx);
     if (!d_in || !d_bwt_out || !origin) return ctx->fail(DK_E_ARG, "null pointer");
     DK_TRY(check_n(ctx, n));
@@ -353,7 +409,7 @@ int dk_dev_bwt_inverse(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t ori
 
 int dk_dev_dc_encode(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t init[256], uint32_t *d_dist, uint8_t *d_sym, uint8_t *d_rank,
                      size_t *m) {
-    DK_TRY(begin_call(ctx));
+    DK_TRY(begin_call(ctx, "dk_dev_dc_encode"));
     ScopedCall sc(ctx);
     if (!d_bwt || !init || !d_dist || !d_sym || !m) return ctx->fail(DK_E_ARG, "null pointer");
     DK_TRY(check_n(ctx, n));
@@ -364,7 +420,7 @@ int dk_dev_dc_encode(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t init[
 }
 
 int dk_dev_block_encode(dk_ctx *ctx, int model_id, const uint8_t *d_in, size_t n, uint8_t *out, size_t out_cap, size_t *out_len) {
-    DK_TRY(begin_call(ctx));
+    DK_TRY(begin_call(ctx, "dk_dev_block_encode"));
     ScopedCall sc(ctx);
     if (!d_in || !out || !out_len) return ctx->fail(DK_E_ARG, "null pointer");
     DK_TRY(check_n(ctx, n));
@@ -433,8 +489,11 @@ struct dk_batch {
 
 extern "C" {
 
-int dk_batch_begin(dk_ctx *ctx, int model_id, int host_threads, dk_batch **out) {
-    DK_TRY(begin_call(ctx));
+}  // extern "C"
+
+// dk_batch_begin for the entry points that are built on it: `entry` is the name a decoder context's refusal carries
+static int batch_begin(dk_ctx *ctx, int model_id, int host_threads, dk_batch **out, const char *entry) {
+    DK_TRY(begin_call(ctx, entry));
     if (!out) return ctx->fail(DK_E_ARG, "null pointer");
     *out = nullptr;
     if (model_max_block(model_id) == 0) return ctx->fail(DK_E_MODEL, "unknown model id %d", model_id);
@@ -450,6 +509,10 @@ int dk_batch_begin(dk_ctx *ctx, int model_id, int host_threads, dk_batch **out) 
     *out = b;
     return DK_OK;
 }
+
+extern "C" {
+
+int dk_batch_begin(dk_ctx *ctx, int model_id, int host_threads, dk_batch **out) { return batch_begin(ctx, model_id, host_threads, out, "dk_batch_begin"); }
 
 int dk_batch_push(dk_batch *b, const uint8_t *d_in, size_t n, uint8_t *out, size_t out_cap, size_t *out_len) {
     if (!b) return DK_E_ARG;
@@ -513,7 +576,7 @@ constexpr int PACKED_MAX_ROUNDS = 12;
 
 int check_pack(dk_ctx *ctx, size_t count, const size_t *n, std::vector<uint32_t> &off) {
     if (!n) return ctx->fail(DK_E_ARG, "null pointer");
-    if (count == 0 || count > DK_PACKED_MAX_BLOCKS) return ctx->fail(DK_E_ARG, "a pack holds 1 .. %d blocks, not %zu", DK_PACKED_MAX_BLOCKS, count);
+    if (count == 0 || count > ctx->max_blocks) return ctx->fail(DK_E_ARG, "a pack holds 1 .. %zu blocks, not %zu", ctx->max_blocks, count);
     off.assign(count + 1, 0);
     size_t total = 0;
     for (size_t i = 0; i < count; ++i) {
@@ -580,7 +643,7 @@ int packed_forward(dk_ctx *ctx, const uint8_t *d_in, const std::vector<uint32_t>
 extern "C" {
 
 int dk_dev_bwt_forward_packed(dk_ctx *ctx, const uint8_t *d_in, size_t count, const size_t *n, uint8_t *d_bwt_out, uint32_t *origin) {
-    DK_TRY(begin_call(ctx));
+    DK_TRY(begin_call(ctx, "dk_dev_bwt_forward_packed"));
     ScopedCall sc(ctx);
     if (!d_in || !n || !d_bwt_out || !origin) return ctx->fail(DK_E_ARG, "null pointer");
     std::vector<uint32_t> off;
@@ -601,7 +664,7 @@ int dk_dev_bwt_forward_packed(dk_ctx *ctx, const uint8_t *d_in, size_t count, co
 
 int dk_dev_suffix_array_packed(dk_ctx *ctx, const uint8_t *d_in, size_t count, const size_t *n, uint32_t *d_sa_out, uint8_t *d_bwt_out,
                                uint32_t *origin) {
-    DK_TRY(begin_call(ctx));
+    DK_TRY(begin_call(ctx, "dk_dev_suffix_array_packed"));
     ScopedCall sc(ctx);
     if (!d_in || !n || !d_sa_out) return ctx->fail(DK_E_ARG, "null pointer");
     if ((d_bwt_out == nullptr) != (origin == nullptr)) return ctx->fail(DK_E_ARG, "d_bwt_out and origin go together: both or neither");
@@ -625,7 +688,7 @@ int dk_dev_suffix_array_packed(dk_ctx *ctx, const uint8_t *d_in, size_t count, c
 
 int dk_dev_dc_encode_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, const size_t *n, uint32_t *init, uint32_t *d_dist, uint8_t *d_sym,
                             uint8_t *d_rank, size_t *m) {
-    DK_TRY(begin_call(ctx));
+    DK_TRY(begin_call(ctx, "dk_dev_dc_encode_packed"));
     ScopedCall sc(ctx);
     if (!d_bwt || !n || !init || !d_dist || !d_sym || !m) return ctx->fail(DK_E_ARG, "null pointer");
     std::vector<uint32_t> off;
@@ -770,7 +833,7 @@ int dk_dev_packed_encode(dk_ctx *ctx, int model_id, const uint8_t *d_in, size_t 
     Timer t;
     dk_batch *b = nullptr;
     const int threads = static_cast<int>(std::max<size_t>(1, std::min<size_t>(static_cast<size_t>(std::max(1, host_threads)), std::max<size_t>(1, count))));
-    DK_TRY(dk_batch_begin(ctx, model_id, threads, &b));
+    DK_TRY(batch_begin(ctx, model_id, threads, &b, "dk_dev_packed_encode"));
     const int rc = dk_batch_push_packed(b, d_in, count, n, out, out_cap, out_len, flags);
     const std::string err = ctx->err;
     const int rc2 = dk_batch_finish(b);
@@ -782,10 +845,11 @@ int dk_dev_packed_encode(dk_ctx *ctx, int model_id, const uint8_t *d_in, size_t 
 int dk_dev_batch_encode(dk_ctx *ctx, int model_id, size_t count, const uint8_t *const *d_in, const size_t *n, uint8_t *const *out,
                         const size_t *out_cap, size_t *out_len, int host_threads) {
     if (!ctx) return DK_E_ARG;
+    if (ctx->purpose == DK_CTX_DECODER) return begin_call(ctx, "dk_dev_batch_encode");
     if (!d_in || !n || !out || !out_cap || !out_len || count == 0) { ctx->err.clear(); return ctx->fail(DK_E_ARG, "null pointer or empty batch"); }
     Timer t;
     dk_batch *b = nullptr;
-    DK_TRY(dk_batch_begin(ctx, model_id, std::max(1, std::min<int>(host_threads, static_cast<int>(count))), &b));
+    DK_TRY(batch_begin(ctx, model_id, std::max(1, std::min<int>(host_threads, static_cast<int>(count))), &b, "dk_dev_batch_encode"));
     int rc = DK_OK;
     for (size_t i = 0; i < count && rc == DK_OK; ++i) rc = dk_batch_push(b, d_in[i], n[i], out[i], out_cap[i], &out_len[i]);
     const int rc2 = dk_batch_finish(b);
@@ -954,7 +1018,7 @@ int dk_dev_packed_decode(dk_ctx *ctx, int model_id, size_t count, const uint8_t 
 
 // ---- host-pointer entry points: stage in, run the device path, stage out ---------------------------------------------
 int dk_suffix_array(dk_ctx *ctx, const uint8_t *in, size_t n, uint32_t *sa_out) {
-    DK_TRY(begin_call(ctx));
+    DK_TRY(begin_call(ctx, "dk_suffix_array"));
     ScopedCall sc(ctx);
     if (!in || !sa_out) return ctx->fail(DK_E_ARG, "null pointer");
     DK_TRY(check_n(ctx, n));
@@ -971,7 +1035,7 @@ int dk_suffix_array(dk_ctx *ctx, const uint8_t *in, size_t n, uint32_t *sa_out) 
 }
 
 int dk_suffix_array_packed(dk_ctx *ctx, const uint8_t *in, size_t count, const size_t *n, uint32_t *sa_out) {
-    DK_TRY(begin_call(ctx));
+    DK_TRY(begin_call(ctx, "dk_suffix_array_packed"));
     ScopedCall sc(ctx);
     if (!in || !n || !sa_out) return ctx->fail(DK_E_ARG, "null pointer");
     std::vector<uint32_t> off;
@@ -994,7 +1058,7 @@ int dk_suffix_array_packed(dk_ctx *ctx, const uint8_t *in, size_t count, const s
 }
 
 int dk_bwt_forward(dk_ctx *ctx, const uint8_t *in, size_t n, uint8_t *bwt_out, uint32_t *origin) {
-    DK_TRY(begin_call(ctx));
+    DK_TRY(begin_call(ctx, "dk_bwt_forward"));
     ScopedCall sc(ctx);
     if (!in || !bwt_out || !origin) return ctx->fail(DK_E_ARG, "null pointer");
     DK_TRY(check_n(ctx, n));
@@ -1030,7 +1094,7 @@ int dk_bwt_inverse(dk_ctx *ctx, const uint8_t *bwt, size_t n, uint32_t origin, u
 }
 
 int dk_dc_encode(dk_ctx *ctx, const uint8_t *bwt, size_t n, uint32_t init[256], uint32_t *dist, uint8_t *sym, uint8_t *rank, size_t *m) {
-    DK_TRY(begin_call(ctx));
+    DK_TRY(begin_call(ctx, "dk_dc_encode"));
     ScopedCall sc(ctx);
     if (!bwt || !init || !dist || !sym || !m) return ctx->fail(DK_E_ARG, "null pointer");
     DK_TRY(check_n(ctx, n));
@@ -1058,7 +1122,7 @@ int dk_dc_decode(dk_ctx *ctx, const uint32_t init[256], const uint32_t *dist, si
 }
 
 int dk_block_encode(dk_ctx *ctx, int model_id, const uint8_t *in, size_t n, uint8_t *out, size_t out_cap, size_t *out_len) {
-    DK_TRY(begin_call(ctx));
+    DK_TRY(begin_call(ctx, "dk_block_encode"));
     ScopedCall sc(ctx);
     if (!in || !out || !out_len) return ctx->fail(DK_E_ARG, "null pointer");
     DK_TRY(check_n(ctx, n));
@@ -1094,7 +1158,7 @@ int dk_block_decode(dk_ctx *ctx, int model_id, const uint8_t *in, size_t in_len,
 // Out (into `dump`) or the bbb coding model (into `out`; host, bit-serial)
 int dk_raw_block_encode(dk_ctx *ctx, int raw_model, const uint8_t *in, size_t n, uint8_t *out, size_t out_cap, size_t *out_len, uint8_t *dump,
                         size_t dump_cap, size_t *dump_len) {
-    DK_TRY(begin_call(ctx));
+    DK_TRY(begin_call(ctx, "dk_raw_block_encode"));
     ScopedCall sc(ctx);
     if (!in || !out || !out_len) return ctx->fail(DK_E_ARG, "null pointer");
     if (raw_model != DK_RAWMODEL_OUT && raw_model != DK_RAWMODEL_BBB) return ctx->fail(DK_E_MODEL, "unknown raw model %d", raw_model);
@@ -1170,7 +1234,7 @@ struct DeviceBuffers {  // input / output blocks of one sub-batch in HBM
     ~DeviceBuffers() { for (uint8_t *p : ptr) if (p) (void)hipFree(p); }
 };
 template <class Work>
-int run_per_device(const int *devices, int ndev, size_t count, const size_t *n, char *err, size_t err_cap, Work work) {
+int run_per_device(int purpose, const int *devices, int ndev, size_t count, const size_t *n, char *err, size_t err_cap, Work work) {
     if (!devices || ndev <= 0 || count == 0 || !n) return DK_E_ARG;
     std::vector<int> rcs(static_cast<size_t>(ndev), DK_OK);
     std::vector<std::string> msgs(static_cast<size_t>(ndev));
@@ -1182,7 +1246,7 @@ int run_per_device(const int *devices, int ndev, size_t count, const size_t *n, 
             for (size_t i = static_cast<size_t>(r); i < count; i += static_cast<size_t>(ndev)) { mine.push_back(i); max_n = std::max(max_n, n[i]); }
             if (mine.empty()) return;
             dk_ctx *ctx = nullptr;
-            int rc = dk_ctx_create(devices[r], max_n, &ctx);
+            int rc = purpose == DK_CTX_DECODER ? dk_ctx_create_decoder(devices[r], max_n, 1, &ctx) : dk_ctx_create(devices[r], max_n, &ctx);
             if (rc != DK_OK) { rcs[r] = rc; msgs[r] = "dk_ctx_create failed on device " + std::to_string(devices[r]); return; }
             rc = work(ctx, mine);
             if (rc != DK_OK) { rcs[r] = rc; msgs[r] = dk_last_error(ctx); }
@@ -1206,7 +1270,7 @@ int dk_multi_block_encode(const int *devices, int ndev, int model_id, size_t cou
                           const size_t *out_cap, size_t *out_len, int host_threads_per_gpu, char *err, size_t err_cap) {
     if (!in || !out || !out_cap || !out_len) return DK_E_ARG;
     const size_t group = static_cast<size_t>(std::max(1, host_threads_per_gpu)) + 1;  // blocks resident in HBM per sub-batch
-    return run_per_device(devices, ndev, count, n, err, err_cap, [&](dk_ctx *ctx, const std::vector<size_t> &mine) -> int {
+    return run_per_device(DK_CTX_FULL, devices, ndev, count, n, err, err_cap, [&](dk_ctx *ctx, const std::vector<size_t> &mine) -> int {
         for (size_t lo = 0; lo < mine.size(); lo += group) {
             const size_t cnt = std::min(group, mine.size() - lo);
             DeviceBuffers db;
@@ -1234,7 +1298,7 @@ int dk_multi_block_decode(const int *devices, int ndev, int model_id, size_t cou
                           uint8_t *const *out, int host_threads_per_gpu, char *err, size_t err_cap) {
     if (!in || !in_len || !out) return DK_E_ARG;
     const size_t group = static_cast<size_t>(std::max(1, host_threads_per_gpu)) + 1;
-    return run_per_device(devices, ndev, count, n, err, err_cap, [&](dk_ctx *ctx, const std::vector<size_t> &mine) -> int {
+    return run_per_device(DK_CTX_DECODER, devices, ndev, count, n, err, err_cap, [&](dk_ctx *ctx, const std::vector<size_t> &mine) -> int {
         for (size_t lo = 0; lo < mine.size(); lo += group) {
             const size_t cnt = std::min(group, mine.size() - lo);
             DeviceBuffers db;
@@ -1348,13 +1412,13 @@ int dk_dbg_stream_encode_gated(int model_id, size_t n, const uint32_t init[256],
     return encode_block_stream(model_id, s, out, out_cap, out_len, host_threads);
 }
 int dk_dbg_dev_local_sort(dk_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, size_t count, int begin_bit, int end_bit) {
-    DK_TRY(begin_call(ctx));
+    DK_TRY(begin_call(ctx, "dk_dbg_dev_local_sort"));
     ScopedCall sc(ctx);
     if (!d_keys || !d_vals) return ctx->fail(DK_E_ARG, "null pointer");
     return local_sort_tiles(ctx, d_keys, d_vals, count, begin_bit, end_bit);
 }
 int dk_dbg_dev_sort_pairs(dk_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, size_t count, int begin_bit, int end_bit) {
-    DK_TRY(begin_call(ctx));
+    DK_TRY(begin_call(ctx, "dk_dbg_dev_sort_pairs"));
     ScopedCall sc(ctx);
     if (!d_keys || !d_vals || count == 0) return ctx->fail(DK_E_ARG, "null pointer or empty input");
     uint64_t *k0 = d_keys, *k1 = ctx->ws_alloc<uint64_t>(count);
@@ -1370,7 +1434,7 @@ int dk_dbg_dev_sort_pairs(dk_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, size_
 }
 int dk_dbg_dev_sort_groups(dk_ctx *ctx, const uint64_t *d_kin, const uint32_t *d_vin, uint64_t *d_kout, uint32_t *d_vout, const uint32_t *starts,
                            size_t ngroups, size_t npairs, uint32_t above, int begin_bit, int end_bit) {
-    DK_TRY(begin_call(ctx));
+    DK_TRY(begin_call(ctx, "dk_dbg_dev_sort_groups"));
     ScopedCall sc(ctx);
     if (!d_kin || !d_vin || !d_kout || !d_vout || !starts || ngroups == 0 || npairs == 0) return ctx->fail(DK_E_ARG, "null pointer or empty input");
     if (npairs > 0xFFFFFFFFull || begin_bit < 0 || end_bit > 64 || begin_bit > end_bit) return ctx->fail(DK_E_ARG, "sort_groups: %zu pairs, bits [%d, %d)", npairs, begin_bit, end_bit);
@@ -1385,7 +1449,7 @@ int dk_dbg_dev_sort_groups(dk_ctx *ctx, const uint64_t *d_kin, const uint32_t *d
     return DK_OK;
 }
 int dk_dbg_dev_inverse_permutation(dk_ctx *ctx, const uint32_t *d_sa, size_t n, uint32_t *d_rank, const uint32_t *d_marked_val) {
-    DK_TRY(begin_call(ctx));
+    DK_TRY(begin_call(ctx, "dk_dbg_dev_inverse_permutation"));
     ScopedCall sc(ctx);
     if (!d_sa || !d_rank || n == 0) return ctx->fail(DK_E_ARG, "null pointer or empty input");
     if (n > (size_t(1) << 31)) return ctx->fail(DK_E_ARG, "inverse_permutation: %zu entries (bit 31 of an entry is its mark)", n);
@@ -1396,7 +1460,7 @@ int dk_dbg_dev_inverse_permutation(dk_ctx *ctx, const uint32_t *d_sa, size_t n, 
     return DK_OK;
 }
 int dk_dbg_sort_pairs(dk_ctx *ctx, uint64_t *keys, uint32_t *vals, size_t count, int begin_bit, int end_bit) {
-    DK_TRY(begin_call(ctx));
+    DK_TRY(begin_call(ctx, "dk_dbg_sort_pairs"));
     ScopedCall sc(ctx);
     if (!keys || !vals || count == 0) return ctx->fail(DK_E_ARG, "null pointer or empty input");
     uint64_t *k0 = ctx->ws_alloc<uint64_t>(count), *k1 = ctx->ws_alloc<uint64_t>(count);

@@ -817,4 +817,38 @@ int packed_ibwt_device(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector<uint
     return DK_OK;
 }
 
+// ---- what the two inverses above take from the workspace (a decoder context is sized by these: abi.cpp decoder_workspace_bytes) ----------
+namespace {
+size_t ws_round(size_t bytes) { return (bytes + 255) & ~static_cast<size_t>(255); }
+// tile histograms, chunk sums, class starts and the successor table of `total` positions.  The chunk count itself is not monotone in the tile
+// count (257 tiles make 129 chunks, 256 tiles 256): min(tiles, IB_MAX_CHUNKS) bounds it and is.
+size_t ibwt_tables(size_t total) {
+    const size_t ntiles = div_up(total, IB_TILE);
+    return ws_round(ntiles * 256 * 4) + ws_round(std::min<size_t>(ntiles, IB_MAX_CHUNKS) * 256 * 4) + ws_round(256 * 4) + ws_round(total * 8);
+}
+size_t ibwt_records(size_t nsplit) { return 2 * ws_round(nsplit * 4) + ws_round(nsplit * IB_REC); }  // len_keep, resume, rec
+}  // namespace
+
+size_t bwt_inverse_workspace(size_t max_n) {
+    // blocks below 2^16: S = 8, four splitter arrays, no records; from 2^16: S = 64, four splitter arrays + records.  One more splitter for an
+    // origin off the grid in both.  A context for max_n serves every smaller block, so both forms count, each at its largest block.
+    const size_t small_n = std::min<size_t>(max_n, (1u << 16) - 1);
+    size_t bytes = ibwt_tables(small_n) + 4 * ws_round((div_up(small_n, 8) + 1) * 4);
+    if (max_n >= (1u << 16)) {
+        const size_t nsplit = div_up(max_n, 64) + 1;
+        bytes = std::max(bytes, ibwt_tables(max_n) + 4 * ws_round(nsplit * 4) + ibwt_records(nsplit));
+    }
+    return bytes;
+}
+
+size_t packed_ibwt_workspace(size_t max_total, size_t max_blocks) {
+    // Every block holds at least one byte: count <= total.  A block of n_i bytes has ceil(n_i / 64) splitters and one more for an origin off
+    // the grid (only where n_i > 1): at most n_i of them, and at most n_i / 64 + 2.  Records are taken only when nsplit * 32 <= total.
+    const size_t count = std::min(max_blocks, max_total);
+    const size_t nsplit = std::min(max_total, max_total / 64 + 2 * count);
+    const size_t nrec = std::min(nsplit, max_total / 32);
+    return ws_round((3 * count + 2) * 4) /* aux */ + ibwt_tables(max_total) + ws_round(count * 256 * 4) /* base */ + ws_round(count * 4) /* cls0 */ +
+           4 * ws_round(nsplit * 4) + ibwt_records(nrec);
+}
+
 }  // namespace dk

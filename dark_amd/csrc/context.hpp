@@ -67,6 +67,8 @@ struct dk_ctx {
     int device = -1;
     int numa_node = -1;  // memory node the GPU hangs on (/sys/bus/pci/devices/<bdf>/numa_node; -1: unknown): where the host coder looks for its L3 group first
     size_t max_n = 0;
+    int purpose = DK_CTX_FULL;                 // DK_CTX_DECODER: the workspace holds the inverse path only, and begin_call refuses every other entry
+    size_t max_blocks = DK_PACKED_MAX_BLOCKS;  // most blocks a packed call may hold (a decoder context's workspace is sized for its own limit)
     hipStream_t stream = nullptr;
     // a second stream for work that needs nothing from what the main stream does meanwhile (the L-first path's deep groups, ordered beside the
     // rounds that follow), forked from and joined to the main stream with the two events
@@ -213,6 +215,11 @@ int bwt_inverse_device(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t ori
 // packed inverse: block i's text at d_out[off[i], off[i+1]) from its L at d_bwt[off[i], ...) and origin[i] (host, < n_i, checked by the caller);
 // off on the host, off[count] = total.  DK_E_STREAM naming the lowest corrupt block, and then nothing is written to d_out.
 int packed_ibwt_device(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector<uint32_t> &off, const uint32_t *origin, uint8_t *d_out);
+// Workspace the two calls above take at most, every ws_alloc rounded up to 256 bytes: bwt_inverse_device for ANY block of at most max_n bytes
+// and any origin, packed_ibwt_device for ANY pack of at most max_total bytes in at most max_blocks blocks.  Non-decreasing in every argument.
+// Host arithmetic only (abi.cpp: decoder_workspace_bytes).
+size_t bwt_inverse_workspace(size_t max_n);
+size_t packed_ibwt_workspace(size_t max_total, size_t max_blocks);
 // dc.hip: d_run_end may be null
 int dc_encode_device(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t init_host[256], uint32_t *d_dist, uint8_t *d_sym,
                      uint8_t *d_rank, uint32_t *d_run_end, size_t *m);

@@ -25,14 +25,16 @@ struct Result { bool ok = true; std::string message; explicit operator bool() co
 namespace detail {
 class Ctx {
 public:
-    Ctx(size_t max_n, int device) {
-        int rc = dk_ctx_create(device, max_n, &h_);
+    // purpose DK_CTX_DECODER: the inverse path's workspace only (dk_ctx_create_decoder, one block per call)
+    Ctx(size_t max_n, int device, int purpose = DK_CTX_FULL) {
+        int rc = purpose == DK_CTX_DECODER ? dk_ctx_create_decoder(device, max_n, 1, &h_) : dk_ctx_create(device, max_n, &h_);
         if (rc != DK_OK) throw Error(rc, "dk_ctx_create failed (no GPU, or out of memory)");
     }
     ~Ctx() { dk_ctx_destroy(h_); }
     Ctx(const Ctx &) = delete;
     Ctx &operator=(const Ctx &) = delete;
     dk_ctx *get() const { return h_; }
+    int purpose() const { return dk_ctx_purpose(h_); }
     std::string error() const { return dk_last_error(h_); }
 private:
     dk_ctx *h_ = nullptr;
@@ -120,7 +122,7 @@ template <class M>
 class Decoder {
 public:
     M model;
-    Decoder(size_t n, M m, int device = 0, bool any_byte = false) : model(m), ctx_(n, device), n_(n), id_(M::ID | (any_byte ? DK_MODEL_ANYBYTE : 0)) { model.reset(); }
+    Decoder(size_t n, M m, int device = 0, bool any_byte = false) : model(m), ctx_(n, device, DK_CTX_DECODER), n_(n), id_(M::ID | (any_byte ? DK_MODEL_ANYBYTE : 0)) { model.reset(); }
     // decode(reader, writer) -> (reader, writer, io::Result<()>)
     template <class W>
     std::tuple<std::vector<uint8_t>, W, Result> decode(std::vector<uint8_t> reader, W writer) {
@@ -130,6 +132,7 @@ public:
         writer.insert(writer.end(), out.begin(), out.end());
         return {std::move(reader), std::move(writer), Result{}};
     }
+    detail::Ctx &context() { return ctx_; }  // Decoder::new makes a decoder context: context().purpose() == DK_CTX_DECODER
 private:
     detail::Ctx ctx_;
     size_t n_;
@@ -163,7 +166,7 @@ template <class M>
 class Decoder {
 public:
     M model;
-    Decoder(size_t n, M m, int device = 0) : model(m), ctx_(n, device), n_(n) { model.reset(); }
+    Decoder(size_t n, M m, int device = 0) : model(m), ctx_(n, device, DK_CTX_DECODER), n_(n) { model.reset(); }
     template <class W>
     std::tuple<std::vector<uint8_t>, W, Result> decode(std::vector<uint8_t> reader, W writer) {
         std::vector<uint8_t> out(n_);
@@ -172,6 +175,7 @@ public:
         writer.insert(writer.end(), out.begin(), out.end());
         return {std::move(reader), std::move(writer), Result{}};
     }
+    detail::Ctx &context() { return ctx_; }  // Decoder::new makes a decoder context: context().purpose() == DK_CTX_DECODER
 private:
     detail::Ctx ctx_;
     size_t n_;

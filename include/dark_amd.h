@@ -56,6 +56,25 @@ typedef struct dk_ctx dk_ctx;
 /* saca::Constructor::new(max_n) src/saca.rs:351-360 + block::dc::{Encoder,Decoder}::new src/block/dc.rs:30-37,106-115.
  * Allocates the device workspace for blocks of up to max_n bytes on GPU `hip_device` (>= 0). */
 int dk_ctx_create(int hip_device, size_t max_n, dk_ctx **out);
+/* The two purposes of a context.  DK_CTX_FULL (dk_ctx_create) serves every entry point; its workspace is sized for the suffix sort, about
+ * 69.4 x max_n + 64 MiB.  DK_CTX_DECODER serves the inverse path only, in about 14.6 x max_n: the inverse BWT never touches the sort's keys,
+ * lists and rank array.  (There is no encoder-only tier: the forward path's L-first route and its fallback share the sort's whole buffer plan.) */
+#define DK_CTX_FULL 0
+#define DK_CTX_DECODER 1
+/* block::dc::Decoder::new / block::raw::Decoder::new (src/block/dc.rs:106-115, src/block/raw.rs): a context that serves the inverse path only.
+ * max_n: largest block, and largest pack (sum of its blocks); max_blocks (>= 1, <= DK_PACKED_MAX_BLOCKS): most blocks a packed call may hold
+ * (a packed call with more is DK_E_ARG).
+ * Served: dk_bwt_inverse, dk_dev_bwt_inverse, dk_block_decode, dk_dev_block_decode, dk_dev_batch_decode, dk_dev_bwt_inverse_packed,
+ * dk_dev_packed_decode, dk_raw_block_decode, dk_dc_decode, and dk_capacity, dk_last_error, dk_last_consumed, statistics and profiling -- with
+ * the results and return codes of a full context, DK_MODEL_ANYBYTE included.
+ * Refused: every entry point that sorts suffixes, builds a BWT or DC arrays or encodes (host, dk_dev_, batch and packed forms), and the
+ * dk_dbg_ entries that take the workspace: DK_E_ARG, dk_last_error names the entry, nothing is allocated, launched or copied, and the
+ * context stays usable. */
+int dk_ctx_create_decoder(int hip_device, size_t max_n, size_t max_blocks, dk_ctx **out);
+/* DK_CTX_FULL or DK_CTX_DECODER (DK_E_ARG for a null context) */
+int dk_ctx_purpose(const dk_ctx *ctx);
+/* the workspace dk_ctx_create (DK_CTX_FULL; max_blocks ignored) / dk_ctx_create_decoder would allocate; needs no GPU; 0 for bad arguments */
+size_t dk_workspace_bytes(int purpose, size_t max_n, size_t max_blocks);
 void dk_ctx_destroy(dk_ctx *ctx);
 /* saca::Constructor::capacity src/saca.rs:363-365 */
 size_t dk_capacity(const dk_ctx *ctx);
@@ -152,7 +171,7 @@ int dk_batch_finish(dk_batch *batch);
  * Per block, every result equals the single-block entry point's (src/saca.rs:368-378 for L / origin, src/block/dc.rs:41-91 for the DC arrays
  * and the coded stream; the reference treats every block as self-contained, src/block/dc.rs:30-37,53).  A block still unresolved after the
  * pack's round limit (long repeats, e.g. two identical halves) is re-run alone through the single-block path (DK_ROUTE_PACKED_GUARD).
- * DK_E_ARG: count == 0, count > DK_PACKED_MAX_BLOCKS, any n[i] == 0 or > DK_PACKED_MAX_BLOCK_BYTES, sum of n > dk_capacity, null pointers. */
+ * DK_E_ARG: count == 0, count > DK_PACKED_MAX_BLOCKS (on a decoder context: > its max_blocks), any n[i] == 0 or > DK_PACKED_MAX_BLOCK_BYTES, sum of n > dk_capacity, null pointers. */
 #define DK_PACKED_MAX_BLOCKS 65536
 #define DK_PACKED_MAX_BLOCK_BYTES (1u << 24)
 /* L of block i at d_bwt_out[off_i, off_i + n[i]), origin[i] (host, count entries) as from dk_dev_bwt_forward */
@@ -253,7 +272,7 @@ typedef struct dk_stats {
     int16_t entropy_l3_numa;  /* memory node of that group (-1: none claimed / unknown) ... */
     int16_t gpu_numa;         /* ... and of the context's GPU (/sys/bus/pci/devices/<bdf>/numa_node; -1: unknown): the coder looks for its group there first */
     uint64_t ws_peak_bytes;   /* most the context's device workspace has held at once since dk_ctx_create ... */
-    uint64_t ws_size_bytes;   /* ... and its size (about 69.4 x the capacity + 64 MiB) */
+    uint64_t ws_size_bytes;   /* ... and its size = dk_workspace_bytes of the context's purpose (full: about 69.4 x the capacity + 64 MiB) */
 } dk_stats;
 #define DK_ROUTE_SHORT_PREFIX 0x1u      /* the prefix probe shortened the initial sort's key */
 #define DK_ROUTE_NARROW_KEYS 0x2u       /* ... and its last pass left 32-bit keys */

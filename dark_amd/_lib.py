@@ -26,11 +26,12 @@ class Stats(C.Structure):
                 ("dc_runs", C.c_uint64), ("entropy_threads", C.c_uint32), ("entropy_l3_group", C.c_int32),
                 ("kernel_launches", C.c_uint32 * NUM_KERNEL_SLOTS), ("kernel_ms", C.c_double * NUM_KERNEL_SLOTS),
                 ("kernel_bytes", C.c_double * NUM_KERNEL_SLOTS), ("sa_route", C.c_uint32), ("entropy_l3_numa", C.c_int16), ("gpu_numa", C.c_int16),
-                ("ws_peak_bytes", C.c_uint64), ("ws_size_bytes", C.c_uint64)]
+                ("ws_peak_bytes", C.c_uint64), ("ws_size_bytes", C.c_uint64),
+                ("lcp_measured", C.c_uint64), ("lcp_bytes_compared", C.c_uint64), ("lcp_passes", C.c_uint32)]
 ROUTES = {"short_prefix": 0x1, "narrow_keys": 0x2, "text_round": 0x4, "isa_windows": 0x8, "isa_marked": 0x10, "isa_buckets": 0x20,
           "general_round": 0x40, "big_groups": 0x80, "inplace_rounds": 0x100, "pair_chains": 0x200, "lfirst": 0x400,
           "lfirst_big_round": 0x800, "lfirst_deep": 0x1000, "lfirst_fallback": 0x2000, "lfirst_giant": 0x4000, "period_round": 0x8000, "packed_pairs": 0x10000,
-          "packed_guard": 0x20000}
+          "packed_guard": 0x20000, "lcp_long": 0x40000, "lcp_giant": 0x80000}
 
 
 # every symbol include/dark_amd.h declares: name -> (restype, argtypes)
@@ -68,6 +69,12 @@ SIGNATURES = {
     "dk_dev_bwt_forward_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _u32p]),
     "dk_dev_suffix_array_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _u32p]),
     "dk_suffix_array_packed": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "dk_dev_lcp": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "dk_dev_suffix_array_lcp": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "dk_suffix_array_lcp": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "dk_dev_lcp_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp]),
+    "dk_dev_suffix_array_packed_lcp": (_i, [_vp, _vp, _sz, _vp, _vp, _vp]),
+    "dk_suffix_array_packed_lcp": (_i, [_vp, _vp, _sz, _vp, _vp, _vp]),
     "dk_dev_dc_encode_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _szp]),
     "dk_batch_push_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "dk_dev_packed_encode": (_i, [_vp, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i]),

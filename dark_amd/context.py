@@ -137,6 +137,26 @@ class Context:
         ends = np.cumsum([len(b) for b in keep])
         return [sa[e - len(b):e] for b, e in zip(keep, ends)]
 
+    def suffix_array_lcp(self, data):
+        """(suffix array, LCP array): LCP[0] = 0, LCP[i] = leading bytes the suffixes SA[i-1] and SA[i] share (dk_suffix_array_lcp)"""
+        t = as_u8(data)
+        sa = np.empty(len(t), dtype=np.uint32)
+        lcp = np.empty(len(t), dtype=np.uint32)
+        self._ck(self._lib.dk_suffix_array_lcp(self._h, _ptr(t), len(t), _ptr(sa), _ptr(lcp)))
+        return sa, lcp
+
+    def suffix_array_packed_lcp(self, blocks):
+        """(suffix array, LCP array) of every block, all of them from one segmented device pass (dk_suffix_array_packed_lcp)"""
+        keep = [as_u8(b) for b in blocks]
+        count = len(keep)
+        ns = (C.c_size_t * max(count, 1))(*[len(b) for b in keep])
+        t = np.concatenate(keep) if count else np.zeros(0, dtype=np.uint8)
+        sa = np.empty(len(t), dtype=np.uint32)
+        lcp = np.empty(len(t), dtype=np.uint32)
+        self._ck(self._lib.dk_suffix_array_packed_lcp(self._h, _ptr(t), count, ns, _ptr(sa), _ptr(lcp)))
+        ends = np.cumsum([len(b) for b in keep])
+        return [(sa[e - len(b):e], lcp[e - len(b):e]) for b, e in zip(keep, ends)]
+
     def bwt_forward(self, data):
         t = as_u8(data)
         out = np.empty(len(t), dtype=np.uint8)
@@ -268,6 +288,31 @@ class Context:
                                                       origin.ctypes.data_as(C.POINTER(C.c_uint32))))
         return [int(o) for o in origin[:count]]
 
+    # ---- LCP arrays (uint32 device tensors) ----
+    def dev_lcp(self, d_in, n, d_sa, d_lcp_out):
+        """d_lcp_out[i] = leading bytes the suffixes d_sa[i-1] and d_sa[i] of d_in[0, n) share, d_lcp_out[0] = 0"""
+        _inputs_ready(d_in, d_sa)
+        self._ck(self._lib.dk_dev_lcp(self._h, _ptr(d_in), n, _ptr(d_sa), _ptr(d_lcp_out)))
+
+    def dev_suffix_array_lcp(self, d_in, n, d_sa_out, d_lcp_out):
+        """dev_suffix_array, then dev_lcp on its result, in one call"""
+        _inputs_ready(d_in)
+        self._ck(self._lib.dk_dev_suffix_array_lcp(self._h, _ptr(d_in), n, _ptr(d_sa_out), _ptr(d_lcp_out)))
+
+    def dev_lcp_packed(self, d_in, sizes, d_sa, d_lcp_out):
+        """the LCP array of every block of a pack (layout of dev_suffix_array_packed: entries of d_sa local to their block) in one pass"""
+        _inputs_ready(d_in, d_sa)
+        count = len(sizes)
+        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
+        self._ck(self._lib.dk_dev_lcp_packed(self._h, _ptr(d_in), count, ns, _ptr(d_sa), _ptr(d_lcp_out)))
+
+    def dev_suffix_array_packed_lcp(self, d_in, sizes, d_sa_out, d_lcp_out):
+        """dev_suffix_array_packed (without L), then the LCP arrays from the same sort's ranks, in one call"""
+        _inputs_ready(d_in)
+        count = len(sizes)
+        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
+        self._ck(self._lib.dk_dev_suffix_array_packed_lcp(self._h, _ptr(d_in), count, ns, _ptr(d_sa_out), _ptr(d_lcp_out)))
+
     def dev_dc_encode_packed(self, d_bwt, sizes, d_dist, d_sym, d_rank=None):
         """DC arrays of a packed L: block i's entries at [off_i, off_i + m_i); returns (list of init tables, list of m)"""
         _inputs_ready(d_bwt)
@@ -368,7 +413,8 @@ class Context:
         self._ck(self._lib.dk_get_stats(self._h, C.byref(st)))
         out = {k: getattr(st, k) for k in ("ms_h2d", "ms_sa", "ms_bwt", "ms_dc", "ms_d2h", "ms_entropy", "ms_ibwt",
                                            "ms_total", "rounds", "sort_passes", "sorted_elements", "dc_runs",
-                                           "entropy_threads", "entropy_l3_group", "entropy_l3_numa", "gpu_numa", "ws_peak_bytes", "ws_size_bytes")}
+                                           "entropy_threads", "entropy_l3_group", "entropy_l3_numa", "gpu_numa", "ws_peak_bytes", "ws_size_bytes",
+                                           "lcp_measured", "lcp_bytes_compared", "lcp_passes")}
         kernels = {}
         for i in range(_lib.NUM_KERNEL_SLOTS):
             name = self._lib.dk_kernel_name(i)

@@ -69,6 +69,10 @@ size_t workspace_bytes(size_t max_n) {
     // The packed suffix arrays (dk_suffix_array_packed: text n, SA 4 n, the pack's temporaries 32 n + the sort's 1.25 n) stay below 39 n.  Their guard
     // runs after those temporaries are released, straight into the block's stretch of the output: text + SA 5 n and the single-block sort
     // 63.4 n_i (no L from the sort, so the L-first path and its 23 MiB never run) = at most 68.4 n.
+    // The LCP pass (lcp.hip: lcp_device) runs after the sort's temporaries are released: Phi / PLCP 4 n in place, tile aggregates n / 1024, and
+    // two lists sized from what is left (at most n + 1 MiB + 32 KiB).  Around it SA 4 n and LCP 4 n (+ text n) in the host-pointer form: below 15 n.
+    // In dk_dev_suffix_array_packed_lcp the 4 n of Phi are held across the packed sort (32 n + 1.25 n) and its guard (63.4 n_i): at most 67.4 n.
+    // tests/test_gpu_lcp.py checks peak <= size for the single and the packed one-call forms on contexts sized exactly to their input.
     // tests/test_gpu_parity.py::test_workspace_accounting checks peak <= size on contexts sized exactly to their block, and
     // tests/test_gpu_fullsize.py checks the n-proportional term where the constant is negligible (peak - 64 MiB <= 69.4 n at 1e8 bytes).
     const size_t sort_temporaries = 62 * max_n + max_n / 8, io = 6 * max_n, on_top = max_n / 4 + max_n;
@@ -591,8 +595,9 @@ int check_pack(dk_ctx *ctx, size_t count, const size_t *n, std::vector<uint32_t>
 
 // L of every block into d_bwt and the origins into h_origin (host, count): one segmented pass, then the guard's blocks one by one.
 // d_sa (may be null): the suffix arrays too, from the same pass (dk_dev_suffix_array_packed); then d_bwt / d_origin may both be null.
+// d_phi (may be null, only with d_sa): Phi of the pack for the LCP pass -- from the sort's rank, and for the guard's blocks from their suffix arrays.
 int packed_forward(dk_ctx *ctx, const uint8_t *d_in, const std::vector<uint32_t> &off, const uint32_t *d_off, uint8_t *d_bwt, uint32_t *d_origin,
-                   std::vector<std::pair<size_t, uint32_t>> *fixed, uint32_t *d_sa = nullptr) {
+                   std::vector<std::pair<size_t, uint32_t>> *fixed, uint32_t *d_sa = nullptr, uint32_t *d_phi = nullptr) {
     hipStream_t st = ctx->stream;
     const size_t count = off.size() - 1, total = off.back();
     Timer t;
@@ -602,7 +607,7 @@ int packed_forward(dk_ctx *ctx, const uint8_t *d_in, const std::vector<uint32_t>
     size_t unresolved = 0;
     // (tuning build: DK_PACKED_ROUNDS lowers the limit, clamped to [0, PACKED_MAX_ROUNDS] -- a test hook that sends blocks through the guard)
     const int max_rounds = std::max(0, std::min(PACKED_MAX_ROUNDS, DK_KNOB("DK_PACKED_ROUNDS", PACKED_MAX_ROUNDS)));
-    if (d_sa) DK_TRY(packed_sa_device(ctx, d_in, d_off, count, total, d_sa, d_bwt, d_origin, d_guard, max_rounds, &unresolved));
+    if (d_sa) DK_TRY(packed_sa_device(ctx, d_in, d_off, count, total, d_sa, d_bwt, d_origin, d_guard, max_rounds, &unresolved, d_phi));
     else DK_TRY(packed_bwt_device(ctx, d_in, d_off, count, total, d_bwt, d_origin, d_guard, max_rounds, &unresolved));
     fixed->clear();
     if (unresolved) {
@@ -621,6 +626,7 @@ int packed_forward(dk_ctx *ctx, const uint8_t *d_in, const std::vector<uint32_t>
                 uint32_t *d_one = d_sa + off[i];
                 DK_TRY(suffix_array_device(ctx, d_in + off[i], n, d_one));
                 if (d_bwt) DK_TRY(bwt_gather_device(ctx, d_in + off[i], d_one, n, d_bwt + off[i], &origin));
+                if (d_phi) DK_TRY(lcp_phi_block_device(ctx, d_sa, d_off, count, off[i], off[i + 1], d_phi));
             } else {
                 uint32_t *d_one = ctx->ws_alloc<uint32_t>(n);
                 if (!d_one) return DK_E_NOMEM;
@@ -1012,6 +1018,150 @@ int dk_dev_packed_decode(dk_ctx *ctx, int model_id, size_t count, const uint8_t 
     Timer t3;
     DK_TRY(packed_ibwt_device(ctx, d_bwt, off, origin.data(), d_out));
     ctx->stats.ms_ibwt = t3.ms();
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+// ---- LCP arrays (csrc/lcp.hip) ----------------------------------------------------------------------
+}  // extern "C"
+
+namespace {
+// a single block is a pack of one: its offsets table {0, n} is written by two fills (no host memory behind an asynchronous copy)
+int lcp_single(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uint32_t *d_sa, uint32_t *d_lcp) {
+    uint32_t *d_off = ctx->ws_alloc<uint32_t>(2);
+    if (!d_off) return DK_E_NOMEM;
+    DK_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_off), 0, 1, ctx->stream));
+    DK_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_off + 1), static_cast<int>(n), 1, ctx->stream));
+    return lcp_device(ctx, d_text, d_off, 1, n, d_sa, d_lcp);
+}
+}  // namespace
+
+extern "C" {
+
+int dk_dev_lcp(dk_ctx *ctx, const uint8_t *d_in, size_t n, const uint32_t *d_sa, uint32_t *d_lcp_out) {
+    DK_TRY(begin_call(ctx, "dk_dev_lcp"));
+    ScopedCall sc(ctx);
+    if (!d_in || !d_sa || !d_lcp_out) return ctx->fail(DK_E_ARG, "null pointer");
+    DK_TRY(check_n(ctx, n));
+    Timer t;
+    ctx->stats.sa_route = 0;
+    DK_TRY(lcp_single(ctx, d_in, n, d_sa, d_lcp_out));
+    DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_dev_suffix_array_lcp(dk_ctx *ctx, const uint8_t *d_in, size_t n, uint32_t *d_sa_out, uint32_t *d_lcp_out) {
+    DK_TRY(begin_call(ctx, "dk_dev_suffix_array_lcp"));
+    ScopedCall sc(ctx);
+    if (!d_in || !d_sa_out || !d_lcp_out) return ctx->fail(DK_E_ARG, "null pointer");
+    DK_TRY(check_n(ctx, n));
+    Timer t;
+    const size_t mark = ctx->ws_mark();
+    DK_TRY(suffix_array_device(ctx, d_in, n, d_sa_out));
+    ctx->ws_release(mark);  // the LCP pass takes the place of the sort's temporaries
+    DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->stats.ms_sa = t.ms();
+    DK_TRY(lcp_single(ctx, d_in, n, d_sa_out, d_lcp_out));
+    DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_suffix_array_lcp(dk_ctx *ctx, const uint8_t *in, size_t n, uint32_t *sa_out, uint32_t *lcp_out) {
+    DK_TRY(begin_call(ctx, "dk_suffix_array_lcp"));
+    ScopedCall sc(ctx);
+    if (!in || !sa_out || !lcp_out) return ctx->fail(DK_E_ARG, "null pointer");
+    DK_TRY(check_n(ctx, n));
+    Timer t;
+    hipStream_t st = ctx->stream;
+    uint8_t *d_text = ctx->ws_alloc<uint8_t>(n);
+    uint32_t *d_sa = ctx->ws_alloc<uint32_t>(n);
+    if (!d_text || !d_sa) return DK_E_NOMEM;
+    DK_HIP(ctx, hipMemcpyAsync(d_text, in, n, hipMemcpyHostToDevice, st));
+    const size_t mark = ctx->ws_mark();
+    DK_TRY(suffix_array_device(ctx, d_text, n, d_sa));
+    ctx->ws_release(mark);
+    uint32_t *d_lcp = ctx->ws_alloc<uint32_t>(n);  // (after the sort: its 63.4 n and the 9 n around it would not fit together)
+    if (!d_lcp) return DK_E_NOMEM;
+    DK_TRY(lcp_single(ctx, d_text, n, d_sa, d_lcp));
+    DK_HIP(ctx, hipMemcpyAsync(sa_out, d_sa, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    DK_HIP(ctx, hipMemcpyAsync(lcp_out, d_lcp, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    DK_HIP(ctx, hipStreamSynchronize(st));
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_dev_lcp_packed(dk_ctx *ctx, const uint8_t *d_in, size_t count, const size_t *n, const uint32_t *d_sa, uint32_t *d_lcp_out) {
+    DK_TRY(begin_call(ctx, "dk_dev_lcp_packed"));
+    ScopedCall sc(ctx);
+    if (!d_in || !n || !d_sa || !d_lcp_out) return ctx->fail(DK_E_ARG, "null pointer");
+    std::vector<uint32_t> off;
+    DK_TRY(check_pack(ctx, count, n, off));
+    Timer t;
+    hipStream_t st = ctx->stream;
+    uint32_t *d_off = ctx->ws_alloc<uint32_t>(count + 1);
+    if (!d_off) return DK_E_NOMEM;
+    DK_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    ctx->stats.sa_route = 0;
+    const int rc = lcp_device(ctx, d_in, d_off, count, off.back(), d_sa, d_lcp_out);
+    const hipError_t e = hipStreamSynchronize(st);  // (also on failure: the copy above reads `off`)
+    DK_TRY(rc);
+    DK_HIP(ctx, e);
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_dev_suffix_array_packed_lcp(dk_ctx *ctx, const uint8_t *d_in, size_t count, const size_t *n, uint32_t *d_sa_out, uint32_t *d_lcp_out) {
+    DK_TRY(begin_call(ctx, "dk_dev_suffix_array_packed_lcp"));
+    ScopedCall sc(ctx);
+    if (!d_in || !n || !d_sa_out || !d_lcp_out) return ctx->fail(DK_E_ARG, "null pointer");
+    std::vector<uint32_t> off;
+    DK_TRY(check_pack(ctx, count, n, off));
+    Timer t;
+    hipStream_t st = ctx->stream;
+    const size_t total = off.back();
+    uint32_t *d_off = ctx->ws_alloc<uint32_t>(count + 1), *d_phi = ctx->ws_alloc<uint32_t>(total);
+    if (!d_off || !d_phi) return DK_E_NOMEM;
+    DK_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    std::vector<std::pair<size_t, uint32_t>> fixed;
+    int rc = packed_forward(ctx, d_in, off, d_off, nullptr, nullptr, &fixed, d_sa_out, d_phi);
+    if (rc == DK_OK) rc = lcp_device(ctx, d_in, d_off, count, total, d_sa_out, d_lcp_out, d_phi);
+    const hipError_t e = hipStreamSynchronize(st);
+    DK_TRY(rc);
+    DK_HIP(ctx, e);
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_suffix_array_packed_lcp(dk_ctx *ctx, const uint8_t *in, size_t count, const size_t *n, uint32_t *sa_out, uint32_t *lcp_out) {
+    DK_TRY(begin_call(ctx, "dk_suffix_array_packed_lcp"));
+    ScopedCall sc(ctx);
+    if (!in || !n || !sa_out || !lcp_out) return ctx->fail(DK_E_ARG, "null pointer");
+    std::vector<uint32_t> off;
+    DK_TRY(check_pack(ctx, count, n, off));
+    Timer t;
+    hipStream_t st = ctx->stream;
+    const size_t total = off.back();
+    uint8_t *d_text = ctx->ws_alloc<uint8_t>(total);
+    uint32_t *d_sa = ctx->ws_alloc<uint32_t>(total), *d_phi = ctx->ws_alloc<uint32_t>(total), *d_off = ctx->ws_alloc<uint32_t>(count + 1);
+    if (!d_text || !d_sa || !d_phi || !d_off) return DK_E_NOMEM;
+    DK_HIP(ctx, hipMemcpyAsync(d_text, in, total, hipMemcpyHostToDevice, st));
+    DK_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    std::vector<std::pair<size_t, uint32_t>> fixed;
+    int rc = packed_forward(ctx, d_text, off, d_off, nullptr, nullptr, &fixed, d_sa, d_phi);
+    // (after the sort and its guard: text, SA and Phi are 9 total, and a guarded block's sort 63.4 n_i with n_i <= 2^24 -- the constant term covers
+    //  the 2.8 n_i by which a pack that is one such block would pass 69.6 total)
+    uint32_t *d_lcp = rc == DK_OK ? ctx->ws_alloc<uint32_t>(total) : nullptr;
+    if (rc == DK_OK && !d_lcp) rc = DK_E_NOMEM;
+    if (rc == DK_OK) rc = lcp_device(ctx, d_text, d_off, count, total, d_sa, d_lcp, d_phi);
+    if (rc == DK_OK) {
+        DK_HIP(ctx, hipMemcpyAsync(sa_out, d_sa, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        DK_HIP(ctx, hipMemcpyAsync(lcp_out, d_lcp, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
+    const hipError_t e = hipStreamSynchronize(st);
+    DK_TRY(rc);
+    DK_HIP(ctx, e);
     ctx->stats.ms_total = t.ms();
     return DK_OK;
 }

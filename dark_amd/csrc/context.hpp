@@ -231,8 +231,21 @@ int packed_bwt_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off,
                       uint32_t *d_guard, int max_rounds, size_t *guarded);
 // packed_sa_device: the same sort, then block i's suffix array at d_sa[off_i, off_i + n_i), entries local to the block; d_bwt / d_origin (both
 // or neither) as from packed_bwt_device, written by the same kernel.  Guarded blocks' stretches are NOT valid, as above.
+// d_phi (may be null; total words): Phi for the LCP pass, from the sort's rank before it is released (lcp_phi_from_rank_device).
 int packed_sa_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, size_t count, size_t total, uint32_t *d_sa, uint8_t *d_bwt,
-                     uint32_t *d_origin, uint32_t *d_guard, int max_rounds, size_t *guarded);
+                     uint32_t *d_origin, uint32_t *d_guard, int max_rounds, size_t *guarded, uint32_t *d_phi = nullptr);
+// lcp.hip: d_lcp[i] = common prefix of the suffixes at slots i - 1 and i of their block, 0 at a block's first slot; layout of
+// d_text / d_sa / d_lcp as in packed_sa_device (a single block: count = 1, d_off = {0, n}).  DK_E_ARG, with d_lcp untouched, for an entry of d_sa
+// outside its block.  Synchronises (the lists' counters are read back); ORs DK_ROUTE_LCP_* into stats.sa_route.  Takes 4 total + total / 1024
+// bytes of workspace and sizes its two lists from what is left; releases all of it.
+// d_phi_ready (may be null; total words, the caller's): Phi as lcp_phi_from_rank_device / lcp_phi_block_device left it -- d_sa is not checked then.
+int lcp_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, size_t count, size_t total, const uint32_t *d_sa, uint32_t *d_lcp,
+               uint32_t *d_phi_ready = nullptr);
+// Phi of the whole pack from the packed sort's rank (the inverse suffix array) and the suffix arrays k_pk_emit wrote from it; the stretches of
+// guarded blocks hold nothing useful afterwards ...
+int lcp_phi_from_rank_device(dk_ctx *ctx, const uint32_t *d_rank, const uint32_t *d_sa, const uint32_t *d_off, size_t count, size_t total, uint32_t *d_phi);
+// ... and are redone here, one block's slots [lo, hi) at a time, from the suffix array the guard has written
+int lcp_phi_block_device(dk_ctx *ctx, const uint32_t *d_sa, const uint32_t *d_off, size_t count, size_t lo, size_t hi, uint32_t *d_phi);
 // packed_dc_device: the DC arrays of every block of a packed L.  compact: block i's entries at [rb_i, rb_i + m_i) (global run order, rb on the
 // device in d_rb[0 .. count], d_rb[count] = all runs); otherwise at [off_i, off_i + m_i).  d_m / d_flags: count words, d_init: count x 256.
 int packed_dc_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, bool compact, uint32_t *d_dist,

@@ -137,4 +137,14 @@ __device__ __forceinline__ uint32_t block_excl_max(uint32_t v, uint32_t *s_tmp, 
     return base > prev ? base : prev;
 }
 
+// Packed layouts (packed.hip, lcp.hip): block of position p = the largest i with off[i] <= p (off[0] = 0 <= p < off[count])
+__device__ __forceinline__ uint32_t seg_of(const uint32_t *__restrict__ off, uint32_t count, uint32_t p) {
+    uint32_t lo = 0, hi = count;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (off[mid] <= p) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
 }  // namespace dk

@@ -85,6 +85,16 @@ struct Mail {
         uint32_t ibwt_bad;        // k_pib_check, then k_pib_copy / k_pib_emit (filled with 0xFF before the first): lowest corrupt block, IB_END: none
         uint32_t ibwt_pending;    // device only: k_ibwt_jump's counter in the packed inverse (k_pib_check decides instead; nobody reads it)
     } packed;
+
+    // ---- LCP arrays (lcp.hip; lcp_device clears the group before its first kernel and reads it back as one, once per pass over the lists) -------
+    struct Lcp {
+        uint32_t bad_sa;          // k_lcp_phi: stores 1 for a suffix-array entry outside its block (racing stores all write 1).  Host: DK_E_ARG
+        struct Lists {            // cleared again by lcp_device before every further pass
+            uint32_t long_count;  // k_lcp_measure (atomicAdd): positions still equal at the lane's cap, listed or not (a full list: the excess says
+                                  // "run again"); read on the device by k_lcp_wave, which walks min(long_count, capacity) entries
+            uint32_t giant_count; // k_lcp_wave (atomicAdd): positions still equal at the wave's cap, as above; the host sizes k_lcp_giant's walk by it
+        } lists;
+    } lcp;
 };
 static_assert(sizeof(Mail) <= 4096, "the mailbox is one page");
 static_assert((LIVE_RING & (LIVE_RING - 1)) == 0, "rounds index the ring with a mask");

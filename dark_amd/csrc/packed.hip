@@ -45,16 +45,6 @@ constexpr int PDC_TILE = 4096;              // runs per wave in k_pdc_summary / 
 constexpr int PDC_WAVES = 4;
 constexpr int PDC_MAX_CHUNKS = 256;
 
-// block of position p: the largest i with off[i] <= p (off[0] = 0 <= p < off[count])
-__device__ __forceinline__ uint32_t seg_of(const uint32_t *__restrict__ off, uint32_t count, uint32_t p) {
-    uint32_t lo = 0, hi = count;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (off[mid] <= p) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // ---- suffix sort ------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_pk_hist(const uint8_t *__restrict__ t, size_t n, uint32_t *__restrict__ present) {
     __shared__ uint32_t s[256];
@@ -565,7 +555,7 @@ int packed_bwt_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off,
 }
 
 int packed_sa_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, size_t count, size_t total, uint32_t *d_sa, uint8_t *d_bwt,
-                     uint32_t *d_origin, uint32_t *d_guard, int max_rounds, size_t *guarded) {
+                     uint32_t *d_origin, uint32_t *d_guard, int max_rounds, size_t *guarded, uint32_t *d_phi) {
     const size_t mark = ctx->ws_mark();
     const uint32_t *rank = nullptr;
     DK_TRY(packed_sort_device(ctx, d_text, d_off, count, total, d_guard, max_rounds, &rank, guarded));
@@ -575,6 +565,7 @@ int packed_sa_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, 
             d_text, d_off, static_cast<uint32_t>(count), static_cast<uint32_t>(total), rank, d_sa, d_bwt, d_origin);
     }
     DK_HIP(ctx, hipGetLastError());
+    if (d_phi) DK_TRY(lcp_phi_from_rank_device(ctx, rank, d_sa, d_off, count, total, d_phi));  // rank is the inverse suffix array: no second one
     ctx->ws_release(mark);
     return DK_OK;
 }

@@ -3,7 +3,8 @@ from .context import Context
 
 
 class Constructor:
-    """saca::Constructor: `new(max_n)`, `capacity()`, `compute(input) -> suffix array`; `compute_packed(inputs)` is this library's packed form."""
+    """saca::Constructor: `new(max_n)`, `capacity()`, `compute(input) -> suffix array`; `compute_packed(inputs)` is this library's packed form; `compute_lcp` /
+    `compute_packed_lcp` give the LCP arrays with the suffix arrays."""
 
     def __init__(self, max_n, device=0):
         self._ctx = Context(max_n, device)
@@ -24,6 +25,19 @@ class Constructor:
         if total > self.capacity():
             raise ValueError("Constructor sized for %d bytes got a pack of %d" % (self.capacity(), total))
         return self._ctx.suffix_array_packed(inputs)
+
+    def compute_lcp(self, data):
+        """compute, and the LCP array with it: (suffix array, LCP array), LCP[0] = 0"""
+        if len(data) != self._n:
+            raise ValueError("Constructor sized for %d bytes got %d" % (self._n, len(data)))
+        return self._ctx.suffix_array_lcp(data)
+
+    def compute_packed_lcp(self, inputs):
+        """compute_packed, and every input's LCP array with it: a list of (suffix array, LCP array), from one segmented device pass"""
+        total = sum(len(x) for x in inputs)
+        if total > self.capacity():
+            raise ValueError("Constructor sized for %d bytes got a pack of %d" % (self.capacity(), total))
+        return self._ctx.suffix_array_packed_lcp(inputs)
 
     def context(self):
         """the analogue of reuse(): the device workspace is lent to the later stages through the context"""

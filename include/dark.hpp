@@ -85,10 +85,42 @@ public:
         }
         return out;
     }
+    // compute, and the LCP array with it (dk_suffix_array_lcp): lcp[0] = 0, lcp[i] = leading symbols the suffixes sa[i-1] and sa[i] share.
+    // Nothing in the reference corresponds; the suffix array is the one compute returns.
+    std::pair<const std::vector<Suffix> &, const std::vector<uint32_t> &> compute_lcp(const std::vector<Symbol> &input) {
+        if (input.size() != n_) throw Error(DK_E_ARG, "assertion failed: input.len() == self.n");
+        lcp_.resize(n_);
+        int rc = dk_suffix_array_lcp(ctx_.get(), input.data(), input.size(), suffixes_.data(), lcp_.data());
+        if (rc != DK_OK) throw Error(rc, ctx_.error());
+        return {suffixes_, lcp_};
+    }
+    // compute_packed with every input's LCP array (dk_suffix_array_packed_lcp): result[i] = (suffix array, LCP array) of inputs[i]
+    std::vector<std::pair<std::vector<Suffix>, std::vector<uint32_t>>> compute_packed_lcp(const std::vector<std::vector<Symbol>> &inputs) {
+        std::vector<size_t> sizes;
+        std::vector<Symbol> text;
+        for (const auto &in : inputs) {
+            sizes.push_back(in.size());
+            text.insert(text.end(), in.begin(), in.end());
+        }
+        if (text.size() > capacity()) throw Error(DK_E_ARG, "assertion failed: total input length <= self.capacity()");
+        std::vector<Suffix> all(text.size());
+        std::vector<uint32_t> lcp(text.size());
+        int rc = dk_suffix_array_packed_lcp(ctx_.get(), text.data(), sizes.size(), sizes.data(), all.data(), lcp.data());
+        if (rc != DK_OK) throw Error(rc, ctx_.error());
+        std::vector<std::pair<std::vector<Suffix>, std::vector<uint32_t>>> out;
+        size_t at = 0;
+        for (size_t n : sizes) {
+            const auto lo = static_cast<std::ptrdiff_t>(at), hi = static_cast<std::ptrdiff_t>(at + n);
+            out.emplace_back(std::vector<Suffix>(all.begin() + lo, all.begin() + hi), std::vector<uint32_t>(lcp.begin() + lo, lcp.begin() + hi));
+            at += n;
+        }
+        return out;
+    }
     detail::Ctx &context() { return ctx_; }  // plays reuse(): later stages share the device workspace through it
 private:
     detail::Ctx ctx_;
     std::vector<Suffix> suffixes_;
+    std::vector<uint32_t> lcp_;
     size_t n_;
 };
 }  // namespace saca

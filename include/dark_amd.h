@@ -67,7 +67,7 @@ int dk_ctx_create(int hip_device, size_t max_n, dk_ctx **out);
  * Served: dk_bwt_inverse, dk_dev_bwt_inverse, dk_block_decode, dk_dev_block_decode, dk_dev_batch_decode, dk_dev_bwt_inverse_packed,
  * dk_dev_packed_decode, dk_raw_block_decode, dk_dc_decode, and dk_capacity, dk_last_error, dk_last_consumed, statistics and profiling -- with
  * the results and return codes of a full context, DK_MODEL_ANYBYTE included.
- * Refused: every entry point that sorts suffixes, builds a BWT or DC arrays or encodes (host, dk_dev_, batch and packed forms), and the
+ * Refused: every entry point that sorts suffixes, builds a BWT, an LCP array or DC arrays or encodes (host, dk_dev_, batch and packed forms), and the
  * dk_dbg_ entries that take the workspace: DK_E_ARG, dk_last_error names the entry, nothing is allocated, launched or copied, and the
  * context stays usable. */
 int dk_ctx_create_decoder(int hip_device, size_t max_n, size_t max_blocks, dk_ctx **out);
@@ -184,6 +184,31 @@ int dk_dev_suffix_array_packed(dk_ctx *ctx, const uint8_t *d_in, size_t count, c
                                uint8_t *d_bwt_out, uint32_t *origin);
 /* the same from host memory (the reference's &[u8] inputs laid back to back): one upload, one pass, one download */
 int dk_suffix_array_packed(dk_ctx *ctx, const uint8_t *in, size_t count, const size_t *n, uint32_t *sa_out);
+/* ---- longest-common-prefix arrays (nothing in the reference corresponds: src/saca.rs stops at the suffix array) ---------------------------
+ * LCP[0] = 0; for i >= 1, LCP[i] = the number of leading bytes the suffixes SA[i-1] and SA[i] share.  No sentinel (the convention of
+ * src/saca.rs:105-113), so LCP[i] <= n - max(SA[i-1], SA[i]).  In a pack every block is on its own: a common prefix ends with the block of
+ * the shorter suffix, whatever the next block starts with.  Phi algorithm with irreducible positions, on the device.
+ * DK_E_ARG as for the suffix-array entries (null pointers, n == 0, n > dk_capacity, the pack checks, a decoder context), and for an entry of
+ * d_sa that is >= n (in a pack: >= n[i]) -- then nothing is written to d_lcp_out.  A d_sa whose entries are in range but which is not the
+ * suffix array of the text: the values written are unspecified, but the call returns, every value is <= n (n[i]), and nothing outside
+ * [0, n) of the text, d_sa and d_lcp_out is touched.
+ * full_ctx: a DK_CTX_FULL context.  (The parameter's name says so; a decoder context gets DK_E_ARG with the entry's name in dk_last_error.) */
+/* d_sa: the suffix array of d_in[0, n) (e.g. from dk_dev_suffix_array); d_lcp_out: n entries.  Any alignment of d_in; d_sa and d_lcp_out
+ * need the four bytes of their element only. */
+int dk_dev_lcp(dk_ctx *full_ctx, const uint8_t *d_in, size_t n, const uint32_t *d_sa, uint32_t *d_lcp_out);
+/* dk_dev_suffix_array, then dk_dev_lcp on its result, in one call (the sort's temporaries are released before the LCP pass takes workspace) */
+int dk_dev_suffix_array_lcp(dk_ctx *full_ctx, const uint8_t *d_in, size_t n, uint32_t *d_sa_out, uint32_t *d_lcp_out);
+/* the same from and to host memory: one upload, two downloads */
+int dk_suffix_array_lcp(dk_ctx *full_ctx, const uint8_t *in, size_t n, uint32_t *sa_out, uint32_t *lcp_out);
+/* Layout and limits of dk_dev_suffix_array_packed: block i's suffix array (entries local to the block) at d_sa[off_i, off_i + n[i]), its LCP
+ * array to d_lcp_out[off_i, off_i + n[i]), equal to what dk_dev_lcp gives for block i alone.  One pass for the whole pack: the launches do
+ * not grow with count. */
+int dk_dev_lcp_packed(dk_ctx *full_ctx, const uint8_t *d_in, size_t count, const size_t *n, const uint32_t *d_sa, uint32_t *d_lcp_out);
+/* dk_dev_suffix_array_packed (without L), then the LCP arrays, in one call.  The pass takes the packed sort's rank array as the inverse suffix
+ * array instead of deriving one; blocks that went through the guard are redone from the suffix arrays the guard wrote. */
+int dk_dev_suffix_array_packed_lcp(dk_ctx *full_ctx, const uint8_t *d_in, size_t count, const size_t *n, uint32_t *d_sa_out, uint32_t *d_lcp_out);
+/* the same from and to host memory (the layout of dk_suffix_array_packed): one upload, one pass, two downloads */
+int dk_suffix_array_packed_lcp(dk_ctx *full_ctx, const uint8_t *in, size_t count, const size_t *n, uint32_t *sa_out, uint32_t *lcp_out);
 /* DC arrays of a packed L: block i's entries at [off_i, off_i + m[i]) of d_dist / d_sym / d_rank (device, sum of n entries each; d_rank may
  * be NULL), init (host, count x 256: block i's table at init[256 i]) and m (host, count) as from dk_dev_dc_encode */
 int dk_dev_dc_encode_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, const size_t *n, uint32_t *init, uint32_t *d_dist, uint8_t *d_sym,
@@ -273,6 +298,10 @@ typedef struct dk_stats {
     int16_t gpu_numa;         /* ... and of the context's GPU (/sys/bus/pci/devices/<bdf>/numa_node; -1: unknown): the coder looks for its group there first */
     uint64_t ws_peak_bytes;   /* most the context's device workspace has held at once since dk_ctx_create ... */
     uint64_t ws_size_bytes;   /* ... and its size = dk_workspace_bytes of the context's purpose (full: about 69.4 x the capacity + 64 MiB) */
+    /* the last LCP pass on this context (dk_dev_lcp and the other *_lcp entries) */
+    uint64_t lcp_measured;        /* positions whose common prefix was measured, i.e. irreducible ones (counted only while profiling is enabled) ... */
+    uint64_t lcp_bytes_compared;  /* ... and the bytes compared for them */
+    uint32_t lcp_passes;          /* passes over the lists of long common prefixes: 1 unless a list was full */
 } dk_stats;
 #define DK_ROUTE_SHORT_PREFIX 0x1u      /* the prefix probe shortened the initial sort's key */
 #define DK_ROUTE_NARROW_KEYS 0x2u       /* ... and its last pass left 32-bit keys */
@@ -294,6 +323,8 @@ typedef struct dk_stats {
 #define DK_ROUTE_PERIOD_ROUND 0x8000u    /* a period round ran: suffixes inside stretches of one short period (runs, (ab)^n, zero padding) placed by where the stretch ends */
 #define DK_ROUTE_PACKED_PAIRS 0x10000u   /* the initial sort moved packed pairs: key, carried code and position in one 64-bit word (at most 32 key bits, small alphabets) */
 #define DK_ROUTE_PACKED_GUARD 0x20000u   /* packed path: at least one block was still unresolved after the pack's round limit and went through the single-block path */
+#define DK_ROUTE_LCP_LONG 0x40000u       /* LCP pass: at least one position was still equal at the lane's cap (256 bytes) and went to the wave kernel */
+#define DK_ROUTE_LCP_GIANT 0x80000u      /* ... and at least one was still equal at the wave's cap (64 KiB) and was measured by the whole grid */
 /* enable (1) / disable (0) HIP-event bracketing of every kernel launch on the context's stream */
 int dk_set_profiling(dk_ctx *ctx, int enabled);
 int dk_stats_reset(dk_ctx *ctx);

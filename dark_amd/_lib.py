@@ -16,6 +16,7 @@ MODEL_IDS.update({name + "+ff": mid | DK_MODEL_ANYBYTE for name, mid in list(MOD
 NUM_KERNEL_SLOTS = 32
 DK_FLAG_HAS_FF, DK_FLAG_SINGLE_SYMBOL = 1, 2
 DK_PACKED_MAX_BLOCKS, DK_PACKED_MAX_BLOCK_BYTES = 65536, 1 << 24
+SA_VERDICTS = {0: "ok", 1: "bad_range", 2: "not_permutation", 3: "bad_order"}  # DK_SA_OK ... DK_SA_BAD_ORDER
 PURPOSES = {"full": 0, "decoder": 1}  # DK_CTX_FULL, DK_CTX_DECODER
 
 
@@ -75,6 +76,12 @@ SIGNATURES = {
     "dk_dev_lcp_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp]),
     "dk_dev_suffix_array_packed_lcp": (_i, [_vp, _vp, _sz, _vp, _vp, _vp]),
     "dk_suffix_array_packed_lcp": (_i, [_vp, _vp, _sz, _vp, _vp, _vp]),
+    "dk_dev_sa_check": (_i, [_vp, _vp, _sz, _vp, _u32p, _u32p]),
+    "dk_sa_check": (_i, [_vp, _vp, _sz, _vp, _u32p, _u32p]),
+    "dk_dev_sa_check_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "dk_dev_sa_search": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "dk_sa_search": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "dk_dev_sa_search_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "dk_dev_dc_encode_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _szp]),
     "dk_batch_push_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "dk_dev_packed_encode": (_i, [_vp, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i]),

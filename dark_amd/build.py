@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_build")
 SO = os.path.join(HERE, "libdark_amd.so")
-SOURCES = ["abi.cpp", "context.cpp", "entropy.cpp", "bbb.cpp", "radix_sort.hip", "suffix_array.hip", "bwt.hip", "dc.hip", "packed.hip", "lcp.hip"]
+SOURCES = ["abi.cpp", "context.cpp", "entropy.cpp", "bbb.cpp", "radix_sort.hip", "suffix_array.hip", "bwt.hip", "dc.hip", "packed.hip", "lcp.hip", "sa_query.hip"]
 ARCH = "gfx950"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result", "--offload-arch=" + ARCH]
@@ -23,7 +23,7 @@ def _deps():
 
 SO_TUNING = os.path.join(HERE, "libdark_amd_tuning.so")
 # sources that hold A/B switches (DK_KNOB, csrc/context.hpp): the tuning build compiles them with -DDK_TUNING, everything else is shared
-TUNING_SOURCES = ("abi.cpp", "context.cpp", "radix_sort.hip", "suffix_array.hip", "bwt.hip", "lcp.hip")
+TUNING_SOURCES = ("abi.cpp", "context.cpp", "radix_sort.hip", "suffix_array.hip", "bwt.hip", "lcp.hip", "sa_query.hip")
 
 
 def build(force=False, verbose=False, tuning=False):

@@ -38,6 +38,17 @@ def as_u8(x):
     return np.frombuffer(bytes(x), dtype=np.uint8)
 
 
+def _pack_patterns(patterns):
+    """a list of byte strings -> (the bytes back to back, their lengths as size_t[], how many)"""
+    keep = [as_u8(p) for p in patterns]
+    npat = len(keep)
+    pat = np.concatenate(keep) if npat else np.zeros(0, dtype=np.uint8)
+    if len(pat) == 0:
+        pat = np.zeros(1, dtype=np.uint8)  # (never read: every pattern is empty)
+    lens = (C.c_size_t * max(npat, 1))(*[len(p) for p in keep])
+    return pat, lens, npat
+
+
 def model_id(m):
     if isinstance(m, str):
         if m not in _lib.MODEL_IDS:
@@ -156,6 +167,29 @@ class Context:
         self._ck(self._lib.dk_suffix_array_packed_lcp(self._h, _ptr(t), count, ns, _ptr(sa), _ptr(lcp)))
         ends = np.cumsum([len(b) for b in keep])
         return [(sa[e - len(b):e], lcp[e - len(b):e]) for b, e in zip(keep, ends)]
+
+    def sa_check(self, data, sa):
+        """is `sa` the suffix array of `data`?  -> (verdict, where): verdict one of _lib.SA_VERDICTS ("ok", "bad_range", "not_permutation",
+        "bad_order"), where = the lowest slot / text position at fault (len(data) with "ok") (dk_sa_check)"""
+        t = as_u8(data)
+        sa = np.ascontiguousarray(sa, dtype=np.uint32)
+        if len(sa) != len(t):
+            raise DarkError(_lib.DK_E_ARG, "%d entries for %d bytes" % (len(sa), len(t)))
+        verdict, where = C.c_uint32(0), C.c_uint32(0)
+        self._ck(self._lib.dk_sa_check(self._h, _ptr(t), len(t), _ptr(sa), C.byref(verdict), C.byref(where)))
+        return _lib.SA_VERDICTS[verdict.value], int(where.value)
+
+    def sa_search(self, data, sa, patterns):
+        """(lo, hi) per pattern, uint32 arrays: sa[lo[q]:hi[q]] are exactly the places patterns[q] occurs in `data`; lo == hi = the insertion
+        slot of a pattern that does not occur (dk_sa_search).  The suffix array is trusted: sa_check verifies one."""
+        t = as_u8(data)
+        sa = np.ascontiguousarray(sa, dtype=np.uint32)
+        if len(sa) != len(t):
+            raise DarkError(_lib.DK_E_ARG, "%d entries for %d bytes" % (len(sa), len(t)))
+        pat, lens, npat = _pack_patterns(patterns)
+        lo, hi = np.zeros(npat, dtype=np.uint32), np.zeros(npat, dtype=np.uint32)
+        self._ck(self._lib.dk_sa_search(self._h, _ptr(t), len(t), _ptr(sa), _ptr(pat), npat, lens, _ptr(lo), _ptr(hi)))
+        return lo, hi
 
     def bwt_forward(self, data):
         t = as_u8(data)
@@ -312,6 +346,43 @@ class Context:
         count = len(sizes)
         ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
         self._ck(self._lib.dk_dev_suffix_array_packed_lcp(self._h, _ptr(d_in), count, ns, _ptr(d_sa_out), _ptr(d_lcp_out)))
+
+    # ---- suffix-array check and search ----
+    def dev_sa_check(self, d_in, n, d_sa):
+        """is d_sa[0, n) the suffix array of d_in[0, n)?  -> (verdict, where) as from sa_check"""
+        _inputs_ready(d_in, d_sa)
+        verdict, where = C.c_uint32(0), C.c_uint32(0)
+        self._ck(self._lib.dk_dev_sa_check(self._h, _ptr(d_in), n, _ptr(d_sa), C.byref(verdict), C.byref(where)))
+        return _lib.SA_VERDICTS[verdict.value], int(where.value)
+
+    def dev_sa_check_packed(self, d_in, sizes, d_sa):
+        """every block of a pack (layout of dev_suffix_array_packed) in one pass -> a list of (verdict, where), where local to the block"""
+        _inputs_ready(d_in, d_sa)
+        count = len(sizes)
+        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
+        verdict, where = np.zeros(max(count, 1), dtype=np.uint32), np.zeros(max(count, 1), dtype=np.uint32)
+        self._ck(self._lib.dk_dev_sa_check_packed(self._h, _ptr(d_in), count, ns, _ptr(d_sa), _ptr(verdict), _ptr(where)))
+        return [(_lib.SA_VERDICTS[int(v)], int(w)) for v, w in zip(verdict[:count], where[:count])]
+
+    def dev_sa_search(self, d_in, n, d_sa, d_pat, pat_lens, d_lo, d_hi):
+        """pattern q = the next pat_lens[q] bytes of the uint8 device tensor d_pat; d_lo[q] / d_hi[q] (uint32 device tensors): d_sa[lo:hi] are its
+        occurrences in d_in[0, n)"""
+        _inputs_ready(d_in, d_sa, d_pat)
+        npat = len(pat_lens)
+        lens = (C.c_size_t * max(npat, 1))(*[int(m) for m in pat_lens])
+        self._ck(self._lib.dk_dev_sa_search(self._h, _ptr(d_in), n, _ptr(d_sa), _ptr(d_pat), npat, lens, _ptr(d_lo), _ptr(d_hi)))
+
+    def dev_sa_search_packed(self, d_in, sizes, d_sa, d_pat, pat_lens, pat_blocks, d_lo, d_hi):
+        """dev_sa_search in a pack: pattern q is searched in block pat_blocks[q], d_lo / d_hi are local to that block"""
+        _inputs_ready(d_in, d_sa, d_pat)
+        count, npat = len(sizes), len(pat_lens)
+        if len(pat_blocks) != npat:
+            raise DarkError(_lib.DK_E_ARG, "%d blocks for %d patterns" % (len(pat_blocks), npat))
+        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
+        lens = (C.c_size_t * max(npat, 1))(*[int(m) for m in pat_lens])
+        blocks = np.array(pat_blocks, dtype=np.int64).astype(np.uint32) if npat else np.zeros(1, np.uint32)
+        self._ck(self._lib.dk_dev_sa_search_packed(self._h, _ptr(d_in), count, ns, _ptr(d_sa), _ptr(d_pat), npat, lens, _ptr(blocks), _ptr(d_lo),
+                                                   _ptr(d_hi)))
 
     def dev_dc_encode_packed(self, d_bwt, sizes, d_dist, d_sym, d_rank=None):
         """DC arrays of a packed L: block i's entries at [off_i, off_i + m_i); returns (list of init tables, list of m)"""

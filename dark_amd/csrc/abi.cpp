@@ -73,6 +73,10 @@ size_t workspace_bytes(size_t max_n) {
     // two lists sized from what is left (at most n + 1 MiB + 32 KiB).  Around it SA 4 n and LCP 4 n (+ text n) in the host-pointer form: below 15 n.
     // In dk_dev_suffix_array_packed_lcp the 4 n of Phi are held across the packed sort (32 n + 1.25 n) and its guard (63.4 n_i): at most 67.4 n.
     // tests/test_gpu_lcp.py checks peak <= size for the single and the packed one-call forms on contexts sized exactly to their input.
+    // The suffix-array check (sa_query.hip: sa_check_device) takes the inverse array 4 n and 12 bytes per block, beside text and SA (5 n) in the
+    // host-pointer form: 9 n + 12 count <= 21 n.  The search takes 8 bytes per pattern; its host-pointer form, which also holds the patterns and
+    // two result words per pattern, refuses a batch that does not fit beside the 5 n (DK_E_ARG).  Both are far below the sort's peak, so this
+    // size does not grow for them; tests/test_gpu_sa_search.py checks peak <= size on contexts sized exactly to their input.
     // tests/test_gpu_parity.py::test_workspace_accounting checks peak <= size on contexts sized exactly to their block, and
     // tests/test_gpu_fullsize.py checks the n-proportional term where the constant is negligible (peak - 64 MiB <= 69.4 n at 1e8 bytes).
     const size_t sort_temporaries = 62 * max_n + max_n / 8, io = 6 * max_n, on_top = max_n / 4 + max_n;
@@ -1027,11 +1031,17 @@ int dk_dev_packed_decode(dk_ctx *ctx, int model_id, size_t count, const uint8_t 
 
 namespace {
 // a single block is a pack of one: its offsets table {0, n} is written by two fills (no host memory behind an asynchronous copy)
-int lcp_single(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uint32_t *d_sa, uint32_t *d_lcp) {
+int single_offsets(dk_ctx *ctx, size_t n, uint32_t **d_off_out) {
     uint32_t *d_off = ctx->ws_alloc<uint32_t>(2);
     if (!d_off) return DK_E_NOMEM;
     DK_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_off), 0, 1, ctx->stream));
     DK_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_off + 1), static_cast<int>(n), 1, ctx->stream));
+    *d_off_out = d_off;
+    return DK_OK;
+}
+int lcp_single(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uint32_t *d_sa, uint32_t *d_lcp) {
+    uint32_t *d_off = nullptr;
+    DK_TRY(single_offsets(ctx, n, &d_off));
     return lcp_device(ctx, d_text, d_off, 1, n, d_sa, d_lcp);
 }
 }  // namespace
@@ -1160,6 +1170,190 @@ int dk_suffix_array_packed_lcp(dk_ctx *ctx, const uint8_t *in, size_t count, con
         DK_HIP(ctx, hipMemcpyAsync(lcp_out, d_lcp, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     }
     const hipError_t e = hipStreamSynchronize(st);
+    DK_TRY(rc);
+    DK_HIP(ctx, e);
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+// ---- suffix-array check and search (csrc/sa_query.hip) -----------------------------------------------
+}  // extern "C"
+
+namespace {
+// the three words of every block (sa_check_device) -> the first kind that failed and where; where = n_i for a block that is in order
+int sa_check_run(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, const std::vector<uint32_t> &off, const uint32_t *d_sa, uint32_t *verdict,
+                 uint32_t *where) {
+    const size_t count = off.size() - 1;
+    std::vector<uint32_t> words(3 * count);
+    DK_TRY(sa_check_device(ctx, d_text, d_off, count, off.back(), d_sa, words.data()));
+    for (size_t i = 0; i < count; ++i) {
+        const uint32_t *w = &words[3 * i];
+        const uint32_t kind = w[0] != 0xFFFFFFFFu ? DK_SA_BAD_RANGE : w[1] != 0xFFFFFFFFu ? DK_SA_NOT_PERMUTATION : w[2] != 0xFFFFFFFFu ? DK_SA_BAD_ORDER : DK_SA_OK;
+        verdict[i] = kind;
+        where[i] = kind == DK_SA_OK ? off[i + 1] - off[i] : w[kind - 1];
+    }
+    return DK_OK;
+}
+
+// pattern offsets (npat + 1 words) from the caller's lengths, and the checks on the batch
+struct Patterns {
+    std::vector<uint32_t> off;
+    size_t longest = 0, shortest = ~size_t(0);
+    size_t bytes() const { return off.back(); }
+};
+int check_patterns(dk_ctx *ctx, size_t npat, const size_t *pat_len, const uint32_t *pat_block, size_t count, Patterns &p) {
+    if (!pat_len) return ctx->fail(DK_E_ARG, "null pointer");
+    if (npat > 0xFFFFFFFEull) return ctx->fail(DK_E_ARG, "%zu patterns in one call", npat);
+    p.off.assign(npat + 1, 0);
+    uint64_t total = 0;
+    for (size_t q = 0; q < npat; ++q) {
+        if (pat_block && pat_block[q] >= count) return ctx->fail(DK_E_ARG, "pattern %zu names block %u of %zu", q, pat_block[q], count);
+        total += pat_len[q];
+        if (pat_len[q] > 0xFFFFFFFFull || total > 0xFFFFFFFFull) return ctx->fail(DK_E_ARG, "the patterns hold more than 2^32 - 1 bytes together");
+        p.off[q + 1] = static_cast<uint32_t>(total);
+        p.longest = std::max(p.longest, pat_len[q]);
+        p.shortest = std::min(p.shortest, pat_len[q]);
+    }
+    return DK_OK;
+}
+// offsets and blocks to the workspace (8 bytes per pattern), then the two kernels.  Synchronises: the copies read the caller's and `p`'s host memory.
+int sa_search_run(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, const uint32_t *d_sa, const uint8_t *d_pat, const Patterns &p,
+                  const uint32_t *pat_block, uint32_t *d_lo, uint32_t *d_hi) {
+    hipStream_t st = ctx->stream;
+    const size_t npat = p.off.size() - 1;
+    uint32_t *d_pat_off = ctx->ws_alloc<uint32_t>(npat + 1), *d_pat_blk = pat_block ? ctx->ws_alloc<uint32_t>(npat) : nullptr;
+    if (!d_pat_off || (pat_block && !d_pat_blk)) return DK_E_NOMEM;
+    DK_HIP(ctx, hipMemcpyAsync(d_pat_off, p.off.data(), (npat + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    int rc = DK_OK;
+    if (pat_block) rc = ctx->hip_ok(hipMemcpyAsync(d_pat_blk, pat_block, npat * sizeof(uint32_t), hipMemcpyHostToDevice, st), "pattern blocks");
+    if (rc == DK_OK) rc = sa_search_device(ctx, d_text, d_off, d_sa, d_pat, d_pat_off, d_pat_blk, npat, p.longest, p.shortest, d_lo, d_hi);
+    const hipError_t e = hipStreamSynchronize(st);
+    DK_TRY(rc);
+    DK_HIP(ctx, e);
+    return DK_OK;
+}
+size_t ws_round(size_t bytes) { return (bytes + 255) & ~size_t(255); }
+}  // namespace
+
+extern "C" {
+
+int dk_dev_sa_check(dk_ctx *ctx, const uint8_t *d_in, size_t n, const uint32_t *d_sa, uint32_t *verdict, uint32_t *where) {
+    DK_TRY(begin_call(ctx, "dk_dev_sa_check"));
+    ScopedCall sc(ctx);
+    if (!d_in || !d_sa || !verdict || !where) return ctx->fail(DK_E_ARG, "null pointer");
+    DK_TRY(check_n(ctx, n));
+    Timer t;
+    uint32_t *d_off = nullptr;
+    DK_TRY(single_offsets(ctx, n, &d_off));
+    DK_TRY(sa_check_run(ctx, d_in, d_off, {0u, static_cast<uint32_t>(n)}, d_sa, verdict, where));
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_sa_check(dk_ctx *ctx, const uint8_t *in, size_t n, const uint32_t *sa, uint32_t *verdict, uint32_t *where) {
+    DK_TRY(begin_call(ctx, "dk_sa_check"));
+    ScopedCall sc(ctx);
+    if (!in || !sa || !verdict || !where) return ctx->fail(DK_E_ARG, "null pointer");
+    DK_TRY(check_n(ctx, n));
+    Timer t;
+    hipStream_t st = ctx->stream;
+    uint8_t *d_text = ctx->ws_alloc<uint8_t>(n);
+    uint32_t *d_sa = ctx->ws_alloc<uint32_t>(n), *d_off = nullptr;
+    if (!d_text || !d_sa) return DK_E_NOMEM;
+    DK_TRY(single_offsets(ctx, n, &d_off));
+    DK_HIP(ctx, hipMemcpyAsync(d_text, in, n, hipMemcpyHostToDevice, st));
+    DK_HIP(ctx, hipMemcpyAsync(d_sa, sa, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    DK_TRY(sa_check_run(ctx, d_text, d_off, {0u, static_cast<uint32_t>(n)}, d_sa, verdict, where));
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_dev_sa_check_packed(dk_ctx *ctx, const uint8_t *d_in, size_t count, const size_t *n, const uint32_t *d_sa, uint32_t *verdict, uint32_t *where) {
+    DK_TRY(begin_call(ctx, "dk_dev_sa_check_packed"));
+    ScopedCall sc(ctx);
+    if (!d_in || !n || !d_sa || !verdict || !where) return ctx->fail(DK_E_ARG, "null pointer");
+    std::vector<uint32_t> off;
+    DK_TRY(check_pack(ctx, count, n, off));
+    Timer t;
+    hipStream_t st = ctx->stream;
+    uint32_t *d_off = ctx->ws_alloc<uint32_t>(count + 1);
+    if (!d_off) return DK_E_NOMEM;
+    DK_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    const int rc = sa_check_run(ctx, d_in, d_off, off, d_sa, verdict, where);
+    const hipError_t e = hipStreamSynchronize(st);  // (also on failure: the copy above reads `off`)
+    DK_TRY(rc);
+    DK_HIP(ctx, e);
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_dev_sa_search(dk_ctx *ctx, const uint8_t *d_in, size_t n, const uint32_t *d_sa, const uint8_t *d_pat, size_t npat, const size_t *pat_len,
+                     uint32_t *d_lo, uint32_t *d_hi) {
+    DK_TRY(begin_call(ctx, "dk_dev_sa_search"));
+    ScopedCall sc(ctx);
+    if (!d_in || !d_sa) return ctx->fail(DK_E_ARG, "null pointer");
+    DK_TRY(check_n(ctx, n));
+    if (npat == 0) return DK_OK;
+    Timer t;
+    Patterns p;
+    DK_TRY(check_patterns(ctx, npat, pat_len, nullptr, 1, p));
+    if ((!d_pat && p.bytes()) || !d_lo || !d_hi) return ctx->fail(DK_E_ARG, "null pointer");
+    uint32_t *d_off = nullptr;
+    DK_TRY(single_offsets(ctx, n, &d_off));
+    DK_TRY(sa_search_run(ctx, d_in, d_off, d_sa, d_pat, p, nullptr, d_lo, d_hi));
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_sa_search(dk_ctx *ctx, const uint8_t *in, size_t n, const uint32_t *sa, const uint8_t *pat, size_t npat, const size_t *pat_len, uint32_t *lo,
+                 uint32_t *hi) {
+    DK_TRY(begin_call(ctx, "dk_sa_search"));
+    ScopedCall sc(ctx);
+    if (!in || !sa) return ctx->fail(DK_E_ARG, "null pointer");
+    DK_TRY(check_n(ctx, n));
+    if (npat == 0) return DK_OK;
+    Timer t;
+    Patterns p;
+    DK_TRY(check_patterns(ctx, npat, pat_len, nullptr, 1, p));
+    if ((!pat && p.bytes()) || !lo || !hi) return ctx->fail(DK_E_ARG, "null pointer");
+    // text n, SA 4 n, the two offsets of the block; then the patterns, their offsets and the two results
+    const size_t need = ws_round(n) + ws_round(4 * n) + 256 + ws_round(p.bytes()) + ws_round(4 * (npat + 1)) + 2 * ws_round(4 * npat);
+    if (need > ctx->ws_size) return ctx->fail(DK_E_ARG, "%zu patterns of %zu bytes and their offsets do not fit the workspace beside the block", npat, p.bytes());
+    hipStream_t st = ctx->stream;
+    uint8_t *d_text = ctx->ws_alloc<uint8_t>(n), *d_pat = ctx->ws_alloc<uint8_t>(std::max<size_t>(p.bytes(), 1));
+    uint32_t *d_sa = ctx->ws_alloc<uint32_t>(n), *d_lo = ctx->ws_alloc<uint32_t>(npat), *d_hi = ctx->ws_alloc<uint32_t>(npat), *d_off = nullptr;
+    if (!d_text || !d_pat || !d_sa || !d_lo || !d_hi) return DK_E_NOMEM;
+    DK_TRY(single_offsets(ctx, n, &d_off));
+    DK_HIP(ctx, hipMemcpyAsync(d_text, in, n, hipMemcpyHostToDevice, st));
+    DK_HIP(ctx, hipMemcpyAsync(d_sa, sa, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    if (p.bytes()) DK_HIP(ctx, hipMemcpyAsync(d_pat, pat, p.bytes(), hipMemcpyHostToDevice, st));
+    DK_TRY(sa_search_run(ctx, d_text, d_off, d_sa, d_pat, p, nullptr, d_lo, d_hi));
+    DK_HIP(ctx, hipMemcpyAsync(lo, d_lo, npat * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    DK_HIP(ctx, hipMemcpyAsync(hi, d_hi, npat * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    DK_HIP(ctx, hipStreamSynchronize(st));
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_dev_sa_search_packed(dk_ctx *ctx, const uint8_t *d_in, size_t count, const size_t *n, const uint32_t *d_sa, const uint8_t *d_pat, size_t npat,
+                            const size_t *pat_len, const uint32_t *pat_block, uint32_t *d_lo, uint32_t *d_hi) {
+    DK_TRY(begin_call(ctx, "dk_dev_sa_search_packed"));
+    ScopedCall sc(ctx);
+    if (!d_in || !n || !d_sa) return ctx->fail(DK_E_ARG, "null pointer");
+    std::vector<uint32_t> off;
+    DK_TRY(check_pack(ctx, count, n, off));
+    if (npat == 0) return DK_OK;
+    if (!pat_block) return ctx->fail(DK_E_ARG, "null pointer");
+    Timer t;
+    Patterns p;
+    DK_TRY(check_patterns(ctx, npat, pat_len, pat_block, count, p));
+    if ((!d_pat && p.bytes()) || !d_lo || !d_hi) return ctx->fail(DK_E_ARG, "null pointer");
+    hipStream_t st = ctx->stream;
+    uint32_t *d_off = ctx->ws_alloc<uint32_t>(count + 1);
+    if (!d_off) return DK_E_NOMEM;
+    DK_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    const int rc = sa_search_run(ctx, d_in, d_off, d_sa, d_pat, p, pat_block, d_lo, d_hi);
+    const hipError_t e = hipStreamSynchronize(st);  // (also on failure: the copy above reads `off`)
     DK_TRY(rc);
     DK_HIP(ctx, e);
     ctx->stats.ms_total = t.ms();

@@ -246,6 +246,16 @@ int lcp_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, size_t
 int lcp_phi_from_rank_device(dk_ctx *ctx, const uint32_t *d_rank, const uint32_t *d_sa, const uint32_t *d_off, size_t count, size_t total, uint32_t *d_phi);
 // ... and are redone here, one block's slots [lo, hi) at a time, from the suffix array the guard has written
 int lcp_phi_block_device(dk_ctx *ctx, const uint32_t *d_sa, const uint32_t *d_off, size_t count, size_t lo, size_t hi, uint32_t *d_phi);
+// sa_query.hip; layout of d_text / d_sa as in lcp_device.
+// sa_check_device: h_words (host, 3 count) = per block the lowest slot whose entry is outside the block, the lowest position no slot names, the lowest
+// slot whose suffix is not greater than the one in front of it; all ones: none.  The order is evaluated only for blocks without the first two.
+// Synchronises.  Takes 4 total + 12 count bytes of workspace and releases them.
+int sa_check_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, size_t count, size_t total, const uint32_t *d_sa, uint32_t *h_words);
+// sa_search_device: pattern q = d_pat[d_pat_off[q], d_pat_off[q + 1]) in block d_pat_blk[q] (d_pat_blk null: block 0; the caller has checked them);
+// d_lo[q] / d_hi[q] = slots of that block whose suffix, cut to the pattern's length, is smaller than / not greater than the pattern.  longest /
+// shortest: of the pattern lengths, which decide the kernels launched.  Enqueues only; takes no workspace.
+int sa_search_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, const uint32_t *d_sa, const uint8_t *d_pat, const uint32_t *d_pat_off,
+                     const uint32_t *d_pat_blk, size_t npat, size_t longest, size_t shortest, uint32_t *d_lo, uint32_t *d_hi);
 // packed_dc_device: the DC arrays of every block of a packed L.  compact: block i's entries at [rb_i, rb_i + m_i) (global run order, rb on the
 // device in d_rb[0 .. count], d_rb[count] = all runs); otherwise at [off_i, off_i + m_i).  d_m / d_flags: count words, d_init: count x 256.
 int packed_dc_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, bool compact, uint32_t *d_dist,

@@ -4,7 +4,7 @@ from .context import Context
 
 class Constructor:
     """saca::Constructor: `new(max_n)`, `capacity()`, `compute(input) -> suffix array`; `compute_packed(inputs)` is this library's packed form; `compute_lcp` /
-    `compute_packed_lcp` give the LCP arrays with the suffix arrays."""
+    `compute_packed_lcp` give the LCP arrays with the suffix arrays; `check` verifies a suffix array and `search` finds patterns with one."""
 
     def __init__(self, max_n, device=0):
         self._ctx = Context(max_n, device)
@@ -38,6 +38,19 @@ class Constructor:
         if total > self.capacity():
             raise ValueError("Constructor sized for %d bytes got a pack of %d" % (self.capacity(), total))
         return self._ctx.suffix_array_packed_lcp(inputs)
+
+    def check(self, data, suffixes):
+        """is `suffixes` what compute(data) returns?  -> (verdict, where): ("ok", n), or the first kind of fault -- "bad_range",
+        "not_permutation", "bad_order" -- and the lowest slot (text position for "not_permutation") that shows it.  The reference has no counterpart."""
+        if len(data) != self._n:
+            raise ValueError("Constructor sized for %d bytes got %d" % (self._n, len(data)))
+        return self._ctx.sa_check(data, suffixes)
+
+    def search(self, data, suffixes, patterns):
+        """(lo, hi) per pattern: suffixes[lo[q]:hi[q]] are exactly the places patterns[q] occurs in data.  `suffixes` is trusted (see check)."""
+        if len(data) != self._n:
+            raise ValueError("Constructor sized for %d bytes got %d" % (self._n, len(data)))
+        return self._ctx.sa_search(data, suffixes, patterns)
 
     def context(self):
         """the analogue of reuse(): the device workspace is lent to the later stages through the context"""

@@ -1,7 +1,7 @@
 // dark.hpp -- C++ mirror of the reference's Rust interface for the hot path, a thin layer over the C ABI (dark_amd.h).
 // The reference is compiled code (Rust); its toolchain is not in this image, so the host side a Rust caller would write is
 // given here in C++ with the same names, argument meaning and error behaviour:
-//   dark::saca::Constructor            src/saca.rs:344-384   new(max_n) / capacity() / compute(input)
+//   dark::saca::Constructor            src/saca.rs:344-384   new(max_n) / capacity() / compute(input); check / search are this library's
 //   dark::block::dc::Encoder<Model>    src/block/dc.rs:21-92  new(n, model) / encode(input, writer) -> (writer, result)
 //   dark::block::dc::Decoder<Model>    src/block/dc.rs:96-161 new(n, model) / decode(reader, writer) -> (reader, writer, result)
 //   dark::block::raw::Encoder<Model> / Decoder<Model>   src/block/raw.rs:17-105 (Model = model::bbb::Model or model::raw::Out)
@@ -114,6 +114,33 @@ public:
             out.emplace_back(std::vector<Suffix>(all.begin() + lo, all.begin() + hi), std::vector<uint32_t>(lcp.begin() + lo, lcp.begin() + hi));
             at += n;
         }
+        return out;
+    }
+    // Is `suffixes` what compute(input) returns (dk_sa_check)?  {DK_SA_OK, n}, or the first kind of fault and the lowest slot (DK_SA_NOT_PERMUTATION:
+    // text position) that shows it.  Nothing in the reference corresponds; "no" is an answer, not an Error.
+    std::pair<uint32_t, uint32_t> check(const std::vector<Symbol> &input, const std::vector<Suffix> &suffixes) {
+        if (input.size() != n_ || suffixes.size() != n_) throw Error(DK_E_ARG, "assertion failed: input.len() == self.n");
+        uint32_t verdict = 0, where = 0;
+        int rc = dk_sa_check(ctx_.get(), input.data(), input.size(), suffixes.data(), &verdict, &where);
+        if (rc != DK_OK) throw Error(rc, ctx_.error());
+        return {verdict, where};
+    }
+    // result[q] = (lo, hi): suffixes[lo .. hi) are exactly the places patterns[q] occurs in input; lo == hi = the insertion slot of a pattern
+    // that does not occur (dk_sa_search).  `suffixes` is trusted: check() verifies one.
+    std::vector<std::pair<uint32_t, uint32_t>> search(const std::vector<Symbol> &input, const std::vector<Suffix> &suffixes,
+                                                      const std::vector<std::vector<Symbol>> &patterns) {
+        if (input.size() != n_ || suffixes.size() != n_) throw Error(DK_E_ARG, "assertion failed: input.len() == self.n");
+        std::vector<size_t> lens;
+        std::vector<Symbol> bytes(1);  // (one byte so that data() is never null)
+        for (const auto &p : patterns) {
+            lens.push_back(p.size());
+            bytes.insert(bytes.end(), p.begin(), p.end());
+        }
+        std::vector<uint32_t> lo(patterns.size() + 1), hi(patterns.size() + 1);
+        int rc = dk_sa_search(ctx_.get(), input.data(), input.size(), suffixes.data(), bytes.data() + 1, patterns.size(), lens.data(), lo.data(), hi.data());
+        if (rc != DK_OK) throw Error(rc, ctx_.error());
+        std::vector<std::pair<uint32_t, uint32_t>> out;
+        for (size_t q = 0; q < patterns.size(); ++q) out.emplace_back(lo[q], hi[q]);
         return out;
     }
     detail::Ctx &context() { return ctx_; }  // plays reuse(): later stages share the device workspace through it

@@ -191,7 +191,7 @@ int dk_suffix_array_packed(dk_ctx *ctx, const uint8_t *in, size_t count, const s
  * DK_E_ARG as for the suffix-array entries (null pointers, n == 0, n > dk_capacity, the pack checks, a decoder context), and for an entry of
  * d_sa that is >= n (in a pack: >= n[i]) -- then nothing is written to d_lcp_out.  A d_sa whose entries are in range but which is not the
  * suffix array of the text: the values written are unspecified, but the call returns, every value is <= n (n[i]), and nothing outside
- * [0, n) of the text, d_sa and d_lcp_out is touched.
+ * [0, n) of the text, d_sa and d_lcp_out is touched.  Whether an array IS the suffix array of its text is what dk_dev_sa_check answers.
  * full_ctx: a DK_CTX_FULL context.  (The parameter's name says so; a decoder context gets DK_E_ARG with the entry's name in dk_last_error.) */
 /* d_sa: the suffix array of d_in[0, n) (e.g. from dk_dev_suffix_array); d_lcp_out: n entries.  Any alignment of d_in; d_sa and d_lcp_out
  * need the four bytes of their element only. */
@@ -209,6 +209,48 @@ int dk_dev_lcp_packed(dk_ctx *full_ctx, const uint8_t *d_in, size_t count, const
 int dk_dev_suffix_array_packed_lcp(dk_ctx *full_ctx, const uint8_t *d_in, size_t count, const size_t *n, uint32_t *d_sa_out, uint32_t *d_lcp_out);
 /* the same from and to host memory (the layout of dk_suffix_array_packed): one upload, one pass, two downloads */
 int dk_suffix_array_packed_lcp(dk_ctx *full_ctx, const uint8_t *in, size_t count, const size_t *n, uint32_t *sa_out, uint32_t *lcp_out);
+/* ---- what a caller does with a suffix array: verify it, search in it (nothing in the reference corresponds: src/saca.rs stops at the array;
+ * libdivsufsort's sufcheck and sa_search are the models).  DESIGN.md section 4.12.  Layout of a pack as in dk_dev_suffix_array_packed: block i's
+ * text at d_in[off_i, off_i + n[i]), its suffix array at d_sa[off_i, off_i + n[i]) with entries LOCAL to the block; every block is on its own.
+ * Order as everywhere here (src/saca.rs:105-113): no sentinel, a suffix that is a proper prefix of another sorts first.
+ * DK_E_ARG as for the suffix-array entries (null pointers, n == 0, n > dk_capacity, the pack checks, a decoder context).
+ * full_ctx: a DK_CTX_FULL context (a decoder context gets DK_E_ARG with the entry's name in dk_last_error).
+ *
+ * The check.  The return code is DK_OK whenever the check ran: "not a suffix array" is an answer (*verdict), not an error.  verdict and where are
+ * HOST memory (packed: count entries each).  Three kinds of failure are tested per block in this order, the first that fails decides and the
+ * later ones are not evaluated for that block, so the answer is deterministic; where is local to the block, and n (n[i]) with DK_SA_OK.
+ * Linear and exact for any input (Burkhardt, Karkkainen 2003): no stretch of text is compared, a^n costs what random bytes cost. */
+#define DK_SA_OK 0u
+#define DK_SA_BAD_RANGE 1u        /* where = lowest slot whose entry is >= n_i */
+#define DK_SA_NOT_PERMUTATION 2u  /* where = lowest text position that no slot names */
+#define DK_SA_BAD_ORDER 3u        /* where = lowest slot i >= 1 whose suffix is not greater than the suffix in slot i-1 */
+/* is d_sa[0, n) the suffix array of d_in[0, n)?  Any alignment of d_in; d_sa needs the four bytes of its element only. */
+int dk_dev_sa_check(dk_ctx *full_ctx, const uint8_t *d_in, size_t n, const uint32_t *d_sa, uint32_t *verdict, uint32_t *where);
+/* the same from host memory: text and array are uploaded (9 n bytes of workspace in all) */
+int dk_sa_check(dk_ctx *full_ctx, const uint8_t *in, size_t n, const uint32_t *sa, uint32_t *verdict, uint32_t *where);
+/* every block of a pack in one pass (the launches do not grow with count): verdict[i] / where[i] = what dk_dev_sa_check gives for block i alone */
+int dk_dev_sa_check_packed(dk_ctx *full_ctx, const uint8_t *d_in, size_t count, const size_t *n, const uint32_t *d_sa,
+                           uint32_t *verdict /* [count] */, uint32_t *where /* [count] */);
+/* The search.  npat patterns lie back to back in d_pat, pattern q of pat_len[q] bytes (pat_len: HOST memory, like n of the packed calls); for a
+ * pack pat_block[q] (HOST) names the block pattern q is searched in.  With "suffix <m P" meaning: the suffix cut to its first m = pat_len[q]
+ * bytes is smaller than P as byte strings, a proper prefix being smaller --
+ *   d_lo[q] = number of slots of the block whose suffix is <m P,   d_hi[q] = number of slots whose suffix is <=m P   (device, npat entries each),
+ * both local to the block, so SA[lo, hi) are exactly the occurrences of P.  A pattern that does not occur gives lo == hi = its insertion slot;
+ * m == 0 gives [0, n_i); m > n_i is an ordinary pattern that does not occur.  npat == 0 is DK_OK and writes nothing.
+ * DK_E_ARG also for pat_block[q] >= count, more than 2^32 - 1 pattern bytes in all, and, in the host form, patterns plus offsets that do not
+ * fit the workspace beside the block.  Workspace: 8 bytes per pattern.
+ * The suffix array is TRUSTED, not verified (dk_dev_sa_check does that).  For any array: an entry >= n_i is treated as the empty suffix and the
+ * text is not read at it, every compare stops at min(m, n_i - SA[slot]); the results are then unspecified, but lo <= hi <= n_i, and nothing
+ * outside the text, the array, the patterns and the two results is touched. */
+int dk_dev_sa_search(dk_ctx *full_ctx, const uint8_t *d_in, size_t n, const uint32_t *d_sa,
+                     const uint8_t *d_pat, size_t npat, const size_t *pat_len, uint32_t *d_lo, uint32_t *d_hi);
+/* the same from and to host memory: text, array and patterns are uploaded, lo and hi downloaded */
+int dk_sa_search(dk_ctx *full_ctx, const uint8_t *in, size_t n, const uint32_t *sa,
+                 const uint8_t *pat, size_t npat, const size_t *pat_len, uint32_t *lo, uint32_t *hi);
+/* patterns searched in the blocks of a pack, one launch for all of them */
+int dk_dev_sa_search_packed(dk_ctx *full_ctx, const uint8_t *d_in, size_t count, const size_t *n, const uint32_t *d_sa,
+                            const uint8_t *d_pat, size_t npat, const size_t *pat_len, const uint32_t *pat_block,
+                            uint32_t *d_lo, uint32_t *d_hi);
 /* DC arrays of a packed L: block i's entries at [off_i, off_i + m[i]) of d_dist / d_sym / d_rank (device, sum of n entries each; d_rank may
  * be NULL), init (host, count x 256: block i's table at init[256 i]) and m (host, count) as from dk_dev_dc_encode */
 int dk_dev_dc_encode_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, const size_t *n, uint32_t *init, uint32_t *d_dist, uint8_t *d_sym,

@@ -147,9 +147,9 @@ def run_one(name, reps):
     print("ROW " + json.dumps(row), flush=True)
 
 
-def child(name, reps):
-    """one workload in a process of its own, under its own time limit -> its row; the first failure ends the run"""
-    p = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--step", name, "--reps", str(reps)], stdout=subprocess.PIPE, text=True)
+def child(name, reps, script=None):
+    """one workload in a process of its own, under its own time limit -> its rows; the first failure ends the run (script: another tool's file)"""
+    p = subprocess.Popen([sys.executable, script or os.path.abspath(__file__), "--step", name, "--reps", str(reps)], stdout=subprocess.PIPE, text=True)
     late = []
     timer = threading.Timer(STEP_TIMEOUT, lambda: (late.append(True), p.kill()))
     timer.start()

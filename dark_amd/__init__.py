@@ -6,6 +6,6 @@ CPU fallback.  Build it with `python dark_amd/build.py`."""
 from . import _lib
 from ._lib import load as load_library
 from .context import Context, DarkError, multi_block_encode, multi_block_decode
-from . import saca, block, model, entropy
+from . import saca, block, model, entropy, fm
 
-__all__ = ["Context", "DarkError", "multi_block_encode", "multi_block_decode", "saca", "block", "model", "entropy", "load_library"]
+__all__ = ["Context", "DarkError", "multi_block_encode", "multi_block_decode", "saca", "block", "model", "entropy", "fm", "load_library"]

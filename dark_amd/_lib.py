@@ -82,6 +82,13 @@ SIGNATURES = {
     "dk_dev_sa_search": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp]),
     "dk_sa_search": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp]),
     "dk_dev_sa_search_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "dk_fm_index_bytes": (_sz, [_sz, _sz]),
+    "dk_dev_fm_build": (_i, [_vp, _vp, _sz, C.c_uint32, _vp]),
+    "dk_dev_fm_build_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp]),
+    "dk_dev_fm_count": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "dk_dev_fm_count_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "dk_fm_count": (_i, [_vp, _vp, _sz, C.c_uint32, _vp, _sz, _vp, _vp, _vp]),
+    "dk_dbg_dev_fm_rank": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
     "dk_dev_dc_encode_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _szp]),
     "dk_batch_push_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "dk_dev_packed_encode": (_i, [_vp, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i]),

@@ -75,6 +75,13 @@ def workspace_bytes(purpose, n, max_blocks=1):
     return int(_lib.load().dk_workspace_bytes(_lib.PURPOSES[purpose], int(n), int(max_blocks)))
 
 
+def fm_index_bytes(total, count=1):
+    """dk_fm_index_bytes: bytes of the FM-index of a pack of `count` blocks and `total` bytes; needs no GPU.  0 for what the pack checks refuse."""
+    if total < 0 or count < 0:
+        return 0
+    return int(_lib.load().dk_fm_index_bytes(int(total), int(count)))
+
+
 class Context:
     def __init__(self, max_n, device=0, purpose="full", max_blocks=1):
         """purpose="decoder": a context for the inverse path only (dk_ctx_create_decoder), about a fifth of the workspace; max_blocks = most
@@ -383,6 +390,55 @@ class Context:
         blocks = np.array(pat_blocks, dtype=np.int64).astype(np.uint32) if npat else np.zeros(1, np.uint32)
         self._ck(self._lib.dk_dev_sa_search_packed(self._h, _ptr(d_in), count, ns, _ptr(d_sa), _ptr(d_pat), npat, lens, _ptr(blocks), _ptr(d_lo),
                                                    _ptr(d_hi)))
+
+    # ---- FM-index: count patterns in L, no text and no suffix array; served by decoder contexts too ----
+    def dev_fm_build(self, d_bwt, n, origin, d_index):
+        """the index of d_bwt[0, n) with its origin into d_index, a device tensor of fm_index_bytes(n) bytes"""
+        _inputs_ready(d_bwt)
+        self._ck(self._lib.dk_dev_fm_build(self._h, _ptr(d_bwt), n, int(origin), _ptr(d_index)))
+
+    def dev_fm_build_packed(self, d_bwt, sizes, origins, d_index):
+        """one index for every block of a packed L (layout of dev_bwt_forward_packed); d_index: fm_index_bytes(sum(sizes), len(sizes)) bytes"""
+        _inputs_ready(d_bwt)
+        count = len(sizes)
+        if len(origins) != count:
+            raise DarkError(_lib.DK_E_ARG, "%d origins for %d blocks" % (len(origins), count))
+        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
+        org = np.array(origins, dtype=np.int64).astype(np.uint32) if count else np.zeros(1, np.uint32)
+        self._ck(self._lib.dk_dev_fm_build_packed(self._h, _ptr(d_bwt), count, ns, _ptr(org), _ptr(d_index)))
+
+    def dev_fm_count(self, d_bwt, n, d_index, d_pat, pat_lens, d_lo, d_hi):
+        """patterns as for dev_sa_search; d_lo[q] / d_hi[q] are what dev_sa_search gives for the text d_bwt is the BWT of: hi - lo occurrences"""
+        _inputs_ready(d_bwt, d_index, d_pat)
+        npat = len(pat_lens)
+        lens = (C.c_size_t * max(npat, 1))(*[int(m) for m in pat_lens])
+        self._ck(self._lib.dk_dev_fm_count(self._h, _ptr(d_bwt), n, _ptr(d_index), _ptr(d_pat), npat, lens, _ptr(d_lo), _ptr(d_hi)))
+
+    def dev_fm_count_packed(self, d_bwt, sizes, d_index, d_pat, pat_lens, pat_blocks, d_lo, d_hi):
+        """dev_fm_count in a pack: pattern q is counted in block pat_blocks[q], d_lo / d_hi are local to that block"""
+        _inputs_ready(d_bwt, d_index, d_pat)
+        count, npat = len(sizes), len(pat_lens)
+        if len(pat_blocks) != npat:
+            raise DarkError(_lib.DK_E_ARG, "%d blocks for %d patterns" % (len(pat_blocks), npat))
+        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
+        lens = (C.c_size_t * max(npat, 1))(*[int(m) for m in pat_lens])
+        blocks = np.array(pat_blocks, dtype=np.int64).astype(np.uint32) if npat else np.zeros(1, np.uint32)
+        self._ck(self._lib.dk_dev_fm_count_packed(self._h, _ptr(d_bwt), count, ns, _ptr(d_index), _ptr(d_pat), npat, lens, _ptr(blocks),
+                                                  _ptr(d_lo), _ptr(d_hi)))
+
+    def fm_count(self, bwt, origin, patterns):
+        """(lo, hi) per pattern, uint32 arrays, from (L, origin) in host memory, e.g. as dk_stream_decode leaves them: what sa_search gives for
+        the text, without the text (dk_fm_count)"""
+        b = as_u8(bwt)
+        pat, lens, npat = _pack_patterns(patterns)
+        lo, hi = np.zeros(npat, dtype=np.uint32), np.zeros(npat, dtype=np.uint32)
+        self._ck(self._lib.dk_fm_count(self._h, _ptr(b), len(b), int(origin), _ptr(pat), npat, lens, _ptr(lo), _ptr(hi)))
+        return lo, hi
+
+    def dbg_dev_fm_rank(self, d_bwt, total, d_index, d_pos, d_sym, d_out):
+        """d_out[q] = occurrences of d_sym[q] in d_bwt[0, d_pos[q]) by the count kernel's rank (uint32 / uint8 / uint32 device tensors)"""
+        _inputs_ready(d_bwt, d_index, d_pos, d_sym)
+        self._ck(self._lib.dk_dbg_dev_fm_rank(self._h, _ptr(d_bwt), total, _ptr(d_index), _ptr(d_pos), _ptr(d_sym), len(d_pos), _ptr(d_out)))
 
     def dev_dc_encode_packed(self, d_bwt, sizes, d_dist, d_sym, d_rank=None):
         """DC arrays of a packed L: block i's entries at [off_i, off_i + m_i); returns (list of init tables, list of m)"""

@@ -77,6 +77,8 @@ size_t workspace_bytes(size_t max_n) {
     // host-pointer form: 9 n + 12 count <= 21 n.  The search takes 8 bytes per pattern; its host-pointer form, which also holds the patterns and
     // two result words per pattern, refuses a batch that does not fit beside the 5 n (DK_E_ARG).  Both are far below the sort's peak, so this
     // size does not grow for them; tests/test_gpu_sa_search.py checks peak <= size on contexts sized exactly to their input.
+    // The FM-index (fm_index.hip) keeps its index in the caller's memory: its build takes at most 256 KiB + 8 bytes per block, its count 8 bytes per
+    // pattern, and its host-pointer form L and the index (2 n + 3 KiB) beside a batch that it refuses when it does not fit (DK_E_ARG).
     // tests/test_gpu_parity.py::test_workspace_accounting checks peak <= size on contexts sized exactly to their block, and
     // tests/test_gpu_fullsize.py checks the n-proportional term where the constant is negligible (peak - 64 MiB <= 69.4 n at 1e8 bytes).
     const size_t sort_temporaries = 62 * max_n + max_n / 8, io = 6 * max_n, on_top = max_n / 4 + max_n;
@@ -107,6 +109,8 @@ size_t decoder_workspace_bytes(size_t max_n, size_t max_blocks) {
     //   around it the pack-sized L of dk_dev_packed_decode                                            total
     //   = 13.625 total for one block, 33.5 total + 1 KiB per block for a pack of one-byte blocks.
     // The larger of the two, + n / 64 + 64 KiB of headroom.  The pinned staging (ensure_stage, ensure_slot) is host memory and not part of this.
+    // The FM-index entries (fm_index.hip) are served too and stay below all of that: the build takes chunk sums of at most min(256 KiB, n + 2 KiB)
+    // and 8 bytes per block, the host-pointer form 2 n + 3 KiB beside them (tests/test_gpu_fm.py checks peak <= size on both purposes).
     // tests/test_gpu_decoder_ctx.py checks peak <= size on contexts sized exactly to their block or pack, through every entry above.
     const size_t single = 2 * ((max_n + 255) & ~size_t(255)) + bwt_inverse_workspace(max_n);
     const size_t packed = ((max_n + 255) & ~size_t(255)) + packed_ibwt_workspace(max_n, max_blocks);
@@ -1357,6 +1361,156 @@ int dk_dev_sa_search_packed(dk_ctx *ctx, const uint8_t *d_in, size_t count, cons
     DK_TRY(rc);
     DK_HIP(ctx, e);
     ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+// ---- FM-index (csrc/fm_index.hip).  Served by contexts of either purpose: begin_call without a forward entry. --------
+}  // extern "C"
+
+namespace {
+bool fm_good_index(const void *d_index) { return d_index && (reinterpret_cast<uintptr_t>(d_index) & 3) == 0; }
+// offsets and blocks of the patterns to the workspace (8 bytes per pattern), then the kernel.  Synchronises, as sa_search_run does.
+int fm_count_run(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, const void *d_index, const uint8_t *d_pat,
+                 const Patterns &p, const uint32_t *pat_block, uint32_t *d_lo, uint32_t *d_hi) {
+    hipStream_t st = ctx->stream;
+    const size_t npat = p.off.size() - 1;
+    uint32_t *d_pat_off = ctx->ws_alloc<uint32_t>(npat + 1), *d_pat_blk = pat_block ? ctx->ws_alloc<uint32_t>(npat) : nullptr;
+    if (!d_pat_off || (pat_block && !d_pat_blk)) return DK_E_NOMEM;
+    DK_HIP(ctx, hipMemcpyAsync(d_pat_off, p.off.data(), (npat + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    int rc = DK_OK;
+    if (pat_block) rc = ctx->hip_ok(hipMemcpyAsync(d_pat_blk, pat_block, npat * sizeof(uint32_t), hipMemcpyHostToDevice, st), "pattern blocks");
+    if (rc == DK_OK) rc = fm_count_device(ctx, d_bwt, d_off, count, total, d_index, d_pat, d_pat_off, d_pat_blk, npat, p.bytes(), d_lo, d_hi);
+    const hipError_t e = hipStreamSynchronize(st);
+    DK_TRY(rc);
+    DK_HIP(ctx, e);
+    return DK_OK;
+}
+}  // namespace
+
+extern "C" {
+
+size_t dk_fm_index_bytes(size_t total, size_t count) {
+    if (total == 0 || total > 0x7FFFFFFEull || count == 0 || count > DK_PACKED_MAX_BLOCKS || count > total) return 0;
+    return fm_index_words(total, count) * sizeof(uint32_t);
+}
+
+int dk_dev_fm_build(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t origin, void *d_index) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!d_bwt || !d_index) return ctx->fail(DK_E_ARG, "null pointer");
+    if (!fm_good_index(d_index)) return ctx->fail(DK_E_ARG, "the index is not 4-byte aligned");
+    DK_TRY(check_n(ctx, n));
+    if (origin >= n) return ctx->fail(DK_E_ARG, "origin %u is outside the block of %zu bytes", origin, n);
+    Timer t;
+    DK_TRY(fm_build_device(ctx, d_bwt, {0u, static_cast<uint32_t>(n)}, &origin, d_index));
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_dev_fm_build_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const uint32_t *origin, void *d_index) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!d_bwt || !n || !origin || !d_index) return ctx->fail(DK_E_ARG, "null pointer");
+    if (!fm_good_index(d_index)) return ctx->fail(DK_E_ARG, "the index is not 4-byte aligned");
+    std::vector<uint32_t> off;
+    DK_TRY(check_pack(ctx, count, n, off));
+    for (size_t i = 0; i < count; ++i)
+        if (origin[i] >= n[i]) return ctx->fail(DK_E_ARG, "origin %u of block %zu is outside its %zu bytes", origin[i], i, n[i]);
+    Timer t;
+    DK_TRY(fm_build_device(ctx, d_bwt, off, origin, d_index));
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_dev_fm_count(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, const void *d_index, const uint8_t *d_pat, size_t npat, const size_t *pat_len,
+                    uint32_t *d_lo, uint32_t *d_hi) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!d_bwt || !d_index) return ctx->fail(DK_E_ARG, "null pointer");
+    if (!fm_good_index(d_index)) return ctx->fail(DK_E_ARG, "the index is not 4-byte aligned");
+    DK_TRY(check_n(ctx, n));
+    if (npat == 0) return DK_OK;
+    Timer t;
+    Patterns p;
+    DK_TRY(check_patterns(ctx, npat, pat_len, nullptr, 1, p));
+    if ((!d_pat && p.bytes()) || !d_lo || !d_hi) return ctx->fail(DK_E_ARG, "null pointer");
+    uint32_t *d_off = nullptr;
+    DK_TRY(single_offsets(ctx, n, &d_off));
+    DK_TRY(fm_count_run(ctx, d_bwt, d_off, 1, n, d_index, d_pat, p, nullptr, d_lo, d_hi));
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_dev_fm_count_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const void *d_index, const uint8_t *d_pat, size_t npat,
+                           const size_t *pat_len, const uint32_t *pat_block, uint32_t *d_lo, uint32_t *d_hi) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!d_bwt || !n || !d_index) return ctx->fail(DK_E_ARG, "null pointer");
+    if (!fm_good_index(d_index)) return ctx->fail(DK_E_ARG, "the index is not 4-byte aligned");
+    std::vector<uint32_t> off;
+    DK_TRY(check_pack(ctx, count, n, off));
+    if (npat == 0) return DK_OK;
+    if (!pat_block) return ctx->fail(DK_E_ARG, "null pointer");
+    Timer t;
+    Patterns p;
+    DK_TRY(check_patterns(ctx, npat, pat_len, pat_block, count, p));
+    if ((!d_pat && p.bytes()) || !d_lo || !d_hi) return ctx->fail(DK_E_ARG, "null pointer");
+    hipStream_t st = ctx->stream;
+    uint32_t *d_off = ctx->ws_alloc<uint32_t>(count + 1);
+    if (!d_off) return DK_E_NOMEM;
+    DK_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    const int rc = fm_count_run(ctx, d_bwt, d_off, count, off.back(), d_index, d_pat, p, pat_block, d_lo, d_hi);
+    const hipError_t e = hipStreamSynchronize(st);  // (also on failure: the copy above reads `off`)
+    DK_TRY(rc);
+    DK_HIP(ctx, e);
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_fm_count(dk_ctx *ctx, const uint8_t *bwt, size_t n, uint32_t origin, const uint8_t *pat, size_t npat, const size_t *pat_len, uint32_t *lo,
+                uint32_t *hi) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!bwt) return ctx->fail(DK_E_ARG, "null pointer");
+    DK_TRY(check_n(ctx, n));
+    if (origin >= n) return ctx->fail(DK_E_ARG, "origin %u is outside the block of %zu bytes", origin, n);
+    if (npat == 0) return DK_OK;
+    Timer t;
+    Patterns p;
+    DK_TRY(check_patterns(ctx, npat, pat_len, nullptr, 1, p));
+    if ((!pat && p.bytes()) || !lo || !hi) return ctx->fail(DK_E_ARG, "null pointer");
+    // L n, the index, the two offsets of the block; then the patterns, their offsets and the two results; the build's workspace while it runs
+    const size_t index_bytes = fm_index_words(n, 1) * sizeof(uint32_t);
+    const size_t need = ws_round(n) + ws_round(index_bytes) + 256 + ws_round(p.bytes()) + ws_round(4 * (npat + 1)) + 2 * ws_round(4 * npat) + fm_build_workspace(n, 1);
+    if (need > ctx->ws_size) return ctx->fail(DK_E_ARG, "%zu patterns of %zu bytes and their offsets do not fit the workspace beside L and its index", npat, p.bytes());
+    hipStream_t st = ctx->stream;
+    uint8_t *d_bwt = ctx->ws_alloc<uint8_t>(n), *d_pat = ctx->ws_alloc<uint8_t>(std::max<size_t>(p.bytes(), 1));
+    uint32_t *d_index = ctx->ws_alloc<uint32_t>(index_bytes / sizeof(uint32_t)), *d_lo = ctx->ws_alloc<uint32_t>(npat), *d_hi = ctx->ws_alloc<uint32_t>(npat);
+    uint32_t *d_off = nullptr;
+    if (!d_bwt || !d_pat || !d_index || !d_lo || !d_hi) return DK_E_NOMEM;
+    DK_TRY(single_offsets(ctx, n, &d_off));
+    DK_HIP(ctx, hipMemcpyAsync(d_bwt, bwt, n, hipMemcpyHostToDevice, st));
+    if (p.bytes()) DK_HIP(ctx, hipMemcpyAsync(d_pat, pat, p.bytes(), hipMemcpyHostToDevice, st));
+    DK_TRY(fm_build_device(ctx, d_bwt, {0u, static_cast<uint32_t>(n)}, &origin, d_index));
+    DK_TRY(fm_count_run(ctx, d_bwt, d_off, 1, n, d_index, d_pat, p, nullptr, d_lo, d_hi));
+    DK_HIP(ctx, hipMemcpyAsync(lo, d_lo, npat * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    DK_HIP(ctx, hipMemcpyAsync(hi, d_hi, npat * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    DK_HIP(ctx, hipStreamSynchronize(st));
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_dbg_dev_fm_rank(dk_ctx *ctx, const uint8_t *d_bwt, size_t total, const void *d_index, const uint32_t *d_pos, const uint8_t *d_sym, size_t nq,
+                       uint32_t *d_out) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!d_bwt || !d_index) return ctx->fail(DK_E_ARG, "null pointer");
+    if (!fm_good_index(d_index)) return ctx->fail(DK_E_ARG, "the index is not 4-byte aligned");
+    DK_TRY(check_n(ctx, total));
+    if (nq == 0) return DK_OK;
+    if (!d_pos || !d_sym || !d_out || nq > 0xFFFFFFFEull) return ctx->fail(DK_E_ARG, "null pointer");
+    DK_TRY(fm_rank_device(ctx, d_bwt, total, d_index, d_pos, d_sym, nq, d_out));
+    DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return DK_OK;
 }
 

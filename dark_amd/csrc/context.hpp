@@ -32,7 +32,7 @@ enum KernelSlot : int {
     K_DC_CARRY,        // k_dc_runscan + k_dc_carry_a/_b/_c + k_fill_u32
     K_DC_MAIN,
     K_DC_INIT,
-    K_IBWT_HIST,       // k_ibwt_hist + k_ibwt_scan_a/_b/_c
+    K_IBWT_HIST,       // k_ibwt_hist + k_ibwt_scan_a/_b/_c; the FM-index build: k_fm_hist + k_fm_scan_a/_b/_c + k_fm_heads
     K_IBWT_LF,
     K_IBWT_WALK,
     K_IBWT_JUMP,
@@ -49,7 +49,7 @@ enum KernelSlot : int {
     K_RADIX_SCATTER_TEXT,  // k_radix_scatter<false, true>: first pass, keys built from the text (13 B per pair)
     K_ISA_PARTITION,       // k_isa_init + k_isa_split<true> + k_isa_split<false> (inverse permutation through LDS windows)
     K_ISA_ASSEMBLE,        // k_isa_assemble
-    K_CHAIN,               // k_chain_extract + _ends + _tiles + _spine + _verdicts + _apply (pair chains; their sort is in the radix slots)
+    K_CHAIN,               // k_chain_extract + _ends + _tiles + _spine + _verdicts + _apply (pair chains; their sort is in the radix slots); k_sa_search*, k_fm_count
     K_PERIOD,              // k_period_first + _spine + _fill (next break of the block's dominant period, for the period round)
     K_SLOT_COUNT
 };
@@ -256,6 +256,18 @@ int sa_check_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, s
 // shortest: of the pattern lengths, which decide the kernels launched.  Enqueues only; takes no workspace.
 int sa_search_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, const uint32_t *d_sa, const uint8_t *d_pat, const uint32_t *d_pat_off,
                      const uint32_t *d_pat_blk, size_t npat, size_t longest, size_t shortest, uint32_t *d_lo, uint32_t *d_hi);
+// fm_index.hip: the FM-index of a packed L and the backward search in it; a single block is a pack of one.
+// fm_index_words: 32-bit words of the index (host arithmetic).  fm_build_workspace: what fm_build_device takes, every ws_alloc rounded up.
+size_t fm_index_words(size_t total, size_t count);
+size_t fm_build_workspace(size_t total, size_t count);
+// off (host, count + 1) and origin (host, count; origin[i] < n_i checked by the caller) describe the pack.  Synchronises; releases its workspace.
+int fm_build_device(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector<uint32_t> &off, const uint32_t *origin, void *d_index);
+// patterns as in sa_search_device; d_lo[q] / d_hi[q] are the numbers sa_search_device gives.  Enqueues only; takes no workspace.
+int fm_count_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, const void *d_index, const uint8_t *d_pat,
+                    const uint32_t *d_pat_off, const uint32_t *d_pat_blk, size_t npat, size_t pat_bytes, uint32_t *d_lo, uint32_t *d_hi);
+// d_out[q] = occurrences of d_sym[q] in d_bwt[0, min(d_pos[q], total)), by the count kernel's rank.  Enqueues only.
+int fm_rank_device(dk_ctx *ctx, const uint8_t *d_bwt, size_t total, const void *d_index, const uint32_t *d_pos, const uint8_t *d_sym, size_t nq,
+                   uint32_t *d_out);
 // packed_dc_device: the DC arrays of every block of a packed L.  compact: block i's entries at [rb_i, rb_i + m_i) (global run order, rb on the
 // device in d_rb[0 .. count], d_rb[count] = all runs); otherwise at [off_i, off_i + m_i).  d_m / d_flags: count words, d_init: count x 256.
 int packed_dc_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, bool compact, uint32_t *d_dist,

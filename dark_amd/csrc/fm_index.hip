@@ -1,0 +1,327 @@
+// Counting the occurrences of patterns in a BWT without the text and without a suffix array: backward search (Ferragina, Manzini: Opportunistic
+// data structures with applications, FOCS 2000) on L itself, for one block or a pack.  Nothing in the reference
+// corresponds.  Conventions are those of bwt.hip: L[i] = T[SA[i] - 1], and T[n - 1] at the slot `origin` where SA[origin] = 0; no sentinel, a
+// suffix that is a proper prefix of another sorts first.  Block b's L sits at bwt[off_b, off_b + n_b); a single block is a pack of one.
+//
+// THE RECURRENCE.  hist[c] = occurrences of c in L, C[c] = sum of hist below c, last = L[origin] = T[n - 1], Occ(c, i) = #{k < i : L[k] = c},
+// Occ'(c, i) = Occ(c, i) - [c == last && origin < i] (the origin's symbol is a wrap-around, not a predecessor).  For P of m bytes, from its last
+// byte to its first:  first step  lo = C[c], hi = C[c] + hist[c];  every later step  x <- C[c] + [c == last] + Occ'(c, x)  for x = lo and hi (the
+// [c == last] term is the one-byte suffix T[n-1..], first of its class, which has no slot to come from).  lo = suffixes <m P, hi = suffixes <=m P:
+// the numbers of sa_query.hip.  With base_b[c] = C_b[c] - Occ_pack(c, off_b) (the cancellation of section 4.8) a step is
+//     x <- base_b[c] + [c == last_b] - [c == last_b && origin_b < x] + Occ_pack(c, off_b + x)
+// and the first step is that very step from (0, n_b) with the [c == last_b] term left out of lo: C_b[c] = base_b[c] + Occ_pack(c, off_b), and
+// origin_b < n_b cancels the two terms of hi.  So the index holds no per-block histogram.
+//
+// THE INDEX (32-bit words; fm_index_words is its size):
+//   [0, 64)                        header: magic, total, count, rows
+//   [64, 64 + 256 rows)            checkpoints: row k = Occ_pack(c, k * FM_BLOCK) for every c, rows = ceil(total / FM_BLOCK) + 1, on a grid over the
+//                                  whole pack (blocks are not aligned to it)
+//   [.., + 4 count)                per block {off, n, origin, last}
+//   [.., + 256 count)              per block base_b[256]
+// Occ_pack(c, x) = checkpoint[x / FM_BLOCK][c] + occurrences of c in L[x / FM_BLOCK * FM_BLOCK, x): one gathered word, and at most FM_BLOCK - 1
+// bytes of L of which every lane of a wave compares 16.
+//
+// BUILD    k_fm_hist       a workgroup per four rows, a wave per row: the histogram of the row's FM_BLOCK bytes in LDS, four copies per wave
+//                          (L is made of runs: LDS atomics of one instruction on one counter are serialised)
+//          k_fm_scan_a/b/c the column-wise exclusive scan of the rows in at most FM_MAX_CHUNKS chunks (the shape of k_ibwt_scan_*)
+//          k_fm_heads      a workgroup per block, a lane per symbol: Occ_pack at the block's head and end from the checkpoints plus at most one
+//                          row's bytes each, their difference scanned over the symbols = C_b; writes base_b and the block's four words
+// COUNT    k_fm_count      a wave per pattern, FM_WAVES per workgroup, grid stride; m dependent steps of one or two ranks
+//          k_fm_rank       the same rank for given (position, symbol) pairs -- the tests' view of it
+// Containment: the geometry (off, n, total) comes from the caller, never from the index; every position is clamped to [0, n_b] before it is used
+// and a rank reads L only below the position it counts to.  With an index or an L that is not what the build made the results are unspecified
+// but <= n_b, and nothing outside L, the index, the patterns and the two results is touched.
+#include <algorithm>
+
+#include "context.hpp"
+#include "device_util.hpp"
+
+namespace dk {
+
+size_t fm_index_words(size_t total, size_t count) {
+    return 64 + 256 * (div_up(total, 1024) + 1) + 4 * count + 256 * count;
+}
+
+namespace {
+
+// Positions per checkpoint row.  UNMEASURED: chosen so that one 16-byte load per lane of a wave covers a row, and the checkpoints cost
+// 256 * 4 / 1024 = 1 byte per byte of L.
+constexpr uint32_t FM_BLOCK = 1024;
+constexpr uint32_t FM_SHIFT = 10;
+static_assert(FM_BLOCK == 64 * 16 && (1u << FM_SHIFT) == FM_BLOCK, "a lane compares 16 bytes of a row");
+constexpr uint32_t FM_WAVES = 4;          // rows per workgroup of k_fm_hist; patterns per workgroup of k_fm_count
+constexpr size_t FM_MAX_CHUNKS = 256;
+constexpr uint32_t FM_MAGIC = 0x31494D46u;  // "FMI1"
+constexpr uint32_t FM_HEADER = 64;
+
+struct FmIndex { uint32_t *blocks, *base, *cp; size_t rows; };
+FmIndex fm_carve(void *d_index, size_t total, size_t count) {
+    uint32_t *w = static_cast<uint32_t *>(d_index);
+    const size_t rows = div_up(total, FM_BLOCK) + 1;
+    return FmIndex{w + FM_HEADER + 256 * rows, w + FM_HEADER + 256 * rows + 4 * count, w + FM_HEADER, rows};
+}
+
+typedef uint64_t __attribute__((aligned(1))) unaligned_u64;
+typedef const unaligned_u64 __attribute__((address_space(1))) *gptr8;
+
+// the 16 bytes at L[s, s + 16) as two little-endian words; only the first k <= 16 of them are looked at afterwards.  L has any alignment.
+// Where 16 bytes do not fit below `total` the k bytes are read one by one (k <= total - s: the caller's).
+__device__ __forceinline__ void fm_load16(const uint8_t *__restrict__ L, uint32_t total, uint32_t s, uint32_t k, uint64_t &a, uint64_t &b) {
+    a = b = 0;
+    if (k == 0) return;
+    if (total - s >= 16u) {
+        a = *(gptr8)(L + s);
+        b = *(gptr8)(L + s + 8);
+    } else {
+        for (uint32_t i = 0; i < k; ++i) {
+            const uint64_t v = L[s + i];
+            if (i < 8) a |= v << (8 * i);
+            else b |= v << (8 * (i - 8));
+        }
+    }
+}
+// one bit (the top one) per byte of v that equals the byte spread over `cc`
+__device__ __forceinline__ uint64_t fm_eq8(uint64_t v, uint64_t cc) {
+    const uint64_t x = v ^ cc, low7 = 0x7F7F7F7F7F7F7F7Full;
+    return ~(((x & low7) + low7) | x | low7);
+}
+// how many of the first k <= 16 bytes of (a, b) equal the symbol
+__device__ __forceinline__ uint32_t fm_count16(uint64_t a, uint64_t b, uint64_t cc, uint32_t k) {
+    const uint32_t ka = k < 8u ? k : 8u, kb = k - ka;
+    const uint64_t ma = ka == 8u ? ~0ull : (1ull << (8 * ka)) - 1ull, mb = kb == 8u ? ~0ull : (1ull << (8 * kb)) - 1ull;
+    return static_cast<uint32_t>(__popcll(fm_eq8(a, cc) & ma) + __popcll(fm_eq8(b, cc) & mb));
+}
+// of the row's bytes below x (x - row start <= FM_BLOCK... < FM_BLOCK by construction), how many this lane looks at
+__device__ __forceinline__ uint32_t fm_lane_bytes(uint32_t x, uint32_t s) { return x > s ? (x - s < 16u ? x - s : 16u) : 0u; }
+
+// Occ_pack(c, x) and Occ_pack(c, y) for x <= y <= total, by the whole wave; every lane gets both.  The loads of both positions are issued
+// before either is used; one load serves both where they share a row.  (x > y, from an index that is no index: still inside L, both <= total.)
+__device__ __forceinline__ void fm_rank2(const uint8_t *__restrict__ L, uint32_t total, const uint32_t *__restrict__ cp, uint32_t c, uint32_t x, uint32_t y,
+                                         uint32_t lane, uint32_t &rx, uint32_t &ry) {
+    const uint32_t row_x = x >> FM_SHIFT, row_y = y >> FM_SHIFT;
+    const uint64_t cc = 0x0101010101010101ull * c;
+    const uint32_t sx = (row_x << FM_SHIFT) + 16u * lane, sy = (row_y << FM_SHIFT) + 16u * lane;
+    const uint32_t kx = fm_lane_bytes(x, sx), ky = fm_lane_bytes(y, sy);
+    const uint32_t base_x = cp[static_cast<size_t>(row_x) * 256 + c];
+    uint32_t base_y = base_x, packed;
+    uint64_t a, b;
+    if (row_x == row_y) {
+        fm_load16(L, total, sx, kx > ky ? kx : ky, a, b);
+        packed = fm_count16(a, b, cc, kx) | (fm_count16(a, b, cc, ky) << 16);
+    } else {
+        uint64_t a2, b2;
+        base_y = cp[static_cast<size_t>(row_y) * 256 + c];
+        fm_load16(L, total, sx, kx, a, b);
+        fm_load16(L, total, sy, ky, a2, b2);
+        packed = fm_count16(a, b, cc, kx) | (fm_count16(a2, b2, cc, ky) << 16);
+    }
+    packed = wave_sum(packed);  // (each half stays below FM_BLOCK)
+    rx = base_x + (packed & 0xFFFFu);
+    ry = base_y + (packed >> 16);
+}
+__device__ __forceinline__ uint32_t fm_rank1(const uint8_t *__restrict__ L, uint32_t total, const uint32_t *__restrict__ cp, uint32_t c, uint32_t x,
+                                             uint32_t lane) {
+    const uint32_t row = x >> FM_SHIFT, s = (row << FM_SHIFT) + 16u * lane, k = fm_lane_bytes(x, s);
+    uint64_t a, b;
+    fm_load16(L, total, s, k, a, b);
+    return cp[static_cast<size_t>(row) * 256 + c] + wave_sum(fm_count16(a, b, 0x0101010101010101ull * c, k));
+}
+
+// ---- build ----------------------------------------------------------------------------------------------------------------------------------
+
+// row r of cp = the histogram of L[r * FM_BLOCK, (r + 1) * FM_BLOCK) (nothing behind `total`: the last row, and every row a grid rounded up
+// to FM_WAVES adds, count no byte -- the rows behind `rows` are not written)
+__global__ __launch_bounds__(64 * FM_WAVES) void k_fm_hist(const uint8_t *__restrict__ L, uint32_t total, uint32_t *__restrict__ cp, uint32_t rows) {
+    __shared__ uint32_t h[FM_WAVES][4][256];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (uint32_t i = threadIdx.x; i < FM_WAVES * 4 * 256; i += 64 * FM_WAVES) (&h[0][0][0])[i] = 0;
+    __syncthreads();
+    const uint32_t row = blockIdx.x * FM_WAVES + wave;
+    const uint64_t s64 = (static_cast<uint64_t>(row) << FM_SHIFT) + 16u * lane;
+    if (row < rows && s64 < total) {
+        const uint32_t s = static_cast<uint32_t>(s64), k = total - s < 16u ? total - s : 16u;
+        uint64_t a, b;
+        fm_load16(L, total, s, k, a, b);
+        uint32_t *mine = h[wave][lane & 3u];
+        for (uint32_t i = 0; i < k; ++i) atomicAdd(&mine[((i < 8 ? a >> (8 * i) : b >> (8 * (i - 8)))) & 0xFFu], 1u);
+    }
+    __syncthreads();
+    if (row < rows) {
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t c = lane + 64u * j;
+            cp[static_cast<size_t>(row) * 256 + c] = h[wave][0][c] + h[wave][1][c] + h[wave][2][c] + h[wave][3][c];
+        }
+    }
+}
+// exclusive scan down every column of the rows, in chunks of rpc rows
+__global__ __launch_bounds__(256) void k_fm_scan_a(const uint32_t *__restrict__ cp, size_t rows, size_t rpc, uint32_t *__restrict__ chunk_sum) {
+    const size_t g = blockIdx.x, r0 = g * rpc, r1 = r0 + rpc < rows ? r0 + rpc : rows;
+    uint32_t s = 0;
+#pragma unroll 8
+    for (size_t r = r0; r < r1; ++r) s += cp[r * 256 + threadIdx.x];
+    chunk_sum[g * 256 + threadIdx.x] = s;
+}
+__global__ __launch_bounds__(256) void k_fm_scan_b(uint32_t *__restrict__ chunk_sum, size_t nchunks) {
+    uint32_t run = 0;
+    for (size_t g = 0; g < nchunks; ++g) {
+        const uint32_t v = chunk_sum[g * 256 + threadIdx.x];
+        chunk_sum[g * 256 + threadIdx.x] = run;
+        run += v;
+    }
+}
+__global__ __launch_bounds__(256) void k_fm_scan_c(uint32_t *__restrict__ cp, size_t rows, size_t rpc, const uint32_t *__restrict__ chunk_sum) {
+    const size_t g = blockIdx.x, r0 = g * rpc, r1 = r0 + rpc < rows ? r0 + rpc : rows;
+    uint32_t run = chunk_sum[g * 256 + threadIdx.x];
+    for (size_t r = r0; r < r1; ++r) {
+        const uint32_t v = cp[r * 256 + threadIdx.x];
+        cp[r * 256 + threadIdx.x] = run;
+        run += v;
+    }
+}
+// block b = blockIdx.x, thread = symbol.  off / org: count + 1 / count words in the workspace (org[b] < n_b: the caller's check)
+__global__ __launch_bounds__(256) void k_fm_heads(const uint8_t *__restrict__ L, const uint32_t *__restrict__ off, const uint32_t *__restrict__ org,
+                                                  const uint32_t *__restrict__ cp, uint32_t *__restrict__ blocks, uint32_t *__restrict__ base) {
+    __shared__ uint32_t h[2][256];
+    __shared__ uint32_t s_tmp[4 + 1];
+    const uint32_t b = blockIdx.x, c = threadIdx.x, s = off[b], e = off[b + 1];
+    h[0][c] = h[1][c] = 0;
+    __syncthreads();
+    const uint32_t row_s = s >> FM_SHIFT, row_e = e >> FM_SHIFT;
+    for (uint32_t q = (row_s << FM_SHIFT) + c; q < s; q += 256u) atomicAdd(&h[0][L[q]], 1u);
+    for (uint32_t q = (row_e << FM_SHIFT) + c; q < e; q += 256u) atomicAdd(&h[1][L[q]], 1u);
+    __syncthreads();
+    const uint32_t occ_s = cp[static_cast<size_t>(row_s) * 256 + c] + h[0][c], occ_e = cp[static_cast<size_t>(row_e) * 256 + c] + h[1][c];
+    const uint32_t cb = block_excl_sum<4>(occ_e - occ_s, s_tmp, nullptr);
+    base[static_cast<size_t>(b) * 256 + c] = cb - occ_s;  // (modulo 2^32, as the step adds it back)
+    if (c == 0) {
+        uint32_t *w = blocks + 4 * static_cast<size_t>(b);
+        w[0] = s;
+        w[1] = e - s;
+        w[2] = org[b];
+        w[3] = L[s + org[b]];
+    }
+}
+
+// ---- count ----------------------------------------------------------------------------------------------------------------------------------
+
+struct FmArgs {
+    const uint8_t *L; const uint32_t *off, *blocks, *base, *cp; const uint8_t *pat; const uint32_t *pat_off, *pat_blk; uint32_t npat, total, count;
+    uint32_t *out_lo, *out_hi;
+};
+__global__ __launch_bounds__(64 * FM_WAVES) void k_fm_count(FmArgs a) {
+    const uint8_t *__restrict__ L = a.L, *__restrict__ pat = a.pat;
+    const uint32_t *__restrict__ off = a.off, *__restrict__ cp = a.cp, *__restrict__ pat_off = a.pat_off, *__restrict__ pat_blk = a.pat_blk;
+    const uint32_t lane = threadIdx.x & 63u, total = a.total;
+    const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * FM_WAVES;
+    for (uint64_t q = static_cast<uint64_t>(blockIdx.x) * FM_WAVES + (threadIdx.x >> 6); q < a.npat; q += nwaves) {
+        const uint32_t po = pat_off[q], m = pat_off[q + 1] - po;
+        const uint32_t b = pat_blk ? pat_blk[q] : 0u, s = off[b], nb = off[b + 1] - s;  // (b < count: the caller's check)
+        const uint32_t origin = a.blocks[4 * static_cast<size_t>(b) + 2], last = a.blocks[4 * static_cast<size_t>(b) + 3];
+        const uint32_t *__restrict__ base = a.base + static_cast<size_t>(b) * 256;
+        const uint8_t *p = pat + po;
+        uint32_t lo = 0, hi = nb;
+        for (uint32_t j = m; j-- > 0;) {
+            const uint32_t c = p[j], is_last = c == last ? 1u : 0u, first = j + 1u == m ? 1u : 0u;
+            const uint32_t bc = base[c];
+            if (lo != hi || first) {
+                uint32_t rl, rh;
+                fm_rank2(L, total, cp, c, s + lo, s + hi, lane, rl, rh);
+                lo = bc + (is_last & ~first) - (is_last & (origin < lo ? 1u : 0u)) + rl;
+                hi = bc + is_last - (is_last & (origin < hi ? 1u : 0u)) + rh;
+            } else {
+                lo = hi = bc + is_last - (is_last & (origin < lo ? 1u : 0u)) + fm_rank1(L, total, cp, c, s + lo, lane);
+            }
+            lo = lo < nb ? lo : nb;
+            hi = hi < nb ? hi : nb;
+        }
+        if (lane == 0) {
+            a.out_lo[q] = lo;
+            a.out_hi[q] = hi;
+        }
+    }
+}
+// out[q] = Occ_pack(sym[q], min(pos[q], total))
+__global__ __launch_bounds__(64 * FM_WAVES) void k_fm_rank(const uint8_t *__restrict__ L, uint32_t total, const uint32_t *__restrict__ cp,
+                                                          const uint32_t *__restrict__ pos, const uint8_t *__restrict__ sym, uint32_t nq,
+                                                          uint32_t *__restrict__ out) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * FM_WAVES;
+    for (uint64_t q = static_cast<uint64_t>(blockIdx.x) * FM_WAVES + (threadIdx.x >> 6); q < nq; q += nwaves) {
+        const uint32_t x = pos[q] < total ? pos[q] : total;
+        const uint32_t r = fm_rank1(L, total, cp, sym[q], x, lane);
+        if (lane == 0) out[q] = r;
+    }
+}
+
+}  // namespace
+
+size_t fm_build_workspace(size_t total, size_t count) {
+    const size_t rows = div_up(total, FM_BLOCK) + 1, rpc = div_up(rows, FM_MAX_CHUNKS), nchunks = div_up(rows, rpc);
+    auto r = [](size_t b) { return (b + 255) & ~size_t(255); };
+    return r(nchunks * 256 * 4) + r(4 * (count + 1)) + r(4 * count);
+}
+
+int fm_build_device(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector<uint32_t> &off, const uint32_t *origin, void *d_index) {
+    hipStream_t st = ctx->stream;
+    const size_t count = off.size() - 1, total = off.back();
+    const FmIndex ix = fm_carve(d_index, total, count);
+    const size_t rows = ix.rows, rpc = div_up(rows, FM_MAX_CHUNKS), nchunks = div_up(rows, rpc);
+    const size_t mark = ctx->ws_mark();
+    uint32_t *chunk_sum = ctx->ws_alloc<uint32_t>(nchunks * 256), *d_off = ctx->ws_alloc<uint32_t>(count + 1), *d_org = ctx->ws_alloc<uint32_t>(count);
+    if (!chunk_sum || !d_off || !d_org) return DK_E_NOMEM;
+    const uint32_t header[4] = {FM_MAGIC, static_cast<uint32_t>(total), static_cast<uint32_t>(count), static_cast<uint32_t>(rows)};
+    DK_HIP(ctx, hipMemsetAsync(d_index, 0, FM_HEADER * sizeof(uint32_t), st));
+    DK_HIP(ctx, hipMemcpyAsync(d_index, header, sizeof(header), hipMemcpyHostToDevice, st));
+    DK_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    int rc = ctx->hip_ok(hipMemcpyAsync(d_org, origin, count * sizeof(uint32_t), hipMemcpyHostToDevice, st), "origins");
+    if (rc == DK_OK) {
+        const uint32_t T = static_cast<uint32_t>(total), R = static_cast<uint32_t>(rows);
+        {
+            LaunchScope ls(ctx, K_IBWT_HIST, 1.0 * total + 3.0 * 1024 * rows);  // L once; the rows written, then read twice and written once by the scans
+            k_fm_hist<<<dim3(static_cast<unsigned>(div_up(rows, FM_WAVES))), dim3(64 * FM_WAVES), 0, st>>>(d_bwt, T, ix.cp, R);
+            k_fm_scan_a<<<dim3(static_cast<unsigned>(nchunks)), dim3(256), 0, st>>>(ix.cp, rows, rpc, chunk_sum);
+            k_fm_scan_b<<<dim3(1), dim3(256), 0, st>>>(chunk_sum, nchunks);
+            k_fm_scan_c<<<dim3(static_cast<unsigned>(nchunks)), dim3(256), 0, st>>>(ix.cp, rows, rpc, chunk_sum);
+        }
+        {
+            LaunchScope ls(ctx, K_IBWT_HIST, 3088.0 * count);  // two checkpoint rows, at most a row of L twice, base_b and four words
+            k_fm_heads<<<dim3(static_cast<unsigned>(count)), dim3(256), 0, st>>>(d_bwt, d_off, d_org, ix.cp, ix.blocks, ix.base);
+        }
+        rc = ctx->hip_ok(hipGetLastError(), "fm build");
+    }
+    const hipError_t e = hipStreamSynchronize(st);  // (also on failure: the copies above read `off`, `origin` and `header`)
+    DK_TRY(rc);
+    DK_HIP(ctx, e);
+    ctx->ws_release(mark);
+    return DK_OK;
+}
+
+int fm_count_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, const void *d_index, const uint8_t *d_pat,
+                    const uint32_t *d_pat_off, const uint32_t *d_pat_blk, size_t npat, size_t pat_bytes, uint32_t *d_lo, uint32_t *d_hi) {
+    const FmIndex ix = fm_carve(const_cast<void *>(d_index), total, count);
+    const unsigned grid = static_cast<unsigned>(std::min<size_t>(div_up(npat, FM_WAVES), 1u << 20));
+    const FmArgs a{d_bwt, d_off, ix.blocks, ix.base, ix.cp, d_pat, d_pat_off, d_pat_blk, static_cast<uint32_t>(npat), static_cast<uint32_t>(total),
+                   static_cast<uint32_t>(count), d_lo, d_hi};
+    {
+        // per step at most two gathered checkpoint words and two rows of L; the pattern bytes, the offsets and the two results
+        LaunchScope ls(ctx, K_CHAIN, 16.0 * npat + pat_bytes * (1.0 + 2.0 * (FM_BLOCK + 64)));
+        k_fm_count<<<dim3(grid), dim3(64 * FM_WAVES), 0, ctx->stream>>>(a);
+    }
+    DK_HIP(ctx, hipGetLastError());
+    return DK_OK;
+}
+
+int fm_rank_device(dk_ctx *ctx, const uint8_t *d_bwt, size_t total, const void *d_index, const uint32_t *d_pos, const uint8_t *d_sym, size_t nq,
+                   uint32_t *d_out) {
+    const FmIndex ix = fm_carve(const_cast<void *>(d_index), total, 0);  // (the checkpoints lie in front of everything that depends on the count)
+    const unsigned grid = static_cast<unsigned>(std::min<size_t>(div_up(nq, FM_WAVES), 1u << 20));
+    {
+        LaunchScope ls(ctx, K_CHAIN, nq * (9.0 + FM_BLOCK + 64));
+        k_fm_rank<<<dim3(grid), dim3(64 * FM_WAVES), 0, ctx->stream>>>(d_bwt, static_cast<uint32_t>(total), ix.cp, d_pos, d_sym, static_cast<uint32_t>(nq), d_out);
+    }
+    DK_HIP(ctx, hipGetLastError());
+    return DK_OK;
+}
+
+}  // namespace dk

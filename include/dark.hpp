@@ -2,6 +2,7 @@
 // The reference is compiled code (Rust); its toolchain is not in this image, so the host side a Rust caller would write is
 // given here in C++ with the same names, argument meaning and error behaviour:
 //   dark::saca::Constructor            src/saca.rs:344-384   new(max_n) / capacity() / compute(input); check / search are this library's
+//   dark::fm::Index                    this library's: count patterns in (L, origin) -- from_text / Index(bwt, origin) / count / occurrences
 //   dark::block::dc::Encoder<Model>    src/block/dc.rs:21-92  new(n, model) / encode(input, writer) -> (writer, result)
 //   dark::block::dc::Decoder<Model>    src/block/dc.rs:96-161 new(n, model) / decode(reader, writer) -> (reader, writer, result)
 //   dark::block::raw::Encoder<Model> / Decoder<Model>   src/block/raw.rs:17-105 (Model = model::bbb::Model or model::raw::Out)
@@ -257,5 +258,52 @@ inline std::vector<uint8_t> decode(detail::Ctx &ctx, const std::vector<uint8_t> 
     return out;
 }
 }  // namespace bwt
+
+namespace fm {
+// Counting patterns in a BWT without the text and without a suffix array (dk_fm_count): the index of (L, origin) as
+// bwt::transform or a stream decoder leaves them.  It lives on a DECODER context: nothing here needs the suffix sort's workspace.  Nothing in the
+// reference corresponds.  (This host-memory form builds the device index anew in every count; a caller that keeps L on the GPU uses
+// dk_dev_fm_build once and dk_dev_fm_count after it.)
+class Index {
+public:
+    Index(std::vector<uint8_t> bwt, size_t origin, int device = 0) : ctx_(bwt.size(), device, DK_CTX_DECODER), bwt_(std::move(bwt)), origin_(origin) {
+        if (origin_ >= bwt_.size()) throw Error(DK_E_ARG, "assertion failed: origin < bwt.len()");
+    }
+    // the index of a text: forward BWT on a full context that is released again, then as above
+    static Index from_text(const std::vector<uint8_t> &text, int device = 0) {
+        detail::Ctx full(text.size(), device);
+        auto lo = bwt::transform(full, text);
+        return Index(std::move(lo.first), lo.second, device);
+    }
+    size_t len() const { return bwt_.size(); }
+    // device bytes that answer a query: L and the index
+    size_t resident_bytes() const { return bwt_.size() + dk_fm_index_bytes(bwt_.size(), 1); }
+    // result[q] = (lo, hi) as from saca::Constructor::search on the text; hi - lo = the number of places patterns[q] occurs
+    std::vector<std::pair<uint32_t, uint32_t>> count(const std::vector<std::vector<uint8_t>> &patterns) {
+        std::vector<size_t> lens;
+        std::vector<uint8_t> bytes(1);  // (one byte so that data() is never null)
+        for (const auto &p : patterns) {
+            lens.push_back(p.size());
+            bytes.insert(bytes.end(), p.begin(), p.end());
+        }
+        std::vector<uint32_t> lo(patterns.size() + 1), hi(patterns.size() + 1);
+        int rc = dk_fm_count(ctx_.get(), bwt_.data(), bwt_.size(), static_cast<uint32_t>(origin_), bytes.data() + 1, patterns.size(), lens.data(), lo.data(), hi.data());
+        if (rc != DK_OK) throw Error(rc, ctx_.error());
+        std::vector<std::pair<uint32_t, uint32_t>> out;
+        for (size_t q = 0; q < patterns.size(); ++q) out.emplace_back(lo[q], hi[q]);
+        return out;
+    }
+    std::vector<uint32_t> occurrences(const std::vector<std::vector<uint8_t>> &patterns) {
+        std::vector<uint32_t> out;
+        for (const auto &r : count(patterns)) out.push_back(r.second - r.first);
+        return out;
+    }
+    detail::Ctx &context() { return ctx_; }  // context().purpose() == DK_CTX_DECODER
+private:
+    detail::Ctx ctx_;
+    std::vector<uint8_t> bwt_;
+    size_t origin_;
+};
+}  // namespace fm
 
 }  // namespace dark

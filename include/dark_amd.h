@@ -251,6 +251,34 @@ int dk_sa_search(dk_ctx *full_ctx, const uint8_t *in, size_t n, const uint32_t *
 int dk_dev_sa_search_packed(dk_ctx *full_ctx, const uint8_t *d_in, size_t count, const size_t *n, const uint32_t *d_sa,
                             const uint8_t *d_pat, size_t npat, const size_t *pat_len, const uint32_t *pat_block,
                             uint32_t *d_lo, uint32_t *d_hi);
+/* ---- FM-index: count patterns in a BWT, without the text and without a suffix array (csrc/fm_index.hip) ----
+ * Backward search on L itself.  The index is an opaque DEVICE buffer of dk_fm_index_bytes(total, count) bytes that the caller supplies (4-byte
+ * aligned): checkpointed symbol counts of the pack every 1024 positions and 1040 bytes per block, about `total` bytes in all; with L itself
+ * about 2 n bytes stay resident, against the 5 n of text and suffix array that dk_dev_sa_search needs.  dk_fm_index_bytes needs no GPU and
+ * returns 0 for what the pack checks refuse (total == 0 or > 2^31 - 2, count == 0 or > DK_PACKED_MAX_BLOCKS, count > total).
+ * (d_bwt, origin) are what dk_dev_bwt_forward / dk_dev_bwt_forward_packed / dk_stream_decode give; d_bwt, any alignment, must stay as it was
+ * when the index was built.  dk_dev_fm_count* give, for the same patterns in the same layout (pat_len / pat_block in HOST memory), exactly
+ * the d_lo / d_hi of dk_dev_sa_search*, insertion slots of absent patterns included; hi - lo = the number of occurrences.  Same error cases;
+ * also DK_E_ARG for origin >= n and an index that is not 4-byte aligned.  The recurrence is defined for ANY bytes L and any origin < n.
+ * any_ctx: a context of EITHER purpose, as the parameter's name says (full_ctx above: DK_CTX_FULL only): decoder contexts serve every entry
+ * of this section; their own max_blocks limits a pack.  Workspace: the build takes at most
+ * 256 KiB + 8 bytes per block, the count 8 bytes per pattern + 4 per block.
+ * The index is TRUSTED.  For any bytes in it, in L and in the patterns the geometry is the caller's, every position is clamped to its block
+ * before use: results are then unspecified but <= n_i, and nothing outside L, the index, the patterns and the two results is touched. */
+size_t dk_fm_index_bytes(size_t total, size_t count);
+int dk_dev_fm_build(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t n, uint32_t origin, void *d_index);
+int dk_dev_fm_build_packed(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const uint32_t *origin /* host */, void *d_index);
+int dk_dev_fm_count(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t n, const void *d_index,
+                    const uint8_t *d_pat, size_t npat, const size_t *pat_len, uint32_t *d_lo, uint32_t *d_hi);
+int dk_dev_fm_count_packed(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const void *d_index,
+                           const uint8_t *d_pat, size_t npat, const size_t *pat_len, const uint32_t *pat_block, uint32_t *d_lo, uint32_t *d_hi);
+/* from and to host memory: L and the patterns are uploaded, the index built, lo and hi downloaded.  DK_E_ARG when L, the index, the patterns,
+ * their offsets and the results (about 2 n + the patterns + 12 bytes per pattern) do not fit the workspace. */
+int dk_fm_count(dk_ctx *any_ctx, const uint8_t *bwt, size_t n, uint32_t origin,
+                const uint8_t *pat, size_t npat, const size_t *pat_len, uint32_t *lo, uint32_t *hi);
+/* for the tests: d_out[q] = occurrences of d_sym[q] in d_bwt[0, min(d_pos[q], total)), computed by the count kernel's rank (all device memory) */
+int dk_dbg_dev_fm_rank(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t total, const void *d_index,
+                       const uint32_t *d_pos, const uint8_t *d_sym, size_t nq, uint32_t *d_out);
 /* DC arrays of a packed L: block i's entries at [off_i, off_i + m[i]) of d_dist / d_sym / d_rank (device, sum of n entries each; d_rank may
  * be NULL), init (host, count x 256: block i's table at init[256 i]) and m (host, count) as from dk_dev_dc_encode */
 int dk_dev_dc_encode_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, const size_t *n, uint32_t *init, uint32_t *d_dist, uint8_t *d_sym,

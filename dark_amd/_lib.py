@@ -8,6 +8,7 @@ SO_PATH = os.environ.get("DARK_AMD_LIB") or os.path.join(HERE, "libdark_amd.so")
 
 DK_OK = 0
 DK_E_ARG, DK_E_NOMEM, DK_E_HIP, DK_E_CAPACITY, DK_E_MODEL, DK_E_STREAM, DK_E_INTERNAL, DK_E_NODEVICE = -1, -2, -3, -4, -5, -6, -7, -8
+FM_NO_HIT = 0xFFFFFFFF  # DK_FM_NO_HIT: a position dk_dev_fm_locate* did not fill
 ERROR_NAMES = {-1: "DK_E_ARG", -2: "DK_E_NOMEM", -3: "DK_E_HIP", -4: "DK_E_CAPACITY", -5: "DK_E_MODEL",
                -6: "DK_E_STREAM", -7: "DK_E_INTERNAL", -8: "DK_E_NODEVICE"}
 MODEL_IDS = {"dark": 0, "exp": 1, "ybs": 2, "simple": 3, "rawdc": 4}
@@ -88,6 +89,12 @@ SIGNATURES = {
     "dk_dev_fm_count": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp]),
     "dk_dev_fm_count_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "dk_fm_count": (_i, [_vp, _vp, _sz, C.c_uint32, _vp, _sz, _vp, _vp, _vp]),
+    "dk_fm_locate_bytes": (_sz, [_sz, _sz, C.c_uint32]),
+    "dk_dev_fm_locate_build": (_i, [_vp, _vp, _sz, C.c_uint32, C.c_uint32, _vp]),
+    "dk_dev_fm_locate_build_packed": (_i, [_vp, _vp, _sz, _vp, _vp, C.c_uint32, _vp]),
+    "dk_dev_fm_locate": (_i, [_vp, _vp, _sz, _vp, _vp, C.c_uint32, _vp, _vp, _sz, _sz, _vp]),
+    "dk_dev_fm_locate_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "dk_fm_locate": (_i, [_vp, _vp, _sz, C.c_uint32, C.c_uint32, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
     "dk_dbg_dev_fm_rank": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
     "dk_dev_dc_encode_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _szp]),
     "dk_batch_push_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),

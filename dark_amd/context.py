@@ -82,6 +82,14 @@ def fm_index_bytes(total, count=1):
     return int(_lib.load().dk_fm_index_bytes(int(total), int(count)))
 
 
+def fm_locate_bytes(total, count=1, step=32):
+    """dk_fm_locate_bytes: bytes of the locate structure beside that index at sampling step `step`; needs no GPU.  0 for what fm_index_bytes
+    refuses and for a step that is no power of two in [1, 4096]."""
+    if total < 0 or count < 0 or not 0 <= step < 2 ** 32:
+        return 0
+    return int(_lib.load().dk_fm_locate_bytes(int(total), int(count), int(step)))
+
+
 class Context:
     def __init__(self, max_n, device=0, purpose="full", max_blocks=1):
         """purpose="decoder": a context for the inverse path only (dk_ctx_create_decoder), about a fifth of the workspace; max_blocks = most
@@ -434,6 +442,49 @@ class Context:
         lo, hi = np.zeros(npat, dtype=np.uint32), np.zeros(npat, dtype=np.uint32)
         self._ck(self._lib.dk_fm_count(self._h, _ptr(b), len(b), int(origin), _ptr(pat), npat, lens, _ptr(lo), _ptr(hi)))
         return lo, hi
+
+    # ---- FM-index locate: positions from a sampled suffix array beside the index; decoder contexts too ----
+    def dev_fm_locate_build(self, d_bwt, n, origin, step, d_loc):
+        """the locate structure of d_bwt[0, n) with its origin into d_loc, a device tensor of fm_locate_bytes(n, 1, step) bytes; needs no index"""
+        _inputs_ready(d_bwt)
+        self._ck(self._lib.dk_dev_fm_locate_build(self._h, _ptr(d_bwt), n, int(origin), int(step), _ptr(d_loc)))
+
+    def dev_fm_locate_build_packed(self, d_bwt, sizes, origins, step, d_loc):
+        """one structure for every block of a packed L; d_loc: fm_locate_bytes(sum(sizes), len(sizes), step) bytes"""
+        _inputs_ready(d_bwt)
+        count = len(sizes)
+        if len(origins) != count:
+            raise DarkError(_lib.DK_E_ARG, "%d origins for %d blocks" % (len(origins), count))
+        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
+        org = np.array(origins, dtype=np.int64).astype(np.uint32) if count else np.zeros(1, np.uint32)
+        self._ck(self._lib.dk_dev_fm_locate_build_packed(self._h, _ptr(d_bwt), count, ns, _ptr(org), int(step), _ptr(d_loc)))
+
+    def dev_fm_locate(self, d_bwt, n, d_index, d_loc, step, d_lo, d_hi, npat, max_hits, d_pos):
+        """d_pos[q * max_hits + j] = the text position of slot d_lo[q] + j for j < min(d_hi[q] - d_lo[q], max_hits), FM_NO_HIT behind them;
+        d_lo / d_hi as dev_fm_count wrote them, d_pos a uint32 device tensor of npat * max_hits words"""
+        _inputs_ready(d_bwt, d_index, d_loc, d_lo, d_hi)
+        self._ck(self._lib.dk_dev_fm_locate(self._h, _ptr(d_bwt), n, _ptr(d_index), _ptr(d_loc), int(step), _ptr(d_lo), _ptr(d_hi), int(npat),
+                                            int(max_hits), _ptr(d_pos)))
+
+    def dev_fm_locate_packed(self, d_bwt, sizes, d_index, d_loc, step, d_lo, d_hi, pat_blocks, max_hits, d_pos):
+        """dev_fm_locate in a pack: row q holds positions local to block pat_blocks[q]"""
+        _inputs_ready(d_bwt, d_index, d_loc, d_lo, d_hi)
+        count, npat = len(sizes), len(pat_blocks)
+        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
+        blocks = np.array(pat_blocks, dtype=np.int64).astype(np.uint32) if npat else np.zeros(1, np.uint32)
+        self._ck(self._lib.dk_dev_fm_locate_packed(self._h, _ptr(d_bwt), count, ns, _ptr(d_index), _ptr(d_loc), int(step), _ptr(d_lo), _ptr(d_hi),
+                                                   npat, _ptr(blocks), int(max_hits), _ptr(d_pos)))
+
+    def fm_locate(self, bwt, origin, patterns, max_hits=16, step=32):
+        """(lo, hi, pos) from (L, origin) in host memory: lo / hi as fm_count gives them, pos a uint32 array of len(patterns) x max_hits whose
+        row q starts with the first min(hi - lo, max_hits) text positions of pattern q in suffix-array order, FM_NO_HIT behind (dk_fm_locate)"""
+        b = as_u8(bwt)
+        pat, lens, npat = _pack_patterns(patterns)
+        lo, hi = np.zeros(npat, dtype=np.uint32), np.zeros(npat, dtype=np.uint32)
+        pos = np.zeros((npat, max(int(max_hits), 1)), dtype=np.uint32)
+        self._ck(self._lib.dk_fm_locate(self._h, _ptr(b), len(b), int(origin), int(step), _ptr(pat), npat, lens, int(max_hits), _ptr(lo), _ptr(hi),
+                                        _ptr(pos)))
+        return lo, hi, pos
 
     def dbg_dev_fm_rank(self, d_bwt, total, d_index, d_pos, d_sym, d_out):
         """d_out[q] = occurrences of d_sym[q] in d_bwt[0, d_pos[q]) by the count kernel's rank (uint32 / uint8 / uint32 device tensors)"""

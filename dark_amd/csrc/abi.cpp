@@ -111,6 +111,8 @@ size_t decoder_workspace_bytes(size_t max_n, size_t max_blocks) {
     // The larger of the two, + n / 64 + 64 KiB of headroom.  The pinned staging (ensure_stage, ensure_slot) is host memory and not part of this.
     // The FM-index entries (fm_index.hip) are served too and stay below all of that: the build takes chunk sums of at most min(256 KiB, n + 2 KiB)
     // and 8 bytes per block, the host-pointer form 2 n + 3 KiB beside them (tests/test_gpu_fm.py checks peak <= size on both purposes).
+    // The locate structure's build (bwt.hip: fm_locate_build_device) is the packed inverse above without its records, for one block too, so it
+    // fits whatever fits `packed`; dk_fm_locate refuses what does not fit (tests/test_gpu_fm_locate.py checks peak <= size on both purposes).
     // tests/test_gpu_decoder_ctx.py checks peak <= size on contexts sized exactly to their block or pack, through every entry above.
     const size_t single = 2 * ((max_n + 255) & ~size_t(255)) + bwt_inverse_workspace(max_n);
     const size_t packed = ((max_n + 255) & ~size_t(255)) + packed_ibwt_workspace(max_n, max_blocks);
@@ -1495,6 +1497,153 @@ int dk_fm_count(dk_ctx *ctx, const uint8_t *bwt, size_t n, uint32_t origin, cons
     DK_TRY(fm_count_run(ctx, d_bwt, d_off, 1, n, d_index, d_pat, p, nullptr, d_lo, d_hi));
     DK_HIP(ctx, hipMemcpyAsync(lo, d_lo, npat * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     DK_HIP(ctx, hipMemcpyAsync(hi, d_hi, npat * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    DK_HIP(ctx, hipStreamSynchronize(st));
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+// ---- locate: a sampled suffix array beside the index, built from (L, origin) alone ------------------------------------
+}  // extern "C"
+
+namespace {
+bool fm_good_step(uint32_t step) { return step >= 1 && step <= 4096 && (step & (step - 1)) == 0; }
+int fm_locate_args(dk_ctx *ctx, uint32_t step, const void *d_loc) {
+    if (!fm_good_step(step)) return ctx->fail(DK_E_ARG, "the sampling step %u is no power of two in [1, 4096]", step);
+    if (!fm_good_index(d_loc)) return ctx->fail(DK_E_ARG, "the locate structure is not 4-byte aligned");
+    return DK_OK;
+}
+int fm_locate_hits(dk_ctx *ctx, size_t npat, size_t max_hits) {
+    if (max_hits == 0 || npat > 0xFFFFFFFEull || max_hits > (size_t(1) << 31) || npat * max_hits > (size_t(1) << 31))
+        return ctx->fail(DK_E_ARG, "%zu patterns of at most %zu hits: 1 .. 2^31 positions in all", npat, max_hits);
+    return DK_OK;
+}
+}  // namespace
+
+extern "C" {
+
+size_t dk_fm_locate_bytes(size_t total, size_t count, uint32_t step) {
+    if (dk_fm_index_bytes(total, count) == 0 || !fm_good_step(step)) return 0;
+    return fm_locate_words(total, count, step) * sizeof(uint32_t);
+}
+
+int dk_dev_fm_locate_build(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t origin, uint32_t step, void *d_loc) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!d_bwt || !d_loc) return ctx->fail(DK_E_ARG, "null pointer");
+    DK_TRY(fm_locate_args(ctx, step, d_loc));
+    DK_TRY(check_n(ctx, n));
+    if (origin >= n) return ctx->fail(DK_E_ARG, "origin %u is outside the block of %zu bytes", origin, n);
+    Timer t;
+    DK_TRY(fm_locate_build_device(ctx, d_bwt, {0u, static_cast<uint32_t>(n)}, &origin, step, d_loc, false));
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_dev_fm_locate_build_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const uint32_t *origin, uint32_t step, void *d_loc) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!d_bwt || !n || !origin || !d_loc) return ctx->fail(DK_E_ARG, "null pointer");
+    DK_TRY(fm_locate_args(ctx, step, d_loc));
+    std::vector<uint32_t> off;
+    DK_TRY(check_pack(ctx, count, n, off));
+    for (size_t i = 0; i < count; ++i)
+        if (origin[i] >= n[i]) return ctx->fail(DK_E_ARG, "origin %u of block %zu is outside its %zu bytes", origin[i], i, n[i]);
+    Timer t;
+    DK_TRY(fm_locate_build_device(ctx, d_bwt, off, origin, step, d_loc, true));
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_dev_fm_locate(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, const void *d_index, const void *d_loc, uint32_t step, const uint32_t *d_lo,
+                     const uint32_t *d_hi, size_t npat, size_t max_hits, uint32_t *d_pos) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!d_bwt || !d_index || !d_loc) return ctx->fail(DK_E_ARG, "null pointer");
+    if (!fm_good_index(d_index)) return ctx->fail(DK_E_ARG, "the index is not 4-byte aligned");
+    DK_TRY(fm_locate_args(ctx, step, d_loc));
+    DK_TRY(check_n(ctx, n));
+    if (npat == 0) return DK_OK;
+    DK_TRY(fm_locate_hits(ctx, npat, max_hits));
+    if (!d_lo || !d_hi || !d_pos) return ctx->fail(DK_E_ARG, "null pointer");
+    if ((reinterpret_cast<uintptr_t>(d_lo) | reinterpret_cast<uintptr_t>(d_hi) | reinterpret_cast<uintptr_t>(d_pos)) & 3)
+        return ctx->fail(DK_E_ARG, "the ranges or the positions are not 4-byte aligned");
+    Timer t;
+    uint32_t *d_off = nullptr;
+    DK_TRY(single_offsets(ctx, n, &d_off));
+    DK_TRY(fm_locate_device(ctx, d_bwt, d_off, 1, n, d_index, d_loc, step, d_lo, d_hi, nullptr, npat, max_hits, d_pos));
+    DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_dev_fm_locate_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const void *d_index, const void *d_loc, uint32_t step,
+                            const uint32_t *d_lo, const uint32_t *d_hi, size_t npat, const uint32_t *pat_block, size_t max_hits, uint32_t *d_pos) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!d_bwt || !n || !d_index || !d_loc) return ctx->fail(DK_E_ARG, "null pointer");
+    if (!fm_good_index(d_index)) return ctx->fail(DK_E_ARG, "the index is not 4-byte aligned");
+    DK_TRY(fm_locate_args(ctx, step, d_loc));
+    std::vector<uint32_t> off;
+    DK_TRY(check_pack(ctx, count, n, off));
+    if (npat == 0) return DK_OK;
+    DK_TRY(fm_locate_hits(ctx, npat, max_hits));
+    if (!pat_block || !d_lo || !d_hi || !d_pos) return ctx->fail(DK_E_ARG, "null pointer");
+    if ((reinterpret_cast<uintptr_t>(d_lo) | reinterpret_cast<uintptr_t>(d_hi) | reinterpret_cast<uintptr_t>(d_pos)) & 3)
+        return ctx->fail(DK_E_ARG, "the ranges or the positions are not 4-byte aligned");
+    for (size_t q = 0; q < npat; ++q)
+        if (pat_block[q] >= count) return ctx->fail(DK_E_ARG, "pattern %zu names block %u of a pack of %zu", q, pat_block[q], count);
+    Timer t;
+    hipStream_t st = ctx->stream;
+    uint32_t *d_off = ctx->ws_alloc<uint32_t>(count + 1), *d_blk = ctx->ws_alloc<uint32_t>(npat);
+    if (!d_off || !d_blk) return DK_E_NOMEM;
+    DK_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    int rc = ctx->hip_ok(hipMemcpyAsync(d_blk, pat_block, npat * sizeof(uint32_t), hipMemcpyHostToDevice, st), "pattern blocks");
+    if (rc == DK_OK) rc = fm_locate_device(ctx, d_bwt, d_off, count, off.back(), d_index, d_loc, step, d_lo, d_hi, d_blk, npat, max_hits, d_pos);
+    const hipError_t e = hipStreamSynchronize(st);  // (also on failure: the copy above reads `off`)
+    DK_TRY(rc);
+    DK_HIP(ctx, e);
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_fm_locate(dk_ctx *ctx, const uint8_t *bwt, size_t n, uint32_t origin, uint32_t step, const uint8_t *pat, size_t npat, const size_t *pat_len,
+                 size_t max_hits, uint32_t *lo, uint32_t *hi, uint32_t *pos) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!bwt) return ctx->fail(DK_E_ARG, "null pointer");
+    if (!fm_good_step(step)) return ctx->fail(DK_E_ARG, "the sampling step %u is no power of two in [1, 4096]", step);
+    DK_TRY(check_n(ctx, n));
+    if (origin >= n) return ctx->fail(DK_E_ARG, "origin %u is outside the block of %zu bytes", origin, n);
+    if (npat == 0) return DK_OK;
+    DK_TRY(fm_locate_hits(ctx, npat, max_hits));
+    Timer t;
+    Patterns p;
+    DK_TRY(check_patterns(ctx, npat, pat_len, nullptr, 1, p));
+    if ((!pat && p.bytes()) || !lo || !hi || !pos) return ctx->fail(DK_E_ARG, "null pointer");
+    // L, the index, the structure and the block's two offsets; the patterns, their offsets, the two results and the positions; the larger of
+    // the two builds' workspaces while it runs
+    const size_t index_words = fm_index_words(n, 1), loc_words = fm_locate_words(n, 1, step), nitems = npat * max_hits;
+    const size_t need = ws_round(n) + ws_round(4 * index_words) + ws_round(4 * loc_words) + 256 + ws_round(p.bytes()) + ws_round(4 * (npat + 1)) +
+                        2 * ws_round(4 * npat) + ws_round(4 * nitems) + std::max(fm_build_workspace(n, 1), fm_locate_build_workspace(n, 1));
+    if (need > ctx->ws_size)
+        return ctx->fail(DK_E_ARG, "%zu patterns of %zu bytes with %zu positions each do not fit the workspace beside L, its index and the locate build",
+                         npat, p.bytes(), max_hits);
+    hipStream_t st = ctx->stream;
+    uint8_t *d_bwt = ctx->ws_alloc<uint8_t>(n), *d_pat = ctx->ws_alloc<uint8_t>(std::max<size_t>(p.bytes(), 1));
+    uint32_t *d_index = ctx->ws_alloc<uint32_t>(index_words), *d_loc = ctx->ws_alloc<uint32_t>(loc_words);
+    uint32_t *d_lo = ctx->ws_alloc<uint32_t>(npat), *d_hi = ctx->ws_alloc<uint32_t>(npat), *d_pos = ctx->ws_alloc<uint32_t>(nitems);
+    uint32_t *d_off = nullptr;
+    if (!d_bwt || !d_pat || !d_index || !d_loc || !d_lo || !d_hi || !d_pos) return DK_E_NOMEM;
+    DK_TRY(single_offsets(ctx, n, &d_off));
+    DK_HIP(ctx, hipMemcpyAsync(d_bwt, bwt, n, hipMemcpyHostToDevice, st));
+    if (p.bytes()) DK_HIP(ctx, hipMemcpyAsync(d_pat, pat, p.bytes(), hipMemcpyHostToDevice, st));
+    DK_TRY(fm_build_device(ctx, d_bwt, {0u, static_cast<uint32_t>(n)}, &origin, d_index));
+    DK_TRY(fm_locate_build_device(ctx, d_bwt, {0u, static_cast<uint32_t>(n)}, &origin, step, d_loc, false));
+    DK_TRY(fm_count_run(ctx, d_bwt, d_off, 1, n, d_index, d_pat, p, nullptr, d_lo, d_hi));
+    DK_TRY(fm_locate_device(ctx, d_bwt, d_off, 1, n, d_index, d_loc, step, d_lo, d_hi, nullptr, npat, max_hits, d_pos));
+    DK_HIP(ctx, hipMemcpyAsync(lo, d_lo, npat * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    DK_HIP(ctx, hipMemcpyAsync(hi, d_hi, npat * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    DK_HIP(ctx, hipMemcpyAsync(pos, d_pos, nitems * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     DK_HIP(ctx, hipStreamSynchronize(st));
     ctx->stats.ms_total = t.ms();
     return DK_OK;

@@ -13,6 +13,8 @@
 //   k_ibwt_rank          pointer jumping over the reduced list -> text offset of every splitter
 //   k_ibwt_emit          one lane per splitter re-walks its sub-list and writes the text bytes
 // Packed inverse (k_pib_*): the same stages over many blocks laid back to back, segmented by the offsets table.
+// The FM-index's locate structure (fm_locate_build_device): the packed inverse's table, walk and jumps, then k_pib_locate
+// twice where the inverse writes the text -- the walk knows the text position of every slot it passes.
 #include <algorithm>
 
 #include "context.hpp"
@@ -605,6 +607,65 @@ __global__ __launch_bounds__(256) void k_pib_copy(const uint64_t *__restrict__ p
     w.flush();
 }
 
+// ---- the FM-index's locate structure (layout: context.hpp fm_locate_words) ----------------------------------------
+// The splitter at position cur with dist_to_end d is the slot of suffix n_b - d of its block, and every psi step from it that of the next
+// suffix: the walk of k_pib_emit, which here looks at text positions instead of writing text bytes.  Two passes of one kernel.  MARK sets the
+// bit of every slot whose (block-local) text position is a multiple of the step, with a vector atomicOr on zeroed words (32 slots of a word
+// belong to as many lanes).  After the rows' counts are scanned, SAMPLE stores position / step at the slot's rank among the marks; every
+// marked slot has its own entry, so these are plain stores.  Both run behind k_pib_check: every d is in [1, n_b] and every walk stays in
+// its block; the tests below keep a walk inside the block and the entry inside the samples whatever the tables hold.
+template <bool SAMPLE>
+__global__ __launch_bounds__(256) void k_pib_locate(const uint64_t *__restrict__ psi, const uint32_t *__restrict__ off, const uint32_t *__restrict__ org,
+                                                     const uint32_t *__restrict__ sb, uint32_t count, uint32_t S, uint32_t nsplit,
+                                                     const uint32_t *__restrict__ dist_to_end, uint32_t step_shift, uint32_t *__restrict__ bits,
+                                                     const uint32_t *__restrict__ marks, uint32_t *__restrict__ samples, uint32_t nsamp) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= nsplit) return;
+    const PibBlock b = pib_block(off, org, sb, count, S, s);
+    const uint32_t d = dist_to_end[s], mask = (1u << step_shift) - 1u;
+    if (d == 0 || d > b.n) return;
+    uint32_t cur = pib_start(b, S, s), pos = b.n - d;
+    for (;;) {
+        if ((pos & mask) == 0) {
+            const uint32_t word = cur >> 5, bit = 1u << (cur & 31u);
+            if (!SAMPLE) {
+                atomicOr(&bits[word], bit);
+            } else {
+                uint32_t r = marks[cur >> 10] + __popc(bits[word] & (bit - 1u));
+                for (uint32_t w = word & ~31u; w < word; ++w) r += __popc(bits[w]);
+                if (r < nsamp) samples[r] = pos >> step_shift;
+            }
+        }
+        const uint32_t p = static_cast<uint32_t>(psi[cur]);
+        if (p == IB_END || p - b.s0 >= b.n || pib_splitter_at(b, S, p) != IB_END || ++pos >= b.n) break;
+        cur = p;
+    }
+}
+// marks[r] = set bits of row r (32 words of 32 slots)
+__global__ __launch_bounds__(256) void k_loc_rows(const uint32_t *__restrict__ bits, uint32_t rows, uint32_t *__restrict__ marks) {
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    uint32_t c = 0;
+#pragma unroll
+    for (int k = 0; k < 32; ++k) c += __popc(bits[32 * static_cast<size_t>(r) + k]);  // (words: d_loc is only 4-byte aligned)
+    marks[r] = c;
+}
+// exclusive scan of marks[0, rows) in place, marks[rows] = all marks.  One workgroup: a stretch of rows per thread, summed, scanned over the
+// workgroup, written back (one column where k_fm_scan_a/b/c have 256: 4 bytes per KiB of L, no chunk sums to keep)
+__global__ __launch_bounds__(1024) void k_loc_scan(uint32_t *__restrict__ marks, uint32_t rows) {
+    __shared__ uint32_t s_tmp[16 + 1];
+    const uint32_t per = (rows + 1023u) / 1024u, r0 = min(threadIdx.x * per, rows), r1 = min(r0 + per, rows);
+    uint32_t sum = 0, all = 0;
+    for (uint32_t r = r0; r < r1; ++r) sum += marks[r];
+    uint32_t run = block_excl_sum<16>(sum, s_tmp, &all);
+    for (uint32_t r = r0; r < r1; ++r) {
+        const uint32_t v = marks[r];
+        marks[r] = run;
+        run += v;
+    }
+    if (threadIdx.x == 0) marks[rows] = all;
+}
+
 }  // namespace
 
 // the origin word back: some kernel has stored the slot of suffix 0 there, whichever way L was written
@@ -817,6 +878,106 @@ int packed_ibwt_device(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector<uint
     return DK_OK;
 }
 
+// The locate structure: packed_ibwt_device's table, walk (no records), jumps and check, then k_pib_locate twice where the inverse writes the
+// text.  A single block is a pack of one here (S = 64 at every size): the workspace is the packed inverse's without its records, which every
+// context that can invert the block or pack holds.
+int fm_locate_build_device(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector<uint32_t> &off, const uint32_t *origin, uint32_t step, void *d_loc,
+                           bool packed) {
+    hipStream_t st = ctx->stream;
+    const size_t count = off.size() - 1, total = off.back();
+    const uint32_t cnt = static_cast<uint32_t>(count), T = static_cast<uint32_t>(total);
+    const FmLocate lc = fm_locate_carve(d_loc, total, count, step);
+    const size_t mark = ctx->ws_mark();
+    constexpr uint32_t S = 64;
+    std::vector<uint32_t> aux(3 * count + 2);  // off | origin | first splitter of every block, as in packed_ibwt_device
+    std::copy(off.begin(), off.end(), aux.begin());
+    uint32_t *h_org = aux.data() + count + 1, *h_sb = h_org + count;
+    uint32_t nsplit = 0, max_split = 1;
+    for (size_t i = 0; i < count; ++i) {
+        h_org[i] = origin[i];
+        h_sb[i] = nsplit;
+        const uint32_t k = static_cast<uint32_t>(div_up(off[i + 1] - off[i], S)) + (origin[i] % S ? 1u : 0u);
+        max_split = std::max(max_split, k);
+        nsplit += k;
+    }
+    h_sb[count] = nsplit;
+    const size_t ntiles = div_up(total, IB_TILE), tpc = div_up(ntiles, IB_MAX_CHUNKS), nchunks = div_up(ntiles, tpc);
+    uint32_t *d_aux = ctx->ws_alloc<uint32_t>(aux.size());
+    uint32_t *tile_hist = ctx->ws_alloc<uint32_t>(ntiles * 256);
+    uint32_t *chunk_sum = ctx->ws_alloc<uint32_t>(nchunks * 256);
+    uint32_t *class_start = ctx->ws_alloc<uint32_t>(256);
+    uint32_t *base = ctx->ws_alloc<uint32_t>(count * 256);
+    uint32_t *cls0 = ctx->ws_alloc<uint32_t>(count);
+    uint64_t *psi = ctx->ws_alloc<uint64_t>(total);
+    uint32_t *nxt = ctx->ws_alloc<uint32_t>(nsplit), *nxt_alt = ctx->ws_alloc<uint32_t>(nsplit);
+    uint32_t *acc = ctx->ws_alloc<uint32_t>(nsplit), *acc_alt = ctx->ws_alloc<uint32_t>(nsplit);
+    if (!d_aux || !tile_hist || !chunk_sum || !class_start || !base || !cls0 || !psi || !nxt || !nxt_alt || !acc || !acc_alt) return DK_E_NOMEM;
+    const uint32_t *d_off = d_aux, *d_org = d_aux + count + 1, *d_sb = d_org + count;
+    const uint32_t header[6] = {FM_LOC_MAGIC, T, cnt, step, static_cast<uint32_t>(lc.rows), static_cast<uint32_t>(lc.nsamp)};
+    // the header, the marks and the mark bits start as zeros (the samples are written one by one)
+    DK_HIP(ctx, hipMemsetAsync(d_loc, 0, (FM_LOC_HEADER + 33 * lc.rows + 1) * sizeof(uint32_t), st));
+    DK_HIP(ctx, hipMemcpyAsync(d_loc, header, sizeof(header), hipMemcpyHostToDevice, st));
+    int rc = ctx->hip_ok(hipMemcpyAsync(d_aux, aux.data(), aux.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st), "pack geometry");
+    const unsigned sgrid = static_cast<unsigned>(div_up(nsplit, 256));
+    uint32_t *d_bad = &ctx->d_mail->packed.ibwt_bad;
+    if (rc == DK_OK) {
+        {
+            LaunchScope ls(ctx, K_IBWT_HIST, 1.0 * total + 2048.0 * count);
+            k_ibwt_hist<<<dim3(ntiles), dim3(IB_BLOCK), 0, st>>>(d_bwt, total, tile_hist);
+            k_ibwt_scan_a<<<dim3(nchunks), dim3(256), 0, st>>>(tile_hist, ntiles, tpc, chunk_sum);
+            k_ibwt_scan_b<<<dim3(1), dim3(256), 0, st>>>(chunk_sum, nchunks, class_start);
+            k_ibwt_scan_c<<<dim3(nchunks), dim3(256), 0, st>>>(tile_hist, ntiles, tpc, chunk_sum);
+            k_pib_heads<<<dim3(cnt), dim3(256), 0, st>>>(d_bwt, d_off, d_org, static_cast<uint32_t>(ntiles), tile_hist, base, cls0);
+        }
+        {
+            LaunchScope ls(ctx, K_IBWT_LF, 5.0 * total);
+            k_pib_lf<<<dim3(ntiles), dim3(IB_BLOCK), 0, st>>>(d_bwt, T, d_off, cnt, d_org, tile_hist, base, cls0, psi);
+        }
+        {
+            LaunchScope ls(ctx, K_IBWT_WALK, 4.0 * total);
+            k_pib_walk<<<dim3(sgrid), dim3(256), 0, st>>>(psi, d_off, d_org, d_sb, cnt, S, nsplit, nxt, acc, nullptr, nullptr, nullptr);
+        }
+        const int steps = static_cast<int>(ceil_log2_u64(max_split)) + 1;
+        for (int it = 0; it < steps; ++it) {
+            {
+                LaunchScope ls(ctx, K_IBWT_JUMP, 24.0 * nsplit);
+                k_ibwt_jump<<<dim3(sgrid), dim3(256), 0, st>>>(nxt, acc, nxt_alt, acc_alt, nsplit, &ctx->d_mail->packed.ibwt_pending);
+            }
+            std::swap(nxt, nxt_alt);
+            std::swap(acc, acc_alt);
+        }
+        rc = ctx->mail_fill(d_bad, 0xFF);
+    }
+    if (rc == DK_OK) {
+        LaunchScope ls(ctx, K_IBWT_JUMP, 12.0 * nsplit);
+        k_pib_check<<<dim3(sgrid), dim3(256), 0, st>>>(d_off, d_org, d_sb, cnt, S, nsplit, nxt, acc, nullptr, d_bad);
+    }
+    if (rc == DK_OK) rc = ctx->hip_ok(hipGetLastError(), "fm locate build");
+    const hipError_t e = hipStreamSynchronize(st);  // (also on failure: the copies above read `aux` and `header`)
+    DK_TRY(rc);
+    DK_HIP(ctx, e);
+    DK_TRY(ctx->mail_read(&ctx->h_mail->packed.ibwt_bad));
+    const uint32_t bad = ctx->h_mail->packed.ibwt_bad;
+    if (bad != IB_END) {
+        ctx->ws_release(mark);
+        if (packed) return ctx->fail(DK_E_STREAM, "fm_locate_build_packed: block %u of the pack: BWT/origin do not describe a single text cycle", bad);
+        return ctx->fail(DK_E_STREAM, "fm_locate_build: BWT/origin do not describe a single text cycle");
+    }
+    const uint32_t shift = static_cast<uint32_t>(ceil_log2_u64(step)), R = static_cast<uint32_t>(lc.rows), NS = static_cast<uint32_t>(lc.nsamp);
+    {
+        // both walks: a successor entry per position (a random 64-byte line each); the marks' words, the samples
+        LaunchScope ls(ctx, K_IBWT_EMIT, 2.0 * 64.0 * total + total / 4.0 + 8.0 * (total >> shift));
+        k_pib_locate<false><<<dim3(sgrid), dim3(256), 0, st>>>(psi, d_off, d_org, d_sb, cnt, S, nsplit, acc, shift, lc.bits, lc.marks, lc.samples, NS);
+        k_loc_rows<<<dim3(static_cast<unsigned>(div_up(lc.rows, 256))), dim3(256), 0, st>>>(lc.bits, R, lc.marks);
+        k_loc_scan<<<dim3(1), dim3(1024), 0, st>>>(lc.marks, R);
+        k_pib_locate<true><<<dim3(sgrid), dim3(256), 0, st>>>(psi, d_off, d_org, d_sb, cnt, S, nsplit, acc, shift, lc.bits, lc.marks, lc.samples, NS);
+    }
+    DK_HIP(ctx, hipGetLastError());
+    DK_HIP(ctx, hipStreamSynchronize(st));
+    ctx->ws_release(mark);
+    return DK_OK;
+}
+
 // ---- what the two inverses above take from the workspace (a decoder context is sized by these: abi.cpp decoder_workspace_bytes) ----------
 namespace {
 size_t ws_round(size_t bytes) { return (bytes + 255) & ~static_cast<size_t>(255); }
@@ -849,6 +1010,12 @@ size_t packed_ibwt_workspace(size_t max_total, size_t max_blocks) {
     const size_t nrec = std::min(nsplit, max_total / 32);
     return ws_round((3 * count + 2) * 4) /* aux */ + ibwt_tables(max_total) + ws_round(count * 256 * 4) /* base */ + ws_round(count * 4) /* cls0 */ +
            4 * ws_round(nsplit * 4) + ibwt_records(nrec);
+}
+
+size_t fm_locate_build_workspace(size_t total, size_t count) {
+    // fm_locate_build_device: the packed inverse's buffers without its records, for this very pack
+    const size_t nsplit = std::min(total, total / 64 + 2 * count);
+    return ws_round((3 * count + 2) * 4) + ibwt_tables(total) + ws_round(count * 256 * 4) + ws_round(count * 4) + 4 * ws_round(nsplit * 4);
 }
 
 }  // namespace dk

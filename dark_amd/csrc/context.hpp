@@ -36,7 +36,7 @@ enum KernelSlot : int {
     K_IBWT_LF,
     K_IBWT_WALK,
     K_IBWT_JUMP,
-    K_IBWT_EMIT,
+    K_IBWT_EMIT,       // k_ibwt_emit / _copy, k_pib_emit / _copy; the locate structure: k_pib_locate x 2 + k_loc_rows + k_loc_scan
     K_LF_FINISH,           // k_lf_finish (slot 18: k_bucket_store's until round 5)
     K_BIG_CLASSIFY,    // k_big_reduce + k_big_spine + k_big_apply
     K_BIG_BACK,
@@ -49,7 +49,7 @@ enum KernelSlot : int {
     K_RADIX_SCATTER_TEXT,  // k_radix_scatter<false, true>: first pass, keys built from the text (13 B per pair)
     K_ISA_PARTITION,       // k_isa_init + k_isa_split<true> + k_isa_split<false> (inverse permutation through LDS windows)
     K_ISA_ASSEMBLE,        // k_isa_assemble
-    K_CHAIN,               // k_chain_extract + _ends + _tiles + _spine + _verdicts + _apply (pair chains; their sort is in the radix slots); k_sa_search*, k_fm_count
+    K_CHAIN,               // k_chain_extract + _ends + _tiles + _spine + _verdicts + _apply (pair chains; their sort is in the radix slots); k_sa_search*, k_fm_count, k_fm_locate
     K_PERIOD,              // k_period_first + _spine + _fill (next break of the block's dominant period, for the period round)
     K_SLOT_COUNT
 };
@@ -268,6 +268,28 @@ int fm_count_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, si
 // d_out[q] = occurrences of d_sym[q] in d_bwt[0, min(d_pos[q], total)), by the count kernel's rank.  Enqueues only.
 int fm_rank_device(dk_ctx *ctx, const uint8_t *d_bwt, size_t total, const void *d_index, const uint32_t *d_pos, const uint8_t *d_sym, size_t nq,
                    uint32_t *d_out);
+// The locate structure of a packed L (bwt.hip builds it, fm_index.hip reads it): 32-bit words, over the whole pack.
+//   [0, 64) header | rows + 1 marks before each 1024-slot row | 32 rows mark bits | total / step + count samples, in slot order
+// step: a power of two in [1, 4096] (the caller's check).  Host arithmetic, and the one place that knows the layout.
+constexpr uint32_t FM_LOC_MAGIC = 0x314C4D46u;  // "FML1"
+constexpr uint32_t FM_LOC_HEADER = 64;
+struct FmLocate { uint32_t *marks, *bits, *samples; size_t rows, nsamp; };
+inline size_t fm_locate_words(size_t total, size_t count, size_t step) { return FM_LOC_HEADER + 33 * div_up(total, 1024) + 1 + total / step + count; }
+inline FmLocate fm_locate_carve(void *d_loc, size_t total, size_t count, size_t step) {
+    uint32_t *w = static_cast<uint32_t *>(d_loc);
+    const size_t rows = div_up(total, 1024);
+    return FmLocate{w + FM_LOC_HEADER, w + FM_LOC_HEADER + rows + 1, w + FM_LOC_HEADER + rows + 1 + 32 * rows, rows, total / step + count};
+}
+// bwt.hip: the structure from (L, origin) alone, by the packed inverse's table, walk and jumps and two more walks (a single block is a pack of
+// one).  off / origin as for fm_build_device.  DK_E_STREAM, naming the lowest such block when `packed`, for a block that is no BWT; d_loc is
+// then unspecified.  Synchronises; takes at most fm_locate_build_workspace(total, count) <= packed_ibwt_workspace(total, count), releases it.
+int fm_locate_build_device(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector<uint32_t> &off, const uint32_t *origin, uint32_t step, void *d_loc,
+                           bool packed);
+size_t fm_locate_build_workspace(size_t total, size_t count);  // an upper bound of what it takes, every ws_alloc rounded up; host arithmetic
+// fm_index.hip: item (q, j), j < max_hits, of pattern q with the range [d_lo[q], d_hi[q]) in block d_pat_blk[q] (null: block 0):
+// d_pos[q * max_hits + j] = SA_b[lo + j], DK_FM_NO_HIT behind the range.  Enqueues only; takes no workspace.
+int fm_locate_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, const void *d_index, const void *d_loc,
+                     uint32_t step, const uint32_t *d_lo, const uint32_t *d_hi, const uint32_t *d_pat_blk, size_t npat, size_t max_hits, uint32_t *d_pos);
 // packed_dc_device: the DC arrays of every block of a packed L.  compact: block i's entries at [rb_i, rb_i + m_i) (global run order, rb on the
 // device in d_rb[0 .. count], d_rb[count] = all runs); otherwise at [off_i, off_i + m_i).  d_m / d_flags: count words, d_init: count x 256.
 int packed_dc_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, bool compact, uint32_t *d_dist,

@@ -28,6 +28,8 @@
 //                          row's bytes each, their difference scanned over the symbols = C_b; writes base_b and the block's four words
 // COUNT    k_fm_count      a wave per pattern, FM_WAVES per workgroup, grid stride; m dependent steps of one or two ranks
 //          k_fm_rank       the same rank for given (position, symbol) pairs -- the tests' view of it
+// LOCATE   k_fm_locate     a wave per (pattern, hit); at most min(step, n_b) dependent LF steps down to a sampled slot (section 4.14; the sampled
+//                          suffix array it reads is built in bwt.hip by the inverse's kernels: fm_locate_build_device)
 // Containment: the geometry (off, n, total) comes from the caller, never from the index; every position is clamped to [0, n_b] before it is used
 // and a rank reads L only below the position it counts to.  With an index or an L that is not what the build made the results are unspecified
 // but <= n_b, and nothing outside L, the index, the patterns and the two results is touched.
@@ -254,6 +256,59 @@ __global__ __launch_bounds__(64 * FM_WAVES) void k_fm_rank(const uint8_t *__rest
     }
 }
 
+// ---- locate ----------------------------------------------------------------------------------------------------------
+
+struct FmLocArgs {
+    const uint8_t *L; const uint32_t *off, *blocks, *base, *cp, *marks, *bits, *samples, *lo, *hi, *pat_blk;
+    uint32_t npat, max_hits, total, step_shift, nsamp; uint32_t *pos;
+};
+// A wave per item (q, j): the text position of slot lo[q] + j of the pattern's block.  From the slot, LF steps (the count's step applied to the
+// slot's own symbol) until a marked slot is met after k of them: its sample * step + k.  Every load of a step but the checkpoint word and base_b[c]
+// depends on the slot alone -- the row's 16 bytes per lane, which hold c = L[slot] in one lane, and the row's 32 mark words in the lower lanes
+// -- so they are issued together and c is taken from its lane; the checkpoint word, which needs c, is the second and last round trip of a step.
+// Containment: lo, hi are clamped to [0, n_b], every slot to [0, n_b), the sample's index to the samples; at most min(step, n_b) steps.
+__global__ __launch_bounds__(64 * FM_WAVES) void k_fm_locate(FmLocArgs a) {
+    const uint8_t *__restrict__ L = a.L;
+    const uint32_t *__restrict__ off = a.off, *__restrict__ cp = a.cp, *__restrict__ bits = a.bits, *__restrict__ pat_blk = a.pat_blk;
+    const uint32_t lane = threadIdx.x & 63u, total = a.total, step = 1u << a.step_shift;
+    const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * FM_WAVES, nitems = static_cast<uint64_t>(a.npat) * a.max_hits;
+    for (uint64_t item = static_cast<uint64_t>(blockIdx.x) * FM_WAVES + (threadIdx.x >> 6); item < nitems; item += nwaves) {
+        const uint32_t q = static_cast<uint32_t>(item / a.max_hits), j = static_cast<uint32_t>(item - static_cast<uint64_t>(q) * a.max_hits);
+        const uint32_t b = pat_blk ? pat_blk[q] : 0u, s = off[b], nb = off[b + 1] - s;  // (b < count: the caller's check)
+        const uint32_t lo = a.lo[q] < nb ? a.lo[q] : nb, hi = a.hi[q] < nb ? a.hi[q] : nb;
+        uint32_t out = 0xFFFFFFFFu;
+        if (lo < hi && j < hi - lo) {
+            const uint32_t origin = a.blocks[4 * static_cast<size_t>(b) + 2], last = a.blocks[4 * static_cast<size_t>(b) + 3];
+            const uint32_t *__restrict__ base = a.base + static_cast<size_t>(b) * 256;
+            const uint32_t bound = step < nb ? step : nb;
+            uint32_t x = lo + j;
+            for (uint32_t k = 0; k < bound; ++k) {
+                const uint32_t g = s + x, row = g >> FM_SHIFT, sl = (row << FM_SHIFT) + 16u * lane;
+                const uint32_t mine = lane < 32u ? bits[static_cast<size_t>(row) * 32 + lane] : 0u;
+                uint64_t v0, v1;
+                fm_load16(L, total, sl, fm_lane_bytes(g + 1u, sl), v0, v1);  // (the bytes below g and the one at g, which is below total)
+                const uint32_t word = (g & (FM_BLOCK - 1u)) >> 5, bit = g & 31u;
+                if ((static_cast<uint32_t>(__shfl(mine, word, 64)) >> bit) & 1u) {
+                    const uint32_t below = lane < word ? __popc(mine) : (lane == word ? __popc(mine & ((1u << bit) - 1u)) : 0u);
+                    uint32_t r = a.marks[row] + wave_sum(below);
+                    r = r < a.nsamp ? r : a.nsamp - 1u;
+                    const uint64_t p = (static_cast<uint64_t>(a.samples[r]) << a.step_shift) + k;
+                    if (p < nb) out = static_cast<uint32_t>(p);
+                    break;
+                }
+                const uint32_t at = g & 15u;
+                const uint32_t c = static_cast<uint32_t>(__shfl(static_cast<uint32_t>((at < 8u ? v0 >> (8u * at) : v1 >> (8u * (at - 8u))) & 0xFFu),
+                                                                (g & (FM_BLOCK - 1u)) >> 4, 64));
+                const uint32_t is_last = c == last ? 1u : 0u;
+                const uint32_t occ = cp[static_cast<size_t>(row) * 256 + c] + wave_sum(fm_count16(v0, v1, 0x0101010101010101ull * c, fm_lane_bytes(g, sl)));
+                x = base[c] + is_last - (is_last & (origin < x ? 1u : 0u)) + occ;
+                x = x < nb ? x : nb - 1u;
+            }
+        }
+        if (lane == 0) a.pos[item] = out;
+    }
+}
+
 }  // namespace
 
 size_t fm_build_workspace(size_t total, size_t count) {
@@ -319,6 +374,24 @@ int fm_rank_device(dk_ctx *ctx, const uint8_t *d_bwt, size_t total, const void *
     {
         LaunchScope ls(ctx, K_CHAIN, nq * (9.0 + FM_BLOCK + 64));
         k_fm_rank<<<dim3(grid), dim3(64 * FM_WAVES), 0, ctx->stream>>>(d_bwt, static_cast<uint32_t>(total), ix.cp, d_pos, d_sym, static_cast<uint32_t>(nq), d_out);
+    }
+    DK_HIP(ctx, hipGetLastError());
+    return DK_OK;
+}
+
+int fm_locate_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, const void *d_index, const void *d_loc,
+                     uint32_t step, const uint32_t *d_lo, const uint32_t *d_hi, const uint32_t *d_pat_blk, size_t npat, size_t max_hits, uint32_t *d_pos) {
+    const FmIndex ix = fm_carve(const_cast<void *>(d_index), total, count);
+    const FmLocate lc = fm_locate_carve(const_cast<void *>(d_loc), total, count, step);
+    const size_t nitems = npat * max_hits;
+    const unsigned grid = static_cast<unsigned>(std::min<size_t>(div_up(nitems, FM_WAVES), 1u << 20));
+    const FmLocArgs a{d_bwt, d_off, ix.blocks, ix.base, ix.cp, lc.marks, lc.bits, lc.samples, d_lo, d_hi, d_pat_blk, static_cast<uint32_t>(npat),
+                      static_cast<uint32_t>(max_hits), static_cast<uint32_t>(total), static_cast<uint32_t>(ceil_log2_u64(step)),
+                      static_cast<uint32_t>(lc.nsamp), d_pos};
+    {
+        // per item about step / 2 steps of a row of L, a row of mark words and a checkpoint word; the range, the sample and the result
+        LaunchScope ls(ctx, K_CHAIN, nitems * (20.0 + 0.5 * step * (FM_BLOCK + 128 + 64)));
+        k_fm_locate<<<dim3(grid), dim3(64 * FM_WAVES), 0, ctx->stream>>>(a);
     }
     DK_HIP(ctx, hipGetLastError());
     return DK_OK;

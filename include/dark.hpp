@@ -264,20 +264,24 @@ namespace fm {
 // bwt::transform or a stream decoder leaves them.  It lives on a DECODER context: nothing here needs the suffix sort's workspace.  Nothing in the
 // reference corresponds.  (This host-memory form builds the device index anew in every count; a caller that keeps L on the GPU uses
 // dk_dev_fm_build once and dk_dev_fm_count after it.)
+// locate_step (0: none, count only; else a power of two in [1, 4096]): the distance of the sampled text positions of `locate` (dk_fm_locate,
+// section 4.14), which says WHERE the patterns occur -- still without the text and without a full suffix array.
 class Index {
 public:
-    Index(std::vector<uint8_t> bwt, size_t origin, int device = 0) : ctx_(bwt.size(), device, DK_CTX_DECODER), bwt_(std::move(bwt)), origin_(origin) {
+    Index(std::vector<uint8_t> bwt, size_t origin, int device = 0, uint32_t locate_step = 0)
+        : ctx_(bwt.size(), device, DK_CTX_DECODER), bwt_(std::move(bwt)), origin_(origin), step_(locate_step) {
         if (origin_ >= bwt_.size()) throw Error(DK_E_ARG, "assertion failed: origin < bwt.len()");
+        if (step_ && dk_fm_locate_bytes(bwt_.size(), 1, step_) == 0) throw Error(DK_E_ARG, "locate_step is no power of two in [1, 4096]");
     }
     // the index of a text: forward BWT on a full context that is released again, then as above
-    static Index from_text(const std::vector<uint8_t> &text, int device = 0) {
+    static Index from_text(const std::vector<uint8_t> &text, int device = 0, uint32_t locate_step = 0) {
         detail::Ctx full(text.size(), device);
         auto lo = bwt::transform(full, text);
-        return Index(std::move(lo.first), lo.second, device);
+        return Index(std::move(lo.first), lo.second, device, locate_step);
     }
     size_t len() const { return bwt_.size(); }
-    // device bytes that answer a query: L and the index
-    size_t resident_bytes() const { return bwt_.size() + dk_fm_index_bytes(bwt_.size(), 1); }
+    // device bytes that answer a query: L and the index, and the locate structure where one was asked for
+    size_t resident_bytes() const { return bwt_.size() + dk_fm_index_bytes(bwt_.size(), 1) + (step_ ? dk_fm_locate_bytes(bwt_.size(), 1, step_) : 0); }
     // result[q] = (lo, hi) as from saca::Constructor::search on the text; hi - lo = the number of places patterns[q] occurs
     std::vector<std::pair<uint32_t, uint32_t>> count(const std::vector<std::vector<uint8_t>> &patterns) {
         std::vector<size_t> lens;
@@ -298,11 +302,30 @@ public:
         for (const auto &r : count(patterns)) out.push_back(r.second - r.first);
         return out;
     }
+    // result[q] = the first min(occurrences, max_hits) text positions of patterns[q], in suffix-array order
+    std::vector<std::vector<uint32_t>> locate(const std::vector<std::vector<uint8_t>> &patterns, size_t max_hits = 16) {
+        if (!step_) throw Error(DK_E_ARG, "the index was made without a locate structure (locate_step = 0)");
+        std::vector<size_t> lens;
+        std::vector<uint8_t> bytes(1);
+        for (const auto &p : patterns) {
+            lens.push_back(p.size());
+            bytes.insert(bytes.end(), p.begin(), p.end());
+        }
+        std::vector<uint32_t> lo(patterns.size() + 1), hi(patterns.size() + 1), pos(patterns.size() * max_hits + 1);
+        int rc = dk_fm_locate(ctx_.get(), bwt_.data(), bwt_.size(), static_cast<uint32_t>(origin_), step_, bytes.data() + 1, patterns.size(), lens.data(),
+                              max_hits, lo.data(), hi.data(), pos.data());
+        if (rc != DK_OK) throw Error(rc, ctx_.error());
+        std::vector<std::vector<uint32_t>> out(patterns.size());
+        for (size_t q = 0; q < patterns.size(); ++q)
+            for (size_t j = 0; j < max_hits && pos[q * max_hits + j] != DK_FM_NO_HIT; ++j) out[q].push_back(pos[q * max_hits + j]);
+        return out;
+    }
     detail::Ctx &context() { return ctx_; }  // context().purpose() == DK_CTX_DECODER
 private:
     detail::Ctx ctx_;
     std::vector<uint8_t> bwt_;
     size_t origin_;
+    uint32_t step_;
 };
 }  // namespace fm
 

@@ -276,6 +276,37 @@ int dk_dev_fm_count_packed(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t count, 
  * their offsets and the results (about 2 n + the patterns + 12 bytes per pattern) do not fit the workspace. */
 int dk_fm_count(dk_ctx *any_ctx, const uint8_t *bwt, size_t n, uint32_t origin,
                 const uint8_t *pat, size_t npat, const size_t *pat_len, uint32_t *lo, uint32_t *hi);
+/* ---- FM-index: locate.  Where the occurrences are, from a sampled suffix array (csrc/bwt.hip, csrc/fm_index.hip) ----
+ * A second opaque DEVICE buffer of the caller's beside the index: dk_fm_locate_bytes(total, count, step) bytes, 4-byte aligned.  It marks the
+ * slots whose suffix starts at a multiple of `step` (positions local to the block; position 0 always) and keeps position / step of each: about
+ * total / 8 + 4 total / step bytes, 0.26 n at step 32.  dk_fm_locate_bytes needs no GPU; 0 for what dk_fm_index_bytes refuses and for a step
+ * that is no power of two in [1, 4096].
+ * dk_dev_fm_locate_build* need (L, origin) only -- neither the index nor a suffix array: they run the inverse BWT's successor table, splitter
+ * walk and jumps, and two more walks in place of the one that writes the text.  DK_E_STREAM, exactly where dk_dev_bwt_inverse* gives it, when
+ * (L, origin) describe no text (in a pack the message names the lowest such block); d_loc is then unspecified.  DK_E_ARG as for
+ * dk_dev_fm_build*, for a bad step and a d_loc that is not 4-byte aligned; a pack obeys DK_PACKED_MAX_BLOCK_BYTES and the context's max_blocks.
+ * Workspace: the packed inverse's without its walk records, which every context that can invert the block or pack holds.
+ * dk_dev_fm_locate*: d_lo / d_hi (device, npat words each) as dk_dev_fm_count* wrote them, `step` the one of the build.  Row q of d_pos
+ * (device, npat x max_hits words): d_pos[q max_hits + j] = SA_b[lo[q] + j] for j < min(hi[q] - lo[q], max_hits), in suffix-array order,
+ * DK_FM_NO_HIT behind them: no scan, no readback.  The empty pattern's range [0, n) with max_hits = n gives the whole suffix array.
+ * DK_E_ARG for max_hits == 0, npat x max_hits > 2^31, pat_block[q] >= count (pat_block in HOST memory), null or misaligned pointers.
+ * Both structures are TRUSTED, and contained as the count is: lo and hi are clamped to [0, n_b] (hi < lo: no hits), every slot to [0, n_b),
+ * the sample's index to the samples, and at most min(step, n_b) steps are taken; for any bytes in L, the index, d_loc, d_lo and d_hi every
+ * value written is < n_b or DK_FM_NO_HIT, and nothing outside those buffers and d_pos is touched. */
+#define DK_FM_NO_HIT 0xFFFFFFFFu
+size_t dk_fm_locate_bytes(size_t total, size_t count, uint32_t step);
+int dk_dev_fm_locate_build(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t n, uint32_t origin, uint32_t step, void *d_loc);
+int dk_dev_fm_locate_build_packed(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const uint32_t *origin /* host */,
+                                  uint32_t step, void *d_loc);
+int dk_dev_fm_locate(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t n, const void *d_index, const void *d_loc, uint32_t step,
+                     const uint32_t *d_lo, const uint32_t *d_hi, size_t npat, size_t max_hits, uint32_t *d_pos);
+int dk_dev_fm_locate_packed(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const void *d_index, const void *d_loc,
+                            uint32_t step, const uint32_t *d_lo, const uint32_t *d_hi, size_t npat, const uint32_t *pat_block /* host */,
+                            size_t max_hits, uint32_t *d_pos);
+/* from and to host memory: upload, both builds, count, locate, download of lo, hi (npat words each) and pos (npat x max_hits).  DK_E_ARG
+ * when L, the two structures, the batch, its results and the locate build's workspace do not fit the context's workspace. */
+int dk_fm_locate(dk_ctx *any_ctx, const uint8_t *bwt, size_t n, uint32_t origin, uint32_t step, const uint8_t *pat, size_t npat,
+                 const size_t *pat_len, size_t max_hits, uint32_t *lo, uint32_t *hi, uint32_t *pos);
 /* for the tests: d_out[q] = occurrences of d_sym[q] in d_bwt[0, min(d_pos[q], total)), computed by the count kernel's rank (all device memory) */
 int dk_dbg_dev_fm_rank(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t total, const void *d_index,
                        const uint32_t *d_pos, const uint8_t *d_sym, size_t nq, uint32_t *d_out);

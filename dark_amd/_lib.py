@@ -95,6 +95,12 @@ SIGNATURES = {
     "dk_dev_fm_locate": (_i, [_vp, _vp, _sz, _vp, _vp, C.c_uint32, _vp, _vp, _sz, _sz, _vp]),
     "dk_dev_fm_locate_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _sz, _vp, _sz, _vp]),
     "dk_fm_locate": (_i, [_vp, _vp, _sz, C.c_uint32, C.c_uint32, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "dk_fm_extract_bytes": (_sz, [_sz, _sz, C.c_uint32]),
+    "dk_dev_fm_extract_build": (_i, [_vp, _vp, _sz, C.c_uint32, C.c_uint32, _vp]),
+    "dk_dev_fm_extract_build_packed": (_i, [_vp, _vp, _sz, _vp, _vp, C.c_uint32, _vp]),
+    "dk_dev_fm_extract": (_i, [_vp, _vp, _sz, _vp, _vp, C.c_uint32, _vp, _vp, _sz, _sz, _vp]),
+    "dk_dev_fm_extract_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "dk_fm_extract": (_i, [_vp, _vp, _sz, C.c_uint32, C.c_uint32, _vp, _vp, _sz, _sz, _vp]),
     "dk_dbg_dev_fm_rank": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
     "dk_dev_dc_encode_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _szp]),
     "dk_batch_push_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),

@@ -90,6 +90,14 @@ def fm_locate_bytes(total, count=1, step=32):
     return int(_lib.load().dk_fm_locate_bytes(int(total), int(count), int(step)))
 
 
+def fm_extract_bytes(total, count=1, step=32):
+    """dk_fm_extract_bytes: bytes of the extract structure beside that index at anchor distance `step`; needs no GPU.  0 for what fm_index_bytes
+    refuses and for a step that is no power of two in [1, 4096]."""
+    if total < 0 or count < 0 or not 0 <= step < 2 ** 32:
+        return 0
+    return int(_lib.load().dk_fm_extract_bytes(int(total), int(count), int(step)))
+
+
 class Context:
     def __init__(self, max_n, device=0, purpose="full", max_blocks=1):
         """purpose="decoder": a context for the inverse path only (dk_ctx_create_decoder), about a fifth of the workspace; max_blocks = most
@@ -485,6 +493,50 @@ class Context:
         self._ck(self._lib.dk_fm_locate(self._h, _ptr(b), len(b), int(origin), int(step), _ptr(pat), npat, lens, int(max_hits), _ptr(lo), _ptr(hi),
                                         _ptr(pos)))
         return lo, hi, pos
+
+    # ---- FM-index extract: text ranges from L, the index and the anchors; decoder contexts too ----
+    def dev_fm_extract_build(self, d_bwt, n, origin, step, d_ext):
+        """the extract structure of d_bwt[0, n) with its origin into d_ext, a device tensor of fm_extract_bytes(n, 1, step) bytes; needs no index"""
+        _inputs_ready(d_bwt)
+        self._ck(self._lib.dk_dev_fm_extract_build(self._h, _ptr(d_bwt), n, int(origin), int(step), _ptr(d_ext)))
+
+    def dev_fm_extract_build_packed(self, d_bwt, sizes, origins, step, d_ext):
+        """one structure for every block of a packed L; d_ext: fm_extract_bytes(sum(sizes), len(sizes), step) bytes"""
+        _inputs_ready(d_bwt)
+        count = len(sizes)
+        if len(origins) != count:
+            raise DarkError(_lib.DK_E_ARG, "%d origins for %d blocks" % (len(origins), count))
+        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
+        org = np.array(origins, dtype=np.int64).astype(np.uint32) if count else np.zeros(1, np.uint32)
+        self._ck(self._lib.dk_dev_fm_extract_build_packed(self._h, _ptr(d_bwt), count, ns, _ptr(org), int(step), _ptr(d_ext)))
+
+    def dev_fm_extract(self, d_bwt, n, d_index, d_ext, step, d_pos, d_len, nrange, max_len, d_out):
+        """row q of d_out (a uint8 device tensor of nrange * max_len bytes, any alignment) = the text at [d_pos[q], d_pos[q] + d_len[q]), cut to
+        max_len and to the block's end, zeros behind; d_pos / d_len uint32 device tensors (d_len None: every range max_len long)"""
+        _inputs_ready(d_bwt, d_index, d_ext, d_pos, *([] if d_len is None else [d_len]))
+        self._ck(self._lib.dk_dev_fm_extract(self._h, _ptr(d_bwt), n, _ptr(d_index), _ptr(d_ext), int(step), _ptr(d_pos),
+                                             None if d_len is None else _ptr(d_len), int(nrange), int(max_len), _ptr(d_out)))
+
+    def dev_fm_extract_packed(self, d_bwt, sizes, d_index, d_ext, step, d_pos, d_len, range_blocks, max_len, d_out):
+        """dev_fm_extract in a pack: range q lies in block range_blocks[q], its start is local to that block"""
+        _inputs_ready(d_bwt, d_index, d_ext, d_pos, *([] if d_len is None else [d_len]))
+        count, nrange = len(sizes), len(range_blocks)
+        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
+        blocks = np.array(range_blocks, dtype=np.int64).astype(np.uint32) if nrange else np.zeros(1, np.uint32)
+        self._ck(self._lib.dk_dev_fm_extract_packed(self._h, _ptr(d_bwt), count, ns, _ptr(d_index), _ptr(d_ext), int(step), _ptr(d_pos),
+                                                    None if d_len is None else _ptr(d_len), nrange, _ptr(blocks), int(max_len), _ptr(d_out)))
+
+    def fm_extract(self, bwt, origin, positions, lengths, max_len, step=32):
+        """a uint8 array of len(positions) x max_len from (L, origin) in host memory: row q = the text at [positions[q], positions[q] +
+        lengths[q]), cut to max_len and the text's end, zeros behind; lengths None: every range max_len long (dk_fm_extract)"""
+        b = as_u8(bwt)
+        pos = np.array(positions, dtype=np.int64).astype(np.uint32) if len(positions) else np.zeros(1, np.uint32)
+        nrange = len(positions)
+        lens = None if lengths is None else (np.array(lengths, dtype=np.int64).astype(np.uint32) if nrange else np.zeros(1, np.uint32))
+        out = np.zeros((nrange, max(int(max_len), 1)), dtype=np.uint8)
+        self._ck(self._lib.dk_fm_extract(self._h, _ptr(b), len(b), int(origin), int(step), _ptr(pos), None if lens is None else _ptr(lens), nrange,
+                                         int(max_len), _ptr(out)))
+        return out
 
     def dbg_dev_fm_rank(self, d_bwt, total, d_index, d_pos, d_sym, d_out):
         """d_out[q] = occurrences of d_sym[q] in d_bwt[0, d_pos[q]) by the count kernel's rank (uint32 / uint8 / uint32 device tensors)"""

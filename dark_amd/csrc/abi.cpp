@@ -113,6 +113,7 @@ size_t decoder_workspace_bytes(size_t max_n, size_t max_blocks) {
     // and 8 bytes per block, the host-pointer form 2 n + 3 KiB beside them (tests/test_gpu_fm.py checks peak <= size on both purposes).
     // The locate structure's build (bwt.hip: fm_locate_build_device) is the packed inverse above without its records, for one block too, so it
     // fits whatever fits `packed`; dk_fm_locate refuses what does not fit (tests/test_gpu_fm_locate.py checks peak <= size on both purposes).
+    // The extract structure's build (fm_extract_build_device) is that front part and 4 bytes per block more, far below the records left out.
     // tests/test_gpu_decoder_ctx.py checks peak <= size on contexts sized exactly to their block or pack, through every entry above.
     const size_t single = 2 * ((max_n + 255) & ~size_t(255)) + bwt_inverse_workspace(max_n);
     const size_t packed = ((max_n + 255) & ~size_t(255)) + packed_ibwt_workspace(max_n, max_blocks);
@@ -1644,6 +1645,152 @@ int dk_fm_locate(dk_ctx *ctx, const uint8_t *bwt, size_t n, uint32_t origin, uin
     DK_HIP(ctx, hipMemcpyAsync(lo, d_lo, npat * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     DK_HIP(ctx, hipMemcpyAsync(hi, d_hi, npat * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     DK_HIP(ctx, hipMemcpyAsync(pos, d_pos, nitems * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    DK_HIP(ctx, hipStreamSynchronize(st));
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+// ---- extract: text ranges from L, the index and the anchors, built from (L, origin) alone ----------------------------
+}  // extern "C"
+
+namespace {
+int fm_extract_args(dk_ctx *ctx, uint32_t step, const void *d_ext) {
+    if (!fm_good_step(step)) return ctx->fail(DK_E_ARG, "the sampling step %u is no power of two in [1, 4096]", step);
+    if (!fm_good_index(d_ext)) return ctx->fail(DK_E_ARG, "the extract structure is not 4-byte aligned");
+    return DK_OK;
+}
+int fm_extract_rows(dk_ctx *ctx, size_t nrange, size_t max_len) {
+    if (max_len == 0 || nrange > 0xFFFFFFFEull || max_len > (size_t(1) << 31) || nrange * max_len > (size_t(1) << 31))
+        return ctx->fail(DK_E_ARG, "%zu ranges of at most %zu bytes: 1 .. 2^31 bytes in all", nrange, max_len);
+    return DK_OK;
+}
+}  // namespace
+
+extern "C" {
+
+size_t dk_fm_extract_bytes(size_t total, size_t count, uint32_t step) {
+    if (dk_fm_index_bytes(total, count) == 0 || !fm_good_step(step)) return 0;
+    return fm_extract_words(total, count, step) * sizeof(uint32_t);
+}
+
+int dk_dev_fm_extract_build(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t origin, uint32_t step, void *d_ext) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!d_bwt || !d_ext) return ctx->fail(DK_E_ARG, "null pointer");
+    DK_TRY(fm_extract_args(ctx, step, d_ext));
+    DK_TRY(check_n(ctx, n));
+    if (origin >= n) return ctx->fail(DK_E_ARG, "origin %u is outside the block of %zu bytes", origin, n);
+    Timer t;
+    DK_TRY(fm_extract_build_device(ctx, d_bwt, {0u, static_cast<uint32_t>(n)}, &origin, step, d_ext, false));
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_dev_fm_extract_build_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const uint32_t *origin, uint32_t step, void *d_ext) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!d_bwt || !n || !origin || !d_ext) return ctx->fail(DK_E_ARG, "null pointer");
+    DK_TRY(fm_extract_args(ctx, step, d_ext));
+    std::vector<uint32_t> off;
+    DK_TRY(check_pack(ctx, count, n, off));
+    for (size_t i = 0; i < count; ++i)
+        if (origin[i] >= n[i]) return ctx->fail(DK_E_ARG, "origin %u of block %zu is outside its %zu bytes", origin[i], i, n[i]);
+    Timer t;
+    DK_TRY(fm_extract_build_device(ctx, d_bwt, off, origin, step, d_ext, true));
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_dev_fm_extract(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, const void *d_index, const void *d_ext, uint32_t step, const uint32_t *d_pos,
+                      const uint32_t *d_len, size_t nrange, size_t max_len, uint8_t *d_out) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!d_bwt || !d_index || !d_ext) return ctx->fail(DK_E_ARG, "null pointer");
+    if (!fm_good_index(d_index)) return ctx->fail(DK_E_ARG, "the index is not 4-byte aligned");
+    DK_TRY(fm_extract_args(ctx, step, d_ext));
+    DK_TRY(check_n(ctx, n));
+    if (nrange == 0) return DK_OK;
+    DK_TRY(fm_extract_rows(ctx, nrange, max_len));
+    if (!d_pos || !d_out) return ctx->fail(DK_E_ARG, "null pointer");  // (d_len may be null: every range max_len long)
+    if ((reinterpret_cast<uintptr_t>(d_pos) | reinterpret_cast<uintptr_t>(d_len)) & 3)
+        return ctx->fail(DK_E_ARG, "the positions or the lengths are not 4-byte aligned");
+    Timer t;
+    uint32_t *d_off = nullptr;
+    DK_TRY(single_offsets(ctx, n, &d_off));
+    DK_TRY(fm_extract_device(ctx, d_bwt, d_off, nullptr, 1, n, d_index, d_ext, step, d_pos, d_len, nullptr, nrange, max_len, d_out));
+    DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_dev_fm_extract_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const void *d_index, const void *d_ext, uint32_t step,
+                             const uint32_t *d_pos, const uint32_t *d_len, size_t nrange, const uint32_t *range_block, size_t max_len, uint8_t *d_out) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!d_bwt || !n || !d_index || !d_ext) return ctx->fail(DK_E_ARG, "null pointer");
+    if (!fm_good_index(d_index)) return ctx->fail(DK_E_ARG, "the index is not 4-byte aligned");
+    DK_TRY(fm_extract_args(ctx, step, d_ext));
+    std::vector<uint32_t> off;
+    DK_TRY(check_pack(ctx, count, n, off));
+    if (nrange == 0) return DK_OK;
+    DK_TRY(fm_extract_rows(ctx, nrange, max_len));
+    if (!range_block || !d_pos || !d_out) return ctx->fail(DK_E_ARG, "null pointer");
+    if ((reinterpret_cast<uintptr_t>(d_pos) | reinterpret_cast<uintptr_t>(d_len)) & 3)
+        return ctx->fail(DK_E_ARG, "the positions or the lengths are not 4-byte aligned");
+    for (size_t q = 0; q < nrange; ++q)
+        if (range_block[q] >= count) return ctx->fail(DK_E_ARG, "range %zu names block %u of a pack of %zu", q, range_block[q], count);
+    Timer t;
+    hipStream_t st = ctx->stream;
+    // the offsets and the anchor bases in one array of 2 count + 1 words: off[0 .. count] | the base of every block
+    std::vector<uint32_t> geo(off);
+    const std::vector<uint32_t> abase = fm_extract_bases(off, step);
+    geo.insert(geo.end(), abase.begin(), abase.end() - 1);
+    uint32_t *d_geo = ctx->ws_alloc<uint32_t>(geo.size()), *d_blk = ctx->ws_alloc<uint32_t>(nrange);
+    if (!d_geo || !d_blk) return DK_E_NOMEM;
+    DK_HIP(ctx, hipMemcpyAsync(d_geo, geo.data(), geo.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    int rc = ctx->hip_ok(hipMemcpyAsync(d_blk, range_block, nrange * sizeof(uint32_t), hipMemcpyHostToDevice, st), "range blocks");
+    if (rc == DK_OK)
+        rc = fm_extract_device(ctx, d_bwt, d_geo, d_geo + count + 1, count, off.back(), d_index, d_ext, step, d_pos, d_len, d_blk, nrange, max_len, d_out);
+    const hipError_t e = hipStreamSynchronize(st);  // (also on failure: the copies above read `geo` and `range_block`)
+    DK_TRY(rc);
+    DK_HIP(ctx, e);
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_fm_extract(dk_ctx *ctx, const uint8_t *bwt, size_t n, uint32_t origin, uint32_t step, const uint32_t *pos, const uint32_t *len, size_t nrange,
+                  size_t max_len, uint8_t *out) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!bwt) return ctx->fail(DK_E_ARG, "null pointer");
+    if (!fm_good_step(step)) return ctx->fail(DK_E_ARG, "the sampling step %u is no power of two in [1, 4096]", step);
+    DK_TRY(check_n(ctx, n));
+    if (origin >= n) return ctx->fail(DK_E_ARG, "origin %u is outside the block of %zu bytes", origin, n);
+    if (nrange == 0) return DK_OK;
+    DK_TRY(fm_extract_rows(ctx, nrange, max_len));
+    if (!pos || !out) return ctx->fail(DK_E_ARG, "null pointer");  // (len may be null)
+    Timer t;
+    // L, the index, the structure and the block's two offsets; the positions, the lengths and the rows; the larger of the two builds' workspaces
+    // while it runs
+    const size_t index_words = fm_index_words(n, 1), ext_words = fm_extract_words(n, 1, step), nbytes = nrange * max_len;
+    const size_t need = ws_round(n) + ws_round(4 * index_words) + ws_round(4 * ext_words) + 256 + 2 * ws_round(4 * nrange) + ws_round(nbytes) +
+                        std::max(fm_build_workspace(n, 1), fm_locate_build_workspace(n, 1) + ws_round(8));
+    if (need > ctx->ws_size)
+        return ctx->fail(DK_E_ARG, "%zu ranges of at most %zu bytes do not fit the workspace beside L, its index and the extract build", nrange, max_len);
+    hipStream_t st = ctx->stream;
+    uint8_t *d_bwt = ctx->ws_alloc<uint8_t>(n), *d_out = ctx->ws_alloc<uint8_t>(nbytes);
+    uint32_t *d_index = ctx->ws_alloc<uint32_t>(index_words), *d_ext = ctx->ws_alloc<uint32_t>(ext_words);
+    uint32_t *d_pos = ctx->ws_alloc<uint32_t>(nrange), *d_len = ctx->ws_alloc<uint32_t>(nrange);
+    uint32_t *d_off = nullptr;
+    if (!d_bwt || !d_out || !d_index || !d_ext || !d_pos || !d_len) return DK_E_NOMEM;
+    DK_TRY(single_offsets(ctx, n, &d_off));
+    DK_HIP(ctx, hipMemcpyAsync(d_bwt, bwt, n, hipMemcpyHostToDevice, st));
+    DK_HIP(ctx, hipMemcpyAsync(d_pos, pos, nrange * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    if (len) DK_HIP(ctx, hipMemcpyAsync(d_len, len, nrange * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    DK_TRY(fm_build_device(ctx, d_bwt, {0u, static_cast<uint32_t>(n)}, &origin, d_index));
+    DK_TRY(fm_extract_build_device(ctx, d_bwt, {0u, static_cast<uint32_t>(n)}, &origin, step, d_ext, false));
+    DK_TRY(fm_extract_device(ctx, d_bwt, d_off, nullptr, 1, n, d_index, d_ext, step, d_pos, len ? d_len : nullptr, nullptr, nrange, max_len, d_out));
+    DK_HIP(ctx, hipMemcpyAsync(out, d_out, nbytes, hipMemcpyDeviceToHost, st));
     DK_HIP(ctx, hipStreamSynchronize(st));
     ctx->stats.ms_total = t.ms();
     return DK_OK;

@@ -14,7 +14,8 @@
 //   k_ibwt_emit          one lane per splitter re-walks its sub-list and writes the text bytes
 // Packed inverse (k_pib_*): the same stages over many blocks laid back to back, segmented by the offsets table.
 // The FM-index's locate structure (fm_locate_build_device): the packed inverse's table, walk and jumps, then k_pib_locate
-// twice where the inverse writes the text -- the walk knows the text position of every slot it passes.
+// twice where the inverse writes the text -- the walk knows the text position of every slot it passes.  The extract structure
+// (fm_extract_build_device, section 4.15) is the same front part and one such walk, k_pib_anchors.
 #include <algorithm>
 
 #include "context.hpp"
@@ -641,6 +642,32 @@ __global__ __launch_bounds__(256) void k_pib_locate(const uint64_t *__restrict__
         cur = p;
     }
 }
+// The extract structure: the walk of k_pib_locate once more.  Where the text position is a multiple of the step, the
+// slot the walk stands on -- the slot of the suffix that starts there -- is that position's anchor.  Every position belongs to one walk, so every
+// anchor has one writer: plain stores, no atomics.  abase[b] = block b's first anchor (the host's prefix of ceil(n_i / step)).  Runs behind
+// k_pib_check like k_pib_locate, with its tests: a walk stays in its block, a store inside the nanch anchors, whatever the tables hold.
+__global__ __launch_bounds__(256) void k_pib_anchors(const uint64_t *__restrict__ psi, const uint32_t *__restrict__ off, const uint32_t *__restrict__ org,
+                                                      const uint32_t *__restrict__ sb, uint32_t count, uint32_t S, uint32_t nsplit,
+                                                      const uint32_t *__restrict__ dist_to_end, uint32_t step_shift, const uint32_t *__restrict__ abase,
+                                                      uint32_t *__restrict__ anchors, uint32_t nanch) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= nsplit) return;
+    const PibBlock b = pib_block(off, org, sb, count, S, s);
+    const uint32_t d = dist_to_end[s], mask = (1u << step_shift) - 1u;
+    if (d == 0 || d > b.n) return;
+    const uint32_t a0 = abase[b.blk];
+    uint32_t cur = pib_start(b, S, s), pos = b.n - d;
+    for (;;) {
+        if ((pos & mask) == 0) {
+            const uint32_t at = a0 + (pos >> step_shift);
+            if (at < nanch) anchors[at] = cur - b.s0;
+        }
+        const uint32_t p = static_cast<uint32_t>(psi[cur]);
+        if (p == IB_END || p - b.s0 >= b.n || pib_splitter_at(b, S, p) != IB_END || ++pos >= b.n) break;
+        cur = p;
+    }
+}
+
 // marks[r] = set bits of row r (32 words of 32 slots)
 __global__ __launch_bounds__(256) void k_loc_rows(const uint32_t *__restrict__ bits, uint32_t rows, uint32_t *__restrict__ marks) {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -878,17 +905,19 @@ int packed_ibwt_device(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector<uint
     return DK_OK;
 }
 
-// The locate structure: packed_ibwt_device's table, walk (no records), jumps and check, then k_pib_locate twice where the inverse writes the
-// text.  A single block is a pack of one here (S = 64 at every size): the workspace is the packed inverse's without its records, which every
-// context that can invert the block or pack holds.
-int fm_locate_build_device(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector<uint32_t> &off, const uint32_t *origin, uint32_t step, void *d_loc,
-                           bool packed) {
+// The front part of both FM-index structure builds: packed_ibwt_device's table, walk (no records), jumps and check.  A single block is a pack of
+// one here (S = 64 at every size): the workspace is the packed inverse's without its records, which every context that can invert the block or
+// pack holds.  Afterwards psi is the successor table, dist[s] the distance of splitter s from its block's end, and every walk from a splitter
+// stays in its block.  Synchronises; DK_E_STREAM in the words of `what` for a block that is no BWT (the workspace is then released to `mark`).
+namespace {
+constexpr uint32_t FMB_S = 64;
+struct FmWalks { const uint64_t *psi; const uint32_t *off, *org, *sb, *dist; uint32_t nsplit; unsigned sgrid; };
+int fm_walks_device(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector<uint32_t> &off, const uint32_t *origin, const char *what, bool packed,
+                    size_t mark, FmWalks &out) {
     hipStream_t st = ctx->stream;
     const size_t count = off.size() - 1, total = off.back();
     const uint32_t cnt = static_cast<uint32_t>(count), T = static_cast<uint32_t>(total);
-    const FmLocate lc = fm_locate_carve(d_loc, total, count, step);
-    const size_t mark = ctx->ws_mark();
-    constexpr uint32_t S = 64;
+    constexpr uint32_t S = FMB_S;
     std::vector<uint32_t> aux(3 * count + 2);  // off | origin | first splitter of every block, as in packed_ibwt_device
     std::copy(off.begin(), off.end(), aux.begin());
     uint32_t *h_org = aux.data() + count + 1, *h_sb = h_org + count;
@@ -913,10 +942,6 @@ int fm_locate_build_device(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector<
     uint32_t *acc = ctx->ws_alloc<uint32_t>(nsplit), *acc_alt = ctx->ws_alloc<uint32_t>(nsplit);
     if (!d_aux || !tile_hist || !chunk_sum || !class_start || !base || !cls0 || !psi || !nxt || !nxt_alt || !acc || !acc_alt) return DK_E_NOMEM;
     const uint32_t *d_off = d_aux, *d_org = d_aux + count + 1, *d_sb = d_org + count;
-    const uint32_t header[6] = {FM_LOC_MAGIC, T, cnt, step, static_cast<uint32_t>(lc.rows), static_cast<uint32_t>(lc.nsamp)};
-    // the header, the marks and the mark bits start as zeros (the samples are written one by one)
-    DK_HIP(ctx, hipMemsetAsync(d_loc, 0, (FM_LOC_HEADER + 33 * lc.rows + 1) * sizeof(uint32_t), st));
-    DK_HIP(ctx, hipMemcpyAsync(d_loc, header, sizeof(header), hipMemcpyHostToDevice, st));
     int rc = ctx->hip_ok(hipMemcpyAsync(d_aux, aux.data(), aux.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st), "pack geometry");
     const unsigned sgrid = static_cast<unsigned>(div_up(nsplit, 256));
     uint32_t *d_bad = &ctx->d_mail->packed.ibwt_bad;
@@ -952,28 +977,88 @@ int fm_locate_build_device(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector<
         LaunchScope ls(ctx, K_IBWT_JUMP, 12.0 * nsplit);
         k_pib_check<<<dim3(sgrid), dim3(256), 0, st>>>(d_off, d_org, d_sb, cnt, S, nsplit, nxt, acc, nullptr, d_bad);
     }
-    if (rc == DK_OK) rc = ctx->hip_ok(hipGetLastError(), "fm locate build");
-    const hipError_t e = hipStreamSynchronize(st);  // (also on failure: the copies above read `aux` and `header`)
+    if (rc == DK_OK) rc = ctx->hip_ok(hipGetLastError(), what);
+    const hipError_t e = hipStreamSynchronize(st);  // (also on failure: the copy above reads `aux`)
     DK_TRY(rc);
     DK_HIP(ctx, e);
     DK_TRY(ctx->mail_read(&ctx->h_mail->packed.ibwt_bad));
     const uint32_t bad = ctx->h_mail->packed.ibwt_bad;
     if (bad != IB_END) {
         ctx->ws_release(mark);
-        if (packed) return ctx->fail(DK_E_STREAM, "fm_locate_build_packed: block %u of the pack: BWT/origin do not describe a single text cycle", bad);
-        return ctx->fail(DK_E_STREAM, "fm_locate_build: BWT/origin do not describe a single text cycle");
+        if (packed) return ctx->fail(DK_E_STREAM, "%s_packed: block %u of the pack: BWT/origin do not describe a single text cycle", what, bad);
+        return ctx->fail(DK_E_STREAM, "%s: BWT/origin do not describe a single text cycle", what);
+    }
+    out = FmWalks{psi, d_off, d_org, d_sb, acc, nsplit, sgrid};
+    return DK_OK;
+}
+}  // namespace
+
+// The locate structure: the front part above, then k_pib_locate twice where the inverse writes the text.
+int fm_locate_build_device(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector<uint32_t> &off, const uint32_t *origin, uint32_t step, void *d_loc,
+                           bool packed) {
+    hipStream_t st = ctx->stream;
+    const size_t count = off.size() - 1, total = off.back();
+    const uint32_t cnt = static_cast<uint32_t>(count), T = static_cast<uint32_t>(total);
+    const FmLocate lc = fm_locate_carve(d_loc, total, count, step);
+    const size_t mark = ctx->ws_mark();
+    const uint32_t header[6] = {FM_LOC_MAGIC, T, cnt, step, static_cast<uint32_t>(lc.rows), static_cast<uint32_t>(lc.nsamp)};
+    // the header, the marks and the mark bits start as zeros (the samples are written one by one)
+    DK_HIP(ctx, hipMemsetAsync(d_loc, 0, (FM_LOC_HEADER + 33 * lc.rows + 1) * sizeof(uint32_t), st));
+    {
+        const hipError_t e = hipMemcpyAsync(d_loc, header, sizeof(header), hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(st);
+            DK_HIP(ctx, e);
+        }
+    }
+    FmWalks w;
+    {
+        const int rc = fm_walks_device(ctx, d_bwt, off, origin, "fm_locate_build", packed, mark, w);
+        if (rc == DK_E_NOMEM) (void)hipStreamSynchronize(st);  // (every other return has synchronised: the copy above reads `header`)
+        DK_TRY(rc);
     }
     const uint32_t shift = static_cast<uint32_t>(ceil_log2_u64(step)), R = static_cast<uint32_t>(lc.rows), NS = static_cast<uint32_t>(lc.nsamp);
     {
         // both walks: a successor entry per position (a random 64-byte line each); the marks' words, the samples
         LaunchScope ls(ctx, K_IBWT_EMIT, 2.0 * 64.0 * total + total / 4.0 + 8.0 * (total >> shift));
-        k_pib_locate<false><<<dim3(sgrid), dim3(256), 0, st>>>(psi, d_off, d_org, d_sb, cnt, S, nsplit, acc, shift, lc.bits, lc.marks, lc.samples, NS);
+        k_pib_locate<false><<<dim3(w.sgrid), dim3(256), 0, st>>>(w.psi, w.off, w.org, w.sb, cnt, FMB_S, w.nsplit, w.dist, shift, lc.bits, lc.marks, lc.samples, NS);
         k_loc_rows<<<dim3(static_cast<unsigned>(div_up(lc.rows, 256))), dim3(256), 0, st>>>(lc.bits, R, lc.marks);
         k_loc_scan<<<dim3(1), dim3(1024), 0, st>>>(lc.marks, R);
-        k_pib_locate<true><<<dim3(sgrid), dim3(256), 0, st>>>(psi, d_off, d_org, d_sb, cnt, S, nsplit, acc, shift, lc.bits, lc.marks, lc.samples, NS);
+        k_pib_locate<true><<<dim3(w.sgrid), dim3(256), 0, st>>>(w.psi, w.off, w.org, w.sb, cnt, FMB_S, w.nsplit, w.dist, shift, lc.bits, lc.marks, lc.samples, NS);
     }
     DK_HIP(ctx, hipGetLastError());
     DK_HIP(ctx, hipStreamSynchronize(st));
+    ctx->ws_release(mark);
+    return DK_OK;
+}
+
+// The extract structure: the same front part, then one walk that stores the slot it stands on at every position that is a multiple of the step.
+int fm_extract_build_device(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector<uint32_t> &off, const uint32_t *origin, uint32_t step, void *d_ext,
+                            bool packed) {
+    hipStream_t st = ctx->stream;
+    const size_t count = off.size() - 1, total = off.back();
+    const uint32_t cnt = static_cast<uint32_t>(count);
+    const std::vector<uint32_t> abase = fm_extract_bases(off, step);
+    uint32_t *anchors = static_cast<uint32_t *>(d_ext) + FM_EXT_HEADER;
+    const size_t mark = ctx->ws_mark();
+    uint32_t *d_abase = ctx->ws_alloc<uint32_t>(count + 1);
+    if (!d_abase) return DK_E_NOMEM;
+    FmWalks w;
+    DK_TRY(fm_walks_device(ctx, d_bwt, off, origin, "fm_extract_build", packed, mark, w));
+    const uint32_t header[5] = {FM_EXT_MAGIC, static_cast<uint32_t>(total), cnt, step, abase.back()};
+    const uint32_t shift = static_cast<uint32_t>(ceil_log2_u64(step));
+    int rc = ctx->hip_ok(hipMemsetAsync(d_ext, 0, FM_EXT_HEADER * sizeof(uint32_t), st), "extract header");
+    if (rc == DK_OK) rc = ctx->hip_ok(hipMemcpyAsync(d_ext, header, sizeof(header), hipMemcpyHostToDevice, st), "extract header");
+    if (rc == DK_OK) rc = ctx->hip_ok(hipMemcpyAsync(d_abase, abase.data(), abase.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st), "anchor bases");
+    if (rc == DK_OK) {
+        // a successor entry per position (a random 64-byte line each); the anchors
+        LaunchScope ls(ctx, K_IBWT_EMIT, 64.0 * total + 4.0 * abase.back());
+        k_pib_anchors<<<dim3(w.sgrid), dim3(256), 0, st>>>(w.psi, w.off, w.org, w.sb, cnt, FMB_S, w.nsplit, w.dist, shift, d_abase, anchors, abase.back());
+        rc = ctx->hip_ok(hipGetLastError(), "fm extract build");
+    }
+    const hipError_t e = hipStreamSynchronize(st);  // (also on failure: the copies above read `header` and `abase`)
+    DK_TRY(rc);
+    DK_HIP(ctx, e);
     ctx->ws_release(mark);
     return DK_OK;
 }

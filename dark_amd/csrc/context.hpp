@@ -36,7 +36,7 @@ enum KernelSlot : int {
     K_IBWT_LF,
     K_IBWT_WALK,
     K_IBWT_JUMP,
-    K_IBWT_EMIT,       // k_ibwt_emit / _copy, k_pib_emit / _copy; the locate structure: k_pib_locate x 2 + k_loc_rows + k_loc_scan
+    K_IBWT_EMIT,       // k_ibwt_emit / _copy, k_pib_emit / _copy; the locate structure: k_pib_locate x 2 + k_loc_rows + k_loc_scan; the extract structure: k_pib_anchors
     K_LF_FINISH,           // k_lf_finish (slot 18: k_bucket_store's until round 5)
     K_BIG_CLASSIFY,    // k_big_reduce + k_big_spine + k_big_apply
     K_BIG_BACK,
@@ -49,7 +49,7 @@ enum KernelSlot : int {
     K_RADIX_SCATTER_TEXT,  // k_radix_scatter<false, true>: first pass, keys built from the text (13 B per pair)
     K_ISA_PARTITION,       // k_isa_init + k_isa_split<true> + k_isa_split<false> (inverse permutation through LDS windows)
     K_ISA_ASSEMBLE,        // k_isa_assemble
-    K_CHAIN,               // k_chain_extract + _ends + _tiles + _spine + _verdicts + _apply (pair chains; their sort is in the radix slots); k_sa_search*, k_fm_count, k_fm_locate
+    K_CHAIN,               // k_chain_extract + _ends + _tiles + _spine + _verdicts + _apply (pair chains; their sort is in the radix slots); k_sa_search*, k_fm_count, k_fm_locate, k_fm_extract
     K_PERIOD,              // k_period_first + _spine + _fill (next break of the block's dominant period, for the period round)
     K_SLOT_COUNT
 };
@@ -290,6 +290,29 @@ size_t fm_locate_build_workspace(size_t total, size_t count);  // an upper bound
 // d_pos[q * max_hits + j] = SA_b[lo + j], DK_FM_NO_HIT behind the range.  Enqueues only; takes no workspace.
 int fm_locate_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, const void *d_index, const void *d_loc,
                      uint32_t step, const uint32_t *d_lo, const uint32_t *d_hi, const uint32_t *d_pat_blk, size_t npat, size_t max_hits, uint32_t *d_pos);
+// The extract structure of a packed L (bwt.hip builds it, fm_index.hip reads it): 32-bit words, over the whole pack.
+//   [0, 64) header: magic, total, count, step, anchors | total / step + count anchors
+// Block b's anchors are the ceil(n_b / step) words from its anchor base, the sum of ceil(n_i / step) over the blocks in front of it: anchor k =
+// the slot (local to the block) of the suffix that starts at position k * step, so anchor 0 = origin_b.  The bases are not stored: the host
+// computes them from the sizes at every call (fm_extract_bases), as it does the offsets.  total / step + count >= their sum.
+constexpr uint32_t FM_EXT_MAGIC = 0x31584D46u;  // "FMX1"
+constexpr uint32_t FM_EXT_HEADER = 64;
+inline size_t fm_extract_words(size_t total, size_t count, size_t step) { return FM_EXT_HEADER + total / step + count; }
+inline std::vector<uint32_t> fm_extract_bases(const std::vector<uint32_t> &off, uint32_t step) {  // count + 1 words; the last one = all anchors
+    std::vector<uint32_t> abase(off.size(), 0);
+    for (size_t i = 0; i + 1 < off.size(); ++i) abase[i + 1] = abase[i] + static_cast<uint32_t>(div_up(off[i + 1] - off[i], step));
+    return abase;
+}
+// bwt.hip: the structure from (L, origin) alone: fm_locate_build_device's front part, then one walk that stores the anchors.  Arguments, errors
+// and synchronisation as there; takes at most fm_locate_build_workspace(total, count) + 4 (count + 1) bytes (rounded up) and releases them.
+int fm_extract_build_device(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector<uint32_t> &off, const uint32_t *origin, uint32_t step, void *d_ext,
+                            bool packed);
+// fm_index.hip: row q of d_out (nrange x max_len bytes, any alignment) = T_b[pos, pos + got) of block d_rng_blk[q] (null: block 0), where pos =
+// d_pos[q] and got = min(d_len[q] (null: max_len), max_len, n_b - pos), 0 for pos >= n_b; zeros behind.  d_abase: the blocks' anchor bases on the
+// device (null: one block, base 0).  Enqueues a memset of the rows and one kernel; takes no workspace.
+int fm_extract_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, const uint32_t *d_abase, size_t count, size_t total, const void *d_index,
+                      const void *d_ext, uint32_t step, const uint32_t *d_pos, const uint32_t *d_len, const uint32_t *d_rng_blk, size_t nrange,
+                      size_t max_len, uint8_t *d_out);
 // packed_dc_device: the DC arrays of every block of a packed L.  compact: block i's entries at [rb_i, rb_i + m_i) (global run order, rb on the
 // device in d_rb[0 .. count], d_rb[count] = all runs); otherwise at [off_i, off_i + m_i).  d_m / d_flags: count words, d_init: count x 256.
 int packed_dc_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, bool compact, uint32_t *d_dist,

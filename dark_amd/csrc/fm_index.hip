@@ -30,6 +30,8 @@
 //          k_fm_rank       the same rank for given (position, symbol) pairs -- the tests' view of it
 // LOCATE   k_fm_locate     a wave per (pattern, hit); at most min(step, n_b) dependent LF steps down to a sampled slot (section 4.14; the sampled
 //                          suffix array it reads is built in bwt.hip by the inverse's kernels: fm_locate_build_device)
+// EXTRACT  k_fm_extract    a wave per (range, chunk of `step` positions): from the chunk's end, whose slot is an anchor, at most min(step, n_b) - 1
+//                          of the same LF steps backwards, a text byte per step (section 4.15; anchors built in bwt.hip: fm_extract_build_device)
 // Containment: the geometry (off, n, total) comes from the caller, never from the index; every position is clamped to [0, n_b] before it is used
 // and a rank reads L only below the position it counts to.  With an index or an L that is not what the build made the results are unspecified
 // but <= n_b, and nothing outside L, the index, the patterns and the two results is touched.
@@ -256,6 +258,23 @@ __global__ __launch_bounds__(64 * FM_WAVES) void k_fm_rank(const uint8_t *__rest
     }
 }
 
+// ---- the LF step of a slot, shared by locate and extract ---------------------------------------------------------------------------------------
+// (v0, v1): this lane's 16 bytes of the row of g = off_b + x, loaded with fm_lane_bytes(g + 1, sl) so that they hold the byte at g.
+// c = L[g], taken from the lane that holds it by a cross-lane read
+__device__ __forceinline__ uint32_t fm_symbol_at(uint64_t v0, uint64_t v1, uint32_t g) {
+    const uint32_t at = g & 15u;
+    return static_cast<uint32_t>(__shfl(static_cast<uint32_t>((at < 8u ? v0 >> (8u * at) : v1 >> (8u * (at - 8u))) & 0xFFu), (g & (FM_BLOCK - 1u)) >> 4, 64));
+}
+// LF(x) for x != origin_b with c = L[g]: the count's later step applied to the slot; the checkpoint word, base_b[c] and one butterfly sum.
+// Clamped to [0, n_b).
+__device__ __forceinline__ uint32_t fm_lf(const uint32_t *__restrict__ cp, const uint32_t *__restrict__ base, uint32_t origin, uint32_t last, uint32_t nb,
+                                          uint32_t x, uint32_t g, uint32_t sl, uint32_t c, uint64_t v0, uint64_t v1) {
+    const uint32_t is_last = c == last ? 1u : 0u;
+    const uint32_t occ = cp[static_cast<size_t>(g >> FM_SHIFT) * 256 + c] + wave_sum(fm_count16(v0, v1, 0x0101010101010101ull * c, fm_lane_bytes(g, sl)));
+    const uint32_t y = base[c] + is_last - (is_last & (origin < x ? 1u : 0u)) + occ;
+    return y < nb ? y : nb - 1u;
+}
+
 // ---- locate ----------------------------------------------------------------------------------------------------------
 
 struct FmLocArgs {
@@ -296,16 +315,82 @@ __global__ __launch_bounds__(64 * FM_WAVES) void k_fm_locate(FmLocArgs a) {
                     if (p < nb) out = static_cast<uint32_t>(p);
                     break;
                 }
-                const uint32_t at = g & 15u;
-                const uint32_t c = static_cast<uint32_t>(__shfl(static_cast<uint32_t>((at < 8u ? v0 >> (8u * at) : v1 >> (8u * (at - 8u))) & 0xFFu),
-                                                                (g & (FM_BLOCK - 1u)) >> 4, 64));
-                const uint32_t is_last = c == last ? 1u : 0u;
-                const uint32_t occ = cp[static_cast<size_t>(row) * 256 + c] + wave_sum(fm_count16(v0, v1, 0x0101010101010101ull * c, fm_lane_bytes(g, sl)));
-                x = base[c] + is_last - (is_last & (origin < x ? 1u : 0u)) + occ;
-                x = x < nb ? x : nb - 1u;
+                x = fm_lf(cp, base, origin, last, nb, x, g, sl, fm_symbol_at(v0, v1, g), v0, v1);
             }
         }
         if (lane == 0) a.pos[item] = out;
+    }
+}
+
+// ---- extract ---------------------------------------------------------------------------------------------------------
+
+struct FmExtArgs {
+    const uint8_t *L; const uint32_t *off, *abase, *blocks, *base, *cp, *anchors, *pos, *len, *rng_blk;
+    uint32_t nrange, max_len, per, total, step_shift; uint8_t *out;
+};
+// A wave per item (q, i), i < per = ceil(max_len / step) + 1: chunk k = pos[q] / step + i of the range's block, [k step, e) with e = min((k + 1)
+// step, n_b), where it meets the range [pos, pos + got).  From the slot of suffix e -- anchor k + 1, or the origin when e = n_b -- L[x] = T[e - 1],
+// and every LF step (locate's, without the marks) gives the byte in front: T[e - 2], ... down to max(k step, pos).  The one step FROM the origin
+// is not the general formula: LF(origin) = C[last] = base_b[last] + Occ_pack(last, off_b), one rank at the block's head.  The byte of step j stays
+// in lane j mod 64; after 64 steps and at the chunk's end every lane stores its own where it lies below pos + got: byte stores from consecutive
+// lanes to consecutive addresses, so a row of any alignment is served.  The rows were zeroed by a memset in front of the kernel.
+// Containment: the anchor index is clamped to the block's anchors, every slot to [0, n_b), `last` to a byte, at most min(step, n_b) steps per item; a store goes
+// to out[q max_len + p - pos] with pos <= p < pos + got <= pos + max_len, and what is stored is a byte of block b's L.
+__global__ __launch_bounds__(64 * FM_WAVES) void k_fm_extract(FmExtArgs a) {
+    const uint8_t *__restrict__ L = a.L;
+    const uint32_t *__restrict__ off = a.off, *__restrict__ cp = a.cp, *__restrict__ rng_blk = a.rng_blk;
+    const uint32_t lane = threadIdx.x & 63u, total = a.total, shift = a.step_shift, step = 1u << shift;
+    const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * FM_WAVES, nitems = static_cast<uint64_t>(a.nrange) * a.per;
+    for (uint64_t item = static_cast<uint64_t>(blockIdx.x) * FM_WAVES + (threadIdx.x >> 6); item < nitems; item += nwaves) {
+        const uint32_t q = static_cast<uint32_t>(item / a.per), i = static_cast<uint32_t>(item - static_cast<uint64_t>(q) * a.per);
+        const uint32_t b = rng_blk ? rng_blk[q] : 0u, s = off[b], nb = off[b + 1] - s;  // (b < count: the caller's check)
+        const uint32_t pos = a.pos[q];
+        if (pos >= nb) continue;
+        uint32_t got = a.len ? a.len[q] : a.max_len;
+        got = got < a.max_len ? got : a.max_len;
+        got = got < nb - pos ? got : nb - pos;
+        const uint64_t cs64 = (static_cast<uint64_t>(pos >> shift) + i) << shift;
+        if (got == 0 || cs64 >= static_cast<uint64_t>(pos) + got) continue;  // an empty range; a chunk behind the range
+        const uint32_t cs = static_cast<uint32_t>(cs64), k = cs >> shift;
+        const uint32_t e = nb - cs > step ? cs + step : nb, lo = cs > pos ? cs : pos, hi = pos + got, steps = e - lo;  // 1 <= steps <= min(step, n_b)
+        // (last indexes base_b and a checkpoint row in the origin's step: cut to a byte, whatever the index holds)
+        const uint32_t origin = a.blocks[4 * static_cast<size_t>(b) + 2], last = a.blocks[4 * static_cast<size_t>(b) + 3] & 0xFFu;
+        const uint32_t *__restrict__ base = a.base + static_cast<size_t>(b) * 256;
+        const uint32_t nanch = (nb + step - 1u) >> shift;
+        uint32_t x;
+        bool at_origin = e == nb;
+        if (at_origin) {
+            x = origin;
+        } else {
+            const uint32_t idx = k + 1u < nanch ? k + 1u : nanch - 1u;
+            x = a.anchors[(a.abase ? a.abase[b] : 0u) + idx];
+        }
+        x = x < nb ? x : nb - 1u;
+        uint8_t *row_out = a.out + static_cast<size_t>(q) * a.max_len;
+        uint32_t mine = 0;
+        for (uint32_t j = 0; j < steps; ++j) {
+            const uint32_t g = s + x, sl = ((g >> FM_SHIFT) << FM_SHIFT) + 16u * lane;
+            uint64_t v0, v1;
+            fm_load16(L, total, sl, fm_lane_bytes(g + 1u, sl), v0, v1);  // (the bytes below g and the one at g, which is below total)
+            const uint32_t c = fm_symbol_at(v0, v1, g);
+            if ((j & 63u) == lane) mine = c;
+            if ((j & 63u) == 63u || j + 1u == steps) {
+                // this lane's byte is that of step j0 + lane, text position e - 1 - (j0 + lane)
+                const uint32_t j0 = j & ~63u;
+                if (j0 + lane <= j) {
+                    const uint32_t p = e - 1u - (j0 + lane);
+                    if (p < hi) row_out[p - pos] = static_cast<uint8_t>(mine);
+                }
+                if (j + 1u == steps) break;
+            }
+            if (at_origin) {
+                const uint32_t y = base[last] + fm_rank1(L, total, cp, last, s, lane);
+                x = y < nb ? y : nb - 1u;
+                at_origin = false;
+            } else {
+                x = fm_lf(cp, base, origin, last, nb, x, g, sl, c, v0, v1);
+            }
+        }
     }
 }
 
@@ -392,6 +477,25 @@ int fm_locate_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, s
         // per item about step / 2 steps of a row of L, a row of mark words and a checkpoint word; the range, the sample and the result
         LaunchScope ls(ctx, K_CHAIN, nitems * (20.0 + 0.5 * step * (FM_BLOCK + 128 + 64)));
         k_fm_locate<<<dim3(grid), dim3(64 * FM_WAVES), 0, ctx->stream>>>(a);
+    }
+    DK_HIP(ctx, hipGetLastError());
+    return DK_OK;
+}
+
+int fm_extract_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, const uint32_t *d_abase, size_t count, size_t total, const void *d_index,
+                      const void *d_ext, uint32_t step, const uint32_t *d_pos, const uint32_t *d_len, const uint32_t *d_rng_blk, size_t nrange,
+                      size_t max_len, uint8_t *d_out) {
+    const FmIndex ix = fm_carve(const_cast<void *>(d_index), total, count);
+    const size_t per = div_up(max_len, step) + 1, nitems = nrange * per;  // the most chunks a range of max_len bytes can touch
+    const unsigned grid = static_cast<unsigned>(std::min<size_t>(div_up(nitems, FM_WAVES), 1u << 20));
+    const FmExtArgs a{d_bwt, d_off, d_abase, ix.blocks, ix.base, ix.cp, static_cast<const uint32_t *>(d_ext) + FM_EXT_HEADER, d_pos, d_len, d_rng_blk,
+                      static_cast<uint32_t>(nrange), static_cast<uint32_t>(max_len), static_cast<uint32_t>(per), static_cast<uint32_t>(total),
+                      static_cast<uint32_t>(ceil_log2_u64(step)), d_out};
+    DK_HIP(ctx, hipMemsetAsync(d_out, 0, nrange * max_len, ctx->stream));  // the zeros behind every range: the kernel stores text bytes only
+    {
+        // per range its two words and its row, twice (zeros, bytes); per byte and per step / 2 bytes walked in vain a row of L and a checkpoint word
+        LaunchScope ls(ctx, K_CHAIN, nrange * (8.0 + 2.0 * max_len + (max_len + 0.5 * step) * (FM_BLOCK + 64)));
+        k_fm_extract<<<dim3(grid), dim3(64 * FM_WAVES), 0, ctx->stream>>>(a);
     }
     DK_HIP(ctx, hipGetLastError());
     return DK_OK;

@@ -1,9 +1,10 @@
 """FM-index over the library's BWT: count the occurrences of patterns without the text and without a suffix array,
-and say where they are from a sampled suffix array (section 4.14).  The reference has no counterpart.  L and the index stay on the GPU, about two
-bytes per text byte; the locate structure adds about n / 8 + 4 n / locate_step."""
+say where they are from a sampled suffix array (section 4.14) and what the text says there from sampled inverse-suffix-array entries (section
+4.15).  The reference has no counterpart.  L and the index stay on the GPU, about two bytes per text byte; the locate structure adds about
+n / 8 + 4 n / locate_step, the extract structure 4 n / extract_step."""
 import numpy as np
 
-from .context import Context, DarkError, _pack_patterns, as_u8, fm_index_bytes, fm_locate_bytes
+from .context import Context, DarkError, _pack_patterns, as_u8, fm_extract_bytes, fm_index_bytes, fm_locate_bytes
 from . import _lib
 
 
@@ -16,9 +17,12 @@ class Index:
     count(patterns[, blocks]) -> (lo, hi) uint32 arrays: the numbers Context.sa_search gives; occurrences(patterns[, blocks]) = hi - lo.
     locate_step (keyword of all four; None: no structure, count only): a power of two in [1, 4096], the distance of the sampled text positions.
     32 is a reasoned choice, not a measured one.
-    locate(patterns[, blocks], max_hits=16) -> a list of uint32 arrays, the first max_hits positions of every pattern in suffix-array order."""
+    locate(patterns[, blocks], max_hits=16) -> a list of uint32 arrays, the first max_hits positions of every pattern in suffix-array order.
+    extract_step (keyword of all four; None: no structure): a power of two in [1, 4096], the distance of the anchored text positions (section 4.15).
+    extract(positions, length[, blocks]) -> a list of bytes, the text at [position, position + length) cut at the block's end; text([block]) ->
+    the whole block; snippets(patterns, before, after[, blocks], max_hits=16) -> per pattern a list of (position, bytes around the hit)."""
 
-    def __init__(self, ctx, d_bwt, sizes, origins, locate_step=None):
+    def __init__(self, ctx, d_bwt, sizes, origins, locate_step=None, extract_step=None):
         import torch
         self._ctx = ctx
         self.sizes = [int(n) for n in sizes]
@@ -44,30 +48,41 @@ class Index:
                 ctx.dev_fm_locate_build(d_bwt, self.total, self.origins[0], self.locate_step, self.d_loc)
             else:
                 ctx.dev_fm_locate_build_packed(d_bwt, self.sizes, self.origins, self.locate_step, self.d_loc)
+        self.extract_step = None if extract_step is None else int(extract_step)
+        self.d_ext = None
+        if extract_step is not None:
+            nbytes = fm_extract_bytes(self.total, len(self.sizes), self.extract_step)
+            if nbytes == 0:
+                raise DarkError(_lib.DK_E_ARG, "extract_step %r is no power of two in [1, 4096]" % (extract_step,))
+            self.d_ext = torch.empty(nbytes // 4, dtype=torch.int32, device=d_bwt.device)
+            if len(self.sizes) == 1:
+                ctx.dev_fm_extract_build(d_bwt, self.total, self.origins[0], self.extract_step, self.d_ext)
+            else:
+                ctx.dev_fm_extract_build_packed(d_bwt, self.sizes, self.origins, self.extract_step, self.d_ext)
 
     @classmethod
-    def from_text(cls, ctx, data, locate_step=None):
+    def from_text(cls, ctx, data, locate_step=None, extract_step=None):
         import torch
         t = as_u8(data)
         d_in = torch.from_numpy(t.copy()).to("cuda:%d" % ctx.device)
         d_bwt = torch.empty_like(d_in)
         origin = ctx.dev_bwt_forward(d_in, len(t), d_bwt)
-        return cls(ctx, d_bwt, [len(t)], [origin], locate_step)
+        return cls(ctx, d_bwt, [len(t)], [origin], locate_step, extract_step)
 
     @classmethod
-    def from_bwt(cls, ctx, bwt, origin, locate_step=None):
+    def from_bwt(cls, ctx, bwt, origin, locate_step=None, extract_step=None):
         import torch
         if not hasattr(bwt, "data_ptr"):
             bwt = torch.from_numpy(as_u8(bwt).copy()).to("cuda:%d" % ctx.device)
-        return cls(ctx, bwt, [bwt.numel()], [origin], locate_step)
+        return cls(ctx, bwt, [bwt.numel()], [origin], locate_step, extract_step)
 
     @classmethod
-    def from_bwt_packed(cls, ctx, d_bwt, sizes, origins, locate_step=None):
-        return cls(ctx, d_bwt, sizes, origins, locate_step)
+    def from_bwt_packed(cls, ctx, d_bwt, sizes, origins, locate_step=None, extract_step=None):
+        return cls(ctx, d_bwt, sizes, origins, locate_step, extract_step)
 
     def resident_bytes(self):
-        """device bytes the index needs to answer: L and the index, and the locate structure where it was built"""
-        return self.total + self.d_index.numel() * 4 + (self.d_loc.numel() * 4 if self.d_loc is not None else 0)
+        """device bytes the index needs to answer: L and the index, and the locate and extract structures where they were built"""
+        return self.total + self.d_index.numel() * 4 + sum(d.numel() * 4 for d in (self.d_loc, self.d_ext) if d is not None)
 
     def count(self, patterns, blocks=None):
         npat = len(patterns)
@@ -99,18 +114,83 @@ class Index:
         npat = len(patterns)
         if npat == 0:
             return []
+        pos = self._locate_dev(patterns, blocks, max_hits).cpu().numpy().view(np.uint32).reshape(npat, -1)
+        return [row[row != _lib.FM_NO_HIT] for row in pos]
+
+    def _locate_dev(self, patterns, blocks, max_hits):
+        """count, then locate: the rows of dev_fm_locate as an int32 device tensor (FM_NO_HIT reads as -1)"""
+        import torch
+        npat = len(patterns)
         d_lo, d_hi = self._count_dev(patterns, blocks)
         d_pos = torch.empty(npat * max(int(max_hits), 1), dtype=torch.int32, device=self.d_bwt.device)
         if len(self.sizes) == 1 and blocks is None:
             self._ctx.dev_fm_locate(self.d_bwt, self.total, self.d_index, self.d_loc, self.locate_step, d_lo, d_hi, npat, max_hits, d_pos)
         else:
             self._ctx.dev_fm_locate_packed(self.d_bwt, self.sizes, self.d_index, self.d_loc, self.locate_step, d_lo, d_hi, blocks, max_hits, d_pos)
-        pos = d_pos.cpu().numpy().view(np.uint32).reshape(npat, -1)
-        return [row[row != _lib.FM_NO_HIT] for row in pos]
+        return d_pos
+
+    def _extract_dev(self, d_pos, d_len, nrange, blocks, max_len):
+        """rows of dev_fm_extract(_packed) for int32 device tensors of starts and lengths (d_len None: max_len each)"""
+        import torch
+        if self.d_ext is None:
+            raise DarkError(_lib.DK_E_ARG, "the index was built without an extract structure (extract_step=None)")
+        d_out = torch.empty(nrange * max(int(max_len), 1), dtype=torch.uint8, device=self.d_bwt.device)
+        if len(self.sizes) == 1 and blocks is None:
+            self._ctx.dev_fm_extract(self.d_bwt, self.total, self.d_index, self.d_ext, self.extract_step, d_pos, d_len, nrange, max_len, d_out)
+        else:
+            if blocks is None:
+                raise DarkError(_lib.DK_E_ARG, "an index over a pack needs the block of every range")
+            self._ctx.dev_fm_extract_packed(self.d_bwt, self.sizes, self.d_index, self.d_ext, self.extract_step, d_pos, d_len, blocks, max_len, d_out)
+        return d_out
+
+    def extract(self, positions, length, blocks=None):
+        """per position the text at [position, position + length) of its block as bytes, cut at the block's end (empty behind it)"""
+        import torch
+        nrange = len(positions)
+        if self.d_ext is None:
+            raise DarkError(_lib.DK_E_ARG, "the index was built without an extract structure (extract_step=None)")
+        if nrange == 0:
+            return []
+        pos = np.array(positions, dtype=np.int64)
+        d_pos = torch.from_numpy(pos.astype(np.uint32).view(np.int32)).to(self.d_bwt.device)
+        rows = self._extract_dev(d_pos, None, nrange, blocks, length).cpu().numpy().reshape(nrange, -1)
+        sizes = np.array(self.sizes, dtype=np.int64)[np.zeros(nrange, np.int64) if blocks is None else np.array(blocks, dtype=np.int64)]
+        got = np.clip(np.minimum(int(length), sizes - pos), 0, None)
+        return [bytes(rows[q, :got[q]]) for q in range(nrange)]
+
+    def text(self, block=0):
+        """the whole text of a block"""
+        return self.extract([0], self.sizes[block], None if len(self.sizes) == 1 else [block])[0]
+
+    def snippets(self, patterns, before, after, blocks=None, max_hits=16):
+        """per pattern a list of (position, bytes): its first max_hits occurrences in suffix-array order, each with the text from `before` bytes
+        in front of it to `after` bytes behind it, cut at the block's ends.  Count, locate and extract run back to back on the device; only the
+        positions and the rows are read back."""
+        import torch
+        if self.d_loc is None or self.d_ext is None:
+            raise DarkError(_lib.DK_E_ARG, "snippets need both structures (locate_step and extract_step)")
+        npat, max_hits, before, after = len(patterns), max(int(max_hits), 1), int(before), int(after)
+        if npat == 0:
+            return []
+        dev = self.d_bwt.device
+        d_hit = self._locate_dev(patterns, blocks, max_hits)  # npat x max_hits positions, -1 where there is none
+        plen = np.repeat(np.array([len(p) for p in patterns], dtype=np.int32), max_hits)
+        found = d_hit >= 0
+        d_start = torch.clamp(d_hit - before, min=0)
+        d_len = torch.where(found, d_hit - d_start + torch.from_numpy(plen).to(dev) + after, torch.zeros_like(d_hit))
+        d_start = torch.where(found, d_start, d_hit)
+        max_len = before + int(plen.max()) + after
+        where = None if blocks is None else [b for b in blocks for _ in range(max_hits)]
+        rows = self._extract_dev(d_start, d_len, npat * max_hits, where, max_len).cpu().numpy().reshape(npat * max_hits, -1)
+        hit = d_hit.cpu().numpy().astype(np.int64)
+        sizes = np.array(self.sizes, dtype=np.int64)[np.zeros(len(hit), np.int64) if where is None else np.array(where, dtype=np.int64)]
+        start = np.maximum(hit - before, 0)
+        got = np.minimum(hit - start + plen + after, sizes - start)
+        return [[(int(hit[i]), bytes(rows[i, :got[i]])) for i in range(q * max_hits, (q + 1) * max_hits) if hit[i] >= 0] for q in range(npat)]
 
     def occurrences(self, patterns, blocks=None):
         lo, hi = self.count(patterns, blocks)
         return (hi - lo).astype(np.uint32)
 
 
-__all__ = ["Index", "Context", "fm_index_bytes", "fm_locate_bytes"]
+__all__ = ["Index", "Context", "fm_index_bytes", "fm_locate_bytes", "fm_extract_bytes"]

@@ -9,6 +9,7 @@
 //   dark::model::{dark,exp,ybs,simple,bbb}::Model, dark::model::raw::Out   src/model/*.rs  (the state lives in the library; the type selects it)
 // Where the Rust code panics (assert!/unwrap) this throws dark::Error; io::Result becomes dark::Result{ok, message}.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -266,22 +267,28 @@ namespace fm {
 // dk_dev_fm_build once and dk_dev_fm_count after it.)
 // locate_step (0: none, count only; else a power of two in [1, 4096]): the distance of the sampled text positions of `locate` (dk_fm_locate,
 // section 4.14), which says WHERE the patterns occur -- still without the text and without a full suffix array.
+// extract_step (0: none; else a power of two in [1, 4096]): the distance of the anchored text positions of `extract` (dk_fm_extract, section
+// 4.15), which says WHAT the text is at given positions -- so L and the structures stand in for the text in every query.
 class Index {
 public:
-    Index(std::vector<uint8_t> bwt, size_t origin, int device = 0, uint32_t locate_step = 0)
-        : ctx_(bwt.size(), device, DK_CTX_DECODER), bwt_(std::move(bwt)), origin_(origin), step_(locate_step) {
+    Index(std::vector<uint8_t> bwt, size_t origin, int device = 0, uint32_t locate_step = 0, uint32_t extract_step = 0)
+        : ctx_(bwt.size(), device, DK_CTX_DECODER), bwt_(std::move(bwt)), origin_(origin), step_(locate_step), ext_step_(extract_step) {
         if (origin_ >= bwt_.size()) throw Error(DK_E_ARG, "assertion failed: origin < bwt.len()");
         if (step_ && dk_fm_locate_bytes(bwt_.size(), 1, step_) == 0) throw Error(DK_E_ARG, "locate_step is no power of two in [1, 4096]");
+        if (ext_step_ && dk_fm_extract_bytes(bwt_.size(), 1, ext_step_) == 0) throw Error(DK_E_ARG, "extract_step is no power of two in [1, 4096]");
     }
     // the index of a text: forward BWT on a full context that is released again, then as above
-    static Index from_text(const std::vector<uint8_t> &text, int device = 0, uint32_t locate_step = 0) {
+    static Index from_text(const std::vector<uint8_t> &text, int device = 0, uint32_t locate_step = 0, uint32_t extract_step = 0) {
         detail::Ctx full(text.size(), device);
         auto lo = bwt::transform(full, text);
-        return Index(std::move(lo.first), lo.second, device, locate_step);
+        return Index(std::move(lo.first), lo.second, device, locate_step, extract_step);
     }
     size_t len() const { return bwt_.size(); }
-    // device bytes that answer a query: L and the index, and the locate structure where one was asked for
-    size_t resident_bytes() const { return bwt_.size() + dk_fm_index_bytes(bwt_.size(), 1) + (step_ ? dk_fm_locate_bytes(bwt_.size(), 1, step_) : 0); }
+    // device bytes that answer a query: L and the index, and the locate and extract structures where they were asked for
+    size_t resident_bytes() const {
+        return bwt_.size() + dk_fm_index_bytes(bwt_.size(), 1) + (step_ ? dk_fm_locate_bytes(bwt_.size(), 1, step_) : 0) +
+               (ext_step_ ? dk_fm_extract_bytes(bwt_.size(), 1, ext_step_) : 0);
+    }
     // result[q] = (lo, hi) as from saca::Constructor::search on the text; hi - lo = the number of places patterns[q] occurs
     std::vector<std::pair<uint32_t, uint32_t>> count(const std::vector<std::vector<uint8_t>> &patterns) {
         std::vector<size_t> lens;
@@ -320,12 +327,28 @@ public:
             for (size_t j = 0; j < max_hits && pos[q * max_hits + j] != DK_FM_NO_HIT; ++j) out[q].push_back(pos[q * max_hits + j]);
         return out;
     }
+    // result[q] = the text at [positions[q], positions[q] + length), cut at the text's end (empty from there on)
+    std::vector<std::vector<uint8_t>> extract(const std::vector<uint32_t> &positions, size_t length) {
+        if (!ext_step_) throw Error(DK_E_ARG, "the index was made without an extract structure (extract_step = 0)");
+        std::vector<uint8_t> rows(positions.size() * length + 1);
+        std::vector<uint32_t> pos(positions);
+        pos.push_back(0);
+        int rc = dk_fm_extract(ctx_.get(), bwt_.data(), bwt_.size(), static_cast<uint32_t>(origin_), ext_step_, pos.data(), nullptr, positions.size(),
+                               length, rows.data());
+        if (rc != DK_OK) throw Error(rc, ctx_.error());
+        std::vector<std::vector<uint8_t>> out(positions.size());
+        for (size_t q = 0; q < positions.size(); ++q) {
+            const size_t got = positions[q] < bwt_.size() ? std::min<size_t>(length, bwt_.size() - positions[q]) : 0;
+            out[q].assign(rows.begin() + static_cast<std::ptrdiff_t>(q * length), rows.begin() + static_cast<std::ptrdiff_t>(q * length + got));
+        }
+        return out;
+    }
     detail::Ctx &context() { return ctx_; }  // context().purpose() == DK_CTX_DECODER
 private:
     detail::Ctx ctx_;
     std::vector<uint8_t> bwt_;
     size_t origin_;
-    uint32_t step_;
+    uint32_t step_, ext_step_;
 };
 }  // namespace fm
 

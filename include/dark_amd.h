@@ -307,6 +307,38 @@ int dk_dev_fm_locate_packed(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t count,
  * when L, the two structures, the batch, its results and the locate build's workspace do not fit the context's workspace. */
 int dk_fm_locate(dk_ctx *any_ctx, const uint8_t *bwt, size_t n, uint32_t origin, uint32_t step, const uint8_t *pat, size_t npat,
                  const size_t *pat_len, size_t max_hits, uint32_t *lo, uint32_t *hi, uint32_t *pos);
+/* ---- FM-index: extract.  What the text says at given positions, from L, the index and sampled inverse-suffix-array entries (csrc/bwt.hip,
+ * csrc/fm_index.hip) ----
+ * A third opaque DEVICE buffer of the caller's: dk_fm_extract_bytes(total, count, step) bytes, 4-byte aligned.  It keeps, for every block, the
+ * slot of the suffix that starts at each multiple of `step` (the block's ANCHORS; positions local to the block): 4 (total / step + count) + 256
+ * bytes, 0.125 n at step 32.  dk_fm_extract_bytes needs no GPU; 0 for what dk_fm_index_bytes refuses and for a step that is no power of two in
+ * [1, 4096].
+ * dk_dev_fm_extract_build* need (L, origin) only: the front part of dk_dev_fm_locate_build* -- the inverse BWT's successor table, splitter walk
+ * and jumps -- and one more walk that stores the anchors.  DK_E_STREAM, DK_E_ARG and the workspace exactly as for dk_dev_fm_locate_build*
+ * (4 bytes per block more).
+ * dk_dev_fm_extract*: d_pos / d_len (device, nrange words each; d_len may be null: every range is max_len long) are start positions local to
+ * the range's block and lengths; a row of dk_dev_fm_locate's d_pos can be passed as it is.  Row q of d_out (device, nrange x max_len BYTES, any
+ * alignment) = T_b[pos[q] + j] for j < got[q] = min(len[q], max_len, n_b - pos[q]), zero bytes behind them; got[q] = 0 for pos[q] >= n_b,
+ * DK_FM_NO_HIT included.  `step` is the one of the build.  One range (0, n) with max_len = n gives the whole text.  nrange == 0: DK_OK, nothing
+ * written.  DK_E_ARG for max_len == 0, nrange x max_len > 2^31, range_block[q] >= count (range_block in HOST memory), null or misaligned word
+ * pointers, a bad step.  Workspace: 8 bytes; in a pack 8 bytes per block and 4 per range.
+ * Both structures are TRUSTED, and contained as count and locate are: every slot is clamped to [0, n_b), every anchor index to the block's
+ * anchors, at most min(step, n_b) steps are taken per (range, chunk of `step` positions), stores go to row q's max_len bytes only; for any
+ * bytes in L, the index, d_ext, d_pos and d_len every byte written is a byte of block b's L or zero, and nothing outside those buffers and
+ * d_out is touched. */
+size_t dk_fm_extract_bytes(size_t total, size_t count, uint32_t step);
+int dk_dev_fm_extract_build(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t n, uint32_t origin, uint32_t step, void *d_ext);
+int dk_dev_fm_extract_build_packed(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const uint32_t *origin /* host */,
+                                   uint32_t step, void *d_ext);
+int dk_dev_fm_extract(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t n, const void *d_index, const void *d_ext, uint32_t step,
+                      const uint32_t *d_pos, const uint32_t *d_len, size_t nrange, size_t max_len, uint8_t *d_out);
+int dk_dev_fm_extract_packed(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const void *d_index, const void *d_ext,
+                             uint32_t step, const uint32_t *d_pos, const uint32_t *d_len, size_t nrange, const uint32_t *range_block /* host */,
+                             size_t max_len, uint8_t *d_out);
+/* from and to host memory: upload, both builds, extract, download of the nrange x max_len rows (len may be null).  DK_E_ARG when L, the two
+ * structures, the ranges, the rows and the larger build workspace do not fit the context's workspace. */
+int dk_fm_extract(dk_ctx *any_ctx, const uint8_t *bwt, size_t n, uint32_t origin, uint32_t step, const uint32_t *pos, const uint32_t *len,
+                  size_t nrange, size_t max_len, uint8_t *out);
 /* for the tests: d_out[q] = occurrences of d_sym[q] in d_bwt[0, min(d_pos[q], total)), computed by the count kernel's rank (all device memory) */
 int dk_dbg_dev_fm_rank(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t total, const void *d_index,
                        const uint32_t *d_pos, const uint8_t *d_sym, size_t nq, uint32_t *d_out);

@@ -1358,33 +1358,76 @@ struct DarkMergeSide5 {
         if (log > 4) DarkMergeSide::flat_tail(e, dist + 1, log);
         return true;
     }
-    bool bulk(const uint32_t *dist, const uint8_t *, size_t count, USink &e) {  // (see DarkMergeSide::bulk)
+    // the sixteen ways four flat mantissa bits can go, most significant first, as the four events they become (flat_tail's events)
+    static const UEvent *flat_table() {
+        struct Table { alignas(64) UEvent ev[16][4]; };
+        static const Table table = [] {
+            Table t;
+            for (uint32_t i = 0; i < 16; ++i)
+                for (uint32_t j = 0; j < 4; ++j) {
+                    const uint32_t one = (i >> (3 - j)) & 1u;
+                    t.ev[i][j] = UEvent{1ull << 52, one << 11, 2048u + (one << 11)};
+                }
+            return t;
+        }();
+        return &table.ev[0][0];
+    }
+    // A stretch of distances with the four rings' cursors in registers (see DarkMergeSide::bulk), in three grades:
+    //   * a RUN of small distances (log 1 .. 7: one mixed decision, at most three flat bits) whose length is bounded beforehand by what the
+    //     four batches hold whatever the distances turn out to be -- a distance takes one event of each half, at most three of the mantissa
+    //     ring and leaves at most seven -- so that the loop over the run asks one question per distance (is it small) and keeps everything in
+    //     registers; the flat bits come as one 64-byte copy out of flat_table().  (With the five bounds asked per distance and the flat events
+    //     built one by one this loop was 110 instructions long, with the mantissa cursor and the loop count on the stack; once the coder's
+    //     chain was shorter the merger was the stage that never waited.)
+    //   * a distance up to log 16 (one in five of a text block has log >= 8), with the bounds asked, still on the local cursors;
+    //   * anything else -- larger still, or close to the end of a batch -- through encode() between two synchronisations of the cursors.
+    bool bulk(const uint32_t *dist, const uint8_t *, size_t count, USink &e) {
         const UEvent *pa_end, *pb_end, *pm_end, *pa = half_a.cursor(&pa_end), *pb = half_b.cursor(&pb_end), *pm = mantissa.cursor(&pm_end);
         UEvent *o_end, *o = e.cursor(&o_end);
-        for (size_t k = 0; k < count; ++k) {
-            const uint32_t d = dist[k];
-            const unsigned log = bit_length(d + 1);
-            const unsigned nm = log > 3 ? 3 : log - 1;
-            if (__builtin_expect(log - 1u <= 6u && pa < pa_end && pb < pb_end && pm + 4 <= pm_end && o + 12 <= o_end, 1)) {  // log 1 .. 7: one mixed decision, flat bits <= 3
+        const UEvent *const flat = flat_table();
+        const uint32_t *dp = dist, *const dist_end = dist + count;
+        while (dp != dist_end) {
+            std::ptrdiff_t run = std::min<std::ptrdiff_t>(std::min(pa_end - pa, pb_end - pb), dist_end - dp);
+            run = std::min(run, pm_end - pm >= 4 ? (pm_end - pm - 4) / 3 + 1 : 0);  // the last of them still reads four events at pm
+            run = std::min(run, o_end - o >= 12 ? (o_end - o - 12) / 7 + 1 : 0);    // ... and still touches twelve places at o
+            for (const uint32_t *const run_end = dp + run; dp != run_end; ++dp) {
+                const uint32_t v = *dp + 1;
+                const unsigned log = bit_length(v);
+                if (__builtin_expect(log - 1u > 6u, 0)) break;
+                const unsigned nm = log > 3 ? 3 : log - 1, left = log > 4 ? log - 4 : 0;
                 *o++ = mixed(*pa++, *pb++, inv);
                 std::memcpy(static_cast<void *>(o), pm, 4 * sizeof(UEvent));
                 o += nm;
                 pm += nm;
-                const uint32_t v = d + 1;
-                const unsigned left = log > 4 ? log - 4 : 0;
-#pragma GCC unroll 4
-                for (unsigned j = 0; j < 4; ++j) {
-                    const uint32_t one = (v >> ((left - 1 - j) & 31u)) & 1u;
-                    o[j] = UEvent{1ull << 52, one << 11, 2048u + (one << 11)};
+                std::memcpy(static_cast<void *>(o), flat + 4 * (((v << 4) >> left) & 15u), 4 * sizeof(UEvent));  // bits left - 1 .. 0 of v on top of a nibble
+                o += left;
+            }
+            if (dp == dist_end) break;
+            const uint32_t v = *dp + 1;
+            const unsigned log = bit_length(v);  // (*dp = 2^32 - 1 gives 0 and goes the slow way, which refuses it)
+            if (log - 1u <= 15u && pa + 10 <= pa_end && pb + 10 <= pb_end && pm + 4 <= pm_end && o + 28 <= o_end) {
+                // log 1 .. 16: log - 7 mixed bits of the unary extension behind the mixed decision (at most nine), at most twelve flat bits
+                const unsigned nm = log > 3 ? 3 : log - 1, left = log > 4 ? log - 4 : 0;
+                *o++ = mixed(*pa++, *pb++, inv);
+                for (unsigned i = kMaxLogCode; i <= log; ++i) *o++ = mixed_bit(*pa++, *pb++, i < log);
+                std::memcpy(static_cast<void *>(o), pm, 4 * sizeof(UEvent));
+                o += nm;
+                pm += nm;
+                std::memcpy(static_cast<void *>(o), flat + 4 * (((v << 4) >> left) & 15u), 4 * sizeof(UEvent));
+                if (left > 4) {  // (what is written beyond `left` is overwritten by the next events)
+                    std::memcpy(static_cast<void *>(o + 4), flat + 4 * (((v << 8) >> left) & 15u), 4 * sizeof(UEvent));
+                    std::memcpy(static_cast<void *>(o + 8), flat + 4 * (((v << 12) >> left) & 15u), 4 * sizeof(UEvent));
                 }
                 o += left;
+                ++dp;
                 continue;
             }
             half_a.done(pa);
             half_b.done(pb);
             mantissa.done(pm);
             e.done(o);
-            if (!encode(d, 0, e)) return false;
+            if (!encode(*dp, 0, e)) return false;
+            ++dp;
             pa = half_a.cursor(&pa_end);
             pb = half_b.cursor(&pb_end);
             pm = mantissa.cursor(&pm_end);
@@ -1398,9 +1441,92 @@ struct DarkMergeSide5 {
     }
 };
 
+// One batch of uniform events on the coder's fast path: the caller has made sure that 4 * count + 12 bytes are writable at *pp.
+// The coder's state is (low, span = hi - low), and what travels from one decision to the next is the QUOTIENT r = span / total.  With
+// w = to - from the new span is s = r * w (< 2^32), and the next quotient floor(s * inv' / 2^64), inv' = ceil(2^64 / total'), is
+//     floor(r * M / 2^64) = r * (M >> 64) + mulhi(r, M mod 2^64)            with M = w * inv' < 2^78:
+// the same number (r * M_hi * 2^64 is a multiple of 2^64), but both products start from r itself, and M is made of event data alone, which
+// lie in the ring long before the chain arrives.  Five decisions in six shift nothing out and nearly all the others one byte, so the
+// quotient after a one-byte shift, the same two products with M << 8, is started beside it and the shift only picks one of them:
+//     r -> (imul || mulx) -> add -> select,
+// six cycles where r -> s = r * w (imul) -> mulhi(s, inv') (mulx) -> select had eight.  The select asks "do the top bytes of the borders
+// differ", (lo ^ h) & 0xFF000000, which is r -> imul -> add -> xor -> test -> select: seven; the count of leading zeros that the shifts
+// need is beside that path.  (The one-byte candidate is only right modulo 2^32 where s << 8 does not fit 32 bits; it is chosen only when
+// the borders share their top byte, s < 2^24.)  A shift of two or three bytes, or a threshold cut, computes its quotient again from the
+// span (rare, predicted), and so does the first decision of a batch: one multiply in 2048 decisions, and no batch ever reads another's slot.
+// (kept out of line: inlined into a large body its loop lost registers to spills -- `low` went through the stack)
+__attribute__((noinline)) int code_uniform_batch(const UEvent *ev, uint32_t count, RangeState &rs, uint8_t **pp) {
+    if (count == 0) return DK_OK;
+    int err = DK_OK;
+    uint8_t *p = *pp;
+    uint32_t low = rs.low, span = rs.hi - rs.low;
+    uint32_t r = static_cast<uint32_t>((static_cast<unsigned __int128>(span) * ev[0].inv) >> 64);
+    const UEvent *const last = ev + (count - 1);
+    for (; ev != last; ++ev) {
+        const uint64_t inv_next = ev[1].inv;
+        const uint32_t from = ev->from, to = ev->to;
+        const unsigned __int128 m = static_cast<unsigned __int128>(inv_next) * (to - from);  // off the chain: event data only
+        const uint64_t m_lo = static_cast<uint64_t>(m), m_hi = static_cast<uint64_t>(m >> 64);
+        uint64_t m_hi8 = m_hi << 8;
+        __asm__("" : "+r"(m_hi8));  // (a factor of its own: otherwise r * m_hi is shifted behind the multiply, on the chain)
+        uint32_t lo = low + r * from, h = low + r * to;
+        const unsigned __int128 t = static_cast<unsigned __int128>(r) * m_lo;  // one multiply, both halves: r * M = (r * M_hi + t_hi) * 2^64 + t_lo
+        const uint64_t t_lo = static_cast<uint64_t>(t), t_hi = static_cast<uint64_t>(t >> 64);
+        uint32_t r_stay = static_cast<uint32_t>(r * m_hi + t_hi);
+        uint64_t byte_part = r * m_hi8 + (t_lo >> 56);  // (r * M) >> 56 = this + (t_hi << 8): only one shift and one add behind the multiply's high half
+        __asm__("" : "+r"(byte_part));                // (left alone the compiler shifts r_stay and t_lo as a pair: a double shift of three cycles behind the add)
+        uint32_t r_byte = static_cast<uint32_t>(byte_part + (t_hi << 8));
+        // (both candidates in registers, then the choice: left alone the compiler may choose first and compute once -- the condition
+        // back on the chain in front of the arithmetic)
+        __asm__("" : "+r"(r_stay), "+r"(r_byte));
+        const uint32_t x = lo ^ h;
+        const unsigned sh = static_cast<unsigned>(__builtin_clz(x | 1u)) & 24u;  // (x = 0, an empty interval or r = 0: s = 0 -- caught below; | 1 moves no other count)
+        const uint32_t be = __builtin_bswap32(lo);
+        std::memcpy(p, &be, 4);
+        p += sh >> 3;
+        uint32_t s = (h - lo) << sh;
+        lo <<= sh;
+        r = (x & kTopMask) ? r_stay : r_byte;
+        if (__builtin_expect(sh > 8u || s <= kRangeThreshold, 0)) {
+            if (x == 0) { err = DK_E_INTERNAL; break; }
+            if (s <= kRangeThreshold) {  // threshold cut: the reference's loop from its second round on
+                h = lo + s;
+                int shifted = static_cast<int>(sh >> 3);
+                for (;;) {
+                    const uint32_t lim = h & kTopMask;
+                    if (h - lim >= lim - lo) lo = lim; else h = lim - 1;
+                    const uint32_t x2 = lo ^ h;
+                    if (x2 == 0) { err = DK_E_INTERNAL; break; }
+                    const unsigned sh2 = static_cast<unsigned>(__builtin_clz(x2)) & 24u;
+                    const uint32_t be2 = __builtin_bswap32(lo);
+                    std::memcpy(p, &be2, 4);
+                    p += sh2 >> 3;
+                    shifted += static_cast<int>(sh2 >> 3);
+                    if (shifted > 4) { err = DK_E_INTERNAL; break; }
+                    lo <<= sh2;
+                    h <<= sh2;
+                    if (h - lo > kRangeThreshold) break;
+                }
+                if (err) break;
+                s = h - lo;
+            }
+            r = static_cast<uint32_t>((static_cast<unsigned __int128>(s) * inv_next) >> 64);
+        }
+        low = lo;
+        span = s;
+    }
+    rs.low = low;
+    rs.hi = low + span;
+    if (!err) {  // the last decision of the batch: nobody's quotient to prepare
+        const int nb = r ? rs.narrow(r, ev->from, ev->to, p) : -1;
+        if (nb < 0) err = DK_E_INTERNAL; else p += nb;
+    }
+    *pp = p;
+    return err;
+}
+
 // the calling thread: the range coder over ring U
-// (kept out of line: inlined into the callers' large bodies its loop lost registers to spills -- `low` went through the stack)
-__attribute__((noinline)) int code_uniform(URing &ring, uint8_t *out, size_t cap, size_t *out_len) {
+int code_uniform(URing &ring, uint8_t *out, size_t cap, size_t *out_len) {
     RangeState rs;
     size_t len = 0;
     int err = DK_OK;
@@ -1409,65 +1535,8 @@ __attribute__((noinline)) int code_uniform(URing &ring, uint8_t *out, size_t cap
         const uint32_t count = v & ~URing::kEnd;
         const UEvent *ev = ring.slot(slot);
         if (!err && len + 4 * static_cast<size_t>(count) + 12 <= cap) {  // room for the worst case of this batch: unchecked stores
-            // The coder's state as (low, span = hi - low): the new span is r * (to - from) shifted like the borders -- computed beside the
-            // two border products instead of by a subtraction after the shift -- so the chain from one decision to the next is
-            //     span -> r (mulx) -> low + r * from (imul, add) -> xor with the upper border -> clz & 24 -> shifted span.
             uint8_t *p = out + len;
-            uint32_t low = rs.low, span = rs.hi - rs.low;
-            // The quotient of the NEXT decision is asked for before this one's byte shift is known: five decisions in six shift nothing out and
-            // nearly all the others one byte, so r' = (s * inv') >> 64 and ((s << 8) * inv') >> 64 are both started as soon as the new span s is
-            // there, and the count of leading zeros only picks one of them.  The chain from one decision to the next is then
-            //     r -> s = r * width (imul) -> r' (mulx) -> select,
-            // eight cycles where the straight form (mulx -> imul, add -> xor -> clz & 24 -> shift -> mulx) has twelve; a shift of two or three
-            // bytes, or a threshold cut, computes its quotient again (rare, predicted).
-            uint32_t r = count ? static_cast<uint32_t>((static_cast<unsigned __int128>(span) * ev[0].inv) >> 64) : 0u;
-            for (uint32_t k = 0; k < count; ++k) {
-                const uint64_t inv_next = ev[k + 1 < count ? k + 1 : k].inv;  // (the last decision of a batch: its own again, never used)
-                uint32_t lo = low + r * ev[k].from, h = low + r * ev[k].to, s = r * (ev[k].to - ev[k].from);
-                const uint32_t r_stay = static_cast<uint32_t>((static_cast<unsigned __int128>(s) * inv_next) >> 64);
-                uint32_t r_byte = static_cast<uint32_t>((static_cast<unsigned __int128>(static_cast<uint64_t>(s) << 8) * inv_next) >> 64);
-                // (both products, then the choice: left alone the compiler chooses between s and s << 8 first and multiplies once -- the shift
-                // count back on the chain in front of the multiply)
-                uint32_t r_stay_ = r_stay;
-                __asm__("" : "+r"(r_stay_), "+r"(r_byte));
-                const uint32_t x = lo ^ h;
-                if (__builtin_expect(r == 0 || x == 0, 0)) { err = DK_E_INTERNAL; break; }
-                const unsigned sh = static_cast<unsigned>(__builtin_clz(x)) & 24u;
-                const uint32_t be = __builtin_bswap32(lo);
-                std::memcpy(p, &be, 4);
-                p += sh >> 3;
-                lo <<= sh;
-                s <<= sh;
-                r = sh ? r_byte : r_stay_;
-                if (__builtin_expect(sh > 8u || s <= kRangeThreshold, 0)) {
-                    if (s <= kRangeThreshold) {  // threshold cut: the reference's loop from its second round on
-                        h = lo + s;
-                        int shifted = static_cast<int>(sh >> 3);
-                        for (;;) {
-                            const uint32_t lim = h & kTopMask;
-                            if (h - lim >= lim - lo) lo = lim; else h = lim - 1;
-                            const uint32_t x2 = lo ^ h;
-                            if (x2 == 0) { err = DK_E_INTERNAL; break; }
-                            const unsigned sh2 = static_cast<unsigned>(__builtin_clz(x2)) & 24u;
-                            const uint32_t be2 = __builtin_bswap32(lo);
-                            std::memcpy(p, &be2, 4);
-                            p += sh2 >> 3;
-                            shifted += static_cast<int>(sh2 >> 3);
-                            if (shifted > 4) { err = DK_E_INTERNAL; break; }
-                            lo <<= sh2;
-                            h <<= sh2;
-                            if (h - lo > kRangeThreshold) break;
-                        }
-                        if (err) break;
-                        s = h - lo;
-                    }
-                    r = static_cast<uint32_t>((static_cast<unsigned __int128>(s) * inv_next) >> 64);
-                }
-                low = lo;
-                span = s;
-            }
-            rs.low = low;
-            rs.hi = low + span;
+            err = code_uniform_batch(ev, count, rs, &p);
             len = static_cast<size_t>(p - out);
         } else if (!err) {  // close to the end of the caller's buffer: every event through a scratch word, exact check
             for (uint32_t k = 0; k < count; ++k) {

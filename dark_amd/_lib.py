@@ -133,6 +133,8 @@ SIGNATURES = {
     "dk_dbg_dev_local_sort": (_i, [_vp, _vp, _vp, _sz, _i, _i]),
     "dk_dbg_dev_sort_groups": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, C.c_uint32, _i, _i]),
     "dk_dbg_dev_inverse_permutation": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "dk_dbg_mail_fill": (_i, [_vp, _i]),
+    "dk_dbg_ws_peek": (_i, [_vp, _sz, _vp]),
 }
 
 _lib = None

@@ -655,6 +655,16 @@ class Context:
         out["routes"] = {name for name, bit in _lib.ROUTES.items() if st.sa_route & bit}  # which ways the last suffix sort took
         return out
 
+    def dbg_mail_fill(self, byte):
+        """dk_dbg_mail_fill: every word of the stages' mailbox (device page and host twin) = byte; between complete calls only"""
+        self._ck(self._lib.dk_dbg_mail_fill(self._h, int(byte)))
+
+    def dbg_ws_peek(self, nbytes):
+        """dk_dbg_ws_peek: nbytes of a fresh workspace allocation as a stage would find them (tuning build, DK_POISON=b: all b) -> uint8 array"""
+        out = np.empty(int(nbytes), dtype=np.uint8)
+        self._ck(self._lib.dk_dbg_ws_peek(self._h, len(out), _ptr(out)))
+        return out
+
     def dbg_sort_pairs(self, keys, vals, begin_bit=0, end_bit=64):
         keys = np.ascontiguousarray(keys, dtype=np.uint64).copy()
         vals = np.ascontiguousarray(vals, dtype=np.uint32).copy()

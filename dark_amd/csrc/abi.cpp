@@ -2205,6 +2205,33 @@ int dk_dbg_stream_encode_gated(int model_id, size_t n, const uint32_t init[256],
     s.stall_ms = stall_ms;
     return encode_block_stream(model_id, s, out, out_cap, out_len, host_threads);
 }
+// Both serve every purpose of a context (no forward_entry): the stages of a decoder context are poisoned through them too.
+int dk_dbg_mail_fill(dk_ctx *ctx, int byte) {
+    DK_TRY(begin_call(ctx));  // (refuses an open batch: its stages are between their clears and their reads)
+    if (byte < 0 || byte > 255) return ctx->fail(DK_E_ARG, "dk_dbg_mail_fill: %d is no byte", byte);
+    // every word: no stage takes one over from the call before it (mailbox.hpp), so there is nothing to leave out
+    DK_TRY(ctx->mail_fill(ctx->d_mail, byte));  // (the whole struct as one "member")
+    DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::memset(ctx->h_mail, byte, sizeof *ctx->h_mail);
+    return DK_OK;
+}
+int dk_dbg_ws_peek(dk_ctx *ctx, size_t nbytes, uint8_t *host_out) {
+    DK_TRY(begin_call(ctx));
+    if (!host_out || nbytes == 0) return ctx->fail(DK_E_ARG, "dk_dbg_ws_peek: null pointer or nothing to read");
+    // as a stage does: an allocation nobody needs first (released again, so that the next one starts where a call's second allocation would,
+    // on bytes an earlier allocation has owned), then the one that is read back before anything has written it
+    const size_t mark = ctx->ws_mark();
+    if (!ctx->ws_alloc_bytes(1)) return DK_E_NOMEM;
+    ctx->ws_release(mark);
+    const uint8_t *p = static_cast<const uint8_t *>(ctx->ws_alloc_bytes(nbytes));
+    if (!p) return DK_E_NOMEM;
+    const hipError_t e = hipMemcpyAsync(host_out, p, nbytes, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+    ctx->ws_release(mark);
+    DK_HIP(ctx, e);
+    DK_HIP(ctx, e2);
+    return DK_OK;
+}
 int dk_dbg_dev_local_sort(dk_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, size_t count, int begin_bit, int end_bit) {
     DK_TRY(begin_call(ctx, "dk_dbg_dev_local_sort"));
     ScopedCall sc(ctx);

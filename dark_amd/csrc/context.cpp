@@ -47,7 +47,9 @@ void *dk_ctx::ws_try_alloc_bytes(size_t bytes) {
 }
 
 // tuning build, DK_POISON=<byte>: every allocation from the workspace is filled with that byte first -- a read of memory nobody has written
-// gives the same wrong answer every time instead of depending on what the previous call left behind
+// gives the same wrong answer every time instead of depending on what the previous call left behind (rounding slack included: ws_alloc_bytes /
+// ws_try_alloc_bytes pass the aligned size).  The fill goes to ctx->stream ONLY: a buffer whose first user runs on side_stream must be allocated
+// before ev_fork is recorded, or the fill may land on top of what the side stream has already written.
 void dk_ctx::ws_poison(void *p, size_t bytes) {
 #ifdef DK_TUNING
     static const int pattern = dk::tuning_knob("DK_POISON", -1);

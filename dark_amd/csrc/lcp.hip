@@ -380,7 +380,11 @@ int lcp_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, size_t
         DK_HIP(ctx, hipGetLastError());
         if (!passes++) limit += longs;  // every pass settles at least one of the positions the first pass wanted to list
         if (longs <= long_cap && giants <= giant_cap) break;
-        if (passes > limit) return ctx->fail(DK_E_INTERNAL, "the LCP pass's lists did not drain");
+        if (passes > limit) {
+            DK_HIP(ctx, hipStreamSynchronize(st));  // (k_lcp_giant may still be walking the list that the release below gives away)
+            ctx->ws_release(mark);
+            return ctx->fail(DK_E_INTERNAL, "the LCP pass's lists did not drain");
+        }
     }
     {
         LaunchScope ls(ctx, K_RERANK_REDUCE, 4.0 * total);

@@ -4,6 +4,10 @@
 // otherwise, the writers are kernels and fills on ctx->stream, and the host reads the twin in h_mail behind a copy and a synchronise on that stream.
 // Two stages of one call never overlap (every API call runs its stages one after another on ctx->stream); what does run beside the main stream is the
 // L-first path's early pass over the deep groups on ctx->side_stream, between ev_fork and ev_join: the words it touches say so.
+// NO WORD LIVES FROM ONE CALL TO THE NEXT.  A word that a stage reads (on the device or on the host) has been stored by a kernel or filled on
+// ctx->stream by that same stage in that same call: "cleared before" / "filled before" below is a mail_fill in the stage's host code, "k_x:" a
+// plain store that the kernel makes on every launch.  dk_dbg_mail_fill therefore fills the whole struct, both twins, with any byte between two
+// calls, and tests/test_gpu_poison_stages.py and tests/test_gpu_call_sequences.py run every stage behind such a fill (0x00, 0xA5, 0xFF).
 #pragma once
 #include <cstdint>
 
@@ -71,7 +75,7 @@ struct Mail {
     uint32_t deep_seen;
 
     // ---- inverse BWT --------------------------------------------------------------------------------------------------------------------------
-    uint32_t ibwt_pending;        // k_ibwt_jump's last step (cleared before it): chains still unresolved, i.e. a cycle
+    uint32_t ibwt_pending;        // k_ibwt_jump's last step (cleared before it; the earlier steps' stores are wiped by that fill): chains still unresolved, i.e. a cycle
     uint32_t ibwt_bad;            // k_ibwt_emit / k_ibwt_copy (cleared before): the walk did not cover the text once
 
     // ---- DC stage -----------------------------------------------------------------------------------------------------------------------------
@@ -80,10 +84,11 @@ struct Mail {
 
     // ---- packed paths (many small blocks in one pass) -----------------------------------------------------------------------------------------
     struct Packed {
-        uint32_t live;            // k_pk_codes: symbols in use; then k_pk_spine, once per round: suffixes still live
+        uint32_t live;            // k_pk_codes: symbols in use; then k_pk_spine, once per round: suffixes still live (plain stores, read back behind each)
         uint32_t dc_runs;         // host only: landing area of the pack's run count (d_rb[count], workspace)
         uint32_t ibwt_bad;        // k_pib_check, then k_pib_copy / k_pib_emit (filled with 0xFF before the first): lowest corrupt block, IB_END: none
-        uint32_t ibwt_pending;    // device only: k_ibwt_jump's counter in the packed inverse (k_pib_check decides instead; nobody reads it)
+        uint32_t ibwt_pending;    // device only: k_ibwt_jump's counter in the packed inverse and the FM structure builds (k_pib_check decides instead;
+                                  // never cleared, and nobody reads it)
     } packed;
 
     // ---- LCP arrays (lcp.hip; lcp_device clears the group before its first kernel and reads it back as one, once per pass over the lists) -------

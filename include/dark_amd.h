@@ -68,8 +68,8 @@ int dk_ctx_create(int hip_device, size_t max_n, dk_ctx **out);
  * dk_dev_packed_decode, dk_raw_block_decode, dk_dc_decode, and dk_capacity, dk_last_error, dk_last_consumed, statistics and profiling -- with
  * the results and return codes of a full context, DK_MODEL_ANYBYTE included.
  * Refused: every entry point that sorts suffixes, builds a BWT, an LCP array or DC arrays or encodes (host, dk_dev_, batch and packed forms), and the
- * dk_dbg_ entries that take the workspace: DK_E_ARG, dk_last_error names the entry, nothing is allocated, launched or copied, and the
- * context stays usable. */
+ * dk_dbg_ entries that run the sort layer (dk_dbg_mail_fill and dk_dbg_ws_peek are served): DK_E_ARG, dk_last_error names the entry, nothing
+ * is allocated, launched or copied, and the context stays usable. */
 int dk_ctx_create_decoder(int hip_device, size_t max_n, size_t max_blocks, dk_ctx **out);
 /* DK_CTX_FULL or DK_CTX_DECODER (DK_E_ARG for a null context) */
 int dk_ctx_purpose(const dk_ctx *ctx);
@@ -510,6 +510,16 @@ int dk_dbg_dev_sort_groups(dk_ctx *ctx, const uint64_t *d_kin, const uint32_t *d
  * 31 set stands for d_sa[p] & 0x7FFFFFFF and its value is d_marked_val[p] instead of p.  The two n-u64 scratch arrays come from the context's
  * workspace: DK_E_NOMEM when they do not fit.  What it does with an input that is no permutation is not defined beyond "no store outside d_rank". */
 int dk_dbg_dev_inverse_permutation(dk_ctx *ctx, const uint32_t *d_sa, size_t n, uint32_t *d_rank, const uint32_t *d_marked_val);
+/* The two instruments of tests/test_gpu_poison_stages.py and tests/test_gpu_call_sequences.py; both are served by a decoder context as well (any_ctx) and
+ * return DK_E_ARG for a null context or while a streaming batch is open.
+ * dk_dbg_mail_fill: every word of the stages' mailbox (csrc/mailbox.hpp), the device page and its pinned host twin, set to `byte` (0 .. 255) on the
+ * context's stream, which is synchronised.  Between complete API calls only.  A stage that reads a word it has not cleared or written in its
+ * own call then reads `byte` instead of what the call before it happened to leave (zeros on a fresh context). */
+int dk_dbg_mail_fill(dk_ctx *any_ctx, int byte);
+/* dk_dbg_ws_peek: nbytes (> 0; DK_E_NOMEM beyond the workspace) allocated from the workspace the way a stage allocates them, copied to host_out
+ * before anything has written them, released.  In the tuning build under DK_POISON=<b> every byte comes back as b, whatever nbytes is and whatever
+ * the call before left there: the proof that a poisoned run is poisoned.  In any other build the bytes are whatever the workspace holds. */
+int dk_dbg_ws_peek(dk_ctx *any_ctx, size_t nbytes, uint8_t *host_out);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,7 @@ SO_PATH = os.environ.get("DARK_AMD_LIB") or os.path.join(HERE, "libdark_amd.so")
 DK_OK = 0
 DK_E_ARG, DK_E_NOMEM, DK_E_HIP, DK_E_CAPACITY, DK_E_MODEL, DK_E_STREAM, DK_E_INTERNAL, DK_E_NODEVICE = -1, -2, -3, -4, -5, -6, -7, -8
 FM_NO_HIT = 0xFFFFFFFF  # DK_FM_NO_HIT: a position dk_dev_fm_locate* did not fill
+FM_FIND_MAX_PAIRS = 1 << 24  # DK_FM_FIND_MAX_PAIRS: most (pattern, block) pairs of one dk_dev_fm_find* call
 ERROR_NAMES = {-1: "DK_E_ARG", -2: "DK_E_NOMEM", -3: "DK_E_HIP", -4: "DK_E_CAPACITY", -5: "DK_E_MODEL",
                -6: "DK_E_STREAM", -7: "DK_E_INTERNAL", -8: "DK_E_NODEVICE"}
 MODEL_IDS = {"dark": 0, "exp": 1, "ybs": 2, "simple": 3, "rawdc": 4}
@@ -19,6 +20,11 @@ DK_FLAG_HAS_FF, DK_FLAG_SINGLE_SYMBOL = 1, 2
 DK_PACKED_MAX_BLOCKS, DK_PACKED_MAX_BLOCK_BYTES = 65536, 1 << 24
 SA_VERDICTS = {0: "ok", 1: "bad_range", 2: "not_permutation", 3: "bad_order"}  # DK_SA_OK ... DK_SA_BAD_ORDER
 PURPOSES = {"full": 0, "decoder": 1}  # DK_CTX_FULL, DK_CTX_DECODER
+
+
+class FmHit(C.Structure):
+    """dk_fm_hit: a record of dk_dev_fm_find* (16 bytes; context.FM_HIT_DTYPE is the same layout for numpy)"""
+    _fields_ = [("pattern", C.c_uint32), ("block", C.c_uint32), ("position", C.c_uint32), ("slot", C.c_uint32)]
 
 
 class Stats(C.Structure):
@@ -101,6 +107,9 @@ SIGNATURES = {
     "dk_dev_fm_extract": (_i, [_vp, _vp, _sz, _vp, _vp, C.c_uint32, _vp, _vp, _sz, _sz, _vp]),
     "dk_dev_fm_extract_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _sz, _vp, _sz, _vp]),
     "dk_fm_extract": (_i, [_vp, _vp, _sz, C.c_uint32, C.c_uint32, _vp, _vp, _sz, _sz, _vp]),
+    "dk_dev_fm_find": (_i, [_vp, _vp, _sz, _vp, _vp, C.c_uint32, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "dk_dev_fm_find_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, C.c_uint32, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "dk_fm_find": (_i, [_vp, _vp, _sz, C.c_uint32, C.c_uint32, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
     "dk_dbg_dev_fm_rank": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
     "dk_dev_dc_encode_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _szp]),
     "dk_batch_push_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),

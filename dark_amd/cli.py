@@ -24,6 +24,12 @@ Extensions beyond the reference (whole file = one block, read into memory, one t
              block with 0xFF is written as [u32 n | 0x80000000][u32 first position of 0xFF in the BWT][stream]: the stream is still the
              reference's, the four bytes in front are what its header leaves out.  Decoding needs no option: bit 31 of a record's n says
              which kind it is.  The reference cannot read a record with bit 31 set.
+  --grep TEXT / --grep-hex HEX (repeatable) FILE.dark
+             search the archive instead of decoding it (dark_amd/search.py): the records are decoded as far as their BWT, a
+             pack at a time is indexed on the GPU and every pattern is looked for in every block; no block is inverted, no file is written.
+             One line per hit in file order, absolute_offset:pattern_index:enclosing line (--context-bytes, default 80, on either side, cut
+             at the nearest newlines); --count-only: pattern_index:count per pattern; --max-hits bounds the hits listed per pack.  Exit status
+             0 with hits, 1 without.  A match that straddles two blocks is NOT found.
 """
 import argparse
 import os
@@ -652,6 +658,45 @@ def _worker_decode(args):
                                 args.host_threads or 1)
 
 
+# ---- search (--grep / --grep-hex: dark_amd/search.py) -----------------------------------------------------------------
+def _escape(data):
+    """bytes outside 0x20 .. 0x7E as \\xNN"""
+    return "".join(chr(c) if 0x20 <= c <= 0x7E else "\\x%02x" % c for c in data)
+
+
+def enclosing_line(window, at, length):
+    """of a window of text around a hit (at: the hit's offset in it, length: the pattern's), the part between the nearest newlines on either side"""
+    left = window.rfind(b"\n", 0, at) + 1
+    right = window.find(b"\n", at + length)
+    return window[left:right if right >= 0 else len(window)]
+
+
+def grep_file(path, model, patterns, device=0, context_bytes=80, count_only=False, max_hits=None, host_threads=0, stats=None, out=None):
+    """search FILE.dark pack by pack without inverting a block; prints `absolute_offset:pattern_index:enclosing line` per hit in file order (or
+    `pattern_index:count` per pattern) and returns the number of occurrences.  A match that straddles two blocks is not found."""
+    from . import search
+    out = out or sys.stdout
+    max_hits = search.DEFAULT_MAX_HITS if max_hits is None else max_hits
+    counts = np.zeros(len(patterns), dtype=np.int64)
+    lines, listed = [], 0
+    for hits, occ, _ in search.search_archive(path, model, patterns, device, context_bytes, context_bytes, max_hits, host_threads,
+                                              count_only=count_only, stats=stats):
+        counts += occ.astype(np.int64).sum(axis=1)
+        listed += len(hits)
+        for _, start, q, pos, text in hits:
+            at = min(pos, context_bytes)
+            lines.append((start + pos, q, enclosing_line(text, at, len(patterns[q]))))
+    if count_only:
+        for q, c in enumerate(counts):
+            print("%d:%d" % (q, c), file=out)
+    else:
+        for where, q, text in sorted(lines):  # file order: the device lists a segment's hits in the order (pattern, block, suffix-array slot)
+            print("%d:%d:%s" % (where, q, _escape(text)), file=out)
+        if listed < int(counts.sum()):
+            _note("max_hits", "%d of %d hits listed: at most --max-hits %d per segment of the archive" % (listed, int(counts.sum()), max_hits))
+    return int(counts.sum())
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="dark_amd.cli", description="Dark compressor usage: [options] input_file[.dark]")
     ap.add_argument("-m", "--model", default="exp", help="dark|exp|ybs|simple|bbb|raw|rawdc (default exp, like the reference; raw and rawdc are dump-only; bbb: DESIGN.md section 7)")
@@ -667,6 +712,17 @@ def main(argv=None):
     ap.add_argument("--packed", action="store_true", help="with -b (at most 16 MiB, one GPU): consecutive blocks share one segmented GPU pass "
                     "per 64 MiB pack; the archive is byte-identical to the one without.  On decode (one GPU): records of at most 16 MiB are "
                     "inverted in packs the same way; the output is byte-identical")
+    ap.add_argument("--grep", action="append", default=[], metavar="TEXT", help="search FILE.dark for TEXT instead of decoding it (repeatable; one GPU; "
+                    "-m as for decoding): the blocks are decoded as far as their BWT and searched there on the GPU, none is inverted and no file is "
+                    "written.  Prints absolute_offset:pattern_index:enclosing line per hit in file order; exit status 0 with hits, 1 without.  A "
+                    "match that straddles two blocks is NOT found")
+    ap.add_argument("--grep-hex", action="append", default=[], metavar="HEX", help="the same for a pattern given as hexadecimal bytes (repeatable; "
+                    "pattern indices count the --grep patterns first)")
+    ap.add_argument("--context-bytes", type=int, default=80, help="--grep: the enclosing line is cut from this many bytes on either side of a hit, "
+                    "at the nearest newlines within them (default 80)")
+    ap.add_argument("--count-only", action="store_true", help="--grep: print pattern_index:count per pattern only")
+    ap.add_argument("--max-hits", type=int, default=None, help="--grep: list at most this many hits per segment of the archive (a pack of up to "
+                    "64 MiB; default 65536); counts are always complete")
     ap.add_argument("--worker", default="", help=argparse.SUPPRESS)
     ap.add_argument("--part", default="", help=argparse.SUPPRESS)
     ap.add_argument("file")
@@ -675,6 +731,30 @@ def main(argv=None):
     if args.worker:
         return _worker_decode(args) if decode else _worker_encode(args)
     t0 = time.perf_counter()
+    if args.grep or args.grep_hex:
+        if not decode:
+            ap.error("--grep searches a .%s archive" % EXTENSION)
+        if args.gpus > 1:
+            ap.error("--grep: one GPU")
+        if args.context_bytes < 0 or (args.max_hits is not None and not 0 <= args.max_hits <= 1 << 31):
+            ap.error("--context-bytes and --max-hits: not negative, --max-hits at most 2^31")
+        patterns = [t.encode("utf-8", "surrogateescape") for t in args.grep]
+        for h in args.grep_hex:
+            try:
+                patterns.append(bytes.fromhex(h))
+            except ValueError:
+                ap.error("--grep-hex %r: not hexadecimal bytes" % h)
+        if any(len(p) == 0 for p in patterns):
+            ap.error("--grep: an empty pattern")
+        st = {}
+        found = grep_file(args.file, args.model, patterns, args.device, args.context_bytes, args.count_only, args.max_hits, args.host_threads, st)
+        if args.stats:
+            import json
+            import resource
+            print(json.dumps({"seconds": round(time.perf_counter() - t0, 3), "input_bytes": os.path.getsize(args.file), "hits": found,
+                              "resident_bytes": st.get("resident_bytes", 0),
+                              "peak_rss_bytes": resource.getrusage(resource.RUSAGE_SELF).ru_maxrss * 1024}), file=sys.stderr)
+        return 0 if found else 1
     if decode:
         out = decode_file(args.file, args.model, args.device, args.gpus, args.host_threads, args.devices, args.packed)
     else:
@@ -693,4 +773,4 @@ def main(argv=None):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1:])
+    sys.exit(main(sys.argv[1:]))  # (None from the coding directions: status 0; --grep: 0 with hits, 1 without)

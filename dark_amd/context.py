@@ -98,6 +98,10 @@ def fm_extract_bytes(total, count=1, step=32):
     return int(_lib.load().dk_fm_extract_bytes(int(total), int(count), int(step)))
 
 
+# dk_fm_hit: a record of dk_dev_fm_find* (16 bytes)
+FM_HIT_DTYPE = np.dtype([("pattern", np.uint32), ("block", np.uint32), ("position", np.uint32), ("slot", np.uint32)])
+
+
 class Context:
     def __init__(self, max_n, device=0, purpose="full", max_blocks=1):
         """purpose="decoder": a context for the inverse path only (dk_ctx_create_decoder), about a fifth of the workspace; max_blocks = most
@@ -537,6 +541,45 @@ class Context:
         self._ck(self._lib.dk_fm_extract(self._h, _ptr(b), len(b), int(origin), int(step), _ptr(pos), None if lens is None else _ptr(lens), nrange,
                                          int(max_len), _ptr(out)))
         return out
+
+    # ---- FM-index find: every pattern in every block, as a compact list of hit records; decoder contexts too ----
+    def dev_fm_find(self, d_bwt, n, d_index, d_loc, step, d_pat, pat_lens, max_hits, d_hits, d_occ=None):
+        """every pattern in d_bwt[0, n): d_occ[q] (a uint32 device tensor, or None) = its occurrences, the return value their sum; d_hits (a
+        16-byte aligned device tensor of max_hits records of four uint32 words: pattern, block, position, slot) receives the first
+        min(sum, max_hits) hits in the order (pattern, slot).  max_hits == 0: d_hits and d_loc may be None"""
+        _inputs_ready(d_bwt, d_index, d_pat)
+        npat = len(pat_lens)
+        lens = (C.c_size_t * max(npat, 1))(*[int(m) for m in pat_lens])
+        total = C.c_uint64(0)
+        self._ck(self._lib.dk_dev_fm_find(self._h, _ptr(d_bwt), n, _ptr(d_index), None if d_loc is None else _ptr(d_loc), int(step), _ptr(d_pat),
+                                          npat, lens, int(max_hits), None if d_hits is None else _ptr(d_hits),
+                                          None if d_occ is None else _ptr(d_occ), C.byref(total)))
+        return int(total.value)
+
+    def dev_fm_find_packed(self, d_bwt, sizes, d_index, d_loc, step, d_pat, pat_lens, max_hits, d_hits, d_occ=None):
+        """dev_fm_find over a pack: every pattern in every block.  d_occ[q * len(sizes) + b] = occurrences of pattern q in block b; the hits in
+        the order (pattern, block, slot), positions and slots local to their block"""
+        _inputs_ready(d_bwt, d_index, d_pat)
+        count, npat = len(sizes), len(pat_lens)
+        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
+        lens = (C.c_size_t * max(npat, 1))(*[int(m) for m in pat_lens])
+        total = C.c_uint64(0)
+        self._ck(self._lib.dk_dev_fm_find_packed(self._h, _ptr(d_bwt), count, ns, _ptr(d_index), None if d_loc is None else _ptr(d_loc), int(step),
+                                                 _ptr(d_pat), npat, lens, int(max_hits), None if d_hits is None else _ptr(d_hits),
+                                                 None if d_occ is None else _ptr(d_occ), C.byref(total)))
+        return int(total.value)
+
+    def fm_find(self, bwt, origin, patterns, max_hits=65536, step=32):
+        """(occ, hits, total) from (L, origin) in host memory: occ a uint32 array per pattern, hits a structured array (FM_HIT_DTYPE) of the
+        first min(total, max_hits) hits in the order (pattern, slot), total their number in all (dk_fm_find)"""
+        b = as_u8(bwt)
+        pat, lens, npat = _pack_patterns(patterns)
+        occ = np.zeros(npat, dtype=np.uint32)
+        hits = np.zeros(max(int(max_hits), 1), dtype=FM_HIT_DTYPE)
+        total = C.c_uint64(0)
+        self._ck(self._lib.dk_fm_find(self._h, _ptr(b), len(b), int(origin), int(step), _ptr(pat), npat, lens, int(max_hits), _ptr(hits), _ptr(occ),
+                                      C.byref(total)))
+        return occ, hits[:min(int(total.value), int(max_hits))], int(total.value)
 
     def dbg_dev_fm_rank(self, d_bwt, total, d_index, d_pos, d_sym, d_out):
         """d_out[q] = occurrences of d_sym[q] in d_bwt[0, d_pos[q]) by the count kernel's rank (uint32 / uint8 / uint32 device tensors)"""

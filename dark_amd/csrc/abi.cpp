@@ -114,6 +114,8 @@ size_t decoder_workspace_bytes(size_t max_n, size_t max_blocks) {
     // The locate structure's build (bwt.hip: fm_locate_build_device) is the packed inverse above without its records, for one block too, so it
     // fits whatever fits `packed`; dk_fm_locate refuses what does not fit (tests/test_gpu_fm_locate.py checks peak <= size on both purposes).
     // The extract structure's build (fm_extract_build_device) is that front part and 4 bytes per block more, far below the records left out.
+    // Find (fm_find_device) takes 16 bytes per (pattern, block) pair and 2 KiB: the caller's choice, not the block's, so this size does not grow
+    // for it and dk_dev_fm_find* refuse a grid that does not fit (tests/test_gpu_fm_find.py checks peak <= size on both purposes).
     // tests/test_gpu_decoder_ctx.py checks peak <= size on contexts sized exactly to their block or pack, through every entry above.
     const size_t single = 2 * ((max_n + 255) & ~size_t(255)) + bwt_inverse_workspace(max_n);
     const size_t packed = ((max_n + 255) & ~size_t(255)) + packed_ibwt_workspace(max_n, max_blocks);
@@ -1791,6 +1793,159 @@ int dk_fm_extract(dk_ctx *ctx, const uint8_t *bwt, size_t n, uint32_t origin, ui
     DK_TRY(fm_extract_build_device(ctx, d_bwt, {0u, static_cast<uint32_t>(n)}, &origin, step, d_ext, false));
     DK_TRY(fm_extract_device(ctx, d_bwt, d_off, nullptr, 1, n, d_index, d_ext, step, d_pos, len ? d_len : nullptr, nullptr, nrange, max_len, d_out));
     DK_HIP(ctx, hipMemcpyAsync(out, d_out, nbytes, hipMemcpyDeviceToHost, st));
+    DK_HIP(ctx, hipStreamSynchronize(st));
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+// ---- find: every pattern in every block, as a compact list of hit records and the occurrence matrix ------------------
+}  // extern "C"
+
+namespace {
+// the checks the three entries share, in front of anything that touches the device
+int fm_find_args(dk_ctx *ctx, size_t npat, size_t count, size_t max_hits, const void *d_loc, uint32_t step, const void *hits, const uint64_t *total) {
+    if (!total) return ctx->fail(DK_E_ARG, "null pointer");
+    if (!fm_good_step(step)) return ctx->fail(DK_E_ARG, "the sampling step %u is no power of two in [1, 4096]", step);
+    if (max_hits > (size_t(1) << 31)) return ctx->fail(DK_E_ARG, "at most 2^31 hit records in one call, not %zu", max_hits);
+    if (npat > DK_FM_FIND_MAX_PAIRS || npat * count > DK_FM_FIND_MAX_PAIRS)
+        return ctx->fail(DK_E_ARG, "%zu patterns in %zu blocks: more than DK_FM_FIND_MAX_PAIRS pairs", npat, count);
+    if (max_hits) {
+        if (!hits) return ctx->fail(DK_E_ARG, "null pointer");
+        if (reinterpret_cast<uintptr_t>(hits) & 15) return ctx->fail(DK_E_ARG, "the hit records are not 16-byte aligned");
+        if (d_loc && !fm_good_index(d_loc)) return ctx->fail(DK_E_ARG, "the locate structure is not 4-byte aligned");
+    }
+    return DK_OK;
+}
+// the pattern offsets to the workspace, then the stage.  d_off: the blocks' offsets on the device (count + 1 words, enqueued by the caller).
+int fm_find_run(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total_bytes, const void *d_index, const void *d_loc,
+                uint32_t step, const uint8_t *d_pat, const Patterns &p, size_t max_hits, dk_fm_hit *d_hits, uint32_t *d_occ, uint64_t *total) {
+    const size_t npat = p.off.size() - 1;
+    uint32_t *d_pat_off = ctx->ws_alloc<uint32_t>(npat + 1);
+    if (!d_pat_off) return DK_E_NOMEM;
+    int rc = ctx->hip_ok(hipMemcpyAsync(d_pat_off, p.off.data(), (npat + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream), "pattern offsets");
+    if (rc == DK_OK)
+        rc = fm_find_device(ctx, d_bwt, d_off, count, total_bytes, d_index, d_loc, step, d_pat, d_pat_off, npat, p.bytes(), max_hits, d_hits, d_occ, total);
+    const hipError_t e = hipStreamSynchronize(ctx->stream);  // (also on failure: the copy above reads `p`)
+    DK_TRY(rc);
+    DK_HIP(ctx, e);
+    return DK_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int dk_dev_fm_find_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const void *d_index, const void *d_loc, uint32_t step,
+                          const uint8_t *d_pat, size_t npat, const size_t *pat_len, size_t max_hits, dk_fm_hit *d_hits, uint32_t *d_occ, uint64_t *total) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!d_bwt || !n || !d_index || (max_hits && !d_loc)) return ctx->fail(DK_E_ARG, "null pointer");
+    if (!fm_good_index(d_index)) return ctx->fail(DK_E_ARG, "the index is not 4-byte aligned");
+    std::vector<uint32_t> off;
+    DK_TRY(check_pack(ctx, count, n, off));
+    DK_TRY(fm_find_args(ctx, npat, count, max_hits, d_loc, step, d_hits, total));
+    if (d_occ && (reinterpret_cast<uintptr_t>(d_occ) & 3)) return ctx->fail(DK_E_ARG, "the occurrence matrix is not 4-byte aligned");
+    if (npat == 0) {
+        *total = 0;
+        return DK_OK;
+    }
+    Timer t;
+    Patterns p;
+    DK_TRY(check_patterns(ctx, npat, pat_len, nullptr, count, p));
+    if (!d_pat && p.bytes()) return ctx->fail(DK_E_ARG, "null pointer");
+    if (ws_round(4 * (count + 1)) + ws_round(4 * (npat + 1)) + fm_find_workspace(npat * count) > ctx->ws_size)
+        return ctx->fail(DK_E_ARG, "%zu patterns in %zu blocks do not fit the workspace (16 bytes per pair)", npat, count);
+    hipStream_t st = ctx->stream;
+    uint32_t *d_off = ctx->ws_alloc<uint32_t>(count + 1);
+    if (!d_off) return DK_E_NOMEM;
+    DK_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    const int rc = fm_find_run(ctx, d_bwt, d_off, count, off.back(), d_index, d_loc, step, d_pat, p, max_hits, d_hits, d_occ, total);
+    const hipError_t e = hipStreamSynchronize(st);  // (also on failure: the copy above reads `off`)
+    DK_TRY(rc);
+    DK_HIP(ctx, e);
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_dev_fm_find(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, const void *d_index, const void *d_loc, uint32_t step, const uint8_t *d_pat, size_t npat,
+                   const size_t *pat_len, size_t max_hits, dk_fm_hit *d_hits, uint32_t *d_occ, uint64_t *total) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!d_bwt || !d_index || (max_hits && !d_loc)) return ctx->fail(DK_E_ARG, "null pointer");
+    if (!fm_good_index(d_index)) return ctx->fail(DK_E_ARG, "the index is not 4-byte aligned");
+    DK_TRY(check_n(ctx, n));
+    DK_TRY(fm_find_args(ctx, npat, 1, max_hits, d_loc, step, d_hits, total));
+    if (d_occ && (reinterpret_cast<uintptr_t>(d_occ) & 3)) return ctx->fail(DK_E_ARG, "the occurrence matrix is not 4-byte aligned");
+    if (npat == 0) {
+        *total = 0;
+        return DK_OK;
+    }
+    Timer t;
+    Patterns p;
+    DK_TRY(check_patterns(ctx, npat, pat_len, nullptr, 1, p));
+    if (!d_pat && p.bytes()) return ctx->fail(DK_E_ARG, "null pointer");
+    if (256 + ws_round(4 * (npat + 1)) + fm_find_workspace(npat) > ctx->ws_size)
+        return ctx->fail(DK_E_ARG, "%zu patterns do not fit the workspace (16 bytes per pair)", npat);
+    uint32_t *d_off = nullptr;
+    DK_TRY(single_offsets(ctx, n, &d_off));
+    DK_TRY(fm_find_run(ctx, d_bwt, d_off, 1, n, d_index, d_loc, step, d_pat, p, max_hits, d_hits, d_occ, total));
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_fm_find(dk_ctx *ctx, const uint8_t *bwt, size_t n, uint32_t origin, uint32_t step, const uint8_t *pat, size_t npat, const size_t *pat_len,
+               size_t max_hits, dk_fm_hit *hits, uint32_t *occ, uint64_t *total) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!bwt) return ctx->fail(DK_E_ARG, "null pointer");
+    DK_TRY(check_n(ctx, n));
+    if (origin >= n) return ctx->fail(DK_E_ARG, "origin %u is outside the block of %zu bytes", origin, n);
+    if (!total) return ctx->fail(DK_E_ARG, "null pointer");
+    if (!fm_good_step(step)) return ctx->fail(DK_E_ARG, "the sampling step %u is no power of two in [1, 4096]", step);
+    if (max_hits > (size_t(1) << 31)) return ctx->fail(DK_E_ARG, "at most 2^31 hit records in one call, not %zu", max_hits);
+    if (npat > DK_FM_FIND_MAX_PAIRS) return ctx->fail(DK_E_ARG, "%zu patterns: more than DK_FM_FIND_MAX_PAIRS pairs", npat);
+    if (max_hits && !hits) return ctx->fail(DK_E_ARG, "null pointer");
+    if (npat == 0) {
+        *total = 0;
+        return DK_OK;
+    }
+    Timer t;
+    Patterns p;
+    DK_TRY(check_patterns(ctx, npat, pat_len, nullptr, 1, p));
+    if (!pat && p.bytes()) return ctx->fail(DK_E_ARG, "null pointer");
+    // L, the index, the structure (only where records are asked for) and the block's two offsets; the patterns, their offsets and the occurrence
+    // words; the larger of the builds' and the stage's workspaces.  The records come last, once their number is known.
+    const size_t index_words = fm_index_words(n, 1), loc_words = max_hits ? fm_locate_words(n, 1, step) : 0;
+    const size_t fixed = ws_round(n) + ws_round(4 * index_words) + ws_round(4 * loc_words) + 256 + ws_round(p.bytes()) + ws_round(4 * (npat + 1)) +
+                         ws_round(4 * npat);
+    const size_t need = fixed + std::max(fm_find_workspace(npat), std::max(fm_build_workspace(n, 1), max_hits ? fm_locate_build_workspace(n, 1) : 0));
+    if (need > ctx->ws_size)
+        return ctx->fail(DK_E_ARG, "%zu patterns of %zu bytes do not fit the workspace beside L, its index and the locate build", npat, p.bytes());
+    hipStream_t st = ctx->stream;
+    uint8_t *d_bwt = ctx->ws_alloc<uint8_t>(n), *d_pat = ctx->ws_alloc<uint8_t>(std::max<size_t>(p.bytes(), 1));
+    uint32_t *d_index = ctx->ws_alloc<uint32_t>(index_words), *d_loc = max_hits ? ctx->ws_alloc<uint32_t>(loc_words) : nullptr;
+    uint32_t *d_occ = ctx->ws_alloc<uint32_t>(npat), *d_pat_off = ctx->ws_alloc<uint32_t>(npat + 1), *d_off = nullptr;
+    if (!d_bwt || !d_pat || !d_index || (max_hits && !d_loc) || !d_occ || !d_pat_off) return DK_E_NOMEM;
+    DK_TRY(single_offsets(ctx, n, &d_off));
+    DK_HIP(ctx, hipMemcpyAsync(d_bwt, bwt, n, hipMemcpyHostToDevice, st));
+    if (p.bytes()) DK_HIP(ctx, hipMemcpyAsync(d_pat, pat, p.bytes(), hipMemcpyHostToDevice, st));
+    DK_TRY(fm_build_device(ctx, d_bwt, {0u, static_cast<uint32_t>(n)}, &origin, d_index));
+    if (max_hits) DK_TRY(fm_locate_build_device(ctx, d_bwt, {0u, static_cast<uint32_t>(n)}, &origin, step, d_loc, false));
+    // the count and the scan alone first: how many records there are decides what the records take
+    int rc = ctx->hip_ok(hipMemcpyAsync(d_pat_off, p.off.data(), (npat + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st), "pattern offsets");
+    if (rc == DK_OK) rc = fm_find_device(ctx, d_bwt, d_off, 1, n, d_index, nullptr, step, d_pat, d_pat_off, npat, p.bytes(), 0, nullptr, d_occ, total);
+    const hipError_t e = hipStreamSynchronize(st);  // (also on failure: the copy above reads `p`)
+    DK_TRY(rc);
+    DK_HIP(ctx, e);
+    const size_t nhits = static_cast<size_t>(std::min<uint64_t>(*total, max_hits));
+    if (nhits) {
+        if (ctx->ws_used + ws_round(16 * nhits) + fm_find_workspace(npat) > ctx->ws_size)
+            return ctx->fail(DK_E_ARG, "%zu hit records do not fit the workspace beside L, its index and the patterns", nhits);
+        dk_fm_hit *d_hits = ctx->ws_alloc<dk_fm_hit>(nhits);
+        if (!d_hits) return DK_E_NOMEM;
+        DK_TRY(fm_find_device(ctx, d_bwt, d_off, 1, n, d_index, d_loc, step, d_pat, d_pat_off, npat, p.bytes(), nhits, d_hits, nullptr, total));
+        DK_HIP(ctx, hipMemcpyAsync(hits, d_hits, nhits * sizeof(dk_fm_hit), hipMemcpyDeviceToHost, st));
+    }
+    if (occ) DK_HIP(ctx, hipMemcpyAsync(occ, d_occ, npat * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     DK_HIP(ctx, hipStreamSynchronize(st));
     ctx->stats.ms_total = t.ms();
     return DK_OK;

@@ -49,7 +49,7 @@ enum KernelSlot : int {
     K_RADIX_SCATTER_TEXT,  // k_radix_scatter<false, true>: first pass, keys built from the text (13 B per pair)
     K_ISA_PARTITION,       // k_isa_init + k_isa_split<true> + k_isa_split<false> (inverse permutation through LDS windows)
     K_ISA_ASSEMBLE,        // k_isa_assemble
-    K_CHAIN,               // k_chain_extract + _ends + _tiles + _spine + _verdicts + _apply (pair chains; their sort is in the radix slots); k_sa_search*, k_fm_count, k_fm_locate, k_fm_extract
+    K_CHAIN,               // k_chain_extract + _ends + _tiles + _spine + _verdicts + _apply (pair chains; their sort is in the radix slots); k_sa_search*, k_fm_count, k_fm_locate, k_fm_extract, k_fm_find_*
     K_PERIOD,              // k_period_first + _spine + _fill (next break of the block's dominant period, for the period round)
     K_SLOT_COUNT
 };
@@ -290,6 +290,14 @@ size_t fm_locate_build_workspace(size_t total, size_t count);  // an upper bound
 // d_pos[q * max_hits + j] = SA_b[lo + j], DK_FM_NO_HIT behind the range.  Enqueues only; takes no workspace.
 int fm_locate_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, const void *d_index, const void *d_loc,
                      uint32_t step, const uint32_t *d_lo, const uint32_t *d_hi, const uint32_t *d_pat_blk, size_t npat, size_t max_hits, uint32_t *d_pos);
+// fm_index.hip: every pattern (d_pat / d_pat_off as for fm_count_device, no blocks) in every block.  Pair p = q * count + b:
+// d_occ[p] (may be null) = its occurrences; *total_out (host) = their sum; d_hits (16-byte aligned records {pattern, block, position, slot}) = the
+// first min(total, max_hits) hits in the order (q, b, slot), position as fm_locate_device gives it.  max_hits == 0: d_hits and d_loc are not looked
+// at.  Takes fm_find_workspace(npat * count) bytes (16 per pair and the chunk sums, every ws_alloc rounded up) and releases them.  Synchronises.
+size_t fm_find_workspace(size_t npairs);
+int fm_find_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, const void *d_index, const void *d_loc,
+                   uint32_t step, const uint8_t *d_pat, const uint32_t *d_pat_off, size_t npat, size_t pat_bytes, size_t max_hits, void *d_hits,
+                   uint32_t *d_occ, uint64_t *total_out);
 // The extract structure of a packed L (bwt.hip builds it, fm_index.hip reads it): 32-bit words, over the whole pack.
 //   [0, 64) header: magic, total, count, step, anchors | total / step + count anchors
 // Block b's anchors are the ceil(n_b / step) words from its anchor base, the sum of ceil(n_i / step) over the blocks in front of it: anchor k =

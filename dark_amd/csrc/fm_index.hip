@@ -32,6 +32,9 @@
 //                          suffix array it reads is built in bwt.hip by the inverse's kernels: fm_locate_build_device)
 // EXTRACT  k_fm_extract    a wave per (range, chunk of `step` positions): from the chunk's end, whose slot is an anchor, at most min(step, n_b) - 1
 //                          of the same LF steps backwards, a text byte per step (section 4.15; anchors built in bwt.hip: fm_extract_build_device)
+// FIND     k_fm_find_count a wave per pair (pattern, block) of the grid npat x count: the count's search, lo and occ of the pair (section 4.16)
+//          k_fm_find_scan_a/b/c  the exclusive scan of occ over the pairs in 64-bit sums, the grand total to the mailbox
+//          k_fm_find_locate a wave per hit: the pair from the offsets by a 64-ary search, then the walk of k_fm_locate; one 16-byte record
 // Containment: the geometry (off, n, total) comes from the caller, never from the index; every position is clamped to [0, n_b] before it is used
 // and a rank reads L only below the position it counts to.  With an index or an L that is not what the build made the results are unspecified
 // but <= n_b, and nothing outside L, the index, the patterns and the two results is touched.
@@ -213,6 +216,31 @@ struct FmArgs {
     const uint8_t *L; const uint32_t *off, *blocks, *base, *cp; const uint8_t *pat; const uint32_t *pat_off, *pat_blk; uint32_t npat, total, count;
     uint32_t *out_lo, *out_hi;
 };
+// The backward search of the pattern p[0, m) in block b = L[s, s + nb), by the whole wave: lo / hi as the header derives them, clamped to
+// [0, nb] behind every step.  Shared by k_fm_count and k_fm_find_count.
+__device__ __forceinline__ void fm_search(const uint8_t *__restrict__ L, uint32_t total, const uint32_t *__restrict__ cp, const uint32_t *__restrict__ blocks,
+                                          const uint32_t *__restrict__ base_all, uint32_t b, uint32_t s, uint32_t nb, const uint8_t *__restrict__ p, uint32_t m,
+                                          uint32_t lane, uint32_t &lo_out, uint32_t &hi_out) {
+    const uint32_t origin = blocks[4 * static_cast<size_t>(b) + 2], last = blocks[4 * static_cast<size_t>(b) + 3];
+    const uint32_t *__restrict__ base = base_all + static_cast<size_t>(b) * 256;
+    uint32_t lo = 0, hi = nb;
+    for (uint32_t j = m; j-- > 0;) {
+        const uint32_t c = p[j], is_last = c == last ? 1u : 0u, first = j + 1u == m ? 1u : 0u;
+        const uint32_t bc = base[c];
+        if (lo != hi || first) {
+            uint32_t rl, rh;
+            fm_rank2(L, total, cp, c, s + lo, s + hi, lane, rl, rh);
+            lo = bc + (is_last & ~first) - (is_last & (origin < lo ? 1u : 0u)) + rl;
+            hi = bc + is_last - (is_last & (origin < hi ? 1u : 0u)) + rh;
+        } else {
+            lo = hi = bc + is_last - (is_last & (origin < lo ? 1u : 0u)) + fm_rank1(L, total, cp, c, s + lo, lane);
+        }
+        lo = lo < nb ? lo : nb;
+        hi = hi < nb ? hi : nb;
+    }
+    lo_out = lo;
+    hi_out = hi;
+}
 __global__ __launch_bounds__(64 * FM_WAVES) void k_fm_count(FmArgs a) {
     const uint8_t *__restrict__ L = a.L, *__restrict__ pat = a.pat;
     const uint32_t *__restrict__ off = a.off, *__restrict__ cp = a.cp, *__restrict__ pat_off = a.pat_off, *__restrict__ pat_blk = a.pat_blk;
@@ -221,24 +249,8 @@ __global__ __launch_bounds__(64 * FM_WAVES) void k_fm_count(FmArgs a) {
     for (uint64_t q = static_cast<uint64_t>(blockIdx.x) * FM_WAVES + (threadIdx.x >> 6); q < a.npat; q += nwaves) {
         const uint32_t po = pat_off[q], m = pat_off[q + 1] - po;
         const uint32_t b = pat_blk ? pat_blk[q] : 0u, s = off[b], nb = off[b + 1] - s;  // (b < count: the caller's check)
-        const uint32_t origin = a.blocks[4 * static_cast<size_t>(b) + 2], last = a.blocks[4 * static_cast<size_t>(b) + 3];
-        const uint32_t *__restrict__ base = a.base + static_cast<size_t>(b) * 256;
-        const uint8_t *p = pat + po;
-        uint32_t lo = 0, hi = nb;
-        for (uint32_t j = m; j-- > 0;) {
-            const uint32_t c = p[j], is_last = c == last ? 1u : 0u, first = j + 1u == m ? 1u : 0u;
-            const uint32_t bc = base[c];
-            if (lo != hi || first) {
-                uint32_t rl, rh;
-                fm_rank2(L, total, cp, c, s + lo, s + hi, lane, rl, rh);
-                lo = bc + (is_last & ~first) - (is_last & (origin < lo ? 1u : 0u)) + rl;
-                hi = bc + is_last - (is_last & (origin < hi ? 1u : 0u)) + rh;
-            } else {
-                lo = hi = bc + is_last - (is_last & (origin < lo ? 1u : 0u)) + fm_rank1(L, total, cp, c, s + lo, lane);
-            }
-            lo = lo < nb ? lo : nb;
-            hi = hi < nb ? hi : nb;
-        }
+        uint32_t lo, hi;
+        fm_search(L, total, cp, a.blocks, a.base, b, s, nb, pat + po, m, lane, lo, hi);
         if (lane == 0) {
             a.out_lo[q] = lo;
             a.out_hi[q] = hi;
@@ -286,39 +298,163 @@ struct FmLocArgs {
 // depends on the slot alone -- the row's 16 bytes per lane, which hold c = L[slot] in one lane, and the row's 32 mark words in the lower lanes
 // -- so they are issued together and c is taken from its lane; the checkpoint word, which needs c, is the second and last round trip of a step.
 // Containment: lo, hi are clamped to [0, n_b], every slot to [0, n_b), the sample's index to the samples; at most min(step, n_b) steps.
+// THE WALK ITSELF is fm_locate_walk, shared by k_fm_locate and k_fm_find_locate: from slot x < nb of block b = L[s, s + nb) down to a marked
+// slot, by the whole wave -> the text position of x, or DK_FM_NO_HIT where no mark is met within min(step, nb) steps or the sample lies outside
+// the block.
+struct FmWalk { const uint8_t *L; const uint32_t *blocks, *base, *cp, *marks, *bits, *samples; uint32_t total, step_shift, nsamp; };
+__device__ __forceinline__ uint32_t fm_locate_walk(const FmWalk &w, uint32_t b, uint32_t s, uint32_t nb, uint32_t x, uint32_t lane) {
+    const uint8_t *__restrict__ L = w.L;
+    const uint32_t *__restrict__ cp = w.cp, *__restrict__ bits = w.bits;
+    const uint32_t total = w.total, step = 1u << w.step_shift;
+    const uint32_t origin = w.blocks[4 * static_cast<size_t>(b) + 2], last = w.blocks[4 * static_cast<size_t>(b) + 3];
+    const uint32_t *__restrict__ base = w.base + static_cast<size_t>(b) * 256;
+    const uint32_t bound = step < nb ? step : nb;
+    uint32_t out = 0xFFFFFFFFu;
+    for (uint32_t k = 0; k < bound; ++k) {
+        const uint32_t g = s + x, row = g >> FM_SHIFT, sl = (row << FM_SHIFT) + 16u * lane;
+        const uint32_t mine = lane < 32u ? bits[static_cast<size_t>(row) * 32 + lane] : 0u;
+        uint64_t v0, v1;
+        fm_load16(L, total, sl, fm_lane_bytes(g + 1u, sl), v0, v1);  // (the bytes below g and the one at g, which is below total)
+        const uint32_t word = (g & (FM_BLOCK - 1u)) >> 5, bit = g & 31u;
+        if ((static_cast<uint32_t>(__shfl(mine, word, 64)) >> bit) & 1u) {
+            const uint32_t below = lane < word ? __popc(mine) : (lane == word ? __popc(mine & ((1u << bit) - 1u)) : 0u);
+            uint32_t r = w.marks[row] + wave_sum(below);
+            r = r < w.nsamp ? r : w.nsamp - 1u;
+            const uint64_t p = (static_cast<uint64_t>(w.samples[r]) << w.step_shift) + k;
+            if (p < nb) out = static_cast<uint32_t>(p);
+            break;
+        }
+        x = fm_lf(cp, base, origin, last, nb, x, g, sl, fm_symbol_at(v0, v1, g), v0, v1);
+    }
+    return out;
+}
 __global__ __launch_bounds__(64 * FM_WAVES) void k_fm_locate(FmLocArgs a) {
-    const uint8_t *__restrict__ L = a.L;
-    const uint32_t *__restrict__ off = a.off, *__restrict__ cp = a.cp, *__restrict__ bits = a.bits, *__restrict__ pat_blk = a.pat_blk;
-    const uint32_t lane = threadIdx.x & 63u, total = a.total, step = 1u << a.step_shift;
+    const uint32_t *__restrict__ off = a.off, *__restrict__ pat_blk = a.pat_blk;
+    const uint32_t lane = threadIdx.x & 63u;
+    const FmWalk w{a.L, a.blocks, a.base, a.cp, a.marks, a.bits, a.samples, a.total, a.step_shift, a.nsamp};
     const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * FM_WAVES, nitems = static_cast<uint64_t>(a.npat) * a.max_hits;
     for (uint64_t item = static_cast<uint64_t>(blockIdx.x) * FM_WAVES + (threadIdx.x >> 6); item < nitems; item += nwaves) {
         const uint32_t q = static_cast<uint32_t>(item / a.max_hits), j = static_cast<uint32_t>(item - static_cast<uint64_t>(q) * a.max_hits);
         const uint32_t b = pat_blk ? pat_blk[q] : 0u, s = off[b], nb = off[b + 1] - s;  // (b < count: the caller's check)
         const uint32_t lo = a.lo[q] < nb ? a.lo[q] : nb, hi = a.hi[q] < nb ? a.hi[q] : nb;
         uint32_t out = 0xFFFFFFFFu;
-        if (lo < hi && j < hi - lo) {
-            const uint32_t origin = a.blocks[4 * static_cast<size_t>(b) + 2], last = a.blocks[4 * static_cast<size_t>(b) + 3];
-            const uint32_t *__restrict__ base = a.base + static_cast<size_t>(b) * 256;
-            const uint32_t bound = step < nb ? step : nb;
-            uint32_t x = lo + j;
-            for (uint32_t k = 0; k < bound; ++k) {
-                const uint32_t g = s + x, row = g >> FM_SHIFT, sl = (row << FM_SHIFT) + 16u * lane;
-                const uint32_t mine = lane < 32u ? bits[static_cast<size_t>(row) * 32 + lane] : 0u;
-                uint64_t v0, v1;
-                fm_load16(L, total, sl, fm_lane_bytes(g + 1u, sl), v0, v1);  // (the bytes below g and the one at g, which is below total)
-                const uint32_t word = (g & (FM_BLOCK - 1u)) >> 5, bit = g & 31u;
-                if ((static_cast<uint32_t>(__shfl(mine, word, 64)) >> bit) & 1u) {
-                    const uint32_t below = lane < word ? __popc(mine) : (lane == word ? __popc(mine & ((1u << bit) - 1u)) : 0u);
-                    uint32_t r = a.marks[row] + wave_sum(below);
-                    r = r < a.nsamp ? r : a.nsamp - 1u;
-                    const uint64_t p = (static_cast<uint64_t>(a.samples[r]) << a.step_shift) + k;
-                    if (p < nb) out = static_cast<uint32_t>(p);
-                    break;
-                }
-                x = fm_lf(cp, base, origin, last, nb, x, g, sl, fm_symbol_at(v0, v1, g), v0, v1);
-            }
-        }
+        if (lo < hi && j < hi - lo) out = fm_locate_walk(w, b, s, nb, lo + j, lane);
         if (lane == 0) a.pos[item] = out;
+    }
+}
+
+// ---- find: every pattern in every block, as a compact list of hit records in the order (pattern, block, slot) ----------
+// Pair p = q * count + b.  k_fm_find_count leaves lo[p] and occ[p]; the scan gives offset[p] = the sum of occ below p in 64 bits and the grand
+// total; k_fm_find_locate takes hit h, finds the pair with offset[p] <= h < offset[p + 1] and walks from slot lo[p] + h - offset[p].  No atomics.
+constexpr uint32_t FM_FIND_ROW = 256;  // pairs per row of the scan: one per thread of a workgroup
+
+struct FmFindArgs {
+    const uint8_t *L; const uint32_t *off, *blocks, *base, *cp; const uint8_t *pat; const uint32_t *pat_off; uint32_t npat, total, count;
+    uint32_t *lo, *occ, *out_occ;
+};
+// A wave per pair, grid stride over the pairs in their own order: the waves in flight together hold one pattern and neighbouring blocks
+// (q-major; UNMEASURED against b-major).  occ = hi - lo, 0 where an index that is none gives hi < lo.
+__global__ __launch_bounds__(64 * FM_WAVES) void k_fm_find_count(FmFindArgs a) {
+    const uint8_t *__restrict__ L = a.L, *__restrict__ pat = a.pat;
+    const uint32_t *__restrict__ off = a.off, *__restrict__ cp = a.cp, *__restrict__ pat_off = a.pat_off;
+    const uint32_t lane = threadIdx.x & 63u, total = a.total, count = a.count;
+    const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * FM_WAVES, npairs = static_cast<uint64_t>(a.npat) * count;
+    for (uint64_t p = static_cast<uint64_t>(blockIdx.x) * FM_WAVES + (threadIdx.x >> 6); p < npairs; p += nwaves) {
+        const uint32_t q = static_cast<uint32_t>(p / count), b = static_cast<uint32_t>(p - static_cast<uint64_t>(q) * count);
+        const uint32_t po = pat_off[q], m = pat_off[q + 1] - po, s = off[b], nb = off[b + 1] - s;
+        uint32_t lo, hi;
+        fm_search(L, total, cp, a.blocks, a.base, b, s, nb, pat + po, m, lane, lo, hi);
+        if (lane == 0) {
+            const uint32_t occ = hi > lo ? hi - lo : 0u;
+            a.lo[p] = lo;
+            a.occ[p] = occ;
+            if (a.out_occ) a.out_occ[p] = occ;
+        }
+    }
+}
+// exclusive sum of 64-bit values over the 256 threads of a workgroup; s_tmp: 4 words.  Two __syncthreads().
+__device__ __forceinline__ uint64_t fm_block_excl_sum64(uint64_t v, uint64_t *s_tmp, uint64_t *all_out) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint64_t inc = v;
+#pragma unroll
+    for (uint32_t o = 1; o < 64u; o <<= 1) {
+        const uint32_t l = __shfl_up(static_cast<uint32_t>(inc), o, 64), h = __shfl_up(static_cast<uint32_t>(inc >> 32), o, 64);
+        if (lane >= o) inc += (static_cast<uint64_t>(h) << 32) | l;
+    }
+    if (lane == 63u) s_tmp[wave] = inc;
+    __syncthreads();
+    uint64_t before = 0, all = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; ++k) {
+        const uint64_t t = s_tmp[k];
+        if (k < wave) before += t;
+        all += t;
+    }
+    *all_out = all;
+    __syncthreads();
+    return before + inc - v;
+}
+// the scan of occ over the pairs: chunk g = rows [g rpc, (g + 1) rpc) of FM_FIND_ROW pairs (the shape of k_fm_scan_*, in 64-bit sums)
+__global__ __launch_bounds__(256) void k_fm_find_scan_a(const uint32_t *__restrict__ occ, uint32_t npairs, uint32_t rpc, uint64_t *__restrict__ chunk_sum) {
+    __shared__ uint64_t s_tmp[4];
+    const uint64_t p0 = static_cast<uint64_t>(blockIdx.x) * rpc * FM_FIND_ROW, p1 = p0 + static_cast<uint64_t>(rpc) * FM_FIND_ROW < npairs ? p0 + static_cast<uint64_t>(rpc) * FM_FIND_ROW : npairs;
+    uint64_t sum = 0, all;
+    for (uint64_t p = p0 + threadIdx.x; p < p1; p += FM_FIND_ROW) sum += occ[p];
+    fm_block_excl_sum64(sum, s_tmp, &all);
+    if (threadIdx.x == 0) chunk_sum[blockIdx.x] = all;
+}
+// one workgroup over the at most FM_MAX_CHUNKS sums; the grand total to the mailbox (a plain store on every launch)
+__global__ __launch_bounds__(256) void k_fm_find_scan_b(uint64_t *__restrict__ chunk_sum, uint32_t nchunks, uint64_t *__restrict__ grand_total) {
+    __shared__ uint64_t s_tmp[4];
+    const uint64_t v = threadIdx.x < nchunks ? chunk_sum[threadIdx.x] : 0;
+    uint64_t all;
+    const uint64_t ex = fm_block_excl_sum64(v, s_tmp, &all);
+    if (threadIdx.x < nchunks) chunk_sum[threadIdx.x] = ex;
+    if (threadIdx.x == 0) *grand_total = all;
+}
+__global__ __launch_bounds__(256) void k_fm_find_scan_c(const uint32_t *__restrict__ occ, uint32_t npairs, uint32_t rpc, const uint64_t *__restrict__ chunk_sum,
+                                                        uint64_t *__restrict__ offset) {
+    __shared__ uint64_t s_tmp[4];
+    const uint64_t p0 = static_cast<uint64_t>(blockIdx.x) * rpc * FM_FIND_ROW;
+    uint64_t run = chunk_sum[blockIdx.x];
+    for (uint32_t r = 0; r < rpc; ++r) {
+        const uint64_t p = p0 + static_cast<uint64_t>(r) * FM_FIND_ROW + threadIdx.x;
+        if (p0 + static_cast<uint64_t>(r) * FM_FIND_ROW >= npairs) break;  // (the same for every thread)
+        uint64_t all;
+        const uint64_t ex = fm_block_excl_sum64(p < npairs ? occ[p] : 0u, s_tmp, &all);
+        if (p < npairs) offset[p] = run + ex;
+        run += all;
+    }
+}
+
+struct FmFindLocArgs {
+    FmWalk w; const uint32_t *off, *lo; const uint64_t *offset; uint32_t npairs, count, nhits; uint4 *hits;
+};
+// A wave per hit h < nhits = min(total, max_hits).  The pair: the last one whose offset is <= h (behind it only pairs without hits share that
+// offset), by a 64-ary search -- every lane probes one offset, the ballot's population count picks the stretch -- in at most four rounds for
+// 2^24 pairs.  Then the walk of k_fm_locate from slot lo + (h - offset), and lane 0 stores the record with one 16-byte store.
+// Containment: the pair stays inside [0, npairs) by construction of the search, lo is clamped to [0, n_b] and the slot to [0, n_b).
+__global__ __launch_bounds__(64 * FM_WAVES) void k_fm_find_locate(FmFindLocArgs a) {
+    const uint32_t *__restrict__ off = a.off;
+    const uint64_t *__restrict__ offset = a.offset;
+    const uint32_t lane = threadIdx.x & 63u, count = a.count;
+    const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * FM_WAVES;
+    for (uint64_t h = static_cast<uint64_t>(blockIdx.x) * FM_WAVES + (threadIdx.x >> 6); h < a.nhits; h += nwaves) {
+        uint32_t plo = 0, phi = a.npairs;  // offset[plo] <= h, and the pair is in [plo, phi)
+        while (phi - plo > 1u) {
+            const uint32_t stride = (phi - plo + 63u) >> 6, idx = plo + lane * stride;
+            uint32_t k = static_cast<uint32_t>(__popcll(__ballot(idx < phi && offset[idx] <= h)));
+            k = k ? k - 1u : 0u;
+            plo += k * stride;
+            phi = phi - plo > stride ? plo + stride : phi;
+        }
+        const uint32_t pair = plo < a.npairs ? plo : a.npairs - 1u;
+        const uint32_t q = pair / count, b = pair - q * count, s = off[b], nb = off[b + 1] - s;
+        const uint32_t lo = a.lo[pair] < nb ? a.lo[pair] : nb;
+        const uint64_t x64 = lo + (h - offset[pair]);
+        const uint32_t x = x64 < nb ? static_cast<uint32_t>(x64) : nb - 1u;
+        const uint32_t pos = fm_locate_walk(a.w, b, s, nb, x, lane);
+        if (lane == 0) a.hits[h] = make_uint4(q, b, pos, x);
     }
 }
 
@@ -479,6 +615,59 @@ int fm_locate_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, s
         k_fm_locate<<<dim3(grid), dim3(64 * FM_WAVES), 0, ctx->stream>>>(a);
     }
     DK_HIP(ctx, hipGetLastError());
+    return DK_OK;
+}
+
+size_t fm_find_workspace(size_t npairs) {
+    auto r = [](size_t b) { return (b + 255) & ~size_t(255); };
+    return 2 * r(4 * npairs) + r(8 * npairs) + r(8 * FM_MAX_CHUNKS);
+}
+
+int fm_find_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, const void *d_index, const void *d_loc,
+                   uint32_t step, const uint8_t *d_pat, const uint32_t *d_pat_off, size_t npat, size_t pat_bytes, size_t max_hits, void *d_hits,
+                   uint32_t *d_occ, uint64_t *total_out) {
+    hipStream_t st = ctx->stream;
+    const FmIndex ix = fm_carve(const_cast<void *>(d_index), total, count);
+    const size_t npairs = npat * count, rows = div_up(npairs, FM_FIND_ROW), rpc = div_up(rows, FM_MAX_CHUNKS), nchunks = div_up(rows, rpc);
+    const size_t mark = ctx->ws_mark();
+    uint32_t *d_lo = ctx->ws_alloc<uint32_t>(npairs), *d_cnt = ctx->ws_alloc<uint32_t>(npairs);
+    uint64_t *d_offset = ctx->ws_alloc<uint64_t>(npairs), *chunk_sum = ctx->ws_alloc<uint64_t>(FM_MAX_CHUNKS);
+    if (!d_lo || !d_cnt || !d_offset || !chunk_sum) return DK_E_NOMEM;
+    const uint32_t P = static_cast<uint32_t>(npairs), R = static_cast<uint32_t>(rpc);
+    {
+        // per pair the count's traffic for its pattern (pat_bytes / npat on average), the three words written
+        LaunchScope ls(ctx, K_CHAIN, 20.0 * npairs + static_cast<double>(count) * pat_bytes * (1.0 + 2.0 * (FM_BLOCK + 64)));
+        const FmFindArgs a{d_bwt, d_off, ix.blocks, ix.base, ix.cp, d_pat, d_pat_off, static_cast<uint32_t>(npat), static_cast<uint32_t>(total),
+                           static_cast<uint32_t>(count), d_lo, d_cnt, d_occ};
+        const unsigned grid = static_cast<unsigned>(std::min<size_t>(div_up(npairs, FM_WAVES), 1u << 20));
+        k_fm_find_count<<<dim3(grid), dim3(64 * FM_WAVES), 0, st>>>(a);
+    }
+    {
+        LaunchScope ls(ctx, K_CHAIN, 16.0 * npairs);  // occ read twice, the offsets written
+        k_fm_find_scan_a<<<dim3(static_cast<unsigned>(nchunks)), dim3(256), 0, st>>>(d_cnt, P, R, chunk_sum);
+        k_fm_find_scan_b<<<dim3(1), dim3(256), 0, st>>>(chunk_sum, static_cast<uint32_t>(nchunks), &ctx->d_mail->fm_find.total);
+        k_fm_find_scan_c<<<dim3(static_cast<unsigned>(nchunks)), dim3(256), 0, st>>>(d_cnt, P, R, chunk_sum, d_offset);
+    }
+    DK_HIP(ctx, hipGetLastError());
+    DK_TRY(ctx->mail_read(&ctx->h_mail->fm_find.total));
+    const uint64_t all = ctx->h_mail->fm_find.total;
+    *total_out = all;
+    const size_t nhits = static_cast<size_t>(std::min<uint64_t>(all, max_hits));
+    if (nhits) {
+        const FmLocate lc = fm_locate_carve(const_cast<void *>(d_loc), total, count, step);
+        const FmFindLocArgs a{FmWalk{d_bwt, ix.blocks, ix.base, ix.cp, lc.marks, lc.bits, lc.samples, static_cast<uint32_t>(total),
+                                     static_cast<uint32_t>(ceil_log2_u64(step)), static_cast<uint32_t>(lc.nsamp)},
+                              d_off, d_lo, d_offset, P, static_cast<uint32_t>(count), static_cast<uint32_t>(nhits), static_cast<uint4 *>(d_hits)};
+        const unsigned grid = static_cast<unsigned>(std::min<size_t>(div_up(nhits, FM_WAVES), 1u << 20));
+        {
+            // per hit four rounds of 64 offsets, the walk of k_fm_locate and the record
+            LaunchScope ls(ctx, K_CHAIN, nhits * (4.0 * 512 + 36.0 + 0.5 * step * (FM_BLOCK + 128 + 64)));
+            k_fm_find_locate<<<dim3(grid), dim3(64 * FM_WAVES), 0, st>>>(a);
+        }
+        DK_HIP(ctx, hipGetLastError());
+        DK_HIP(ctx, hipStreamSynchronize(st));
+    }
+    ctx->ws_release(mark);
     return DK_OK;
 }
 

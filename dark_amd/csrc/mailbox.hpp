@@ -100,6 +100,11 @@ struct Mail {
             uint32_t giant_count; // k_lcp_wave (atomicAdd): positions still equal at the wave's cap, as above; the host sizes k_lcp_giant's walk by it
         } lists;
     } lcp;
+
+    // ---- FM-index find (fm_index.hip: fm_find_device) ---------------------------------------------------------------------------------------------
+    struct FmFind {
+        alignas(8) uint64_t total;  // k_fm_find_scan_b: the hits of all pairs together (a plain store on every launch); the host reads it behind the scan
+    } fm_find;
 };
 static_assert(sizeof(Mail) <= 4096, "the mailbox is one page");
 static_assert((LIVE_RING & (LIVE_RING - 1)) == 0, "rounds index the ring with a mask");

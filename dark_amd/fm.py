@@ -20,7 +20,9 @@ class Index:
     locate(patterns[, blocks], max_hits=16) -> a list of uint32 arrays, the first max_hits positions of every pattern in suffix-array order.
     extract_step (keyword of all four; None: no structure): a power of two in [1, 4096], the distance of the anchored text positions (section 4.15).
     extract(positions, length[, blocks]) -> a list of bytes, the text at [position, position + length) cut at the block's end; text([block]) ->
-    the whole block; snippets(patterns, before, after[, blocks], max_hits=16) -> per pattern a list of (position, bytes around the hit)."""
+    the whole block; snippets(patterns, before, after[, blocks], max_hits=16) -> per pattern a list of (position, bytes around the hit).
+    find(patterns, max_hits=65536) -> (occ, hits, total): every pattern in EVERY block as one compact list of (pattern, block, position, slot)
+    records (section 4.16); grep(patterns, before, after) -> (pattern, block, position, bytes around the hit) per record."""
 
     def __init__(self, ctx, d_bwt, sizes, origins, locate_step=None, extract_step=None):
         import torch
@@ -187,6 +189,56 @@ class Index:
         start = np.maximum(hit - before, 0)
         got = np.minimum(hit - start + plen + after, sizes - start)
         return [[(int(hit[i]), bytes(rows[i, :got[i]])) for i in range(q * max_hits, (q + 1) * max_hits) if hit[i] >= 0] for q in range(npat)]
+
+    def find(self, patterns, max_hits=65536):
+        """every pattern in every block (section 4.16) -> (occ, hits, total): occ a uint32 array of len(patterns) x blocks, hits a structured
+        array (pattern, block, position, slot) of the first min(total, max_hits) hits in the order (pattern, block, suffix-array slot), total
+        the number of hits in all.  max_hits=0 needs no locate structure.  The default 65536 (1 MiB of records) is a choice, not a measurement."""
+        import torch
+        from .context import FM_HIT_DTYPE
+        npat, count, max_hits = len(patterns), len(self.sizes), int(max_hits)
+        if max_hits and self.d_loc is None:
+            raise DarkError(_lib.DK_E_ARG, "the index was built without a locate structure (locate_step=None): only max_hits=0 is served")
+        if npat == 0:
+            return np.zeros((0, count), np.uint32), np.zeros(0, FM_HIT_DTYPE), 0
+        pat, lens, npat = _pack_patterns(patterns)
+        dev = self.d_bwt.device
+        d_pat = torch.from_numpy(pat).to(dev)
+        d_occ = torch.empty(npat * count, dtype=torch.int32, device=dev)
+        d_hits = torch.empty(4 * max_hits, dtype=torch.int32, device=dev) if max_hits else None  # (torch allocations are 256-byte aligned)
+        step = self.locate_step if self.locate_step is not None else 32
+        if count == 1:
+            total = self._ctx.dev_fm_find(self.d_bwt, self.total, self.d_index, self.d_loc, step, d_pat, list(lens)[:npat], max_hits, d_hits, d_occ)
+        else:
+            total = self._ctx.dev_fm_find_packed(self.d_bwt, self.sizes, self.d_index, self.d_loc, step, d_pat, list(lens)[:npat], max_hits, d_hits,
+                                                 d_occ)
+        got = min(total, max_hits)
+        hits = d_hits[:4 * got].cpu().numpy().view(FM_HIT_DTYPE) if got else np.zeros(0, FM_HIT_DTYPE)
+        return d_occ.cpu().numpy().view(np.uint32).reshape(npat, count), hits, total
+
+    def grep(self, patterns, before, after, max_hits=65536):
+        """a list of (pattern, block, position, bytes) for the hits of find(patterns, max_hits), in its order: bytes is the text from `before`
+        bytes in front of the hit to `after` bytes behind it, cut at the block's ends.  One find, the hits read back, one extract with a
+        window per hit; the blocks come from the records.  Needs both structures, as snippets does."""
+        import torch
+        if self.d_loc is None or self.d_ext is None:
+            raise DarkError(_lib.DK_E_ARG, "grep needs both structures (locate_step and extract_step)")
+        before, after = int(before), int(after)
+        _, hits, _ = self.find(patterns, max_hits)
+        hits = hits[hits["position"] != _lib.FM_NO_HIT]
+        if len(hits) == 0:
+            return []
+        plen = np.array([len(as_u8(p)) for p in patterns], dtype=np.int64)[hits["pattern"]]
+        pos, blk = hits["position"].astype(np.int64), hits["block"].astype(np.int64)
+        start = np.maximum(pos - before, 0)
+        got = np.minimum(pos - start + plen + after, np.array(self.sizes, dtype=np.int64)[blk] - start)
+        max_len = max(int(got.max()), 1)
+        dev = self.d_bwt.device
+        d_start = torch.from_numpy(start.astype(np.uint32).view(np.int32)).to(dev)
+        d_len = torch.from_numpy(got.astype(np.uint32).view(np.int32)).to(dev)
+        where = None if len(self.sizes) == 1 else [int(b) for b in blk]
+        rows = self._extract_dev(d_start, d_len, len(hits), where, max_len).cpu().numpy().reshape(len(hits), -1)
+        return [(int(hits["pattern"][i]), int(blk[i]), int(pos[i]), bytes(rows[i, :got[i]])) for i in range(len(hits))]
 
     def occurrences(self, patterns, blocks=None):
         lo, hi = self.count(patterns, blocks)

@@ -343,6 +343,28 @@ public:
         }
         return out;
     }
+    // Every pattern at once as one list (dk_fm_find, section 4.16): occ[q] = the occurrences of patterns[q], total their sum, hits the first
+    // min(total, max_hits) records {pattern, block = 0, position, slot} in the order (pattern, suffix-array slot).  max_hits = 0 needs no
+    // locate structure.  The default of 65536 records is a choice, not a measurement.
+    struct Found { std::vector<uint32_t> occ; std::vector<dk_fm_hit> hits; uint64_t total = 0; };
+    Found find(const std::vector<std::vector<uint8_t>> &patterns, size_t max_hits = 65536) {
+        if (max_hits && !step_) throw Error(DK_E_ARG, "the index was made without a locate structure (locate_step = 0)");
+        std::vector<size_t> lens;
+        std::vector<uint8_t> bytes(1);
+        for (const auto &p : patterns) {
+            lens.push_back(p.size());
+            bytes.insert(bytes.end(), p.begin(), p.end());
+        }
+        Found out;
+        out.occ.resize(patterns.size() + 1);
+        out.hits.resize(max_hits + 1);
+        int rc = dk_fm_find(ctx_.get(), bwt_.data(), bwt_.size(), static_cast<uint32_t>(origin_), step_ ? step_ : 32u, bytes.data() + 1, patterns.size(),
+                            lens.data(), max_hits, out.hits.data(), out.occ.data(), &out.total);
+        if (rc != DK_OK) throw Error(rc, ctx_.error());
+        out.occ.resize(patterns.size());
+        out.hits.resize(static_cast<size_t>(std::min<uint64_t>(out.total, max_hits)));
+        return out;
+    }
     detail::Ctx &context() { return ctx_; }  // context().purpose() == DK_CTX_DECODER
 private:
     detail::Ctx ctx_;

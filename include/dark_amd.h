@@ -339,6 +339,34 @@ int dk_dev_fm_extract_packed(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t count
  * structures, the ranges, the rows and the larger build workspace do not fit the context's workspace. */
 int dk_fm_extract(dk_ctx *any_ctx, const uint8_t *bwt, size_t n, uint32_t origin, uint32_t step, const uint32_t *pos, const uint32_t *len,
                   size_t nrange, size_t max_len, uint8_t *out);
+/* ---- FM-index: find.  Every pattern in every block, as one compact list of hits (csrc/fm_index.hip) ----
+ * The query of an archive search: the patterns are given once (layout of dk_dev_fm_count, no pat_block) and the grid (pattern q, block b) is
+ * walked on the device.  With [lo, hi) = what dk_dev_fm_count_packed gives for q in b:
+ *   d_occ[q * count + b] = hi - lo (0 where an index that is none gives hi < lo); d_occ (device, npat x count words) may be null
+ *   *total (HOST, 64 bits) = the sum of all occ
+ *   the hits, in ascending order of (q, b, j), j < occ, are the records {q, b, SA_b[lo + j], lo + j}: `position` is exactly what
+ *   dk_dev_fm_locate_packed writes for that slot (DK_FM_NO_HIT included), and the order inside a pair is its order
+ *   d_hits (device, 16-byte aligned) receives the first min(*total, max_hits) records; nothing behind them is written.
+ * max_hits == 0 is allowed: d_hits and d_loc may then be null, and only d_occ and *total come back.  The empty pattern counts every position.
+ * The order is fixed by an exclusive scan of occ over the pairs; no global atomics, so two calls give the same bytes.
+ * DK_E_ARG for what dk_dev_fm_count* and dk_dev_fm_locate* refuse (null or misaligned structures, a bad step, a bad pack), for npat x count >
+ * DK_FM_FIND_MAX_PAIRS, max_hits > 2^31, a d_hits that is not 16-byte aligned, a null `total`, and for a workspace that cannot hold the
+ * pattern offsets, 4 bytes per block and 16 bytes per pair.  DK_FM_FIND_MAX_PAIRS is a reasoned bound (256 MiB of workspace), not a measured one.
+ * Contained as count and locate are: lo and hi are clamped to [0, n_b], every slot to [0, n_b), the pair a hit belongs to to the pairs, and
+ * at most min(step, n_b) steps are taken per hit; for any bytes in L, the index and d_loc every record written has pattern < npat, block <
+ * count, slot < n_b and position < n_b or DK_FM_NO_HIT, and nothing outside the named buffers is touched. */
+typedef struct dk_fm_hit { uint32_t pattern, block, position, slot; } dk_fm_hit; /* 16 bytes */
+#define DK_FM_FIND_MAX_PAIRS (1u << 24)
+int dk_dev_fm_find(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t n, const void *d_index, const void *d_loc, uint32_t step, const uint8_t *d_pat,
+                   size_t npat, const size_t *pat_len /* host */, size_t max_hits, dk_fm_hit *d_hits, uint32_t *d_occ /* may be NULL */,
+                   uint64_t *total /* host */);
+int dk_dev_fm_find_packed(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const void *d_index, const void *d_loc,
+                          uint32_t step, const uint8_t *d_pat, size_t npat, const size_t *pat_len /* host */, size_t max_hits, dk_fm_hit *d_hits,
+                          uint32_t *d_occ /* may be NULL */, uint64_t *total /* host */);
+/* from and to host memory: upload, the builds (the locate structure only when max_hits > 0), find, download of min(*total, max_hits) records
+ * and of occ (npat words; may be null).  DK_E_ARG when L, the structures, the batch and the records do not fit the context's workspace. */
+int dk_fm_find(dk_ctx *any_ctx, const uint8_t *bwt, size_t n, uint32_t origin, uint32_t step, const uint8_t *pat, size_t npat,
+               const size_t *pat_len, size_t max_hits, dk_fm_hit *hits, uint32_t *occ, uint64_t *total);
 /* for the tests: d_out[q] = occurrences of d_sym[q] in d_bwt[0, min(d_pos[q], total)), computed by the count kernel's rank (all device memory) */
 int dk_dbg_dev_fm_rank(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t total, const void *d_index,
                        const uint32_t *d_pos, const uint8_t *d_sym, size_t nq, uint32_t *d_out);

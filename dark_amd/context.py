@@ -756,6 +756,61 @@ class Context:
                                                   int(above), int(begin_bit), int(end_bit)))
         return self._to_host(d_ko, np.uint64), self._to_host(d_vo, np.uint32)
 
+    def dbg_dev_rerank(self, keys, idx, pos_in=None, gid_in=None, bucket_starts=None, cmp_shift=0, rank=None, sa=None, bwt=None, sym_in=None,
+                       origin=None, ls_max=1024, reduce_tiles_per_wg=0, first_tiles_per_wg=0, sparse_max=-1, shift=None, fill=0xC3, pad=64):
+        """dk_dbg_dev_rerank: one regrouping and its classification.  keys: uint64, or uint32 with bucket_starts (256 words).  pos_in None: the
+        first rerank.  rank / sa / bwt / origin: what those arrays hold before the call (None: a null pointer).  shift: {name: elements} by which
+        the device view of keys / idx / gid_in / sym_in / bwt starts behind its allocation.  Every output array holds `fill` bytes before the
+        call; gstart has count // 2 + 1 + pad words, bigidx and bigoff count // 2 + pad.  -> dict of the arrays after the call (whole, the
+        untouched parts included; None for the null ones) and counts = (active, groups, big_slots, big_groups, above_pl_slots)"""
+        import torch
+        shift = shift or {}
+        dev = "cuda:%d" % self.device
+
+        def up(name, a, dtype):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dtype)
+            off = int(shift.get(name, 0))
+            whole = np.concatenate([np.zeros(off, dtype), a]) if off else a.copy()
+            return torch.from_numpy(whole.view({1: np.uint8, 4: np.int32, 8: np.int64}[whole.dtype.itemsize])).to(dev)[off:]
+
+        def out(words, dtype):
+            return torch.from_numpy(np.full(words * np.dtype(dtype).itemsize, fill, np.uint8)).to(dev)
+
+        narrow = np.asarray(keys).dtype == np.uint32
+        count = len(keys)
+        d = dict(keys=up("keys", keys, np.uint32 if narrow else np.uint64), bucket_starts=up("bucket_starts", bucket_starts, np.uint32),
+                 idx=up("idx", idx, np.uint32), pos_in=up("pos_in", pos_in, np.uint32), gid_in=up("gid_in", gid_in, np.uint32),
+                 rank=up("rank", rank, np.uint32), sa=up("sa", sa, np.uint32), bwt=up("bwt", bwt, np.uint8), sym_in=up("sym_in", sym_in, np.uint8),
+                 origin=up("origin", None if origin is None else [origin], np.uint32))
+        for name in ("idx", "pos_in", "gid_in", "sym_in"):
+            if d[name] is not None and len(d[name]) != count:
+                raise DarkError(_lib.DK_E_ARG, "%d keys, %d entries of %s" % (count, len(d[name]), name))
+        if pos_in is None and bwt is not None and len(d["bwt"]) != count:
+            raise DarkError(_lib.DK_E_ARG, "the first rerank reads L[slot]: %d keys, %d bytes of bwt" % (count, len(d["bwt"])))
+        outs = dict(out_idx=(count + pad, np.uint32), out_pos=(count + pad, np.uint32), out_gid=(count + pad, np.uint32),
+                    sym_out=(count + pad, np.uint8), gstart=(count // 2 + 1 + pad, np.uint32), bigidx=(count // 2 + pad, np.uint32),
+                    bigoff=(count // 2 + pad, np.uint32))
+        if bwt is None:
+            del outs["sym_out"]
+        o = {name: out(words, dtype) for name, (words, dtype) in outs.items()}
+        counts = np.zeros(5, np.uint32)
+        p = lambda t: None if t is None else _ptr(t)  # noqa: E731
+        _inputs_ready(d["keys"])
+        self._ck(self._lib.dk_dbg_dev_rerank(self._h, p(d["keys"]), 4 if narrow else 8, p(d["bucket_starts"]), p(d["idx"]), p(d["pos_in"]), p(d["gid_in"]),
+                                             int(cmp_shift), count, p(d["rank"]), p(d["sa"]), p(d["bwt"]), p(d["sym_in"]), p(o.get("sym_out")),
+                                             p(d["origin"]), p(o["out_idx"]), p(o["out_pos"]), p(o["out_gid"]), p(o["gstart"]), p(o["bigidx"]),
+                                             p(o["bigoff"]), int(ls_max), _ptr(counts), int(reduce_tiles_per_wg), int(first_tiles_per_wg),
+                                             int(sparse_max)))
+        res = {name: self._to_host(t, outs[name][1]) for name, t in o.items()}
+        res.setdefault("sym_out", None)
+        for name, dtype in (("rank", np.uint32), ("sa", np.uint32), ("bwt", np.uint8)):
+            res[name] = None if d[name] is None else self._to_host(d[name], dtype)
+        res["origin"] = None if d["origin"] is None else int(self._to_host(d["origin"], np.uint32)[0])
+        res["counts"] = tuple(int(c) for c in counts)
+        return res
+
     def dbg_dev_inverse_permutation(self, sa, marked_val=None):
         """dk_dbg_dev_inverse_permutation: rank[sa[p] & 0x7FFFFFFF] = marked_val[p] if sa[p] has bit 31 set (and marked_val is given) else p"""
         d_sa = self._to_dev(sa, np.uint32)

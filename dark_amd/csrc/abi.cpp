@@ -2424,6 +2424,30 @@ int dk_dbg_dev_sort_groups(dk_ctx *ctx, const uint64_t *d_kin, const uint32_t *d
     DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return DK_OK;
 }
+int dk_dbg_dev_rerank(dk_ctx *ctx, const void *d_keys, int key_bytes, const uint32_t *d_bucket_starts, const uint32_t *d_idx, const uint32_t *d_pos_in,
+                      const uint32_t *d_gid_in, int cmp_shift, size_t count, uint32_t *d_rank, uint32_t *d_sa, uint8_t *d_bwt, const uint8_t *d_sym_in,
+                      uint8_t *d_sym_out, uint32_t *d_origin, uint32_t *d_out_idx, uint32_t *d_out_pos, uint32_t *d_out_gid, uint32_t *d_gstart,
+                      uint32_t *d_bigidx, uint32_t *d_bigoff, uint32_t ls_max, uint32_t counts_out[5], unsigned reduce_tiles_per_wg,
+                      unsigned first_tiles_per_wg, int sparse_max) {
+    DK_TRY(begin_call(ctx, "dk_dbg_dev_rerank"));
+    ScopedCall sc(ctx);
+    if (!d_keys || !d_idx || !d_out_idx || !d_out_pos || !d_out_gid || !d_gstart || !d_bigidx || !d_bigoff || !counts_out)
+        return ctx->fail(DK_E_ARG, "rerank: null pointer");
+    if (count == 0 || count > ctx->max_n || count > 0x7FFFFFFEull) return ctx->fail(DK_E_ARG, "rerank: %zu slots (context capacity %zu)", count, ctx->max_n);
+    if (key_bytes != 4 && key_bytes != 8) return ctx->fail(DK_E_ARG, "rerank: keys of %d bytes", key_bytes);
+    if ((key_bytes == 4) != (d_bucket_starts != nullptr)) return ctx->fail(DK_E_ARG, "rerank: bucket starts go with 4-byte keys, and only with them");
+    if (key_bytes == 4 && (d_pos_in || d_gid_in)) return ctx->fail(DK_E_ARG, "rerank: narrow keys only in the first rerank (no d_pos_in, no d_gid_in)");
+    if (d_rank && !d_pos_in) return ctx->fail(DK_E_ARG, "rerank: the first rerank (no d_pos_in) writes no ranks");
+    if (cmp_shift < 0 || cmp_shift > 63 || (cmp_shift && (d_pos_in || key_bytes == 4)))
+        return ctx->fail(DK_E_ARG, "rerank: cmp_shift %d (0 .. 63, and only the first rerank of 8-byte keys leaves low bits out)", cmp_shift);
+    if (d_bwt && (!d_sym_out || (d_pos_in && (!d_sym_in || !d_origin)))) return ctx->fail(DK_E_ARG, "rerank: d_bwt without the rest of the carry");
+    if (reduce_tiles_per_wg > 64 || first_tiles_per_wg > 64)
+        return ctx->fail(DK_E_ARG, "rerank: %u / %u tiles per workgroup (at most 64)", reduce_tiles_per_wg, first_tiles_per_wg);
+    if (sparse_max > 2048) return ctx->fail(DK_E_ARG, "rerank: sparse_max %d (a tile holds 2048 slots)", sparse_max);
+    const DbgRerank a{static_cast<const uint64_t *>(d_keys), d_bucket_starts, d_idx, d_pos_in, d_gid_in, cmp_shift, count, d_rank, d_sa, d_bwt, d_sym_in, d_sym_out,
+                      d_origin, d_out_idx, d_out_pos, d_out_gid, d_gstart, d_bigidx, d_bigoff, ls_max, reduce_tiles_per_wg, first_tiles_per_wg, sparse_max};
+    return dbg_rerank_device(ctx, a, counts_out);
+}
 int dk_dbg_dev_inverse_permutation(dk_ctx *ctx, const uint32_t *d_sa, size_t n, uint32_t *d_rank, const uint32_t *d_marked_val) {
     DK_TRY(begin_call(ctx, "dk_dbg_dev_inverse_permutation"));
     ScopedCall sc(ctx);

@@ -209,6 +209,15 @@ bool inverse_through_windows(size_t n);  // does the inverse of a permutation of
 int suffix_array_device(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d_sa_out, uint8_t *d_bwt = nullptr,
                         uint32_t *d_origin = nullptr, bool *bwt_written = nullptr);
 int bwt_forward_device(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d_sa, uint8_t *d_bwt, uint32_t *origin);
+// dk_dbg_dev_rerank's arguments under the names of the header: one rerank() and the classify_and_read() behind it on the caller's arrays.
+// keys: 32-bit words when bucket_starts is given.  counts_out: active, groups, big_slots, big_groups, above_pl_slots.  Synchronises.
+struct DbgRerank {
+    const uint64_t *keys; const uint32_t *bucket_starts, *idx, *pos_in, *gid_in; int cmp_shift; size_t count;
+    uint32_t *rank, *sa; uint8_t *bwt; const uint8_t *sym_in; uint8_t *sym_out; uint32_t *origin;
+    uint32_t *out_idx, *out_pos, *out_gid, *gstart, *bigidx, *bigoff; uint32_t ls_max;
+    uint32_t reduce_tiles_per_wg, first_tiles_per_wg; int sparse_max;
+};
+int dbg_rerank_device(dk_ctx *ctx, const DbgRerank &args, uint32_t counts_out[5]);
 // bwt.hip
 int bwt_gather_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_sa, size_t n, uint8_t *d_bwt, uint32_t *origin);
 int bwt_inverse_device(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t origin, uint8_t *d_out);

@@ -797,11 +797,16 @@ __global__ __launch_bounds__(RR_BLOCK) void k_rerank_apply_first(const uint8_t *
     }
 }
 
+// The launch shapes a test may set (dk_dbg_dev_rerank: the multi-tile stretches of k_rerank_reduce and k_rerank_apply_first start at 2^26 and
+// 2^25 slots otherwise); the sort passes none.  Tiles per workgroup: 1 .. RA_FIRST_TILES (the caller's check), 0 = by the number of tiles;
+// sparse_max: survivors per tile up to which k_rerank_apply_first fetches them one by one, negative = RA_SPARSE (or its knob).
+struct RerankShape { uint32_t reduce_tiles_per_wg = 0, first_tiles_per_wg = 0; int sparse_max = -1; };
+
 // rank == nullptr: no rank array exists yet (first rerank, text rounds)
 // narrow_starts != nullptr (first rerank only): `keys` holds 32-bit words (SortFinalOut::narrow_shift), narrow_starts the 256 bucket starts
 int rerank(dk_ctx *ctx, const uint64_t *keys, const uint32_t *idx, const uint32_t *pos_in, size_t count, const uint32_t *gid_in, uint32_t *rank,
            uint32_t *sa, uint32_t *out_idx, uint32_t *out_pos, uint32_t *out_gid, uint32_t *gstart, BwtCarry fb = NO_CARRY,
-           const uint32_t *narrow_starts = nullptr) {
+           const uint32_t *narrow_starts = nullptr, RerankShape shape = RerankShape{}) {
     const size_t ntiles = div_up(count, RR_TILE);
     const size_t mark = ctx->ws_mark();
     RerankAgg *agg = ctx->ws_alloc<RerankAgg>(ntiles);
@@ -810,7 +815,7 @@ int rerank(dk_ctx *ctx, const uint64_t *keys, const uint32_t *idx, const uint32_
     hipStream_t st = ctx->stream;
     {
         LaunchScope ls(ctx, K_RERANK_REDUCE, ((narrow_starts ? 4.0 : 8.0) + (gid_in ? 4.0 : 0.0) + 1.0) * count);
-        const uint32_t per_wg = static_cast<uint32_t>(std::min<size_t>(std::max<size_t>(ntiles / 16384, 1), 64));
+        const uint32_t per_wg = shape.reduce_tiles_per_wg ? shape.reduce_tiles_per_wg : static_cast<uint32_t>(std::min<size_t>(std::max<size_t>(ntiles / 16384, 1), 64));
         const dim3 grid(static_cast<unsigned>(div_up(ntiles, per_wg))), block(RR_BLOCK);
         if (narrow_starts) {
             if (pos_in || gid_in) return ctx->fail(DK_E_INTERNAL, "rerank: narrow keys only in the first rerank");
@@ -840,9 +845,10 @@ int rerank(dk_ctx *ctx, const uint64_t *keys, const uint32_t *idx, const uint32_
             k_rerank_apply<<<dim3(ntiles), dim3(RR_BLOCK), 0, st>>>(flags, idx, pos_in, count, agg, rank, sa, out_idx, out_pos, out_gid, gstart, fb);
         } else {
             if (rank) return ctx->fail(DK_E_INTERNAL, "rerank: the first rerank writes no ranks");
-            const uint32_t per_wg = static_cast<uint32_t>(std::min<size_t>(std::max<size_t>(ntiles / 8192, 1), RA_FIRST_TILES));
+            const uint32_t per_wg = shape.first_tiles_per_wg ? shape.first_tiles_per_wg : static_cast<uint32_t>(std::min<size_t>(std::max<size_t>(ntiles / 8192, 1), RA_FIRST_TILES));
+            const uint32_t sparse_max = static_cast<uint32_t>(shape.sparse_max >= 0 ? shape.sparse_max : DK_KNOB("DK_RA_SPARSE", RA_SPARSE));
             k_rerank_apply_first<<<dim3(div_up(ntiles, per_wg)), dim3(RR_BLOCK), 0, st>>>(flags, idx, count, agg, out_idx, out_pos, out_gid, gstart, &ctx->d_mail->cls.rounds, fb,
-                                                                                          static_cast<uint32_t>(ntiles), per_wg, static_cast<uint32_t>(DK_KNOB("DK_RA_SPARSE", RA_SPARSE)));
+                                                                                          static_cast<uint32_t>(ntiles), per_wg, sparse_max);
         }
     }
     DK_HIP(ctx, hipGetLastError());
@@ -1586,6 +1592,22 @@ int classify_and_read(dk_ctx *ctx, size_t max_groups, uint32_t *gstart, uint32_t
     ctx->ws_release(mark);
     return DK_OK;
 }
+
+}  // namespace
+
+// dk_dbg_dev_rerank (abi.cpp has checked the arguments): one rerank and the classification behind it, as a round of the sort runs them
+int dbg_rerank_device(dk_ctx *ctx, const DbgRerank &a, uint32_t counts_out[5]) {
+    const BwtCarry bc{a.cmp_shift, a.bwt, nullptr, a.origin, a.sym_in, a.sym_out};  // (without bwt the kernels look at none of the three behind it)
+    const RerankShape shape{a.reduce_tiles_per_wg, a.first_tiles_per_wg, a.sparse_max};
+    DK_TRY(rerank(ctx, a.keys, a.idx, a.pos_in, a.count, a.gid_in, a.rank, a.sa, a.out_idx, a.out_pos, a.out_gid, a.gstart, bc, a.bucket_starts, shape));
+    GroupCounts c;
+    DK_TRY(classify_and_read(ctx, a.count / 2, a.gstart, a.bigidx, a.bigoff, &c, a.ls_max));
+    const size_t v[5] = {c.active, c.groups, c.big, c.big_groups, c.above_pl};
+    for (int i = 0; i < 5; ++i) counts_out[i] = static_cast<uint32_t>(v[i]);
+    return DK_OK;
+}
+
+namespace {
 
 // How a stretch of the sort ends, for the functions that may end the whole call.  They return one of these or a (negative) DK_E_* code.
 enum SortStep : int {

@@ -534,6 +534,32 @@ int dk_dbg_dev_local_sort(dk_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, size_
  * memory, ngroups + 1 entries: DK_E_ARG unless it is non-decreasing and ends at most at npairs. */
 int dk_dbg_dev_sort_groups(dk_ctx *ctx, const uint64_t *d_kin, const uint32_t *d_vin, uint64_t *d_kout, uint32_t *d_vout, const uint32_t *starts,
                            size_t ngroups, size_t npairs, uint32_t above, int begin_bit, int end_bit);
+/* One regrouping of the suffix sort on device arrays the caller built: rerank() (k_rerank_reduce, k_rerank_scan / _a / _c, k_rerank_apply or
+ * k_rerank_apply_first) and the classification of the new groups behind it (k_big_reduce / _spine / _apply), with the mailbox read back as the
+ * sort reads it.  A full context only.  tests/rerank_model.py is the definition of every output.
+ *   d_keys, key_bytes   `count` sorted keys of 8 or 4 bytes (naturally aligned).  4: the narrow first rerank, with d_bucket_starts[256] (slots that
+ *                       are heads whatever their words say; values from `count` up name no slot); otherwise d_bucket_starts is null
+ *   d_idx, d_pos_in     the suffix and the SA position of every slot.  d_pos_in null: the FIRST rerank (slot a is SA position a; finals are left
+ *                       where they stand, so d_sa, d_sym_in and d_origin are not looked at and d_bwt is read, L[a] being slot a's symbol)
+ *   d_gid_in            (may be null) the group every slot was in before: a head wherever it changes, and such heads keep their members' ranks
+ *   cmp_shift           low key bits outside the comparison; only the first rerank of 8-byte keys has any, 0 everywhere else
+ *   d_rank, d_sa        (either may be null) later reranks: rank[idx] = SA position of the group's head; sa[pos] = idx for finals
+ *   d_bwt, d_sym_in, d_sym_out, d_origin   the carry (d_bwt null: none; otherwise d_sym_out, and in a later rerank all four)
+ *   d_out_idx, d_out_pos, d_out_gid        the new active list; d_gstart (count / 2 + 1 words); d_bigidx, d_bigoff (count / 2 words each)
+ *   ls_max              groups of more members are big
+ *   counts_out          (host) active, groups, big_slots, big_groups, above_pl_slots
+ *   reduce_tiles_per_wg, first_tiles_per_wg, sparse_max   the launch shapes of k_rerank_reduce and k_rerank_apply_first: 1 .. 64 tiles per
+ *                       workgroup and 0 .. 2048 survivors up to which a tile is fetched slot by slot; 0, 0 and a negative number = what the sort
+ *                       itself takes.  The outputs do not depend on them.
+ * The caller's duties are the sort's own: idx[a] < the length of d_rank, pos_in[a] < the length of d_sa and d_bwt, and arrays of the sizes above.
+ * DK_E_ARG before anything is launched: a null context or array, an open batch, count == 0 or above the context's capacity or 2^31 - 2, other key
+ * sizes, 4-byte keys with d_pos_in or d_gid_in or without bucket starts, d_rank without d_pos_in, a cmp_shift where there is none, half a carry,
+ * more than 64 tiles per workgroup, sparse_max above 2048.  DK_E_NOMEM when rerank()'s workspace (1.01 bytes per slot) does not fit. */
+int dk_dbg_dev_rerank(dk_ctx *ctx, const void *d_keys, int key_bytes, const uint32_t *d_bucket_starts, const uint32_t *d_idx, const uint32_t *d_pos_in,
+                      const uint32_t *d_gid_in, int cmp_shift, size_t count, uint32_t *d_rank, uint32_t *d_sa, uint8_t *d_bwt, const uint8_t *d_sym_in,
+                      uint8_t *d_sym_out, uint32_t *d_origin, uint32_t *d_out_idx, uint32_t *d_out_pos, uint32_t *d_out_gid, uint32_t *d_gstart,
+                      uint32_t *d_bigidx, uint32_t *d_bigoff, uint32_t ls_max, uint32_t counts_out[5], unsigned reduce_tiles_per_wg,
+                      unsigned first_tiles_per_wg, int sparse_max);
 /* d_rank[d_sa[p]] = p for a permutation d_sa of 0 .. n-1 (n <= 2^31), through LDS windows.  d_marked_val (may be null): an entry of d_sa with bit
  * 31 set stands for d_sa[p] & 0x7FFFFFFF and its value is d_marked_val[p] instead of p.  The two n-u64 scratch arrays come from the context's
  * workspace: DK_E_NOMEM when they do not fit.  What it does with an input that is no permutation is not defined beyond "no store outside d_rank". */

@@ -6,7 +6,7 @@ Every context is opened by open_ctx: it proves that the library is the tuning bu
 every size asked, a multiple of 256 or not), then puts FillingLib between the context and the library, so that dk_dbg_mail_fill(BYTE) runs in
 front of EVERY call that takes the context -- the helpers of the stage tests, imported from their files, need no change for that.  Results
 are compared with the CPU models those helpers use (oracle/orc.py, ibwt_model, lcp_model, sa_query_model, fm_model, fm_locate_model,
-fm_extract_model), never with another GPU run, unless a helper does both.  The shapes are the smallest that reach each route; a larger one
+fm_extract_model, rerank_model), never with another GPU run, unless a helper does both.  The shapes are the smallest that reach each route; a larger one
 says why where it is defined."""
 import json
 import os
@@ -459,7 +459,31 @@ def group_fm():
     done_with(dec)
 
 
-GROUPS = {"dc": group_dc, "inverse": group_inverse, "packed": group_packed, "lcp": group_lcp, "sa": group_sa, "fm": group_fm}
+# ---- one regrouping of the suffix sort: rerank() and classify_and_read() ---------------------------------------------------------------------------
+def group_rerank():
+    import test_gpu_rerank_layer as R
+    # 13 tiles and five slots with heads around every tile border, 40 tiles of sparse, dense and surviving-free tiles, a heavy-tailed mixture:
+    # the flags are read for whole tiles (the last one's rest and k_rerank_apply_first's look at tiles it then skips) and the tile aggregates
+    # are scanned in place; classify_and_read clears above_pl_slots itself, which only groups above PL_MAX add to.  Every form, the sort's own
+    # shapes and stretches of 2, 3 and 64 tiles.
+    ctx = open_ctx(41 * R.TILE)
+    rng = np.random.default_rng(31)
+    count = 13 * R.TILE + 5
+    plan = [0, "pair", 0, 64, 65, R.TILE, 0, 0, 0, 2, 0, 0, R.TILE, 0, 5, 0] * 2 + [0] * 8
+    lists = [("borders", R.sizes_from_heads(count, R.border_heads(rng, count)), R.FORMS), ("tile plan", R.tile_plan_sizes(plan), ("first", "narrow")),
+             ("heavy tail", R.heavy_sizes(rng, 7 * R.TILE - 1), R.FORMS), ("nothing above PL_MAX", R.heavy_sizes(rng, 3 * R.TILE + 1, cap=R.M.PL_MAX), R.FORMS),
+             ("all singletons", np.ones(2 * R.TILE + 9, np.int64), R.FORMS)]
+    for name, sizes, forms in lists:
+        for form in forms:
+            say("%s, %s form" % (name, form))
+            c = R.make_case(rng, sizes, form, zero="final", ls_max=R.M.PL_MAX)
+            if name == "nothing above PL_MAX":
+                assert R.expected(c)[0].above_pl_slots == 0
+            R.check(ctx, c, name, overrides=R.OVERRIDES[1:4])
+    done_with(ctx)
+
+
+GROUPS = {"rerank": group_rerank, "dc": group_dc, "inverse": group_inverse, "packed": group_packed, "lcp": group_lcp, "sa": group_sa, "fm": group_fm}
 
 if __name__ == "__main__":
     import time

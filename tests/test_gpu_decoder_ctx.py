@@ -345,6 +345,8 @@ def refused_calls(ctx, n):
         ("dk_dbg_dev_sort_pairs", lambda: lib.dk_dbg_dev_sort_pairs(h, p(d_a), p(d_b), n, 0, 64)),
         ("dk_dbg_dev_local_sort", lambda: lib.dk_dbg_dev_local_sort(h, p(d_a), p(d_b), n, 0, 64)),
         ("dk_dbg_dev_sort_groups", lambda: lib.dk_dbg_dev_sort_groups(h, p(d_a), p(d_b), p(d_c), p(d_d), p(starts), 1, n, 0, 0, 64)),
+        ("dk_dbg_dev_rerank", lambda: lib.dk_dbg_dev_rerank(h, p(d_a), 8, None, p(d_b), None, None, 0, n, None, None, None, None, None, None, p(d_c), p(d_c, 4 * n),
+                                                            p(d_d), p(d_d, 4 * n), p(d_b, 4 * n), p(d_b, 6 * n), 1024, p(host), 0, 0, -1)),
         ("dk_dbg_dev_inverse_permutation", lambda: lib.dk_dbg_dev_inverse_permutation(h, p(d_a), n, p(d_b), None)),
     ], batch
 

@@ -12,6 +12,7 @@ helpers and compares with their CPU models (DESIGN.md section 3 has the table of
   lcp       phi, the long and the giant list, single and packed, and a suffix array that is refused
   sa        sa_check on valid and damaged arrays, sa_search on both sides of its kernels' border, in one block and in a pack
   fm        the FM-index: build and count, the locate and extract structures at steps 8 and 32, snippets; full and decoder contexts
+  rerank    one regrouping of the suffix sort (rerank, classify_and_read) on built lists of a few tiles: first, narrow and later forms
 The bytes, in this order: 0 imitates a fresh allocation, 255 the all-ones sentinels (IB_END, DK_FM_NO_HIT, LCP_MARK, the 0xFF fills), 165
 neither; each hides what the others show.  First in every worker: dbg_ws_peek returns the byte and the library is the tuning build --
 otherwise the run proves nothing and fails."""
@@ -29,7 +30,7 @@ pytestmark = pytest.mark.gpu
 TUNING_LIB = os.path.join(ROOT, "dark_amd", "libdark_amd_tuning.so")
 WORKER = os.path.join(ROOT, "tests", "poison_worker.py")
 TIMEOUT = 240  # seconds per subprocess, as in tests/test_gpu_fallbacks.py; a group takes a few
-GROUPS = ("dc", "inverse", "packed", "lcp", "sa", "fm")
+GROUPS = ("dc", "inverse", "packed", "lcp", "sa", "fm", "rerank")
 BYTES = (0, 255, 165)
 # what a group must have gone through (stats()["routes"] of its calls, asserted case by case in the worker as the stage's own test does)
 ROUTES = {"packed": {"packed_guard"}, "lcp": {"lcp_long", "lcp_giant", "packed_guard"}}

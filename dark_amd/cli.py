@@ -29,7 +29,12 @@ Extensions beyond the reference (whole file = one block, read into memory, one t
              pack at a time is indexed on the GPU and every pattern is looked for in every block; no block is inverted, no file is written.
              One line per hit in file order, absolute_offset:pattern_index:enclosing line (--context-bytes, default 80, on either side, cut
              at the nearest newlines); --count-only: pattern_index:count per pattern; --max-hits bounds the hits listed per pack.  Exit status
-             0 with hits, 1 without.  A match that straddles two blocks is NOT found.
+             0 with hits, 1 without.  A match that straddles two blocks is NOT found, unless --across-blocks is given.
+  --across-blocks (with --grep / --grep-hex)
+             also find the matches that straddle block borders: every pattern is compared at every border of a pack on the
+             GPU, with the last bytes of the text so far carried from pack to pack.  They are listed among the others in file order, in the
+             same format; their line is cut at the start of the block holding the match's first byte and at the end of the block holding its
+             last one.  --count-only adds them to the counts.  Patterns above 4096 bytes are searched inside the blocks only (a note says so).
 """
 import argparse
 import os
@@ -671,21 +676,30 @@ def enclosing_line(window, at, length):
     return window[left:right if right >= 0 else len(window)]
 
 
-def grep_file(path, model, patterns, device=0, context_bytes=80, count_only=False, max_hits=None, host_threads=0, stats=None, out=None):
+def grep_file(path, model, patterns, device=0, context_bytes=80, count_only=False, max_hits=None, host_threads=0, stats=None, out=None, across=False):
     """search FILE.dark pack by pack without inverting a block; prints `absolute_offset:pattern_index:enclosing line` per hit in file order (or
-    `pattern_index:count` per pattern) and returns the number of occurrences.  A match that straddles two blocks is not found."""
+    `pattern_index:count` per pattern) and returns the number of occurrences.  A match that straddles two blocks is found with across=True
+    only (--across-blocks)."""
     from . import search
     out = out or sys.stdout
     max_hits = search.DEFAULT_MAX_HITS if max_hits is None else max_hits
     counts = np.zeros(len(patterns), dtype=np.int64)
     lines, listed = [], 0
-    for hits, occ, _ in search.search_archive(path, model, patterns, device, context_bytes, context_bytes, max_hits, host_threads,
-                                              count_only=count_only, stats=stats):
+    stats = {} if stats is None else stats
+    for found in search.search_archive(path, model, patterns, device, context_bytes, context_bytes, max_hits, host_threads,
+                                       count_only=count_only, stats=stats, across=across):
+        hits, occ = found[0], found[1]
         counts += occ.astype(np.int64).sum(axis=1)
+        if across:  # the same five fields, from the record that holds the match's first byte
+            hits = hits + found[3][0]
+            counts += found[3][1].astype(np.int64).sum(axis=1)
         listed += len(hits)
         for _, start, q, pos, text in hits:
             at = min(pos, context_bytes)
             lines.append((start + pos, q, enclosing_line(text, at, len(patterns[q]))))
+    if stats.get("seam_skipped"):
+        _note("seam_skipped", "pattern%s %s: longer than 4096 bytes, searched inside the blocks only" % (
+            "s" if len(stats["seam_skipped"]) > 1 else "", ", ".join(str(q) for q in stats["seam_skipped"])))
     if count_only:
         for q, c in enumerate(counts):
             print("%d:%d" % (q, c), file=out)
@@ -715,7 +729,9 @@ def main(argv=None):
     ap.add_argument("--grep", action="append", default=[], metavar="TEXT", help="search FILE.dark for TEXT instead of decoding it (repeatable; one GPU; "
                     "-m as for decoding): the blocks are decoded as far as their BWT and searched there on the GPU, none is inverted and no file is "
                     "written.  Prints absolute_offset:pattern_index:enclosing line per hit in file order; exit status 0 with hits, 1 without.  A "
-                    "match that straddles two blocks is NOT found")
+                    "match that straddles two blocks is NOT found unless --across-blocks is given")
+    ap.add_argument("--across-blocks", action="store_true", help="--grep: also find the matches that straddle block borders, by one more GPU query "
+                    "per pack over its borders; they are listed and counted among the others")
     ap.add_argument("--grep-hex", action="append", default=[], metavar="HEX", help="the same for a pattern given as hexadecimal bytes (repeatable; "
                     "pattern indices count the --grep patterns first)")
     ap.add_argument("--context-bytes", type=int, default=80, help="--grep: the enclosing line is cut from this many bytes on either side of a hit, "
@@ -731,6 +747,8 @@ def main(argv=None):
     if args.worker:
         return _worker_decode(args) if decode else _worker_encode(args)
     t0 = time.perf_counter()
+    if args.across_blocks and not (args.grep or args.grep_hex):
+        ap.error("--across-blocks goes with --grep / --grep-hex")
     if args.grep or args.grep_hex:
         if not decode:
             ap.error("--grep searches a .%s archive" % EXTENSION)
@@ -747,7 +765,8 @@ def main(argv=None):
         if any(len(p) == 0 for p in patterns):
             ap.error("--grep: an empty pattern")
         st = {}
-        found = grep_file(args.file, args.model, patterns, args.device, args.context_bytes, args.count_only, args.max_hits, args.host_threads, st)
+        found = grep_file(args.file, args.model, patterns, args.device, args.context_bytes, args.count_only, args.max_hits, args.host_threads, st,
+                          across=args.across_blocks)
         if args.stats:
             import json
             import resource

@@ -100,6 +100,8 @@ def fm_extract_bytes(total, count=1, step=32):
 
 # dk_fm_hit: a record of dk_dev_fm_find* (16 bytes)
 FM_HIT_DTYPE = np.dtype([("pattern", np.uint32), ("block", np.uint32), ("position", np.uint32), ("slot", np.uint32)])
+# dk_fm_seam_hit: a record of dk_dev_fm_seams* (16 bytes)
+FM_SEAM_HIT_DTYPE = np.dtype([("pattern", np.uint32), ("block", np.uint32), ("back", np.uint32), ("reserved", np.uint32)])
 
 
 class Context:
@@ -580,6 +582,34 @@ class Context:
         self._ck(self._lib.dk_fm_find(self._h, _ptr(b), len(b), int(origin), int(step), _ptr(pat), npat, lens, int(max_hits), _ptr(hits), _ptr(occ),
                                       C.byref(total)))
         return occ, hits[:min(int(total.value), int(max_hits))], int(total.value)
+
+    # ---- FM-index seams: the matches that straddle block borders; decoder contexts too ----
+    def dev_fm_seams(self, d_bwt, n, d_index, d_ext, step, d_prev, d_pat, pat_lens, max_hits, d_hits, d_occ=None):
+        """the occurrences of every pattern in (d_prev + the block's text) that start in d_prev (a uint8 device tensor, or None) and end in the
+        block: d_occ[q] their number, the return value the sum; d_hits (16-byte aligned, max_hits records of four uint32 words: pattern, block,
+        back, 0) receives the first min(sum, max_hits) in the order (pattern, back descending), back = the match's bytes in front of the block"""
+        _inputs_ready(d_bwt, d_index, d_ext, d_pat)
+        npat, prev_len = len(pat_lens), 0 if d_prev is None else int(d_prev.numel())
+        lens = (C.c_size_t * max(npat, 1))(*[int(m) for m in pat_lens])
+        total = C.c_uint64(0)
+        self._ck(self._lib.dk_dev_fm_seams(self._h, _ptr(d_bwt), n, _ptr(d_index), _ptr(d_ext), int(step), _ptr(d_prev) if prev_len else None, prev_len,
+                                           _ptr(d_pat), npat, lens, int(max_hits), None if d_hits is None else _ptr(d_hits),
+                                           None if d_occ is None else _ptr(d_occ), C.byref(total)))
+        return int(total.value)
+
+    def dev_fm_seams_packed(self, d_bwt, sizes, d_index, d_ext, step, d_prev, d_pat, pat_lens, max_hits, d_hits, d_occ=None):
+        """dev_fm_seams over a pack: d_prev and the blocks are the consecutive pieces of one text, and a seam hit -- first and last byte in
+        different pieces -- belongs to the block of its last byte.  d_occ[q * len(sizes) + b]; the hits in the order (pattern, block, back
+        descending)"""
+        _inputs_ready(d_bwt, d_index, d_ext, d_pat)
+        count, npat, prev_len = len(sizes), len(pat_lens), 0 if d_prev is None else int(d_prev.numel())
+        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
+        lens = (C.c_size_t * max(npat, 1))(*[int(m) for m in pat_lens])
+        total = C.c_uint64(0)
+        self._ck(self._lib.dk_dev_fm_seams_packed(self._h, _ptr(d_bwt), count, ns, _ptr(d_index), _ptr(d_ext), int(step),
+                                                  _ptr(d_prev) if prev_len else None, prev_len, _ptr(d_pat), npat, lens, int(max_hits),
+                                                  None if d_hits is None else _ptr(d_hits), None if d_occ is None else _ptr(d_occ), C.byref(total)))
+        return int(total.value)
 
     def dbg_dev_fm_rank(self, d_bwt, total, d_index, d_pos, d_sym, d_out):
         """d_out[q] = occurrences of d_sym[q] in d_bwt[0, d_pos[q]) by the count kernel's rank (uint32 / uint8 / uint32 device tensors)"""

@@ -1951,6 +1951,96 @@ int dk_fm_find(dk_ctx *ctx, const uint8_t *bwt, size_t n, uint32_t origin, uint3
     return DK_OK;
 }
 
+// ---- seams: the matches that straddle the borders of a pack, with the bytes carried over from the text in front ---------
+}  // extern "C"
+
+namespace {
+// the checks of both entries behind the geometry, then the plan, the uploads and the stage.  off: the blocks' offsets (count + 1).
+int fm_seams_run(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector<uint32_t> &off, const void *d_index, const void *d_ext, uint32_t step,
+                 const uint8_t *d_prev, size_t prev_len, const uint8_t *d_pat, size_t npat, const size_t *pat_len, size_t max_hits, dk_fm_seam_hit *d_hits,
+                 uint32_t *d_occ, uint64_t *total) {
+    const size_t count = off.size() - 1;
+    if (!total) return ctx->fail(DK_E_ARG, "null pointer");
+    if (max_hits > (size_t(1) << 31)) return ctx->fail(DK_E_ARG, "at most 2^31 hit records in one call, not %zu", max_hits);
+    if (npat > DK_FM_FIND_MAX_PAIRS || npat * count > DK_FM_FIND_MAX_PAIRS)
+        return ctx->fail(DK_E_ARG, "%zu patterns at %zu borders: more than DK_FM_FIND_MAX_PAIRS pairs", npat, count);
+    if (max_hits && !d_hits) return ctx->fail(DK_E_ARG, "null pointer");
+    if (max_hits && (reinterpret_cast<uintptr_t>(d_hits) & 15)) return ctx->fail(DK_E_ARG, "the hit records are not 16-byte aligned");
+    if (d_occ && (reinterpret_cast<uintptr_t>(d_occ) & 3)) return ctx->fail(DK_E_ARG, "the occurrence matrix is not 4-byte aligned");
+    if (prev_len >= DK_FM_SEAM_MAX_PATTERN) return ctx->fail(DK_E_ARG, "%zu carried bytes: fewer than DK_FM_SEAM_MAX_PATTERN can matter", prev_len);
+    if (prev_len && !d_prev) return ctx->fail(DK_E_ARG, "null pointer");
+    if (npat == 0) {
+        *total = 0;
+        return DK_OK;
+    }
+    Patterns p;
+    DK_TRY(check_patterns(ctx, npat, pat_len, nullptr, count, p));
+    if (p.longest > DK_FM_SEAM_MAX_PATTERN) return ctx->fail(DK_E_ARG, "a pattern of %zu bytes: more than DK_FM_SEAM_MAX_PATTERN", p.longest);
+    if (!d_pat && p.bytes()) return ctx->fail(DK_E_ARG, "null pointer");
+    hipStream_t st = ctx->stream;
+    if (p.longest < 2) {  // no pattern can straddle a border
+        *total = 0;
+        if (d_occ) DK_HIP(ctx, hipMemsetAsync(d_occ, 0, npat * count * sizeof(uint32_t), st));
+        DK_HIP(ctx, hipStreamSynchronize(st));
+        return DK_OK;
+    }
+    const FmSeamPlan pl = fm_seam_plan(off, prev_len, p.longest - 1);
+    if (pl.strip_len > 0xFFFFFFFFull) return ctx->fail(DK_E_ARG, "the edge strip of %zu bytes cannot be addressed", pl.strip_len);
+    // the offsets and the anchor bases in one array of 2 count + 1 words, as dk_dev_fm_extract_packed lays them out
+    std::vector<uint32_t> geo(off);
+    const std::vector<uint32_t> abase = fm_extract_bases(off, step);
+    geo.insert(geo.end(), abase.begin(), abase.end() - 1);
+    if (ws_round(4 * geo.size()) + ws_round(4 * (npat + 1)) + fm_seams_workspace(pl, npat * count) > ctx->ws_size)
+        return ctx->fail(DK_E_ARG, "%zu patterns at %zu borders do not fit the workspace (a strip of %zu bytes, 52 bytes per block, 16 per pair)", npat,
+                         count, pl.strip_len);
+    uint32_t *d_geo = ctx->ws_alloc<uint32_t>(geo.size()), *d_pat_off = ctx->ws_alloc<uint32_t>(npat + 1);
+    if (!d_geo || !d_pat_off) return DK_E_NOMEM;
+    DK_HIP(ctx, hipMemcpyAsync(d_geo, geo.data(), geo.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    int rc = ctx->hip_ok(hipMemcpyAsync(d_pat_off, p.off.data(), (npat + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st), "pattern offsets");
+    if (rc == DK_OK)
+        rc = fm_seams_device(ctx, d_bwt, d_geo, d_geo + count + 1, count, off.back(), d_index, d_ext, step, d_prev, prev_len, pl, d_pat, d_pat_off, npat,
+                             p.bytes(), max_hits, d_hits, d_occ, total);
+    const hipError_t e = hipStreamSynchronize(st);  // (also on failure: the copies above read `geo`, `p` and `pl`)
+    DK_TRY(rc);
+    DK_HIP(ctx, e);
+    return DK_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int dk_dev_fm_seams_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const void *d_index, const void *d_ext, uint32_t step,
+                           const uint8_t *d_prev, size_t prev_len, const uint8_t *d_pat, size_t npat, const size_t *pat_len, size_t max_hits,
+                           dk_fm_seam_hit *d_hits, uint32_t *d_occ, uint64_t *total) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!d_bwt || !n || !d_index || !d_ext) return ctx->fail(DK_E_ARG, "null pointer");
+    if (!fm_good_index(d_index)) return ctx->fail(DK_E_ARG, "the index is not 4-byte aligned");
+    DK_TRY(fm_extract_args(ctx, step, d_ext));
+    std::vector<uint32_t> off;
+    DK_TRY(check_pack(ctx, count, n, off));
+    Timer t;
+    DK_TRY(fm_seams_run(ctx, d_bwt, off, d_index, d_ext, step, d_prev, prev_len, d_pat, npat, pat_len, max_hits, d_hits, d_occ, total));
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_dev_fm_seams(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, const void *d_index, const void *d_ext, uint32_t step, const uint8_t *d_prev,
+                    size_t prev_len, const uint8_t *d_pat, size_t npat, const size_t *pat_len, size_t max_hits, dk_fm_seam_hit *d_hits, uint32_t *d_occ,
+                    uint64_t *total) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!d_bwt || !d_index || !d_ext) return ctx->fail(DK_E_ARG, "null pointer");
+    if (!fm_good_index(d_index)) return ctx->fail(DK_E_ARG, "the index is not 4-byte aligned");
+    DK_TRY(fm_extract_args(ctx, step, d_ext));
+    DK_TRY(check_n(ctx, n));
+    Timer t;
+    DK_TRY(fm_seams_run(ctx, d_bwt, {0u, static_cast<uint32_t>(n)}, d_index, d_ext, step, d_prev, prev_len, d_pat, npat, pat_len, max_hits, d_hits,
+                        d_occ, total));
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
 int dk_dbg_dev_fm_rank(dk_ctx *ctx, const uint8_t *d_bwt, size_t total, const void *d_index, const uint32_t *d_pos, const uint8_t *d_sym, size_t nq,
                        uint32_t *d_out) {
     DK_TRY(begin_call(ctx));

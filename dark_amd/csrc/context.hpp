@@ -49,7 +49,7 @@ enum KernelSlot : int {
     K_RADIX_SCATTER_TEXT,  // k_radix_scatter<false, true>: first pass, keys built from the text (13 B per pair)
     K_ISA_PARTITION,       // k_isa_init + k_isa_split<true> + k_isa_split<false> (inverse permutation through LDS windows)
     K_ISA_ASSEMBLE,        // k_isa_assemble
-    K_CHAIN,               // k_chain_extract + _ends + _tiles + _spine + _verdicts + _apply (pair chains; their sort is in the radix slots); k_sa_search*, k_fm_count, k_fm_locate, k_fm_extract, k_fm_find_*
+    K_CHAIN,               // k_chain_extract + _ends + _tiles + _spine + _verdicts + _apply (pair chains; their sort is in the radix slots); k_sa_search*, k_fm_count, k_fm_locate, k_fm_extract, k_fm_find_*, k_fm_seam_*
     K_PERIOD,              // k_period_first + _spine + _fill (next break of the block's dominant period, for the period round)
     K_SLOT_COUNT
 };
@@ -330,6 +330,18 @@ int fm_extract_build_device(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector
 int fm_extract_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, const uint32_t *d_abase, size_t count, size_t total, const void *d_index,
                       const void *d_ext, uint32_t step, const uint32_t *d_pos, const uint32_t *d_len, const uint32_t *d_rng_blk, size_t nrange,
                       size_t max_len, uint8_t *d_out);
+// fm_index.hip: the matches that straddle the borders of a pack whose text is preceded by prev_len bytes d_prev.
+// fm_seam_plan lays out the edge strip for W = longest pattern - 1 (host arithmetic): words = 3 per block {strip offset of the block's first byte,
+// min(n_b, W), start of the contiguous run that reaches it}, then block, start, length and strip offset of each of the nrange <= 2 count - 1
+// extract ranges.  fm_seams_device fills the strip through k_fm_extract, counts, scans and emits as fm_find_device does: d_occ[q * count + b]
+// (may be null), *total_out (host), d_hits = the first min(total, max_hits) records {pattern, block, back, 0} in the order (q, b, back
+// descending).  Takes fm_seams_workspace bytes and releases them.  Synchronises.
+struct FmSeamPlan { std::vector<uint32_t> words; size_t nrange = 0, strip_len = 0, max_len = 1; };
+FmSeamPlan fm_seam_plan(const std::vector<uint32_t> &off, size_t prev_len, size_t W);
+size_t fm_seams_workspace(const FmSeamPlan &pl, size_t npairs);
+int fm_seams_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, const uint32_t *d_abase, size_t count, size_t total, const void *d_index,
+                    const void *d_ext, uint32_t step, const uint8_t *d_prev, size_t prev_len, const FmSeamPlan &pl, const uint8_t *d_pat,
+                    const uint32_t *d_pat_off, size_t npat, size_t pat_bytes, size_t max_hits, void *d_hits, uint32_t *d_occ, uint64_t *total_out);
 // packed_dc_device: the DC arrays of every block of a packed L.  compact: block i's entries at [rb_i, rb_i + m_i) (global run order, rb on the
 // device in d_rb[0 .. count], d_rb[count] = all runs); otherwise at [off_i, off_i + m_i).  d_m / d_flags: count words, d_init: count x 256.
 int packed_dc_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, bool compact, uint32_t *d_dist,

@@ -32,6 +32,9 @@
 //                          suffix array it reads is built in bwt.hip by the inverse's kernels: fm_locate_build_device)
 // EXTRACT  k_fm_extract    a wave per (range, chunk of `step` positions): from the chunk's end, whose slot is an anchor, at most min(step, n_b) - 1
 //                          of the same LF steps backwards, a text byte per step (section 4.15; anchors built in bwt.hip: fm_extract_build_device)
+// SEAMS    k_fm_seam_count a wave per pair (pattern, block): the candidates `back` of the border in front of the block, 64 at a time, compared
+//                          against an edge strip that k_fm_extract filled (section 4.17); k_fm_find_scan_a/b/c; k_fm_seam_emit the same
+//                          compare again, every hit lane stores its record at the pair's offset plus its rank in the ballot
 // FIND     k_fm_find_count a wave per pair (pattern, block) of the grid npat x count: the count's search, lo and occ of the pair (section 4.16)
 //          k_fm_find_scan_a/b/c  the exclusive scan of occ over the pairs in 64-bit sums, the grand total to the mailbox
 //          k_fm_find_locate a wave per hit: the pair from the offsets by a 64-ary search, then the walk of k_fm_locate; one 16-byte record
@@ -463,6 +466,7 @@ __global__ __launch_bounds__(64 * FM_WAVES) void k_fm_find_locate(FmFindLocArgs 
 struct FmExtArgs {
     const uint8_t *L; const uint32_t *off, *abase, *blocks, *base, *cp, *anchors, *pos, *len, *rng_blk;
     uint32_t nrange, max_len, per, total, step_shift; uint8_t *out;
+    const uint32_t *out_off;  // null: row q starts at out + q max_len.  Otherwise at out + out_off[q] (the seams' ragged strip, section 4.17)
 };
 // A wave per item (q, i), i < per = ceil(max_len / step) + 1: chunk k = pos[q] / step + i of the range's block, [k step, e) with e = min((k + 1)
 // step, n_b), where it meets the range [pos, pos + got).  From the slot of suffix e -- anchor k + 1, or the origin when e = n_b -- L[x] = T[e - 1],
@@ -471,7 +475,8 @@ struct FmExtArgs {
 // in lane j mod 64; after 64 steps and at the chunk's end every lane stores its own where it lies below pos + got: byte stores from consecutive
 // lanes to consecutive addresses, so a row of any alignment is served.  The rows were zeroed by a memset in front of the kernel.
 // Containment: the anchor index is clamped to the block's anchors, every slot to [0, n_b), `last` to a byte, at most min(step, n_b) steps per item; a store goes
-// to out[q max_len + p - pos] with pos <= p < pos + got <= pos + max_len, and what is stored is a byte of block b's L.
+// to out[q max_len + p - pos] (out[out_off[q] + p - pos] for the seams' strip, whose planner gives every range len[q] bytes of its own) with
+// pos <= p < pos + got <= pos + min(len[q], max_len), and what is stored is a byte of block b's L.
 __global__ __launch_bounds__(64 * FM_WAVES) void k_fm_extract(FmExtArgs a) {
     const uint8_t *__restrict__ L = a.L;
     const uint32_t *__restrict__ off = a.off, *__restrict__ cp = a.cp, *__restrict__ rng_blk = a.rng_blk;
@@ -502,7 +507,7 @@ __global__ __launch_bounds__(64 * FM_WAVES) void k_fm_extract(FmExtArgs a) {
             x = a.anchors[(a.abase ? a.abase[b] : 0u) + idx];
         }
         x = x < nb ? x : nb - 1u;
-        uint8_t *row_out = a.out + static_cast<size_t>(q) * a.max_len;
+        uint8_t *row_out = a.out + (a.out_off ? static_cast<size_t>(a.out_off[q]) : static_cast<size_t>(q) * a.max_len);
         uint32_t mine = 0;
         for (uint32_t j = 0; j < steps; ++j) {
             const uint32_t g = s + x, sl = ((g >> FM_SHIFT) << FM_SHIFT) + 16u * lane;
@@ -526,6 +531,81 @@ __global__ __launch_bounds__(64 * FM_WAVES) void k_fm_extract(FmExtArgs a) {
             } else {
                 x = fm_lf(cp, base, origin, last, nb, x, g, sl, c, v0, v1);
             }
+        }
+    }
+}
+
+// ---- seams: the matches that straddle block borders ---------------------------------------------------------------------
+// The strip: prev, then of every block its whole text (n_b <= 2 W) or its first W and its last W bytes, W = longest pattern - 1.  geo[3 b ..]:
+// sb = the strip offset of block b's first byte, head = min(n_b, W), rs = where the contiguous run that reaches sb starts.  A seam hit of
+// pattern q (m bytes) in block b with `back` bytes in front of the block stands at strip[sb - back, sb - back + m): back <= min(m - 1, sb - rs)
+// keeps its front inside the run, m - back <= head keeps its last byte inside the block.  The candidates of a pair are therefore
+// back = hi, hi - 1, ..., lo with hi = min(m - 1, sb - rs) and lo = max(1, m - head): file order of the starts.
+struct FmSeamArgs {
+    const uint8_t *strip; const uint32_t *geo; const uint8_t *pat; const uint32_t *pat_off; uint32_t npat, count, strip_len;
+    uint32_t *occ, *out_occ; const uint64_t *offset; uint32_t nhits; uint4 *hits;
+};
+struct FmSeamPair { uint32_t q, b, m, sb, hi, ncand; const uint8_t *p; };
+// the pair's candidates, every strip offset clamped to the strip: ncand = 0 where nothing can match
+__device__ __forceinline__ FmSeamPair fm_seam_pair(const FmSeamArgs &a, uint64_t pair) {
+    FmSeamPair r;
+    r.q = static_cast<uint32_t>(pair / a.count);
+    r.b = static_cast<uint32_t>(pair - static_cast<uint64_t>(r.q) * a.count);
+    const uint32_t po = a.pat_off[r.q];
+    r.m = a.pat_off[r.q + 1] - po;
+    r.p = a.pat + po;
+    const uint32_t sb = a.geo[3 * static_cast<size_t>(r.b)], head = a.geo[3 * static_cast<size_t>(r.b) + 1], rs = a.geo[3 * static_cast<size_t>(r.b) + 2];
+    r.sb = sb < a.strip_len ? sb : a.strip_len;
+    const uint32_t reach = rs < r.sb ? r.sb - rs : 0u, room = a.strip_len - r.sb, fit = head < room ? head : room;
+    r.hi = r.m < 2u ? 0u : (r.m - 1u < reach ? r.m - 1u : reach);
+    const uint32_t lo = r.m > fit ? r.m - fit : 1u;
+    r.ncand = r.hi >= lo ? r.hi - lo + 1u : 0u;
+    return r;
+}
+// does the pattern stand at s[0, m)?  Eight bytes at a time (neither side is aligned: every lane's candidate starts one byte on), then the rest.
+__device__ __forceinline__ bool fm_seam_equal(const uint8_t *__restrict__ s, const uint8_t *__restrict__ p, uint32_t m) {
+    uint32_t j = 0;
+    for (; j + 8u <= m; j += 8u)
+        if (*(gptr8)(s + j) != *(gptr8)(p + j)) return false;
+    for (; j < m; ++j)
+        if (s[j] != p[j]) return false;
+    return true;
+}
+// round r of a pair: lane l takes candidate k = 64 r + l, back = hi - k; the ballot of the hits.  (hi - k >= lo >= 1 and sb - back + m <= strip_len
+// by fm_seam_pair.)
+__device__ __forceinline__ uint64_t fm_seam_round(const uint8_t *__restrict__ strip, const FmSeamPair &r, uint32_t round, uint32_t lane, uint32_t &back) {
+    const uint32_t k = round * 64u + lane;
+    back = k < r.ncand ? r.hi - k : 0u;
+    return __ballot(k < r.ncand && fm_seam_equal(strip + (r.sb - back), r.p, r.m));
+}
+__global__ __launch_bounds__(64 * FM_WAVES) void k_fm_seam_count(FmSeamArgs a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * FM_WAVES, npairs = static_cast<uint64_t>(a.npat) * a.count;
+    for (uint64_t pair = static_cast<uint64_t>(blockIdx.x) * FM_WAVES + (threadIdx.x >> 6); pair < npairs; pair += nwaves) {
+        const FmSeamPair r = fm_seam_pair(a, pair);
+        uint32_t occ = 0, back;
+        for (uint32_t round = 0; round * 64u < r.ncand; ++round) occ += static_cast<uint32_t>(__popcll(fm_seam_round(a.strip, r, round, lane, back)));
+        if (lane == 0) {
+            a.occ[pair] = occ;
+            if (a.out_occ) a.out_occ[pair] = occ;
+        }
+    }
+}
+// A wave per pair again, not per hit: a pair's hits come out of one more pass over its candidates, where a wave per hit would repeat that pass
+// occ times (a^m on a^n has occ = m - 1).  Hit lanes store {pattern, block, back, 0} at offset[pair] + their rank, below nhits only.
+__global__ __launch_bounds__(64 * FM_WAVES) void k_fm_seam_emit(FmSeamArgs a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * FM_WAVES, npairs = static_cast<uint64_t>(a.npat) * a.count;
+    for (uint64_t pair = static_cast<uint64_t>(blockIdx.x) * FM_WAVES + (threadIdx.x >> 6); pair < npairs; pair += nwaves) {
+        uint64_t at = a.offset[pair];
+        if (a.occ[pair] == 0 || at >= a.nhits) continue;
+        const FmSeamPair r = fm_seam_pair(a, pair);
+        for (uint32_t round = 0; round * 64u < r.ncand && at < a.nhits; ++round) {
+            uint32_t back;
+            const uint64_t hit = fm_seam_round(a.strip, r, round, lane, back);
+            const uint64_t idx = at + static_cast<uint32_t>(__popcll(hit & ((1ull << lane) - 1ull)));
+            if (((hit >> lane) & 1ull) && idx < a.nhits) a.hits[idx] = make_uint4(r.q, r.b, back, 0u);
+            at += static_cast<uint32_t>(__popcll(hit));
         }
     }
 }
@@ -687,6 +767,102 @@ int fm_extract_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, 
         k_fm_extract<<<dim3(grid), dim3(64 * FM_WAVES), 0, ctx->stream>>>(a);
     }
     DK_HIP(ctx, hipGetLastError());
+    return DK_OK;
+}
+
+FmSeamPlan fm_seam_plan(const std::vector<uint32_t> &off, size_t prev_len, size_t W) {
+    FmSeamPlan pl;
+    const size_t count = off.size() - 1;
+    std::vector<uint32_t> geo(3 * count), blk, pos, len, out;
+    size_t at = prev_len, run = 0;
+    pl.max_len = 1;
+    auto range = [&](size_t b, size_t p, size_t l) {
+        blk.push_back(static_cast<uint32_t>(b)), pos.push_back(static_cast<uint32_t>(p)), len.push_back(static_cast<uint32_t>(l));
+        out.push_back(static_cast<uint32_t>(at));
+        pl.max_len = std::max(pl.max_len, l);
+        at += l;
+    };
+    for (size_t b = 0; b < count; ++b) {
+        const size_t nb = off[b + 1] - off[b];
+        geo[3 * b] = static_cast<uint32_t>(at), geo[3 * b + 1] = static_cast<uint32_t>(std::min(nb, W)), geo[3 * b + 2] = static_cast<uint32_t>(run);
+        if (b + 1 == count) {
+            range(b, 0, std::min(nb, W));  // nothing follows the last block: its head is all a match can need
+        } else if (nb <= 2 * W) {
+            range(b, 0, nb);
+        } else {
+            range(b, 0, W);
+            run = at;  // the run breaks here: the block's middle is not in the strip
+            range(b, nb - W, W);
+        }
+    }
+    pl.nrange = blk.size();
+    pl.strip_len = at;
+    pl.words = std::move(geo);
+    for (const auto *v : {&blk, &pos, &len, &out}) pl.words.insert(pl.words.end(), v->begin(), v->end());
+    return pl;
+}
+
+size_t fm_seams_workspace(const FmSeamPlan &pl, size_t npairs) {
+    auto r = [](size_t b) { return (b + 255) & ~size_t(255); };
+    return r(std::max<size_t>(pl.strip_len, 1)) + r(4 * pl.words.size()) + r(4 * npairs) + r(8 * npairs) + r(8 * FM_MAX_CHUNKS);
+}
+
+int fm_seams_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, const uint32_t *d_abase, size_t count, size_t total, const void *d_index,
+                    const void *d_ext, uint32_t step, const uint8_t *d_prev, size_t prev_len, const FmSeamPlan &pl, const uint8_t *d_pat,
+                    const uint32_t *d_pat_off, size_t npat, size_t pat_bytes, size_t max_hits, void *d_hits, uint32_t *d_occ, uint64_t *total_out) {
+    hipStream_t st = ctx->stream;
+    const FmIndex ix = fm_carve(const_cast<void *>(d_index), total, count);
+    const size_t npairs = npat * count, rows = div_up(npairs, FM_FIND_ROW), rpc = div_up(rows, FM_MAX_CHUNKS), nchunks = div_up(rows, rpc);
+    const size_t mark = ctx->ws_mark(), nr = pl.nrange;
+    uint8_t *strip = ctx->ws_alloc<uint8_t>(std::max<size_t>(pl.strip_len, 1));
+    uint32_t *d_plan = ctx->ws_alloc<uint32_t>(pl.words.size()), *d_cnt = ctx->ws_alloc<uint32_t>(npairs);
+    uint64_t *d_offset = ctx->ws_alloc<uint64_t>(npairs), *chunk_sum = ctx->ws_alloc<uint64_t>(FM_MAX_CHUNKS);
+    if (!strip || !d_plan || !d_cnt || !d_offset || !chunk_sum) return DK_E_NOMEM;
+    const uint32_t *d_geo = d_plan, *d_blk = d_plan + 3 * count, *d_pos = d_blk + nr, *d_len = d_pos + nr, *d_out_off = d_len + nr;
+    const uint32_t P = static_cast<uint32_t>(npairs), R = static_cast<uint32_t>(rpc);
+    // (pl outlives the copy: mail_read below synchronises, and so does every caller on failure)
+    DK_HIP(ctx, hipMemcpyAsync(d_plan, pl.words.data(), pl.words.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    DK_HIP(ctx, hipMemsetAsync(strip, 0, std::max<size_t>(pl.strip_len, 1), st));
+    if (prev_len) DK_HIP(ctx, hipMemcpyAsync(strip, d_prev, prev_len, hipMemcpyDeviceToDevice, st));
+    {
+        const size_t per = div_up(pl.max_len, step) + 1, nitems = nr * per;
+        const FmExtArgs e{d_bwt, d_off, d_abase, ix.blocks, ix.base, ix.cp, static_cast<const uint32_t *>(d_ext) + FM_EXT_HEADER, d_pos, d_len, d_blk,
+                          static_cast<uint32_t>(nr), static_cast<uint32_t>(pl.max_len), static_cast<uint32_t>(per), static_cast<uint32_t>(total),
+                          static_cast<uint32_t>(ceil_log2_u64(step)), strip, d_out_off};
+        const unsigned grid = static_cast<unsigned>(std::min<size_t>(div_up(nitems, FM_WAVES), 1u << 20));
+        // extract's traffic for the strip's bytes: per byte, and per step / 2 bytes walked in vain per range, a row of L and a checkpoint word
+        LaunchScope ls(ctx, K_CHAIN, 16.0 * nr + 2.0 * pl.strip_len + (static_cast<double>(pl.strip_len) + 0.5 * step * nr) * (FM_BLOCK + 64));
+        k_fm_extract<<<dim3(grid), dim3(64 * FM_WAVES), 0, st>>>(e);
+    }
+    FmSeamArgs a{strip, d_geo, d_pat, d_pat_off, static_cast<uint32_t>(npat), static_cast<uint32_t>(count), static_cast<uint32_t>(pl.strip_len),
+                 d_cnt, d_occ, d_offset, 0u, static_cast<uint4 *>(d_hits)};
+    const unsigned grid = static_cast<unsigned>(std::min<size_t>(div_up(npairs, FM_WAVES), 1u << 20));
+    {
+        // per pair its three words, the pattern's first word per candidate (a mismatch ends a compare; pat_bytes / npat candidates at most) and occ
+        LaunchScope ls(ctx, K_CHAIN, 24.0 * npairs + 16.0 * static_cast<double>(count) * pat_bytes);
+        k_fm_seam_count<<<dim3(grid), dim3(64 * FM_WAVES), 0, st>>>(a);
+    }
+    {
+        LaunchScope ls(ctx, K_CHAIN, 16.0 * npairs);  // occ read twice, the offsets written
+        k_fm_find_scan_a<<<dim3(static_cast<unsigned>(nchunks)), dim3(256), 0, st>>>(d_cnt, P, R, chunk_sum);
+        k_fm_find_scan_b<<<dim3(1), dim3(256), 0, st>>>(chunk_sum, static_cast<uint32_t>(nchunks), &ctx->d_mail->fm_find.total);
+        k_fm_find_scan_c<<<dim3(static_cast<unsigned>(nchunks)), dim3(256), 0, st>>>(d_cnt, P, R, chunk_sum, d_offset);
+    }
+    DK_HIP(ctx, hipGetLastError());
+    DK_TRY(ctx->mail_read(&ctx->h_mail->fm_find.total));
+    const uint64_t all = ctx->h_mail->fm_find.total;
+    *total_out = all;
+    a.nhits = static_cast<uint32_t>(std::min<uint64_t>(all, max_hits));
+    if (a.nhits) {
+        {
+            // per pair occ and its offset; per hit the pair's compare again and the record
+            LaunchScope ls(ctx, K_CHAIN, 12.0 * npairs + a.nhits * 48.0);
+            k_fm_seam_emit<<<dim3(grid), dim3(64 * FM_WAVES), 0, st>>>(a);
+        }
+        DK_HIP(ctx, hipGetLastError());
+        DK_HIP(ctx, hipStreamSynchronize(st));
+    }
+    ctx->ws_release(mark);
     return DK_OK;
 }
 

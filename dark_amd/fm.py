@@ -22,7 +22,9 @@ class Index:
     extract(positions, length[, blocks]) -> a list of bytes, the text at [position, position + length) cut at the block's end; text([block]) ->
     the whole block; snippets(patterns, before, after[, blocks], max_hits=16) -> per pattern a list of (position, bytes around the hit).
     find(patterns, max_hits=65536) -> (occ, hits, total): every pattern in EVERY block as one compact list of (pattern, block, position, slot)
-    records (section 4.16); grep(patterns, before, after) -> (pattern, block, position, bytes around the hit) per record."""
+    records (section 4.16); grep(patterns, before, after) -> (pattern, block, position, bytes around the hit) per record.
+    seams(patterns, prev=b"", max_hits=65536) -> (occ, hits, total): the matches find cannot see, those that straddle a border between two
+    blocks or between `prev` and the first block (section 4.17); tail(nbytes) -> the last bytes of the whole text, the `prev` of what follows."""
 
     def __init__(self, ctx, d_bwt, sizes, origins, locate_step=None, extract_step=None):
         import torch
@@ -239,6 +241,84 @@ class Index:
         where = None if len(self.sizes) == 1 else [int(b) for b in blk]
         rows = self._extract_dev(d_start, d_len, len(hits), where, max_len).cpu().numpy().reshape(len(hits), -1)
         return [(int(hits["pattern"][i]), int(blk[i]), int(pos[i]), bytes(rows[i, :got[i]])) for i in range(len(hits))]
+
+    def seams(self, patterns, prev=b"", max_hits=65536):
+        """the matches that straddle block borders (section 4.17) -> (occ, hits, total).  `prev` and the blocks are the consecutive pieces of one
+        text; a seam hit has its first and its last byte in different pieces and belongs to the block of its last byte.  occ: a uint32 array
+        len(patterns) x blocks; hits: a structured array (pattern, block, back, reserved) of the first min(total, max_hits) in the order (pattern,
+        block, back descending), back = the match's bytes in front of that block.  Only the last longest - 1 bytes of `prev` can matter and only
+        they are uploaded.  find(...) and seams(...) together are every occurrence in prev + text that does not lie inside prev, each once."""
+        import torch
+        from .context import FM_SEAM_HIT_DTYPE
+        if self.d_ext is None:
+            raise DarkError(_lib.DK_E_ARG, "the index was built without an extract structure (extract_step=None)")
+        npat, count, max_hits = len(patterns), len(self.sizes), int(max_hits)
+        if npat == 0:
+            return np.zeros((0, count), np.uint32), np.zeros(0, FM_SEAM_HIT_DTYPE), 0
+        pat, lens, npat = _pack_patterns(patterns)
+        dev = self.d_bwt.device
+        keep = max(max(list(lens)[:npat]) - 1, 0)
+        prev = as_u8(prev)
+        prev = prev[len(prev) - min(len(prev), keep):]
+        d_prev = torch.from_numpy(prev.copy()).to(dev) if len(prev) else None
+        d_pat = torch.from_numpy(pat).to(dev)
+        d_occ = torch.empty(npat * count, dtype=torch.int32, device=dev)
+        d_hits = torch.empty(4 * max_hits, dtype=torch.int32, device=dev) if max_hits else None  # (torch allocations are 256-byte aligned)
+        if count == 1:
+            total = self._ctx.dev_fm_seams(self.d_bwt, self.total, self.d_index, self.d_ext, self.extract_step, d_prev, d_pat, list(lens)[:npat],
+                                           max_hits, d_hits, d_occ)
+        else:
+            total = self._ctx.dev_fm_seams_packed(self.d_bwt, self.sizes, self.d_index, self.d_ext, self.extract_step, d_prev, d_pat,
+                                                  list(lens)[:npat], max_hits, d_hits, d_occ)
+        got = min(total, max_hits)
+        hits = d_hits[:4 * got].cpu().numpy().view(FM_SEAM_HIT_DTYPE) if got else np.zeros(0, FM_SEAM_HIT_DTYPE)
+        return d_occ.cpu().numpy().view(np.uint32).reshape(npat, count), hits, total
+
+    def _pieces_before(self, block, nbytes):
+        """(block, start, length) of the pieces that make the last min(nbytes, bytes in front) bytes in front of block `block`, in text order"""
+        want, pieces = int(nbytes), []
+        for b in range(block - 1, -1, -1):
+            if want <= 0:
+                break
+            take = min(self.sizes[b], want)
+            pieces.append((b, self.sizes[b] - take, take))
+            want -= take
+        return pieces[::-1]
+
+    def _extract_pieces(self, groups):
+        """the bytes of every group of (block, start, length) pieces, joined per group; ONE extract call for all of them"""
+        import torch
+        pieces = [p for g in groups for p in g]
+        if not pieces:
+            return [b"" for _ in groups]
+        dev = self.d_bwt.device
+        d_pos = torch.tensor([p for _, p, _ in pieces], dtype=torch.int64).to(torch.int32).to(dev)
+        d_len = torch.tensor([n for _, _, n in pieces], dtype=torch.int64).to(torch.int32).to(dev)
+        max_len = max(n for _, _, n in pieces)
+        where = None if len(self.sizes) == 1 else [b for b, _, _ in pieces]
+        rows = self._extract_dev(d_pos, d_len, len(pieces), where, max_len).cpu().numpy().reshape(len(pieces), -1)
+        out, i = [], 0
+        for g in groups:
+            out.append(b"".join(bytes(rows[i + j, :g[j][2]]) for j in range(len(g))))
+            i += len(g)
+        return out
+
+    def tail(self, nbytes):
+        """the last min(nbytes, total) bytes of the pack's concatenated text, across block borders, in one extract call"""
+        if self.d_ext is None:
+            raise DarkError(_lib.DK_E_ARG, "the index was built without an extract structure (extract_step=None)")
+        return self._extract_pieces([self._pieces_before(len(self.sizes), nbytes)])[0]
+
+    def edges(self, blocks, nfront, nhead):
+        """per block of `blocks` (front, head): the last min(nfront, bytes in front) bytes of the pack's text in front of the block, across block
+        borders, and the block's first min(nhead, n_b) bytes -- the text around the border a seam hit crosses last.  One extract call."""
+        if self.d_ext is None:
+            raise DarkError(_lib.DK_E_ARG, "the index was built without an extract structure (extract_step=None)")
+        groups = []
+        for b in blocks:
+            groups += [self._pieces_before(b, nfront), [(b, 0, min(self.sizes[b], int(nhead)))]]
+        got = self._extract_pieces(groups)
+        return [(got[2 * i], got[2 * i + 1]) for i in range(len(blocks))]
 
     def occurrences(self, patterns, blocks=None):
         lo, hi = self.count(patterns, blocks)

@@ -272,7 +272,7 @@ namespace fm {
 class Index {
 public:
     Index(std::vector<uint8_t> bwt, size_t origin, int device = 0, uint32_t locate_step = 0, uint32_t extract_step = 0)
-        : ctx_(bwt.size(), device, DK_CTX_DECODER), bwt_(std::move(bwt)), origin_(origin), step_(locate_step), ext_step_(extract_step) {
+        : ctx_(bwt.size(), device, DK_CTX_DECODER), bwt_(std::move(bwt)), origin_(origin), step_(locate_step), ext_step_(extract_step), device_(device) {
         if (origin_ >= bwt_.size()) throw Error(DK_E_ARG, "assertion failed: origin < bwt.len()");
         if (step_ && dk_fm_locate_bytes(bwt_.size(), 1, step_) == 0) throw Error(DK_E_ARG, "locate_step is no power of two in [1, 4096]");
         if (ext_step_ && dk_fm_extract_bytes(bwt_.size(), 1, ext_step_) == 0) throw Error(DK_E_ARG, "extract_step is no power of two in [1, 4096]");
@@ -365,12 +365,62 @@ public:
         out.hits.resize(static_cast<size_t>(std::min<uint64_t>(out.total, max_hits)));
         return out;
     }
+#ifdef DARK_WITH_HIP
+    // The matches of `patterns` in prev + text that start in prev and end in the text (dk_dev_fm_seams, section 4.17) -- for a single block the
+    // only border there is; with find() they are every occurrence in prev + text that does not lie inside prev.  occ[q] = their number, total
+    // the sum, hits the first min(total, max_hits) records {pattern, block = 0, back, 0} in the order (pattern, back descending), back = the
+    // match's bytes in front of the text.  Needs an extract structure (extract_step).  The entry has no host-memory form, so this one holds
+    // L, the index and the structure in device memory of its own for the call: it is compiled only where DARK_WITH_HIP is defined in front of
+    // this header (the HIP runtime's headers on the include path, amdhip64 on the link line).
+    struct Seams { std::vector<uint32_t> occ; std::vector<dk_fm_seam_hit> hits; uint64_t total = 0; };
+    Seams seams(const std::vector<std::vector<uint8_t>> &patterns, const std::vector<uint8_t> &prev = {}, size_t max_hits = 65536) {
+        if (!ext_step_) throw Error(DK_E_ARG, "the index was made without an extract structure (extract_step = 0)");
+        struct Dev {  // device bytes, at least one
+            void *p = nullptr;
+            explicit Dev(size_t bytes) { if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) throw Error(DK_E_NOMEM, "hipMalloc failed"); }
+            ~Dev() { (void)hipFree(p); }
+            Dev(const Dev &) = delete;
+            Dev &operator=(const Dev &) = delete;
+            void put(const void *src, size_t bytes) { if (bytes && hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) != hipSuccess) throw Error(DK_E_HIP, "upload failed"); }
+            void get(void *dst, size_t bytes) { if (bytes && hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost) != hipSuccess) throw Error(DK_E_HIP, "download failed"); }
+        };
+        if (hipSetDevice(device_) != hipSuccess) throw Error(DK_E_NODEVICE, "hipSetDevice failed");
+        std::vector<size_t> lens;
+        std::vector<uint8_t> bytes;
+        size_t longest = 1;
+        for (const auto &p : patterns) {
+            lens.push_back(p.size());
+            bytes.insert(bytes.end(), p.begin(), p.end());
+            longest = std::max(longest, p.size());
+        }
+        const size_t n = bwt_.size(), keep = std::min(prev.size(), longest - 1);  // only the last longest - 1 bytes of prev can matter
+        Dev d_bwt(n), d_index(dk_fm_index_bytes(n, 1)), d_ext(dk_fm_extract_bytes(n, 1, ext_step_)), d_prev(keep), d_pat(bytes.size());
+        Dev d_hits(max_hits * sizeof(dk_fm_seam_hit)), d_occ(patterns.size() * sizeof(uint32_t));
+        d_bwt.put(bwt_.data(), n);
+        d_prev.put(prev.data() + (prev.size() - keep), keep);
+        d_pat.put(bytes.data(), bytes.size());
+        Seams out;
+        int rc = dk_dev_fm_build(ctx_.get(), static_cast<const uint8_t *>(d_bwt.p), n, static_cast<uint32_t>(origin_), d_index.p);
+        if (rc == DK_OK) rc = dk_dev_fm_extract_build(ctx_.get(), static_cast<const uint8_t *>(d_bwt.p), n, static_cast<uint32_t>(origin_), ext_step_, d_ext.p);
+        if (rc == DK_OK)
+            rc = dk_dev_fm_seams(ctx_.get(), static_cast<const uint8_t *>(d_bwt.p), n, d_index.p, d_ext.p, ext_step_, static_cast<const uint8_t *>(d_prev.p), keep,
+                                 static_cast<const uint8_t *>(d_pat.p), patterns.size(), lens.data(), max_hits, static_cast<dk_fm_seam_hit *>(d_hits.p),
+                                 static_cast<uint32_t *>(d_occ.p), &out.total);
+        if (rc != DK_OK) throw Error(rc, ctx_.error());
+        out.occ.resize(patterns.size());
+        out.hits.resize(static_cast<size_t>(std::min<uint64_t>(out.total, max_hits)));
+        d_occ.get(out.occ.data(), out.occ.size() * sizeof(uint32_t));
+        d_hits.get(out.hits.data(), out.hits.size() * sizeof(dk_fm_seam_hit));
+        return out;
+    }
+#endif
     detail::Ctx &context() { return ctx_; }  // context().purpose() == DK_CTX_DECODER
 private:
     detail::Ctx ctx_;
     std::vector<uint8_t> bwt_;
     size_t origin_;
     uint32_t step_, ext_step_;
+    int device_;
 };
 }  // namespace fm
 

@@ -367,6 +367,38 @@ int dk_dev_fm_find_packed(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t count, c
  * and of occ (npat words; may be null).  DK_E_ARG when L, the structures, the batch and the records do not fit the context's workspace. */
 int dk_fm_find(dk_ctx *any_ctx, const uint8_t *bwt, size_t n, uint32_t origin, uint32_t step, const uint8_t *pat, size_t npat,
                const size_t *pat_len, size_t max_hits, dk_fm_hit *hits, uint32_t *occ, uint64_t *total);
+/* ---- FM-index: seams.  The matches that straddle block borders (csrc/fm_index.hip) ----
+ * dk_dev_fm_find* search every block on its own.  Here a pack's blocks 0 .. count - 1, in pack order and preceded by prev_len >= 0 carried
+ * bytes d_prev (device; piece -1), are the consecutive PIECES of one text.  A SEAM HIT of pattern q (m bytes) is an occurrence in that
+ * concatenation whose first and last byte lie in different pieces.  It belongs to the block b that holds its LAST byte, and `back` in
+ * [1, m - 1] is the number of its bytes in front of block b's first byte; they may span several tiny blocks and reach into prev.  Patterns of
+ * 0 and 1 bytes have no seam hits, and an occurrence wholly inside one piece (prev included) is none: find reports those.  For any cutting
+ * of a file into blocks and packs, the hits of find and the seam hits with prev = the last bytes in front of the pack are together exactly
+ * the occurrences in the file, each once.
+ *   d_occ[q * count + b] (device, may be null) = seam hits of q that belong to b;  *total (HOST, 64 bits) = their sum
+ *   d_hits (device, 16-byte aligned) receives the first min(*total, max_hits) records {q, b, back, 0} in the order (q, b, back descending),
+ *   the file order of the starts inside a pair; nothing behind them is written.  max_hits == 0: d_hits may be null, counts only.
+ * The order comes from an exclusive scan of occ over the pairs; no global atomics, so two calls give the same bytes.
+ * dk_dev_fm_seams is the single-block form: its only border is the one against prev.  There is NO host-memory form: a single block has no
+ * inner border, and find has no packed host form either.  Contexts of either purpose serve both.  `step` is the extract structure's.
+ * DK_E_ARG for what dk_dev_fm_find* and dk_dev_fm_extract* refuse (null or misaligned structures, a bad step, a bad pack), a pattern longer
+ * than DK_FM_SEAM_MAX_PATTERN, prev_len >= DK_FM_SEAM_MAX_PATTERN (only the last longest - 1 carried bytes can matter), prev_len > 0 with a
+ * null d_prev, npat x count > DK_FM_FIND_MAX_PAIRS, max_hits > 2^31, a d_hits that is not 16-byte aligned, a null `total`, and for a
+ * workspace that cannot hold the edge strip (at most prev_len + min(total, 2 (longest - 1) count) bytes), 52 bytes per block, the pattern
+ * offsets and 16 bytes per pair.  dk_workspace_bytes does not grow for it.  DK_FM_SEAM_MAX_PATTERN is a reasoned bound, not a measured one:
+ * the window at a border stays a few KiB and the quadratic worst case (a periodic pattern on a periodic text) stays bounded.
+ * Both structures are TRUSTED and contained as find and extract are: the strip's layout comes from the sizes, never from the structures;
+ * every strip index is clamped to the strip; for any bytes in L, the index, d_ext and d_prev every record written has pattern < npat,
+ * block < count and 1 <= back < m, and nothing outside the named buffers is touched. */
+typedef struct dk_fm_seam_hit { uint32_t pattern, block, back, reserved /* 0 */; } dk_fm_seam_hit; /* 16 bytes */
+#define DK_FM_SEAM_MAX_PATTERN 4096u
+int dk_dev_fm_seams(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t n, const void *d_index, const void *d_ext, uint32_t step,
+                    const uint8_t *d_prev, size_t prev_len, const uint8_t *d_pat, size_t npat, const size_t *pat_len /* host */, size_t max_hits,
+                    dk_fm_seam_hit *d_hits, uint32_t *d_occ /* may be NULL */, uint64_t *total /* host */);
+int dk_dev_fm_seams_packed(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const void *d_index, const void *d_ext,
+                           uint32_t step, const uint8_t *d_prev, size_t prev_len, const uint8_t *d_pat, size_t npat,
+                           const size_t *pat_len /* host */, size_t max_hits, dk_fm_seam_hit *d_hits, uint32_t *d_occ /* may be NULL */,
+                           uint64_t *total /* host */);
 /* for the tests: d_out[q] = occurrences of d_sym[q] in d_bwt[0, min(d_pos[q], total)), computed by the count kernel's rank (all device memory) */
 int dk_dbg_dev_fm_rank(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t total, const void *d_index,
                        const uint32_t *d_pos, const uint8_t *d_sym, size_t nq, uint32_t *d_out);

@@ -45,8 +45,23 @@ def _pack_patterns(patterns):
     pat = np.concatenate(keep) if npat else np.zeros(0, dtype=np.uint8)
     if len(pat) == 0:
         pat = np.zeros(1, dtype=np.uint8)  # (never read: every pattern is empty)
-    lens = (C.c_size_t * max(npat, 1))(*[len(p) for p in keep])
-    return pat, lens, npat
+    return pat, _sizes([len(p) for p in keep]), npat
+
+
+def _sizes(xs):
+    """lengths of blocks or patterns -> size_t[], of one element at least (an empty list still needs an address)"""
+    return (C.c_size_t * max(len(xs), 1))(*[int(n) for n in xs])
+
+
+def _u32s(xs):
+    """origins or block numbers -> a uint32 array, of one element at least"""
+    return np.array(xs, dtype=np.int64).astype(np.uint32) if len(xs) else np.zeros(1, np.uint32)
+
+
+def _same_length(xs, what, count, of):
+    """one of `xs` for every one of the `count` things they belong to"""
+    if len(xs) != count:
+        raise DarkError(_lib.DK_E_ARG, "%d %s for %d %s" % (len(xs), what, count, of))
 
 
 def model_id(m):
@@ -170,7 +185,7 @@ class Context:
         """the suffix array of every block (entries local to the block), all of them from one segmented device pass"""
         keep = [as_u8(b) for b in blocks]
         count = len(keep)
-        ns = (C.c_size_t * max(count, 1))(*[len(b) for b in keep])
+        ns = _sizes([len(b) for b in keep])
         t = np.concatenate(keep) if count else np.zeros(0, dtype=np.uint8)
         sa = np.empty(len(t), dtype=np.uint32)
         self._ck(self._lib.dk_suffix_array_packed(self._h, _ptr(t), count, ns, _ptr(sa)))
@@ -189,7 +204,7 @@ class Context:
         """(suffix array, LCP array) of every block, all of them from one segmented device pass (dk_suffix_array_packed_lcp)"""
         keep = [as_u8(b) for b in blocks]
         count = len(keep)
-        ns = (C.c_size_t * max(count, 1))(*[len(b) for b in keep])
+        ns = _sizes([len(b) for b in keep])
         t = np.concatenate(keep) if count else np.zeros(0, dtype=np.uint8)
         sa = np.empty(len(t), dtype=np.uint32)
         lcp = np.empty(len(t), dtype=np.uint32)
@@ -202,8 +217,7 @@ class Context:
         "bad_order"), where = the lowest slot / text position at fault (len(data) with "ok") (dk_sa_check)"""
         t = as_u8(data)
         sa = np.ascontiguousarray(sa, dtype=np.uint32)
-        if len(sa) != len(t):
-            raise DarkError(_lib.DK_E_ARG, "%d entries for %d bytes" % (len(sa), len(t)))
+        _same_length(sa, "entries", len(t), "bytes")
         verdict, where = C.c_uint32(0), C.c_uint32(0)
         self._ck(self._lib.dk_sa_check(self._h, _ptr(t), len(t), _ptr(sa), C.byref(verdict), C.byref(where)))
         return _lib.SA_VERDICTS[verdict.value], int(where.value)
@@ -213,8 +227,7 @@ class Context:
         slot of a pattern that does not occur (dk_sa_search).  The suffix array is trusted: sa_check verifies one."""
         t = as_u8(data)
         sa = np.ascontiguousarray(sa, dtype=np.uint32)
-        if len(sa) != len(t):
-            raise DarkError(_lib.DK_E_ARG, "%d entries for %d bytes" % (len(sa), len(t)))
+        _same_length(sa, "entries", len(t), "bytes")
         pat, lens, npat = _pack_patterns(patterns)
         lo, hi = np.zeros(npat, dtype=np.uint32), np.zeros(npat, dtype=np.uint32)
         self._ck(self._lib.dk_sa_search(self._h, _ptr(t), len(t), _ptr(sa), _ptr(pat), npat, lens, _ptr(lo), _ptr(hi)))
@@ -331,7 +344,7 @@ class Context:
         """L of every block into d_bwt_out (same layout as d_in); returns the list of origins"""
         _inputs_ready(d_in)
         count = len(sizes)
-        ns = (C.c_size_t * count)(*[int(n) for n in sizes])
+        ns = _sizes(sizes)
         origin = np.zeros(max(count, 1), dtype=np.uint32)
         self._ck(self._lib.dk_dev_bwt_forward_packed(self._h, _ptr(d_in), count, ns, _ptr(d_bwt_out),
                                                      origin.ctypes.data_as(C.POINTER(C.c_uint32))))
@@ -342,7 +355,7 @@ class Context:
         of every block, from the same pass: returns the list of origins then, else None"""
         _inputs_ready(d_in)
         count = len(sizes)
-        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
+        ns = _sizes(sizes)
         if d_bwt_out is None:
             self._ck(self._lib.dk_dev_suffix_array_packed(self._h, _ptr(d_in), count, ns, _ptr(d_sa_out), None, None))
             return None
@@ -366,14 +379,14 @@ class Context:
         """the LCP array of every block of a pack (layout of dev_suffix_array_packed: entries of d_sa local to their block) in one pass"""
         _inputs_ready(d_in, d_sa)
         count = len(sizes)
-        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
+        ns = _sizes(sizes)
         self._ck(self._lib.dk_dev_lcp_packed(self._h, _ptr(d_in), count, ns, _ptr(d_sa), _ptr(d_lcp_out)))
 
     def dev_suffix_array_packed_lcp(self, d_in, sizes, d_sa_out, d_lcp_out):
         """dev_suffix_array_packed (without L), then the LCP arrays from the same sort's ranks, in one call"""
         _inputs_ready(d_in)
         count = len(sizes)
-        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
+        ns = _sizes(sizes)
         self._ck(self._lib.dk_dev_suffix_array_packed_lcp(self._h, _ptr(d_in), count, ns, _ptr(d_sa_out), _ptr(d_lcp_out)))
 
     # ---- suffix-array check and search (DESIGN.md section 4.12) ----
@@ -388,7 +401,7 @@ class Context:
         """every block of a pack (layout of dev_suffix_array_packed) in one pass -> a list of (verdict, where), where local to the block"""
         _inputs_ready(d_in, d_sa)
         count = len(sizes)
-        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
+        ns = _sizes(sizes)
         verdict, where = np.zeros(max(count, 1), dtype=np.uint32), np.zeros(max(count, 1), dtype=np.uint32)
         self._ck(self._lib.dk_dev_sa_check_packed(self._h, _ptr(d_in), count, ns, _ptr(d_sa), _ptr(verdict), _ptr(where)))
         return [(_lib.SA_VERDICTS[int(v)], int(w)) for v, w in zip(verdict[:count], where[:count])]
@@ -398,18 +411,17 @@ class Context:
         occurrences in d_in[0, n)"""
         _inputs_ready(d_in, d_sa, d_pat)
         npat = len(pat_lens)
-        lens = (C.c_size_t * max(npat, 1))(*[int(m) for m in pat_lens])
+        lens = _sizes(pat_lens)
         self._ck(self._lib.dk_dev_sa_search(self._h, _ptr(d_in), n, _ptr(d_sa), _ptr(d_pat), npat, lens, _ptr(d_lo), _ptr(d_hi)))
 
     def dev_sa_search_packed(self, d_in, sizes, d_sa, d_pat, pat_lens, pat_blocks, d_lo, d_hi):
         """dev_sa_search in a pack: pattern q is searched in block pat_blocks[q], d_lo / d_hi are local to that block"""
         _inputs_ready(d_in, d_sa, d_pat)
         count, npat = len(sizes), len(pat_lens)
-        if len(pat_blocks) != npat:
-            raise DarkError(_lib.DK_E_ARG, "%d blocks for %d patterns" % (len(pat_blocks), npat))
-        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
-        lens = (C.c_size_t * max(npat, 1))(*[int(m) for m in pat_lens])
-        blocks = np.array(pat_blocks, dtype=np.int64).astype(np.uint32) if npat else np.zeros(1, np.uint32)
+        _same_length(pat_blocks, "blocks", npat, "patterns")
+        ns = _sizes(sizes)
+        lens = _sizes(pat_lens)
+        blocks = _u32s(pat_blocks)
         self._ck(self._lib.dk_dev_sa_search_packed(self._h, _ptr(d_in), count, ns, _ptr(d_sa), _ptr(d_pat), npat, lens, _ptr(blocks), _ptr(d_lo),
                                                    _ptr(d_hi)))
 
@@ -423,28 +435,26 @@ class Context:
         """one index for every block of a packed L (layout of dev_bwt_forward_packed); d_index: fm_index_bytes(sum(sizes), len(sizes)) bytes"""
         _inputs_ready(d_bwt)
         count = len(sizes)
-        if len(origins) != count:
-            raise DarkError(_lib.DK_E_ARG, "%d origins for %d blocks" % (len(origins), count))
-        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
-        org = np.array(origins, dtype=np.int64).astype(np.uint32) if count else np.zeros(1, np.uint32)
+        _same_length(origins, "origins", count, "blocks")
+        ns = _sizes(sizes)
+        org = _u32s(origins)
         self._ck(self._lib.dk_dev_fm_build_packed(self._h, _ptr(d_bwt), count, ns, _ptr(org), _ptr(d_index)))
 
     def dev_fm_count(self, d_bwt, n, d_index, d_pat, pat_lens, d_lo, d_hi):
         """patterns as for dev_sa_search; d_lo[q] / d_hi[q] are what dev_sa_search gives for the text d_bwt is the BWT of: hi - lo occurrences"""
         _inputs_ready(d_bwt, d_index, d_pat)
         npat = len(pat_lens)
-        lens = (C.c_size_t * max(npat, 1))(*[int(m) for m in pat_lens])
+        lens = _sizes(pat_lens)
         self._ck(self._lib.dk_dev_fm_count(self._h, _ptr(d_bwt), n, _ptr(d_index), _ptr(d_pat), npat, lens, _ptr(d_lo), _ptr(d_hi)))
 
     def dev_fm_count_packed(self, d_bwt, sizes, d_index, d_pat, pat_lens, pat_blocks, d_lo, d_hi):
         """dev_fm_count in a pack: pattern q is counted in block pat_blocks[q], d_lo / d_hi are local to that block"""
         _inputs_ready(d_bwt, d_index, d_pat)
         count, npat = len(sizes), len(pat_lens)
-        if len(pat_blocks) != npat:
-            raise DarkError(_lib.DK_E_ARG, "%d blocks for %d patterns" % (len(pat_blocks), npat))
-        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
-        lens = (C.c_size_t * max(npat, 1))(*[int(m) for m in pat_lens])
-        blocks = np.array(pat_blocks, dtype=np.int64).astype(np.uint32) if npat else np.zeros(1, np.uint32)
+        _same_length(pat_blocks, "blocks", npat, "patterns")
+        ns = _sizes(sizes)
+        lens = _sizes(pat_lens)
+        blocks = _u32s(pat_blocks)
         self._ck(self._lib.dk_dev_fm_count_packed(self._h, _ptr(d_bwt), count, ns, _ptr(d_index), _ptr(d_pat), npat, lens, _ptr(blocks),
                                                   _ptr(d_lo), _ptr(d_hi)))
 
@@ -467,10 +477,9 @@ class Context:
         """one structure for every block of a packed L; d_loc: fm_locate_bytes(sum(sizes), len(sizes), step) bytes"""
         _inputs_ready(d_bwt)
         count = len(sizes)
-        if len(origins) != count:
-            raise DarkError(_lib.DK_E_ARG, "%d origins for %d blocks" % (len(origins), count))
-        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
-        org = np.array(origins, dtype=np.int64).astype(np.uint32) if count else np.zeros(1, np.uint32)
+        _same_length(origins, "origins", count, "blocks")
+        ns = _sizes(sizes)
+        org = _u32s(origins)
         self._ck(self._lib.dk_dev_fm_locate_build_packed(self._h, _ptr(d_bwt), count, ns, _ptr(org), int(step), _ptr(d_loc)))
 
     def dev_fm_locate(self, d_bwt, n, d_index, d_loc, step, d_lo, d_hi, npat, max_hits, d_pos):
@@ -484,8 +493,8 @@ class Context:
         """dev_fm_locate in a pack: row q holds positions local to block pat_blocks[q]"""
         _inputs_ready(d_bwt, d_index, d_loc, d_lo, d_hi)
         count, npat = len(sizes), len(pat_blocks)
-        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
-        blocks = np.array(pat_blocks, dtype=np.int64).astype(np.uint32) if npat else np.zeros(1, np.uint32)
+        ns = _sizes(sizes)
+        blocks = _u32s(pat_blocks)
         self._ck(self._lib.dk_dev_fm_locate_packed(self._h, _ptr(d_bwt), count, ns, _ptr(d_index), _ptr(d_loc), int(step), _ptr(d_lo), _ptr(d_hi),
                                                    npat, _ptr(blocks), int(max_hits), _ptr(d_pos)))
 
@@ -510,10 +519,9 @@ class Context:
         """one structure for every block of a packed L; d_ext: fm_extract_bytes(sum(sizes), len(sizes), step) bytes"""
         _inputs_ready(d_bwt)
         count = len(sizes)
-        if len(origins) != count:
-            raise DarkError(_lib.DK_E_ARG, "%d origins for %d blocks" % (len(origins), count))
-        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
-        org = np.array(origins, dtype=np.int64).astype(np.uint32) if count else np.zeros(1, np.uint32)
+        _same_length(origins, "origins", count, "blocks")
+        ns = _sizes(sizes)
+        org = _u32s(origins)
         self._ck(self._lib.dk_dev_fm_extract_build_packed(self._h, _ptr(d_bwt), count, ns, _ptr(org), int(step), _ptr(d_ext)))
 
     def dev_fm_extract(self, d_bwt, n, d_index, d_ext, step, d_pos, d_len, nrange, max_len, d_out):
@@ -527,8 +535,8 @@ class Context:
         """dev_fm_extract in a pack: range q lies in block range_blocks[q], its start is local to that block"""
         _inputs_ready(d_bwt, d_index, d_ext, d_pos, *([] if d_len is None else [d_len]))
         count, nrange = len(sizes), len(range_blocks)
-        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
-        blocks = np.array(range_blocks, dtype=np.int64).astype(np.uint32) if nrange else np.zeros(1, np.uint32)
+        ns = _sizes(sizes)
+        blocks = _u32s(range_blocks)
         self._ck(self._lib.dk_dev_fm_extract_packed(self._h, _ptr(d_bwt), count, ns, _ptr(d_index), _ptr(d_ext), int(step), _ptr(d_pos),
                                                     None if d_len is None else _ptr(d_len), nrange, _ptr(blocks), int(max_len), _ptr(d_out)))
 
@@ -536,7 +544,7 @@ class Context:
         """a uint8 array of len(positions) x max_len from (L, origin) in host memory: row q = the text at [positions[q], positions[q] +
         lengths[q]), cut to max_len and the text's end, zeros behind; lengths None: every range max_len long (dk_fm_extract)"""
         b = as_u8(bwt)
-        pos = np.array(positions, dtype=np.int64).astype(np.uint32) if len(positions) else np.zeros(1, np.uint32)
+        pos = _u32s(positions)
         nrange = len(positions)
         lens = None if lengths is None else (np.array(lengths, dtype=np.int64).astype(np.uint32) if nrange else np.zeros(1, np.uint32))
         out = np.zeros((nrange, max(int(max_len), 1)), dtype=np.uint8)
@@ -551,7 +559,7 @@ class Context:
         min(sum, max_hits) hits in the order (pattern, slot).  max_hits == 0: d_hits and d_loc may be None"""
         _inputs_ready(d_bwt, d_index, d_pat)
         npat = len(pat_lens)
-        lens = (C.c_size_t * max(npat, 1))(*[int(m) for m in pat_lens])
+        lens = _sizes(pat_lens)
         total = C.c_uint64(0)
         self._ck(self._lib.dk_dev_fm_find(self._h, _ptr(d_bwt), n, _ptr(d_index), None if d_loc is None else _ptr(d_loc), int(step), _ptr(d_pat),
                                           npat, lens, int(max_hits), None if d_hits is None else _ptr(d_hits),
@@ -563,8 +571,8 @@ class Context:
         the order (pattern, block, slot), positions and slots local to their block"""
         _inputs_ready(d_bwt, d_index, d_pat)
         count, npat = len(sizes), len(pat_lens)
-        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
-        lens = (C.c_size_t * max(npat, 1))(*[int(m) for m in pat_lens])
+        ns = _sizes(sizes)
+        lens = _sizes(pat_lens)
         total = C.c_uint64(0)
         self._ck(self._lib.dk_dev_fm_find_packed(self._h, _ptr(d_bwt), count, ns, _ptr(d_index), None if d_loc is None else _ptr(d_loc), int(step),
                                                  _ptr(d_pat), npat, lens, int(max_hits), None if d_hits is None else _ptr(d_hits),
@@ -590,7 +598,7 @@ class Context:
         back, 0) receives the first min(sum, max_hits) in the order (pattern, back descending), back = the match's bytes in front of the block"""
         _inputs_ready(d_bwt, d_index, d_ext, d_pat)
         npat, prev_len = len(pat_lens), 0 if d_prev is None else int(d_prev.numel())
-        lens = (C.c_size_t * max(npat, 1))(*[int(m) for m in pat_lens])
+        lens = _sizes(pat_lens)
         total = C.c_uint64(0)
         self._ck(self._lib.dk_dev_fm_seams(self._h, _ptr(d_bwt), n, _ptr(d_index), _ptr(d_ext), int(step), _ptr(d_prev) if prev_len else None, prev_len,
                                            _ptr(d_pat), npat, lens, int(max_hits), None if d_hits is None else _ptr(d_hits),
@@ -603,8 +611,8 @@ class Context:
         descending)"""
         _inputs_ready(d_bwt, d_index, d_ext, d_pat)
         count, npat, prev_len = len(sizes), len(pat_lens), 0 if d_prev is None else int(d_prev.numel())
-        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
-        lens = (C.c_size_t * max(npat, 1))(*[int(m) for m in pat_lens])
+        ns = _sizes(sizes)
+        lens = _sizes(pat_lens)
         total = C.c_uint64(0)
         self._ck(self._lib.dk_dev_fm_seams_packed(self._h, _ptr(d_bwt), count, ns, _ptr(d_index), _ptr(d_ext), int(step),
                                                   _ptr(d_prev) if prev_len else None, prev_len, _ptr(d_pat), npat, lens, int(max_hits),
@@ -620,7 +628,7 @@ class Context:
         """DC arrays of a packed L: block i's entries at [off_i, off_i + m_i); returns (list of init tables, list of m)"""
         _inputs_ready(d_bwt)
         count = len(sizes)
-        ns = (C.c_size_t * count)(*[int(n) for n in sizes])
+        ns = _sizes(sizes)
         init = np.zeros((max(count, 1), 256), dtype=np.uint32)
         m = (C.c_size_t * max(count, 1))()
         self._ck(self._lib.dk_dev_dc_encode_packed(self._h, _ptr(d_bwt), count, ns, _ptr(init), _ptr(d_dist), _ptr(d_sym),
@@ -634,7 +642,7 @@ class Context:
         mid = model_id(model)
         if outs is None:  # (rawdc: one 10-byte record per distance)
             outs = [np.empty(_stream_cap(mid, n), dtype=np.uint8) for n in sizes]
-        ns = (C.c_size_t * count)(*[int(n) for n in sizes])
+        ns = _sizes(sizes)
         optrs = (C.c_void_p * count)(*[_ptr(o) for o in outs])
         caps = (C.c_size_t * count)(*[len(o) for o in outs])
         lens = (C.c_size_t * count)()
@@ -647,10 +655,9 @@ class Context:
         """inverse of dev_bwt_forward_packed: block i's text into d_out (same layout as d_bwt) from its L and origins[i]"""
         _inputs_ready(d_bwt)
         count = len(sizes)
-        if len(origins) != count:
-            raise DarkError(_lib.DK_E_ARG, "%d origins for %d blocks" % (len(origins), count))
-        ns = (C.c_size_t * count)(*[int(n) for n in sizes])
-        org = np.array(origins, dtype=np.int64).astype(np.uint32) if count else np.zeros(1, np.uint32)
+        _same_length(origins, "origins", count, "blocks")
+        ns = _sizes(sizes)
+        org = _u32s(origins)
         self._ck(self._lib.dk_dev_bwt_inverse_packed(self._h, _ptr(d_bwt), count, ns, _ptr(org), _ptr(d_out)))
 
     def dev_packed_decode(self, model, streams, sizes, d_out, host_threads=8):
@@ -659,7 +666,7 @@ class Context:
         keep = [as_u8(x) for x in streams]
         ins = (C.c_void_p * max(count, 1))(*[_ptr(x) for x in keep])
         lens = (C.c_size_t * max(count, 1))(*[len(x) for x in keep])
-        ns = (C.c_size_t * max(count, 1))(*[int(n) for n in sizes])
+        ns = _sizes(sizes)
         self._ck(self._lib.dk_dev_packed_decode(self._h, model_id(model), count, ins, lens, ns, _ptr(d_out), int(host_threads)))
 
     def dev_block_encode(self, model, d_in, n, out=None):
@@ -680,7 +687,7 @@ class Context:
         if outs is None:
             outs = [np.empty(2 * int(n) + 4096 + _prefix(mid), dtype=np.uint8) for n in sizes]
         ptrs = (C.c_void_p * count)(*[_ptr(b) for b in d_blocks])
-        ns = (C.c_size_t * count)(*[int(n) for n in sizes])
+        ns = _sizes(sizes)
         optrs = (C.c_void_p * count)(*[_ptr(o) for o in outs])
         caps = (C.c_size_t * count)(*[len(o) for o in outs])
         lens = (C.c_size_t * count)()
@@ -696,7 +703,7 @@ class Context:
         keep = [as_u8(x) for x in streams]
         ins = (C.c_void_p * count)(*[_ptr(x) for x in keep])
         lens = (C.c_size_t * count)(*[len(x) for x in keep])
-        ns = (C.c_size_t * count)(*[int(n) for n in sizes])
+        ns = _sizes(sizes)
         outs = (C.c_void_p * count)(*[_ptr(o) for o in d_outs])
         self._ck(self._lib.dk_dev_batch_decode(self._h, model_id(model), count, ins, lens, ns, outs, int(host_threads)))
 
@@ -916,7 +923,7 @@ class Batch:
         count = len(sizes)
         outs = [np.empty(_stream_cap(self._model, n), dtype=np.uint8) for n in sizes]
         lens = (C.c_size_t * max(count, 1))()
-        ns = (C.c_size_t * count)(*[int(n) for n in sizes])
+        ns = _sizes(sizes)
         optrs = (C.c_void_p * count)(*[_ptr(o) for o in outs])
         caps = (C.c_size_t * count)(*[len(o) for o in outs])
         flags = (C.c_uint * max(count, 1))()
@@ -974,7 +981,7 @@ def multi_block_decode(model, streams, sizes, devices, host_threads_per_gpu=4):
     devs = (C.c_int * len(devices))(*[int(d) for d in devices])
     ins = (C.c_void_p * count)(*[_ptr(s) for s in keep])
     lens = (C.c_size_t * count)(*[len(s) for s in keep])
-    ns = (C.c_size_t * count)(*[int(n) for n in sizes])
+    ns = _sizes(sizes)
     optrs = (C.c_void_p * count)(*[_ptr(o) for o in outs])
     err = C.create_string_buffer(512)
     rc = lib.dk_multi_block_decode(devs, len(devices), model_id(model), count, ins, lens, ns, optrs, int(host_threads_per_gpu), err, 512)

@@ -1,4 +1,5 @@
-// extern "C" boundary (include/dark_amd.h).  Thin: argument checks, workspace carving, stage sequencing, timing.
+// extern "C" boundary (include/dark_amd.h): contexts, the codec, batches, the packed stages and the debug entries; the query entries (LCP,
+// suffix-array check / search, FM-index) are in abi_query.cpp.  Thin: argument checks, workspace carving, stage sequencing, timing.
 #include <algorithm>
 #include <cctype>
 #include <cstdio>
@@ -11,18 +12,14 @@
 #include <thread>
 #include <vector>
 
-#include "context.hpp"
+#include "abi_common.hpp"
 #include <cstdlib>
 #include <atomic>
 #include "entropy.hpp"
 
 using namespace dk;
 
-namespace {
-
-// forward_entry: the name of an entry point that needs the suffix sort's workspace (everything but the inverse path).  A decoder context
-// refuses it here, before anything is reset, allocated, launched or copied.
-int begin_call(dk_ctx *ctx, const char *forward_entry = nullptr) {
+int dk::begin_call(dk_ctx *ctx, const char *forward_entry) {
     if (!ctx) return DK_E_ARG;
     if (forward_entry && ctx->purpose == DK_CTX_DECODER)
         return ctx->fail(DK_E_ARG, "%s: not served by a decoder context (dk_ctx_create_decoder sizes the workspace for the inverse path only)", forward_entry);
@@ -35,14 +32,9 @@ int begin_call(dk_ctx *ctx, const char *forward_entry = nullptr) {
     if (hipSetDevice(ctx->device) != hipSuccess) return ctx->fail(DK_E_HIP, "hipSetDevice(%d) failed", ctx->device);
     return DK_OK;
 }
-void end_call(dk_ctx *ctx) {
-    if (ctx->profiling) ctx->prof_collect();
-}
-int check_n(dk_ctx *ctx, size_t n) {
-    if (n == 0) return ctx->fail(DK_E_ARG, "empty block (the reference panics at src/saca.rs:107)");
-    if (n > ctx->max_n) return ctx->fail(DK_E_ARG, "block of %zu bytes exceeds the context capacity %zu", n, ctx->max_n);
-    return DK_OK;
-}
+
+namespace {
+
 #ifndef DK_D2H_OVERLAP
 #define DK_D2H_OVERLAP 1  // the distance stream of a large single block leaves the GPU in pieces while the host coder already runs (0: A/B builds)
 #endif
@@ -125,12 +117,6 @@ bool good_ctx_size(int purpose, size_t max_n, size_t max_blocks) {
     if (max_n == 0 || max_n > 0x7FFFFFFEull) return false;
     return purpose == DK_CTX_FULL || (purpose == DK_CTX_DECODER && max_blocks >= 1 && max_blocks <= DK_PACKED_MAX_BLOCKS);
 }
-struct ScopedCall {
-    dk_ctx *c;
-    explicit ScopedCall(dk_ctx *ctx) : c(ctx) {}
-    ~ScopedCall() { end_call(c); }
-};
-
 // device-resident forward path up to the compact DC stream in pinned host memory
 struct ForwardResult {
     uint32_t init[256];
@@ -591,26 +577,13 @@ namespace {
 // at most 10 rounds on its text shapes (wiki_like; english_like 2, random bytes 0), so 12 leaves two rounds of headroom.
 constexpr int PACKED_MAX_ROUNDS = 12;
 
-int check_pack(dk_ctx *ctx, size_t count, const size_t *n, std::vector<uint32_t> &off) {
-    if (!n) return ctx->fail(DK_E_ARG, "null pointer");
-    if (count == 0 || count > ctx->max_blocks) return ctx->fail(DK_E_ARG, "a pack holds 1 .. %zu blocks, not %zu", ctx->max_blocks, count);
-    off.assign(count + 1, 0);
-    size_t total = 0;
-    for (size_t i = 0; i < count; ++i) {
-        if (n[i] == 0) return ctx->fail(DK_E_ARG, "empty block %zu in the pack (the reference panics at src/saca.rs:107)", i);
-        if (n[i] > DK_PACKED_MAX_BLOCK_BYTES) return ctx->fail(DK_E_ARG, "block %zu of %zu bytes exceeds DK_PACKED_MAX_BLOCK_BYTES", i, n[i]);
-        total += n[i];
-        if (total > ctx->max_n) return ctx->fail(DK_E_ARG, "the pack exceeds the context capacity %zu", ctx->max_n);
-        off[i + 1] = static_cast<uint32_t>(total);
-    }
-    return DK_OK;
-}
+}  // namespace
 
 // L of every block into d_bwt and the origins into h_origin (host, count): one segmented pass, then the guard's blocks one by one.
 // d_sa (may be null): the suffix arrays too, from the same pass (dk_dev_suffix_array_packed); then d_bwt / d_origin may both be null.
 // d_phi (may be null, only with d_sa): Phi of the pack for the LCP pass -- from the sort's rank, and for the guard's blocks from their suffix arrays.
-int packed_forward(dk_ctx *ctx, const uint8_t *d_in, const std::vector<uint32_t> &off, const uint32_t *d_off, uint8_t *d_bwt, uint32_t *d_origin,
-                   std::vector<std::pair<size_t, uint32_t>> *fixed, uint32_t *d_sa = nullptr, uint32_t *d_phi = nullptr) {
+int dk::packed_forward(dk_ctx *ctx, const uint8_t *d_in, const std::vector<uint32_t> &off, const uint32_t *d_off, uint8_t *d_bwt, uint32_t *d_origin,
+                       std::vector<std::pair<size_t, uint32_t>> *fixed, uint32_t *d_sa, uint32_t *d_phi) {
     hipStream_t st = ctx->stream;
     const size_t count = off.size() - 1, total = off.back();
     Timer t;
@@ -657,23 +630,23 @@ int packed_forward(dk_ctx *ctx, const uint8_t *d_in, const std::vector<uint32_t>
     return DK_OK;
 }
 
-}  // namespace
-
 extern "C" {
 
 int dk_dev_bwt_forward_packed(dk_ctx *ctx, const uint8_t *d_in, size_t count, const size_t *n, uint8_t *d_bwt_out, uint32_t *origin) {
     DK_TRY(begin_call(ctx, "dk_dev_bwt_forward_packed"));
     ScopedCall sc(ctx);
     if (!d_in || !n || !d_bwt_out || !origin) return ctx->fail(DK_E_ARG, "null pointer");
-    std::vector<uint32_t> off;
-    DK_TRY(check_pack(ctx, count, n, off));
+    Layout lay(count, n);
+    DK_TRY(lay.check(ctx));
+    std::vector<std::pair<size_t, uint32_t>> fixed;
+    Upload up(ctx);
     Timer t;
     hipStream_t st = ctx->stream;
-    uint32_t *d_off = ctx->ws_alloc<uint32_t>(count + 1), *d_origin = ctx->ws_alloc<uint32_t>(count);
-    if (!d_off || !d_origin) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    std::vector<std::pair<size_t, uint32_t>> fixed;
-    DK_TRY(packed_forward(ctx, d_in, off, d_off, d_bwt_out, d_origin, &fixed));
+    const uint32_t *d_off = lay.device(up);
+    uint32_t *d_origin = ctx->ws_alloc<uint32_t>(count);
+    if (!d_off || !d_origin) return up.failed();
+    DK_TRY(packed_forward(ctx, d_in, lay.off(), d_off, d_bwt_out, d_origin, &fixed));
+    up.synchronised();  // (packed_forward ends with a wait)
     DK_HIP(ctx, hipMemcpyAsync(origin, d_origin, count * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     DK_HIP(ctx, hipStreamSynchronize(st));
     for (const auto &f : fixed) origin[f.first] = f.second;
@@ -687,15 +660,17 @@ int dk_dev_suffix_array_packed(dk_ctx *ctx, const uint8_t *d_in, size_t count, c
     ScopedCall sc(ctx);
     if (!d_in || !n || !d_sa_out) return ctx->fail(DK_E_ARG, "null pointer");
     if ((d_bwt_out == nullptr) != (origin == nullptr)) return ctx->fail(DK_E_ARG, "d_bwt_out and origin go together: both or neither");
-    std::vector<uint32_t> off;
-    DK_TRY(check_pack(ctx, count, n, off));
+    Layout lay(count, n);
+    DK_TRY(lay.check(ctx));
+    std::vector<std::pair<size_t, uint32_t>> fixed;
+    Upload up(ctx);
     Timer t;
     hipStream_t st = ctx->stream;
-    uint32_t *d_off = ctx->ws_alloc<uint32_t>(count + 1), *d_origin = d_bwt_out ? ctx->ws_alloc<uint32_t>(count) : nullptr;
-    if (!d_off || (d_bwt_out && !d_origin)) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    std::vector<std::pair<size_t, uint32_t>> fixed;
-    DK_TRY(packed_forward(ctx, d_in, off, d_off, d_bwt_out, d_origin, &fixed, d_sa_out));
+    const uint32_t *d_off = lay.device(up);
+    uint32_t *d_origin = d_bwt_out ? ctx->ws_alloc<uint32_t>(count) : nullptr;
+    if (!d_off || (d_bwt_out && !d_origin)) return up.failed();
+    DK_TRY(packed_forward(ctx, d_in, lay.off(), d_off, d_bwt_out, d_origin, &fixed, d_sa_out));
+    up.synchronised();  // (packed_forward ends with a wait)
     if (d_bwt_out) {
         DK_HIP(ctx, hipMemcpyAsync(origin, d_origin, count * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         DK_HIP(ctx, hipStreamSynchronize(st));
@@ -710,20 +685,21 @@ int dk_dev_dc_encode_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, con
     DK_TRY(begin_call(ctx, "dk_dev_dc_encode_packed"));
     ScopedCall sc(ctx);
     if (!d_bwt || !n || !init || !d_dist || !d_sym || !m) return ctx->fail(DK_E_ARG, "null pointer");
-    std::vector<uint32_t> off;
-    DK_TRY(check_pack(ctx, count, n, off));
+    Layout lay(count, n);
+    DK_TRY(lay.check(ctx));
+    Upload up(ctx);
     Timer t;
     hipStream_t st = ctx->stream;
     // read-back block: m | flags | rb (count + 1) | init (count x 256)
     const size_t words = 3 * count + 1 + 256 * count;
-    uint32_t *d_off = ctx->ws_alloc<uint32_t>(count + 1), *d_res = ctx->ws_alloc<uint32_t>(words);
-    if (!d_off || !d_res) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    DK_TRY(packed_dc_device(ctx, d_bwt, d_off, count, off.back(), false, d_dist, d_sym, d_rank, nullptr, d_res, d_res + count, d_res + 2 * count,
+    const uint32_t *d_off = lay.device(up);
+    uint32_t *d_res = ctx->ws_alloc<uint32_t>(words);
+    if (!d_off || !d_res) return up.failed();
+    DK_TRY(packed_dc_device(ctx, d_bwt, d_off, count, lay.total(), false, d_dist, d_sym, d_rank, nullptr, d_res, d_res + count, d_res + 2 * count,
                             d_res + 3 * count + 1));
     std::vector<uint32_t> res(words);
     DK_HIP(ctx, hipMemcpyAsync(res.data(), d_res, words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipStreamSynchronize(st));
+    DK_TRY(up.sync());
     for (size_t i = 0; i < count; ++i) m[i] = res[i];
     std::memcpy(init, res.data() + 3 * count + 1, 256 * count * sizeof(uint32_t));
     ctx->stats.ms_dc = ctx->stats.ms_total = t.ms();
@@ -735,22 +711,25 @@ int dk_dev_dc_encode_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, con
 namespace {
 
 // device stages of a pack for an open batch: everything up to the distance streams in staging slot `slot`, then one coding job per block
-int push_packed_body(dk_batch *b, int slot, const uint8_t *d_in, const std::vector<uint32_t> &off, uint8_t *const *out, const size_t *out_cap,
-                     size_t *out_len, unsigned *flags) {
+int push_packed_body(dk_batch *b, int slot, const uint8_t *d_in, const Layout &lay, uint8_t *const *out, const size_t *out_cap, size_t *out_len,
+                     unsigned *flags) {
     dk_ctx *ctx = b->ctx;
     hipStream_t st = ctx->stream;
-    const size_t count = off.size() - 1, total = off.back();
+    const std::vector<uint32_t> &off = lay.off();
+    const size_t count = lay.count(), total = lay.total();
+    std::vector<std::pair<size_t, uint32_t>> fixed;
+    Upload up(ctx);
     const bool want = dk::model_base(b->model_id) == DK_MODEL_RAWDC;
     // read-back block: origin | m | flags | rb (count + 1) | init (count x 256)
     const size_t words = 4 * count + 1 + 256 * count;
-    uint32_t *d_off = ctx->ws_alloc<uint32_t>(count + 1), *d_res = ctx->ws_alloc<uint32_t>(words);
+    const uint32_t *d_off = lay.device(up);
+    uint32_t *d_res = ctx->ws_alloc<uint32_t>(words);
     uint8_t *d_bwt = ctx->ws_alloc<uint8_t>(total);
-    if (!d_off || !d_res || !d_bwt) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    std::vector<std::pair<size_t, uint32_t>> fixed;
+    if (!d_off || !d_res || !d_bwt) return up.failed();
     {
         const size_t mark = ctx->ws_mark();
         DK_TRY(packed_forward(ctx, d_in, off, d_off, d_bwt, d_res, &fixed));
+        up.synchronised();  // (packed_forward ends with a wait)
         ctx->ws_release(mark);
     }
     uint32_t *d_dist = ctx->ws_alloc<uint32_t>(total);
@@ -819,8 +798,8 @@ int dk_batch_push_packed(dk_batch *b, const uint8_t *d_in, size_t count, const s
     if (!b) return DK_E_ARG;
     dk_ctx *ctx = b->ctx;
     if (!d_in || !n || !out || !out_cap || !out_len) return ctx->fail(DK_E_ARG, "null pointer");
-    std::vector<uint32_t> off;
-    DK_TRY(check_pack(ctx, count, n, off));
+    Layout lay(count, n);
+    DK_TRY(lay.check(ctx));
     for (size_t i = 0; i < count; ++i) {
         if (!out[i]) return ctx->fail(DK_E_ARG, "null output for block %zu of the pack", i);
         if (n[i] > model_max_block(b->model_id)) return ctx->fail(DK_E_MODEL, "model %d cannot code a block of %zu bytes", b->model_id, n[i]);
@@ -835,7 +814,7 @@ int dk_batch_push_packed(dk_batch *b, const uint8_t *d_in, size_t count, const s
     }
     ctx->ws_reset();
     Timer t;
-    const int rc = push_packed_body(b, slot, d_in, off, out, out_cap, out_len, flags);
+    const int rc = push_packed_body(b, slot, d_in, lay, out, out_cap, out_len, flags);
     ctx->stats.ms_total = t.ms();
     if (ctx->profiling) ctx->prof_collect();
     if (rc != DK_OK) {
@@ -976,12 +955,11 @@ int dk_dev_bwt_inverse_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, c
     DK_TRY(begin_call(ctx));
     ScopedCall sc(ctx);
     if (!d_bwt || !n || !origin || !d_out) return ctx->fail(DK_E_ARG, "null pointer");
-    std::vector<uint32_t> off;
-    DK_TRY(check_pack(ctx, count, n, off));
-    for (size_t i = 0; i < count; ++i)
-        if (origin[i] >= n[i]) return ctx->fail(DK_E_ARG, "origin %u of block %zu is outside its %zu bytes", origin[i], i, n[i]);
+    Layout lay(count, n);
+    DK_TRY(lay.check(ctx));
+    DK_TRY(lay.check_origins(ctx, origin));
     Timer t;
-    DK_TRY(packed_ibwt_device(ctx, d_bwt, off, origin, d_out));
+    DK_TRY(packed_ibwt_device(ctx, d_bwt, lay.off(), origin, d_out));
     ctx->stats.ms_ibwt = ctx->stats.ms_total = t.ms();
     return DK_OK;
 }
@@ -993,12 +971,13 @@ int dk_dev_packed_decode(dk_ctx *ctx, int model_id, size_t count, const uint8_t 
     ScopedCall sc(ctx);
     if (!in || !in_len || !n || !d_out) return ctx->fail(DK_E_ARG, "null pointer");
     if (dk::model_base(model_id) == DK_MODEL_RAWDC || model_max_block(model_id) == 0) return ctx->fail(DK_E_MODEL, "model %d cannot decode", model_id);
-    std::vector<uint32_t> off;
-    DK_TRY(check_pack(ctx, count, n, off));
+    Layout lay(count, n);
+    DK_TRY(lay.check(ctx));
+    const std::vector<uint32_t> &off = lay.off();
     for (size_t i = 0; i < count; ++i)
         if (!in[i]) return ctx->fail(DK_E_ARG, "null stream for block %zu of the pack", i);
     Timer t;
-    const size_t total = off.back();
+    const size_t total = lay.total();
     DK_TRY(ctx->ensure_slot(0, total + 64));
     uint8_t *h_bwt = reinterpret_cast<uint8_t *>(ctx->slots[0].h);
     std::vector<uint32_t> origin(count);
@@ -1035,1040 +1014,21 @@ int dk_dev_packed_decode(dk_ctx *ctx, int model_id, size_t count, const uint8_t 
     return DK_OK;
 }
 
-// ---- LCP arrays (csrc/lcp.hip) ----------------------------------------------------------------------
-}  // extern "C"
-
-namespace {
-// a single block is a pack of one: its offsets table {0, n} is written by two fills (no host memory behind an asynchronous copy)
-int single_offsets(dk_ctx *ctx, size_t n, uint32_t **d_off_out) {
-    uint32_t *d_off = ctx->ws_alloc<uint32_t>(2);
-    if (!d_off) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_off), 0, 1, ctx->stream));
-    DK_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_off + 1), static_cast<int>(n), 1, ctx->stream));
-    *d_off_out = d_off;
-    return DK_OK;
-}
-int lcp_single(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uint32_t *d_sa, uint32_t *d_lcp) {
-    uint32_t *d_off = nullptr;
-    DK_TRY(single_offsets(ctx, n, &d_off));
-    return lcp_device(ctx, d_text, d_off, 1, n, d_sa, d_lcp);
-}
-}  // namespace
-
-extern "C" {
-
-int dk_dev_lcp(dk_ctx *ctx, const uint8_t *d_in, size_t n, const uint32_t *d_sa, uint32_t *d_lcp_out) {
-    DK_TRY(begin_call(ctx, "dk_dev_lcp"));
-    ScopedCall sc(ctx);
-    if (!d_in || !d_sa || !d_lcp_out) return ctx->fail(DK_E_ARG, "null pointer");
-    DK_TRY(check_n(ctx, n));
-    Timer t;
-    ctx->stats.sa_route = 0;
-    DK_TRY(lcp_single(ctx, d_in, n, d_sa, d_lcp_out));
-    DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-int dk_dev_suffix_array_lcp(dk_ctx *ctx, const uint8_t *d_in, size_t n, uint32_t *d_sa_out, uint32_t *d_lcp_out) {
-    DK_TRY(begin_call(ctx, "dk_dev_suffix_array_lcp"));
-    ScopedCall sc(ctx);
-    if (!d_in || !d_sa_out || !d_lcp_out) return ctx->fail(DK_E_ARG, "null pointer");
-    DK_TRY(check_n(ctx, n));
-    Timer t;
-    const size_t mark = ctx->ws_mark();
-    DK_TRY(suffix_array_device(ctx, d_in, n, d_sa_out));
-    ctx->ws_release(mark);  // the LCP pass takes the place of the sort's temporaries
-    DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->stats.ms_sa = t.ms();
-    DK_TRY(lcp_single(ctx, d_in, n, d_sa_out, d_lcp_out));
-    DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-int dk_suffix_array_lcp(dk_ctx *ctx, const uint8_t *in, size_t n, uint32_t *sa_out, uint32_t *lcp_out) {
-    DK_TRY(begin_call(ctx, "dk_suffix_array_lcp"));
-    ScopedCall sc(ctx);
-    if (!in || !sa_out || !lcp_out) return ctx->fail(DK_E_ARG, "null pointer");
-    DK_TRY(check_n(ctx, n));
-    Timer t;
-    hipStream_t st = ctx->stream;
-    uint8_t *d_text = ctx->ws_alloc<uint8_t>(n);
-    uint32_t *d_sa = ctx->ws_alloc<uint32_t>(n);
-    if (!d_text || !d_sa) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(d_text, in, n, hipMemcpyHostToDevice, st));
-    const size_t mark = ctx->ws_mark();
-    DK_TRY(suffix_array_device(ctx, d_text, n, d_sa));
-    ctx->ws_release(mark);
-    uint32_t *d_lcp = ctx->ws_alloc<uint32_t>(n);  // (after the sort: its 63.4 n and the 9 n around it would not fit together)
-    if (!d_lcp) return DK_E_NOMEM;
-    DK_TRY(lcp_single(ctx, d_text, n, d_sa, d_lcp));
-    DK_HIP(ctx, hipMemcpyAsync(sa_out, d_sa, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipMemcpyAsync(lcp_out, d_lcp, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipStreamSynchronize(st));
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-int dk_dev_lcp_packed(dk_ctx *ctx, const uint8_t *d_in, size_t count, const size_t *n, const uint32_t *d_sa, uint32_t *d_lcp_out) {
-    DK_TRY(begin_call(ctx, "dk_dev_lcp_packed"));
-    ScopedCall sc(ctx);
-    if (!d_in || !n || !d_sa || !d_lcp_out) return ctx->fail(DK_E_ARG, "null pointer");
-    std::vector<uint32_t> off;
-    DK_TRY(check_pack(ctx, count, n, off));
-    Timer t;
-    hipStream_t st = ctx->stream;
-    uint32_t *d_off = ctx->ws_alloc<uint32_t>(count + 1);
-    if (!d_off) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    ctx->stats.sa_route = 0;
-    const int rc = lcp_device(ctx, d_in, d_off, count, off.back(), d_sa, d_lcp_out);
-    const hipError_t e = hipStreamSynchronize(st);  // (also on failure: the copy above reads `off`)
-    DK_TRY(rc);
-    DK_HIP(ctx, e);
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-int dk_dev_suffix_array_packed_lcp(dk_ctx *ctx, const uint8_t *d_in, size_t count, const size_t *n, uint32_t *d_sa_out, uint32_t *d_lcp_out) {
-    DK_TRY(begin_call(ctx, "dk_dev_suffix_array_packed_lcp"));
-    ScopedCall sc(ctx);
-    if (!d_in || !n || !d_sa_out || !d_lcp_out) return ctx->fail(DK_E_ARG, "null pointer");
-    std::vector<uint32_t> off;
-    DK_TRY(check_pack(ctx, count, n, off));
-    Timer t;
-    hipStream_t st = ctx->stream;
-    const size_t total = off.back();
-    uint32_t *d_off = ctx->ws_alloc<uint32_t>(count + 1), *d_phi = ctx->ws_alloc<uint32_t>(total);
-    if (!d_off || !d_phi) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    std::vector<std::pair<size_t, uint32_t>> fixed;
-    int rc = packed_forward(ctx, d_in, off, d_off, nullptr, nullptr, &fixed, d_sa_out, d_phi);
-    if (rc == DK_OK) rc = lcp_device(ctx, d_in, d_off, count, total, d_sa_out, d_lcp_out, d_phi);
-    const hipError_t e = hipStreamSynchronize(st);
-    DK_TRY(rc);
-    DK_HIP(ctx, e);
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-int dk_suffix_array_packed_lcp(dk_ctx *ctx, const uint8_t *in, size_t count, const size_t *n, uint32_t *sa_out, uint32_t *lcp_out) {
-    DK_TRY(begin_call(ctx, "dk_suffix_array_packed_lcp"));
-    ScopedCall sc(ctx);
-    if (!in || !n || !sa_out || !lcp_out) return ctx->fail(DK_E_ARG, "null pointer");
-    std::vector<uint32_t> off;
-    DK_TRY(check_pack(ctx, count, n, off));
-    Timer t;
-    hipStream_t st = ctx->stream;
-    const size_t total = off.back();
-    uint8_t *d_text = ctx->ws_alloc<uint8_t>(total);
-    uint32_t *d_sa = ctx->ws_alloc<uint32_t>(total), *d_phi = ctx->ws_alloc<uint32_t>(total), *d_off = ctx->ws_alloc<uint32_t>(count + 1);
-    if (!d_text || !d_sa || !d_phi || !d_off) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(d_text, in, total, hipMemcpyHostToDevice, st));
-    DK_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    std::vector<std::pair<size_t, uint32_t>> fixed;
-    int rc = packed_forward(ctx, d_text, off, d_off, nullptr, nullptr, &fixed, d_sa, d_phi);
-    // (after the sort and its guard: text, SA and Phi are 9 total, and a guarded block's sort 63.4 n_i with n_i <= 2^24 -- the constant term covers
-    //  the 2.8 n_i by which a pack that is one such block would pass 69.6 total)
-    uint32_t *d_lcp = rc == DK_OK ? ctx->ws_alloc<uint32_t>(total) : nullptr;
-    if (rc == DK_OK && !d_lcp) rc = DK_E_NOMEM;
-    if (rc == DK_OK) rc = lcp_device(ctx, d_text, d_off, count, total, d_sa, d_lcp, d_phi);
-    if (rc == DK_OK) {
-        DK_HIP(ctx, hipMemcpyAsync(sa_out, d_sa, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        DK_HIP(ctx, hipMemcpyAsync(lcp_out, d_lcp, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    }
-    const hipError_t e = hipStreamSynchronize(st);
-    DK_TRY(rc);
-    DK_HIP(ctx, e);
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-// ---- suffix-array check and search (csrc/sa_query.hip) -----------------------------------------------
-}  // extern "C"
-
-namespace {
-// the three words of every block (sa_check_device) -> the first kind that failed and where; where = n_i for a block that is in order
-int sa_check_run(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, const std::vector<uint32_t> &off, const uint32_t *d_sa, uint32_t *verdict,
-                 uint32_t *where) {
-    const size_t count = off.size() - 1;
-    std::vector<uint32_t> words(3 * count);
-    DK_TRY(sa_check_device(ctx, d_text, d_off, count, off.back(), d_sa, words.data()));
-    for (size_t i = 0; i < count; ++i) {
-        const uint32_t *w = &words[3 * i];
-        const uint32_t kind = w[0] != 0xFFFFFFFFu ? DK_SA_BAD_RANGE : w[1] != 0xFFFFFFFFu ? DK_SA_NOT_PERMUTATION : w[2] != 0xFFFFFFFFu ? DK_SA_BAD_ORDER : DK_SA_OK;
-        verdict[i] = kind;
-        where[i] = kind == DK_SA_OK ? off[i + 1] - off[i] : w[kind - 1];
-    }
-    return DK_OK;
-}
-
-// pattern offsets (npat + 1 words) from the caller's lengths, and the checks on the batch
-struct Patterns {
-    std::vector<uint32_t> off;
-    size_t longest = 0, shortest = ~size_t(0);
-    size_t bytes() const { return off.back(); }
-};
-int check_patterns(dk_ctx *ctx, size_t npat, const size_t *pat_len, const uint32_t *pat_block, size_t count, Patterns &p) {
-    if (!pat_len) return ctx->fail(DK_E_ARG, "null pointer");
-    if (npat > 0xFFFFFFFEull) return ctx->fail(DK_E_ARG, "%zu patterns in one call", npat);
-    p.off.assign(npat + 1, 0);
-    uint64_t total = 0;
-    for (size_t q = 0; q < npat; ++q) {
-        if (pat_block && pat_block[q] >= count) return ctx->fail(DK_E_ARG, "pattern %zu names block %u of %zu", q, pat_block[q], count);
-        total += pat_len[q];
-        if (pat_len[q] > 0xFFFFFFFFull || total > 0xFFFFFFFFull) return ctx->fail(DK_E_ARG, "the patterns hold more than 2^32 - 1 bytes together");
-        p.off[q + 1] = static_cast<uint32_t>(total);
-        p.longest = std::max(p.longest, pat_len[q]);
-        p.shortest = std::min(p.shortest, pat_len[q]);
-    }
-    return DK_OK;
-}
-// offsets and blocks to the workspace (8 bytes per pattern), then the two kernels.  Synchronises: the copies read the caller's and `p`'s host memory.
-int sa_search_run(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, const uint32_t *d_sa, const uint8_t *d_pat, const Patterns &p,
-                  const uint32_t *pat_block, uint32_t *d_lo, uint32_t *d_hi) {
-    hipStream_t st = ctx->stream;
-    const size_t npat = p.off.size() - 1;
-    uint32_t *d_pat_off = ctx->ws_alloc<uint32_t>(npat + 1), *d_pat_blk = pat_block ? ctx->ws_alloc<uint32_t>(npat) : nullptr;
-    if (!d_pat_off || (pat_block && !d_pat_blk)) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(d_pat_off, p.off.data(), (npat + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    int rc = DK_OK;
-    if (pat_block) rc = ctx->hip_ok(hipMemcpyAsync(d_pat_blk, pat_block, npat * sizeof(uint32_t), hipMemcpyHostToDevice, st), "pattern blocks");
-    if (rc == DK_OK) rc = sa_search_device(ctx, d_text, d_off, d_sa, d_pat, d_pat_off, d_pat_blk, npat, p.longest, p.shortest, d_lo, d_hi);
-    const hipError_t e = hipStreamSynchronize(st);
-    DK_TRY(rc);
-    DK_HIP(ctx, e);
-    return DK_OK;
-}
-size_t ws_round(size_t bytes) { return (bytes + 255) & ~size_t(255); }
-}  // namespace
-
-extern "C" {
-
-int dk_dev_sa_check(dk_ctx *ctx, const uint8_t *d_in, size_t n, const uint32_t *d_sa, uint32_t *verdict, uint32_t *where) {
-    DK_TRY(begin_call(ctx, "dk_dev_sa_check"));
-    ScopedCall sc(ctx);
-    if (!d_in || !d_sa || !verdict || !where) return ctx->fail(DK_E_ARG, "null pointer");
-    DK_TRY(check_n(ctx, n));
-    Timer t;
-    uint32_t *d_off = nullptr;
-    DK_TRY(single_offsets(ctx, n, &d_off));
-    DK_TRY(sa_check_run(ctx, d_in, d_off, {0u, static_cast<uint32_t>(n)}, d_sa, verdict, where));
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-int dk_sa_check(dk_ctx *ctx, const uint8_t *in, size_t n, const uint32_t *sa, uint32_t *verdict, uint32_t *where) {
-    DK_TRY(begin_call(ctx, "dk_sa_check"));
-    ScopedCall sc(ctx);
-    if (!in || !sa || !verdict || !where) return ctx->fail(DK_E_ARG, "null pointer");
-    DK_TRY(check_n(ctx, n));
-    Timer t;
-    hipStream_t st = ctx->stream;
-    uint8_t *d_text = ctx->ws_alloc<uint8_t>(n);
-    uint32_t *d_sa = ctx->ws_alloc<uint32_t>(n), *d_off = nullptr;
-    if (!d_text || !d_sa) return DK_E_NOMEM;
-    DK_TRY(single_offsets(ctx, n, &d_off));
-    DK_HIP(ctx, hipMemcpyAsync(d_text, in, n, hipMemcpyHostToDevice, st));
-    DK_HIP(ctx, hipMemcpyAsync(d_sa, sa, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    DK_TRY(sa_check_run(ctx, d_text, d_off, {0u, static_cast<uint32_t>(n)}, d_sa, verdict, where));
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-int dk_dev_sa_check_packed(dk_ctx *ctx, const uint8_t *d_in, size_t count, const size_t *n, const uint32_t *d_sa, uint32_t *verdict, uint32_t *where) {
-    DK_TRY(begin_call(ctx, "dk_dev_sa_check_packed"));
-    ScopedCall sc(ctx);
-    if (!d_in || !n || !d_sa || !verdict || !where) return ctx->fail(DK_E_ARG, "null pointer");
-    std::vector<uint32_t> off;
-    DK_TRY(check_pack(ctx, count, n, off));
-    Timer t;
-    hipStream_t st = ctx->stream;
-    uint32_t *d_off = ctx->ws_alloc<uint32_t>(count + 1);
-    if (!d_off) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    const int rc = sa_check_run(ctx, d_in, d_off, off, d_sa, verdict, where);
-    const hipError_t e = hipStreamSynchronize(st);  // (also on failure: the copy above reads `off`)
-    DK_TRY(rc);
-    DK_HIP(ctx, e);
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-int dk_dev_sa_search(dk_ctx *ctx, const uint8_t *d_in, size_t n, const uint32_t *d_sa, const uint8_t *d_pat, size_t npat, const size_t *pat_len,
-                     uint32_t *d_lo, uint32_t *d_hi) {
-    DK_TRY(begin_call(ctx, "dk_dev_sa_search"));
-    ScopedCall sc(ctx);
-    if (!d_in || !d_sa) return ctx->fail(DK_E_ARG, "null pointer");
-    DK_TRY(check_n(ctx, n));
-    if (npat == 0) return DK_OK;
-    Timer t;
-    Patterns p;
-    DK_TRY(check_patterns(ctx, npat, pat_len, nullptr, 1, p));
-    if ((!d_pat && p.bytes()) || !d_lo || !d_hi) return ctx->fail(DK_E_ARG, "null pointer");
-    uint32_t *d_off = nullptr;
-    DK_TRY(single_offsets(ctx, n, &d_off));
-    DK_TRY(sa_search_run(ctx, d_in, d_off, d_sa, d_pat, p, nullptr, d_lo, d_hi));
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-int dk_sa_search(dk_ctx *ctx, const uint8_t *in, size_t n, const uint32_t *sa, const uint8_t *pat, size_t npat, const size_t *pat_len, uint32_t *lo,
-                 uint32_t *hi) {
-    DK_TRY(begin_call(ctx, "dk_sa_search"));
-    ScopedCall sc(ctx);
-    if (!in || !sa) return ctx->fail(DK_E_ARG, "null pointer");
-    DK_TRY(check_n(ctx, n));
-    if (npat == 0) return DK_OK;
-    Timer t;
-    Patterns p;
-    DK_TRY(check_patterns(ctx, npat, pat_len, nullptr, 1, p));
-    if ((!pat && p.bytes()) || !lo || !hi) return ctx->fail(DK_E_ARG, "null pointer");
-    // text n, SA 4 n, the two offsets of the block; then the patterns, their offsets and the two results
-    const size_t need = ws_round(n) + ws_round(4 * n) + 256 + ws_round(p.bytes()) + ws_round(4 * (npat + 1)) + 2 * ws_round(4 * npat);
-    if (need > ctx->ws_size) return ctx->fail(DK_E_ARG, "%zu patterns of %zu bytes and their offsets do not fit the workspace beside the block", npat, p.bytes());
-    hipStream_t st = ctx->stream;
-    uint8_t *d_text = ctx->ws_alloc<uint8_t>(n), *d_pat = ctx->ws_alloc<uint8_t>(std::max<size_t>(p.bytes(), 1));
-    uint32_t *d_sa = ctx->ws_alloc<uint32_t>(n), *d_lo = ctx->ws_alloc<uint32_t>(npat), *d_hi = ctx->ws_alloc<uint32_t>(npat), *d_off = nullptr;
-    if (!d_text || !d_pat || !d_sa || !d_lo || !d_hi) return DK_E_NOMEM;
-    DK_TRY(single_offsets(ctx, n, &d_off));
-    DK_HIP(ctx, hipMemcpyAsync(d_text, in, n, hipMemcpyHostToDevice, st));
-    DK_HIP(ctx, hipMemcpyAsync(d_sa, sa, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    if (p.bytes()) DK_HIP(ctx, hipMemcpyAsync(d_pat, pat, p.bytes(), hipMemcpyHostToDevice, st));
-    DK_TRY(sa_search_run(ctx, d_text, d_off, d_sa, d_pat, p, nullptr, d_lo, d_hi));
-    DK_HIP(ctx, hipMemcpyAsync(lo, d_lo, npat * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipMemcpyAsync(hi, d_hi, npat * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipStreamSynchronize(st));
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-int dk_dev_sa_search_packed(dk_ctx *ctx, const uint8_t *d_in, size_t count, const size_t *n, const uint32_t *d_sa, const uint8_t *d_pat, size_t npat,
-                            const size_t *pat_len, const uint32_t *pat_block, uint32_t *d_lo, uint32_t *d_hi) {
-    DK_TRY(begin_call(ctx, "dk_dev_sa_search_packed"));
-    ScopedCall sc(ctx);
-    if (!d_in || !n || !d_sa) return ctx->fail(DK_E_ARG, "null pointer");
-    std::vector<uint32_t> off;
-    DK_TRY(check_pack(ctx, count, n, off));
-    if (npat == 0) return DK_OK;
-    if (!pat_block) return ctx->fail(DK_E_ARG, "null pointer");
-    Timer t;
-    Patterns p;
-    DK_TRY(check_patterns(ctx, npat, pat_len, pat_block, count, p));
-    if ((!d_pat && p.bytes()) || !d_lo || !d_hi) return ctx->fail(DK_E_ARG, "null pointer");
-    hipStream_t st = ctx->stream;
-    uint32_t *d_off = ctx->ws_alloc<uint32_t>(count + 1);
-    if (!d_off) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    const int rc = sa_search_run(ctx, d_in, d_off, d_sa, d_pat, p, pat_block, d_lo, d_hi);
-    const hipError_t e = hipStreamSynchronize(st);  // (also on failure: the copy above reads `off`)
-    DK_TRY(rc);
-    DK_HIP(ctx, e);
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-// ---- FM-index (csrc/fm_index.hip).  Served by contexts of either purpose: begin_call without a forward entry. --------
-}  // extern "C"
-
-namespace {
-bool fm_good_index(const void *d_index) { return d_index && (reinterpret_cast<uintptr_t>(d_index) & 3) == 0; }
-// offsets and blocks of the patterns to the workspace (8 bytes per pattern), then the kernel.  Synchronises, as sa_search_run does.
-int fm_count_run(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, const void *d_index, const uint8_t *d_pat,
-                 const Patterns &p, const uint32_t *pat_block, uint32_t *d_lo, uint32_t *d_hi) {
-    hipStream_t st = ctx->stream;
-    const size_t npat = p.off.size() - 1;
-    uint32_t *d_pat_off = ctx->ws_alloc<uint32_t>(npat + 1), *d_pat_blk = pat_block ? ctx->ws_alloc<uint32_t>(npat) : nullptr;
-    if (!d_pat_off || (pat_block && !d_pat_blk)) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(d_pat_off, p.off.data(), (npat + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    int rc = DK_OK;
-    if (pat_block) rc = ctx->hip_ok(hipMemcpyAsync(d_pat_blk, pat_block, npat * sizeof(uint32_t), hipMemcpyHostToDevice, st), "pattern blocks");
-    if (rc == DK_OK) rc = fm_count_device(ctx, d_bwt, d_off, count, total, d_index, d_pat, d_pat_off, d_pat_blk, npat, p.bytes(), d_lo, d_hi);
-    const hipError_t e = hipStreamSynchronize(st);
-    DK_TRY(rc);
-    DK_HIP(ctx, e);
-    return DK_OK;
-}
-}  // namespace
-
-extern "C" {
-
-size_t dk_fm_index_bytes(size_t total, size_t count) {
-    if (total == 0 || total > 0x7FFFFFFEull || count == 0 || count > DK_PACKED_MAX_BLOCKS || count > total) return 0;
-    return fm_index_words(total, count) * sizeof(uint32_t);
-}
-
-int dk_dev_fm_build(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t origin, void *d_index) {
-    DK_TRY(begin_call(ctx));
-    ScopedCall sc(ctx);
-    if (!d_bwt || !d_index) return ctx->fail(DK_E_ARG, "null pointer");
-    if (!fm_good_index(d_index)) return ctx->fail(DK_E_ARG, "the index is not 4-byte aligned");
-    DK_TRY(check_n(ctx, n));
-    if (origin >= n) return ctx->fail(DK_E_ARG, "origin %u is outside the block of %zu bytes", origin, n);
-    Timer t;
-    DK_TRY(fm_build_device(ctx, d_bwt, {0u, static_cast<uint32_t>(n)}, &origin, d_index));
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-int dk_dev_fm_build_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const uint32_t *origin, void *d_index) {
-    DK_TRY(begin_call(ctx));
-    ScopedCall sc(ctx);
-    if (!d_bwt || !n || !origin || !d_index) return ctx->fail(DK_E_ARG, "null pointer");
-    if (!fm_good_index(d_index)) return ctx->fail(DK_E_ARG, "the index is not 4-byte aligned");
-    std::vector<uint32_t> off;
-    DK_TRY(check_pack(ctx, count, n, off));
-    for (size_t i = 0; i < count; ++i)
-        if (origin[i] >= n[i]) return ctx->fail(DK_E_ARG, "origin %u of block %zu is outside its %zu bytes", origin[i], i, n[i]);
-    Timer t;
-    DK_TRY(fm_build_device(ctx, d_bwt, off, origin, d_index));
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-int dk_dev_fm_count(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, const void *d_index, const uint8_t *d_pat, size_t npat, const size_t *pat_len,
-                    uint32_t *d_lo, uint32_t *d_hi) {
-    DK_TRY(begin_call(ctx));
-    ScopedCall sc(ctx);
-    if (!d_bwt || !d_index) return ctx->fail(DK_E_ARG, "null pointer");
-    if (!fm_good_index(d_index)) return ctx->fail(DK_E_ARG, "the index is not 4-byte aligned");
-    DK_TRY(check_n(ctx, n));
-    if (npat == 0) return DK_OK;
-    Timer t;
-    Patterns p;
-    DK_TRY(check_patterns(ctx, npat, pat_len, nullptr, 1, p));
-    if ((!d_pat && p.bytes()) || !d_lo || !d_hi) return ctx->fail(DK_E_ARG, "null pointer");
-    uint32_t *d_off = nullptr;
-    DK_TRY(single_offsets(ctx, n, &d_off));
-    DK_TRY(fm_count_run(ctx, d_bwt, d_off, 1, n, d_index, d_pat, p, nullptr, d_lo, d_hi));
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-int dk_dev_fm_count_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const void *d_index, const uint8_t *d_pat, size_t npat,
-                           const size_t *pat_len, const uint32_t *pat_block, uint32_t *d_lo, uint32_t *d_hi) {
-    DK_TRY(begin_call(ctx));
-    ScopedCall sc(ctx);
-    if (!d_bwt || !n || !d_index) return ctx->fail(DK_E_ARG, "null pointer");
-    if (!fm_good_index(d_index)) return ctx->fail(DK_E_ARG, "the index is not 4-byte aligned");
-    std::vector<uint32_t> off;
-    DK_TRY(check_pack(ctx, count, n, off));
-    if (npat == 0) return DK_OK;
-    if (!pat_block) return ctx->fail(DK_E_ARG, "null pointer");
-    Timer t;
-    Patterns p;
-    DK_TRY(check_patterns(ctx, npat, pat_len, pat_block, count, p));
-    if ((!d_pat && p.bytes()) || !d_lo || !d_hi) return ctx->fail(DK_E_ARG, "null pointer");
-    hipStream_t st = ctx->stream;
-    uint32_t *d_off = ctx->ws_alloc<uint32_t>(count + 1);
-    if (!d_off) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    const int rc = fm_count_run(ctx, d_bwt, d_off, count, off.back(), d_index, d_pat, p, pat_block, d_lo, d_hi);
-    const hipError_t e = hipStreamSynchronize(st);  // (also on failure: the copy above reads `off`)
-    DK_TRY(rc);
-    DK_HIP(ctx, e);
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-int dk_fm_count(dk_ctx *ctx, const uint8_t *bwt, size_t n, uint32_t origin, const uint8_t *pat, size_t npat, const size_t *pat_len, uint32_t *lo,
-                uint32_t *hi) {
-    DK_TRY(begin_call(ctx));
-    ScopedCall sc(ctx);
-    if (!bwt) return ctx->fail(DK_E_ARG, "null pointer");
-    DK_TRY(check_n(ctx, n));
-    if (origin >= n) return ctx->fail(DK_E_ARG, "origin %u is outside the block of %zu bytes", origin, n);
-    if (npat == 0) return DK_OK;
-    Timer t;
-    Patterns p;
-    DK_TRY(check_patterns(ctx, npat, pat_len, nullptr, 1, p));
-    if ((!pat && p.bytes()) || !lo || !hi) return ctx->fail(DK_E_ARG, "null pointer");
-    // L n, the index, the two offsets of the block; then the patterns, their offsets and the two results; the build's workspace while it runs
-    const size_t index_bytes = fm_index_words(n, 1) * sizeof(uint32_t);
-    const size_t need = ws_round(n) + ws_round(index_bytes) + 256 + ws_round(p.bytes()) + ws_round(4 * (npat + 1)) + 2 * ws_round(4 * npat) + fm_build_workspace(n, 1);
-    if (need > ctx->ws_size) return ctx->fail(DK_E_ARG, "%zu patterns of %zu bytes and their offsets do not fit the workspace beside L and its index", npat, p.bytes());
-    hipStream_t st = ctx->stream;
-    uint8_t *d_bwt = ctx->ws_alloc<uint8_t>(n), *d_pat = ctx->ws_alloc<uint8_t>(std::max<size_t>(p.bytes(), 1));
-    uint32_t *d_index = ctx->ws_alloc<uint32_t>(index_bytes / sizeof(uint32_t)), *d_lo = ctx->ws_alloc<uint32_t>(npat), *d_hi = ctx->ws_alloc<uint32_t>(npat);
-    uint32_t *d_off = nullptr;
-    if (!d_bwt || !d_pat || !d_index || !d_lo || !d_hi) return DK_E_NOMEM;
-    DK_TRY(single_offsets(ctx, n, &d_off));
-    DK_HIP(ctx, hipMemcpyAsync(d_bwt, bwt, n, hipMemcpyHostToDevice, st));
-    if (p.bytes()) DK_HIP(ctx, hipMemcpyAsync(d_pat, pat, p.bytes(), hipMemcpyHostToDevice, st));
-    DK_TRY(fm_build_device(ctx, d_bwt, {0u, static_cast<uint32_t>(n)}, &origin, d_index));
-    DK_TRY(fm_count_run(ctx, d_bwt, d_off, 1, n, d_index, d_pat, p, nullptr, d_lo, d_hi));
-    DK_HIP(ctx, hipMemcpyAsync(lo, d_lo, npat * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipMemcpyAsync(hi, d_hi, npat * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipStreamSynchronize(st));
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-// ---- locate: a sampled suffix array beside the index, built from (L, origin) alone ------------------------------------
-}  // extern "C"
-
-namespace {
-bool fm_good_step(uint32_t step) { return step >= 1 && step <= 4096 && (step & (step - 1)) == 0; }
-int fm_locate_args(dk_ctx *ctx, uint32_t step, const void *d_loc) {
-    if (!fm_good_step(step)) return ctx->fail(DK_E_ARG, "the sampling step %u is no power of two in [1, 4096]", step);
-    if (!fm_good_index(d_loc)) return ctx->fail(DK_E_ARG, "the locate structure is not 4-byte aligned");
-    return DK_OK;
-}
-int fm_locate_hits(dk_ctx *ctx, size_t npat, size_t max_hits) {
-    if (max_hits == 0 || npat > 0xFFFFFFFEull || max_hits > (size_t(1) << 31) || npat * max_hits > (size_t(1) << 31))
-        return ctx->fail(DK_E_ARG, "%zu patterns of at most %zu hits: 1 .. 2^31 positions in all", npat, max_hits);
-    return DK_OK;
-}
-}  // namespace
-
-extern "C" {
-
-size_t dk_fm_locate_bytes(size_t total, size_t count, uint32_t step) {
-    if (dk_fm_index_bytes(total, count) == 0 || !fm_good_step(step)) return 0;
-    return fm_locate_words(total, count, step) * sizeof(uint32_t);
-}
-
-int dk_dev_fm_locate_build(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t origin, uint32_t step, void *d_loc) {
-    DK_TRY(begin_call(ctx));
-    ScopedCall sc(ctx);
-    if (!d_bwt || !d_loc) return ctx->fail(DK_E_ARG, "null pointer");
-    DK_TRY(fm_locate_args(ctx, step, d_loc));
-    DK_TRY(check_n(ctx, n));
-    if (origin >= n) return ctx->fail(DK_E_ARG, "origin %u is outside the block of %zu bytes", origin, n);
-    Timer t;
-    DK_TRY(fm_locate_build_device(ctx, d_bwt, {0u, static_cast<uint32_t>(n)}, &origin, step, d_loc, false));
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-int dk_dev_fm_locate_build_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const uint32_t *origin, uint32_t step, void *d_loc) {
-    DK_TRY(begin_call(ctx));
-    ScopedCall sc(ctx);
-    if (!d_bwt || !n || !origin || !d_loc) return ctx->fail(DK_E_ARG, "null pointer");
-    DK_TRY(fm_locate_args(ctx, step, d_loc));
-    std::vector<uint32_t> off;
-    DK_TRY(check_pack(ctx, count, n, off));
-    for (size_t i = 0; i < count; ++i)
-        if (origin[i] >= n[i]) return ctx->fail(DK_E_ARG, "origin %u of block %zu is outside its %zu bytes", origin[i], i, n[i]);
-    Timer t;
-    DK_TRY(fm_locate_build_device(ctx, d_bwt, off, origin, step, d_loc, true));
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-int dk_dev_fm_locate(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, const void *d_index, const void *d_loc, uint32_t step, const uint32_t *d_lo,
-                     const uint32_t *d_hi, size_t npat, size_t max_hits, uint32_t *d_pos) {
-    DK_TRY(begin_call(ctx));
-    ScopedCall sc(ctx);
-    if (!d_bwt || !d_index || !d_loc) return ctx->fail(DK_E_ARG, "null pointer");
-    if (!fm_good_index(d_index)) return ctx->fail(DK_E_ARG, "the index is not 4-byte aligned");
-    DK_TRY(fm_locate_args(ctx, step, d_loc));
-    DK_TRY(check_n(ctx, n));
-    if (npat == 0) return DK_OK;
-    DK_TRY(fm_locate_hits(ctx, npat, max_hits));
-    if (!d_lo || !d_hi || !d_pos) return ctx->fail(DK_E_ARG, "null pointer");
-    if ((reinterpret_cast<uintptr_t>(d_lo) | reinterpret_cast<uintptr_t>(d_hi) | reinterpret_cast<uintptr_t>(d_pos)) & 3)
-        return ctx->fail(DK_E_ARG, "the ranges or the positions are not 4-byte aligned");
-    Timer t;
-    uint32_t *d_off = nullptr;
-    DK_TRY(single_offsets(ctx, n, &d_off));
-    DK_TRY(fm_locate_device(ctx, d_bwt, d_off, 1, n, d_index, d_loc, step, d_lo, d_hi, nullptr, npat, max_hits, d_pos));
-    DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-int dk_dev_fm_locate_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const void *d_index, const void *d_loc, uint32_t step,
-                            const uint32_t *d_lo, const uint32_t *d_hi, size_t npat, const uint32_t *pat_block, size_t max_hits, uint32_t *d_pos) {
-    DK_TRY(begin_call(ctx));
-    ScopedCall sc(ctx);
-    if (!d_bwt || !n || !d_index || !d_loc) return ctx->fail(DK_E_ARG, "null pointer");
-    if (!fm_good_index(d_index)) return ctx->fail(DK_E_ARG, "the index is not 4-byte aligned");
-    DK_TRY(fm_locate_args(ctx, step, d_loc));
-    std::vector<uint32_t> off;
-    DK_TRY(check_pack(ctx, count, n, off));
-    if (npat == 0) return DK_OK;
-    DK_TRY(fm_locate_hits(ctx, npat, max_hits));
-    if (!pat_block || !d_lo || !d_hi || !d_pos) return ctx->fail(DK_E_ARG, "null pointer");
-    if ((reinterpret_cast<uintptr_t>(d_lo) | reinterpret_cast<uintptr_t>(d_hi) | reinterpret_cast<uintptr_t>(d_pos)) & 3)
-        return ctx->fail(DK_E_ARG, "the ranges or the positions are not 4-byte aligned");
-    for (size_t q = 0; q < npat; ++q)
-        if (pat_block[q] >= count) return ctx->fail(DK_E_ARG, "pattern %zu names block %u of a pack of %zu", q, pat_block[q], count);
-    Timer t;
-    hipStream_t st = ctx->stream;
-    uint32_t *d_off = ctx->ws_alloc<uint32_t>(count + 1), *d_blk = ctx->ws_alloc<uint32_t>(npat);
-    if (!d_off || !d_blk) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    int rc = ctx->hip_ok(hipMemcpyAsync(d_blk, pat_block, npat * sizeof(uint32_t), hipMemcpyHostToDevice, st), "pattern blocks");
-    if (rc == DK_OK) rc = fm_locate_device(ctx, d_bwt, d_off, count, off.back(), d_index, d_loc, step, d_lo, d_hi, d_blk, npat, max_hits, d_pos);
-    const hipError_t e = hipStreamSynchronize(st);  // (also on failure: the copy above reads `off`)
-    DK_TRY(rc);
-    DK_HIP(ctx, e);
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-int dk_fm_locate(dk_ctx *ctx, const uint8_t *bwt, size_t n, uint32_t origin, uint32_t step, const uint8_t *pat, size_t npat, const size_t *pat_len,
-                 size_t max_hits, uint32_t *lo, uint32_t *hi, uint32_t *pos) {
-    DK_TRY(begin_call(ctx));
-    ScopedCall sc(ctx);
-    if (!bwt) return ctx->fail(DK_E_ARG, "null pointer");
-    if (!fm_good_step(step)) return ctx->fail(DK_E_ARG, "the sampling step %u is no power of two in [1, 4096]", step);
-    DK_TRY(check_n(ctx, n));
-    if (origin >= n) return ctx->fail(DK_E_ARG, "origin %u is outside the block of %zu bytes", origin, n);
-    if (npat == 0) return DK_OK;
-    DK_TRY(fm_locate_hits(ctx, npat, max_hits));
-    Timer t;
-    Patterns p;
-    DK_TRY(check_patterns(ctx, npat, pat_len, nullptr, 1, p));
-    if ((!pat && p.bytes()) || !lo || !hi || !pos) return ctx->fail(DK_E_ARG, "null pointer");
-    // L, the index, the structure and the block's two offsets; the patterns, their offsets, the two results and the positions; the larger of
-    // the two builds' workspaces while it runs
-    const size_t index_words = fm_index_words(n, 1), loc_words = fm_locate_words(n, 1, step), nitems = npat * max_hits;
-    const size_t need = ws_round(n) + ws_round(4 * index_words) + ws_round(4 * loc_words) + 256 + ws_round(p.bytes()) + ws_round(4 * (npat + 1)) +
-                        2 * ws_round(4 * npat) + ws_round(4 * nitems) + std::max(fm_build_workspace(n, 1), fm_locate_build_workspace(n, 1));
-    if (need > ctx->ws_size)
-        return ctx->fail(DK_E_ARG, "%zu patterns of %zu bytes with %zu positions each do not fit the workspace beside L, its index and the locate build",
-                         npat, p.bytes(), max_hits);
-    hipStream_t st = ctx->stream;
-    uint8_t *d_bwt = ctx->ws_alloc<uint8_t>(n), *d_pat = ctx->ws_alloc<uint8_t>(std::max<size_t>(p.bytes(), 1));
-    uint32_t *d_index = ctx->ws_alloc<uint32_t>(index_words), *d_loc = ctx->ws_alloc<uint32_t>(loc_words);
-    uint32_t *d_lo = ctx->ws_alloc<uint32_t>(npat), *d_hi = ctx->ws_alloc<uint32_t>(npat), *d_pos = ctx->ws_alloc<uint32_t>(nitems);
-    uint32_t *d_off = nullptr;
-    if (!d_bwt || !d_pat || !d_index || !d_loc || !d_lo || !d_hi || !d_pos) return DK_E_NOMEM;
-    DK_TRY(single_offsets(ctx, n, &d_off));
-    DK_HIP(ctx, hipMemcpyAsync(d_bwt, bwt, n, hipMemcpyHostToDevice, st));
-    if (p.bytes()) DK_HIP(ctx, hipMemcpyAsync(d_pat, pat, p.bytes(), hipMemcpyHostToDevice, st));
-    DK_TRY(fm_build_device(ctx, d_bwt, {0u, static_cast<uint32_t>(n)}, &origin, d_index));
-    DK_TRY(fm_locate_build_device(ctx, d_bwt, {0u, static_cast<uint32_t>(n)}, &origin, step, d_loc, false));
-    DK_TRY(fm_count_run(ctx, d_bwt, d_off, 1, n, d_index, d_pat, p, nullptr, d_lo, d_hi));
-    DK_TRY(fm_locate_device(ctx, d_bwt, d_off, 1, n, d_index, d_loc, step, d_lo, d_hi, nullptr, npat, max_hits, d_pos));
-    DK_HIP(ctx, hipMemcpyAsync(lo, d_lo, npat * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipMemcpyAsync(hi, d_hi, npat * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipMemcpyAsync(pos, d_pos, nitems * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipStreamSynchronize(st));
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-// ---- extract: text ranges from L, the index and the anchors, built from (L, origin) alone ----------------------------
-}  // extern "C"
-
-namespace {
-int fm_extract_args(dk_ctx *ctx, uint32_t step, const void *d_ext) {
-    if (!fm_good_step(step)) return ctx->fail(DK_E_ARG, "the sampling step %u is no power of two in [1, 4096]", step);
-    if (!fm_good_index(d_ext)) return ctx->fail(DK_E_ARG, "the extract structure is not 4-byte aligned");
-    return DK_OK;
-}
-int fm_extract_rows(dk_ctx *ctx, size_t nrange, size_t max_len) {
-    if (max_len == 0 || nrange > 0xFFFFFFFEull || max_len > (size_t(1) << 31) || nrange * max_len > (size_t(1) << 31))
-        return ctx->fail(DK_E_ARG, "%zu ranges of at most %zu bytes: 1 .. 2^31 bytes in all", nrange, max_len);
-    return DK_OK;
-}
-}  // namespace
-
-extern "C" {
-
-size_t dk_fm_extract_bytes(size_t total, size_t count, uint32_t step) {
-    if (dk_fm_index_bytes(total, count) == 0 || !fm_good_step(step)) return 0;
-    return fm_extract_words(total, count, step) * sizeof(uint32_t);
-}
-
-int dk_dev_fm_extract_build(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t origin, uint32_t step, void *d_ext) {
-    DK_TRY(begin_call(ctx));
-    ScopedCall sc(ctx);
-    if (!d_bwt || !d_ext) return ctx->fail(DK_E_ARG, "null pointer");
-    DK_TRY(fm_extract_args(ctx, step, d_ext));
-    DK_TRY(check_n(ctx, n));
-    if (origin >= n) return ctx->fail(DK_E_ARG, "origin %u is outside the block of %zu bytes", origin, n);
-    Timer t;
-    DK_TRY(fm_extract_build_device(ctx, d_bwt, {0u, static_cast<uint32_t>(n)}, &origin, step, d_ext, false));
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-int dk_dev_fm_extract_build_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const uint32_t *origin, uint32_t step, void *d_ext) {
-    DK_TRY(begin_call(ctx));
-    ScopedCall sc(ctx);
-    if (!d_bwt || !n || !origin || !d_ext) return ctx->fail(DK_E_ARG, "null pointer");
-    DK_TRY(fm_extract_args(ctx, step, d_ext));
-    std::vector<uint32_t> off;
-    DK_TRY(check_pack(ctx, count, n, off));
-    for (size_t i = 0; i < count; ++i)
-        if (origin[i] >= n[i]) return ctx->fail(DK_E_ARG, "origin %u of block %zu is outside its %zu bytes", origin[i], i, n[i]);
-    Timer t;
-    DK_TRY(fm_extract_build_device(ctx, d_bwt, off, origin, step, d_ext, true));
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-int dk_dev_fm_extract(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, const void *d_index, const void *d_ext, uint32_t step, const uint32_t *d_pos,
-                      const uint32_t *d_len, size_t nrange, size_t max_len, uint8_t *d_out) {
-    DK_TRY(begin_call(ctx));
-    ScopedCall sc(ctx);
-    if (!d_bwt || !d_index || !d_ext) return ctx->fail(DK_E_ARG, "null pointer");
-    if (!fm_good_index(d_index)) return ctx->fail(DK_E_ARG, "the index is not 4-byte aligned");
-    DK_TRY(fm_extract_args(ctx, step, d_ext));
-    DK_TRY(check_n(ctx, n));
-    if (nrange == 0) return DK_OK;
-    DK_TRY(fm_extract_rows(ctx, nrange, max_len));
-    if (!d_pos || !d_out) return ctx->fail(DK_E_ARG, "null pointer");  // (d_len may be null: every range max_len long)
-    if ((reinterpret_cast<uintptr_t>(d_pos) | reinterpret_cast<uintptr_t>(d_len)) & 3)
-        return ctx->fail(DK_E_ARG, "the positions or the lengths are not 4-byte aligned");
-    Timer t;
-    uint32_t *d_off = nullptr;
-    DK_TRY(single_offsets(ctx, n, &d_off));
-    DK_TRY(fm_extract_device(ctx, d_bwt, d_off, nullptr, 1, n, d_index, d_ext, step, d_pos, d_len, nullptr, nrange, max_len, d_out));
-    DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-int dk_dev_fm_extract_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const void *d_index, const void *d_ext, uint32_t step,
-                             const uint32_t *d_pos, const uint32_t *d_len, size_t nrange, const uint32_t *range_block, size_t max_len, uint8_t *d_out) {
-    DK_TRY(begin_call(ctx));
-    ScopedCall sc(ctx);
-    if (!d_bwt || !n || !d_index || !d_ext) return ctx->fail(DK_E_ARG, "null pointer");
-    if (!fm_good_index(d_index)) return ctx->fail(DK_E_ARG, "the index is not 4-byte aligned");
-    DK_TRY(fm_extract_args(ctx, step, d_ext));
-    std::vector<uint32_t> off;
-    DK_TRY(check_pack(ctx, count, n, off));
-    if (nrange == 0) return DK_OK;
-    DK_TRY(fm_extract_rows(ctx, nrange, max_len));
-    if (!range_block || !d_pos || !d_out) return ctx->fail(DK_E_ARG, "null pointer");
-    if ((reinterpret_cast<uintptr_t>(d_pos) | reinterpret_cast<uintptr_t>(d_len)) & 3)
-        return ctx->fail(DK_E_ARG, "the positions or the lengths are not 4-byte aligned");
-    for (size_t q = 0; q < nrange; ++q)
-        if (range_block[q] >= count) return ctx->fail(DK_E_ARG, "range %zu names block %u of a pack of %zu", q, range_block[q], count);
-    Timer t;
-    hipStream_t st = ctx->stream;
-    // the offsets and the anchor bases in one array of 2 count + 1 words: off[0 .. count] | the base of every block
-    std::vector<uint32_t> geo(off);
-    const std::vector<uint32_t> abase = fm_extract_bases(off, step);
-    geo.insert(geo.end(), abase.begin(), abase.end() - 1);
-    uint32_t *d_geo = ctx->ws_alloc<uint32_t>(geo.size()), *d_blk = ctx->ws_alloc<uint32_t>(nrange);
-    if (!d_geo || !d_blk) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(d_geo, geo.data(), geo.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    int rc = ctx->hip_ok(hipMemcpyAsync(d_blk, range_block, nrange * sizeof(uint32_t), hipMemcpyHostToDevice, st), "range blocks");
-    if (rc == DK_OK)
-        rc = fm_extract_device(ctx, d_bwt, d_geo, d_geo + count + 1, count, off.back(), d_index, d_ext, step, d_pos, d_len, d_blk, nrange, max_len, d_out);
-    const hipError_t e = hipStreamSynchronize(st);  // (also on failure: the copies above read `geo` and `range_block`)
-    DK_TRY(rc);
-    DK_HIP(ctx, e);
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-int dk_fm_extract(dk_ctx *ctx, const uint8_t *bwt, size_t n, uint32_t origin, uint32_t step, const uint32_t *pos, const uint32_t *len, size_t nrange,
-                  size_t max_len, uint8_t *out) {
-    DK_TRY(begin_call(ctx));
-    ScopedCall sc(ctx);
-    if (!bwt) return ctx->fail(DK_E_ARG, "null pointer");
-    if (!fm_good_step(step)) return ctx->fail(DK_E_ARG, "the sampling step %u is no power of two in [1, 4096]", step);
-    DK_TRY(check_n(ctx, n));
-    if (origin >= n) return ctx->fail(DK_E_ARG, "origin %u is outside the block of %zu bytes", origin, n);
-    if (nrange == 0) return DK_OK;
-    DK_TRY(fm_extract_rows(ctx, nrange, max_len));
-    if (!pos || !out) return ctx->fail(DK_E_ARG, "null pointer");  // (len may be null)
-    Timer t;
-    // L, the index, the structure and the block's two offsets; the positions, the lengths and the rows; the larger of the two builds' workspaces
-    // while it runs
-    const size_t index_words = fm_index_words(n, 1), ext_words = fm_extract_words(n, 1, step), nbytes = nrange * max_len;
-    const size_t need = ws_round(n) + ws_round(4 * index_words) + ws_round(4 * ext_words) + 256 + 2 * ws_round(4 * nrange) + ws_round(nbytes) +
-                        std::max(fm_build_workspace(n, 1), fm_locate_build_workspace(n, 1) + ws_round(8));
-    if (need > ctx->ws_size)
-        return ctx->fail(DK_E_ARG, "%zu ranges of at most %zu bytes do not fit the workspace beside L, its index and the extract build", nrange, max_len);
-    hipStream_t st = ctx->stream;
-    uint8_t *d_bwt = ctx->ws_alloc<uint8_t>(n), *d_out = ctx->ws_alloc<uint8_t>(nbytes);
-    uint32_t *d_index = ctx->ws_alloc<uint32_t>(index_words), *d_ext = ctx->ws_alloc<uint32_t>(ext_words);
-    uint32_t *d_pos = ctx->ws_alloc<uint32_t>(nrange), *d_len = ctx->ws_alloc<uint32_t>(nrange);
-    uint32_t *d_off = nullptr;
-    if (!d_bwt || !d_out || !d_index || !d_ext || !d_pos || !d_len) return DK_E_NOMEM;
-    DK_TRY(single_offsets(ctx, n, &d_off));
-    DK_HIP(ctx, hipMemcpyAsync(d_bwt, bwt, n, hipMemcpyHostToDevice, st));
-    DK_HIP(ctx, hipMemcpyAsync(d_pos, pos, nrange * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    if (len) DK_HIP(ctx, hipMemcpyAsync(d_len, len, nrange * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    DK_TRY(fm_build_device(ctx, d_bwt, {0u, static_cast<uint32_t>(n)}, &origin, d_index));
-    DK_TRY(fm_extract_build_device(ctx, d_bwt, {0u, static_cast<uint32_t>(n)}, &origin, step, d_ext, false));
-    DK_TRY(fm_extract_device(ctx, d_bwt, d_off, nullptr, 1, n, d_index, d_ext, step, d_pos, len ? d_len : nullptr, nullptr, nrange, max_len, d_out));
-    DK_HIP(ctx, hipMemcpyAsync(out, d_out, nbytes, hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipStreamSynchronize(st));
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-// ---- find: every pattern in every block, as a compact list of hit records and the occurrence matrix ------------------
-}  // extern "C"
-
-namespace {
-// the checks the three entries share, in front of anything that touches the device
-int fm_find_args(dk_ctx *ctx, size_t npat, size_t count, size_t max_hits, const void *d_loc, uint32_t step, const void *hits, const uint64_t *total) {
-    if (!total) return ctx->fail(DK_E_ARG, "null pointer");
-    if (!fm_good_step(step)) return ctx->fail(DK_E_ARG, "the sampling step %u is no power of two in [1, 4096]", step);
-    if (max_hits > (size_t(1) << 31)) return ctx->fail(DK_E_ARG, "at most 2^31 hit records in one call, not %zu", max_hits);
-    if (npat > DK_FM_FIND_MAX_PAIRS || npat * count > DK_FM_FIND_MAX_PAIRS)
-        return ctx->fail(DK_E_ARG, "%zu patterns in %zu blocks: more than DK_FM_FIND_MAX_PAIRS pairs", npat, count);
-    if (max_hits) {
-        if (!hits) return ctx->fail(DK_E_ARG, "null pointer");
-        if (reinterpret_cast<uintptr_t>(hits) & 15) return ctx->fail(DK_E_ARG, "the hit records are not 16-byte aligned");
-        if (d_loc && !fm_good_index(d_loc)) return ctx->fail(DK_E_ARG, "the locate structure is not 4-byte aligned");
-    }
-    return DK_OK;
-}
-// the pattern offsets to the workspace, then the stage.  d_off: the blocks' offsets on the device (count + 1 words, enqueued by the caller).
-int fm_find_run(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total_bytes, const void *d_index, const void *d_loc,
-                uint32_t step, const uint8_t *d_pat, const Patterns &p, size_t max_hits, dk_fm_hit *d_hits, uint32_t *d_occ, uint64_t *total) {
-    const size_t npat = p.off.size() - 1;
-    uint32_t *d_pat_off = ctx->ws_alloc<uint32_t>(npat + 1);
-    if (!d_pat_off) return DK_E_NOMEM;
-    int rc = ctx->hip_ok(hipMemcpyAsync(d_pat_off, p.off.data(), (npat + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream), "pattern offsets");
-    if (rc == DK_OK)
-        rc = fm_find_device(ctx, d_bwt, d_off, count, total_bytes, d_index, d_loc, step, d_pat, d_pat_off, npat, p.bytes(), max_hits, d_hits, d_occ, total);
-    const hipError_t e = hipStreamSynchronize(ctx->stream);  // (also on failure: the copy above reads `p`)
-    DK_TRY(rc);
-    DK_HIP(ctx, e);
-    return DK_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int dk_dev_fm_find_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const void *d_index, const void *d_loc, uint32_t step,
-                          const uint8_t *d_pat, size_t npat, const size_t *pat_len, size_t max_hits, dk_fm_hit *d_hits, uint32_t *d_occ, uint64_t *total) {
-    DK_TRY(begin_call(ctx));
-    ScopedCall sc(ctx);
-    if (!d_bwt || !n || !d_index || (max_hits && !d_loc)) return ctx->fail(DK_E_ARG, "null pointer");
-    if (!fm_good_index(d_index)) return ctx->fail(DK_E_ARG, "the index is not 4-byte aligned");
-    std::vector<uint32_t> off;
-    DK_TRY(check_pack(ctx, count, n, off));
-    DK_TRY(fm_find_args(ctx, npat, count, max_hits, d_loc, step, d_hits, total));
-    if (d_occ && (reinterpret_cast<uintptr_t>(d_occ) & 3)) return ctx->fail(DK_E_ARG, "the occurrence matrix is not 4-byte aligned");
-    if (npat == 0) {
-        *total = 0;
-        return DK_OK;
-    }
-    Timer t;
-    Patterns p;
-    DK_TRY(check_patterns(ctx, npat, pat_len, nullptr, count, p));
-    if (!d_pat && p.bytes()) return ctx->fail(DK_E_ARG, "null pointer");
-    if (ws_round(4 * (count + 1)) + ws_round(4 * (npat + 1)) + fm_find_workspace(npat * count) > ctx->ws_size)
-        return ctx->fail(DK_E_ARG, "%zu patterns in %zu blocks do not fit the workspace (16 bytes per pair)", npat, count);
-    hipStream_t st = ctx->stream;
-    uint32_t *d_off = ctx->ws_alloc<uint32_t>(count + 1);
-    if (!d_off) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    const int rc = fm_find_run(ctx, d_bwt, d_off, count, off.back(), d_index, d_loc, step, d_pat, p, max_hits, d_hits, d_occ, total);
-    const hipError_t e = hipStreamSynchronize(st);  // (also on failure: the copy above reads `off`)
-    DK_TRY(rc);
-    DK_HIP(ctx, e);
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-int dk_dev_fm_find(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, const void *d_index, const void *d_loc, uint32_t step, const uint8_t *d_pat, size_t npat,
-                   const size_t *pat_len, size_t max_hits, dk_fm_hit *d_hits, uint32_t *d_occ, uint64_t *total) {
-    DK_TRY(begin_call(ctx));
-    ScopedCall sc(ctx);
-    if (!d_bwt || !d_index || (max_hits && !d_loc)) return ctx->fail(DK_E_ARG, "null pointer");
-    if (!fm_good_index(d_index)) return ctx->fail(DK_E_ARG, "the index is not 4-byte aligned");
-    DK_TRY(check_n(ctx, n));
-    DK_TRY(fm_find_args(ctx, npat, 1, max_hits, d_loc, step, d_hits, total));
-    if (d_occ && (reinterpret_cast<uintptr_t>(d_occ) & 3)) return ctx->fail(DK_E_ARG, "the occurrence matrix is not 4-byte aligned");
-    if (npat == 0) {
-        *total = 0;
-        return DK_OK;
-    }
-    Timer t;
-    Patterns p;
-    DK_TRY(check_patterns(ctx, npat, pat_len, nullptr, 1, p));
-    if (!d_pat && p.bytes()) return ctx->fail(DK_E_ARG, "null pointer");
-    if (256 + ws_round(4 * (npat + 1)) + fm_find_workspace(npat) > ctx->ws_size)
-        return ctx->fail(DK_E_ARG, "%zu patterns do not fit the workspace (16 bytes per pair)", npat);
-    uint32_t *d_off = nullptr;
-    DK_TRY(single_offsets(ctx, n, &d_off));
-    DK_TRY(fm_find_run(ctx, d_bwt, d_off, 1, n, d_index, d_loc, step, d_pat, p, max_hits, d_hits, d_occ, total));
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-int dk_fm_find(dk_ctx *ctx, const uint8_t *bwt, size_t n, uint32_t origin, uint32_t step, const uint8_t *pat, size_t npat, const size_t *pat_len,
-               size_t max_hits, dk_fm_hit *hits, uint32_t *occ, uint64_t *total) {
-    DK_TRY(begin_call(ctx));
-    ScopedCall sc(ctx);
-    if (!bwt) return ctx->fail(DK_E_ARG, "null pointer");
-    DK_TRY(check_n(ctx, n));
-    if (origin >= n) return ctx->fail(DK_E_ARG, "origin %u is outside the block of %zu bytes", origin, n);
-    if (!total) return ctx->fail(DK_E_ARG, "null pointer");
-    if (!fm_good_step(step)) return ctx->fail(DK_E_ARG, "the sampling step %u is no power of two in [1, 4096]", step);
-    if (max_hits > (size_t(1) << 31)) return ctx->fail(DK_E_ARG, "at most 2^31 hit records in one call, not %zu", max_hits);
-    if (npat > DK_FM_FIND_MAX_PAIRS) return ctx->fail(DK_E_ARG, "%zu patterns: more than DK_FM_FIND_MAX_PAIRS pairs", npat);
-    if (max_hits && !hits) return ctx->fail(DK_E_ARG, "null pointer");
-    if (npat == 0) {
-        *total = 0;
-        return DK_OK;
-    }
-    Timer t;
-    Patterns p;
-    DK_TRY(check_patterns(ctx, npat, pat_len, nullptr, 1, p));
-    if (!pat && p.bytes()) return ctx->fail(DK_E_ARG, "null pointer");
-    // L, the index, the structure (only where records are asked for) and the block's two offsets; the patterns, their offsets and the occurrence
-    // words; the larger of the builds' and the stage's workspaces.  The records come last, once their number is known.
-    const size_t index_words = fm_index_words(n, 1), loc_words = max_hits ? fm_locate_words(n, 1, step) : 0;
-    const size_t fixed = ws_round(n) + ws_round(4 * index_words) + ws_round(4 * loc_words) + 256 + ws_round(p.bytes()) + ws_round(4 * (npat + 1)) +
-                         ws_round(4 * npat);
-    const size_t need = fixed + std::max(fm_find_workspace(npat), std::max(fm_build_workspace(n, 1), max_hits ? fm_locate_build_workspace(n, 1) : 0));
-    if (need > ctx->ws_size)
-        return ctx->fail(DK_E_ARG, "%zu patterns of %zu bytes do not fit the workspace beside L, its index and the locate build", npat, p.bytes());
-    hipStream_t st = ctx->stream;
-    uint8_t *d_bwt = ctx->ws_alloc<uint8_t>(n), *d_pat = ctx->ws_alloc<uint8_t>(std::max<size_t>(p.bytes(), 1));
-    uint32_t *d_index = ctx->ws_alloc<uint32_t>(index_words), *d_loc = max_hits ? ctx->ws_alloc<uint32_t>(loc_words) : nullptr;
-    uint32_t *d_occ = ctx->ws_alloc<uint32_t>(npat), *d_pat_off = ctx->ws_alloc<uint32_t>(npat + 1), *d_off = nullptr;
-    if (!d_bwt || !d_pat || !d_index || (max_hits && !d_loc) || !d_occ || !d_pat_off) return DK_E_NOMEM;
-    DK_TRY(single_offsets(ctx, n, &d_off));
-    DK_HIP(ctx, hipMemcpyAsync(d_bwt, bwt, n, hipMemcpyHostToDevice, st));
-    if (p.bytes()) DK_HIP(ctx, hipMemcpyAsync(d_pat, pat, p.bytes(), hipMemcpyHostToDevice, st));
-    DK_TRY(fm_build_device(ctx, d_bwt, {0u, static_cast<uint32_t>(n)}, &origin, d_index));
-    if (max_hits) DK_TRY(fm_locate_build_device(ctx, d_bwt, {0u, static_cast<uint32_t>(n)}, &origin, step, d_loc, false));
-    // the count and the scan alone first: how many records there are decides what the records take
-    int rc = ctx->hip_ok(hipMemcpyAsync(d_pat_off, p.off.data(), (npat + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st), "pattern offsets");
-    if (rc == DK_OK) rc = fm_find_device(ctx, d_bwt, d_off, 1, n, d_index, nullptr, step, d_pat, d_pat_off, npat, p.bytes(), 0, nullptr, d_occ, total);
-    const hipError_t e = hipStreamSynchronize(st);  // (also on failure: the copy above reads `p`)
-    DK_TRY(rc);
-    DK_HIP(ctx, e);
-    const size_t nhits = static_cast<size_t>(std::min<uint64_t>(*total, max_hits));
-    if (nhits) {
-        if (ctx->ws_used + ws_round(16 * nhits) + fm_find_workspace(npat) > ctx->ws_size)
-            return ctx->fail(DK_E_ARG, "%zu hit records do not fit the workspace beside L, its index and the patterns", nhits);
-        dk_fm_hit *d_hits = ctx->ws_alloc<dk_fm_hit>(nhits);
-        if (!d_hits) return DK_E_NOMEM;
-        DK_TRY(fm_find_device(ctx, d_bwt, d_off, 1, n, d_index, d_loc, step, d_pat, d_pat_off, npat, p.bytes(), nhits, d_hits, nullptr, total));
-        DK_HIP(ctx, hipMemcpyAsync(hits, d_hits, nhits * sizeof(dk_fm_hit), hipMemcpyDeviceToHost, st));
-    }
-    if (occ) DK_HIP(ctx, hipMemcpyAsync(occ, d_occ, npat * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipStreamSynchronize(st));
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-// ---- seams: the matches that straddle the borders of a pack, with the bytes carried over from the text in front ---------
-}  // extern "C"
-
-namespace {
-// the checks of both entries behind the geometry, then the plan, the uploads and the stage.  off: the blocks' offsets (count + 1).
-int fm_seams_run(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector<uint32_t> &off, const void *d_index, const void *d_ext, uint32_t step,
-                 const uint8_t *d_prev, size_t prev_len, const uint8_t *d_pat, size_t npat, const size_t *pat_len, size_t max_hits, dk_fm_seam_hit *d_hits,
-                 uint32_t *d_occ, uint64_t *total) {
-    const size_t count = off.size() - 1;
-    if (!total) return ctx->fail(DK_E_ARG, "null pointer");
-    if (max_hits > (size_t(1) << 31)) return ctx->fail(DK_E_ARG, "at most 2^31 hit records in one call, not %zu", max_hits);
-    if (npat > DK_FM_FIND_MAX_PAIRS || npat * count > DK_FM_FIND_MAX_PAIRS)
-        return ctx->fail(DK_E_ARG, "%zu patterns at %zu borders: more than DK_FM_FIND_MAX_PAIRS pairs", npat, count);
-    if (max_hits && !d_hits) return ctx->fail(DK_E_ARG, "null pointer");
-    if (max_hits && (reinterpret_cast<uintptr_t>(d_hits) & 15)) return ctx->fail(DK_E_ARG, "the hit records are not 16-byte aligned");
-    if (d_occ && (reinterpret_cast<uintptr_t>(d_occ) & 3)) return ctx->fail(DK_E_ARG, "the occurrence matrix is not 4-byte aligned");
-    if (prev_len >= DK_FM_SEAM_MAX_PATTERN) return ctx->fail(DK_E_ARG, "%zu carried bytes: fewer than DK_FM_SEAM_MAX_PATTERN can matter", prev_len);
-    if (prev_len && !d_prev) return ctx->fail(DK_E_ARG, "null pointer");
-    if (npat == 0) {
-        *total = 0;
-        return DK_OK;
-    }
-    Patterns p;
-    DK_TRY(check_patterns(ctx, npat, pat_len, nullptr, count, p));
-    if (p.longest > DK_FM_SEAM_MAX_PATTERN) return ctx->fail(DK_E_ARG, "a pattern of %zu bytes: more than DK_FM_SEAM_MAX_PATTERN", p.longest);
-    if (!d_pat && p.bytes()) return ctx->fail(DK_E_ARG, "null pointer");
-    hipStream_t st = ctx->stream;
-    if (p.longest < 2) {  // no pattern can straddle a border
-        *total = 0;
-        if (d_occ) DK_HIP(ctx, hipMemsetAsync(d_occ, 0, npat * count * sizeof(uint32_t), st));
-        DK_HIP(ctx, hipStreamSynchronize(st));
-        return DK_OK;
-    }
-    const FmSeamPlan pl = fm_seam_plan(off, prev_len, p.longest - 1);
-    if (pl.strip_len > 0xFFFFFFFFull) return ctx->fail(DK_E_ARG, "the edge strip of %zu bytes cannot be addressed", pl.strip_len);
-    // the offsets and the anchor bases in one array of 2 count + 1 words, as dk_dev_fm_extract_packed lays them out
-    std::vector<uint32_t> geo(off);
-    const std::vector<uint32_t> abase = fm_extract_bases(off, step);
-    geo.insert(geo.end(), abase.begin(), abase.end() - 1);
-    if (ws_round(4 * geo.size()) + ws_round(4 * (npat + 1)) + fm_seams_workspace(pl, npat * count) > ctx->ws_size)
-        return ctx->fail(DK_E_ARG, "%zu patterns at %zu borders do not fit the workspace (a strip of %zu bytes, 52 bytes per block, 16 per pair)", npat,
-                         count, pl.strip_len);
-    uint32_t *d_geo = ctx->ws_alloc<uint32_t>(geo.size()), *d_pat_off = ctx->ws_alloc<uint32_t>(npat + 1);
-    if (!d_geo || !d_pat_off) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(d_geo, geo.data(), geo.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    int rc = ctx->hip_ok(hipMemcpyAsync(d_pat_off, p.off.data(), (npat + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st), "pattern offsets");
-    if (rc == DK_OK)
-        rc = fm_seams_device(ctx, d_bwt, d_geo, d_geo + count + 1, count, off.back(), d_index, d_ext, step, d_prev, prev_len, pl, d_pat, d_pat_off, npat,
-                             p.bytes(), max_hits, d_hits, d_occ, total);
-    const hipError_t e = hipStreamSynchronize(st);  // (also on failure: the copies above read `geo`, `p` and `pl`)
-    DK_TRY(rc);
-    DK_HIP(ctx, e);
-    return DK_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int dk_dev_fm_seams_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const void *d_index, const void *d_ext, uint32_t step,
-                           const uint8_t *d_prev, size_t prev_len, const uint8_t *d_pat, size_t npat, const size_t *pat_len, size_t max_hits,
-                           dk_fm_seam_hit *d_hits, uint32_t *d_occ, uint64_t *total) {
-    DK_TRY(begin_call(ctx));
-    ScopedCall sc(ctx);
-    if (!d_bwt || !n || !d_index || !d_ext) return ctx->fail(DK_E_ARG, "null pointer");
-    if (!fm_good_index(d_index)) return ctx->fail(DK_E_ARG, "the index is not 4-byte aligned");
-    DK_TRY(fm_extract_args(ctx, step, d_ext));
-    std::vector<uint32_t> off;
-    DK_TRY(check_pack(ctx, count, n, off));
-    Timer t;
-    DK_TRY(fm_seams_run(ctx, d_bwt, off, d_index, d_ext, step, d_prev, prev_len, d_pat, npat, pat_len, max_hits, d_hits, d_occ, total));
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-int dk_dev_fm_seams(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, const void *d_index, const void *d_ext, uint32_t step, const uint8_t *d_prev,
-                    size_t prev_len, const uint8_t *d_pat, size_t npat, const size_t *pat_len, size_t max_hits, dk_fm_seam_hit *d_hits, uint32_t *d_occ,
-                    uint64_t *total) {
-    DK_TRY(begin_call(ctx));
-    ScopedCall sc(ctx);
-    if (!d_bwt || !d_index || !d_ext) return ctx->fail(DK_E_ARG, "null pointer");
-    if (!fm_good_index(d_index)) return ctx->fail(DK_E_ARG, "the index is not 4-byte aligned");
-    DK_TRY(fm_extract_args(ctx, step, d_ext));
-    DK_TRY(check_n(ctx, n));
-    Timer t;
-    DK_TRY(fm_seams_run(ctx, d_bwt, {0u, static_cast<uint32_t>(n)}, d_index, d_ext, step, d_prev, prev_len, d_pat, npat, pat_len, max_hits, d_hits,
-                        d_occ, total));
-    ctx->stats.ms_total = t.ms();
-    return DK_OK;
-}
-
-int dk_dbg_dev_fm_rank(dk_ctx *ctx, const uint8_t *d_bwt, size_t total, const void *d_index, const uint32_t *d_pos, const uint8_t *d_sym, size_t nq,
-                       uint32_t *d_out) {
-    DK_TRY(begin_call(ctx));
-    ScopedCall sc(ctx);
-    if (!d_bwt || !d_index) return ctx->fail(DK_E_ARG, "null pointer");
-    if (!fm_good_index(d_index)) return ctx->fail(DK_E_ARG, "the index is not 4-byte aligned");
-    DK_TRY(check_n(ctx, total));
-    if (nq == 0) return DK_OK;
-    if (!d_pos || !d_sym || !d_out || nq > 0xFFFFFFFEull) return ctx->fail(DK_E_ARG, "null pointer");
-    DK_TRY(fm_rank_device(ctx, d_bwt, total, d_index, d_pos, d_sym, nq, d_out));
-    DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return DK_OK;
-}
-
 // ---- host-pointer entry points: stage in, run the device path, stage out ---------------------------------------------
 int dk_suffix_array(dk_ctx *ctx, const uint8_t *in, size_t n, uint32_t *sa_out) {
     DK_TRY(begin_call(ctx, "dk_suffix_array"));
     ScopedCall sc(ctx);
+    Upload up(ctx);
     if (!in || !sa_out) return ctx->fail(DK_E_ARG, "null pointer");
     DK_TRY(check_n(ctx, n));
     Timer t;
     uint8_t *d_text = ctx->ws_alloc<uint8_t>(n);
     uint32_t *d_sa = ctx->ws_alloc<uint32_t>(n);
     if (!d_text || !d_sa) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(d_text, in, n, hipMemcpyHostToDevice, ctx->stream));
+    DK_TRY(up.copy(d_text, in, n, "text"));
     DK_TRY(suffix_array_device(ctx, d_text, n, d_sa));
     DK_HIP(ctx, hipMemcpyAsync(sa_out, d_sa, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    DK_TRY(up.sync());
     ctx->stats.ms_total = t.ms();
     return DK_OK;
 }
@@ -2077,21 +1037,20 @@ int dk_suffix_array_packed(dk_ctx *ctx, const uint8_t *in, size_t count, const s
     DK_TRY(begin_call(ctx, "dk_suffix_array_packed"));
     ScopedCall sc(ctx);
     if (!in || !n || !sa_out) return ctx->fail(DK_E_ARG, "null pointer");
-    std::vector<uint32_t> off;
-    DK_TRY(check_pack(ctx, count, n, off));
+    Layout lay(count, n);
+    DK_TRY(lay.check(ctx));
+    std::vector<std::pair<size_t, uint32_t>> fixed;
+    Upload up(ctx);
     Timer t;
     hipStream_t st = ctx->stream;
-    const size_t total = off.back();
-    uint8_t *d_text = ctx->ws_alloc<uint8_t>(total);
+    const size_t total = lay.total();
+    const uint8_t *d_text = up.stage(in, total, "text");
     uint32_t *d_sa = ctx->ws_alloc<uint32_t>(total);
-    uint32_t *d_off = ctx->ws_alloc<uint32_t>(count + 1);
-    if (!d_text || !d_sa || !d_off) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(d_text, in, total, hipMemcpyHostToDevice, st));
-    DK_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (count + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    std::vector<std::pair<size_t, uint32_t>> fixed;
-    DK_TRY(packed_forward(ctx, d_text, off, d_off, nullptr, nullptr, &fixed, d_sa));
+    const uint32_t *d_off = lay.device(up);
+    if (!d_text || !d_sa || !d_off) return up.failed();
+    DK_TRY(packed_forward(ctx, d_text, lay.off(), d_off, nullptr, nullptr, &fixed, d_sa));
     DK_HIP(ctx, hipMemcpyAsync(sa_out, d_sa, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    DK_HIP(ctx, hipStreamSynchronize(st));
+    DK_TRY(up.sync());
     ctx->stats.ms_total = t.ms();
     return DK_OK;
 }
@@ -2099,6 +1058,7 @@ int dk_suffix_array_packed(dk_ctx *ctx, const uint8_t *in, size_t count, const s
 int dk_bwt_forward(dk_ctx *ctx, const uint8_t *in, size_t n, uint8_t *bwt_out, uint32_t *origin) {
     DK_TRY(begin_call(ctx, "dk_bwt_forward"));
     ScopedCall sc(ctx);
+    Upload up(ctx);
     if (!in || !bwt_out || !origin) return ctx->fail(DK_E_ARG, "null pointer");
     DK_TRY(check_n(ctx, n));
     Timer t;
@@ -2106,10 +1066,10 @@ int dk_bwt_forward(dk_ctx *ctx, const uint8_t *in, size_t n, uint8_t *bwt_out, u
     uint8_t *d_bwt = ctx->ws_alloc<uint8_t>(n);
     uint32_t *d_sa = ctx->ws_alloc<uint32_t>(n);
     if (!d_text || !d_bwt || !d_sa) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(d_text, in, n, hipMemcpyHostToDevice, ctx->stream));
+    DK_TRY(up.copy(d_text, in, n, "text"));
     DK_TRY(bwt_forward_device(ctx, d_text, n, d_sa, d_bwt, origin));
     DK_HIP(ctx, hipMemcpyAsync(bwt_out, d_bwt, n, hipMemcpyDeviceToHost, ctx->stream));
-    DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    DK_TRY(up.sync());
     ctx->stats.ms_total = t.ms();
     return DK_OK;
 }
@@ -2117,6 +1077,7 @@ int dk_bwt_forward(dk_ctx *ctx, const uint8_t *in, size_t n, uint8_t *bwt_out, u
 int dk_bwt_inverse(dk_ctx *ctx, const uint8_t *bwt, size_t n, uint32_t origin, uint8_t *out) {
     DK_TRY(begin_call(ctx));
     ScopedCall sc(ctx);
+    Upload up(ctx);
     if (!bwt || !out) return ctx->fail(DK_E_ARG, "null pointer");
     DK_TRY(check_n(ctx, n));
     if (origin >= n) return ctx->fail(DK_E_ARG, "origin %u outside the block of %zu bytes", origin, n);
@@ -2124,10 +1085,10 @@ int dk_bwt_inverse(dk_ctx *ctx, const uint8_t *bwt, size_t n, uint32_t origin, u
     uint8_t *d_bwt = ctx->ws_alloc<uint8_t>(n);
     uint8_t *d_out = ctx->ws_alloc<uint8_t>(n);
     if (!d_bwt || !d_out) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(d_bwt, bwt, n, hipMemcpyHostToDevice, ctx->stream));
+    DK_TRY(up.copy(d_bwt, bwt, n, "L"));
     DK_TRY(bwt_inverse_device(ctx, d_bwt, n, origin, d_out));
     DK_HIP(ctx, hipMemcpyAsync(out, d_out, n, hipMemcpyDeviceToHost, ctx->stream));
-    DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    DK_TRY(up.sync());
     ctx->stats.ms_total = t.ms();
     return DK_OK;
 }
@@ -2135,6 +1096,7 @@ int dk_bwt_inverse(dk_ctx *ctx, const uint8_t *bwt, size_t n, uint32_t origin, u
 int dk_dc_encode(dk_ctx *ctx, const uint8_t *bwt, size_t n, uint32_t init[256], uint32_t *dist, uint8_t *sym, uint8_t *rank, size_t *m) {
     DK_TRY(begin_call(ctx, "dk_dc_encode"));
     ScopedCall sc(ctx);
+    Upload up(ctx);
     if (!bwt || !init || !dist || !sym || !m) return ctx->fail(DK_E_ARG, "null pointer");
     DK_TRY(check_n(ctx, n));
     Timer t;
@@ -2143,12 +1105,12 @@ int dk_dc_encode(dk_ctx *ctx, const uint8_t *bwt, size_t n, uint32_t init[256], 
     uint8_t *d_sym = ctx->ws_alloc<uint8_t>(n);
     uint8_t *d_rank = ctx->ws_alloc<uint8_t>(n);
     if (!d_bwt || !d_dist || !d_sym || !d_rank) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(d_bwt, bwt, n, hipMemcpyHostToDevice, ctx->stream));
+    DK_TRY(up.copy(d_bwt, bwt, n, "L"));
     DK_TRY(dc_encode_device(ctx, d_bwt, n, init, d_dist, d_sym, d_rank, nullptr, m));
     DK_HIP(ctx, hipMemcpyAsync(dist, d_dist, *m * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     DK_HIP(ctx, hipMemcpyAsync(sym, d_sym, *m, hipMemcpyDeviceToHost, ctx->stream));
     if (rank) DK_HIP(ctx, hipMemcpyAsync(rank, d_rank, *m, hipMemcpyDeviceToHost, ctx->stream));
-    DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    DK_TRY(up.sync());
     ctx->stats.ms_total = t.ms();
     return DK_OK;
 }
@@ -2163,13 +1125,14 @@ int dk_dc_decode(dk_ctx *ctx, const uint32_t init[256], const uint32_t *dist, si
 int dk_block_encode(dk_ctx *ctx, int model_id, const uint8_t *in, size_t n, uint8_t *out, size_t out_cap, size_t *out_len) {
     DK_TRY(begin_call(ctx, "dk_block_encode"));
     ScopedCall sc(ctx);
+    Upload up(ctx);
     if (!in || !out || !out_len) return ctx->fail(DK_E_ARG, "null pointer");
     DK_TRY(check_n(ctx, n));
     Timer t;
     uint8_t *d_text = ctx->ws_alloc<uint8_t>(n);
     if (!d_text) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(d_text, in, n, hipMemcpyHostToDevice, ctx->stream));
-    DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    DK_TRY(up.copy(d_text, in, n, "text"));
+    DK_TRY(up.sync());
     ctx->stats.ms_h2d = t.ms();
     int rc = block_encode_common(ctx, model_id, d_text, n, out, out_cap, out_len);
     ctx->stats.ms_total = t.ms();
@@ -2199,6 +1162,7 @@ int dk_raw_block_encode(dk_ctx *ctx, int raw_model, const uint8_t *in, size_t n,
                         size_t dump_cap, size_t *dump_len) {
     DK_TRY(begin_call(ctx, "dk_raw_block_encode"));
     ScopedCall sc(ctx);
+    Upload up(ctx);
     if (!in || !out || !out_len) return ctx->fail(DK_E_ARG, "null pointer");
     if (raw_model != DK_RAWMODEL_OUT && raw_model != DK_RAWMODEL_BBB) return ctx->fail(DK_E_MODEL, "unknown raw model %d", raw_model);
     if (raw_model == DK_RAWMODEL_OUT && (!dump || !dump_len)) return ctx->fail(DK_E_ARG, "the Out model needs a dump buffer");
@@ -2209,12 +1173,12 @@ int dk_raw_block_encode(dk_ctx *ctx, int raw_model, const uint8_t *in, size_t n,
     uint8_t *d_bwt = ctx->ws_alloc<uint8_t>(n);
     uint32_t *d_sa = ctx->ws_alloc<uint32_t>(n);
     if (!d_text || !d_bwt || !d_sa) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(d_text, in, n, hipMemcpyHostToDevice, ctx->stream));
+    DK_TRY(up.copy(d_text, in, n, "text"));
     uint32_t origin = 0;
     DK_TRY(bwt_forward_device(ctx, d_text, n, d_sa, d_bwt, &origin));
     if (raw_model == DK_RAWMODEL_OUT) {
         DK_HIP(ctx, hipMemcpyAsync(dump + 4, d_bwt, n, hipMemcpyDeviceToHost, ctx->stream));
-        DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        DK_TRY(up.sync());
         for (int i = 0; i < 4; ++i) dump[i] = static_cast<uint8_t>(origin >> (24 - 8 * i));  // src/block/raw.rs:48-51
         *dump_len = n + 4;
         std::memset(out, 0, 4);  // ari::Encoder::finish of a coder nothing was coded with: low = 0, four bytes
@@ -2223,7 +1187,7 @@ int dk_raw_block_encode(dk_ctx *ctx, int raw_model, const uint8_t *in, size_t n,
         DK_TRY(ctx->ensure_stage(n + 64));
         uint8_t *h_bwt = reinterpret_cast<uint8_t *>(ctx->h_stage);
         DK_HIP(ctx, hipMemcpyAsync(h_bwt, d_bwt, n, hipMemcpyDeviceToHost, ctx->stream));
-        DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        DK_TRY(up.sync());
         Timer te;
         const int rc = raw_bbb_encode_stream(h_bwt, n, origin, out, out_cap, out_len);
         ctx->stats.ms_entropy = te.ms();
@@ -2316,17 +1280,19 @@ int dk_multi_block_encode(const int *devices, int ndev, int model_id, size_t cou
             std::vector<const uint8_t *> d_in(cnt);
             std::vector<size_t> ns(cnt), caps(cnt), lens(cnt);
             std::vector<uint8_t *> outs(cnt);
+            Upload up(ctx);  // (behind db: the uploads have landed before their destinations are freed)
             for (size_t k = 0; k < cnt; ++k) {
                 const size_t i = mine[lo + k];
                 uint8_t *p = nullptr;
                 if (!in[i] || !out[i] || n[i] == 0) return ctx->fail(DK_E_ARG, "null pointer or empty block %zu", i);
                 if (hipMalloc(reinterpret_cast<void **>(&p), n[i]) != hipSuccess) return ctx->fail(DK_E_NOMEM, "hipMalloc of block %zu failed", i);
                 db.ptr.push_back(p);
-                if (hipMemcpyAsync(p, in[i], n[i], hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return ctx->fail(DK_E_HIP, "upload of block %zu failed", i);  // (ordered with the kernels that read it)
+                if (up.copy(p, in[i], n[i], "upload") != DK_OK) return ctx->fail(DK_E_HIP, "upload of block %zu failed", i);  // (ordered with the kernels that read it)
                 d_in[k] = p; ns[k] = n[i]; caps[k] = out_cap[i]; outs[k] = out[i];
             }
             const int rc = dk_dev_batch_encode(ctx, model_id, cnt, d_in.data(), ns.data(), outs.data(), caps.data(), lens.data(), host_threads_per_gpu);
             if (rc != DK_OK) return rc;
+            up.synchronised();  // (every stream of the batch is coded: its blocks were read long ago)
             for (size_t k = 0; k < cnt; ++k) out_len[mine[lo + k]] = lens[k];
         }
         return DK_OK;
@@ -2502,6 +1468,7 @@ int dk_dbg_dev_sort_groups(dk_ctx *ctx, const uint64_t *d_kin, const uint32_t *d
                            size_t ngroups, size_t npairs, uint32_t above, int begin_bit, int end_bit) {
     DK_TRY(begin_call(ctx, "dk_dbg_dev_sort_groups"));
     ScopedCall sc(ctx);
+    Upload up(ctx);
     if (!d_kin || !d_vin || !d_kout || !d_vout || !starts || ngroups == 0 || npairs == 0) return ctx->fail(DK_E_ARG, "null pointer or empty input");
     if (npairs > 0xFFFFFFFFull || begin_bit < 0 || end_bit > 64 || begin_bit > end_bit) return ctx->fail(DK_E_ARG, "sort_groups: %zu pairs, bits [%d, %d)", npairs, begin_bit, end_bit);
     for (size_t g = 0; g < ngroups; ++g)
@@ -2509,9 +1476,9 @@ int dk_dbg_dev_sort_groups(dk_ctx *ctx, const uint64_t *d_kin, const uint32_t *d
     if (starts[ngroups] > npairs) return ctx->fail(DK_E_ARG, "sort_groups: the last group ends at %u of %zu pairs", starts[ngroups], npairs);
     uint32_t *d_starts = ctx->ws_alloc<uint32_t>(ngroups + 1);
     if (!d_starts) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(d_starts, starts, (ngroups + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    DK_TRY(up.copy(d_starts, starts, (ngroups + 1) * sizeof(uint32_t), "group starts"));
     DK_TRY(sort_groups(ctx, d_kin, d_vin, d_kout, d_vout, d_starts, ngroups, npairs, above, begin_bit, end_bit));
-    DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    DK_TRY(up.sync());
     return DK_OK;
 }
 int dk_dbg_dev_rerank(dk_ctx *ctx, const void *d_keys, int key_bytes, const uint32_t *d_bucket_starts, const uint32_t *d_idx, const uint32_t *d_pos_in,
@@ -2552,16 +1519,17 @@ int dk_dbg_dev_inverse_permutation(dk_ctx *ctx, const uint32_t *d_sa, size_t n, 
 int dk_dbg_sort_pairs(dk_ctx *ctx, uint64_t *keys, uint32_t *vals, size_t count, int begin_bit, int end_bit) {
     DK_TRY(begin_call(ctx, "dk_dbg_sort_pairs"));
     ScopedCall sc(ctx);
+    Upload up(ctx);
     if (!keys || !vals || count == 0) return ctx->fail(DK_E_ARG, "null pointer or empty input");
     uint64_t *k0 = ctx->ws_alloc<uint64_t>(count), *k1 = ctx->ws_alloc<uint64_t>(count);
     uint32_t *v0 = ctx->ws_alloc<uint32_t>(count), *v1 = ctx->ws_alloc<uint32_t>(count);
     if (!k0 || !k1 || !v0 || !v1) return DK_E_NOMEM;
-    DK_HIP(ctx, hipMemcpyAsync(k0, keys, count * 8, hipMemcpyHostToDevice, ctx->stream));
-    DK_HIP(ctx, hipMemcpyAsync(v0, vals, count * 4, hipMemcpyHostToDevice, ctx->stream));
+    DK_TRY(up.copy(k0, keys, count * 8, "keys"));
+    DK_TRY(up.copy(v0, vals, count * 4, "values"));
     DK_TRY(sort_pairs(ctx, k0, k1, v0, v1, count, begin_bit, end_bit));
     DK_HIP(ctx, hipMemcpyAsync(keys, k0, count * 8, hipMemcpyDeviceToHost, ctx->stream));
     DK_HIP(ctx, hipMemcpyAsync(vals, v0, count * 4, hipMemcpyDeviceToHost, ctx->stream));
-    DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    DK_TRY(up.sync());
     return DK_OK;
 }
 

@@ -147,6 +147,8 @@ SIGNATURES = {
     # ctx, keys, key_bytes, bucket_starts, idx, pos_in, gid_in, cmp_shift, count | rank, sa | bwt, sym_in, sym_out, origin | out_idx, out_pos, out_gid,
     # gstart, bigidx, bigoff | ls_max, counts_out[5] | reduce_tiles_per_wg, first_tiles_per_wg, sparse_max
     "dk_dbg_dev_rerank": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _sz] + [_vp] * 2 + [_vp] * 4 + [_vp] * 6 + [C.c_uint32, _vp, C.c_uint, C.c_uint, _i]),
+    "dk_dbg_dev_lf_refine": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, C.c_uint32, _i, _vp, _vp, _vp]),
+    "dk_dbg_dev_lf_rerank": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _sz] + [_vp] * 8 + [C.c_uint32, _vp, _i, C.c_uint32, _vp, C.c_uint]),
     "dk_dbg_dev_inverse_permutation": (_i, [_vp, _vp, _sz, _vp, _vp]),
     "dk_dbg_mail_fill": (_i, [_vp, _i]),
     "dk_dbg_ws_peek": (_i, [_vp, _sz, _vp]),

@@ -848,6 +848,85 @@ class Context:
         res["counts"] = tuple(int(c) for c in counts)
         return res
 
+    def dbg_dev_lf_rerank(self, keys, idx, sym=None, pos_in=None, bucket_starts=None, cmp_shift=0, sym_from_key=False, zero_slot=None, bwt=None,
+                          origin=None, depth=None, bigdepth=None, key_shift=0, depth_add=0, reduce_tiles_per_wg=0, shift=None, fill=0xC3, pad=64):
+        """dk_dbg_dev_lf_rerank: one rerank of the L-first path and its classification.  keys: uint64, or uint32 (with bucket_starts, 256 words:
+        the narrow first rerank; without: group ids).  sym: the symbol in front of every slot (sym_from_key: what the array holds before the
+        call; None: `fill` bytes).  pos_in None: the first rerank.  zero_slot: the word *d_zero_slot (None: a null pointer).  bwt / origin: what
+        L and the origin word hold before the call (None: null pointers).  depth None: no d_gdepth_out; a number: every live group's; with
+        bigdepth (words): the big-list rule bigdepth[key >> key_shift] + depth_add.  shift: {name: elements} by which the device view of keys /
+        idx / sym / pos_in starts behind its allocation.  Every output array holds `fill` bytes before the call: the lists count + pad entries,
+        gstart count // 2 + 1 + pad words, gdepth count // 2 + pad.  -> dict of the arrays after the call (whole, the untouched parts
+        included; None for the null ones), sym, bwt, origin, and counts = (active, groups, big_slots, big_groups)"""
+        import torch
+        shift = shift or {}
+        dev = "cuda:%d" % self.device
+
+        def up(name, a, dtype):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dtype)
+            off = int(shift.get(name, 0))
+            whole = np.concatenate([np.zeros(off, dtype), a]) if off else a.copy()
+            return torch.from_numpy(whole.view({1: np.uint8, 4: np.int32, 8: np.int64}[whole.dtype.itemsize])).to(dev)[off:]
+
+        def out(words, dtype):
+            return torch.from_numpy(np.full(words * np.dtype(dtype).itemsize, fill, np.uint8)).to(dev)
+
+        narrow = np.asarray(keys).dtype == np.uint32
+        count = len(keys)
+        if sym is None:
+            sym = np.full(count, fill, np.uint8)
+        d = dict(keys=up("keys", keys, np.uint32 if narrow else np.uint64), bucket_starts=up("bucket_starts", bucket_starts, np.uint32),
+                 idx=up("idx", idx, np.uint32), sym=up("sym", sym, np.uint8), pos_in=up("pos_in", pos_in, np.uint32),
+                 zero_slot=up("zero_slot", None if zero_slot is None else [zero_slot], np.uint32), bwt=up("bwt", bwt, np.uint8),
+                 origin=up("origin", None if origin is None else [origin], np.uint32), bigdepth=up("bigdepth", bigdepth, np.uint32))
+        for name in ("idx", "sym", "pos_in"):
+            if d[name] is not None and len(d[name]) != count:
+                raise DarkError(_lib.DK_E_ARG, "%d keys, %d entries of %s" % (count, len(d[name]), name))
+        outs = dict(out_idx=(count + pad, np.uint32), out_pos=(count + pad, np.uint32), out_gid=(count + pad, np.uint32), out_sym=(count + pad, np.uint8),
+                    gstart=(count // 2 + 1 + pad, np.uint32), gdepth=(count // 2 + pad, np.uint32))
+        if depth is None and bigdepth is None:
+            del outs["gdepth"]
+        o = {name: out(words, dtype) for name, (words, dtype) in outs.items()}
+        counts = np.zeros(4, np.uint32)
+        p = lambda t: None if t is None else _ptr(t)  # noqa: E731
+        _inputs_ready(d["keys"])
+        self._ck(self._lib.dk_dbg_dev_lf_rerank(self._h, p(d["keys"]), 4 if narrow else 8, p(d["bucket_starts"]), int(cmp_shift), p(d["sym"]),
+                                                int(bool(sym_from_key)), p(d["idx"]), p(d["zero_slot"]), p(d["pos_in"]), count, p(o["out_idx"]),
+                                                p(o["out_pos"]), p(o["out_gid"]), p(o["out_sym"]), p(o["gstart"]), p(d["bwt"]), p(d["origin"]),
+                                                p(o.get("gdepth")), int(depth or 0), p(d["bigdepth"]), int(key_shift), int(depth_add), _ptr(counts),
+                                                int(reduce_tiles_per_wg)))
+        res = {name: self._to_host(t, outs[name][1]) for name, t in o.items()}
+        res.setdefault("gdepth", None)
+        res["sym"] = self._to_host(d["sym"], np.uint8)
+        res["bwt"] = None if d["bwt"] is None else self._to_host(d["bwt"], np.uint8)
+        res["origin"] = None if d["origin"] is None else int(self._to_host(d["origin"], np.uint32)[0])
+        res["counts"] = tuple(int(c) for c in counts)
+        return res
+
+    def dbg_dev_lf_refine(self, text, idx, pos, gid, sym, h0, period=0, fill=0xC3, origin=0xC3C3C3C3):
+        """dk_dbg_dev_lf_refine: the L-first path from a list (suffix, place in L, group, symbol in front per slot; the members of a group equal in
+        h0 symbols) to its end.  L holds `fill` bytes and the origin word `origin` before the call.  -> dict: bwt (n bytes), origin, verdict
+        ("l_complete" / "start_over"), routes (names), and the counters rounds, deep_count, arena_used, giant_count, fallback, giant_count_1"""
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        import torch
+        dev = "cuda:%d" % self.device
+        d_text = torch.from_numpy(text.copy()).to(dev)
+        d_sym = torch.from_numpy(np.ascontiguousarray(sym, dtype=np.uint8).copy()).to(dev)
+        d_idx, d_pos, d_gid = (self._to_dev(a, np.uint32) for a in (idx, pos, gid))
+        if not (len(d_idx) == len(d_pos) == len(d_gid) == len(d_sym)):
+            raise DarkError(_lib.DK_E_ARG, "list arrays of different lengths")
+        d_bwt = torch.from_numpy(np.full(len(text), fill, np.uint8)).to(dev)
+        d_origin = self._to_dev(np.array([origin], np.uint32), np.uint32)
+        out = np.zeros(8, np.uint32)
+        _inputs_ready(d_text)
+        self._ck(self._lib.dk_dbg_dev_lf_refine(self._h, _ptr(d_text), len(text), _ptr(d_idx), _ptr(d_pos), _ptr(d_gid), _ptr(d_sym), len(d_idx), int(h0),
+                                                int(period), _ptr(d_bwt), _ptr(d_origin), _ptr(out)))
+        return dict(bwt=d_bwt.cpu().numpy(), origin=int(self._to_host(d_origin, np.uint32)[0]), verdict={1: "l_complete", 2: "start_over"}[int(out[0])],
+                    routes={name for name, bit in _lib.ROUTES.items() if int(out[1]) & bit}, rounds=int(out[2]), deep_count=int(out[3]),
+                    arena_used=int(out[4]), giant_count=int(out[5]), fallback=int(out[6]), giant_count_1=int(out[7]))
+
     def dbg_dev_inverse_permutation(self, sa, marked_val=None):
         """dk_dbg_dev_inverse_permutation: rank[sa[p] & 0x7FFFFFFF] = marked_val[p] if sa[p] has bit 31 set (and marked_val is given) else p"""
         d_sa = self._to_dev(sa, np.uint32)

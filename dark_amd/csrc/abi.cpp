@@ -1505,6 +1505,42 @@ int dk_dbg_dev_rerank(dk_ctx *ctx, const void *d_keys, int key_bytes, const uint
                       d_origin, d_out_idx, d_out_pos, d_out_gid, d_gstart, d_bigidx, d_bigoff, ls_max, reduce_tiles_per_wg, first_tiles_per_wg, sparse_max};
     return dbg_rerank_device(ctx, a, counts_out);
 }
+int dk_dbg_dev_lf_rerank(dk_ctx *ctx, const void *d_keys, int key_bytes, const uint32_t *d_bucket_starts, int cmp_shift, uint8_t *d_sym, int sym_from_key,
+                         const uint32_t *d_idx, const uint32_t *d_zero_slot, const uint32_t *d_pos_in, size_t count, uint32_t *d_out_idx, uint32_t *d_out_pos,
+                         uint32_t *d_out_gid, uint8_t *d_out_sym, uint32_t *d_gstart, uint8_t *d_bwt, uint32_t *d_origin, uint32_t *d_gdepth_out,
+                         uint32_t depth_uniform, const uint32_t *d_bigdepth, int key_shift, uint32_t depth_add, uint32_t counts_out[4],
+                         unsigned reduce_tiles_per_wg) {
+    DK_TRY(begin_call(ctx, "dk_dbg_dev_lf_rerank"));
+    ScopedCall sc(ctx);
+    if (!d_keys || !d_sym || !d_idx || !d_out_idx || !d_out_pos || !d_out_gid || !d_out_sym || !d_gstart || !counts_out)
+        return ctx->fail(DK_E_ARG, "lf_rerank: null pointer");
+    if (count == 0 || count > ctx->max_n || count > 0x7FFFFFFEull) return ctx->fail(DK_E_ARG, "lf_rerank: %zu slots (context capacity %zu)", count, ctx->max_n);
+    if (key_bytes != 4 && key_bytes != 8) return ctx->fail(DK_E_ARG, "lf_rerank: keys of %d bytes", key_bytes);
+    if (key_bytes == 8 && d_bucket_starts) return ctx->fail(DK_E_ARG, "lf_rerank: bucket starts go with 4-byte keys only");
+    if (cmp_shift < 0 || cmp_shift > 63 || (cmp_shift && key_bytes == 4))
+        return ctx->fail(DK_E_ARG, "lf_rerank: cmp_shift %d (0 .. 63, and only 8-byte keys leave low bits out)", cmp_shift);
+    if (sym_from_key && key_bytes == 4) return ctx->fail(DK_E_ARG, "lf_rerank: only 8-byte keys carry the symbol in their low byte");
+    if (d_pos_in && (!d_bwt || !d_origin)) return ctx->fail(DK_E_ARG, "lf_rerank: a later rerank (d_pos_in) writes its finals: d_bwt and d_origin");
+    if (d_bigdepth && (key_bytes != 8 || !d_gdepth_out || key_shift < 0 || key_shift > 63))
+        return ctx->fail(DK_E_ARG, "lf_rerank: the big-list depth rule reads 8-byte keys above key_shift 0 .. 63 and writes d_gdepth_out");
+    if (reduce_tiles_per_wg > 64) return ctx->fail(DK_E_ARG, "lf_rerank: %u tiles per workgroup (at most 64)", reduce_tiles_per_wg);
+    const DbgLfRerank a{d_keys, key_bytes, d_bucket_starts, cmp_shift, d_sym, sym_from_key, d_idx, d_zero_slot, d_pos_in, count, d_out_idx, d_out_pos, d_out_gid,
+                        d_out_sym, d_gstart, d_bwt, d_origin, d_gdepth_out, depth_uniform, d_bigdepth, key_shift, depth_add, reduce_tiles_per_wg};
+    return dbg_lf_rerank_device(ctx, a, counts_out);
+}
+int dk_dbg_dev_lf_refine(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uint32_t *d_idx, const uint32_t *d_pos, const uint32_t *d_gid, const uint8_t *d_sym,
+                         size_t count, uint32_t h0, int period, uint8_t *d_bwt, uint32_t *d_origin, uint32_t out[8]) {
+    DK_TRY(begin_call(ctx, "dk_dbg_dev_lf_refine"));
+    ScopedCall sc(ctx);
+    if (!d_text || !d_idx || !d_pos || !d_gid || !d_sym || !d_bwt || !d_origin || !out) return ctx->fail(DK_E_ARG, "lf_refine: null pointer");
+    if (n < 64 || n > ctx->max_n || n > 0x7FFFFFFEull) return ctx->fail(DK_E_ARG, "lf_refine: text of %zu bytes (64 .. the context capacity %zu)", n, ctx->max_n);
+    if (count == 0 || count > n) return ctx->fail(DK_E_ARG, "lf_refine: %zu slots for a text of %zu bytes", count, n);
+    if (h0 == 0 || h0 > n) return ctx->fail(DK_E_ARG, "lf_refine: depth %u of a text of %zu bytes", h0, n);
+    if (period < 0 || (period > 0 && static_cast<uint32_t>(period) > h0))
+        return ctx->fail(DK_E_ARG, "lf_refine: period %d (0: no tokens; otherwise 1 .. h0 = %u: the members of a group share the period string)", period, h0);
+    const DbgLfRefine a{d_text, n, d_idx, d_pos, d_gid, d_sym, count, h0, period, d_bwt, d_origin};
+    return dbg_lf_refine_device(ctx, a, out);
+}
 int dk_dbg_dev_inverse_permutation(dk_ctx *ctx, const uint32_t *d_sa, size_t n, uint32_t *d_rank, const uint32_t *d_marked_val) {
     DK_TRY(begin_call(ctx, "dk_dbg_dev_inverse_permutation"));
     ScopedCall sc(ctx);

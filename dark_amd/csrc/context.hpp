@@ -218,6 +218,24 @@ struct DbgRerank {
     uint32_t reduce_tiles_per_wg, first_tiles_per_wg; int sparse_max;
 };
 int dbg_rerank_device(dk_ctx *ctx, const DbgRerank &args, uint32_t counts_out[5]);
+// dk_dbg_dev_lf_rerank's arguments under the names of the header: one lf_rerank() (lfirst.inc) on the caller's arrays and the classification behind
+// it as lfirst_path runs it after its first rerank.  keys: 32-bit words when key_bytes is 4 (with bucket_starts: the narrow first rerank; without:
+// group ids, the take-over form).  bigdepth != nullptr: the big-list depth rule.  counts_out: active, groups, big_slots, big_groups.  Synchronises.
+struct DbgLfRerank {
+    const void *keys; int key_bytes; const uint32_t *bucket_starts; int cmp_shift; uint8_t *sym; int sym_from_key;
+    const uint32_t *idx, *zero_slot, *pos_in; size_t count;
+    uint32_t *out_idx, *out_pos, *out_gid; uint8_t *out_sym; uint32_t *gstart; uint8_t *bwt; uint32_t *origin;
+    uint32_t *gdepth_out; uint32_t depth_uniform; const uint32_t *bigdepth; int key_shift; uint32_t depth_add;
+    uint32_t reduce_tiles_per_wg;
+};
+int dbg_lf_rerank_device(dk_ctx *ctx, const DbgLfRerank &args, uint32_t counts_out[4]);
+// dk_dbg_dev_lf_refine's arguments: lfirst_path() from the caller's list (count slots of groups equal in their first h0 symbols) to its end.
+// out: verdict, sa_route, rounds, deep_count, arena_used, giant_count[0], fallback, giant_count[1].  Synchronises.
+struct DbgLfRefine {
+    const uint8_t *text; size_t n; const uint32_t *idx, *pos, *gid; const uint8_t *sym; size_t count; uint32_t h0; int period;
+    uint8_t *bwt; uint32_t *origin;
+};
+int dbg_lf_refine_device(dk_ctx *ctx, const DbgLfRefine &args, uint32_t out[8]);
 // bwt.hip
 int bwt_gather_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_sa, size_t n, uint8_t *d_bwt, uint32_t *origin);
 int bwt_inverse_device(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t origin, uint8_t *d_out);

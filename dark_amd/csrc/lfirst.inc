@@ -457,7 +457,7 @@ __global__ __launch_bounds__(RR_BLOCK) void k_lf_apply(const uint8_t *__restrict
 // in the low byte) -> active list of the live groups.  The counts come back through classify_and_read like after rerank().
 int lf_rerank(dk_ctx *ctx, const uint64_t *keys, int cmp_shift, const uint32_t *narrow_starts, uint8_t *sym, int sym_from_key, const uint32_t *idx,
               const uint32_t *zero_slot, const uint32_t *pos_in, size_t count, uint32_t *out_idx, uint32_t *out_pos, uint32_t *out_gid, uint8_t *out_sym,
-              uint32_t *gstart, uint8_t *bwt, uint32_t *origin, const LfDepthRule &dr, bool keys32 = false) {
+              uint32_t *gstart, uint8_t *bwt, uint32_t *origin, const LfDepthRule &dr, bool keys32 = false, uint32_t reduce_tiles_per_wg = 0) {
     const size_t ntiles = div_up(count, RR_TILE);
     const size_t mark = ctx->ws_mark();
     RerankAgg *agg = ctx->ws_alloc<RerankAgg>(ntiles);
@@ -467,7 +467,8 @@ int lf_rerank(dk_ctx *ctx, const uint64_t *keys, int cmp_shift, const uint32_t *
     hipStream_t st = ctx->stream;
     {
         LaunchScope ls(ctx, K_RERANK_REDUCE, ((narrow_starts || keys32 ? 4.0 : 8.0) + (zero_slot ? 0.0 : 4.0) + 1.0 + 1.0) * count);
-        const uint32_t per_wg = static_cast<uint32_t>(std::min<size_t>(std::max<size_t>(ntiles / 16384, 1), 64));
+        // (reduce_tiles_per_wg: a launch shape a test may set, dk_dbg_dev_lf_rerank -- the multi-tile stretch starts at 2^25 slots; the outputs do not depend on it)
+        const uint32_t per_wg = reduce_tiles_per_wg ? reduce_tiles_per_wg : static_cast<uint32_t>(std::min<size_t>(std::max<size_t>(ntiles / 16384, 1), 64));
         const dim3 grid(static_cast<unsigned>(div_up(ntiles, per_wg))), block(RR_BLOCK);
         if (narrow_starts || keys32)
             k_lf_reduce<uint32_t><<<grid, block, 0, st>>>(reinterpret_cast<const uint32_t *>(keys), count, 0, sym, 0, idx, zero_slot, agg, tiles, flags, narrow_starts,

@@ -2362,6 +2362,60 @@ int run_phases(SaSort &s) {
 
 }  // namespace
 
+// dk_dbg_dev_lf_rerank (abi.cpp has checked the arguments): one lf_rerank and the classification behind it, as lfirst_path runs them after its first
+// rerank -- the line of the big groups at the path's ls_max (LFS_CAP; tuning build: DK_LF_MAX), two classes unless DK_LF_MEDIUM=0.  (It stands
+// here and not beside dbg_rerank_device because lf_rerank is defined behind that.)  bigidx / bigoff are the classification's own outputs, which
+// no kernel of lf_rerank reads: workspace.
+int dbg_lf_rerank_device(dk_ctx *ctx, const DbgLfRerank &a, uint32_t counts_out[4]) {
+    const size_t mark = ctx->ws_mark();
+    uint32_t *bigidx = ctx->ws_alloc<uint32_t>(a.count / 2 + 2), *bigoff = ctx->ws_alloc<uint32_t>(a.count / 32 + 2);
+    if (!bigidx || !bigoff) return DK_E_NOMEM;
+    const LfDepthRule rule{a.gdepth_out, a.depth_uniform, a.bigdepth ? static_cast<const uint64_t *>(a.keys) : nullptr, a.key_shift, a.bigdepth, a.depth_add,
+                           nullptr, 0, 0u, nullptr};
+    const bool keys32 = a.key_bytes == 4 && !a.bucket_starts;
+    DK_TRY(lf_rerank(ctx, static_cast<const uint64_t *>(a.keys), a.cmp_shift, a.bucket_starts, a.sym, a.sym_from_key, a.idx, a.zero_slot, a.pos_in, a.count, a.out_idx,
+                     a.out_pos, a.out_gid, a.out_sym, a.gstart, a.bwt, a.origin, rule, keys32, a.reduce_tiles_per_wg));
+    const uint32_t ls_max = static_cast<uint32_t>(std::min(LFS_CAP, std::max(32, DK_KNOB("DK_LF_MAX", LFS_CAP))));
+    GroupCounts c;
+    if (DK_KNOB("DK_LF_MEDIUM", 1) != 0) DK_TRY(classify_two_and_read(ctx, a.gstart, bigidx, bigoff, ls_max, &c));
+    else DK_TRY(classify_and_read(ctx, 0, a.gstart, bigidx, bigoff, &c, ls_max));
+    const size_t v[4] = {c.active, c.groups, c.big, c.big_groups};
+    for (int i = 0; i < 4; ++i) counts_out[i] = static_cast<uint32_t>(v[i]);
+    ctx->ws_release(mark);
+    return DK_OK;
+}
+
+// dk_dbg_dev_lf_refine (abi.cpp has checked the arguments): the L-first path from a caller's list to its end, the way take_over() starts it -- the
+// sort's buffers for n from the workspace, the list copied into the current set (vals, pos, gid, sym), lf_buffers_take_over for the rest, force.
+// period > 0: a token plan with n words of next-break room of its own (the take-over layout has none to spare) and tokens in the first round.
+// out: verdict (L_COMPLETE / START_OVER) | sa_route | rounds | deep_count | arena_used | giant_count[0] | fallback | giant_count[1], the mailbox
+// words as the path's last kernel left them.
+int dbg_lf_refine_device(dk_ctx *ctx, const DbgLfRefine &a, uint32_t out[8]) {
+    const size_t n = a.n, mark = ctx->ws_mark();
+    ctx->stats.rounds = 0;
+    ctx->stats.sa_route = DK_ROUTE_LFIRST;
+    SaBuffers b;
+    DK_TRY(alloc_buffers(ctx, n, true, &b));
+    uint32_t *next_break = a.period > 0 ? ctx->ws_alloc<uint32_t>(n) : nullptr;
+    if (a.period > 0 && !next_break) return DK_E_NOMEM;
+    hipStream_t st = ctx->stream;
+    DK_HIP(ctx, hipMemcpyAsync(b.vals, a.idx, a.count * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    DK_HIP(ctx, hipMemcpyAsync(b.pos, a.pos, a.count * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    DK_HIP(ctx, hipMemcpyAsync(b.gid, a.gid, a.count * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    DK_HIP(ctx, hipMemcpyAsync(b.sym, a.sym, a.count, hipMemcpyDeviceToDevice, st));
+    LfFrom from;
+    from.idx = b.vals, from.pos = b.pos, from.gid = b.gid, from.sym = b.sym, from.count = a.count, from.h0 = a.h0;
+    const LfTokenPlan plan{a.period, next_break, a.period > 0};
+    const int step = lfirst_path(ctx, a.text, n, a.bwt, a.origin, lf_buffers_take_over(b, n), from, plan, DK_KNOB("DK_TRACE", 0) != 0, true);
+    if (step < 0) return step;
+    DK_TRY(ctx->mail_read(&ctx->h_mail->lf));
+    const Mail::LFirst &lf = ctx->h_mail->lf;
+    const uint32_t v[8] = {static_cast<uint32_t>(step), ctx->stats.sa_route, ctx->stats.rounds, lf.deep_count, lf.arena_used, lf.giant_count[0], lf.fallback, lf.giant_count[1]};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    ctx->ws_release(mark);
+    return DK_OK;
+}
+
 // runs the phases at most twice: with the L-first path allowed, and (after it gave up half way) without
 int suffix_array_device(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d_sa, uint8_t *d_bwt, uint32_t *d_origin, bool *bwt_written) {
     if (bwt_written) *bwt_written = false;

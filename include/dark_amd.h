@@ -592,6 +592,53 @@ int dk_dbg_dev_rerank(dk_ctx *ctx, const void *d_keys, int key_bytes, const uint
                       uint8_t *d_sym_out, uint32_t *d_origin, uint32_t *d_out_idx, uint32_t *d_out_pos, uint32_t *d_out_gid, uint32_t *d_gstart,
                       uint32_t *d_bigidx, uint32_t *d_bigoff, uint32_t ls_max, uint32_t counts_out[5], unsigned reduce_tiles_per_wg,
                       unsigned first_tiles_per_wg, int sparse_max);
+/* One rerank of the L-first path on device arrays the caller built: lf_rerank() of csrc/lfirst.inc (k_lf_reduce<u64 | u32>, k_lf_straddle, the scan
+ * k_rerank_scan / _a / _c, k_lf_apply) and the classification of the live groups behind it as the path runs it after its first rerank, with the
+ * mailbox read back as the path reads it.  A full context only.  tests/lf_rerank_model.py is the definition of every output.  The rules:
+ *   heads     slot 0; every slot whose compared key bits differ from the slot's in front (8-byte keys: the bits from cmp_shift up; 4-byte keys:
+ *             the whole word); with d_bucket_starts every slot that one of its 256 words names (values from `count` up name no slot)
+ *   live      a group (a head's slot up to the next head) is LIVE iff it has more than one member and (two different symbols in front, or suffix
+ *             0 among its members: the slot *d_zero_slot where that is given, the slot with d_idx == 0 otherwise).  Every other slot is FINAL
+ *   list      the live slots in slot order: d_out_idx = d_idx, d_out_pos = d_pos_in (null: the slot number), d_out_gid = the live groups in
+ *             front of the slot's group, d_out_sym = its symbol; d_gstart[g] = the list place of live group g's head, d_gstart[groups] = active
+ *   depths    d_gdepth_out (may be null: nothing is written) per live group: depth_uniform, or with d_bigdepth (the big-list rule)
+ *             d_bigdepth[key of the group's head >> key_shift] + depth_add.  (The rule's token fields are left out: no next-break positions.)
+ *   finals    d_pos_in given (a LATER rerank): d_bwt[d_pos_in] = the slot's symbol, *d_origin = d_pos_in where d_idx == 0.  d_pos_in null
+ *             (the FIRST rerank: slot a is SA position a and L holds its symbol already): nothing is written to d_bwt or d_origin
+ *   symbols   sym_from_key (8-byte keys): a slot's symbol is its key's low byte, and d_sym holds those bytes afterwards; otherwise d_sym is read
+ *   counts_out (host) active, groups, and the slots and groups of the big groups: more than 256 members (the tuning build's DK_LF_MAX lowers it)
+ *   reduce_tiles_per_wg   tiles a workgroup of k_lf_reduce takes: 1 .. 64, 0 = what the sort takes (ntiles / 16384, so 1 below 2^25 slots).  The
+ *                         outputs do not depend on it.
+ * Everything else stays as it was: the lists from `active` on, d_gstart from groups + 1 on, d_gdepth_out from `groups` on, d_bwt at the places of
+ * live slots, the origin word unless suffix 0 is final.  The caller's duties: arrays of `count` entries (d_gstart: count / 2 + 1 words,
+ * d_gdepth_out: count / 2), d_pos_in[a] below the length of d_bwt, with d_bigdepth every key >> key_shift below its length.
+ * DK_E_ARG before anything is launched: a null context or array (d_bucket_starts, d_zero_slot, d_pos_in, d_gdepth_out, d_bigdepth may be null;
+ * d_bwt and d_origin in the first rerank), an open batch, count == 0 or above the context's capacity or 2^31 - 2, other key sizes, bucket starts
+ * with 8-byte keys, a cmp_shift outside 0 .. 63 or with 4-byte keys, sym_from_key with 4-byte keys, d_bigdepth with 4-byte keys or without
+ * d_gdepth_out or with a key_shift outside 0 .. 63, more than 64 tiles per workgroup.  DK_E_NOMEM when the workspace (3.2 bytes per slot) does not fit. */
+int dk_dbg_dev_lf_rerank(dk_ctx *ctx, const void *d_keys, int key_bytes, const uint32_t *d_bucket_starts, int cmp_shift, uint8_t *d_sym, int sym_from_key,
+                         const uint32_t *d_idx, const uint32_t *d_zero_slot, const uint32_t *d_pos_in, size_t count, uint32_t *d_out_idx, uint32_t *d_out_pos,
+                         uint32_t *d_out_gid, uint8_t *d_out_sym, uint32_t *d_gstart, uint8_t *d_bwt, uint32_t *d_origin, uint32_t *d_gdepth_out,
+                         uint32_t depth_uniform, const uint32_t *d_bigdepth, int key_shift, uint32_t depth_add, uint32_t counts_out[4],
+                         unsigned reduce_tiles_per_wg);
+/* The refinement of the L-first path from a list the caller built, to its end: lfirst_path() of csrc/lfirst.inc in its take-over form -- the filter
+ * (lf_rerank on the group ids), k_lf_finish, the big rounds (global and grouped sorts, lf_rerank, k_lf_medium) and the passes over the deep groups
+ * (k_lf_deep_wave, k_lf_deep_block, k_lf_lce) -- with the sort's own buffers for n from the workspace.  A full context only.  The tuning build's
+ * DK_LF_* knobs act as in dk_dev_bwt_forward.  tests/lf_refine_model.py is the definition of the outputs:
+ *   the list   `count` <= n slots: the suffix d_idx[a] (< n, distinct), its place d_pos[a] in L (< n, distinct), its group d_gid[a] (a group is a run
+ *              of equal words) and the symbol in front d_sym[a].  The members of a group are equal in their first h0 symbols (the caller's duty)
+ *   L          for every group: its members ordered by their suffixes (plain byte comparison, a proper prefix is smaller), its places taken in
+ *              list order; d_bwt[k-th place] = d_sym of the k-th smallest member.  *d_origin = the place of suffix 0 if it is listed.  Every other
+ *              byte of d_bwt (n bytes) and the origin word stay as they were.  No kernel derives a symbol from the text: d_sym is a free label
+ *   period     0: no tokens.  1 .. h0: the text's short period; big groups whose members follow it through their depth are keyed by where their
+ *              stretch ends (DK_ROUTE_PERIOD_ROUND), from the first round on; the n words of next-break room come from the workspace
+ *   out        (host, 8 words) the verdict: 1 = L is complete, 2 = the path gave up half way (L has been written to, at listed places only; the
+ *              sort would start over without it) | DK_ROUTE_* bits | rounds (k_lf_finish launches) | and the path's counters as its last kernel left
+ *              them: entries of the deep list | members in the deep groups' arena | subgroups on giant list 0 | the give-up word | giant list 1
+ * DK_E_ARG before anything is launched: a null context or pointer, an open batch, n below 64 or above the context's capacity, count == 0 or above n,
+ * h0 == 0 or above n, a period below 0 or above h0.  DK_E_NOMEM when the sort's workspace for n (and 4 n bytes with a period) does not fit. */
+int dk_dbg_dev_lf_refine(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uint32_t *d_idx, const uint32_t *d_pos, const uint32_t *d_gid, const uint8_t *d_sym,
+                         size_t count, uint32_t h0, int period, uint8_t *d_bwt, uint32_t *d_origin, uint32_t out[8]);
 /* d_rank[d_sa[p]] = p for a permutation d_sa of 0 .. n-1 (n <= 2^31), through LDS windows.  d_marked_val (may be null): an entry of d_sa with bit
  * 31 set stands for d_sa[p] & 0x7FFFFFFF and its value is d_marked_val[p] instead of p.  The two n-u64 scratch arrays come from the context's
  * workspace: DK_E_NOMEM when they do not fit.  What it does with an input that is no permutation is not defined beyond "no store outside d_rank". */

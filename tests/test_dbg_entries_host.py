@@ -18,6 +18,26 @@ def test_null_context():
     assert not any(buf)
 
 
+def test_layer_entries_of_the_lfirst_path():
+    """dk_dbg_dev_lf_rerank and dk_dbg_dev_lf_refine (tests/test_gpu_lfirst_layer.py): a null context is refused before any argument is looked
+    at; both are declared in the header for a full context (the parameter's name is ctx: tests/test_gpu_decoder_ctx.py::test_refusals goes by
+    it) and signed in _lib with as many arguments as the header has"""
+    lib = dark_amd.load_library()
+    counts = (C.c_uint32 * 4)(7, 7, 7, 7)
+    assert lib.dk_dbg_dev_lf_rerank(None, None, 8, None, 0, None, 0, None, None, None, 100, None, None, None, None, None, None, None, None, 0, None, 0, 0,
+                                    C.cast(counts, C.c_void_p), 0) == _lib.DK_E_ARG
+    assert list(counts) == [7, 7, 7, 7]
+    out = (C.c_uint32 * 8)(*([7] * 8))
+    assert lib.dk_dbg_dev_lf_refine(None, None, 100, None, None, None, None, 10, 4, 0, None, None, C.cast(out, C.c_void_p)) == _lib.DK_E_ARG
+    assert list(out) == [7] * 8
+    with open(os.path.join(ROOT, "include", "dark_amd.h")) as f:
+        header = f.read()
+    for name in ("dk_dbg_dev_lf_rerank", "dk_dbg_dev_lf_refine"):
+        assert re.search(r"\bint %s\(dk_ctx \*ctx," % name, header), name
+        assert name in _lib.SIGNATURES
+        assert len(_lib.SIGNATURES[name][1]) == len(re.search(r"\bint %s\(([^;]*)\);" % name, header).group(1).split(",")), name
+
+
 def test_declared_for_either_purpose():
     """a decoder context serves both: the header names the parameter any_ctx, which tests/test_gpu_decoder_ctx.py::test_refusals goes by"""
     with open(os.path.join(ROOT, "include", "dark_amd.h")) as f:

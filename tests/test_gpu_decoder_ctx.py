@@ -347,6 +347,9 @@ def refused_calls(ctx, n):
         ("dk_dbg_dev_sort_groups", lambda: lib.dk_dbg_dev_sort_groups(h, p(d_a), p(d_b), p(d_c), p(d_d), p(starts), 1, n, 0, 0, 64)),
         ("dk_dbg_dev_rerank", lambda: lib.dk_dbg_dev_rerank(h, p(d_a), 8, None, p(d_b), None, None, 0, n, None, None, None, None, None, None, p(d_c), p(d_c, 4 * n),
                                                             p(d_d), p(d_d, 4 * n), p(d_b, 4 * n), p(d_b, 6 * n), 1024, p(host), 0, 0, -1)),
+        ("dk_dbg_dev_lf_rerank", lambda: lib.dk_dbg_dev_lf_rerank(h, p(d_a), 8, None, 0, p(d_b), 0, p(d_b, 4 * n), None, None, n, p(d_c), p(d_c, 4 * n), p(d_d), p(d_d, 4 * n),
+                                                                  p(d_d, 5 * n), None, None, None, 0, None, 0, 0, p(host), 0)),
+        ("dk_dbg_dev_lf_refine", lambda: lib.dk_dbg_dev_lf_refine(h, p(d_text), n, p(d_a), p(d_a, 4 * n), p(d_b), p(d_b, 4 * n), n // 2, 4, 0, p(d_c), p(d_d), p(host))),
         ("dk_dbg_dev_inverse_permutation", lambda: lib.dk_dbg_dev_inverse_permutation(h, p(d_a), n, p(d_b), None)),
     ], batch
 

@@ -4,8 +4,11 @@ A tile of 2048 slots, 256 threads x 8 slots: heads (the key changes) and reasons
 decides every group that lies inside the tile with two segmented ORs over the waves' ballots and marks the stretches of groups that cross the
 tile's borders (LF_EDGE_FIRST / LF_EDGE_LAST) for k_lf_straddle.  `sim` follows the kernel's arithmetic (ballots as Python integers, the same
 per-wave summaries, the same two scans); `brute` is the definition: a group inside the tile is live iff it has more than one member and a reason.
-This is the model the kernel was written from -- it ran (3000 random tiles) before the kernel ever did; the kernel itself is tested on the GPU
-(tests/test_gpu_parity.py::test_lfirst_bwt_without_the_suffix_array, the fuzz campaign with DK_LFIRST=2)."""
+This is the model the kernel was written from -- it ran (3000 random tiles) before the kernel ever did.  The kernel itself, k_lf_straddle and
+k_lf_apply behind it are tested directly on the GPU by tests/test_gpu_lfirst_layer.py (dk_dbg_dev_lf_rerank on built lists, bit-exact against
+tests/lf_rerank_model.py, whose liveness tests/test_lf_rerank_model.py compares with `brute` below), and the kernels that refine the live groups
+by its second half (dk_dbg_dev_lf_refine); end to end the path is covered by tests/test_gpu_parity.py::test_lfirst_bwt_without_the_suffix_array
+and the fuzz campaign with DK_LFIRST=2.  `_pivot_order` further down is the rule of the deep kernels, checked against plain sorting."""
 import random
 IPT=8; WAVES=4; BLOCK=256; TILE=2048
 def ctz(x): return (x & -x).bit_length()-1

@@ -11,6 +11,9 @@ DK_E_ARG, DK_E_NOMEM, DK_E_HIP, DK_E_CAPACITY, DK_E_MODEL, DK_E_STREAM, DK_E_INT
 FM_NO_HIT = 0xFFFFFFFF  # DK_FM_NO_HIT: a position dk_dev_fm_locate* did not fill
 FM_FIND_MAX_PAIRS = 1 << 24  # DK_FM_FIND_MAX_PAIRS: most (pattern, block) pairs of one dk_dev_fm_find* call
 FM_SEAM_MAX_PATTERN = 4096  # DK_FM_SEAM_MAX_PATTERN: longest pattern of one dk_dev_fm_seams* call (and prev_len stays below it)
+FM_NEAR_MAX_PATTERN = 128  # DK_FM_NEAR_MAX_PATTERN: most positions of a pattern of dk_dev_fm_near*
+FM_NEAR_MAX_K = 3  # DK_FM_NEAR_MAX_K: the largest budget of mismatches
+FM_NEAR_NODE_LIMIT = 1 << 20  # DK_FM_NEAR_NODE_LIMIT: nodes of the search tree one (pattern, block) pair visits where node_limit is 0
 ERROR_NAMES = {-1: "DK_E_ARG", -2: "DK_E_NOMEM", -3: "DK_E_HIP", -4: "DK_E_CAPACITY", -5: "DK_E_MODEL",
                -6: "DK_E_STREAM", -7: "DK_E_INTERNAL", -8: "DK_E_NODEVICE"}
 MODEL_IDS = {"dark": 0, "exp": 1, "ybs": 2, "simple": 3, "rawdc": 4}
@@ -113,6 +116,8 @@ SIGNATURES = {
     "dk_dev_fm_seams": (_i, [_vp, _vp, _sz, _vp, _vp, C.c_uint32, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
     "dk_dev_fm_seams_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, C.c_uint32, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
     "dk_fm_find": (_i, [_vp, _vp, _sz, C.c_uint32, C.c_uint32, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "dk_dev_fm_near": (_i, [_vp, _vp, _sz, _vp, _vp, C.c_uint32, _vp, _sz, _vp, C.c_uint32, C.c_uint32, _sz, _vp, _vp, _vp, _vp]),
+    "dk_dev_fm_near_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, C.c_uint32, _vp, _sz, _vp, C.c_uint32, C.c_uint32, _sz, _vp, _vp, _vp, _vp]),
     "dk_dbg_dev_fm_rank": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
     "dk_dev_dc_encode_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _szp]),
     "dk_batch_push_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),

@@ -35,6 +35,11 @@ Extensions beyond the reference (whole file = one block, read into memory, one t
              GPU, with the last bytes of the text so far carried from pack to pack.  They are listed among the others in file order, in the
              same format; their line is cut at the start of the block holding the match's first byte and at the end of the block holding its
              last one.  --count-only adds them to the counts.  Patterns above 4096 bytes are searched inside the blocks only (a note says so).
+  --mismatches K (0..3) / -i, --ignore-case (with --grep / --grep-hex, not with --across-blocks)
+             approximate search (DESIGN.md 4.18): the places that differ from a pattern in at most K bytes, without insertions or deletions;
+             -i: ASCII letters of every pattern, hexadecimal ones included, match either case.  Patterns hold at most 128 bytes.  With K > 0
+             the lines are absolute_offset:pattern_index:cost:enclosing line; --count-only counts these hits.  A search is bounded: a note
+             says how many (pattern, block) searches stopped at the node limit, whose counts are lower bounds.
 """
 import argparse
 import os
@@ -676,10 +681,12 @@ def enclosing_line(window, at, length):
     return window[left:right if right >= 0 else len(window)]
 
 
-def grep_file(path, model, patterns, device=0, context_bytes=80, count_only=False, max_hits=None, host_threads=0, stats=None, out=None, across=False):
+def grep_file(path, model, patterns, device=0, context_bytes=80, count_only=False, max_hits=None, host_threads=0, stats=None, out=None, across=False,
+              mismatches=0, ignore_case=False):
     """search FILE.dark pack by pack without inverting a block; prints `absolute_offset:pattern_index:enclosing line` per hit in file order (or
     `pattern_index:count` per pattern) and returns the number of occurrences.  A match that straddles two blocks is found with across=True
-    only (--across-blocks)."""
+    only (--across-blocks).  mismatches=K > 0: the places that differ from a pattern in at most K bytes, as
+    `absolute_offset:pattern_index:cost:enclosing line`; ignore_case: ASCII letters without case (--mismatches, -i)."""
     from . import search
     out = out or sys.stdout
     max_hits = search.DEFAULT_MAX_HITS if max_hits is None else max_hits
@@ -687,25 +694,32 @@ def grep_file(path, model, patterns, device=0, context_bytes=80, count_only=Fals
     lines, listed = [], 0
     stats = {} if stats is None else stats
     for found in search.search_archive(path, model, patterns, device, context_bytes, context_bytes, max_hits, host_threads,
-                                       count_only=count_only, stats=stats, across=across):
+                                       count_only=count_only, stats=stats, across=across, mismatches=mismatches, ignore_case=ignore_case):
         hits, occ = found[0], found[1]
         counts += occ.astype(np.int64).sum(axis=1)
         if across:  # the same five fields, from the record that holds the match's first byte
             hits = hits + found[3][0]
             counts += found[3][1].astype(np.int64).sum(axis=1)
         listed += len(hits)
-        for _, start, q, pos, text in hits:
+        for hit in hits:  # (a sixth field, the cost, with mismatches or ignore_case)
+            _, start, q, pos, text = hit[:5]
             at = min(pos, context_bytes)
-            lines.append((start + pos, q, enclosing_line(text, at, len(patterns[q]))))
+            lines.append((start + pos, q, enclosing_line(text, at, len(patterns[q]))) + tuple(hit[5:]))
     if stats.get("seam_skipped"):
         _note("seam_skipped", "pattern%s %s: longer than 4096 bytes, searched inside the blocks only" % (
             "s" if len(stats["seam_skipped"]) > 1 else "", ", ".join(str(q) for q in stats["seam_skipped"])))
+    if stats.get("cut_pairs"):
+        _note("cut_pairs", "%d (pattern, block) searches stopped at the node limit: their counts are lower bounds" % stats["cut_pairs"])
     if count_only:
         for q, c in enumerate(counts):
             print("%d:%d" % (q, c), file=out)
     else:
-        for where, q, text in sorted(lines):  # file order: the device lists a segment's hits in the order (pattern, block, suffix-array slot)
-            print("%d:%d:%s" % (where, q, _escape(text)), file=out)
+        for line in sorted(lines):  # file order: the device lists a segment's hits in the order (pattern, block, suffix-array slot)
+            where, q, text = line[:3]
+            if mismatches:
+                print("%d:%d:%d:%s" % (where, q, line[3], _escape(text)), file=out)
+            else:
+                print("%d:%d:%s" % (where, q, _escape(text)), file=out)
         if listed < int(counts.sum()):
             _note("max_hits", "%d of %d hits listed: at most --max-hits %d per segment of the archive" % (listed, int(counts.sum()), max_hits))
     return int(counts.sum())
@@ -739,6 +753,11 @@ def main(argv=None):
     ap.add_argument("--count-only", action="store_true", help="--grep: print pattern_index:count per pattern only")
     ap.add_argument("--max-hits", type=int, default=None, help="--grep: list at most this many hits per segment of the archive (a pack of up to "
                     "64 MiB; default 65536); counts are always complete")
+    ap.add_argument("--mismatches", type=int, default=None, metavar="K", help="--grep: also list the places that differ from a pattern in at most K "
+                    "bytes (0..3; no insertions or deletions).  With K > 0 the lines are absolute_offset:pattern_index:cost:enclosing line.  Not "
+                    "with --across-blocks")
+    ap.add_argument("-i", "--ignore-case", action="store_true", help="--grep: ASCII letters of every pattern, hexadecimal ones included, match "
+                    "either case.  Not with --across-blocks")
     ap.add_argument("--worker", default="", help=argparse.SUPPRESS)
     ap.add_argument("--part", default="", help=argparse.SUPPRESS)
     ap.add_argument("file")
@@ -749,6 +768,12 @@ def main(argv=None):
     t0 = time.perf_counter()
     if args.across_blocks and not (args.grep or args.grep_hex):
         ap.error("--across-blocks goes with --grep / --grep-hex")
+    if (args.mismatches is not None or args.ignore_case) and not (args.grep or args.grep_hex):
+        ap.error("--mismatches and -i / --ignore-case go with --grep / --grep-hex")
+    if args.mismatches is not None and not 0 <= args.mismatches <= 3:
+        ap.error("--mismatches: 0 .. 3")
+    if (args.mismatches or args.ignore_case) and args.across_blocks:
+        ap.error("--mismatches and -i / --ignore-case do not go with --across-blocks: near hits across block borders are not built")
     if args.grep or args.grep_hex:
         if not decode:
             ap.error("--grep searches a .%s archive" % EXTENSION)
@@ -764,9 +789,11 @@ def main(argv=None):
                 ap.error("--grep-hex %r: not hexadecimal bytes" % h)
         if any(len(p) == 0 for p in patterns):
             ap.error("--grep: an empty pattern")
+        if (args.mismatches or args.ignore_case) and any(len(p) > 128 for p in patterns):
+            ap.error("--mismatches and -i / --ignore-case: patterns of at most 128 bytes")
         st = {}
         found = grep_file(args.file, args.model, patterns, args.device, args.context_bytes, args.count_only, args.max_hits, args.host_threads, st,
-                          across=args.across_blocks)
+                          across=args.across_blocks, mismatches=args.mismatches or 0, ignore_case=args.ignore_case)
         if args.stats:
             import json
             import resource

@@ -117,6 +117,9 @@ def fm_extract_bytes(total, count=1, step=32):
 FM_HIT_DTYPE = np.dtype([("pattern", np.uint32), ("block", np.uint32), ("position", np.uint32), ("slot", np.uint32)])
 # dk_fm_seam_hit: a record of dk_dev_fm_seams* (16 bytes)
 FM_SEAM_HIT_DTYPE = np.dtype([("pattern", np.uint32), ("block", np.uint32), ("back", np.uint32), ("reserved", np.uint32)])
+# dk_fm_near_hit: a record of dk_dev_fm_near* (16 bytes)
+FM_NEAR_HIT_DTYPE = np.dtype([("pattern", np.uint32), ("block", np.uint32), ("position", np.uint32), ("cost", np.uint32)])
+FM_NEAR_MAX_PATTERN, FM_NEAR_MAX_K, FM_NEAR_NODE_LIMIT = _lib.FM_NEAR_MAX_PATTERN, _lib.FM_NEAR_MAX_K, _lib.FM_NEAR_NODE_LIMIT
 
 
 class Context:
@@ -618,6 +621,37 @@ class Context:
                                                   _ptr(d_prev) if prev_len else None, prev_len, _ptr(d_pat), npat, lens, int(max_hits),
                                                   None if d_hits is None else _ptr(d_hits), None if d_occ is None else _ptr(d_occ), C.byref(total)))
         return int(total.value)
+
+    # ---- FM-index near: byte classes and a budget of mismatches; decoder contexts too ----
+    def dev_fm_near(self, d_bwt, n, d_index, d_loc, step, d_cls, pat_lens, k, node_limit, max_hits, d_hits, d_occ=None):
+        """every pattern in d_bwt[0, n) with at most k positions missed -> (total, cut).  d_cls (a uint8 device tensor): 32 bytes per pattern
+        position, bit c & 7 of byte c >> 3 set where byte value c matches, the patterns back to back.  d_occ[q] (uint32 device tensor, or None) =
+        the hits of pattern q; d_hits (16-byte aligned, max_hits records of four uint32 words: pattern, block, position, cost) receives the
+        first min(total, max_hits) in the preorder of the search tree, of which node_limit nodes (0: FM_NEAR_NODE_LIMIT) are visited per pattern;
+        cut = the patterns that stopped there.  max_hits == 0: d_hits and d_loc may be None"""
+        _inputs_ready(d_bwt, d_index, d_cls)
+        npat = len(pat_lens)
+        lens = _sizes(pat_lens)
+        total, cut = C.c_uint64(0), C.c_uint64(0)
+        self._ck(self._lib.dk_dev_fm_near(self._h, _ptr(d_bwt), n, _ptr(d_index), None if d_loc is None else _ptr(d_loc), int(step),
+                                          None if d_cls is None else _ptr(d_cls), npat, lens, int(k), int(node_limit), int(max_hits),
+                                          None if d_hits is None else _ptr(d_hits), None if d_occ is None else _ptr(d_occ), C.byref(total),
+                                          C.byref(cut)))
+        return int(total.value), int(cut.value)
+
+    def dev_fm_near_packed(self, d_bwt, sizes, d_index, d_loc, step, d_cls, pat_lens, k, node_limit, max_hits, d_hits, d_occ=None):
+        """dev_fm_near over a pack: every pattern in every block.  d_occ[q * len(sizes) + b]; the hits in the order (pattern, block, preorder of
+        the pair's tree, slot), positions local to their block; cut = the (pattern, block) pairs that stopped at the node limit"""
+        _inputs_ready(d_bwt, d_index, d_cls)
+        count, npat = len(sizes), len(pat_lens)
+        ns = _sizes(sizes)
+        lens = _sizes(pat_lens)
+        total, cut = C.c_uint64(0), C.c_uint64(0)
+        self._ck(self._lib.dk_dev_fm_near_packed(self._h, _ptr(d_bwt), count, ns, _ptr(d_index), None if d_loc is None else _ptr(d_loc), int(step),
+                                                 None if d_cls is None else _ptr(d_cls), npat, lens, int(k), int(node_limit), int(max_hits),
+                                                 None if d_hits is None else _ptr(d_hits), None if d_occ is None else _ptr(d_occ),
+                                                 C.byref(total), C.byref(cut)))
+        return int(total.value), int(cut.value)
 
     def dbg_dev_fm_rank(self, d_bwt, total, d_index, d_pos, d_sym, d_out):
         """d_out[q] = occurrences of d_sym[q] in d_bwt[0, d_pos[q]) by the count kernel's rank (uint32 / uint8 / uint32 device tensors)"""

@@ -783,6 +783,63 @@ int dk_dev_fm_seams_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, cons
     return dev_fm_seams(ctx, d_bwt, Layout(count, n), d_index, d_ext, step, d_prev, prev_len, d_pat, npat, pat_len, max_hits, d_hits, d_occ, total);
 }
 
+// ---- near: byte classes and a budget of mismatches; find's checks, layout and guard ------------------------------------
+}  // extern "C"
+
+namespace {
+int dev_fm_near(dk_ctx *ctx, const uint8_t *d_bwt, Layout &&lay, const void *d_index, const void *d_loc, uint32_t step, const uint8_t *d_cls, size_t npat,
+                const size_t *pat_len, uint32_t k, uint32_t node_limit, size_t max_hits, dk_fm_near_hit *d_hits, uint32_t *d_occ, uint64_t *total,
+                uint64_t *cut) {
+    DK_TRY(begin_call(ctx));
+    ScopedCall sc(ctx);
+    if (!d_bwt || lay.null() || !d_index || (max_hits && !d_loc)) return ctx->fail(DK_E_ARG, "null pointer");
+    DK_TRY(check_index(ctx, d_index));
+    DK_TRY(lay.check(ctx));
+    const size_t count = lay.count();
+    if (!total) return ctx->fail(DK_E_ARG, "null pointer");
+    DK_TRY(check_step(ctx, step));
+    DK_TRY(check_records(ctx, npat, count, "%zu patterns in %zu blocks: more than DK_FM_FIND_MAX_PAIRS pairs", max_hits, d_hits, 16));
+    if (max_hits) DK_TRY(check_aligned(ctx, addr(d_loc), 4, LOCATE_IS));
+    DK_TRY(check_aligned(ctx, addr(d_occ), 4, "the occurrence matrix is"));
+    if (k > DK_FM_NEAR_MAX_K) return ctx->fail(DK_E_ARG, "a budget of %u mismatches: more than DK_FM_NEAR_MAX_K", k);
+    if (npat == 0) {
+        *total = 0;
+        if (cut) *cut = 0;
+        return DK_OK;
+    }
+    Timer t;
+    Patterns p;
+    DK_TRY(check_patterns(ctx, npat, pat_len, nullptr, count, p));
+    if (p.longest > DK_FM_NEAR_MAX_PATTERN) return ctx->fail(DK_E_ARG, "a pattern of %zu positions: more than DK_FM_NEAR_MAX_PATTERN", p.longest);
+    if (!d_cls && p.bytes()) return ctx->fail(DK_E_ARG, "null pointer");
+    if (ws_round(4 * (count + 1)) + ws_round(4 * (npat + 1)) + fm_near_workspace(npat * count) > ctx->ws_size) {
+        if (lay.packed()) return ctx->fail(DK_E_ARG, "%zu patterns in %zu blocks do not fit the workspace (16 bytes per pair)", npat, count);
+        return ctx->fail(DK_E_ARG, "%zu patterns do not fit the workspace (16 bytes per pair)", npat);
+    }
+    Upload up(ctx);
+    const uint32_t *d_off = lay.device(up), *d_pat_off = upload_offsets(up, p);
+    if (!d_off || !d_pat_off) return up.failed();
+    DK_TRY(fm_near_device(ctx, d_bwt, d_off, count, lay.total(), d_index, d_loc, step, d_cls, d_pat_off, npat, p.bytes(), k, node_limit, max_hits, d_hits,
+                          d_occ, total, cut));
+    DK_TRY(up.sync());
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int dk_dev_fm_near(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, const void *d_index, const void *d_loc, uint32_t step, const uint8_t *d_cls, size_t npat,
+                   const size_t *pat_len, uint32_t k, uint32_t node_limit, size_t max_hits, dk_fm_near_hit *d_hits, uint32_t *d_occ, uint64_t *total,
+                   uint64_t *cut) {
+    return dev_fm_near(ctx, d_bwt, Layout(&n), d_index, d_loc, step, d_cls, npat, pat_len, k, node_limit, max_hits, d_hits, d_occ, total, cut);
+}
+int dk_dev_fm_near_packed(dk_ctx *ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const void *d_index, const void *d_loc, uint32_t step,
+                          const uint8_t *d_cls, size_t npat, const size_t *pat_len, uint32_t k, uint32_t node_limit, size_t max_hits,
+                          dk_fm_near_hit *d_hits, uint32_t *d_occ, uint64_t *total, uint64_t *cut) {
+    return dev_fm_near(ctx, d_bwt, Layout(count, n), d_index, d_loc, step, d_cls, npat, pat_len, k, node_limit, max_hits, d_hits, d_occ, total, cut);
+}
+
 int dk_dbg_dev_fm_rank(dk_ctx *ctx, const uint8_t *d_bwt, size_t total, const void *d_index, const uint32_t *d_pos, const uint8_t *d_sym, size_t nq,
                        uint32_t *d_out) {
     DK_TRY(begin_call(ctx));

@@ -49,7 +49,7 @@ enum KernelSlot : int {
     K_RADIX_SCATTER_TEXT,  // k_radix_scatter<false, true>: first pass, keys built from the text (13 B per pair)
     K_ISA_PARTITION,       // k_isa_init + k_isa_split<true> + k_isa_split<false> (inverse permutation through LDS windows)
     K_ISA_ASSEMBLE,        // k_isa_assemble
-    K_CHAIN,               // k_chain_extract + _ends + _tiles + _spine + _verdicts + _apply (pair chains; their sort is in the radix slots); k_sa_search*, k_fm_count, k_fm_locate, k_fm_extract, k_fm_find_*, k_fm_seam_*
+    K_CHAIN,               // k_chain_extract + _ends + _tiles + _spine + _verdicts + _apply (pair chains; their sort is in the radix slots); k_sa_search*, k_fm_count, k_fm_locate, k_fm_extract, k_fm_find_*, k_fm_seam_*, k_fm_near_*
     K_PERIOD,              // k_period_first + _spine + _fill (next break of the block's dominant period, for the period round)
     K_SLOT_COUNT
 };
@@ -325,6 +325,15 @@ size_t fm_find_workspace(size_t npairs);
 int fm_find_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, const void *d_index, const void *d_loc,
                    uint32_t step, const uint8_t *d_pat, const uint32_t *d_pat_off, size_t npat, size_t pat_bytes, size_t max_hits, void *d_hits,
                    uint32_t *d_occ, uint64_t *total_out);
+// fm_index.hip: every pattern in every block again, the pattern's positions byte classes (d_cls: 32 bytes per position,
+// the patterns back to back as d_pat_off says) and up to k of them missed.  d_occ, *total_out and the order of the pairs as for fm_find_device;
+// inside a pair the hits stand in the preorder of the search tree, of which at most node_limit nodes (0: DK_FM_NEAR_NODE_LIMIT) are visited.
+// *cut_out (host, may be null) = the pairs that stopped there.  d_hits: records {pattern, block, position, cost}.  Takes
+// fm_near_workspace(npat * count) bytes (16 per pair and two rows of chunk sums) and releases them.  Synchronises.
+size_t fm_near_workspace(size_t npairs);
+int fm_near_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, const void *d_index, const void *d_loc,
+                   uint32_t step, const uint8_t *d_cls, const uint32_t *d_pat_off, size_t npat, size_t pat_bytes, uint32_t k, uint32_t node_limit,
+                   size_t max_hits, void *d_hits, uint32_t *d_occ, uint64_t *total_out, uint64_t *cut_out);
 // The extract structure of a packed L (bwt.hip builds it, fm_index.hip reads it): 32-bit words, over the whole pack.
 //   [0, 64) header: magic, total, count, step, anchors | total / step + count anchors
 // Block b's anchors are the ceil(n_b / step) words from its anchor base, the sum of ceil(n_i / step) over the blocks in front of it: anchor k =

@@ -38,6 +38,9 @@
 // FIND     k_fm_find_count a wave per pair (pattern, block) of the grid npat x count: the count's search, lo and occ of the pair (section 4.16)
 //          k_fm_find_scan_a/b/c  the exclusive scan of occ over the pairs in 64-bit sums, the grand total to the mailbox
 //          k_fm_find_locate a wave per hit: the pair from the offsets by a 64-ary search, then the walk of k_fm_locate; one 16-byte record
+// NEAR     k_fm_near_count a wave per pair: backward search that branches over byte classes and a budget of mismatches, depth first with a
+//                          stack in LDS (section 4.18); k_fm_find_scan_a/b/c; k_fm_near_emit the same walk again, every leaf's records at the
+//                          pair's offset; k_fm_near_locate a wave per record, the walk of k_fm_locate from the staged slot
 // Containment: the geometry (off, n, total) comes from the caller, never from the index; every position is clamped to [0, n_b] before it is used
 // and a rank reads L only below the position it counts to.  With an index or an L that is not what the build made the results are unspecified
 // but <= n_b, and nothing outside L, the index, the patterns and the two results is touched.
@@ -219,6 +222,24 @@ struct FmArgs {
     const uint8_t *L; const uint32_t *off, *blocks, *base, *cp; const uint8_t *pat; const uint32_t *pat_off, *pat_blk; uint32_t npat, total, count;
     uint32_t *out_lo, *out_hi;
 };
+// ONE STEP of the backward search in block b = L[s, s + nb), by the whole wave: [lo, hi) of a string w becomes that of c w, as the header derives
+// it; first = 1 for the step from the empty string's (0, nb).  lo and hi are clamped to [0, nb].  Shared by fm_search and the branching search
+// of near (section 4.18): the recurrence stands here and nowhere else.
+__device__ __forceinline__ void fm_step(const uint8_t *__restrict__ L, uint32_t total, const uint32_t *__restrict__ cp, const uint32_t *__restrict__ base,
+                                        uint32_t origin, uint32_t last, uint32_t s, uint32_t nb, uint32_t c, uint32_t first, uint32_t lane, uint32_t &lo,
+                                        uint32_t &hi) {
+    const uint32_t is_last = c == last ? 1u : 0u, bc = base[c];
+    if (lo != hi || first) {
+        uint32_t rl, rh;
+        fm_rank2(L, total, cp, c, s + lo, s + hi, lane, rl, rh);
+        lo = bc + (is_last & ~first) - (is_last & (origin < lo ? 1u : 0u)) + rl;
+        hi = bc + is_last - (is_last & (origin < hi ? 1u : 0u)) + rh;
+    } else {
+        lo = hi = bc + is_last - (is_last & (origin < lo ? 1u : 0u)) + fm_rank1(L, total, cp, c, s + lo, lane);
+    }
+    lo = lo < nb ? lo : nb;
+    hi = hi < nb ? hi : nb;
+}
 // The backward search of the pattern p[0, m) in block b = L[s, s + nb), by the whole wave: lo / hi as the header derives them, clamped to
 // [0, nb] behind every step.  Shared by k_fm_count and k_fm_find_count.
 __device__ __forceinline__ void fm_search(const uint8_t *__restrict__ L, uint32_t total, const uint32_t *__restrict__ cp, const uint32_t *__restrict__ blocks,
@@ -227,20 +248,7 @@ __device__ __forceinline__ void fm_search(const uint8_t *__restrict__ L, uint32_
     const uint32_t origin = blocks[4 * static_cast<size_t>(b) + 2], last = blocks[4 * static_cast<size_t>(b) + 3];
     const uint32_t *__restrict__ base = base_all + static_cast<size_t>(b) * 256;
     uint32_t lo = 0, hi = nb;
-    for (uint32_t j = m; j-- > 0;) {
-        const uint32_t c = p[j], is_last = c == last ? 1u : 0u, first = j + 1u == m ? 1u : 0u;
-        const uint32_t bc = base[c];
-        if (lo != hi || first) {
-            uint32_t rl, rh;
-            fm_rank2(L, total, cp, c, s + lo, s + hi, lane, rl, rh);
-            lo = bc + (is_last & ~first) - (is_last & (origin < lo ? 1u : 0u)) + rl;
-            hi = bc + is_last - (is_last & (origin < hi ? 1u : 0u)) + rh;
-        } else {
-            lo = hi = bc + is_last - (is_last & (origin < lo ? 1u : 0u)) + fm_rank1(L, total, cp, c, s + lo, lane);
-        }
-        lo = lo < nb ? lo : nb;
-        hi = hi < nb ? hi : nb;
-    }
+    for (uint32_t j = m; j-- > 0;) fm_step(L, total, cp, base, origin, last, s, nb, p[j], j + 1u == m ? 1u : 0u, lane, lo, hi);
     lo_out = lo;
     hi_out = hi;
 }
@@ -610,6 +618,195 @@ __global__ __launch_bounds__(64 * FM_WAVES) void k_fm_seam_emit(FmSeamArgs a) {
     }
 }
 
+// ---- near: backward search that branches -- byte classes and a budget of k mismatches ----------------------------------
+// Position j of pattern q is a set of byte values, 32 bytes at cls + 32 (pat_off[q] + j): bit c & 7 of byte c >> 3.  A NODE is (j, w): w a string
+// of m - j bytes that occurs inside block b, whose cost against cls[j, m) -- the positions whose byte is outside its class -- is <= k.  Its
+// range [lo, hi) is not empty.  The root is (m, ""), the children of (j, w) are the nodes (j - 1, c w) in ascending order of c, the leaves are
+// the nodes with j = 0, and the walk is the tree's preorder, at most node_limit nodes of it (the root is the first).  A leaf's slots are hits.
+// A wave walks one pair's tree depth first.  The node it stands at lives in registers: lo, hi, cost and the symbols still to try as four
+// 64-bit masks (symbol 64 j + bit).  Going down pushes them to the wave's stack in LDS, level d = the m - j of the node, at most m - 1 <= 127
+// levels (a leaf is never pushed); every lane stores and loads the same words, so no lane reads what another one wrote.
+constexpr uint32_t FM_NEAR_MAX_M = DK_FM_NEAR_MAX_PATTERN;
+// Which symbols to try at a node.  Without budget left and with a class of at most FM_NEAR_FEW symbols: the class itself -- a rank each, an
+// empty child is dropped behind it.  Otherwise the symbols that occur in L[s + lo, s + hi) (a superset of those with a child: the origin's
+// symbol is among them), cut to the class where no budget is left.  Up to FM_NEAR_ROW bytes the lanes look at the bytes themselves, 16 each;
+// above, at the checkpoint rows around the range.  Both thresholds are REASONED, NOT MEASURED: a presence pass costs about what one rank
+// costs, and a row is what one load per lane covers.
+constexpr uint32_t FM_NEAR_FEW = 2, FM_NEAR_ROW = FM_BLOCK;
+struct FmNearStack {
+    uint32_t lo[FM_NEAR_MAX_M], hi[FM_NEAR_MAX_M], cost[FM_NEAR_MAX_M];
+    uint64_t set[FM_NEAR_MAX_M][4];
+    uint32_t seen[64];  // the presence table of the narrow form, a byte per symbol
+};
+static_assert(sizeof(FmNearStack) * FM_WAVES <= 24 * 1024, "four waves' stacks stay at about 23 KB of LDS");
+
+struct FmNearArgs {
+    const uint8_t *L; const uint32_t *off, *blocks, *base, *cp; const uint8_t *cls; const uint32_t *pat_off; uint32_t npat, total, count, rows, k, limit;
+    uint32_t *occ, *cut, *out_occ;                          // count
+    const uint64_t *offset; uint32_t nhits; uint4 *hits;    // emit
+};
+__device__ __forceinline__ void fm_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// the class at cls32[0, 32) as masks: every lane tests its symbol of each quarter
+__device__ __forceinline__ void fm_near_class(const uint8_t *__restrict__ cls32, uint32_t lane, uint64_t m[4]) {
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) {
+        const uint32_t c = 64u * j + lane;
+        m[j] = __ballot((cls32[c >> 3] >> (c & 7u)) & 1u);
+    }
+}
+// the symbols of L[s + lo, s + hi), lo < hi <= nb, or a superset of them
+__device__ __forceinline__ void fm_near_present(const uint8_t *__restrict__ L, uint32_t total, const uint32_t *__restrict__ cp, uint32_t rows, uint32_t s,
+                                                uint32_t lo, uint32_t hi, uint32_t lane, uint32_t *seen, uint64_t m[4]) {
+    if (hi - lo > FM_NEAR_ROW) {
+        // row k counts L[0, k FM_BLOCK): the rows at and below s + lo and at and above s + hi (the last row covers `total`)
+        const uint32_t row_lo = (s + lo) >> FM_SHIFT, up = (s + hi + FM_BLOCK - 1u) >> FM_SHIFT, row_hi = up < rows ? up : rows - 1u;
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t c = 64u * j + lane;
+            m[j] = __ballot(cp[static_cast<size_t>(row_hi) * 256 + c] != cp[static_cast<size_t>(row_lo) * 256 + c]);
+        }
+        return;
+    }
+    const uint32_t len = hi - lo, mine = len > 16u * lane ? (len - 16u * lane < 16u ? len - 16u * lane : 16u) : 0u;
+    uint64_t a, b;
+    fm_load16(L, total, s + lo + 16u * lane, mine, a, b);  // (s + hi <= total: the geometry is the caller's)
+    seen[lane] = 0;
+    fm_wave_sync();
+    uint8_t *flag = reinterpret_cast<uint8_t *>(seen);
+    for (uint32_t i = 0; i < mine; ++i) flag[(i < 8u ? a >> (8u * i) : b >> (8u * (i - 8u))) & 0xFFu] = 1;  // (racing stores all write 1)
+    fm_wave_sync();
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) m[j] = __ballot(flag[64u * j + lane] != 0);
+    fm_wave_sync();  // (the next call clears the table)
+}
+// The walk of pair (q, b).  Returns the pair's hits; cut = 1 where a node beyond the limit exists.  EMIT: the records of the hits are stored at
+// hits[at + their number in the walk], below nhits only, the slot staged in `position`; the walk ends once nothing below nhits is left.
+// hits never passes nb (it cannot, where the index is one: a position has one text behind it) so that any index gives a count within the block.
+template <bool EMIT>
+__device__ __forceinline__ uint32_t fm_near_walk(const FmNearArgs &a, FmNearStack &st, uint32_t q, uint32_t b, uint32_t lane, uint64_t at, uint32_t &cut) {
+    const uint8_t *__restrict__ L = a.L;
+    const uint32_t *__restrict__ cp = a.cp;
+    const uint32_t po = a.pat_off[q], m_all = a.pat_off[q + 1] - po, m = m_all < FM_NEAR_MAX_M ? m_all : FM_NEAR_MAX_M;
+    const uint32_t s = a.off[b], nb = a.off[b + 1] - s, total = a.total, k = a.k;
+    const uint32_t origin = a.blocks[4 * static_cast<size_t>(b) + 2], last = a.blocks[4 * static_cast<size_t>(b) + 3];
+    const uint32_t *__restrict__ base = a.base + static_cast<size_t>(b) * 256;
+    const uint8_t *__restrict__ cls = a.cls + 32 * static_cast<size_t>(po);
+    uint32_t hits = 0, nodes = 1, d = 0, lo = 0, hi = nb, cost = 0;
+    uint64_t set[4];
+    cut = 0;
+    // the symbols to try at the node in (lo, hi, cost) whose children stand at pattern position pos
+    auto candidates = [&](uint32_t pos) {
+        uint64_t in[4];
+        fm_near_class(cls + 32 * static_cast<size_t>(pos), lane, in);
+        const uint32_t few = static_cast<uint32_t>(__popcll(in[0]) + __popcll(in[1]) + __popcll(in[2]) + __popcll(in[3])) <= FM_NEAR_FEW ? 1u : 0u;
+        if (cost == k && few) {
+            set[0] = in[0], set[1] = in[1], set[2] = in[2], set[3] = in[3];
+            return;
+        }
+        fm_near_present(L, total, cp, a.rows, s, lo, hi, lane, st.seen, set);
+        if (cost == k) set[0] &= in[0], set[1] &= in[1], set[2] &= in[2], set[3] &= in[3];
+    };
+    // a leaf's slots [x, y), its cost: the records of those that still count
+    auto leaf = [&](uint32_t x, uint32_t y, uint32_t leaf_cost) {
+        const uint32_t take = y - x < nb - hits ? y - x : nb - hits;
+        if (EMIT) {
+            for (uint32_t i = lane; i < take; i += 64u) {
+                const uint64_t idx = at + hits + i;
+                if (idx < a.nhits) a.hits[idx] = make_uint4(q, b, x + i, leaf_cost);
+            }
+        }
+        hits += take;
+    };
+    if (m == 0) {  // the root is the only node, and a leaf
+        leaf(lo, hi, 0u);
+        return hits;
+    }
+    candidates(m - 1u);
+    for (;;) {
+        uint32_t c;
+        if (set[0]) c = static_cast<uint32_t>(__builtin_ctzll(set[0])), set[0] &= set[0] - 1ull;
+        else if (set[1]) c = 64u + static_cast<uint32_t>(__builtin_ctzll(set[1])), set[1] &= set[1] - 1ull;
+        else if (set[2]) c = 128u + static_cast<uint32_t>(__builtin_ctzll(set[2])), set[2] &= set[2] - 1ull;
+        else if (set[3]) c = 192u + static_cast<uint32_t>(__builtin_ctzll(set[3])), set[3] &= set[3] - 1ull;
+        else {  // every child of this node has been walked: back to its parent
+            if (d == 0) break;
+            --d;
+            lo = st.lo[d], hi = st.hi[d], cost = st.cost[d];
+            set[0] = st.set[d][0], set[1] = st.set[d][1], set[2] = st.set[d][2], set[3] = st.set[d][3];
+            continue;
+        }
+        const uint32_t pos = m - 1u - d;  // the pattern position of the children
+        uint32_t x = lo, y = hi;
+        fm_step(L, total, cp, base, origin, last, s, nb, c, d == 0 ? 1u : 0u, lane, x, y);
+        if (x >= y) continue;  // no such string in the block
+        const uint32_t child_cost = cost + (((cls[32 * static_cast<size_t>(pos) + (c >> 3)] >> (c & 7u)) & 1u) ^ 1u);
+        if (child_cost > k) continue;
+        if (nodes >= a.limit) {  // a node beyond the limit: the walk stops in front of it
+            cut = 1;
+            break;
+        }
+        ++nodes;
+        if (pos == 0) {
+            leaf(x, y, child_cost);
+            if (EMIT && at + hits >= a.nhits) break;
+            continue;
+        }
+        st.lo[d] = lo, st.hi[d] = hi, st.cost[d] = cost;
+        st.set[d][0] = set[0], st.set[d][1] = set[1], st.set[d][2] = set[2], st.set[d][3] = set[3];
+        ++d;
+        lo = x, hi = y, cost = child_cost;
+        candidates(pos - 1u);
+    }
+    return hits;
+}
+// A wave per pair p = q count + b, grid stride in find's order.  Lane 0 stores the pair's hits and whether it was cut.
+__global__ __launch_bounds__(64 * FM_WAVES) void k_fm_near_count(FmNearArgs a) {
+    __shared__ FmNearStack st[FM_WAVES];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, count = a.count;
+    const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * FM_WAVES, npairs = static_cast<uint64_t>(a.npat) * count;
+    for (uint64_t p = static_cast<uint64_t>(blockIdx.x) * FM_WAVES + wave; p < npairs; p += nwaves) {
+        const uint32_t q = static_cast<uint32_t>(p / count), b = static_cast<uint32_t>(p - static_cast<uint64_t>(q) * count);
+        uint32_t cut;
+        const uint32_t occ = fm_near_walk<false>(a, st[wave], q, b, lane, 0, cut);
+        if (lane == 0) {
+            a.occ[p] = occ;
+            a.cut[p] = cut;
+            if (a.out_occ) a.out_occ[p] = occ;
+        }
+    }
+}
+// A wave per pair with hits below nhits: the same walk with the same limit visits the same nodes, and every leaf's records go to the pair's
+// offset plus the hits so far.  The pair's work is repeated once, not once per hit (the seam emit's decision, section 4.17).
+__global__ __launch_bounds__(64 * FM_WAVES) void k_fm_near_emit(FmNearArgs a) {
+    __shared__ FmNearStack st[FM_WAVES];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, count = a.count;
+    const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * FM_WAVES, npairs = static_cast<uint64_t>(a.npat) * count;
+    for (uint64_t p = static_cast<uint64_t>(blockIdx.x) * FM_WAVES + wave; p < npairs; p += nwaves) {
+        const uint64_t at = a.offset[p];
+        if (a.occ[p] == 0 || at >= a.nhits) continue;
+        const uint32_t q = static_cast<uint32_t>(p / count), b = static_cast<uint32_t>(p - static_cast<uint64_t>(q) * count);
+        uint32_t cut;
+        fm_near_walk<true>(a, st[wave], q, b, lane, at, cut);
+    }
+}
+// A wave per record below nhits: the walk of k_fm_locate from the staged slot; lane 0 rewrites `position`.
+struct FmNearLocArgs { FmWalk w; const uint32_t *off; uint32_t count, nhits; uint4 *hits; };
+__global__ __launch_bounds__(64 * FM_WAVES) void k_fm_near_locate(FmNearLocArgs a) {
+    const uint32_t *__restrict__ off = a.off;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * FM_WAVES;
+    for (uint64_t h = static_cast<uint64_t>(blockIdx.x) * FM_WAVES + (threadIdx.x >> 6); h < a.nhits; h += nwaves) {
+        const uint4 r = a.hits[h];
+        const uint32_t b = r.y < a.count ? r.y : a.count - 1u, s = off[b], nb = off[b + 1] - s, x = r.z < nb ? r.z : nb - 1u;
+        const uint32_t pos = fm_locate_walk(a.w, b, s, nb, x, lane);
+        if (lane == 0) reinterpret_cast<uint32_t *>(a.hits + h)[2] = pos;
+    }
+}
+
 }  // namespace
 
 size_t fm_build_workspace(size_t total, size_t count) {
@@ -743,6 +940,69 @@ int fm_find_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, siz
             // per hit four rounds of 64 offsets, the walk of k_fm_locate and the record
             LaunchScope ls(ctx, K_CHAIN, nhits * (4.0 * 512 + 36.0 + 0.5 * step * (FM_BLOCK + 128 + 64)));
             k_fm_find_locate<<<dim3(grid), dim3(64 * FM_WAVES), 0, st>>>(a);
+        }
+        DK_HIP(ctx, hipGetLastError());
+        DK_HIP(ctx, hipStreamSynchronize(st));
+    }
+    ctx->ws_release(mark);
+    return DK_OK;
+}
+
+size_t fm_near_workspace(size_t npairs) {
+    auto r = [](size_t b) { return (b + 255) & ~size_t(255); };
+    return 2 * r(4 * npairs) + r(8 * npairs) + 2 * r(8 * FM_MAX_CHUNKS);
+}
+
+int fm_near_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, const void *d_index, const void *d_loc,
+                   uint32_t step, const uint8_t *d_cls, const uint32_t *d_pat_off, size_t npat, size_t pat_bytes, uint32_t k, uint32_t node_limit,
+                   size_t max_hits, void *d_hits, uint32_t *d_occ, uint64_t *total_out, uint64_t *cut_out) {
+    hipStream_t st = ctx->stream;
+    const FmIndex ix = fm_carve(const_cast<void *>(d_index), total, count);
+    const size_t npairs = npat * count, rows = div_up(npairs, FM_FIND_ROW), rpc = div_up(rows, FM_MAX_CHUNKS), nchunks = div_up(rows, rpc);
+    const size_t mark = ctx->ws_mark();
+    uint32_t *d_cnt = ctx->ws_alloc<uint32_t>(npairs), *d_cut = ctx->ws_alloc<uint32_t>(npairs);
+    uint64_t *d_offset = ctx->ws_alloc<uint64_t>(npairs), *chunk_sum = ctx->ws_alloc<uint64_t>(FM_MAX_CHUNKS), *cut_sum = ctx->ws_alloc<uint64_t>(FM_MAX_CHUNKS);
+    if (!d_cnt || !d_cut || !d_offset || !chunk_sum || !cut_sum) return DK_E_NOMEM;
+    const uint32_t P = static_cast<uint32_t>(npairs), R = static_cast<uint32_t>(rpc);
+    FmNearArgs a{d_bwt, d_off, ix.blocks, ix.base, ix.cp, d_cls, d_pat_off, static_cast<uint32_t>(npat), static_cast<uint32_t>(total),
+                 static_cast<uint32_t>(count), static_cast<uint32_t>(ix.rows), k, node_limit ? node_limit : DK_FM_NEAR_NODE_LIMIT,
+                 d_cnt, d_cut, d_occ, d_offset, 0u, static_cast<uint4 *>(d_hits)};
+    const unsigned grid = static_cast<unsigned>(std::min<size_t>(div_up(npairs, FM_WAVES), 1u << 20));
+    // What a pair's tree costs is the answer itself.  The bytes given are those of the one path a search without branching takes -- find's, with
+    // 32 bytes of class per position -- so the slot's GB/s is a lower bound.
+    const double path_bytes = static_cast<double>(count) * pat_bytes * (32.0 + 2.0 * (FM_BLOCK + 64));
+    {
+        LaunchScope ls(ctx, K_CHAIN, 20.0 * npairs + path_bytes);
+        k_fm_near_count<<<dim3(grid), dim3(64 * FM_WAVES), 0, st>>>(a);
+    }
+    {
+        LaunchScope ls(ctx, K_CHAIN, 24.0 * npairs);  // occ read twice, the cut flags once, the offsets written
+        k_fm_find_scan_a<<<dim3(static_cast<unsigned>(nchunks)), dim3(256), 0, st>>>(d_cnt, P, R, chunk_sum);
+        k_fm_find_scan_b<<<dim3(1), dim3(256), 0, st>>>(chunk_sum, static_cast<uint32_t>(nchunks), &ctx->d_mail->fm_find.total);
+        k_fm_find_scan_c<<<dim3(static_cast<unsigned>(nchunks)), dim3(256), 0, st>>>(d_cnt, P, R, chunk_sum, d_offset);
+        k_fm_find_scan_a<<<dim3(static_cast<unsigned>(nchunks)), dim3(256), 0, st>>>(d_cut, P, R, cut_sum);
+        k_fm_find_scan_b<<<dim3(1), dim3(256), 0, st>>>(cut_sum, static_cast<uint32_t>(nchunks), &ctx->d_mail->fm_find.near_cut);
+    }
+    DK_HIP(ctx, hipGetLastError());
+    DK_TRY(ctx->mail_read(&ctx->h_mail->fm_find));
+    const uint64_t all = ctx->h_mail->fm_find.total;
+    *total_out = all;
+    if (cut_out) *cut_out = ctx->h_mail->fm_find.near_cut;
+    a.nhits = static_cast<uint32_t>(std::min<uint64_t>(all, max_hits));
+    if (a.nhits) {
+        const FmLocate lc = fm_locate_carve(const_cast<void *>(d_loc), total, count, step);
+        const FmNearLocArgs l{FmWalk{d_bwt, ix.blocks, ix.base, ix.cp, lc.marks, lc.bits, lc.samples, static_cast<uint32_t>(total),
+                                     static_cast<uint32_t>(ceil_log2_u64(step)), static_cast<uint32_t>(lc.nsamp)},
+                              d_off, static_cast<uint32_t>(count), a.nhits, static_cast<uint4 *>(d_hits)};
+        {
+            LaunchScope ls(ctx, K_CHAIN, 12.0 * npairs + path_bytes + 16.0 * a.nhits);  // the pairs' walks again, and the records
+            k_fm_near_emit<<<dim3(grid), dim3(64 * FM_WAVES), 0, st>>>(a);
+        }
+        {
+            // per record the walk of k_fm_locate; the record read, its position written
+            LaunchScope ls(ctx, K_CHAIN, a.nhits * (36.0 + 0.5 * step * (FM_BLOCK + 128 + 64)));
+            const unsigned lgrid = static_cast<unsigned>(std::min<size_t>(div_up(a.nhits, FM_WAVES), 1u << 20));
+            k_fm_near_locate<<<dim3(lgrid), dim3(64 * FM_WAVES), 0, st>>>(l);
         }
         DK_HIP(ctx, hipGetLastError());
         DK_HIP(ctx, hipStreamSynchronize(st));

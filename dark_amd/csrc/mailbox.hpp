@@ -104,6 +104,8 @@ struct Mail {
     // ---- FM-index find (fm_index.hip: fm_find_device) ---------------------------------------------------------------------------------------------
     struct FmFind {
         alignas(8) uint64_t total;  // k_fm_find_scan_b: the hits of all pairs together (a plain store on every launch); the host reads it behind the scan
+        uint64_t near_cut;          // fm_near_device only: k_fm_find_scan_b over the pairs' cut flags (the same plain store, a launch of its own in
+                                    // every call): the pairs that stopped at the node limit; the host reads it with `total`, as one group
     } fm_find;
 };
 static_assert(sizeof(Mail) <= 4096, "the mailbox is one page");

@@ -8,6 +8,26 @@ from .context import Context, DarkError, _pack_patterns, as_u8, fm_extract_bytes
 from . import _lib
 
 
+def classes(pattern, ignore_case=False, wildcard=None):
+    """the byte classes of a pattern for Index.near (section 4.18): an m x 32 uint8 array, row j the set of byte values position j matches, bit
+    c & 7 of byte c >> 3 for byte value c.  Every position is the one-bit class of its byte; under ignore_case an ASCII letter gets the bits
+    of both its cases; the byte value `wildcard`, if given, becomes the full class."""
+    p = as_u8(pattern).astype(np.int64)
+    out = np.zeros((len(p), 32), dtype=np.uint8)
+    rows = np.arange(len(p))
+    out[rows, p >> 3] = (1 << (p & 7)).astype(np.uint8)
+    if ignore_case:
+        letter = ((p | 0x20) >= 0x61) & ((p | 0x20) <= 0x7A)
+        other = p ^ 0x20
+        out[rows[letter], other[letter] >> 3] |= (1 << (other[letter] & 7)).astype(np.uint8)
+    if wildcard is not None:
+        out[p == int(wildcard)] = 0xFF
+    return out
+
+
+_classes = classes  # (Index.near has a keyword of that name)
+
+
 class Index:
     """The index of one block, or of a pack of blocks (`sizes` their lengths, `origins` their origins).
 
@@ -24,7 +44,9 @@ class Index:
     find(patterns, max_hits=65536) -> (occ, hits, total): every pattern in EVERY block as one compact list of (pattern, block, position, slot)
     records (section 4.16); grep(patterns, before, after) -> (pattern, block, position, bytes around the hit) per record.
     seams(patterns, prev=b"", max_hits=65536) -> (occ, hits, total): the matches find cannot see, those that straddle a border between two
-    blocks or between `prev` and the first block (section 4.17); tail(nbytes) -> the last bytes of the whole text, the `prev` of what follows."""
+    blocks or between `prev` and the first block (section 4.17); tail(nbytes) -> the last bytes of the whole text, the `prev` of what follows.
+    near(patterns, k=0, ignore_case=False, wildcard=None) -> (occ, hits, total, cut): find with byte classes at the pattern's positions and up
+    to k of them missed (section 4.18), records (pattern, block, position, cost); near_grep(...) -> the same with the bytes around each hit."""
 
     def __init__(self, ctx, d_bwt, sizes, origins, locate_step=None, extract_step=None):
         import torch
@@ -242,6 +264,68 @@ class Index:
         rows = self._extract_dev(d_start, d_len, len(hits), where, max_len).cpu().numpy().reshape(len(hits), -1)
         return [(int(hits["pattern"][i]), int(blk[i]), int(pos[i]), bytes(rows[i, :got[i]])) for i in range(len(hits))]
 
+    def near(self, patterns, k=0, ignore_case=False, wildcard=None, classes=None, max_hits=65536, node_limit=0):
+        """every pattern in every block with at most k positions missed (section 4.18) -> (occ, hits, total, cut): occ a uint32 array of
+        patterns x blocks, hits a structured array (pattern, block, position, cost) of the first min(total, max_hits) hits in the order
+        (pattern, block, preorder of the pair's search tree, suffix-array slot), total the hits in all, cut the (pattern, block) pairs that
+        stopped at node_limit nodes (0: FM_NEAR_NODE_LIMIT) and whose occ is a lower bound.  A pattern's positions are byte classes: those of
+        fm.classes(pattern, ignore_case, wildcard), or ready-made m x 32 arrays given as classes= in place of `patterns`.  max_hits=0 needs no
+        locate structure."""
+        import torch
+        from .context import FM_NEAR_HIT_DTYPE
+        made = [np.ascontiguousarray(c, dtype=np.uint8).reshape(-1, 32) for c in classes] if classes is not None else \
+            [_classes(p, ignore_case, wildcard) for p in patterns]
+        npat, count, max_hits = len(made), len(self.sizes), int(max_hits)
+        if max_hits and self.d_loc is None:
+            raise DarkError(_lib.DK_E_ARG, "the index was built without a locate structure (locate_step=None): only max_hits=0 is served")
+        if npat == 0:
+            return np.zeros((0, count), np.uint32), np.zeros(0, FM_NEAR_HIT_DTYPE), 0, 0
+        lens = [len(c) for c in made]
+        dev = self.d_bwt.device
+        flat = np.concatenate(made).reshape(-1) if sum(lens) else np.zeros(32, np.uint8)  # (never read: every pattern is empty)
+        d_cls = torch.from_numpy(flat).to(dev)
+        d_occ = torch.empty(npat * count, dtype=torch.int32, device=dev)
+        d_hits = torch.empty(4 * max_hits, dtype=torch.int32, device=dev) if max_hits else None  # (torch allocations are 256-byte aligned)
+        step = self.locate_step if self.locate_step is not None else 32
+        if count == 1:
+            total, cut = self._ctx.dev_fm_near(self.d_bwt, self.total, self.d_index, self.d_loc, step, d_cls, lens, k, node_limit, max_hits, d_hits,
+                                               d_occ)
+        else:
+            total, cut = self._ctx.dev_fm_near_packed(self.d_bwt, self.sizes, self.d_index, self.d_loc, step, d_cls, lens, k, node_limit, max_hits,
+                                                      d_hits, d_occ)
+        got = min(total, max_hits)
+        hits = d_hits[:4 * got].cpu().numpy().view(FM_NEAR_HIT_DTYPE) if got else np.zeros(0, FM_NEAR_HIT_DTYPE)
+        return d_occ.cpu().numpy().view(np.uint32).reshape(npat, count), hits, total, cut
+
+    def near_grep(self, patterns, before, after, k=0, ignore_case=False, wildcard=None, classes=None, max_hits=65536, node_limit=0):
+        """a list of (pattern, block, position, cost, bytes) for the hits of near(...), in its order: bytes is the text from `before` bytes in
+        front of the hit to `after` bytes behind it, cut at the block's ends.  One near, the hits read back, one extract with a window per hit,
+        as grep does.  Needs both structures."""
+        if self.d_loc is None or self.d_ext is None:
+            raise DarkError(_lib.DK_E_ARG, "near_grep needs both structures (locate_step and extract_step)")
+        _, hits, _, _ = self.near(patterns, k, ignore_case, wildcard, classes, max_hits, node_limit)
+        lens = [len(np.asarray(c).reshape(-1, 32)) for c in classes] if classes is not None else [len(as_u8(p)) for p in patterns]
+        return self.near_windows(hits, lens, before, after)
+
+    def near_windows(self, hits, lens, before, after):
+        """near_grep's second half: the records of near(...) with the text around them; lens: the patterns' lengths.  One extract call."""
+        import torch
+        before, after = int(before), int(after)
+        hits = hits[hits["position"] != _lib.FM_NO_HIT]
+        if len(hits) == 0:
+            return []
+        plen = np.array(lens, dtype=np.int64)[hits["pattern"]]
+        pos, blk = hits["position"].astype(np.int64), hits["block"].astype(np.int64)
+        start = np.maximum(pos - before, 0)
+        got = np.minimum(pos - start + plen + after, np.array(self.sizes, dtype=np.int64)[blk] - start)
+        max_len = max(int(got.max()), 1)
+        dev = self.d_bwt.device
+        d_start = torch.from_numpy(start.astype(np.uint32).view(np.int32)).to(dev)
+        d_len = torch.from_numpy(got.astype(np.uint32).view(np.int32)).to(dev)
+        where = None if len(self.sizes) == 1 else [int(b) for b in blk]
+        rows = self._extract_dev(d_start, d_len, len(hits), where, max_len).cpu().numpy().reshape(len(hits), -1)
+        return [(int(hits["pattern"][i]), int(blk[i]), int(pos[i]), int(hits["cost"][i]), bytes(rows[i, :got[i]])) for i in range(len(hits))]
+
     def seams(self, patterns, prev=b"", max_hits=65536):
         """the matches that straddle block borders (section 4.17) -> (occ, hits, total).  `prev` and the blocks are the consecutive pieces of one
         text; a seam hit has its first and its last byte in different pieces and belongs to the block of its last byte.  occ: a uint32 array
@@ -325,4 +409,4 @@ class Index:
         return (hi - lo).astype(np.uint32)
 
 
-__all__ = ["Index", "Context", "fm_index_bytes", "fm_locate_bytes", "fm_extract_bytes"]
+__all__ = ["Index", "classes", "Context", "fm_index_bytes", "fm_locate_bytes", "fm_extract_bytes"]

@@ -15,7 +15,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from ._lib import FM_SEAM_MAX_PATTERN
+from ._lib import FM_NEAR_MAX_K, FM_SEAM_MAX_PATTERN
 from .cli import (ANY_BYTE_SUFFIX, DUMP_MODELS, PACK_BYTES, PACKED_MAX_BLOCK_BYTES, PACKED_MAX_BLOCKS, RAW_CODING_MODELS, _host_threads, _split_n,
                   read_footer)
 
@@ -80,7 +80,7 @@ def _decode_to_bwt(model, word, stream):
 
 
 def search_archive(path, model, patterns, device=0, before=0, after=0, max_hits=DEFAULT_MAX_HITS, host_threads=0, locate_step=32, extract_step=32,
-                   count_only=False, stats=None, across=False, pack_bytes=None):
+                   count_only=False, stats=None, across=False, pack_bytes=None, mismatches=0, ignore_case=False):
     """A generator over the archive's segments.  Per segment it yields (hits, occ, records):
         hits     a list of (record, offset in the original file of the record's first byte, pattern, position in the record, bytes) for the first
                  max_hits hits of the segment in the order (pattern, record, suffix-array slot); bytes is the text from `before` bytes in front of
@@ -99,7 +99,18 @@ def search_archive(path, model, patterns, device=0, before=0, after=0, max_hits=
                    of the record holding the last byte
     The extract structure is then built even for count_only.  Patterns longer than DK_FM_SEAM_MAX_PATTERN are left out of the seam query and
     their indices listed in stats["seam_skipped"].  Between segments the last longest - 1 + before bytes of the text so far are kept on the host
-    (Index.tail).  pack_bytes: see plan."""
+    (Index.tail).  pack_bytes: see plan.
+    mismatches=K (0 .. DK_FM_NEAR_MAX_K) and ignore_case=True search approximately (Index.near): a hit is a place whose text
+    differs from the pattern in at most K bytes, ASCII letters compared without case under ignore_case.  With either option the hit tuples gain
+    `cost`, the number of bytes that differ, as a sixth field, and `bytes` starts `before` bytes in front of the MATCHED TEXT -- which is not the
+    pattern -- so the extract structure is built unless count_only.  stats["cut_pairs"] receives the (pattern, record) searches that stopped at
+    the node limit; their occ is a lower bound.  With both at their defaults the generator runs the exact search and yields its tuples.
+    across=True together with either option raises ValueError: near hits across record borders are not built."""
+    near = bool(mismatches) or bool(ignore_case)
+    if near and across:
+        raise ValueError("across=True goes with the exact search only: near hits across block borders are not built")
+    if not 0 <= int(mismatches) <= FM_NEAR_MAX_K:
+        raise ValueError("mismatches = %r: 0 .. %d" % (mismatches, FM_NEAR_MAX_K))
     import torch
     from . import fm
     from .context import Context
@@ -127,7 +138,9 @@ def search_archive(path, model, patterns, device=0, before=0, after=0, max_hits=
         threads = host_threads or max(1, _host_threads() - 1)
         cap = max(nb for _, _, nb in segments)
         most = max(len(ks) for _, ks, _ in segments)
-        want_text = not count_only and (before or after)
+        want_text = not count_only and (before or after or near)
+        if near and stats is not None:
+            stats["cut_pairs"] = 0
         with Context(cap, device, purpose="decoder", max_blocks=min(most, PACKED_MAX_BLOCKS)) as ctx, ThreadPoolExecutor(threads) as pool:
             for kind, ks, nbytes in segments:
                 streams = []
@@ -149,6 +162,14 @@ def search_archive(path, model, patterns, device=0, before=0, after=0, max_hits=
                     index = fm.Index.from_bwt(ctx, d_bwt, origins[0], locate_step=lstep, extract_step=estep)
                 if stats is not None:
                     stats["resident_bytes"] = max(stats.get("resident_bytes", 0), index.resident_bytes())
+                if near:
+                    occ, recs, _, cut = index.near(patterns, int(mismatches), ignore_case, max_hits=0 if count_only else max_hits)
+                    if stats is not None:
+                        stats["cut_pairs"] += cut
+                    found = index.near_windows(recs, [len(p) for p in patterns], before, after)
+                    yield [(ks[b], int(starts[ks[b]]), q, p, text, cost) for q, b, p, cost, text in found], occ, list(ks)
+                    del index, d_bwt
+                    continue
                 if count_only:
                     occ, _, _ = index.find(patterns, 0)
                     found = []

@@ -399,6 +399,46 @@ int dk_dev_fm_seams_packed(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t count, 
                            uint32_t step, const uint8_t *d_prev, size_t prev_len, const uint8_t *d_pat, size_t npat,
                            const size_t *pat_len /* host */, size_t max_hits, dk_fm_seam_hit *d_hits, uint32_t *d_occ /* may be NULL */,
                            uint64_t *total /* host */);
+/* ---- FM-index: near.  Byte classes and a budget of mismatches (csrc/fm_index.hip) ----
+ * dk_dev_fm_find* with patterns that are sequences of BYTE CLASSES and with up to k positions missed.  Position j of pattern q is a set of
+ * byte values given as 32 bytes: bit c & 7 of byte c >> 3 is set when byte value c matches (one bit: an exact byte; two: an ASCII letter under
+ * ignore-case; all 256: a wildcard; none: legal, never matches for free).  The classes of all patterns lie back to back in d_cls (device,
+ * 32 x the sum of pat_len bytes, any alignment); pat_len in HOST memory, as for find.
+ * The COST of a string w of m bytes against pattern q (m positions) is the number of positions i with w[i] outside cls_q[i]: the Hamming
+ * distance, no insertions or deletions.  The NEAR HITS of q in block b are the positions p in [0, n_b - m] whose text T_b[p, p + m) has cost
+ * <= k, each once, with its cost; a match lies wholly inside its block.  The empty pattern has n_b hits of cost 0.  With k = 0 and one-bit
+ * classes the set of (pattern, block, position) is find's.
+ * THE SEARCH TREE fixes the order and the node limit.  A node is (j, w): 0 <= j <= m, w a string of m - j bytes that occurs wholly inside
+ * block b with cost <= k against cls_q[j .. m).  The root is (m, ""), the children of (j, w) are the nodes (j - 1, c w) in ascending order
+ * of c, the leaves are the nodes with j = 0.  The records stand in ascending order of (pattern, block, leaf in preorder, suffix-array slot
+ * inside the leaf's range) -- the leaves in the order of the matched strings compared from their LAST byte to their first.  The order comes
+ * from an exclusive scan of the pairs' counts; no global atomics, two calls give the same bytes.
+ * Each pair visits at most node_limit nodes, the first min(node_limit, N) of its N in preorder, the root being the first; its hits are the
+ * leaves among them, a prefix of its whole list, and the pair is CUT when N > node_limit.  node_limit = 0: DK_FM_NEAR_NODE_LIMIT.
+ *   d_occ[q * count + b] (device, may be null) = the hits found for the pair, a lower bound where the pair was cut
+ *   *total (HOST, 64 bits) = their sum; *cut (HOST, may be null) = the number of cut pairs
+ *   d_hits (device, 16-byte aligned) receives the first min(*total, max_hits) records; nothing behind them is written.  `position` is what
+ *   dk_dev_fm_locate_packed gives for the slot, DK_FM_NO_HIT included.  max_hits == 0 counts only: d_hits and d_loc may be null.
+ * Contexts of either purpose serve both entries.  There is NO host-memory form and NO C++ mirror (include/dark.hpp) of near.
+ * DK_E_ARG for what dk_dev_fm_find* refuses, a pattern longer than DK_FM_NEAR_MAX_PATTERN, k > DK_FM_NEAR_MAX_K, a null d_cls with patterns
+ * that are not all empty, npat x count > DK_FM_FIND_MAX_PAIRS, max_hits > 2^31, a misaligned d_hits, a null `total`, and a workspace that
+ * cannot hold the pattern offsets, 4 bytes per block and 16 bytes per pair.  dk_workspace_bytes does not grow for it.
+ * The three constants are REASONED, NOT MEASURED: 128 positions keep four waves' stacks at about 23 KB of LDS per workgroup, 3 is where
+ * Hamming search on an index is still commonly used, 2^20 nodes is a guess at "well under a second for one wave".
+ * Contained as find is: the geometry is the caller's, every slot is clamped, the stack's depth is bounded by m, the nodes by the limit and
+ * the children tried per node by 256; for any bytes in L, the index, d_loc and d_cls the call returns, every record has pattern < npat,
+ * block < count, cost <= k and position < n_b or DK_FM_NO_HIT, and nothing outside the named buffers is touched. */
+typedef struct dk_fm_near_hit { uint32_t pattern, block, position, cost; } dk_fm_near_hit; /* 16 bytes */
+#define DK_FM_NEAR_MAX_PATTERN 128u
+#define DK_FM_NEAR_MAX_K 3u
+#define DK_FM_NEAR_NODE_LIMIT (1u << 20)
+int dk_dev_fm_near(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t n, const void *d_index, const void *d_loc, uint32_t step,
+                   const uint8_t *d_cls, size_t npat, const size_t *pat_len /* host */, uint32_t k, uint32_t node_limit, size_t max_hits,
+                   dk_fm_near_hit *d_hits, uint32_t *d_occ /* may be NULL */, uint64_t *total /* host */, uint64_t *cut /* host, may be NULL */);
+int dk_dev_fm_near_packed(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t count, const size_t *n, const void *d_index, const void *d_loc,
+                          uint32_t step, const uint8_t *d_cls, size_t npat, const size_t *pat_len /* host */, uint32_t k, uint32_t node_limit,
+                          size_t max_hits, dk_fm_near_hit *d_hits, uint32_t *d_occ /* may be NULL */, uint64_t *total /* host */,
+                          uint64_t *cut /* host, may be NULL */);
 /* for the tests: d_out[q] = occurrences of d_sym[q] in d_bwt[0, min(d_pos[q], total)), computed by the count kernel's rank (all device memory) */
 int dk_dbg_dev_fm_rank(dk_ctx *any_ctx, const uint8_t *d_bwt, size_t total, const void *d_index,
                        const uint32_t *d_pos, const uint8_t *d_sym, size_t nq, uint32_t *d_out);

@@ -154,6 +154,9 @@ SIGNATURES = {
     "dk_dbg_dev_rerank": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _sz] + [_vp] * 2 + [_vp] * 4 + [_vp] * 6 + [C.c_uint32, _vp, C.c_uint, C.c_uint, _i]),
     "dk_dbg_dev_lf_refine": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, C.c_uint32, _i, _vp, _vp, _vp]),
     "dk_dbg_dev_lf_rerank": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _sz] + [_vp] * 8 + [C.c_uint32, _vp, _i, C.c_uint32, _vp, C.c_uint]),
+    # ctx, n, h, count, idx, pos, gid, gstart, groups | rank, sa, bwt, sym, origin | chain_group, record_cap, max_rounds, always_compact |
+    # out_idx, out_meta, out_sym, out_pos, out[8]
+    "dk_dbg_dev_in_place": (_i, [_vp, _sz, C.c_uint32, _sz, _vp, _vp, _vp, _vp, _sz] + [_vp] * 5 + [_i, C.c_uint32, _i, _i] + [_vp] * 5),
     "dk_dbg_dev_inverse_permutation": (_i, [_vp, _vp, _sz, _vp, _vp]),
     "dk_dbg_mail_fill": (_i, [_vp, _i]),
     "dk_dbg_ws_peek": (_i, [_vp, _sz, _vp]),

@@ -961,6 +961,42 @@ class Context:
                     routes={name for name, bit in _lib.ROUTES.items() if int(out[1]) & bit}, rounds=int(out[2]), deep_count=int(out[3]),
                     arena_used=int(out[4]), giant_count=int(out[5]), fallback=int(out[6]), giant_count_1=int(out[7]))
 
+    def dbg_dev_in_place(self, n, h, idx, pos, gid, gstart, rank, sa=None, bwt=None, sym=None, origin=0xC3C3C3C3, chain_group=-1, record_cap=0,
+                         max_rounds=-1, always_compact=False, fill=0xC3, pad=64):
+        """dk_dbg_dev_in_place: the pair chains, the in-place rounds and the compaction on a list (suffix, SA position and group per slot, gstart
+        with its end entry; rank for every suffix of the text).  sa (n words): the suffix-array mode; bwt (n bytes) with sym: the carried-L mode,
+        the origin word holding `origin` before the call.  Every list output holds `fill` bytes before the call, count + pad entries.
+        -> dict: idx, meta, pos, sym (whole, pad included; sym None in the sa mode), rank, sa or bwt, origin (None in the sa mode) and the
+        counters slots, live, records, list_full, settled, rounds, compactions, routes (names)"""
+        import torch
+        dev = "cuda:%d" % self.device
+        d_idx, d_pos, d_gid, d_gstart, d_rank = (self._to_dev(a, np.uint32) for a in (idx, pos, gid, gstart, rank))
+        count = len(d_idx)
+        if not (len(d_pos) == len(d_gid) == count) or len(d_rank) != n or (sa is None) == (bwt is None) or (bwt is None) != (sym is None):
+            raise DarkError(_lib.DK_E_ARG, "list arrays of different lengths, %d ranks for n = %d, or not exactly one of sa and bwt + sym" % (len(d_rank), n))
+        l_mode = sa is None
+        if len(sa if not l_mode else bwt) != n or (l_mode and len(sym) != count):
+            raise DarkError(_lib.DK_E_ARG, "sa / bwt of n entries, sym of one per slot")
+        u8 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8).copy()).to(dev)  # noqa: E731
+        d_sa = None if l_mode else self._to_dev(sa, np.uint32)
+        d_bwt, d_sym = (u8(bwt), u8(sym)) if l_mode else (None, None)
+        d_origin = self._to_dev(np.array([origin], np.uint32), np.uint32) if l_mode else None
+        out_words = lambda: torch.from_numpy(np.full(4 * (count + pad), fill, np.uint8)).to(dev)  # noqa: E731
+        o_idx, o_meta, o_pos = out_words(), out_words(), out_words()
+        o_sym = u8(np.full(count + pad, fill, np.uint8)) if l_mode else None
+        out = np.zeros(8, np.uint32)
+        p = lambda t: None if t is None else _ptr(t)  # noqa: E731
+        _inputs_ready(d_idx)
+        self._ck(self._lib.dk_dbg_dev_in_place(self._h, int(n), int(h), count, _ptr(d_idx), _ptr(d_pos), _ptr(d_gid), _ptr(d_gstart), len(d_gstart) - 1, _ptr(d_rank),
+                                               p(d_sa), p(d_bwt), p(d_sym), p(d_origin), int(chain_group), int(record_cap), int(max_rounds),
+                                               int(bool(always_compact)), _ptr(o_idx), _ptr(o_meta), p(o_sym), _ptr(o_pos), _ptr(out)))
+        return dict(idx=self._to_host(o_idx, np.uint32), meta=self._to_host(o_meta, np.uint32), pos=self._to_host(o_pos, np.uint32),
+                    sym=None if o_sym is None else o_sym.cpu().numpy(), rank=self._to_host(d_rank, np.uint32),
+                    sa=None if l_mode else self._to_host(d_sa, np.uint32), bwt=d_bwt.cpu().numpy() if l_mode else None,
+                    origin=int(self._to_host(d_origin, np.uint32)[0]) if l_mode else None, slots=int(out[0]), live=int(out[1]), records=int(out[2]),
+                    list_full=int(out[3]), settled=int(out[4]), rounds=int(out[5]), compactions=int(out[6]),
+                    routes={name for name, bit in _lib.ROUTES.items() if int(out[7]) & bit})
+
     def dbg_dev_inverse_permutation(self, sa, marked_val=None):
         """dk_dbg_dev_inverse_permutation: rank[sa[p] & 0x7FFFFFFF] = marked_val[p] if sa[p] has bit 31 set (and marked_val is given) else p"""
         d_sa = self._to_dev(sa, np.uint32)

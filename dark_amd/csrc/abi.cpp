@@ -1541,6 +1541,24 @@ int dk_dbg_dev_lf_refine(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uin
     const DbgLfRefine a{d_text, n, d_idx, d_pos, d_gid, d_sym, count, h0, period, d_bwt, d_origin};
     return dbg_lf_refine_device(ctx, a, out);
 }
+int dk_dbg_dev_in_place(dk_ctx *ctx, size_t n, uint32_t h, size_t count, const uint32_t *d_idx, const uint32_t *d_pos, const uint32_t *d_gid, const uint32_t *d_gstart,
+                        size_t groups, uint32_t *d_rank, uint32_t *d_sa, uint8_t *d_bwt, const uint8_t *d_sym, uint32_t *d_origin, int chain_group, uint32_t record_cap,
+                        int max_rounds, int always_compact, uint32_t *d_out_idx, uint32_t *d_out_meta, uint8_t *d_out_sym, uint32_t *d_out_pos, uint32_t out[8]) {
+    DK_TRY(begin_call(ctx, "dk_dbg_dev_in_place"));
+    ScopedCall sc(ctx);
+    if (!d_idx || !d_pos || !d_gid || !d_gstart || !d_rank || !d_out_idx || !d_out_meta || !d_out_pos || !out) return ctx->fail(DK_E_ARG, "in_place: null pointer");
+    const bool sa_mode = d_sa && !d_bwt && !d_sym && !d_origin && !d_out_sym, l_mode = !d_sa && d_bwt && d_sym && d_origin && d_out_sym;
+    if (!sa_mode && !l_mode) return ctx->fail(DK_E_ARG, "in_place: exactly one of d_sa and (d_bwt, d_sym, d_origin, d_out_sym)");
+    if (n < 2 || n > ctx->max_n || n > 0x7FFFFFFEull) return ctx->fail(DK_E_ARG, "in_place: text of %zu bytes (2 .. the context capacity %zu)", n, ctx->max_n);
+    if (count == 0 || count > n) return ctx->fail(DK_E_ARG, "in_place: %zu slots for a text of %zu bytes", count, n);
+    if (groups == 0 || groups > count || groups > n / 2 + 1) return ctx->fail(DK_E_ARG, "in_place: %zu groups of %zu slots (the table holds n / 2 + 2 words)", groups, count);
+    if (h == 0) return ctx->fail(DK_E_ARG, "in_place: depth 0");
+    if (chain_group > 4) return ctx->fail(DK_E_ARG, "in_place: chain_group %d (0: no chains, 2 .. 4, negative: the sort's own)", chain_group);
+    if (record_cap > n) return ctx->fail(DK_E_ARG, "in_place: record_cap %u above n = %zu, what the record buffers hold", record_cap, n);
+    const DbgInPlace a{n, h, count, d_idx, d_pos, d_gid, d_gstart, groups, d_rank, d_sa, d_bwt, d_sym, d_origin, chain_group, record_cap, max_rounds, always_compact,
+                       d_out_idx, d_out_meta, d_out_sym, d_out_pos};
+    return dbg_in_place_device(ctx, a, out);
+}
 int dk_dbg_dev_inverse_permutation(dk_ctx *ctx, const uint32_t *d_sa, size_t n, uint32_t *d_rank, const uint32_t *d_marked_val) {
     DK_TRY(begin_call(ctx, "dk_dbg_dev_inverse_permutation"));
     ScopedCall sc(ctx);

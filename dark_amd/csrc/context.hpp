@@ -236,6 +236,15 @@ struct DbgLfRefine {
     uint8_t *bwt; uint32_t *origin;
 };
 int dbg_lf_refine_device(dk_ctx *ctx, const DbgLfRefine &args, uint32_t out[8]);
+// dk_dbg_dev_in_place's arguments under the names of the header: in_place_rounds() on the caller's list.  sa, or bwt + sym + origin (+ out_sym).
+// out: slots, live, chain records, list full, settled by the chains, rounds launched, compactions, sa_route.  Synchronises.
+struct DbgInPlace {
+    size_t n; uint32_t h; size_t count; const uint32_t *idx, *pos, *gid, *gstart; size_t groups;
+    uint32_t *rank, *sa; uint8_t *bwt; const uint8_t *sym; uint32_t *origin;
+    int chain_group; uint32_t record_cap; int max_rounds, always_compact;
+    uint32_t *out_idx, *out_meta; uint8_t *out_sym; uint32_t *out_pos;
+};
+int dbg_in_place_device(dk_ctx *ctx, const DbgInPlace &args, uint32_t out[8]);
 // bwt.hip
 int bwt_gather_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_sa, size_t n, uint8_t *d_bwt, uint32_t *origin);
 int bwt_inverse_device(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t origin, uint8_t *d_out);

@@ -2177,20 +2177,36 @@ struct InPlaceList {
 };
 constexpr unsigned PL_RING = LIVE_RING - 1u;
 
+// What dk_dbg_dev_in_place may ask of in_place_rounds; the sort itself passes the defaults.
+struct InPlacePlan {
+    int chain_group = -1;         // 0: no pair chains; 2 .. CH_K: groups of up to this many members get records; negative: DK_PAIR_CHAINS / DK_CHAIN_GROUP
+    uint32_t record_cap = 0;      // records k_chain_extract may reserve; 0: n, what the buffers hold
+    int max_rounds = -1;          // in-place rounds launched at most, the ring drained behind them; negative: to the end
+    bool always_compact = false;  // compact behind the chains and behind every round read, whatever the counts
+};
+// ... and what it tells about the run (null: nobody asks)
+struct InPlaceReport {
+    InPlaceList list{};  // as the last round or compaction left it: the `_a` set is current (pos: SaBuffers::pos)
+    uint32_t records = 0, list_full = 0;
+    size_t settled = 0;
+    unsigned rounds = 0, compactions = 0;
+};
+
 // pair chains first: the groups of two (three, four) that long repeats leave behind are settled by one comparison per chain.
 // Expects the in-place list before its first round; leaves the settled slots dead and *settled = how many.
-int pair_chains(SaSort &s, InPlaceList &l, size_t *settled) {
+int pair_chains(SaSort &s, InPlaceList &l, size_t *settled, const InPlacePlan &plan, InPlaceReport *rep) {
     SaBuffers &b = s.b;
     const size_t n = s.n, slots = l.slots;
     *settled = 0;
-    if (DK_KNOB("DK_PAIR_CHAINS", 1) == 0 || slots < 2) return DK_OK;
+    if ((plan.chain_group < 0 ? DK_KNOB("DK_PAIR_CHAINS", 1) : plan.chain_group) == 0 || slots < 2) return DK_OK;
     uint64_t *rec_key = b.keys, *rec_key_alt = b.keys_alt;  // (all free at this point: nothing is sorted globally any more)
     uint32_t *rec_slot = b.vals_3, *rec_slot_alt = b.pos_alt;
     uint8_t *planes = reinterpret_cast<uint8_t *>(b.keys_3);  // CH_K - 1 planes of one verdict byte per slot (3 n of the buffer's 8 n bytes) ...
     uint8_t *rec_verdict = planes + static_cast<size_t>(CH_K - 1) * n;  // ... and one byte per record behind them
-    const int kmax = std::min(CH_K, std::max(2, DK_KNOB("DK_CHAIN_GROUP", CH_K)));
+    const int kmax = std::min(CH_K, std::max(2, plan.chain_group < 0 ? DK_KNOB("DK_CHAIN_GROUP", CH_K) : plan.chain_group));
     const int lbits = static_cast<int>(ceil_log2_u64(n));
-    const uint32_t cap = static_cast<uint32_t>(std::min<size_t>(n, 0xFFFFFFF0u));  // records the buffers hold (n each); what does not fit stays with the rounds
+    uint32_t cap = static_cast<uint32_t>(std::min<size_t>(n, 0xFFFFFFF0u));  // records the buffers hold (n each); what does not fit stays with the rounds
+    if (plan.record_cap) cap = std::min(cap, plan.record_cap);
     uint32_t *d_cnt = s.ctx->d_mail->chain_cnt;  // [0] records, [1] first reservation that did not fit
     const uint32_t *cnt = s.ctx->h_mail->chain_cnt;
     DK_TRY(s.ctx->mail_fill(&d_cnt[0], 0));
@@ -2203,6 +2219,7 @@ int pair_chains(SaSort &s, InPlaceList &l, size_t *settled) {
     DK_HIP(s.ctx, hipGetLastError());
     DK_TRY(s.ctx->mail_read(&s.ctx->h_mail->chain_cnt));
     const uint32_t m = std::min(cnt[0], cnt[1]);
+    if (rep) rep->records = m, rep->list_full = cnt[1] != 0xFFFFFFFFu;
     if (s.trace) fprintf(stderr, "[dk] pair chains: %u pairs inside groups of 2..%d among %zu slots%s (h = %llu)\n", m, kmax, slots, cnt[1] != 0xFFFFFFFFu ? " (list full)" : "",
                          static_cast<unsigned long long>(s.h));
     if (m == 0) return DK_OK;
@@ -2301,7 +2318,7 @@ int in_place_read(SaSort &s, InPlaceList &l) {
 
 // ... then in place (k_plateau_sort): one sort kernel + one rank kernel per round, the live count read back one round late.
 // Expects what doubling_rounds left: the ranks, and a list whose groups all have at most PL_MAX members; leaves every suffix placed.
-int in_place_rounds(SaSort &s) {
+int in_place_rounds(SaSort &s, const InPlacePlan &plan = InPlacePlan(), InPlaceReport *rep = nullptr) {
     if (s.c.active == 0) return DK_OK;
     SaBuffers &b = s.b;
     s.route() |= DK_ROUTE_INPLACE_ROUNDS;
@@ -2313,22 +2330,31 @@ int in_place_rounds(SaSort &s) {
     }
     std::swap(l.meta_a, l.meta_b);  // gid was read, gid_alt written
     size_t settled_by_chains = 0;
-    DK_TRY(pair_chains(s, l, &settled_by_chains));
+    unsigned rounds = 0, compactions = 0;  // launched | run, over the whole call
+    DK_TRY(pair_chains(s, l, &settled_by_chains, plan, rep));
     l.live = s.c.active - settled_by_chains;
-    if (l.live > 0 && settled_by_chains && l.live * 4 <= l.slots && l.slots >= (1u << 16)) DK_TRY(in_place_compact(s, l));  // the chains left mostly dead slots behind
-    for (; l.live > 0;) {
+    if (l.live > 0 && (plan.always_compact || (settled_by_chains && l.live * 4 <= l.slots && l.slots >= (1u << 16)))) {  // the chains left mostly dead slots behind
+        DK_TRY(in_place_compact(s, l));
+        ++compactions;
+    }
+    for (; l.live > 0 && (plan.max_rounds < 0 || rounds < static_cast<unsigned>(plan.max_rounds));) {
         DK_TRY(check_round_limit(s.ctx));
         DK_TRY(in_place_launch(s, l));
+        ++rounds;
         if (l.launched - l.read < 2) continue;  // keep one round ahead of the host
         DK_TRY(in_place_read(s, l));
         if (l.live == 0) break;  // the round launched since ran over dead slots only
-        if (l.live * 4 <= l.slots && l.slots >= (1u << 16)) {
+        if (plan.always_compact || (l.live * 4 <= l.slots && l.slots >= (1u << 16))) {
             // mostly dead slots: drain the round in flight, then compact (live slots keep their order: groups stay contiguous)
             DK_TRY(in_place_read(s, l));
             if (l.live == 0) break;
             DK_TRY(in_place_compact(s, l));
+            ++compactions;
         }
     }
+    if (plan.max_rounds >= 0)  // a bounded run is looked at afterwards: nothing stays in flight
+        while (l.read < l.launched) DK_TRY(in_place_read(s, l));
+    if (rep) rep->list = l, rep->settled = settled_by_chains, rep->rounds = rounds, rep->compactions = compactions;
     s.c.active = 0;
     return DK_OK;
 }
@@ -2411,6 +2437,48 @@ int dbg_lf_refine_device(dk_ctx *ctx, const DbgLfRefine &a, uint32_t out[8]) {
     DK_TRY(ctx->mail_read(&ctx->h_mail->lf));
     const Mail::LFirst &lf = ctx->h_mail->lf;
     const uint32_t v[8] = {static_cast<uint32_t>(step), ctx->stats.sa_route, ctx->stats.rounds, lf.deep_count, lf.arena_used, lf.giant_count[0], lf.fallback, lf.giant_count[1]};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    ctx->ws_release(mark);
+    return DK_OK;
+}
+
+// dk_dbg_dev_in_place (abi.cpp has checked the arguments): in_place_rounds() on the caller's list -- the sort's buffers for n from the workspace, the
+// list copied into the set the rounds start from (vals, pos, gid, gstart, sym) and the ranks into theirs; SA / L and the origin word are the
+// caller's own arrays, as in the sort.  Afterwards the ranks and the list's current set go back to the caller.
+// out: slots | live | chain records | list full | slots the chains settled | rounds launched | compactions | sa_route
+int dbg_in_place_device(dk_ctx *ctx, const DbgInPlace &a, uint32_t out[8]) {
+    const size_t n = a.n, mark = ctx->ws_mark();
+    ctx->stats.rounds = 0;
+    ctx->stats.sa_route = 0;
+    SaSort s{};
+    s.ctx = ctx, s.st = ctx->stream, s.n = n, s.d_sa = a.sa, s.d_bwt = a.bwt, s.d_origin = a.origin, s.carry_bwt = a.bwt != nullptr;
+    s.trace = DK_KNOB("DK_TRACE", 0) != 0;
+    s.h = a.h, s.have_ranks = true;
+    DK_TRY(alloc_buffers(ctx, n, s.carry_bwt, &s.b));
+    SaBuffers &b = s.b;
+    hipStream_t st = ctx->stream;
+    DK_HIP(ctx, hipMemcpyAsync(b.vals, a.idx, a.count * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    DK_HIP(ctx, hipMemcpyAsync(b.pos, a.pos, a.count * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    DK_HIP(ctx, hipMemcpyAsync(b.gid, a.gid, a.count * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    DK_HIP(ctx, hipMemcpyAsync(b.gstart, a.gstart, (a.groups + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    DK_HIP(ctx, hipMemcpyAsync(b.rank, a.rank, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    if (s.carry_bwt) DK_HIP(ctx, hipMemcpyAsync(b.sym, a.sym, a.count, hipMemcpyDeviceToDevice, st));
+    s.c.active = a.count, s.c.groups = a.groups;
+    InPlacePlan plan;
+    plan.chain_group = a.chain_group, plan.record_cap = a.record_cap, plan.max_rounds = a.max_rounds, plan.always_compact = a.always_compact != 0;
+    InPlaceReport rep;
+    DK_TRY(in_place_rounds(s, plan, &rep));
+    const InPlaceList &l = rep.list;
+    DK_HIP(ctx, hipMemcpyAsync(a.rank, b.rank, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    if (l.live > 0) {  // (nothing alive: the last round launched has copied nothing, and nobody reads the list again)
+        DK_HIP(ctx, hipMemcpyAsync(a.out_idx, l.idx_a, l.slots * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        DK_HIP(ctx, hipMemcpyAsync(a.out_meta, l.meta_a, l.slots * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        DK_HIP(ctx, hipMemcpyAsync(a.out_pos, b.pos, l.slots * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        if (s.carry_bwt) DK_HIP(ctx, hipMemcpyAsync(a.out_sym, l.sym_a, l.slots, hipMemcpyDeviceToDevice, st));
+    }
+    DK_HIP(ctx, hipStreamSynchronize(st));
+    const uint32_t v[8] = {static_cast<uint32_t>(l.slots), static_cast<uint32_t>(l.live), rep.records, rep.list_full, static_cast<uint32_t>(rep.settled), rep.rounds,
+                           rep.compactions, ctx->stats.sa_route};
     for (int i = 0; i < 8; ++i) out[i] = v[i];
     ctx->ws_release(mark);
     return DK_OK;

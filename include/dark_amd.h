@@ -679,6 +679,34 @@ int dk_dbg_dev_lf_rerank(dk_ctx *ctx, const void *d_keys, int key_bytes, const u
  * h0 == 0 or above n, a period below 0 or above h0.  DK_E_NOMEM when the sort's workspace for n (and 4 n bytes with a period) does not fit. */
 int dk_dbg_dev_lf_refine(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uint32_t *d_idx, const uint32_t *d_pos, const uint32_t *d_gid, const uint8_t *d_sym,
                          size_t count, uint32_t h0, int period, uint8_t *d_bwt, uint32_t *d_origin, uint32_t out[8]);
+/* The last stage of the suffix-array path on a list the caller built: in_place_rounds() of csrc/suffix_array.hip -- k_to_inplace, the pair chains
+ * (k_chain_extract, the record sort, k_chain_ends / _tiles / _spine / _verdicts / _apply), the in-place rounds (k_plateau_sort, k_plateau_ranks) and the
+ * compaction (k_plateau_count / _scan / _compact) -- with the sort's own buffers for n from the workspace.  A full context only.  None of these
+ * kernels reads the text: they work from the ranks, the list and h.  tests/in_place_model.py is the definition of every output.
+ *   n, h        the text's length and the depth the members of a group are equal to (the kernels get min(h, n))
+ *   the list    `count` slots: the suffix d_idx[a] and its SA position d_pos[a]; d_gid[a] = the slot's group and d_gstart[g] = the group's first
+ *               slot, d_gstart[groups] = count: the format rerank writes, which k_to_inplace reads
+ *   d_rank      n words, in and out: rank[x] = the SA position of the head of x's group (of x itself where x is final)
+ *   the mode    d_sa (n words): finals are written as sa[position] = suffix.  Or d_bwt (n bytes) with d_sym (the symbol in front of every slot), d_origin
+ *               and d_out_sym: finals are written as bwt[position] = symbol, *d_origin = the position of suffix 0 when it becomes final.  The symbol is
+ *               a free label: no kernel here derives it from the text.  In the d_sa mode there is no origin word
+ *   chain_group    0: no pair chains; 2 .. 4: groups of up to that many members get records (1 counts as 2); negative: the sort's own
+ *   record_cap     0: n, as in the sort; otherwise the records k_chain_extract may reserve (what does not fit stays with the rounds)
+ *   max_rounds     negative: to the end; k: at most k rounds are launched and waited for; 0: k_to_inplace and the chains only
+ *   always_compact 0: as the sort decides; 1: a compaction behind the chains and behind every round read while slots are alive, whatever the counts
+ *   the list afterwards   d_out_idx, d_out_meta, d_out_pos (d_out_sym): out[0] entries of the set the last round or compaction wrote -- a suffix with
+ *               bit 31 set is final since the last round, 0xFFFFFFFF since longer; meta = offset in the group | (size - 1) << 8 | moved << 16; meta and
+ *               sym mean something in live slots only.  Nothing is copied when no slot is alive (out[1] == 0): nobody reads the list again
+ *   out         (host, 8 words) slots | live slots | chain records | 1 = the record list was full | slots the chains settled | rounds launched |
+ *               compactions | DK_ROUTE_* bits
+ * The caller's duties: every group has at most 256 members; the members of a group are equal in their first h symbols (so each has h symbols);
+ * d_rank as above for EVERY suffix of the text; d_idx distinct and below n, d_pos distinct and below n; output arrays of `count` entries.
+ * DK_E_ARG before anything is launched: a null context or pointer, both modes or neither (or half of the second), an open batch, n below 2 or above
+ * the context's capacity, count == 0 or above n, groups == 0 or above count or n / 2 + 1, h == 0, chain_group above 4, record_cap above n.
+ * DK_E_NOMEM when the sort's workspace for n does not fit. */
+int dk_dbg_dev_in_place(dk_ctx *ctx, size_t n, uint32_t h, size_t count, const uint32_t *d_idx, const uint32_t *d_pos, const uint32_t *d_gid, const uint32_t *d_gstart,
+                        size_t groups, uint32_t *d_rank, uint32_t *d_sa, uint8_t *d_bwt, const uint8_t *d_sym, uint32_t *d_origin, int chain_group, uint32_t record_cap,
+                        int max_rounds, int always_compact, uint32_t *d_out_idx, uint32_t *d_out_meta, uint8_t *d_out_sym, uint32_t *d_out_pos, uint32_t out[8]);
 /* d_rank[d_sa[p]] = p for a permutation d_sa of 0 .. n-1 (n <= 2^31), through LDS windows.  d_marked_val (may be null): an entry of d_sa with bit
  * 31 set stands for d_sa[p] & 0x7FFFFFFF and its value is d_marked_val[p] instead of p.  The two n-u64 scratch arrays come from the context's
  * workspace: DK_E_NOMEM when they do not fit.  What it does with an input that is no permutation is not defined beyond "no store outside d_rank". */

@@ -38,6 +38,20 @@ def test_layer_entries_of_the_lfirst_path():
         assert len(_lib.SIGNATURES[name][1]) == len(re.search(r"\bint %s\(([^;]*)\);" % name, header).group(1).split(",")), name
 
 
+def test_layer_entry_of_the_in_place_rounds():
+    """dk_dbg_dev_in_place (tests/test_gpu_in_place.py): the same three facts"""
+    lib = dark_amd.load_library()
+    out = (C.c_uint32 * 8)(*([7] * 8))
+    assert lib.dk_dbg_dev_in_place(None, 100, 4, 10, None, None, None, None, 5, None, None, None, None, None, -1, 0, -1, 0, None, None, None, None,
+                                   C.cast(out, C.c_void_p)) == _lib.DK_E_ARG
+    assert list(out) == [7] * 8
+    with open(os.path.join(ROOT, "include", "dark_amd.h")) as f:
+        header = f.read()
+    name = "dk_dbg_dev_in_place"
+    assert re.search(r"\bint %s\(dk_ctx \*ctx," % name, header)
+    assert len(_lib.SIGNATURES[name][1]) == len(re.search(r"\bint %s\(([^;]*)\);" % name, header).group(1).split(","))
+
+
 def test_declared_for_either_purpose():
     """a decoder context serves both: the header names the parameter any_ctx, which tests/test_gpu_decoder_ctx.py::test_refusals goes by"""
     with open(os.path.join(ROOT, "include", "dark_amd.h")) as f:

@@ -350,6 +350,8 @@ def refused_calls(ctx, n):
         ("dk_dbg_dev_lf_rerank", lambda: lib.dk_dbg_dev_lf_rerank(h, p(d_a), 8, None, 0, p(d_b), 0, p(d_b, 4 * n), None, None, n, p(d_c), p(d_c, 4 * n), p(d_d), p(d_d, 4 * n),
                                                                   p(d_d, 5 * n), None, None, None, 0, None, 0, 0, p(host), 0)),
         ("dk_dbg_dev_lf_refine", lambda: lib.dk_dbg_dev_lf_refine(h, p(d_text), n, p(d_a), p(d_a, 4 * n), p(d_b), p(d_b, 4 * n), n // 2, 4, 0, p(d_c), p(d_d), p(host))),
+        ("dk_dbg_dev_in_place", lambda: lib.dk_dbg_dev_in_place(h, n, 4, n // 2, p(d_a), p(d_a, 4 * n), p(d_b), p(d_b, 4 * n), n // 4, p(d_c), p(d_c, 4 * n), None, None, None,
+                                                                -1, 0, -1, 0, p(d_d), p(d_d, 2 * n), None, p(d_d, 4 * n), p(host))),
         ("dk_dbg_dev_inverse_permutation", lambda: lib.dk_dbg_dev_inverse_permutation(h, p(d_a), n, p(d_b), None)),
     ], batch
 

@@ -157,6 +157,11 @@ SIGNATURES = {
     # ctx, n, h, count, idx, pos, gid, gstart, groups | rank, sa, bwt, sym, origin | chain_group, record_cap, max_rounds, always_compact |
     # out_idx, out_meta, out_sym, out_pos, out[8]
     "dk_dbg_dev_in_place": (_i, [_vp, _sz, C.c_uint32, _sz, _vp, _vp, _vp, _vp, _sz] + [_vp] * 5 + [_i, C.c_uint32, _i, _i] + [_vp] * 5),
+    # ctx, text, n, h, count, idx, pos, gid, gstart, groups | rank, tsym, period, next_break | sa, bwt, sym, origin |
+    # out_sorted_keys, out_sorted_idx, out_sorted_sym, out_idx, out_pos, out_gid, out_gstart, out_sym, out[8]
+    "dk_dbg_dev_round": (_i, [_vp, _vp, _sz, C.c_uint32, _sz, _vp, _vp, _vp, _vp, _sz] + [_vp, _i, _i, _vp] + [_vp] * 4 + [_vp] * 9),
+    # ctx, text, n | period, next_break | run_out[2], probe_out[8] | count_p, count_out | search_pmax, found_out[32] | m, span, cands, ncands, dups_out[4]
+    "dk_dbg_dev_period": (_i, [_vp, _vp, _sz, _i, _vp, _vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _i, _vp]),
     "dk_dbg_dev_inverse_permutation": (_i, [_vp, _vp, _sz, _vp, _vp]),
     "dk_dbg_mail_fill": (_i, [_vp, _i]),
     "dk_dbg_ws_peek": (_i, [_vp, _sz, _vp]),

@@ -997,6 +997,79 @@ class Context:
                     list_full=int(out[3]), settled=int(out[4]), rounds=int(out[5]), compactions=int(out[6]),
                     routes={name for name, bit in _lib.ROUTES.items() if int(out[7]) & bit})
 
+    def _text_at(self, text, offset):
+        """the text on the device `offset` bytes behind an aligned address -> (tensor that owns it, address of its first byte)"""
+        import torch
+        host = np.zeros(len(text) + offset, np.uint8)
+        host[offset:] = np.asarray(text, dtype=np.uint8)
+        t = torch.from_numpy(host).to("cuda:%d" % self.device)
+        return t, t.data_ptr() + offset
+
+    def dbg_dev_round(self, text, h, idx, pos, gid, gstart, rank=None, tsym=0, period=0, next_break=None, sa=None, bwt=None, sym=None, origin=0xC3C3C3C3,
+                      text_offset=0, fill=0xC3, pad=64):
+        """dk_dbg_dev_round: one general round on a list (suffix, SA position and group per slot, gstart with its end entry).  tsym 0: a doubling
+        round on rank; above: a text round; period with next_break: a token round.  sa (n words): the suffix-array mode; bwt (n bytes) with sym: the
+        carried-L mode, the origin word holding `origin` before the call.  text_offset: bytes between an aligned address and the text's first.
+        Every list output holds `fill` bytes before the call, count + pad entries.
+        -> dict: sorted_keys, sorted_idx, sorted_sym, idx, pos, gid, gstart, sym (whole, pad included; the syms None in the sa mode), rank (None
+        without), sa or bwt, origin (None in the sa mode) and the counters active, groups, big_slots, big_groups, above_pl_slots, advanced,
+        routes (names), kb"""
+        import torch
+        dev = "cuda:%d" % self.device
+        n = len(text)
+        d_idx, d_pos, d_gid, d_gstart = (self._to_dev(a, np.uint32) for a in (idx, pos, gid, gstart))
+        count = len(d_idx)
+        if not (len(d_pos) == len(d_gid) == count) or (sa is None) == (bwt is None) or (bwt is None) != (sym is None):
+            raise DarkError(_lib.DK_E_ARG, "list arrays of different lengths, or not exactly one of sa and bwt + sym")
+        l_mode = sa is None
+        if len(sa if not l_mode else bwt) != n or (l_mode and len(sym) != count) or (rank is not None and len(rank) != n) or \
+                (next_break is not None and len(next_break) != n):
+            raise DarkError(_lib.DK_E_ARG, "sa / bwt / rank / next_break of n entries, sym of one per slot")
+        u8 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8).copy()).to(dev)  # noqa: E731
+        keep, d_text = self._text_at(text, text_offset)
+        d_rank = None if rank is None else self._to_dev(rank, np.uint32)
+        d_nb = None if next_break is None else self._to_dev(next_break, np.uint32)
+        d_sa = None if l_mode else self._to_dev(sa, np.uint32)
+        d_bwt, d_sym = (u8(bwt), u8(sym)) if l_mode else (None, None)
+        d_origin = self._to_dev(np.array([origin], np.uint32), np.uint32) if l_mode else None
+        filled = lambda width: torch.from_numpy(np.full(width * (count + pad), fill, np.uint8)).to(dev)  # noqa: E731
+        o_skeys, o_sidx, o_idx, o_pos, o_gid, o_gstart = filled(8), filled(4), filled(4), filled(4), filled(4), filled(4)
+        o_ssym, o_sym = (filled(1), filled(1)) if l_mode else (None, None)
+        out = np.zeros(8, np.uint32)
+        p = lambda t: None if t is None else _ptr(t)  # noqa: E731
+        _inputs_ready(d_idx)
+        self._ck(self._lib.dk_dbg_dev_round(self._h, d_text, n, int(h), count, _ptr(d_idx), _ptr(d_pos), _ptr(d_gid), _ptr(d_gstart), len(d_gstart) - 1, p(d_rank),
+                                            int(tsym), int(period), p(d_nb), p(d_sa), p(d_bwt), p(d_sym), p(d_origin), _ptr(o_skeys), _ptr(o_sidx), p(o_ssym),
+                                            _ptr(o_idx), _ptr(o_pos), _ptr(o_gid), _ptr(o_gstart), p(o_sym), _ptr(out)))
+        del keep
+        words = lambda t: self._to_host(t, np.uint32)  # noqa: E731
+        return dict(sorted_keys=self._to_host(o_skeys, np.uint64), sorted_idx=words(o_sidx), sorted_sym=None if o_ssym is None else o_ssym.cpu().numpy(),
+                    idx=words(o_idx), pos=words(o_pos), gid=words(o_gid), gstart=words(o_gstart), sym=None if o_sym is None else o_sym.cpu().numpy(),
+                    rank=None if d_rank is None else words(d_rank), sa=None if l_mode else words(d_sa), bwt=d_bwt.cpu().numpy() if l_mode else None,
+                    origin=int(words(d_origin)[0]) if l_mode else None, active=int(out[0]), groups=int(out[1]), big_slots=int(out[2]), big_groups=int(out[3]),
+                    above_pl_slots=int(out[4]), advanced=int(out[5]), routes={name for name, bit in _lib.ROUTES.items() if int(out[6]) & bit}, kb=int(out[7]))
+
+    def dbg_dev_period(self, text, period=0, run=False, probe=False, count_p=0, search_pmax=0, prefix=None, text_offset=0, fill=0xC3, pad=64):
+        """dk_dbg_dev_period: the period kernels and the probes on a text `text_offset` bytes behind an aligned address.  period: the next-break
+        array (n + pad words over `fill`); run / probe: k_run_probe's 2 and k_period_probe's 8 words; count_p: k_period_count's word; search_pmax:
+        k_period_search's words; prefix = (m, span, lengths): k_prefix_probe's four.  -> dict of what was asked for: next_break, run, probe,
+        count, found, dups"""
+        import torch
+        n = len(text)
+        keep, d_text = self._text_at(text, text_offset)
+        d_nb = torch.from_numpy(np.full(4 * (n + pad), fill, np.uint8)).to("cuda:%d" % self.device) if period else None
+        host = lambda words, on: np.full(words, 0xC3C3C3C3, np.uint32) if on else None  # noqa: E731
+        run_out, probe_out, count_out, found_out, dups_out = host(2, run), host(8, probe), host(1, count_p), host(32, search_pmax), host(4, prefix is not None)
+        m, span, lengths = prefix if prefix is not None else (0, 0, None)
+        cands = None if lengths is None else np.asarray(lengths, dtype=np.int32)
+        p = lambda a: None if a is None else _ptr(a)  # noqa: E731
+        _inputs_ready(keep)
+        self._ck(self._lib.dk_dbg_dev_period(self._h, d_text, n, int(period), p(d_nb), p(run_out), p(probe_out), int(count_p), p(count_out), int(search_pmax),
+                                             p(found_out), int(m), int(span), p(cands), 0 if cands is None else len(cands), p(dups_out)))
+        del keep
+        return dict(next_break=None if d_nb is None else self._to_host(d_nb, np.uint32), run=run_out, probe=probe_out,
+                    count=None if count_out is None else int(count_out[0]), found=found_out, dups=dups_out)
+
     def dbg_dev_inverse_permutation(self, sa, marked_val=None):
         """dk_dbg_dev_inverse_permutation: rank[sa[p] & 0x7FFFFFFF] = marked_val[p] if sa[p] has bit 31 set (and marked_val is given) else p"""
         d_sa = self._to_dev(sa, np.uint32)

@@ -1559,6 +1559,51 @@ int dk_dbg_dev_in_place(dk_ctx *ctx, size_t n, uint32_t h, size_t count, const u
                        d_out_idx, d_out_meta, d_out_sym, d_out_pos};
     return dbg_in_place_device(ctx, a, out);
 }
+int dk_dbg_dev_round(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t h, size_t count, const uint32_t *d_idx, const uint32_t *d_pos, const uint32_t *d_gid,
+                     const uint32_t *d_gstart, size_t groups, uint32_t *d_rank, int tsym, int period, const uint32_t *d_next_break, uint32_t *d_sa, uint8_t *d_bwt,
+                     const uint8_t *d_sym, uint32_t *d_origin, uint64_t *d_out_sorted_keys, uint32_t *d_out_sorted_idx, uint8_t *d_out_sorted_sym, uint32_t *d_out_idx,
+                     uint32_t *d_out_pos, uint32_t *d_out_gid, uint32_t *d_out_gstart, uint8_t *d_out_sym, uint32_t out[8]) {
+    DK_TRY(begin_call(ctx, "dk_dbg_dev_round"));
+    ScopedCall sc(ctx);
+    if (!d_text || !d_idx || !d_pos || !d_gid || !d_gstart || !d_out_sorted_keys || !d_out_sorted_idx || !d_out_idx || !d_out_pos || !d_out_gid || !d_out_gstart || !out)
+        return ctx->fail(DK_E_ARG, "round: null pointer");
+    const bool sa_mode = d_sa && !d_bwt && !d_sym && !d_origin && !d_out_sorted_sym && !d_out_sym;
+    const bool l_mode = !d_sa && d_bwt && d_sym && d_origin && d_out_sorted_sym && d_out_sym;
+    if (!sa_mode && !l_mode) return ctx->fail(DK_E_ARG, "round: exactly one of d_sa and (d_bwt, d_sym, d_origin, d_out_sorted_sym, d_out_sym)");
+    if (n < 2 || n > ctx->max_n || n > 0x7FFFFFFEull) return ctx->fail(DK_E_ARG, "round: text of %zu bytes (2 .. the context capacity %zu)", n, ctx->max_n);
+    if (count == 0 || count > n) return ctx->fail(DK_E_ARG, "round: %zu slots for a text of %zu bytes", count, n);
+    if (groups == 0 || groups > count || groups > n / 2 + 1) return ctx->fail(DK_E_ARG, "round: %zu groups of %zu slots (the table holds n / 2 + 2 words)", groups, count);
+    if (h == 0) return ctx->fail(DK_E_ARG, "round: depth 0");
+    if (tsym < 0 || tsym > 63) return ctx->fail(DK_E_ARG, "round: tsym %d (0: a doubling round, 1 .. 63 symbols of text)", tsym);
+    if (tsym == 0 && !d_rank) return ctx->fail(DK_E_ARG, "round: a doubling round without d_rank");
+    if (period < 0 || static_cast<uint32_t>(period) > h || period > (1 << 18)) return ctx->fail(DK_E_ARG, "round: period %d (0 .. min(h, 2^18))", period);
+    if ((period > 0) != (d_next_break != nullptr)) return ctx->fail(DK_E_ARG, "round: d_next_break goes with a period, and only with one");
+    if (period > 0 && tsym != 8) return ctx->fail(DK_E_ARG, "round: a token round has tsym 8, as the sort passes it (got %d)", tsym);
+    const DbgRound a{d_text, n, h, count, d_idx, d_pos, d_gid, d_gstart, groups, d_rank, tsym, period, d_next_break, d_sa, d_bwt, d_sym, d_origin,
+                     d_out_sorted_keys, d_out_sorted_idx, d_out_sorted_sym, d_out_idx, d_out_pos, d_out_gid, d_out_gstart, d_out_sym};
+    return dbg_round_device(ctx, a, out);
+}
+int dk_dbg_dev_period(dk_ctx *ctx, const uint8_t *d_text, size_t n, int period, uint32_t *d_next_break, uint32_t run_out[2], uint32_t probe_out[8], uint32_t count_p,
+                      uint32_t *count_out, uint32_t search_pmax, uint32_t *found_out, uint32_t m, uint32_t span, const int *cands, int ncands, uint32_t dups_out[4]) {
+    DK_TRY(begin_call(ctx, "dk_dbg_dev_period"));
+    ScopedCall sc(ctx);
+    if (!d_text) return ctx->fail(DK_E_ARG, "period: null text");
+    if (n == 0 || n > ctx->max_n || n > 0x7FFFFFFEull) return ctx->fail(DK_E_ARG, "period: text of %zu bytes (1 .. the context capacity %zu)", n, ctx->max_n);
+    if (period < 0 || period > (1 << 18) || (period > 0) != (d_next_break != nullptr))
+        return ctx->fail(DK_E_ARG, "period: period %d (0: no next breaks, 1 .. 2^18 with d_next_break, and d_next_break only with one)", period);
+    if ((count_p != 0) != (count_out != nullptr)) return ctx->fail(DK_E_ARG, "period: count_out goes with a period to count, and only with one");
+    if ((search_pmax != 0) != (found_out != nullptr) || (search_pmax != 0 && (search_pmax < 9 || search_pmax > (1u << 18))))
+        return ctx->fail(DK_E_ARG, "period: search_pmax %u (0: no search, 9 .. 2^18 with found_out, and found_out only with one)", search_pmax);
+    if (dups_out) {
+        if (!cands || ncands < 1 || ncands > 4) return ctx->fail(DK_E_ARG, "period: %d candidate lengths (1 .. 4)", ncands);
+        if (m == 0 || m > n || m > (1u << 24) || span == 0) return ctx->fail(DK_E_ARG, "period: %u samples (1 .. min(n, 2^24)) a span of %u (at least 1) apart", m, span);
+    } else if (m || span || cands || ncands) {
+        return ctx->fail(DK_E_ARG, "period: prefix-probe arguments without dups_out");
+    }
+    if (period == 0 && !run_out && !probe_out && !count_out && !found_out && !dups_out) return ctx->fail(DK_E_ARG, "period: no part asked for");
+    const DbgPeriod a{d_text, n, period, d_next_break, run_out, probe_out, count_p, count_out, search_pmax, found_out, m, span, cands, ncands, dups_out};
+    return dbg_period_device(ctx, a);
+}
 int dk_dbg_dev_inverse_permutation(dk_ctx *ctx, const uint32_t *d_sa, size_t n, uint32_t *d_rank, const uint32_t *d_marked_val) {
     DK_TRY(begin_call(ctx, "dk_dbg_dev_inverse_permutation"));
     ScopedCall sc(ctx);

@@ -245,6 +245,24 @@ struct DbgInPlace {
     uint32_t *out_idx, *out_meta; uint8_t *out_sym; uint32_t *out_pos;
 };
 int dbg_in_place_device(dk_ctx *ctx, const DbgInPlace &args, uint32_t out[8]);
+// dk_dbg_dev_round's arguments under the names of the header: one general_round() on the caller's list.  sa, or bwt + sym + origin (+ out_sym, out_sorted_sym).
+// out: active, groups, big slots, big groups, slots above PL_MAX, symbols advanced, sa_route, kb.  Synchronises.
+struct DbgRound {
+    const uint8_t *text; size_t n; uint32_t h; size_t count; const uint32_t *idx, *pos, *gid, *gstart; size_t groups;
+    uint32_t *rank; int tsym, period; const uint32_t *next_break;
+    uint32_t *sa; uint8_t *bwt; const uint8_t *sym; uint32_t *origin;
+    uint64_t *out_sorted_keys; uint32_t *out_sorted_idx; uint8_t *out_sorted_sym;
+    uint32_t *out_idx, *out_pos, *out_gid, *out_gstart; uint8_t *out_sym;
+};
+int dbg_round_device(dk_ctx *ctx, const DbgRound &args, uint32_t out[8]);
+// dk_dbg_dev_period's arguments under the names of the header: the period kernels and the probes on the caller's text, each part switched on by its
+// output (next_break: by period > 0).  Synchronises.
+struct DbgPeriod {
+    const uint8_t *text; size_t n; int period; uint32_t *next_break;
+    uint32_t *run_out, *probe_out; uint32_t count_p, *count_out; uint32_t search_pmax, *found_out;
+    uint32_t m, span; const int *cands; int ncands; uint32_t *dups_out;
+};
+int dbg_period_device(dk_ctx *ctx, const DbgPeriod &args);
 // bwt.hip
 int bwt_gather_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_sa, size_t n, uint8_t *d_bwt, uint32_t *origin);
 int bwt_inverse_device(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t origin, uint8_t *d_out);

@@ -1744,6 +1744,40 @@ struct SaSort {
     const uint32_t *narrow_starts() const { return narrow_keys ? ctx->d_mail->narrow_starts : nullptr; }
 };
 
+// The launches of the probes, shared by the phases below and dk_dbg_dev_period.  Each enqueues on ctx->stream and nothing else: the phases keep their
+// size thresholds, the clearing of the words written and the reading back.
+void enqueue_run_probe(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d_flag) {
+    k_run_probe<<<dim3(div_up(div_up(n, 256), 256)), dim3(256), 0, ctx->stream>>>(d_text, n, d_flag);
+}
+void enqueue_period_probe(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t *d_counts) {
+    k_period_probe<<<dim3(div_up(div_up(n, 64), 256)), dim3(256), 0, ctx->stream>>>(d_text, n, d_counts);
+}
+void enqueue_period_search(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t pmax, uint32_t *d_found) {
+    LaunchScope ls(ctx, K_PERIOD, 0.0);
+    k_period_search<<<dim3(PS_SAMPLES), dim3(256), 0, ctx->stream>>>(d_text, n, pmax, d_found);
+}
+void enqueue_period_count(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t p, uint32_t *d_windows) {
+    LaunchScope ls(ctx, K_PERIOD, 2.0 * n);
+    k_period_count<<<dim3(div_up(div_up(n, 64), 256)), dim3(256), 0, ctx->stream>>>(d_text, n, p, d_windows);
+}
+// the smallest table the probe of m samples and cands.count lengths gets: a power of two, at most half full
+uint32_t prefix_probe_table(uint32_t m, int cands) {
+    uint32_t table_size = 1;
+    while (table_size < 2u * cands * m) table_size <<= 1;
+    return table_size;
+}
+// table: table_size words, emptied here; d_dups: cleared by the caller
+int enqueue_prefix_probe(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uint8_t *d_code, int bits, int spk, uint32_t m, uint32_t span, const ProbeCands &cands,
+                         uint64_t *table, uint32_t table_size, uint32_t *d_dups) {
+    DK_HIP(ctx, hipMemsetAsync(table, 0xFF, static_cast<size_t>(table_size) * sizeof(uint64_t), ctx->stream));
+    {
+        LaunchScope ls(ctx, K_PREFIX_PROBE, 16.0 * m);
+        k_prefix_probe<<<dim3(div_up(m, 256)), dim3(256), 0, ctx->stream>>>(d_text, n, d_code, bits, spk, m, span, cands, table, table_size - 1, d_dups);
+    }
+    DK_HIP(ctx, hipGetLastError());
+    return DK_OK;
+}
+
 // 1. alphabet.  Expects nothing; leaves the code table, sigma / bits / spk and the probes' verdicts (sigma <= 1: bits and spk unset)
 int read_alphabet(SaSort &s) {
     const size_t n = s.n;
@@ -1754,8 +1788,8 @@ int read_alphabet(SaSort &s) {
         LaunchScope ls(s.ctx, K_SYM_HIST, 1.0 * n);
         const size_t blocks = std::min<size_t>(div_up(n, 256 * 64), 2048);
         k_sym_hist<<<dim3(blocks), dim3(256), 0, s.st>>>(s.d_text, n, d_alpha->hist);
-        if (s.d_bwt && s.allow_lfirst && n >= (1u << 16)) k_run_probe<<<dim3(div_up(div_up(n, 256), 256)), dim3(256), 0, s.st>>>(s.d_text, n, d_alpha->run_probe);
-        if (s.period_mode != 0 && n >= (1u << 12)) k_period_probe<<<dim3(div_up(div_up(n, 64), 256)), dim3(256), 0, s.st>>>(s.d_text, n, d_alpha->period_probe);
+        if (s.d_bwt && s.allow_lfirst && n >= (1u << 16)) enqueue_run_probe(s.ctx, s.d_text, n, d_alpha->run_probe);
+        if (s.period_mode != 0 && n >= (1u << 12)) enqueue_period_probe(s.ctx, s.d_text, n, d_alpha->period_probe);
     }
     DK_TRY(s.ctx->mail_read(&s.ctx->h_mail->alphabet));
     const Mail::Alphabet &alpha = s.alpha();
@@ -1774,6 +1808,12 @@ int read_alphabet(SaSort &s) {
     return DK_OK;
 }
 
+// the code table to the device, where the text-key kernels read it
+int upload_code(SaSort &s) {
+    DK_HIP(s.ctx, hipMemcpyAsync(s.ctx->d_mail->code, s.code, sizeof s.code, hipMemcpyHostToDevice, s.st));
+    return DK_OK;
+}
+
 // 2. how long a prefix must the initial sort cover?  Expects the alphabet, carry_bwt and the buffers; leaves spk_sort, key_shift, narrow_keys,
 //    short_prefix, probe_big_share, and the code tables on the device.
 //    DK_PREFIX: 0 = always the full key, 1 = ask the sample (default),
@@ -1783,7 +1823,7 @@ int choose_prefix(SaSort &s) {
     const size_t n = s.n;
     const int bits = s.bits, spk = s.spk;
     uint8_t *d_code = s.ctx->d_mail->code;
-    DK_HIP(s.ctx, hipMemcpyAsync(d_code, s.code, sizeof s.code, hipMemcpyHostToDevice, s.st));
+    DK_TRY(upload_code(s));
     const int prefix_mode = DK_KNOB("DK_PREFIX", 1);
     s.spk_sort = spk;
     s.probe_big_share = 0.0;
@@ -1798,19 +1838,10 @@ int choose_prefix(SaSort &s) {
         } else if (cands.count > 0) {
             const uint32_t m = static_cast<uint32_t>(std::min<double>(n / 2.0, 10.0 * std::sqrt(static_cast<double>(n))));
             const uint32_t span = static_cast<uint32_t>(n / m);
-            uint32_t table_size = 1;
-            while (table_size < 2u * cands.count * m) table_size <<= 1;
             uint64_t *table = s.b.keys_3;  // free until the first big-group sort
-            uint32_t *d_dups = s.ctx->d_mail->dups;
             const uint32_t *dups = s.ctx->h_mail->dups;
-            DK_HIP(s.ctx, hipMemsetAsync(table, 0xFF, static_cast<size_t>(table_size) * sizeof(uint64_t), s.st));
             DK_TRY(s.ctx->mail_fill(&s.ctx->d_mail->dups, 0));
-            {
-                LaunchScope ls(s.ctx, K_PREFIX_PROBE, 16.0 * m);
-                k_prefix_probe<<<dim3(div_up(m, 256)), dim3(256), 0, s.st>>>(s.d_text, n, d_code, bits, spk, m, span, cands, table, table_size - 1,
-                                                                            d_dups);
-            }
-            DK_HIP(s.ctx, hipGetLastError());
+            DK_TRY(enqueue_prefix_probe(s.ctx, s.d_text, n, d_code, bits, spk, m, span, cands, table, prefix_probe_table(m, cands.count), s.ctx->d_mail->dups));
             DK_TRY(s.ctx->mail_read(&s.ctx->h_mail->dups));
             // m is 10 sqrt(n), so c equal pairs in the sample say that about c / 50 of ALL suffixes share their prefix with another one.
             // A radix pass over everything costs what a text round costs for about an eighth of it: up to 4 equal pairs (8 %) the
@@ -1929,7 +1960,9 @@ int first_rerank(SaSort &s) {
 // own slot range (small groups in LDS, big ones through the global sort) -> rerank.  *advanced: the symbols the round added (text
 // rounds: the big groups' keys may hold fewer symbols than the small groups' -- the depth every group is known to is the smaller).
 // Expects the active list and its counts (and the ranks when tsym == 0); leaves the next list and its counts.  h is the caller's to advance.
-int general_round(SaSort &s, int tsym, int *advanced, int period = 0, const uint32_t *next_break = nullptr) {
+// rep (null: nobody asks): the key widths the round chose, for dk_dbg_dev_round.
+struct RoundReport { int kbits = 0, kb = 0, bsbits = 0, big_carry = 0; };
+int general_round(SaSort &s, int tsym, int *advanced, int period = 0, const uint32_t *next_break = nullptr, RoundReport *rep = nullptr) {
     SaBuffers &b = s.b;
     const size_t n = s.n, active = s.c.active, nbig = s.c.big;
     const int bsbits = s.c.big_groups > 1 ? static_cast<int>(ceil_log2_u64(s.c.big_groups)) : 1;  // bits of a big group's dense index
@@ -1963,6 +1996,7 @@ int general_round(SaSort &s, int tsym, int *advanced, int period = 0, const uint
     if (nbig > 0) s.route() |= DK_ROUTE_BIG_GROUPS;
     const int big_carry = s.carry_bwt && kb + bsbits + 8 <= 64 ? 1 : 0;  // the big list's keys have room for the symbol in front
     uint32_t *bslot = b.pos_alt;  // written by the rerank at the end of the round only: free until k_big_back has read it
+    if (rep) rep->kbits = kbits, rep->kb = kb, rep->bsbits = bsbits, rep->big_carry = big_carry;
     {
         LaunchScope ls(s.ctx, K_ROUND_LOCAL, 8.0 * active + 4.0 * active + 12.0 * active);
         const auto round_local = tsym > 0 ? k_round_local<true> : k_round_local<false>;
@@ -2109,10 +2143,7 @@ int find_long_period(SaSort &s) {
     const uint32_t pmax = static_cast<uint32_t>(std::min<uint64_t>(PS_MAX, n / 4));
     DK_TRY(s.ctx->mail_fill(&s.ctx->d_mail->found, 0xFF));
     DK_TRY(s.ctx->mail_fill(d_windows, 0));
-    {
-        LaunchScope ls(s.ctx, K_PERIOD, 0.0);
-        k_period_search<<<dim3(PS_SAMPLES), dim3(256), 0, s.st>>>(s.d_text, n, pmax, d_found);
-    }
+    enqueue_period_search(s.ctx, s.d_text, n, pmax, d_found);
     DK_TRY(s.ctx->mail_read(&s.ctx->h_mail->found));
     uint32_t best = 0, best_votes = 0;  // the period most samples agree on
     for (int a = 0; a < PS_SAMPLES; ++a) {
@@ -2123,10 +2154,7 @@ int find_long_period(SaSort &s) {
         if (votes > best_votes || (votes == best_votes && v < best)) { best = v; best_votes = votes; }
     }
     if (best_votes < PS_SAMPLES / 4) return DK_OK;
-    {
-        LaunchScope ls(s.ctx, K_PERIOD, 2.0 * n);
-        k_period_count<<<dim3(div_up(div_up(n, 64), 256)), dim3(256), 0, s.st>>>(s.d_text, n, best, d_windows);
-    }
+    enqueue_period_count(s.ctx, s.d_text, n, best, d_windows);
     DK_TRY(s.ctx->mail_read(&s.ctx->h_mail->found_windows));
     const uint32_t windows = s.ctx->h_mail->found_windows;
     // three quarters of the block: a Fibonacci word follows "period 55" in 47 % of its windows, in stretches of a few hundred symbols that one
@@ -2480,6 +2508,132 @@ int dbg_in_place_device(dk_ctx *ctx, const DbgInPlace &a, uint32_t out[8]) {
     const uint32_t v[8] = {static_cast<uint32_t>(l.slots), static_cast<uint32_t>(l.live), rep.records, rep.list_full, static_cast<uint32_t>(rep.settled), rep.rounds,
                            rep.compactions, ctx->stats.sa_route};
     for (int i = 0; i < 8; ++i) out[i] = v[i];
+    ctx->ws_release(mark);
+    return DK_OK;
+}
+
+namespace {
+// what a rerank leaves in the mailbox for the classification behind it (k_big_reduce reads `groups` on the device), for a list that no rerank wrote
+int set_list_counts(dk_ctx *ctx, size_t active, size_t groups) {
+    Mail::Rounds &r = ctx->h_mail->cls.rounds;  // (pinned: the copy reads it when it runs, and the next write to it is a mail_read behind that copy)
+    r = Mail::Rounds{};
+    r.active = static_cast<uint32_t>(active), r.groups = static_cast<uint32_t>(groups);
+    DK_HIP(ctx, hipMemcpyAsync(&ctx->d_mail->cls.rounds, &r, sizeof r, hipMemcpyHostToDevice, ctx->stream));
+    return DK_OK;
+}
+// the alphabet of a text for an entry that starts behind read_alphabet's place in the sort: a text of one byte value gets one-bit codes
+int dbg_alphabet(SaSort &s) {
+    DK_TRY(read_alphabet(s));
+    if (s.sigma <= 1) s.bits = 1, s.spk = 64;
+    return upload_code(s);
+}
+}  // namespace
+
+// dk_dbg_dev_round (abi.cpp has checked the arguments): one general_round() on the caller's list -- the sort's buffers for n from the workspace, the
+// list copied into the set a round starts from (vals, pos, gid, gstart, sym), the ranks into theirs, the counts into the mailbox as a rerank leaves
+// them, and the groups classified by classify_and_read; the text, SA / L, the origin word and the next-break positions are the caller's own arrays.
+// Afterwards: the sorted state rerank has read (keys, vals_alt, sym_alt), the next list, the ranks.
+// out: active | groups | big slots | big groups | slots above PL_MAX | symbols advanced | sa_route | kb
+int dbg_round_device(dk_ctx *ctx, const DbgRound &a, uint32_t out[8]) {
+    const size_t n = a.n, mark = ctx->ws_mark();
+    ctx->stats.rounds = 0;
+    ctx->stats.sa_route = 0;
+    SaSort s{};
+    s.ctx = ctx, s.st = ctx->stream, s.d_text = a.text, s.n = n, s.d_sa = a.sa, s.d_bwt = a.bwt, s.d_origin = a.origin, s.carry_bwt = a.bwt != nullptr;
+    s.trace = DK_KNOB("DK_TRACE", 0) != 0;
+    s.h = a.h, s.have_ranks = a.rank != nullptr;
+    DK_TRY(alloc_buffers(ctx, n, s.carry_bwt, &s.b));
+    SaBuffers &b = s.b;
+    hipStream_t st = ctx->stream;
+    int tsym = a.tsym;
+    if (tsym > 0) {
+        DK_TRY(dbg_alphabet(s));
+        if (a.period == 0 && s.bits < 5) tsym = std::min(tsym, 63 / s.bits);  // coded keys: what 63 bits hold, as text_rounds passes
+    }
+    DK_HIP(ctx, hipMemcpyAsync(b.vals, a.idx, a.count * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    DK_HIP(ctx, hipMemcpyAsync(b.pos, a.pos, a.count * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    DK_HIP(ctx, hipMemcpyAsync(b.gid, a.gid, a.count * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    DK_HIP(ctx, hipMemcpyAsync(b.gstart, a.gstart, (a.groups + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    if (a.rank) DK_HIP(ctx, hipMemcpyAsync(b.rank, a.rank, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    if (s.carry_bwt) DK_HIP(ctx, hipMemcpyAsync(b.sym, a.sym, a.count, hipMemcpyDeviceToDevice, st));
+    DK_TRY(set_list_counts(ctx, a.count, a.groups));
+    DK_TRY(classify_and_read(ctx, a.count / 2, b.gstart, b.bigidx, b.bigoff, &s.c));
+    int advanced = 0;
+    RoundReport rep;
+    DK_TRY(general_round(s, tsym, &advanced, a.period, a.next_break, &rep));
+    DK_HIP(ctx, hipMemcpyAsync(a.out_sorted_keys, b.keys, a.count * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+    DK_HIP(ctx, hipMemcpyAsync(a.out_sorted_idx, b.vals_alt, a.count * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    if (s.carry_bwt) DK_HIP(ctx, hipMemcpyAsync(a.out_sorted_sym, b.sym_alt, a.count, hipMemcpyDeviceToDevice, st));
+    if (s.c.active > 0) {
+        DK_HIP(ctx, hipMemcpyAsync(a.out_idx, b.vals, s.c.active * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        DK_HIP(ctx, hipMemcpyAsync(a.out_pos, b.pos, s.c.active * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        DK_HIP(ctx, hipMemcpyAsync(a.out_gid, b.gid, s.c.active * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        if (s.carry_bwt) DK_HIP(ctx, hipMemcpyAsync(a.out_sym, b.sym, s.c.active, hipMemcpyDeviceToDevice, st));
+    }
+    DK_HIP(ctx, hipMemcpyAsync(a.out_gstart, b.gstart, (s.c.groups + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    if (a.rank) DK_HIP(ctx, hipMemcpyAsync(a.rank, b.rank, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    DK_HIP(ctx, hipStreamSynchronize(st));
+    const size_t v[8] = {s.c.active, s.c.groups, s.c.big, s.c.big_groups, s.c.above_pl, static_cast<size_t>(advanced), ctx->stats.sa_route, static_cast<size_t>(rep.kb)};
+    for (int i = 0; i < 8; ++i) out[i] = static_cast<uint32_t>(v[i]);
+    ctx->ws_release(mark);
+    return DK_OK;
+}
+
+// dk_dbg_dev_period (abi.cpp has checked the arguments): the period kernels and the probes through the launches the phases use, without the
+// phases' size thresholds; the counters pass through the mailbox words the sort keeps them in.  The prefix probe comes first: reading the
+// alphabet clears and reads the group that holds the run and period probes' words.
+int dbg_period_device(dk_ctx *ctx, const DbgPeriod &a) {
+    const size_t n = a.n, mark = ctx->ws_mark();
+    Mail *dm = ctx->d_mail, *hm = ctx->h_mail;
+    if (a.dups_out) {
+        SaSort s{};
+        s.ctx = ctx, s.st = ctx->stream, s.d_text = a.text, s.n = n;
+        DK_TRY(dbg_alphabet(s));
+        ProbeCands cands{a.ncands, {0, 0, 0, 0}};
+        for (int c = 0; c < a.ncands; ++c) {
+            cands.sym[c] = a.cands[c];
+            if (a.cands[c] < 1 || a.cands[c] > s.spk || a.cands[c] * s.bits > 56)
+                return ctx->fail(DK_E_ARG, "period: a candidate of %d symbols of %d bits (1 .. %d, at most 56 bits)", a.cands[c], s.bits, s.spk);
+        }
+        const uint32_t table_size = prefix_probe_table(a.m, cands.count);
+        uint64_t *table = ctx->ws_alloc<uint64_t>(table_size);
+        if (!table) return DK_E_NOMEM;
+        DK_TRY(ctx->mail_fill(&dm->dups, 0));
+        DK_TRY(enqueue_prefix_probe(ctx, a.text, n, dm->code, s.bits, s.spk, a.m, a.span, cands, table, table_size, dm->dups));
+        DK_TRY(ctx->mail_fetch(&hm->dups));
+    }
+    if (a.period > 0) {
+        uint32_t *tile_first = ctx->ws_alloc<uint32_t>(div_up(n, PB_TILE));
+        if (!tile_first) return DK_E_NOMEM;
+        DK_TRY(enqueue_next_breaks(ctx, a.text, n, a.period, tile_first, a.next_break));
+    }
+    if (a.run_out) {
+        DK_TRY(ctx->mail_fill(&dm->alphabet.run_probe, 0));
+        enqueue_run_probe(ctx, a.text, n, dm->alphabet.run_probe);
+        DK_TRY(ctx->mail_fetch(&hm->alphabet.run_probe));
+    }
+    if (a.probe_out) {
+        DK_TRY(ctx->mail_fill(&dm->alphabet.period_probe, 0));
+        enqueue_period_probe(ctx, a.text, n, dm->alphabet.period_probe);
+        DK_TRY(ctx->mail_fetch(&hm->alphabet.period_probe));
+    }
+    if (a.count_out) {
+        DK_TRY(ctx->mail_fill(&dm->found_windows, 0));
+        enqueue_period_count(ctx, a.text, n, a.count_p, &dm->found_windows);
+        DK_TRY(ctx->mail_fetch(&hm->found_windows));
+    }
+    if (a.found_out) {
+        DK_TRY(ctx->mail_fill(&dm->found, 0xFF));
+        enqueue_period_search(ctx, a.text, n, a.search_pmax, dm->found);
+        DK_TRY(ctx->mail_fetch(&hm->found));
+    }
+    DK_HIP(ctx, hipGetLastError());
+    DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (a.dups_out) std::memcpy(a.dups_out, hm->dups, sizeof hm->dups);
+    if (a.run_out) std::memcpy(a.run_out, hm->alphabet.run_probe, sizeof hm->alphabet.run_probe);
+    if (a.probe_out) std::memcpy(a.probe_out, hm->alphabet.period_probe, sizeof hm->alphabet.period_probe);
+    if (a.count_out) *a.count_out = hm->found_windows;
+    if (a.found_out) std::memcpy(a.found_out, hm->found, sizeof hm->found);
     ctx->ws_release(mark);
     return DK_OK;
 }

@@ -707,6 +707,58 @@ int dk_dbg_dev_lf_refine(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uin
 int dk_dbg_dev_in_place(dk_ctx *ctx, size_t n, uint32_t h, size_t count, const uint32_t *d_idx, const uint32_t *d_pos, const uint32_t *d_gid, const uint32_t *d_gstart,
                         size_t groups, uint32_t *d_rank, uint32_t *d_sa, uint8_t *d_bwt, const uint8_t *d_sym, uint32_t *d_origin, int chain_group, uint32_t record_cap,
                         int max_rounds, int always_compact, uint32_t *d_out_idx, uint32_t *d_out_meta, uint8_t *d_out_sym, uint32_t *d_out_pos, uint32_t out[8]);
+/* One general round of the suffix sort on a list the caller built: general_round() of csrc/suffix_array.hip -- k_round_local<false> / <true>, the big
+ * list through the global sort, k_big_back, then the rerank and the classification behind it -- with the sort's own buffers for n from the
+ * workspace and the caller's groups classified by the sort's own classify_and_read.  A full context only.  tests/round_model.py is the definition
+ * of every output.
+ *   d_text, n, h   the text and the depth the members of a group are equal to (the kernels get min(h, n))
+ *   the list    `count` slots in the format rerank writes: the suffix d_idx[a], its SA position d_pos[a], d_gid[a] = the slot's group, d_gstart[g] =
+ *               the group's first slot, d_gstart[groups] = count
+ *   d_rank      n words, in and out; needed when tsym == 0, optional otherwise (null: no ranks exist yet, as in the sort's text rounds):
+ *               rank[x] = the SA position of the head of x's group (of x itself where x is final)
+ *   tsym        0: a doubling round, the secondary key is the rank h further on.  Above 0: a text round of that many symbols behind the first h; the
+ *               entry reads the alphabet as the sort does and takes raw bytes (eight of them, whatever tsym) from 17 byte values on, else coded
+ *               symbols, at most as many as 63 bits hold
+ *   period, d_next_break   period > 0 (with tsym == 8): a token round -- the members of a group that follows the period through its first h symbols
+ *               are keyed by where their stretch ends; d_next_break (n words) is the caller's: nb[i] = min{j >= i: j + period >= n or T[j] != T[j + period]}
+ *   the mode    d_sa (n words): finals are written as sa[position] = suffix.  Or d_bwt (n bytes) with d_sym (the symbol in front of every slot), d_origin,
+ *               d_out_sorted_sym and d_out_sym: finals are written as bwt[position] = symbol, *d_origin = the position of suffix 0 when it becomes
+ *               final.  The symbol is a free label wherever the big list's keys have room for it (always, below 2^40 bytes of text)
+ *   the sorted state   d_out_sorted_keys, d_out_sorted_idx (d_out_sorted_sym): `count` entries, every group sorted inside its own slot range by its
+ *               secondary key, ties in slot order; the key of a member of a big group is its group's index among the big groups << kb | the
+ *               leading kb bits of its secondary key
+ *   the next list      d_out_idx, d_out_pos, d_out_gid (d_out_sym): out[0] entries; d_out_gstart: out[1] + 1 entries
+ *   out         (host, 8 words) slots of the next list | its groups | slots in its groups above 1024 | those groups | slots in groups above 256 |
+ *               symbols the round advanced the depth by | DK_ROUTE_* bits | kb
+ * The caller's duties: the members of a group are equal in their first h symbols; d_idx distinct and below n, d_pos distinct and below n; d_gid and
+ * d_gstart as above; d_rank as above for EVERY suffix of the text; d_next_break as above; output arrays of `count` entries (gstart: count / 2 + 2).
+ * DK_E_ARG before anything is launched: a null context or pointer, both modes or neither (or part of the second), an open batch, n below 2 or above
+ * the context's capacity, count == 0 or above n, groups == 0 or above count or n / 2 + 1, h == 0, tsym below 0 or above 63, tsym == 0 without
+ * d_rank, a period below 0 or above h or 2^18, a period without d_next_break or the reverse, a period with a tsym other than 8.
+ * DK_E_NOMEM when the sort's workspace for n does not fit. */
+int dk_dbg_dev_round(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t h, size_t count, const uint32_t *d_idx, const uint32_t *d_pos, const uint32_t *d_gid,
+                     const uint32_t *d_gstart, size_t groups, uint32_t *d_rank, int tsym, int period, const uint32_t *d_next_break, uint32_t *d_sa, uint8_t *d_bwt,
+                     const uint8_t *d_sym, uint32_t *d_origin, uint64_t *d_out_sorted_keys, uint32_t *d_out_sorted_idx, uint8_t *d_out_sorted_sym, uint32_t *d_out_idx,
+                     uint32_t *d_out_pos, uint32_t *d_out_gid, uint32_t *d_out_gstart, uint8_t *d_out_sym, uint32_t out[8]);
+/* The period kernels and the text probes of the suffix sort on the caller's text, through the launches the sort's phases use but without their size
+ * thresholds.  A full context only.  d_text may have any alignment.  Every part is optional and switched on by its argument; the outputs other than
+ * d_next_break are host arrays.  tests/period_model.py is the definition of every output.
+ *   period, d_next_break   period > 0: k_period_first / _spine / _fill; d_next_break[i] (n words) = min{j >= i: j + period >= n or T[j] != T[j + period]}
+ *   run_out[2]     k_run_probe: [0] = 1 when an aligned 256-byte window of one byte value exists, [1] = 16-byte pieces of one value in whole windows
+ *   probe_out[8]   k_period_probe: [p - 1] = the 64-byte windows w with 64 w + 72 <= n that follow period p
+ *                  (a d_text that is not 16-byte / 8-byte aligned forgoes these two verdicts: all zero)
+ *   count_p, count_out     k_period_count: the 64-byte windows w with 64 w + 64 + count_p <= n that follow period count_p
+ *   search_pmax, found_out[32]   k_period_search: per sample position x = (2 b + 1) n / 64 the smallest p in [9, search_pmax] with 48 equal bytes
+ *                  at x and x + p; 0xFFFFFFFF: none, or x + search_pmax + 48 > n
+ *   m, span, cands, ncands, dups_out[4]   k_prefix_probe: m samples a span apart (jittered by a hash of the sample's number), ncands prefix
+ *                  lengths in symbols of the code the entry reads from the text as the sort does; dups_out[c] = samples minus distinct prefixes
+ *                  of cands[c] symbols ([ncands, 4): zero)
+ * DK_E_ARG before anything is launched: a null context or text, an open batch, n == 0 or above the context's capacity, a period below 0 or above
+ * 2^18, an argument of a part without its output or the reverse, search_pmax outside 9 .. 2^18, ncands outside 1 .. 4, m == 0 or above n or 2^24,
+ * span == 0, no part at all.  DK_E_ARG once the alphabet has been read: a candidate below 1 symbol, above what a key holds, or above 56 bits.
+ * DK_E_NOMEM when n / 4096 words or the probe's table (the power of two from 2 ncands m on, 8 bytes each) do not fit. */
+int dk_dbg_dev_period(dk_ctx *ctx, const uint8_t *d_text, size_t n, int period, uint32_t *d_next_break, uint32_t run_out[2], uint32_t probe_out[8], uint32_t count_p,
+                      uint32_t *count_out, uint32_t search_pmax, uint32_t *found_out, uint32_t m, uint32_t span, const int *cands, int ncands, uint32_t dups_out[4]);
 /* d_rank[d_sa[p]] = p for a permutation d_sa of 0 .. n-1 (n <= 2^31), through LDS windows.  d_marked_val (may be null): an entry of d_sa with bit
  * 31 set stands for d_sa[p] & 0x7FFFFFFF and its value is d_marked_val[p] instead of p.  The two n-u64 scratch arrays come from the context's
  * workspace: DK_E_NOMEM when they do not fit.  What it does with an input that is no permutation is not defined beyond "no store outside d_rank". */

@@ -52,6 +52,23 @@ def test_layer_entry_of_the_in_place_rounds():
     assert len(_lib.SIGNATURES[name][1]) == len(re.search(r"\bint %s\(([^;]*)\);" % name, header).group(1).split(","))
 
 
+def test_layer_entries_of_the_general_round_and_the_period_kernels():
+    """dk_dbg_dev_round (tests/test_gpu_round.py) and dk_dbg_dev_period (tests/test_gpu_period.py): the same three facts"""
+    lib = dark_amd.load_library()
+    out = (C.c_uint32 * 8)(*([7] * 8))
+    o = C.cast(out, C.c_void_p)
+    assert lib.dk_dbg_dev_round(None, None, 100, 4, 10, None, None, None, None, 5, None, 0, 0, None, None, None, None, None, None, None, None, None, None, None, None,
+                                None, o) == _lib.DK_E_ARG
+    assert lib.dk_dbg_dev_period(None, None, 100, 0, None, o, o, 3, o, 100, o, 10, 10, None, 0, o) == _lib.DK_E_ARG
+    assert list(out) == [7] * 8
+    with open(os.path.join(ROOT, "include", "dark_amd.h")) as f:
+        header = f.read()
+    for name in ("dk_dbg_dev_round", "dk_dbg_dev_period"):
+        assert re.search(r"\bint %s\(dk_ctx \*ctx," % name, header), name
+        assert name in _lib.SIGNATURES
+        assert len(_lib.SIGNATURES[name][1]) == len(re.search(r"\bint %s\(([^;]*)\);" % name, header).group(1).split(",")), name
+
+
 def test_declared_for_either_purpose():
     """a decoder context serves both: the header names the parameter any_ctx, which tests/test_gpu_decoder_ctx.py::test_refusals goes by"""
     with open(os.path.join(ROOT, "include", "dark_amd.h")) as f:

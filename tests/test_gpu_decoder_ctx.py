@@ -310,7 +310,7 @@ def refused_calls(ctx, n):
     host = np.zeros(16 * n + 4096, np.uint8)
     text = np.frombuffer(b"abracadabra" * (n // 11 + 1), np.uint8)[:n].copy()
     d_text = torch.from_numpy(text).cuda()
-    d_a, d_b, d_c, d_d = (torch.zeros(8 * n + 64, dtype=torch.uint8, device="cuda") for _ in range(4))
+    d_a, d_b, d_c, d_d, d_e = (torch.zeros(8 * n + 64, dtype=torch.uint8, device="cuda") for _ in range(5))
     p = lambda x, at=0: C.c_void_p(_ptr(x).value + at)  # noqa: E731
     sz, u32 = C.c_size_t(0), C.c_uint32(0)
     one = (C.c_size_t * 1)(n)
@@ -352,6 +352,9 @@ def refused_calls(ctx, n):
         ("dk_dbg_dev_lf_refine", lambda: lib.dk_dbg_dev_lf_refine(h, p(d_text), n, p(d_a), p(d_a, 4 * n), p(d_b), p(d_b, 4 * n), n // 2, 4, 0, p(d_c), p(d_d), p(host))),
         ("dk_dbg_dev_in_place", lambda: lib.dk_dbg_dev_in_place(h, n, 4, n // 2, p(d_a), p(d_a, 4 * n), p(d_b), p(d_b, 4 * n), n // 4, p(d_c), p(d_c, 4 * n), None, None, None,
                                                                 -1, 0, -1, 0, p(d_d), p(d_d, 2 * n), None, p(d_d, 4 * n), p(host))),
+        ("dk_dbg_dev_round", lambda: lib.dk_dbg_dev_round(h, p(d_text), n, 4, n // 2, p(d_a), p(d_a, 4 * n), p(d_b), p(d_b, 4 * n), n // 4, p(d_c), 0, 0, None, p(d_c, 4 * n),
+                                                          None, None, None, p(d_d), p(d_d, 4 * n), None, p(d_e), p(d_e, 2 * n), p(d_e, 4 * n), p(d_e, 6 * n), None, p(host))),
+        ("dk_dbg_dev_period", lambda: lib.dk_dbg_dev_period(h, p(d_text), n, 1, p(d_a), p(host), p(host, 64), 3, p(host, 128), 0, None, 0, 0, None, 0, None)),
         ("dk_dbg_dev_inverse_permutation", lambda: lib.dk_dbg_dev_inverse_permutation(h, p(d_a), n, p(d_b), None)),
     ], batch
 

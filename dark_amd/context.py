@@ -1070,6 +1070,35 @@ class Context:
         return dict(next_break=None if d_nb is None else self._to_host(d_nb, np.uint32), run=run_out, probe=probe_out,
                     count=None if count_out is None else int(count_out[0]), found=found_out, dups=dups_out)
 
+    def dbg_dev_initial_sort(self, text, code, bits, spk, inv=None, narrow=False, text_offset=0, fill=0xC3, pad=64):
+        """dk_dbg_dev_initial_sort: the suffix sort's initial sort by itself on a text `text_offset` bytes behind an aligned address, under the
+        caller's code table (256 codes below 2^bits).  inv (256 bytes): the carry -- L and the origin word are written.  narrow: 32-bit keys and
+        the 256 bucket starts.  Every device output holds `fill` bytes before the call and has `pad` guard entries in front and behind (the origin
+        word: one each side).  -> dict of the whole arrays after the call, guards included: keys (uint64, or uint32 when narrow), sa, bwt and
+        origin (3 words; both None without the carry), bucket_starts (None unless narrow), and route (DK_ROUTE_* bits), passes, sorted_elements,
+        out (the four words)"""
+        import torch
+        n, kb, carry = len(text), 4 if narrow else 8, inv is not None
+        keep, d_text = self._text_at(text, text_offset)
+        code = np.ascontiguousarray(code, dtype=np.uint8)
+        inv = None if inv is None else np.ascontiguousarray(inv, dtype=np.uint8)
+        if len(code) != 256 or (carry and len(inv) != 256):
+            raise DarkError(_lib.DK_E_ARG, "code and inv are tables of 256 bytes")
+        filled = lambda nbytes: torch.from_numpy(np.full(nbytes, fill, np.uint8)).to("cuda:%d" % self.device)  # noqa: E731
+        d_keys, d_sa = filled(kb * (n + 2 * pad)), filled(4 * (n + 2 * pad))
+        d_bwt, d_origin = (filled(n + 2 * pad), filled(12)) if carry else (None, None)
+        starts = np.full(256, 0xC3C3C3C3, np.uint32) if narrow else None
+        out = np.full(4, 0xC3C3C3C3, np.uint32)
+        at = lambda t, nbytes: None if t is None else C.c_void_p(t.data_ptr() + nbytes)  # noqa: E731
+        _inputs_ready(keep)
+        self._ck(self._lib.dk_dbg_dev_initial_sort(self._h, d_text, n, _ptr(code), int(bits), int(spk), None if inv is None else _ptr(inv), int(bool(narrow)),
+                                                   at(d_keys, kb * pad), at(d_sa, 4 * pad), at(d_bwt, pad), at(d_origin, 4), None if starts is None else _ptr(starts),
+                                                   _ptr(out)))
+        del keep
+        return dict(keys=self._to_host(d_keys, np.uint32 if narrow else np.uint64), sa=self._to_host(d_sa, np.uint32),
+                    bwt=None if d_bwt is None else d_bwt.cpu().numpy(), origin=None if d_origin is None else self._to_host(d_origin, np.uint32),
+                    bucket_starts=starts, route=int(out[0]), passes=int(out[1]), sorted_elements=int(out[2]), out=out)
+
     def dbg_dev_inverse_permutation(self, sa, marked_val=None):
         """dk_dbg_dev_inverse_permutation: rank[sa[p] & 0x7FFFFFFF] = marked_val[p] if sa[p] has bit 31 set (and marked_val is given) else p"""
         d_sa = self._to_dev(sa, np.uint32)

@@ -1604,6 +1604,25 @@ int dk_dbg_dev_period(dk_ctx *ctx, const uint8_t *d_text, size_t n, int period, 
     const DbgPeriod a{d_text, n, period, d_next_break, run_out, probe_out, count_p, count_out, search_pmax, found_out, m, span, cands, ncands, dups_out};
     return dbg_period_device(ctx, a);
 }
+int dk_dbg_dev_initial_sort(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uint8_t code[256], int bits, int spk, const uint8_t inv[256], int narrow, void *d_keys_out,
+                            uint32_t *d_sa, uint8_t *d_bwt, uint32_t *d_origin, uint32_t bucket_starts_out[256], uint32_t out[4]) {
+    DK_TRY(begin_call(ctx, "dk_dbg_dev_initial_sort"));
+    ScopedCall sc(ctx);
+    if (!d_text || !code || !d_keys_out || !d_sa || !out) return ctx->fail(DK_E_ARG, "initial_sort: null pointer");
+    const bool with_prev = inv && d_bwt && d_origin;
+    if (!with_prev && (inv || d_bwt || d_origin)) return ctx->fail(DK_E_ARG, "initial_sort: inv, d_bwt and d_origin are the carry: all three or none");
+    if (n == 0 || n > ctx->max_n || n > 0x7FFFFFFEull) return ctx->fail(DK_E_ARG, "initial_sort: text of %zu bytes (1 .. the context capacity %zu)", n, ctx->max_n);
+    if (bits < 1 || bits > 8) return ctx->fail(DK_E_ARG, "initial_sort: codes of %d bits (1 .. 8)", bits);
+    if (spk < 1 || spk > 64 || bits * spk + (with_prev ? 8 : 0) > 64)
+        return ctx->fail(DK_E_ARG, "initial_sort: %d symbols of %d bits%s (at least one, and a key holds 64 bits)", spk, bits, with_prev ? " and the carried byte" : "");
+    for (int c = 0; c < 256; ++c)
+        if (code[c] >> bits) return ctx->fail(DK_E_ARG, "initial_sort: code[%d] = %d has more than %d bits", c, code[c], bits);
+    if (narrow != 0 && narrow != 1) return ctx->fail(DK_E_ARG, "initial_sort: narrow is 0 or 1 (got %d)", narrow);
+    if (narrow && bits * spk > 40) return ctx->fail(DK_E_ARG, "initial_sort: narrow keys behind a sort of %d bits (at most 40: five passes)", bits * spk);
+    if ((narrow != 0) != (bucket_starts_out != nullptr)) return ctx->fail(DK_E_ARG, "initial_sort: bucket_starts_out goes with narrow keys, and only with them");
+    const DbgInitialSort a{d_text, n, code, bits, spk, with_prev ? inv : nullptr, narrow, d_keys_out, d_sa, d_bwt, d_origin, bucket_starts_out};
+    return dbg_initial_sort_device(ctx, a, out);
+}
 int dk_dbg_dev_inverse_permutation(dk_ctx *ctx, const uint32_t *d_sa, size_t n, uint32_t *d_rank, const uint32_t *d_marked_val) {
     DK_TRY(begin_call(ctx, "dk_dbg_dev_inverse_permutation"));
     ScopedCall sc(ctx);

@@ -263,6 +263,15 @@ struct DbgPeriod {
     uint32_t m, span; const int *cands; int ncands; uint32_t *dups_out;
 };
 int dbg_period_device(dk_ctx *ctx, const DbgPeriod &args);
+// dk_dbg_dev_initial_sort's arguments under the names of the header: one sort_pairs() with the TextKeys and the SortFinalOut that initial_sort()
+// builds, the code tables the caller's.  inv, bwt and origin: all three or none (their presence is with_prev).  keys_out: n words of 8 bytes, of 4
+// when narrow.  bucket_starts_out (host, 256 words): narrow only.  out: sa_route bits the sort set | sort_passes | sorted_elements (low word) | 0.
+// Synchronises.
+struct DbgInitialSort {
+    const uint8_t *text; size_t n; const uint8_t *code; int bits, spk; const uint8_t *inv; int narrow;
+    void *keys_out; uint32_t *sa; uint8_t *bwt; uint32_t *origin; uint32_t *bucket_starts_out;
+};
+int dbg_initial_sort_device(dk_ctx *ctx, const DbgInitialSort &args, uint32_t out[4]);
 // bwt.hip
 int bwt_gather_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_sa, size_t n, uint8_t *d_bwt, uint32_t *origin);
 int bwt_inverse_device(dk_ctx *ctx, const uint8_t *d_bwt, size_t n, uint32_t origin, uint8_t *d_out);

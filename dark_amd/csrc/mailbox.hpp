@@ -50,7 +50,7 @@ struct Mail {
     uint32_t found[PS_SAMPLES];   // k_period_search (filled with 0xFF before): the period every sample position found, 0xFFFFFFFF: none
     uint32_t found_windows;       // k_period_count (cleared before): 64-byte windows that follow the period most samples voted for
     uint32_t narrow_starts[256];  // device only: bucket starts of a narrow-key sort (SortFinalOut::bucket_starts), written by the sort's last pass,
-                                  // read by the first rerank's reduce kernel
+                                  // read by the first rerank's reduce kernel (the host twin: only dk_dbg_dev_initial_sort fetches them)
     uint32_t chain_cnt[2];        // pair chains: k_chain_extract [0] records, [1] first reservation that did not fit (host: 0 / 0xFF fills before);
                                   // then k_plateau_scan [0]: slots still live behind the chains
     uint32_t live_ring[LIVE_RING];  // in-place rounds: round r clears and counts its live slots at [r % LIVE_RING] (k_plateau_sort) and the round behind

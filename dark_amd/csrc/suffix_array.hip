@@ -1887,18 +1887,27 @@ int choose_prefix(SaSort &s) {
 }
 
 // 3. initial sort; its first pass builds the keys from the text (no key array is ever written unsorted).  Expects choose_prefix's verdicts; leaves
-//    the sorted keys in b.keys, every suffix at its slot of the suffix array and (carry_bwt) its symbol in L
-int initial_sort(SaSort &s) {
-    TextKeys tk;
-    tk.t = s.d_text; tk.n = s.n; tk.code = s.ctx->d_mail->code; tk.bits = s.bits; tk.spk = s.spk_sort; tk.with_prev = s.carry_bwt ? 1 : 0;
+//    the sorted keys in b.keys, every suffix at its slot of the suffix array and (carry_bwt) its symbol in L.
+//    plan_initial_sort: what the sort is handed, from plain values (the phase and dk_dbg_dev_initial_sort both build it here) -- the text keys of `spk`
+//    symbols of `bits` bits, the code tables and the bucket starts where the sort keeps them (the mailbox), the sorted bits [begin_bit, end_bit)
+struct InitialSortPlan { TextKeys tk; SortFinalOut fin; int begin_bit, end_bit; };
+InitialSortPlan plan_initial_sort(dk_ctx *ctx, const uint8_t *d_text, size_t n, int bits, int spk, bool with_prev, bool narrow, uint32_t *d_sa, uint8_t *d_bwt,
+                                  uint32_t *d_origin) {
+    InitialSortPlan p;
+    p.tk.t = d_text; p.tk.n = n; p.tk.code = ctx->d_mail->code; p.tk.bits = bits; p.tk.spk = spk; p.tk.with_prev = with_prev ? 1 : 0;
+    p.begin_bit = with_prev ? 8 : 0;
+    p.end_bit = bits * spk + p.begin_bit;
     // the last pass leaves every suffix at its slot of the suffix array itself (and the symbol in front of it in L): what the first
     // rerank finds final is final where it stands -- it stores nothing for it, and a tile without a survivor costs it nothing
-    SortFinalOut fin;
-    fin.vals = s.d_sa;
-    if (s.carry_bwt) { fin.bwt = s.d_bwt; fin.inv_code = s.ctx->d_mail->inv; fin.origin = s.d_origin; }
+    p.fin.vals = d_sa;
+    if (with_prev) { p.fin.bwt = d_bwt; p.fin.inv_code = ctx->d_mail->inv; p.fin.origin = d_origin; }
     // up to 40 sorted bits (short prefixes: random bytes, small alphabets): the last pass leaves 32-bit keys for the first rerank
-    if (s.narrow_keys) { fin.narrow_shift = s.key_shift; fin.bucket_starts = s.ctx->d_mail->narrow_starts; }
-    DK_TRY(sort_pairs(s.ctx, s.b.keys, s.b.keys_alt, s.b.vals, s.b.vals_alt, s.n, s.key_shift, s.bits * s.spk_sort + s.key_shift, &tk, &fin));
+    if (narrow) { p.fin.narrow_shift = p.begin_bit; p.fin.bucket_starts = ctx->d_mail->narrow_starts; }
+    return p;
+}
+int initial_sort(SaSort &s) {
+    const InitialSortPlan p = plan_initial_sort(s.ctx, s.d_text, s.n, s.bits, s.spk_sort, s.carry_bwt, s.narrow_keys, s.d_sa, s.d_bwt, s.d_origin);
+    DK_TRY(sort_pairs(s.ctx, s.b.keys, s.b.keys_alt, s.b.vals, s.b.vals_alt, s.n, p.begin_bit, p.end_bit, &p.tk, &p.fin));
     if (s.short_prefix) s.route() |= DK_ROUTE_SHORT_PREFIX;
     if (s.narrow_keys) s.route() |= DK_ROUTE_NARROW_KEYS;
     return DK_OK;
@@ -2634,6 +2643,37 @@ int dbg_period_device(dk_ctx *ctx, const DbgPeriod &a) {
     if (a.probe_out) std::memcpy(a.probe_out, hm->alphabet.period_probe, sizeof hm->alphabet.period_probe);
     if (a.count_out) *a.count_out = hm->found_windows;
     if (a.found_out) std::memcpy(a.found_out, hm->found, sizeof hm->found);
+    ctx->ws_release(mark);
+    return DK_OK;
+}
+
+// dk_dbg_dev_initial_sort (abi.cpp has checked the arguments): ONE sort_pairs() with the text keys and the final destinations that initial_sort()
+// builds (plan_initial_sort), on the caller's text and the caller's code tables, which go where the sort keeps them: d_mail->code, d_mail->inv; the
+// bucket starts land in d_mail->narrow_starts and come back through the host twin.  The four sort buffers are the workspace's; the sorted keys are
+// copied from whichever of the pair sort_pairs hands back.  out: sa_route bits the sort set | sort_passes | sorted_elements (low word) | 0
+int dbg_initial_sort_device(dk_ctx *ctx, const DbgInitialSort &a, uint32_t out[4]) {
+    const size_t n = a.n, mark = ctx->ws_mark();
+    hipStream_t st = ctx->stream;
+    Mail *dm = ctx->d_mail, *hm = ctx->h_mail;
+    const bool with_prev = a.inv != nullptr, narrow = a.narrow != 0;
+    ctx->stats.sa_route = 0;
+    ctx->stats.sort_passes = 0;
+    ctx->stats.sorted_elements = 0;
+    uint64_t *keys = ctx->ws_alloc<uint64_t>(n), *keys_alt = keys ? ctx->ws_alloc<uint64_t>(n) : nullptr;
+    uint32_t *vals = keys_alt ? ctx->ws_alloc<uint32_t>(n) : nullptr, *vals_alt = vals ? ctx->ws_alloc<uint32_t>(n) : nullptr;
+    if (!vals_alt) return DK_E_NOMEM;
+    DK_HIP(ctx, hipMemcpyAsync(dm->code, a.code, sizeof dm->code, hipMemcpyHostToDevice, st));
+    if (with_prev) {
+        std::memcpy(hm->inv, a.inv, sizeof hm->inv);
+        DK_HIP(ctx, hipMemcpyAsync(dm->inv, hm->inv, sizeof hm->inv, hipMemcpyHostToDevice, st));
+    }
+    const InitialSortPlan p = plan_initial_sort(ctx, a.text, n, a.bits, a.spk, with_prev, narrow, a.sa, a.bwt, a.origin);
+    DK_TRY(sort_pairs(ctx, keys, keys_alt, vals, vals_alt, n, p.begin_bit, p.end_bit, &p.tk, &p.fin));
+    DK_HIP(ctx, hipMemcpyAsync(a.keys_out, keys, n * (narrow ? sizeof(uint32_t) : sizeof(uint64_t)), hipMemcpyDeviceToDevice, st));
+    if (narrow) DK_TRY(ctx->mail_fetch(&hm->narrow_starts));
+    DK_HIP(ctx, hipStreamSynchronize(st));
+    if (narrow) std::memcpy(a.bucket_starts_out, hm->narrow_starts, sizeof hm->narrow_starts);
+    out[0] = ctx->stats.sa_route, out[1] = static_cast<uint32_t>(ctx->stats.sort_passes), out[2] = static_cast<uint32_t>(ctx->stats.sorted_elements), out[3] = 0;
     ctx->ws_release(mark);
     return DK_OK;
 }

@@ -759,6 +759,29 @@ int dk_dbg_dev_round(dk_ctx *ctx, const uint8_t *d_text, size_t n, uint32_t h, s
  * DK_E_NOMEM when n / 4096 words or the probe's table (the power of two from 2 ncands m on, 8 bytes each) do not fit. */
 int dk_dbg_dev_period(dk_ctx *ctx, const uint8_t *d_text, size_t n, int period, uint32_t *d_next_break, uint32_t run_out[2], uint32_t probe_out[8], uint32_t count_p,
                       uint32_t *count_out, uint32_t search_pmax, uint32_t *found_out, uint32_t m, uint32_t span, const int *cands, int ncands, uint32_t dups_out[4]);
+/* The initial sort of the suffix sort by itself: ONE sort_pairs() of csrc/radix_sort.hip with the text keys and the final destinations that
+ * initial_sort() of csrc/suffix_array.hip hands it (both build them in one function) -- k_radix_hist<HS_TEXT>, the text pass of k_radix_scatter in its
+ * plain and its packed form, the passes behind it and the last pass's stores to their final homes.  A full context only.  The alphabet is the
+ * CALLER'S, not the one the sort reads from the text: no kernel of this stage derives one table from the other, so `code` may be non-injective
+ * and `inv` is then any table.  tests/initial_sort_model.py is the definition of every output.
+ *   d_text, n      the text; any alignment (only a 16-byte aligned text lets a tile take the 16-byte loads)
+ *   code[256], bits, spk   (host) the code of every byte value, below 2^bits each; the window of position i = the codes of T[i .. i + spk) packed
+ *                  big-endian, `bits` each, zero for positions from n on.  The tables go where the sort keeps them, the stages' mailbox
+ *   inv[256], d_bwt, d_origin   the carry: all three or none.  With it the key of position i is window << 8 | code[T[i - 1]] (T[n - 1] for i = 0),
+ *                  d_bwt[slot] = inv[key & 0xFF] (n bytes) and *d_origin = the slot of position 0; without it the key is the window
+ *   narrow         1 (sorts of at most 40 bits): the last pass leaves 32-bit words, the window's low 32 bits; 0: the 64-bit keys
+ *   the order      stable by window: an LSD sort on exactly the window's bits, ceil(bits spk / 8) passes, whose input stands in position order
+ *   d_keys_out     n sorted keys, 8 bytes each or 4 when narrow, copied from whichever buffer of its pair the sort hands back
+ *   d_sa           n words, written by the sort's last pass itself: the position at every slot
+ *   bucket_starts_out[256]   (host; narrow only, null otherwise) [d] = the pairs whose last-pass digit -- the window's top bits, what the passes
+ *                  before the last leave of it -- is below d: where two neighbours may differ in the bits a narrow word has lost
+ *   out            (host, 4 words) the DK_ROUTE_* bits the sort set (DK_ROUTE_PACKED_PAIRS or none) | passes | pairs sorted over all passes, low word | 0
+ * The four sort buffers (24 bytes per position) and the sort's tables come from the workspace, which is marked and released.
+ * DK_E_ARG before anything is launched: a null context or array, an open batch, n == 0 or above the context's capacity or 2^31 - 2, bits outside
+ * 1 .. 8, spk below 1 or bits spk + 8 (with the carry) above 64, a code[c] of more than `bits` bits (the packed word cannot hold it), half a carry,
+ * narrow outside 0 / 1 or with more than 40 sorted bits, bucket_starts_out without narrow or the reverse.  DK_E_NOMEM when the workspace does not fit. */
+int dk_dbg_dev_initial_sort(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uint8_t code[256], int bits, int spk, const uint8_t inv[256], int narrow,
+                            void *d_keys_out, uint32_t *d_sa, uint8_t *d_bwt, uint32_t *d_origin, uint32_t bucket_starts_out[256], uint32_t out[4]);
 /* d_rank[d_sa[p]] = p for a permutation d_sa of 0 .. n-1 (n <= 2^31), through LDS windows.  d_marked_val (may be null): an entry of d_sa with bit
  * 31 set stands for d_sa[p] & 0x7FFFFFFF and its value is d_marked_val[p] instead of p.  The two n-u64 scratch arrays come from the context's
  * workspace: DK_E_NOMEM when they do not fit.  What it does with an input that is no permutation is not defined beyond "no store outside d_rank". */

@@ -69,6 +69,22 @@ def test_layer_entries_of_the_general_round_and_the_period_kernels():
         assert len(_lib.SIGNATURES[name][1]) == len(re.search(r"\bint %s\(([^;]*)\);" % name, header).group(1).split(",")), name
 
 
+def test_layer_entry_of_the_initial_sort():
+    """dk_dbg_dev_initial_sort (tests/test_gpu_initial_sort.py): the same three facts"""
+    lib = dark_amd.load_library()
+    out = (C.c_uint32 * 4)(*([7] * 4))
+    starts = (C.c_uint32 * 256)(*([7] * 256))
+    code = (C.c_uint8 * 256)()
+    assert lib.dk_dbg_dev_initial_sort(None, None, 100, C.cast(code, C.c_void_p), 2, 8, None, 1, None, None, None, None, C.cast(starts, C.c_void_p),
+                                       C.cast(out, C.c_void_p)) == _lib.DK_E_ARG
+    assert list(out) == [7] * 4 and list(starts) == [7] * 256
+    with open(os.path.join(ROOT, "include", "dark_amd.h")) as f:
+        header = f.read()
+    name = "dk_dbg_dev_initial_sort"
+    assert re.search(r"\bint %s\(dk_ctx \*ctx," % name, header)
+    assert len(_lib.SIGNATURES[name][1]) == len(re.search(r"\bint %s\(([^;]*)\);" % name, header).group(1).split(","))
+
+
 def test_declared_for_either_purpose():
     """a decoder context serves both: the header names the parameter any_ctx, which tests/test_gpu_decoder_ctx.py::test_refusals goes by"""
     with open(os.path.join(ROOT, "include", "dark_amd.h")) as f:

@@ -355,6 +355,7 @@ def refused_calls(ctx, n):
         ("dk_dbg_dev_round", lambda: lib.dk_dbg_dev_round(h, p(d_text), n, 4, n // 2, p(d_a), p(d_a, 4 * n), p(d_b), p(d_b, 4 * n), n // 4, p(d_c), 0, 0, None, p(d_c, 4 * n),
                                                           None, None, None, p(d_d), p(d_d, 4 * n), None, p(d_e), p(d_e, 2 * n), p(d_e, 4 * n), p(d_e, 6 * n), None, p(host))),
         ("dk_dbg_dev_period", lambda: lib.dk_dbg_dev_period(h, p(d_text), n, 1, p(d_a), p(host), p(host, 64), 3, p(host, 128), 0, None, 0, 0, None, 0, None)),
+        ("dk_dbg_dev_initial_sort", lambda: lib.dk_dbg_dev_initial_sort(h, p(d_text), n, p(init), 8, 7, None, 0, p(d_a), p(d_b), None, None, None, p(host))),
         ("dk_dbg_dev_inverse_permutation", lambda: lib.dk_dbg_dev_inverse_permutation(h, p(d_a), n, p(d_b), None)),
     ], batch
 

@@ -137,6 +137,20 @@ bool DarkModel::encode_mantissa_modelled(uint32_t dist, E &e) {  // dark.rs:216-
     return true;
 }
 template <class E>
+bool DarkModel::encode_mantissa_first_two(uint32_t dist, E &e) {  // encode_mantissa_modelled's bits 1 and 2 (bit 3: third_bit_zero, on another thread's model)
+    if (dist >= 0x7FFFFFFFu) return false;
+    const uint32_t v = dist + 1;
+    const unsigned log = bit_length(v);
+    BinFreq *mc = mantissa_[log];
+    const unsigned modelled = log > 2 ? 2 : log - 1;
+    for (unsigned i = 1; i <= modelled; ++i) {
+        const bool bit = (v >> (log - i - 1)) & 1u;
+        if (!encode_bit_p(e, mc[i - 1].zero, bit)) return false;
+        mc[i - 1].learn<8>(bit);
+    }
+    return true;
+}
+template <class E>
 bool DarkModel::encode_mantissa_flat(uint32_t dist, E &e) {  // dark.rs:225-227: the rest through the never-updated 4th model
     const uint32_t v = dist + 1;
     const unsigned log = bit_length(v);
@@ -1194,6 +1208,25 @@ struct DarkMantissaSide {
         return true;
     }
 };
+struct DarkMantissaTwoSide {  // six stages: the first two modelled bits only (the third one's cells live with the prepare stage)
+    DarkModel &m;
+    bool encode(uint32_t dist, uint8_t, USink &e) { return m.encode_mantissa_first_two(dist, e); }
+    bool bulk(const uint32_t *dist, const uint8_t *, size_t count, USink &e) {
+        UEvent *o_end;
+        UCursor c{e.cursor(&o_end)};
+        for (size_t k = 0; k < count; ++k) {
+            if (__builtin_expect(c.o + 2 <= o_end, 1)) {
+                if (!m.encode_mantissa_first_two(dist[k], c)) { e.done(c.o); return false; }
+            } else {
+                e.done(c.o);
+                if (!m.encode_mantissa_first_two(dist[k], e)) return false;
+                c.o = e.cursor(&o_end);
+            }
+        }
+        e.done(c.o);
+        return true;
+    }
+};
 struct DarkMergeSide {  // the order of dark.rs:180-232: table decision, unary extension, mantissa bits
     UReader &exponent;
     UReader &mantissa;
@@ -1330,7 +1363,41 @@ struct DarkGlobalHalfSide {
         return true;
     }
 };
-struct DarkMergeSide5 {
+struct DarkGlobalHalfThirdSide {  // six stages: the global half, and behind it the third modelled mantissa bit (the thread with the most time to spare)
+    DarkModel &m;
+    template <class E> inline bool both(uint32_t dist, uint8_t symbol, E &e) {
+        if (!m.encode_exponent_global_half(dist, symbol, e)) return false;
+        const uint32_t v = dist + 1;
+        const unsigned log = bit_length(v);
+        if (log >= 4) {
+            const bool bit = (v >> (log - 4)) & 1u;
+            BinFreq *const cell = m.third_bit_cell(log);
+            e.put_bit12(cell->zero, bit);
+            cell->learn<8>(bit);
+        }
+        return true;
+    }
+    bool encode(uint32_t dist, uint8_t symbol, USink &e) { return both(dist, symbol, e); }
+    bool bulk(const uint32_t *dist, const uint8_t *sym, size_t count, USink &e) {  // at most 1 + 25 half decisions and one whole one per distance
+        UEvent *o_end;
+        UCursor c{e.cursor(&o_end)};
+        for (size_t k = 0; k < count; ++k) {
+            if (__builtin_expect(c.o + 32 <= o_end, 1)) {
+                if (!both(dist[k], sym[k], c)) { e.done(c.o); return false; }
+            } else {
+                e.done(c.o);
+                if (!both(dist[k], sym[k], e)) return false;
+                c.o = e.cursor(&o_end);
+            }
+        }
+        e.done(c.o);
+        return true;
+    }
+};
+// kThirdFromB (six stages): ring M carries the first two modelled mantissa bits only; the third one's decision (distances with four or more
+// significant bits) comes ready-made at the end of the distance's events in ring B (DarkGlobalHalfThirdSide).
+template <bool kThirdFromB>
+struct DarkMergeSide5T {
     UReader &half_a, &half_b, &mantissa;
     const uint64_t *inv;
     static inline UEvent mixed(const UEvent &a, const UEvent &b, const uint64_t *inv) {  // table::SumProxy::new(1, a, 2, b, 0) of the two halves
@@ -1354,7 +1421,12 @@ struct DarkMergeSide5 {
             if (!a || !b) return false;
             if (!e.raw(mixed_bit(*a, *b, i + kMaxLogCode < log))) return false;
         }
-        if (!DarkMergeSide::move(mantissa, e, DarkModel::modelled_mantissa_bits(dist))) return false;
+        const unsigned nm = DarkModel::modelled_mantissa_bits(dist);
+        if (!DarkMergeSide::move(mantissa, e, kThirdFromB && nm == 3 ? 2 : nm)) return false;
+        if (kThirdFromB && nm == 3) {
+            b = half_b.next();
+            if (!b || !e.raw(*b)) return false;
+        }
         if (log > 4) DarkMergeSide::flat_tail(e, dist + 1, log);
         return true;
     }
@@ -1387,7 +1459,7 @@ struct DarkMergeSide5 {
         const UEvent *const flat = flat_table();
         const uint32_t *dp = dist, *const dist_end = dist + count;
         while (dp != dist_end) {
-            std::ptrdiff_t run = std::min<std::ptrdiff_t>(std::min(pa_end - pa, pb_end - pb), dist_end - dp);
+            std::ptrdiff_t run = std::min<std::ptrdiff_t>(std::min(pa_end - pa, (pb_end - pb) / (kThirdFromB ? 2 : 1)), dist_end - dp);  // (ring B: a half and, at most, a third bit)
             run = std::min(run, pm_end - pm >= 4 ? (pm_end - pm - 4) / 3 + 1 : 0);  // the last of them still reads four events at pm
             run = std::min(run, o_end - o >= 12 ? (o_end - o - 12) / 7 + 1 : 0);    // ... and still touches twelve places at o
             for (const uint32_t *const run_end = dp + run; dp != run_end; ++dp) {
@@ -1397,22 +1469,36 @@ struct DarkMergeSide5 {
                 const unsigned nm = log > 3 ? 3 : log - 1, left = log > 4 ? log - 4 : 0;
                 *o++ = mixed(*pa++, *pb++, inv);
                 std::memcpy(static_cast<void *>(o), pm, 4 * sizeof(UEvent));
+                if (kThirdFromB) {  // (where no third bit is due this copies ring B's next event, which the flat copy overwrites)
+                    const unsigned third = nm == 3 ? 1u : 0u, from_ring = nm - third;
+                    o[from_ring] = *pb;
+                    pb += third;
+                    pm += from_ring;
+                } else {
+                    pm += nm;
+                }
                 o += nm;
-                pm += nm;
                 std::memcpy(static_cast<void *>(o), flat + 4 * (((v << 4) >> left) & 15u), 4 * sizeof(UEvent));  // bits left - 1 .. 0 of v on top of a nibble
                 o += left;
             }
             if (dp == dist_end) break;
             const uint32_t v = *dp + 1;
             const unsigned log = bit_length(v);  // (*dp = 2^32 - 1 gives 0 and goes the slow way, which refuses it)
-            if (log - 1u <= 15u && pa + 10 <= pa_end && pb + 10 <= pb_end && pm + 4 <= pm_end && o + 28 <= o_end) {
+            if (log - 1u <= 15u && pa + 10 <= pa_end && pb + 10 + (kThirdFromB ? 2 : 0) <= pb_end && pm + 4 <= pm_end && o + 28 <= o_end) {
                 // log 1 .. 16: log - 7 mixed bits of the unary extension behind the mixed decision (at most nine), at most twelve flat bits
                 const unsigned nm = log > 3 ? 3 : log - 1, left = log > 4 ? log - 4 : 0;
                 *o++ = mixed(*pa++, *pb++, inv);
                 for (unsigned i = kMaxLogCode; i <= log; ++i) *o++ = mixed_bit(*pa++, *pb++, i < log);
                 std::memcpy(static_cast<void *>(o), pm, 4 * sizeof(UEvent));
+                if (kThirdFromB) {
+                    const unsigned third = nm == 3 ? 1u : 0u, from_ring = nm - third;
+                    o[from_ring] = *pb;
+                    pb += third;
+                    pm += from_ring;
+                } else {
+                    pm += nm;
+                }
                 o += nm;
-                pm += nm;
                 std::memcpy(static_cast<void *>(o), flat + 4 * (((v << 4) >> left) & 15u), 4 * sizeof(UEvent));
                 if (left > 4) {  // (what is written beyond `left` is overwritten by the next events)
                     std::memcpy(static_cast<void *>(o + 4), flat + 4 * (((v << 8) >> left) & 15u), 4 * sizeof(UEvent));
@@ -1440,6 +1526,7 @@ struct DarkMergeSide5 {
         return true;
     }
 };
+using DarkMergeSide5 = DarkMergeSide5T<false>;
 
 // One batch of uniform events on the coder's fast path: the caller has made sure that 4 * count + 12 bytes are writable at *pp.
 // The coder's state is (low, span = hi - low), and what travels from one decision to the next is the QUOTIENT r = span / total.  With
@@ -1560,6 +1647,263 @@ int code_uniform(URing &ring, uint8_t *out, size_t cap, size_t *out_len) {
     *out_len = len;
     return err;
 }
+
+// ------------------------------------------------------------------------------------------------------------------
+// Prepared events (six stages): a stage between the merger and the coder forms everything the coder's loop used to derive from event data
+// alone -- M = (to - from) * inv_next as M_lo, M_hi and M_hi << 8 -- so that the loop only loads its factors.  M < 2^78 (to - from < 2^15,
+// inv_next <= 2^63), so M_hi < 2^14, and from < 2^15, to <= 2^15: one 64-bit word beside M_lo holds them all,
+//     byte 0-7 M_lo | 8-9 from | 10 zero | 11-12 M_hi | 13 zero | 14-15 to,
+// laid out so that every factor is one zero-extending load and no shift or mask: from = u16 at 8, M_hi << 8 = u32 at 10, M_hi = u16 at 11,
+// to = u16 at 14.  The reciprocal itself, which only the rare path and a batch's first decision need, travels in a cold array of the
+// same ring slot.  The last event of a batch carries M = 0: nobody's quotient to prepare, and no batch ever reads another's slot.
+// ------------------------------------------------------------------------------------------------------------------
+struct PEvent {
+    uint64_t m_lo, w;
+    static inline PEvent pack(uint32_t from, uint32_t to, uint64_t m_lo, uint64_t m_hi) { return PEvent{m_lo, from | (m_hi << 24) | (static_cast<uint64_t>(to) << 48)}; }
+#if defined(__BYTE_ORDER__) && __BYTE_ORDER__ == __ORDER_LITTLE_ENDIAN__
+    inline uint32_t from() const { return load16(8); }
+    inline uint32_t to() const { return load16(14); }
+    inline uint32_t m_hi() const { return load16(11); }
+    inline uint32_t m_hi8() const { uint32_t v; std::memcpy(&v, reinterpret_cast<const uint8_t *>(this) + 10, 4); return v; }
+#else
+    inline uint32_t from() const { return static_cast<uint32_t>(w & 0xFFFFu); }
+    inline uint32_t to() const { return static_cast<uint32_t>(w >> 48); }
+    inline uint32_t m_hi() const { return static_cast<uint32_t>((w >> 24) & 0xFFFFu); }
+    inline uint32_t m_hi8() const { return static_cast<uint32_t>((w >> 16) & 0xFFFFFFFFu); }
+#endif
+private:
+    inline uint32_t load16(size_t at) const { uint16_t v; std::memcpy(&v, reinterpret_cast<const uint8_t *>(this) + at, 2); return v; }
+};
+static_assert(sizeof(PEvent) == 16, "prepared event is 16 bytes");
+
+// One batch of uniform events as prepared events plus their reciprocals (the prepare stage's whole work; EV: PEvent, or a layout under
+// measurement in tools/coder_loop_bench.cpp).  false: an event outside the layout's bounds -- it is written as an empty interval, which the coder refuses.
+template <class EV>
+inline bool prepare_batch(const UEvent *ev, uint32_t count, EV *out, uint64_t *inv_out) {
+    bool ok = true;
+    for (uint32_t k = 0; k < count; ++k) {
+        const uint32_t from = ev[k].from, to = ev[k].to;
+        inv_out[k] = ev[k].inv;
+        if (__builtin_expect(!(from < to && to <= 32768u), 0)) { out[k] = EV::pack(0, 0, 0, 0); ok = false; continue; }
+        const unsigned __int128 m = k + 1 < count ? static_cast<unsigned __int128>(ev[k + 1].inv) * (to - from) : 0;
+        out[k] = EV::pack(from, to, static_cast<uint64_t>(m), static_cast<uint64_t>(m >> 64));
+    }
+    return ok;
+}
+
+// code_uniform_batch over prepared events: the same chain r -> (imul || mulx) -> add -> select with the same two candidates, and a body that
+// derives nothing.  The loop only ever shifts nothing or one byte out, which the select's own condition says ("do the borders differ in their
+// top byte"), so the count of leading zeros is left to the rare path: two or three equal bytes (the borders agree in their top sixteen bits),
+// a span at or below the threshold, or an empty interval.  That path starts again from the decision's borders through RangeState::renorm --
+// the definition of what is to come out -- and takes its quotient from the span and the cold reciprocal.
+template <class EV>
+__attribute__((noinline)) int code_prepared_batch(const EV *ev, const uint64_t *inv, uint32_t count, RangeState &rs, uint8_t **pp) {
+    if (count == 0) return DK_OK;
+    int err = DK_OK;
+    uint8_t *p = *pp;
+    uint32_t low = rs.low, span = rs.hi - rs.low;
+    uint32_t r = static_cast<uint32_t>((static_cast<unsigned __int128>(span) * inv[0]) >> 64);
+    const EV *const first = ev, *const last = ev + (count - 1);
+    for (; ev != last; ++ev) {
+        const uint32_t from = ev->from(), to = ev->to(), m_hi = ev->m_hi(), m_hi8 = ev->m_hi8();
+        const uint32_t lo0 = low + r * from, h = low + r * to;
+        const unsigned __int128 t = static_cast<unsigned __int128>(r) * ev->m_lo;  // one multiply, both halves: r * M = (r * M_hi + t_hi) * 2^64 + t_lo
+        const uint64_t t_lo = static_cast<uint64_t>(t), t_hi = static_cast<uint64_t>(t >> 64);
+        uint32_t r_stay = r * m_hi + static_cast<uint32_t>(t_hi);
+        uint32_t byte_part = r * m_hi8 + static_cast<uint32_t>(t_lo >> 56);  // (r * M) >> 56 = this + (t_hi << 8), all of it modulo 2^32
+        __asm__("" : "+r"(byte_part));                                       // (only one shift and one add behind the multiply's high half)
+        uint32_t r_byte = byte_part + (static_cast<uint32_t>(t_hi) << 8);
+        __asm__("" : "+r"(r_stay), "+r"(r_byte));  // both candidates in registers, then the choice
+        const uint32_t x = lo0 ^ h, d = h - lo0;
+        const uint32_t be = __builtin_bswap32(lo0);
+        std::memcpy(p, &be, 4);
+        const bool stay = (x & kTopMask) != 0;
+        const unsigned out_bytes = stay ? 0u : 1u, sh = 8u * out_bytes;
+        r = stay ? r_stay : r_byte;
+        p += out_bytes;
+        low = lo0 << sh;
+        span = d << sh;
+        if (__builtin_expect(span <= kRangeThreshold || (x >> 16) == 0, 0)) {
+            p -= out_bytes;
+            RangeState again;
+            const int nb = x ? again.renorm(lo0, h, p) : -1;  // x = 0: an empty interval (or r = 0)
+            if (nb < 0) { err = DK_E_INTERNAL; break; }       // (the state is worth nothing after an error)
+            p += nb;
+            low = again.low;
+            span = again.hi - again.low;
+            r = static_cast<uint32_t>((static_cast<unsigned __int128>(span) * inv[(ev - first) + 1]) >> 64);
+        }
+    }
+    rs.low = low;
+    rs.hi = low + span;
+    if (!err) {  // the last decision of the batch
+        const int nb = r ? rs.narrow(r, ev->from(), ev->to(), p) : -1;
+        if (nb < 0) err = DK_E_INTERNAL; else p += nb;
+    }
+    *pp = p;
+    return err;
+}
+
+class PRing {  // URing's protocol over prepared events and their reciprocals
+public:
+    static constexpr uint32_t kBatch = URing::kBatch;
+    static constexpr int kSlots = URing::kSlots;
+    PRing() : buf_(new PEvent[static_cast<size_t>(kSlots) * kBatch]), inv_(new uint64_t[static_cast<size_t>(kSlots) * kBatch]) {
+        for (auto &c : ready_) c.store(0, std::memory_order_relaxed);
+    }
+    PEvent *slot(int i) { return buf_.get() + static_cast<size_t>(i) * kBatch; }
+    uint64_t *inv(int i) { return inv_.get() + static_cast<size_t>(i) * kBatch; }
+    void acquire_free(int i) { unsigned spins = 0; while (ready_[i].load(std::memory_order_acquire) != 0) backoff(spins); producer_spins += spins; }
+    void publish(int i, uint32_t count_and_flags) { ready_[i].store(count_and_flags | kFull, std::memory_order_release); }
+    uint32_t acquire_full(int i) {
+        unsigned spins = 0;
+        uint32_t v;
+        while ((v = ready_[i].load(std::memory_order_acquire)) == 0) backoff(spins);
+        consumer_spins += spins;
+        return v & ~kFull;
+    }
+    void release(int i) { ready_[i].store(0, std::memory_order_release); }
+    uint64_t producer_spins = 0, consumer_spins = 0;
+
+private:
+    static constexpr uint32_t kFull = 0x40000000u;
+    static void backoff(unsigned &spins) {
+        if (++spins < (1u << 14)) {
+#if defined(__x86_64__)
+            __builtin_ia32_pause();
+#endif
+        } else {
+            std::this_thread::yield();
+        }
+    }
+    std::unique_ptr<PEvent[]> buf_;
+    std::unique_ptr<uint64_t[]> inv_;
+    alignas(64) std::atomic<uint32_t> ready_[kSlots];
+};
+
+// the prepare stage: ring U batch by batch into the prepared ring, slot for slot (a batch stays a batch: its last event carries no M)
+int prepare_uniform(URing &in, PRing &out) {
+    int err = DK_OK;
+    for (int slot = 0;; slot = (slot + 1) % URing::kSlots) {
+        const uint32_t v = in.acquire_full(slot);
+        const uint32_t count = v & ~URing::kEnd;
+        out.acquire_free(slot);
+        if (!prepare_batch(in.slot(slot), count, out.slot(slot), out.inv(slot)) && !err) err = DK_E_INTERNAL;
+        out.publish(slot, v);
+        in.release(slot);
+        if (v & URing::kEnd) break;
+    }
+    return err;
+}
+
+// the calling thread of the six-stage form: the range coder over the prepared ring (code_uniform's shape)
+int code_prepared(PRing &ring, uint8_t *out, size_t cap, size_t *out_len) {
+    RangeState rs;
+    size_t len = 0;
+    int err = DK_OK;
+    for (int slot = 0;; slot = (slot + 1) % PRing::kSlots) {
+        const uint32_t v = ring.acquire_full(slot);
+        const uint32_t count = v & ~URing::kEnd;
+        const PEvent *ev = ring.slot(slot);
+        const uint64_t *inv = ring.inv(slot);
+        if (!err && len + 4 * static_cast<size_t>(count) + 12 <= cap) {  // room for the worst case of this batch: unchecked stores
+            uint8_t *p = out + len;
+            err = code_prepared_batch(ev, inv, count, rs, &p);
+            len = static_cast<size_t>(p - out);
+        } else if (!err) {  // close to the end of the caller's buffer: every event through a scratch word, exact check
+            for (uint32_t k = 0; k < count; ++k) {
+                uint8_t tmp[8];
+                const uint32_t span = rs.hi - rs.low;
+                const uint32_t r = static_cast<uint32_t>((static_cast<unsigned __int128>(span) * inv[k]) >> 64);
+                const int nb = r ? rs.narrow(r, ev[k].from(), ev[k].to(), tmp) : -1;
+                if (nb < 0) { err = DK_E_INTERNAL; break; }
+                if (len + static_cast<size_t>(nb) > cap) { err = DK_E_CAPACITY; break; }  // (keep draining so the helpers can end)
+                std::memcpy(out + len, tmp, static_cast<size_t>(nb));
+                len += static_cast<size_t>(nb);
+            }
+        }
+        ring.release(slot);
+        if (v & URing::kEnd) break;
+    }
+    if (!err) {
+        if (len + 4 > cap) err = DK_E_CAPACITY;
+        else for (int i = 0; i < 4; ++i) out[len++] = static_cast<uint8_t>(rs.low >> (24 - 8 * i));  // ari::Encoder::finish
+    }
+    *out_len = len;
+    return err;
+}
+
+// Six stages where the L3 group has six cores for it: the five-stage form with the prepare stage between the merger and the coder,
+//     ... merger  ->  ring U  ->  prepare  ->  prepared ring  ->  range coder.
+// With the coder's loop shorter the mantissa model was the stage that never waited, so here it models the first two bits only; the third
+// bit's cells -- no other bit reads them -- live on the global-half thread, the one with the most time to spare (DarkGlobalHalfThirdSide).
+// DK_E_NODEVICE: no such group (or a helper thread could not be started).  claim = false (tools/prepared_events_check.cpp on a host
+// without such a group): the same six threads, unconfined.
+int encode_six_stages(DarkModel &model, const DcStream &s, uint8_t *out, size_t cap, size_t *out_len, bool claim = true) {
+    ThreadPair tp;
+    if (claim && !tp.acquire(6)) return DK_E_NODEVICE;
+    auto pin = [&] { if (claim) tp.pin_partner(); };
+    auto unclaim = [&] { if (claim) tp.release(); };
+    const uint64_t *inv = reciprocal_table();
+    URing ring_a, ring_b, ring_m, ring_u;
+    PRing ring_p;
+    int rc_a = DK_OK, rc_b = DK_OK, rc_m = DK_OK, rc_u = DK_OK, rc_p = DK_OK;
+    auto global_model = std::make_unique<DarkModel>(), mantissa_model = std::make_unique<DarkModel>();
+    std::thread t_a, t_b, t_m, t_u, t_p;
+    auto run_a = [&] { pin(); USink sink(ring_a); DarkSymbolHalfSide side{model}; rc_a = write_stream(side, s, sink); sink.finish(); };
+    auto run_b = [&] { pin(); USink sink(ring_b); DarkGlobalHalfThirdSide side{*global_model}; rc_b = write_stream(side, s, sink); sink.finish(); };
+    auto run_m = [&] { pin(); USink sink(ring_m); DarkMantissaTwoSide side{*mantissa_model}; rc_m = write_stream(side, s, sink); sink.finish(); };
+    auto run_u = [&] {
+        pin();
+        UReader rd_a(ring_a), rd_b(ring_b), rd_m(ring_m);
+        USink sink(ring_u);
+        DarkMergeSide5T<true> side{rd_a, rd_b, rd_m, inv};
+        rc_u = write_stream(side, s, sink);
+        sink.finish();
+        rd_a.drain();
+        rd_b.drain();
+        rd_m.drain();
+    };
+    auto run_p = [&] { pin(); rc_p = prepare_uniform(ring_u, ring_p); };
+    int started = 0;
+    try {
+        t_a = std::thread(run_a); ++started;
+        t_b = std::thread(run_b); ++started;
+        t_m = std::thread(run_m); ++started;
+        t_u = std::thread(run_u); ++started;
+        t_p = std::thread(run_p); ++started;
+    } catch (...) {
+        // let whatever did start run to its end: somebody has to empty the rings it fills
+        if (started >= 4) { UReader rd(ring_u); rd.drain(); t_u.join(); }  // (the merger empties the three rings in front of it)
+        else {
+            if (started >= 1) { UReader rd(ring_a); rd.drain(); }
+            if (started >= 2) { UReader rd(ring_b); rd.drain(); }
+            if (started >= 3) { UReader rd(ring_m); rd.drain(); }
+        }
+        if (started >= 1) t_a.join();
+        if (started >= 2) t_b.join();
+        if (started >= 3) t_m.join();
+        unclaim();
+        return DK_E_NODEVICE;
+    }
+    const int rc = code_prepared(ring_p, out, cap, out_len);
+    t_p.join();
+    t_u.join();
+    t_a.join();
+    t_b.join();
+    t_m.join();
+    unclaim();
+    if (getenv("DK_TRACE"))
+        fprintf(stderr, "[dark_amd] entropy: six stages inside the L3 group of cpu %d; waits (pause iterations): symbol half %llu, global half %llu, "
+                        "mantissa model %llu, merger in %llu + %llu + %llu out %llu, prepare in %llu out %llu, coder %llu\n", tp.me,
+                (unsigned long long)ring_a.producer_spins, (unsigned long long)ring_b.producer_spins, (unsigned long long)ring_m.producer_spins,
+                (unsigned long long)ring_a.consumer_spins, (unsigned long long)ring_b.consumer_spins, (unsigned long long)ring_m.consumer_spins,
+                (unsigned long long)ring_u.producer_spins, (unsigned long long)ring_u.consumer_spins, (unsigned long long)ring_p.producer_spins,
+                (unsigned long long)ring_p.consumer_spins);
+    return rc_a ? rc_a : (rc_b ? rc_b : (rc_m ? rc_m : (rc_u ? rc_u : (rc_p ? rc_p : rc))));
+}
+template <class M>
+int encode_six_stages(M &, const DcStream &, uint8_t *, size_t, size_t *) { return DK_E_NODEVICE; }
 
 // Five stages where the L3 group has five cores for it.  DK_E_NODEVICE: no such group (or a helper thread could not be started).
 int encode_five_stages(DarkModel &model, const DcStream &s, uint8_t *out, size_t cap, size_t *out_len) {
@@ -1699,7 +2043,7 @@ int cgroup_cpu_budget() {
 }
 
 // 0 = automatic, 1 = one thread, 2 = models | coder, 4 = the four-stage pipeline (dark model), 5 = five stages (the exponent model in two
-// halves), each whenever the cores exist (else the next narrower form).
+// halves; for 2^21 distances or more with a prepare stage as a sixth thread), each whenever the cores exist (else the next narrower form).
 // Process-wide: DK_ENTROPY_THREADS at load time, dk_set_entropy_threads() afterwards (a launcher that has compared what every rank of a
 // node can claim sets the same form on all of them, so that the slowest rank is not decided by who wins the race for an L3 group).
 std::atomic<int> g_thread_mode{[] { const char *e = getenv("DK_ENTROPY_THREADS"); return e ? atoi(e) : 0; }()};
@@ -1788,6 +2132,13 @@ int encode_block_stream(int model_id, const DcStream &s, uint8_t *out, size_t ca
         t_last_group = -1;
         const bool large = s.m >= (1u << 21);
         const int budget = cgroup_cpu_budget();
+        // The five-stage form with a prepare stage in front of the coder, where a sixth core is free: what the process-wide thread mode 5 and
+        // the automatic choice take for a large stream.  A caller that names a form for this one call (host_threads) gets exactly that form.
+        if (large && host_threads == 0 && (mode == 5 || (mode == 0 && budget >= 6))) {
+            const int rc6 = encode_six_stages(model, s, out, cap, out_len);
+            if (rc6 != DK_E_NODEVICE) { t_last_threads = 6; return rc6; }
+            model.reset();  // not this model, or fewer than six cores: five stages
+        }
         if (mode == 5 || (mode == 0 && large && budget >= 5)) {
             const int rc5 = encode_five_stages(model, s, out, cap, out_len);
             if (rc5 != DK_E_NODEVICE) { t_last_threads = 5; return rc5; }

@@ -423,6 +423,11 @@ public:
     template <class E> bool encode_exponent_symbol_half(uint32_t dist, uint8_t symbol, E &e);
     template <class E> bool encode_exponent_global_half(uint32_t dist, uint8_t symbol, E &e);
     template <class E> static bool encode_mantissa_flat(uint32_t dist, E &e);  // stateless
+    // encode_mantissa_modelled() without its third bit (six-stage pipeline, entropy.cpp: bit i of every length has a cell of its own that no
+    // other bit reads, so the third bit's cells can live with another thread), and that thread's view of them: the cell of the third bit of a
+    // distance with `log` significant bits (it codes the cell's zero, then learns the bit at rate 8 like encode_mantissa_modelled)
+    template <class E> bool encode_mantissa_first_two(uint32_t dist, E &e);
+    inline BinFreq *third_bit_cell(unsigned log) { return &mantissa_[log & 31u][2]; }
     // number of binary decisions encode_exponent emits after its one table decision
     static unsigned exponent_bits(uint32_t dist) { const unsigned log = bit_length(dist + 1); return log >= 8 ? log - 7 : 0; }
     static unsigned modelled_mantissa_bits(uint32_t dist) { const unsigned log = bit_length(dist + 1); return log > 3 ? 3 : log - 1; }
@@ -496,14 +501,15 @@ struct DcStream {          // what the GPU DC stage hands to the entropy stage
 };
 constexpr size_t DC_STREAM_POISON = ~static_cast<size_t>(0);  // *ready: the producer gave up, nothing more will arrive
 // src/block/dc.rs:53-90: init-table RLE header, distances, origin, finish
-// host_threads: 0 = automatic (two threads for large blocks when a partner core sharing the L3 can be pinned), 1 = one thread
+// host_threads: 0 = the process-wide thread mode (set_entropy_thread_mode; automatic by default), else exactly that form for this call: 1 = one
+// thread, 2, 4, 5 (five stages -- the six-stage form belongs to the process-wide mode 5 and to the automatic choice)
 int encode_block_stream(int model_id, const DcStream &s, uint8_t *out, size_t cap, size_t *out_len, int host_threads = 0);
 int last_entropy_threads();  // threads the calling thread's last encode_block_stream used
 int last_entropy_group();    // and the last-level-cache group (lowest cpu number in it) that pass claimed; -1: none (one thread)
 int last_entropy_group_numa();  // ... and that group's memory node (-1: none claimed / unknown)
 void set_preferred_numa(int node);  // calling thread: the memory node its next coding passes should claim their L3 group on (-1: no preference)
 std::vector<size_t> l3_claim_order(const std::vector<int> &numa, size_t own, int preferred);  // (entropy.cpp: the order groups are tried in)
-int set_entropy_thread_mode(int mode);  // 0 automatic | 1 | 2 | 4, process-wide (overrides DK_ENTROPY_THREADS)
+int set_entropy_thread_mode(int mode);  // 0 automatic | 1 | 2 | 4 | 5 (six threads where a sixth core is free: entropy.cpp), process-wide (overrides DK_ENTROPY_THREADS)
 int host_l3_groups(int min_cores);      // L3 groups with at least min_cores cores usable by the calling thread
 // src/block/dc.rs:121-151: header, dc::decode pulling model.decode, origin.  *single = 1 when the block has a
 // one-symbol alphabet (the reference then mis-reads origin; see DESIGN.md "Reference quirks").

@@ -520,7 +520,7 @@ typedef struct dk_stats {
     uint32_t sort_passes;     /* radix passes executed by the last suffix sort */
     uint64_t sorted_elements; /* sum over passes of elements moved */
     uint64_t dc_runs;         /* m of the last dc encode */
-    uint32_t entropy_threads; /* host threads the last range-coder pass used: 1, 2 (models | coder), 4 (exponent model, mantissa model, merger, coder) or 5 (the exponent model in two halves) */
+    uint32_t entropy_threads; /* host threads the last range-coder pass used: 1, 2 (models | coder), 4 (exponent model, mantissa model, merger, coder), 5 (the exponent model in two halves) or 6 (five stages and a prepare stage in front of the coder) */
     int32_t entropy_l3_group; /* the last-level-cache group that pass claimed for its threads (lowest cpu number in it); -1: none */
     /* per-kernel HIP-event timings accumulated since dk_stats_reset (only while profiling is enabled) */
     uint32_t kernel_launches[DK_NUM_KERNEL_SLOTS];
@@ -566,14 +566,17 @@ int dk_get_stats(const dk_ctx *ctx, dk_stats *out);
 const char *dk_kernel_name(int slot);
 
 /* ---- host coding threads (operations; nothing in the reference corresponds: its coder is one thread) ------------------------------------
- * A large single block is coded by a pipeline of 2 or 4 host threads confined to one last-level-cache group; groups are
+ * A large single block is coded by a pipeline of 2, 4, 5 or 6 host threads confined to one last-level-cache group; groups are
  * claimed per process, and a process that finds none free codes on one thread.  A launcher of several ranks per node can make that
  * deterministic: ask every rank how many groups it could claim, and set the same form everywhere. */
-/* thread form of the host coding pass, process-wide: 0 automatic (default; or DK_ENTROPY_THREADS at load time) | 1 | 2 | 4 | 5 */
+/* thread form of the host coding pass, process-wide: 0 automatic (default; or DK_ENTROPY_THREADS at load time) | 1 | 2 | 4 | 5.
+ * 5 = the five-stage pipeline; for a stream of 2^21 distances or more, where the claimed L3 group has a sixth usable core, the same pipeline
+ * with a sixth thread between the merger and the coder that prepares the coder's factors (six threads are reported).  Automatic takes the
+ * same form under the same conditions.  Every form codes the same bytes. */
 int dk_set_entropy_threads(int mode);
 /* number of last-level-cache groups in which the calling thread may use at least min_cores cores */
 int dk_host_l3_groups(int min_cores);
-/* the calling thread's last host coding pass: threads used (1 / 2 / 4 / 5) and the L3 group claimed (-1: none).  Either may be NULL. */
+/* the calling thread's last host coding pass: threads used (1 / 2 / 4 / 5 / 6) and the L3 group claimed (-1: none).  Either may be NULL. */
 void dk_last_entropy_info(int *threads, int *l3_group);
 /* memory node the calling thread's coding passes should claim their L3 group on first (-1: none; the block entry points set it to their
  * context's GPU's node themselves -- for callers of dk_stream_encode that know where their staging memory lives) */

@@ -164,6 +164,10 @@ SIGNATURES = {
     "dk_dbg_dev_period": (_i, [_vp, _vp, _sz, _i, _vp, _vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _i, _vp]),
     # ctx, text, n | code[256], bits, spk, inv[256], narrow | keys_out, sa, bwt, origin | bucket_starts_out[256], out[4]
     "dk_dbg_dev_initial_sort": (_i, [_vp, _vp, _sz, _vp, _i, _i, _vp, _i] + [_vp] * 4 + [_vp, _vp]),
+    # ctx, text, count, n | keys, vals, rank, act | code[256], out[8]
+    "dk_dbg_dev_packed_first": (_i, [_vp, _vp, _sz, _vp] + [_vp] * 4 + [_vp, _vp]),
+    # ctx, count, n, h, act, c, rank | keys, vals, next_act, guard | out[8]
+    "dk_dbg_dev_packed_round": (_i, [_vp, _sz, _vp, C.c_uint32, _vp, _sz, _vp] + [_vp] * 4 + [_vp]),
     "dk_dbg_dev_inverse_permutation": (_i, [_vp, _vp, _sz, _vp, _vp]),
     "dk_dbg_mail_fill": (_i, [_vp, _i]),
     "dk_dbg_ws_peek": (_i, [_vp, _sz, _vp]),

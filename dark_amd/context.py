@@ -1099,6 +1099,50 @@ class Context:
                     bwt=None if d_bwt is None else d_bwt.cpu().numpy(), origin=None if d_origin is None else self._to_host(d_origin, np.uint32),
                     bucket_starts=starts, route=int(out[0]), passes=int(out[1]), sorted_elements=int(out[2]), out=out)
 
+    def dbg_dev_packed_first(self, blocks, fill=0xC3, pad=64):
+        """dk_dbg_dev_packed_first: the first step of the segmented suffix sort on the pack `blocks` (byte arrays).  Every device output holds
+        `fill` bytes before the call and has `pad` guard entries in front and behind.  -> dict of the whole arrays after the call, guards
+        included: keys (uint64), vals, rank, act, and code (256 uint16, over `fill`), out (8 words, over `fill`), live"""
+        import torch
+        blocks = [np.ascontiguousarray(b, dtype=np.uint8) for b in blocks]
+        total = sum(len(b) for b in blocks)
+        d_text = torch.from_numpy(np.concatenate(blocks) if blocks else np.zeros(1, np.uint8)).to("cuda:%d" % self.device)
+        filled = lambda width: torch.from_numpy(np.full(width * (total + 2 * pad), fill, np.uint8)).to("cuda:%d" % self.device)  # noqa: E731
+        d_keys, d_vals, d_rank, d_act = filled(8), filled(4), filled(4), filled(4)
+        code, out = np.full(512, fill, np.uint8).view(np.uint16), np.full(32, fill, np.uint8).view(np.uint32)
+        at = lambda t, width: C.c_void_p(t.data_ptr() + width * pad)  # noqa: E731
+        _inputs_ready(d_text)
+        self._ck(self._lib.dk_dbg_dev_packed_first(self._h, _ptr(d_text), len(blocks), _sizes([len(b) for b in blocks]), at(d_keys, 8), at(d_vals, 4),
+                                                   at(d_rank, 4), at(d_act, 4), _ptr(code), _ptr(out)))
+        words = lambda t: self._to_host(t, np.uint32)  # noqa: E731
+        return dict(keys=self._to_host(d_keys, np.uint64), vals=words(d_vals), rank=words(d_rank), act=words(d_act), code=code, out=out, live=int(out[4]))
+
+    def dbg_dev_packed_round(self, sizes, h, act, rank, guard=True, fill=0xC3, pad=64):
+        """dk_dbg_dev_packed_round: one round of the segmented suffix sort at depth h on the list `act` and the ranks `rank` (one word per byte of
+        the pack of blocks of `sizes` bytes), and the guard words of the next list (guard=False: a null d_guard).  Every device output holds `fill`
+        bytes before the call and has `pad` guard entries in front and behind; rank stands between such guards too.  -> dict of the whole
+        arrays after the call, guards included: keys (uint64), vals, next_act, rank, guard (None without), and out (8 words, over `fill`), live"""
+        import torch
+        dev = "cuda:%d" % self.device
+        act, rank = np.ascontiguousarray(act, dtype=np.uint32), np.ascontiguousarray(rank, dtype=np.uint32)
+        if len(rank) != sum(int(n) for n in sizes):
+            raise DarkError(_lib.DK_E_ARG, "rank holds one word per byte of the pack")
+        c = len(act)
+        guards = np.full(pad, fill * 0x01010101, np.uint32)
+        d_act = self._to_dev(act if c else np.zeros(1, np.uint32), np.uint32)
+        d_rank = self._to_dev(np.concatenate([guards, rank, guards]), np.uint32)
+        filled = lambda width, entries: torch.from_numpy(np.full(width * (entries + 2 * pad), fill, np.uint8)).to(dev)  # noqa: E731
+        d_keys, d_vals, d_next = filled(8, c), filled(4, c), filled(4, c)
+        d_guard = filled(4, len(sizes)) if guard else None
+        out = np.full(32, fill, np.uint8).view(np.uint32)
+        at = lambda t, width: None if t is None else C.c_void_p(t.data_ptr() + width * pad)  # noqa: E731
+        _inputs_ready(d_act)
+        self._ck(self._lib.dk_dbg_dev_packed_round(self._h, len(sizes), _sizes(sizes), int(h), _ptr(d_act), c, at(d_rank, 4), at(d_keys, 8), at(d_vals, 4),
+                                                   at(d_next, 4), at(d_guard, 4), _ptr(out)))
+        words = lambda t: self._to_host(t, np.uint32)  # noqa: E731
+        return dict(keys=self._to_host(d_keys, np.uint64), vals=words(d_vals), next_act=words(d_next), rank=words(d_rank),
+                    guard=None if d_guard is None else words(d_guard), out=out, live=int(out[2]))
+
     def dbg_dev_inverse_permutation(self, sa, marked_val=None):
         """dk_dbg_dev_inverse_permutation: rank[sa[p] & 0x7FFFFFFF] = marked_val[p] if sa[p] has bit 31 set (and marked_val is given) else p"""
         d_sa = self._to_dev(sa, np.uint32)

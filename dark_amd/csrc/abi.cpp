@@ -1623,6 +1623,38 @@ int dk_dbg_dev_initial_sort(dk_ctx *ctx, const uint8_t *d_text, size_t n, const 
     const DbgInitialSort a{d_text, n, code, bits, spk, with_prev ? inv : nullptr, narrow, d_keys_out, d_sa, d_bwt, d_origin, bucket_starts_out};
     return dbg_initial_sort_device(ctx, a, out);
 }
+int dk_dbg_dev_packed_first(dk_ctx *ctx, const uint8_t *d_text, size_t count, const size_t *n, uint64_t *d_keys, uint32_t *d_vals, uint32_t *d_rank,
+                            uint32_t *d_act, uint16_t code[256], uint32_t out[8]) {
+    DK_TRY(begin_call(ctx, "dk_dbg_dev_packed_first"));
+    ScopedCall sc(ctx);
+    if (!d_text || !n || !d_keys || !d_vals || !d_rank || !d_act || !code || !out) return ctx->fail(DK_E_ARG, "packed_first: null pointer");
+    Layout lay(count, n);
+    DK_TRY(lay.check(ctx));
+    Upload up(ctx);
+    const uint32_t *d_off = lay.device(up);
+    if (!d_off) return up.failed();
+    const DbgPackedFirst a{d_text, d_off, count, lay.total(), d_keys, d_vals, d_rank, d_act, code};
+    DK_TRY(dbg_packed_first_device(ctx, a, out));
+    up.synchronised();  // (the stage ends with a wait)
+    return DK_OK;
+}
+int dk_dbg_dev_packed_round(dk_ctx *ctx, size_t count, const size_t *n, uint32_t h, const uint32_t *d_act, size_t c, uint32_t *d_rank, uint64_t *d_keys,
+                            uint32_t *d_vals, uint32_t *d_next_act, uint32_t *d_guard, uint32_t out[8]) {
+    DK_TRY(begin_call(ctx, "dk_dbg_dev_packed_round"));
+    ScopedCall sc(ctx);
+    if (!n || !d_act || !d_rank || !d_keys || !d_vals || !d_next_act || !out) return ctx->fail(DK_E_ARG, "packed_round: null pointer");
+    Layout lay(count, n);
+    DK_TRY(lay.check(ctx));
+    if (c == 0 || c > lay.total()) return ctx->fail(DK_E_ARG, "packed_round: a list of %zu suffixes of a pack of %zu bytes", c, lay.total());
+    if (h == 0 || h > (1u << 31)) return ctx->fail(DK_E_ARG, "packed_round: depth %u (1 .. 2^31)", h);
+    Upload up(ctx);
+    const uint32_t *d_off = lay.device(up);
+    if (!d_off) return up.failed();
+    const DbgPackedRound a{d_off, count, lay.total(), h, d_act, c, d_rank, d_keys, d_vals, d_next_act, d_guard};
+    DK_TRY(dbg_packed_round_device(ctx, a, out));
+    up.synchronised();  // (the stage ends with a wait)
+    return DK_OK;
+}
 int dk_dbg_dev_inverse_permutation(dk_ctx *ctx, const uint32_t *d_sa, size_t n, uint32_t *d_rank, const uint32_t *d_marked_val) {
     DK_TRY(begin_call(ctx, "dk_dbg_dev_inverse_permutation"));
     ScopedCall sc(ctx);

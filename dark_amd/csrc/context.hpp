@@ -297,6 +297,22 @@ int packed_bwt_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off,
 // d_phi (may be null; total words): Phi for the LCP pass, from the sort's rank before it is released (lcp_phi_from_rank_device).
 int packed_sa_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, size_t count, size_t total, uint32_t *d_sa, uint8_t *d_bwt,
                      uint32_t *d_origin, uint32_t *d_guard, int max_rounds, size_t *guarded, uint32_t *d_phi = nullptr);
+// dk_dbg_dev_packed_first's arguments under the names of the header: the first step of the segmented sort (code table, first keys, their sort, the
+// first regroup) on the caller's pack; off on the device.  keys / vals / rank: total entries, act: its first `live`.  code_out (host, 256 codes).
+// out: sigma | bits | blk_bits | k_used | live | the sort's end bit | 0 | 0.  Synchronises; releases its workspace.
+struct DbgPackedFirst {
+    const uint8_t *text; const uint32_t *off; size_t count, total;
+    uint64_t *keys; uint32_t *vals, *rank, *act; uint16_t *code_out;
+};
+int dbg_packed_first_device(dk_ctx *ctx, const DbgPackedFirst &args, uint32_t out[8]);
+// dk_dbg_dev_packed_round's arguments under the names of the header: one round of the segmented sort at depth h on the caller's list act[0, c) and
+// the caller's ranks, and the guard step on the next list when guard (count words) is given.  out: rbits | gbits | live | 0 ...  Synchronises;
+// releases its workspace.
+struct DbgPackedRound {
+    const uint32_t *off; size_t count, total; uint32_t h; const uint32_t *act; size_t c; uint32_t *rank;
+    uint64_t *keys; uint32_t *vals, *next_act, *guard;
+};
+int dbg_packed_round_device(dk_ctx *ctx, const DbgPackedRound &args, uint32_t out[8]);
 // lcp.hip: d_lcp[i] = common prefix of the suffixes at slots i - 1 and i of their block, 0 at a block's first slot; layout of
 // d_text / d_sa / d_lcp as in packed_sa_device (a single block: count = 1, d_off = {0, n}).  DK_E_ARG, with d_lcp untouched, for an entry of d_sa
 // outside its block.  Synchronises (the lists' counters are read back); ORs DK_ROUTE_LCP_* into stats.sa_route.  Takes 4 total + total / 1024

@@ -451,21 +451,50 @@ __global__ __launch_bounds__(256) void k_pdc_final(const uint32_t *__restrict__ 
     }
 }
 
-// The segmented suffix sort, up to and including the guard: *rank_out[p] = the final slot of suffix p (the first slot of its group for the
-// members of a group still unresolved after max_rounds), d_guard[i] = 1 for the blocks that hold such a group, *guarded = their suffixes.
-// rank lives in the workspace together with the sort's temporaries: the caller takes ws_mark() before the call and releases it once it
-// has emitted what it wants from rank.
-int packed_sort_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, size_t count, size_t total, uint32_t *d_guard, int max_rounds,
-                       const uint32_t **rank_out, size_t *guarded) {
+// The buffers of one segmented sort over `entries` list entries (the first step: the whole pack), and the pack they belong to.
+struct PkSort {
+    dk_ctx *ctx;
+    const uint32_t *d_off;
+    uint32_t cnt;
+    size_t total;
+    uint64_t *keys, *keys_alt;  // the sorted list stands in keys / vals behind every step (sort_pairs swaps each pair as it needs)
+    uint32_t *vals, *vals_alt;
+    GroupAgg *agg;              // one per tile of the list
+};
+
+// what the first step chose: the pack's alphabet, the key's layout and the bit the sort ended at
+struct PkFirst { uint32_t sigma; int bits, blk_bits, k_used, end_bit; };
+
+// one scan over the sorted list keys / vals of c entries: ranks written, live entries (order kept) into next_act; *live = their number
+int pk_regroup(const PkSort &s, uint32_t c, int rbits, uint32_t *rank, uint32_t *next_act, uint32_t *live) {
+    dk_ctx *ctx = s.ctx;
     hipStream_t st = ctx->stream;
-    const uint32_t cnt = static_cast<uint32_t>(count), T = static_cast<uint32_t>(total);
-    uint64_t *keys = ctx->ws_alloc<uint64_t>(total), *keys_alt = ctx->ws_alloc<uint64_t>(total);
-    uint32_t *vals = ctx->ws_alloc<uint32_t>(total), *vals_alt = ctx->ws_alloc<uint32_t>(total);
-    uint32_t *act = ctx->ws_alloc<uint32_t>(total), *rank = ctx->ws_alloc<uint32_t>(total);
-    GroupAgg *agg = ctx->ws_alloc<GroupAgg>(div_up(total, PK_TILE));
-    uint32_t *present = ctx->ws_alloc<uint32_t>(256);
-    uint16_t *code = ctx->ws_alloc<uint16_t>(256);
-    if (!keys || !keys_alt || !vals || !vals_alt || !act || !rank || !agg || !present || !code) return DK_E_NOMEM;
+    uint32_t *d_live = &ctx->d_mail->packed.live;
+    const uint32_t ntiles = static_cast<uint32_t>(div_up(c, PK_TILE));
+    {
+        LaunchScope ls(ctx, K_RERANK_REDUCE, 8.0 * c);
+        k_pk_tile_sum<<<dim3(ntiles), dim3(PK_BLOCK), 0, st>>>(s.keys, c, rbits, s.agg);
+    }
+    {
+        LaunchScope ls(ctx, K_RERANK_SCAN, 32.0 * ntiles);
+        k_pk_spine<<<dim3(1), dim3(1024), 0, st>>>(s.agg, ntiles, d_live);
+    }
+    {
+        LaunchScope ls(ctx, K_RERANK_APPLY, 20.0 * c);
+        k_pk_tile_apply<<<dim3(ntiles), dim3(PK_BLOCK), 0, st>>>(s.keys, s.vals, c, rbits, s.agg, rank, next_act);
+    }
+    DK_HIP(ctx, hipGetLastError());
+    DK_TRY(ctx->mail_read(&ctx->h_mail->packed.live));
+    *live = ctx->h_mail->packed.live;
+    return DK_OK;
+}
+
+// The first step: the pack's code table (present: 256 words, code: 256 codes, both on the device), the first keys of every suffix, their sort and
+// the first regroup: rank[p] for every p, the members of groups of two or more into act.
+int pk_first(PkSort &s, const uint8_t *d_text, uint32_t *present, uint16_t *code, uint32_t *rank, uint32_t *act, PkFirst *f, uint32_t *live) {
+    dk_ctx *ctx = s.ctx;
+    hipStream_t st = ctx->stream;
+    const size_t total = s.total;
     uint32_t *d_live = &ctx->d_mail->packed.live;
     DK_HIP(ctx, hipMemsetAsync(present, 0, 256 * sizeof(uint32_t), st));
     {
@@ -475,63 +504,78 @@ int packed_sort_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off
     }
     DK_HIP(ctx, hipGetLastError());
     DK_TRY(ctx->mail_read(&ctx->h_mail->packed.live));
-    const uint32_t sigma = ctx->h_mail->packed.live;
-    const int bits = static_cast<int>(std::max(1u, ceil_log2_u64(static_cast<uint64_t>(sigma) + 1)));
-    const int blk_bits = static_cast<int>(ceil_log2_u64(count));
-    const int k = std::max(1, (64 - blk_bits) / bits);
+    f->sigma = ctx->h_mail->packed.live;
+    f->bits = static_cast<int>(std::max(1u, ceil_log2_u64(static_cast<uint64_t>(f->sigma) + 1)));
+    f->blk_bits = static_cast<int>(ceil_log2_u64(s.cnt));
+    const int k = std::max(1, (64 - f->blk_bits) / f->bits);
     // a key of k symbols resolves k symbols: no point in more than the longest block
-    const int k_used = static_cast<int>(std::min<uint64_t>(k, std::max<uint64_t>(1, total)));
+    f->k_used = static_cast<int>(std::min<uint64_t>(k, std::max<uint64_t>(1, total)));
+    f->end_bit = f->blk_bits + f->bits * f->k_used;
     {
         LaunchScope ls(ctx, K_RADIX_SCATTER_TEXT, 9.0 * total);
-        k_pk_init_keys<<<dim3(static_cast<unsigned>(div_up(total, 256))), dim3(256), 0, st>>>(d_text, d_off, cnt, T, code, bits, k_used, keys, vals);
+        k_pk_init_keys<<<dim3(static_cast<unsigned>(div_up(total, 256))), dim3(256), 0, st>>>(d_text, s.d_off, s.cnt, static_cast<uint32_t>(total), code, f->bits,
+                                                                                             f->k_used, s.keys, s.vals);
     }
     DK_HIP(ctx, hipGetLastError());
-    DK_TRY(sort_pairs(ctx, keys, keys_alt, vals, vals_alt, total, 0, blk_bits + bits * k_used));
-    // one scan over a sorted list: ranks written, live entries into act; returns the live count
-    auto regroup = [&](uint32_t c, int rbits, uint32_t *live) -> int {
-        const uint32_t ntiles = static_cast<uint32_t>(div_up(c, PK_TILE));
-        {
-            LaunchScope ls(ctx, K_RERANK_REDUCE, 8.0 * c);
-            k_pk_tile_sum<<<dim3(ntiles), dim3(PK_BLOCK), 0, st>>>(keys, c, rbits, agg);
-        }
-        {
-            LaunchScope ls(ctx, K_RERANK_SCAN, 32.0 * ntiles);
-            k_pk_spine<<<dim3(1), dim3(1024), 0, st>>>(agg, ntiles, d_live);
-        }
-        {
-            LaunchScope ls(ctx, K_RERANK_APPLY, 20.0 * c);
-            k_pk_tile_apply<<<dim3(ntiles), dim3(PK_BLOCK), 0, st>>>(keys, vals, c, rbits, agg, rank, act);
-        }
-        DK_HIP(ctx, hipGetLastError());
-        DK_TRY(ctx->mail_read(&ctx->h_mail->packed.live));
-        *live = ctx->h_mail->packed.live;
-        return DK_OK;
-    };
+    DK_TRY(sort_pairs(ctx, s.keys, s.keys_alt, s.vals, s.vals_alt, total, 0, f->end_bit));
+    return pk_regroup(s, static_cast<uint32_t>(total), 64, rank, act, live);
+}
+
+// One round at depth h on the list act[0, c): the round keys, their sort, the regroup.  next_act may be act itself (the keys are complete before
+// the scan writes the next list).  *rbits_out (may be null): the width of rank2 in the key.
+int pk_round(PkSort &s, const uint32_t *act, uint32_t c, uint64_t h, uint32_t *rank, uint32_t *next_act, int *rbits_out, uint32_t *live) {
+    dk_ctx *ctx = s.ctx;
+    const int rbits = static_cast<int>(ceil_log2_u64(s.total + h));
+    const int gbits = static_cast<int>(ceil_log2_u64(s.total));
+    {
+        LaunchScope ls(ctx, K_ROUND_LOCAL, 20.0 * c);
+        k_pk_round_keys<<<dim3(static_cast<unsigned>(div_up(c, 256))), dim3(256), 0, ctx->stream>>>(act, c, rank, s.d_off, s.cnt, static_cast<uint32_t>(h), rbits,
+                                                                                                    s.keys, s.vals);
+    }
+    DK_HIP(ctx, hipGetLastError());
+    DK_TRY(sort_pairs(ctx, s.keys, s.keys_alt, s.vals, s.vals_alt, c, 0, rbits + gbits));
+    if (rbits_out) *rbits_out = rbits;
+    return pk_regroup(s, c, rbits, rank, next_act, live);
+}
+
+// The guard: d_guard[i] = 1 for the blocks that hold a suffix of act[0, live), 0 for the others
+int pk_guard(const PkSort &s, const uint32_t *act, uint32_t live, uint32_t *d_guard) {
+    dk_ctx *ctx = s.ctx;
+    DK_HIP(ctx, hipMemsetAsync(d_guard, 0, s.cnt * sizeof(uint32_t), ctx->stream));
+    if (live > 0) {
+        LaunchScope ls(ctx, K_RERANK_APPLY, 8.0 * live);
+        k_pk_guard_mark<<<dim3(static_cast<unsigned>(div_up(live, 256))), dim3(256), 0, ctx->stream>>>(act, live, s.d_off, s.cnt, d_guard);
+    }
+    DK_HIP(ctx, hipGetLastError());
+    return DK_OK;
+}
+
+// The segmented suffix sort, up to and including the guard: *rank_out[p] = the final slot of suffix p (the first slot of its group for the
+// members of a group still unresolved after max_rounds), d_guard[i] = 1 for the blocks that hold such a group, *guarded = their suffixes.
+// rank lives in the workspace together with the sort's temporaries: the caller takes ws_mark() before the call and releases it once it
+// has emitted what it wants from rank.  The steps are pk_first, pk_round and pk_guard, which dk_dbg_dev_packed_first / _round run one at a time.
+int packed_sort_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, size_t count, size_t total, uint32_t *d_guard, int max_rounds,
+                       const uint32_t **rank_out, size_t *guarded) {
+    uint64_t *keys = ctx->ws_alloc<uint64_t>(total), *keys_alt = ctx->ws_alloc<uint64_t>(total);
+    uint32_t *vals = ctx->ws_alloc<uint32_t>(total), *vals_alt = ctx->ws_alloc<uint32_t>(total);
+    uint32_t *act = ctx->ws_alloc<uint32_t>(total), *rank = ctx->ws_alloc<uint32_t>(total);
+    GroupAgg *agg = ctx->ws_alloc<GroupAgg>(div_up(total, PK_TILE));
+    uint32_t *present = ctx->ws_alloc<uint32_t>(256);
+    uint16_t *code = ctx->ws_alloc<uint16_t>(256);
+    if (!keys || !keys_alt || !vals || !vals_alt || !act || !rank || !agg || !present || !code) return DK_E_NOMEM;
+    PkSort s{ctx, d_off, static_cast<uint32_t>(count), total, keys, keys_alt, vals, vals_alt, agg};
+    PkFirst f{};
     uint32_t live = 0;
-    DK_TRY(regroup(T, 64, &live));
-    uint64_t h = static_cast<uint64_t>(k_used);
-    const int gbits = static_cast<int>(ceil_log2_u64(total));
+    DK_TRY(pk_first(s, d_text, present, code, rank, act, &f, &live));
+    uint64_t h = static_cast<uint64_t>(f.k_used);
     uint32_t rounds = 0;
     while (live > 0 && static_cast<int>(rounds) < max_rounds) {
-        const int rbits = static_cast<int>(ceil_log2_u64(total + h));
-        {
-            LaunchScope ls(ctx, K_ROUND_LOCAL, 20.0 * live);
-            k_pk_round_keys<<<dim3(static_cast<unsigned>(div_up(live, 256))), dim3(256), 0, st>>>(act, live, rank, d_off, cnt, static_cast<uint32_t>(h),
-                                                                                                 rbits, keys, vals);
-        }
-        DK_HIP(ctx, hipGetLastError());
-        DK_TRY(sort_pairs(ctx, keys, keys_alt, vals, vals_alt, live, 0, rbits + gbits));
-        DK_TRY(regroup(live, rbits, &live));
+        DK_TRY(pk_round(s, act, live, h, rank, act, nullptr, &live));
         h *= 2;
         ++rounds;
     }
     ctx->stats.rounds = rounds;
-    DK_HIP(ctx, hipMemsetAsync(d_guard, 0, count * sizeof(uint32_t), st));
-    if (live > 0) {
-        LaunchScope ls(ctx, K_RERANK_APPLY, 8.0 * live);
-        k_pk_guard_mark<<<dim3(static_cast<unsigned>(div_up(live, 256))), dim3(256), 0, st>>>(act, live, d_off, cnt, d_guard);
-    }
-    DK_HIP(ctx, hipGetLastError());
+    DK_TRY(pk_guard(s, act, live, d_guard));
     *rank_out = rank;
     *guarded = live;
     return DK_OK;
@@ -566,6 +610,56 @@ int packed_sa_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, 
     }
     DK_HIP(ctx, hipGetLastError());
     if (d_phi) DK_TRY(lcp_phi_from_rank_device(ctx, rank, d_sa, d_off, count, total, d_phi));  // rank is the inverse suffix array: no second one
+    ctx->ws_release(mark);
+    return DK_OK;
+}
+
+// dk_dbg_dev_packed_first (abi.cpp has checked the arguments): pk_first() on the caller's pack.  rank and act are the caller's arrays; the sort's
+// four buffers, the tile aggregates and the code table are the workspace's, the sorted list and the table are copied out.
+int dbg_packed_first_device(dk_ctx *ctx, const DbgPackedFirst &a, uint32_t out[8]) {
+    const size_t total = a.total, mark = ctx->ws_mark();
+    hipStream_t st = ctx->stream;
+    uint64_t *keys = ctx->ws_alloc<uint64_t>(total), *keys_alt = ctx->ws_alloc<uint64_t>(total);
+    uint32_t *vals = ctx->ws_alloc<uint32_t>(total), *vals_alt = ctx->ws_alloc<uint32_t>(total);
+    GroupAgg *agg = ctx->ws_alloc<GroupAgg>(div_up(total, PK_TILE));
+    uint32_t *present = ctx->ws_alloc<uint32_t>(256);
+    uint16_t *code = ctx->ws_alloc<uint16_t>(256);
+    if (!keys || !keys_alt || !vals || !vals_alt || !agg || !present || !code) return DK_E_NOMEM;
+    PkSort s{ctx, a.off, static_cast<uint32_t>(a.count), total, keys, keys_alt, vals, vals_alt, agg};
+    PkFirst f{};
+    uint32_t live = 0;
+    DK_TRY(pk_first(s, a.text, present, code, a.rank, a.act, &f, &live));
+    DK_HIP(ctx, hipMemcpyAsync(a.keys, s.keys, total * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+    DK_HIP(ctx, hipMemcpyAsync(a.vals, s.vals, total * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    uint16_t h_code[256];
+    DK_HIP(ctx, hipMemcpyAsync(h_code, code, sizeof h_code, hipMemcpyDeviceToHost, st));
+    DK_HIP(ctx, hipStreamSynchronize(st));
+    std::copy(h_code, h_code + 256, a.code_out);
+    out[0] = f.sigma, out[1] = static_cast<uint32_t>(f.bits), out[2] = static_cast<uint32_t>(f.blk_bits), out[3] = static_cast<uint32_t>(f.k_used);
+    out[4] = live, out[5] = static_cast<uint32_t>(f.end_bit), out[6] = 0, out[7] = 0;
+    ctx->ws_release(mark);
+    return DK_OK;
+}
+
+// dk_dbg_dev_packed_round (abi.cpp has checked the arguments): pk_round() on the caller's list and ranks, then pk_guard() on the next list when
+// the guard words are asked for.  The sort's buffers for c entries are the workspace's; the sorted list is copied out.
+int dbg_packed_round_device(dk_ctx *ctx, const DbgPackedRound &a, uint32_t out[8]) {
+    const size_t c = a.c, mark = ctx->ws_mark();
+    hipStream_t st = ctx->stream;
+    uint64_t *keys = ctx->ws_alloc<uint64_t>(c), *keys_alt = ctx->ws_alloc<uint64_t>(c);
+    uint32_t *vals = ctx->ws_alloc<uint32_t>(c), *vals_alt = ctx->ws_alloc<uint32_t>(c);
+    GroupAgg *agg = ctx->ws_alloc<GroupAgg>(div_up(c, PK_TILE));
+    if (!keys || !keys_alt || !vals || !vals_alt || !agg) return DK_E_NOMEM;
+    PkSort s{ctx, a.off, static_cast<uint32_t>(a.count), a.total, keys, keys_alt, vals, vals_alt, agg};
+    int rbits = 0;
+    uint32_t live = 0;
+    DK_TRY(pk_round(s, a.act, static_cast<uint32_t>(c), a.h, a.rank, a.next_act, &rbits, &live));
+    if (a.guard) DK_TRY(pk_guard(s, a.next_act, live, a.guard));
+    DK_HIP(ctx, hipMemcpyAsync(a.keys, s.keys, c * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+    DK_HIP(ctx, hipMemcpyAsync(a.vals, s.vals, c * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    DK_HIP(ctx, hipStreamSynchronize(st));
+    out[0] = static_cast<uint32_t>(rbits), out[1] = ceil_log2_u64(a.total), out[2] = live;
+    for (int i = 3; i < 8; ++i) out[i] = 0;
     ctx->ws_release(mark);
     return DK_OK;
 }

@@ -785,6 +785,42 @@ int dk_dbg_dev_period(dk_ctx *ctx, const uint8_t *d_text, size_t n, int period, 
  * narrow outside 0 / 1 or with more than 40 sorted bits, bucket_starts_out without narrow or the reverse.  DK_E_NOMEM when the workspace does not fit. */
 int dk_dbg_dev_initial_sort(dk_ctx *ctx, const uint8_t *d_text, size_t n, const uint8_t code[256], int bits, int spk, const uint8_t inv[256], int narrow,
                             void *d_keys_out, uint32_t *d_sa, uint8_t *d_bwt, uint32_t *d_origin, uint32_t bucket_starts_out[256], uint32_t out[4]);
+/* The segmented suffix sort of csrc/packed.hip one step at a time: the production sort is pk_first(), pk_round() until no
+ * group is left or the round limit, and pk_guard(); these two entries run the same functions on their own.  A full context only.  The pack is
+ * `count` blocks of n[i] bytes back to back, block i at [off_i, e_i), total = their sum; its limits are those of dk_dev_bwt_forward_packed.
+ * tests/packed_round_model.py is the definition of every output.
+ *
+ * dk_dbg_dev_packed_first: k_pk_hist, k_pk_codes, k_pk_init_keys, their sort and the first regroup.
+ *   code[256]      (host, out) code[c] = 1 + the present byte values below c, 0 for an absent c; sigma = the present values
+ *   the key        block id, then k_used codes of `bits` bits, 0 from the block's end on; bits = max(1, ceil_log2(sigma + 1)),
+ *                  blk_bits = ceil_log2(count), k_used = min(max(1, (64 - blk_bits) / bits), total)
+ *   d_keys, d_vals total entries each: the keys in order and the position each belongs to; stable, so equal keys stand in position order
+ *   d_rank         total words: d_rank[p] = the slot of the first member of p's group (the suffixes with p's key)
+ *   d_act          total words, of which the first `live` are written and the rest left untouched: the members of groups of two or more,
+ *                  in list order
+ *   out            (host, 8 words) sigma | bits | blk_bits | k_used | live | the bit the sort ended at (blk_bits + bits k_used) | 0 | 0
+ * DK_E_ARG before anything is launched: a null context or pointer, an open batch, a decoder context, a pack that dk_dev_bwt_forward_packed refuses.
+ *
+ * dk_dbg_dev_packed_round: k_pk_round_keys, the sort and the regroup (k_pk_tile_sum, k_pk_spine, k_pk_tile_apply) at depth h on a state the
+ * CALLER built, and k_pk_guard_mark on the list it leaves.  The round reads no text, and the ranks need not come from one.
+ *   d_act, c       the list: c distinct suffixes below total
+ *   d_rank         total words, in and out; only the entries of listed suffixes change
+ *   the key        d_rank[p] << rbits | rank2, rbits = ceil_log2(total + h), rank2 = d_rank[p + h] + h, or e_i - 1 - p when p + h >= e_i
+ *   d_keys, d_vals c entries each: the round keys in order and their suffixes; stable, so equal keys keep the order of d_act
+ *   the ranks      a member at list index k of an old group (the entries with one d_rank) that starts at list index ks and has the rank g gets
+ *                  g + (list index of the first entry with its key - ks)
+ *   d_next_act     c words, of which the first `live` are written: the entries whose key occurs twice or more, order kept
+ *   d_guard        (may be null) count words: 1 where the block holds a suffix of the next list, else 0
+ *   out            (host, 8 words) rbits | gbits = ceil_log2(total) | live | 0 ...
+ * The caller's duties: the entries of d_act are distinct and below total; every d_rank[p] is below total, and d_rank[p] plus the number of listed
+ * members of p's old group is at most total.
+ * DK_E_ARG before anything is launched: a null context or required pointer, an open batch, a decoder context, a pack refused as above, c == 0 or
+ * above total, h == 0 or above 2^31.
+ * Both: the sort's buffers come from the workspace, which is marked and released; DK_E_NOMEM when they do not fit.  Both synchronise. */
+int dk_dbg_dev_packed_first(dk_ctx *ctx, const uint8_t *d_text, size_t count, const size_t *n, uint64_t *d_keys, uint32_t *d_vals, uint32_t *d_rank,
+                            uint32_t *d_act, uint16_t code[256], uint32_t out[8]);
+int dk_dbg_dev_packed_round(dk_ctx *ctx, size_t count, const size_t *n, uint32_t h, const uint32_t *d_act, size_t c, uint32_t *d_rank, uint64_t *d_keys,
+                            uint32_t *d_vals, uint32_t *d_next_act, uint32_t *d_guard, uint32_t out[8]);
 /* d_rank[d_sa[p]] = p for a permutation d_sa of 0 .. n-1 (n <= 2^31), through LDS windows.  d_marked_val (may be null): an entry of d_sa with bit
  * 31 set stands for d_sa[p] & 0x7FFFFFFF and its value is d_marked_val[p] instead of p.  The two n-u64 scratch arrays come from the context's
  * workspace: DK_E_NOMEM when they do not fit.  What it does with an input that is no permutation is not defined beyond "no store outside d_rank". */

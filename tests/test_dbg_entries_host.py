@@ -85,6 +85,24 @@ def test_layer_entry_of_the_initial_sort():
     assert len(_lib.SIGNATURES[name][1]) == len(re.search(r"\bint %s\(([^;]*)\);" % name, header).group(1).split(","))
 
 
+def test_layer_entries_of_the_packed_sort():
+    """dk_dbg_dev_packed_first and dk_dbg_dev_packed_round (tests/test_gpu_packed_round.py): the same three facts"""
+    lib = dark_amd.load_library()
+    out = (C.c_uint32 * 8)(*([7] * 8))
+    code = (C.c_uint16 * 256)(*([7] * 256))
+    ns = (C.c_size_t * 1)(100)
+    o = C.cast(out, C.c_void_p)
+    assert lib.dk_dbg_dev_packed_first(None, None, 1, C.cast(ns, C.c_void_p), None, None, None, None, C.cast(code, C.c_void_p), o) == _lib.DK_E_ARG
+    assert lib.dk_dbg_dev_packed_round(None, 1, C.cast(ns, C.c_void_p), 4, None, 10, None, None, None, None, None, o) == _lib.DK_E_ARG
+    assert list(out) == [7] * 8 and list(code) == [7] * 256
+    with open(os.path.join(ROOT, "include", "dark_amd.h")) as f:
+        header = f.read()
+    for name in ("dk_dbg_dev_packed_first", "dk_dbg_dev_packed_round"):
+        assert re.search(r"\bint %s\(dk_ctx \*ctx," % name, header), name
+        assert name in _lib.SIGNATURES
+        assert len(_lib.SIGNATURES[name][1]) == len(re.search(r"\bint %s\(([^;]*)\);" % name, header).group(1).split(",")), name
+
+
 def test_declared_for_either_purpose():
     """a decoder context serves both: the header names the parameter any_ctx, which tests/test_gpu_decoder_ctx.py::test_refusals goes by"""
     with open(os.path.join(ROOT, "include", "dark_amd.h")) as f:

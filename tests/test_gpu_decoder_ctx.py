@@ -356,6 +356,8 @@ def refused_calls(ctx, n):
                                                           None, None, None, p(d_d), p(d_d, 4 * n), None, p(d_e), p(d_e, 2 * n), p(d_e, 4 * n), p(d_e, 6 * n), None, p(host))),
         ("dk_dbg_dev_period", lambda: lib.dk_dbg_dev_period(h, p(d_text), n, 1, p(d_a), p(host), p(host, 64), 3, p(host, 128), 0, None, 0, 0, None, 0, None)),
         ("dk_dbg_dev_initial_sort", lambda: lib.dk_dbg_dev_initial_sort(h, p(d_text), n, p(init), 8, 7, None, 0, p(d_a), p(d_b), None, None, None, p(host))),
+        ("dk_dbg_dev_packed_first", lambda: lib.dk_dbg_dev_packed_first(h, p(d_text), 1, one, p(d_a), p(d_b), p(d_c), p(d_d), p(host), p(host, 1024))),
+        ("dk_dbg_dev_packed_round", lambda: lib.dk_dbg_dev_packed_round(h, 1, one, 4, p(d_a), n // 2, p(d_b), p(d_c), p(d_d), p(d_e), None, p(host))),
         ("dk_dbg_dev_inverse_permutation", lambda: lib.dk_dbg_dev_inverse_permutation(h, p(d_a), n, p(d_b), None)),
     ], batch
 

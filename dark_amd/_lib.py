@@ -31,6 +31,11 @@ class FmHit(C.Structure):
     _fields_ = [("pattern", C.c_uint32), ("block", C.c_uint32), ("position", C.c_uint32), ("slot", C.c_uint32)]
 
 
+class SaSmem(C.Structure):
+    """dk_sa_smem: a record of dk_dev_sa_smems* (16 bytes; context.SA_SMEM_DTYPE is the same layout for numpy)"""
+    _fields_ = [("at", C.c_uint32), ("len", C.c_uint32), ("lo", C.c_uint32), ("hi", C.c_uint32)]
+
+
 class Stats(C.Structure):
     _fields_ = [("ms_h2d", C.c_double), ("ms_sa", C.c_double), ("ms_bwt", C.c_double), ("ms_dc", C.c_double),
                 ("ms_d2h", C.c_double), ("ms_entropy", C.c_double), ("ms_ibwt", C.c_double), ("ms_total", C.c_double),
@@ -93,6 +98,12 @@ SIGNATURES = {
     "dk_dev_sa_search": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp]),
     "dk_sa_search": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp]),
     "dk_dev_sa_search_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "dk_dev_sa_match": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "dk_dev_sa_match_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "dk_sa_match": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "dk_dev_sa_smems": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _sz, _sz, _vp, _vp]),
+    "dk_dev_sa_smems_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _sz, _sz, _vp, _vp]),
+    "dk_sa_smems": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _sz, _sz, _vp, _vp]),
     "dk_fm_index_bytes": (_sz, [_sz, _sz]),
     "dk_dev_fm_build": (_i, [_vp, _vp, _sz, C.c_uint32, _vp]),
     "dk_dev_fm_build_packed": (_i, [_vp, _vp, _sz, _vp, _vp, _vp]),

@@ -119,6 +119,8 @@ FM_HIT_DTYPE = np.dtype([("pattern", np.uint32), ("block", np.uint32), ("positio
 FM_SEAM_HIT_DTYPE = np.dtype([("pattern", np.uint32), ("block", np.uint32), ("back", np.uint32), ("reserved", np.uint32)])
 # dk_fm_near_hit: a record of dk_dev_fm_near* (16 bytes)
 FM_NEAR_HIT_DTYPE = np.dtype([("pattern", np.uint32), ("block", np.uint32), ("position", np.uint32), ("cost", np.uint32)])
+# dk_sa_smem: a record of dk_dev_sa_smems* (16 bytes)
+SA_SMEM_DTYPE = np.dtype([("at", np.uint32), ("len", np.uint32), ("lo", np.uint32), ("hi", np.uint32)])
 FM_NEAR_MAX_PATTERN, FM_NEAR_MAX_K, FM_NEAR_NODE_LIMIT = _lib.FM_NEAR_MAX_PATTERN, _lib.FM_NEAR_MAX_K, _lib.FM_NEAR_NODE_LIMIT
 
 
@@ -427,6 +429,68 @@ class Context:
         blocks = _u32s(pat_blocks)
         self._ck(self._lib.dk_dev_sa_search_packed(self._h, _ptr(d_in), count, ns, _ptr(d_sa), _ptr(d_pat), npat, lens, _ptr(blocks), _ptr(d_lo),
                                                    _ptr(d_hi)))
+
+    # ---- matching statistics and super-maximal matches ----
+    def dev_sa_match(self, d_in, n, d_sa, d_query, query_lens, max_len, d_len, d_lo=None, d_hi=None):
+        """query j = the next query_lens[j] bytes of the uint8 device tensor d_query; for every position g of the queries, d_len[g] = the longest
+        prefix of its window (at most max_len bytes, inside its query) that occurs in d_in[0, n), d_lo[g] / d_hi[g] (both or neither) = what
+        dev_sa_search gives for that prefix (uint32 device tensors of sum(query_lens) entries)"""
+        _inputs_ready(d_in, d_sa, d_query)
+        self._ck(self._lib.dk_dev_sa_match(self._h, _ptr(d_in), n, _ptr(d_sa), _ptr(d_query), len(query_lens), _sizes(query_lens), int(max_len),
+                                           _ptr(d_len), None if d_lo is None else _ptr(d_lo), None if d_hi is None else _ptr(d_hi)))
+
+    def dev_sa_match_packed(self, d_in, sizes, d_sa, d_query, query_lens, query_blocks, max_len, d_len, d_lo=None, d_hi=None):
+        """dev_sa_match in a pack: query j is matched against block query_blocks[j], d_lo / d_hi are local to that block"""
+        _inputs_ready(d_in, d_sa, d_query)
+        _same_length(query_blocks, "blocks", len(query_lens), "queries")
+        blocks = _u32s(query_blocks)
+        self._ck(self._lib.dk_dev_sa_match_packed(self._h, _ptr(d_in), len(sizes), _sizes(sizes), _ptr(d_sa), _ptr(d_query), len(query_lens),
+                                                  _sizes(query_lens), _ptr(blocks), int(max_len), _ptr(d_len), None if d_lo is None else _ptr(d_lo),
+                                                  None if d_hi is None else _ptr(d_hi)))
+
+    def sa_match(self, data, sa, queries, max_len):
+        """(len, lo, hi), uint32 arrays over the positions of the queries back to back, from host memory (dk_sa_match)"""
+        t = as_u8(data)
+        sa = np.ascontiguousarray(sa, dtype=np.uint32)
+        _same_length(sa, "entries", len(t), "bytes")
+        qry, lens, nq = _pack_patterns(queries)
+        total = sum(int(x) for x in lens[:nq])
+        out = [np.zeros(total, dtype=np.uint32) for _ in range(3)]
+        self._ck(self._lib.dk_sa_match(self._h, _ptr(t), len(t), _ptr(sa), _ptr(qry), nq, lens, int(max_len), *[_ptr(x) for x in out]))
+        return tuple(out)
+
+    def dev_sa_smems(self, d_in, n, d_sa, d_query, query_lens, min_len, max_len, max_hits, d_hits):
+        """the super-maximal matches of the queries in d_in[0, n): d_hits (a 16-byte aligned device tensor of max_hits records of four uint32
+        words: at, len, lo, hi) receives the first min(total, max_hits) in rising order of at; returns the total.  max_hits == 0: d_hits may be None"""
+        _inputs_ready(d_in, d_sa, d_query)
+        total = C.c_uint64(0)
+        self._ck(self._lib.dk_dev_sa_smems(self._h, _ptr(d_in), n, _ptr(d_sa), _ptr(d_query), len(query_lens), _sizes(query_lens), int(min_len),
+                                           int(max_len), int(max_hits), None if d_hits is None else _ptr(d_hits), C.byref(total)))
+        return int(total.value)
+
+    def dev_sa_smems_packed(self, d_in, sizes, d_sa, d_query, query_lens, query_blocks, min_len, max_len, max_hits, d_hits):
+        """dev_sa_smems in a pack: query j against block query_blocks[j]"""
+        _inputs_ready(d_in, d_sa, d_query)
+        _same_length(query_blocks, "blocks", len(query_lens), "queries")
+        blocks = _u32s(query_blocks)
+        total = C.c_uint64(0)
+        self._ck(self._lib.dk_dev_sa_smems_packed(self._h, _ptr(d_in), len(sizes), _sizes(sizes), _ptr(d_sa), _ptr(d_query), len(query_lens),
+                                                  _sizes(query_lens), _ptr(blocks), int(min_len), int(max_len), int(max_hits),
+                                                  None if d_hits is None else _ptr(d_hits), C.byref(total)))
+        return int(total.value)
+
+    def sa_smems(self, data, sa, queries, min_len, max_len, max_hits=65536):
+        """(records, total) from host memory: a structured array (SA_SMEM_DTYPE) of the first min(total, max_hits) super-maximal matches in
+        rising order of at, and their number in all (dk_sa_smems)"""
+        t = as_u8(data)
+        sa = np.ascontiguousarray(sa, dtype=np.uint32)
+        _same_length(sa, "entries", len(t), "bytes")
+        qry, lens, nq = _pack_patterns(queries)
+        hits = np.zeros(max(min(int(max_hits), sum(int(x) for x in lens[:nq])), 1), dtype=SA_SMEM_DTYPE)
+        total = C.c_uint64(0)
+        self._ck(self._lib.dk_sa_smems(self._h, _ptr(t), len(t), _ptr(sa), _ptr(qry), nq, lens, int(min_len), int(max_len), int(max_hits), _ptr(hits),
+                                       C.byref(total)))
+        return hits[:min(int(total.value), int(max_hits))], int(total.value)
 
     # ---- FM-index: count patterns in L, no text and no suffix array (DESIGN.md section 4.13); served by decoder contexts too ----
     def dev_fm_build(self, d_bwt, n, origin, d_index):

@@ -1,4 +1,4 @@
-// extern "C" boundary (include/dark_amd.h), the query entries: LCP arrays, suffix-array check and search, the FM-index.  Thin, as abi.cpp is:
+// extern "C" boundary (include/dark_amd.h), the query entries: LCP arrays, suffix-array check, search and matching statistics, the FM-index.  Thin, as abi.cpp is:
 // argument checks, workspace carving, stage sequencing, timing.  An entry names its blocks with a Layout and sends every host array to the
 // device through an Upload (abi_common.hpp); the single-block and the packed form of an entry are one body behind two Layouts.
 #include <algorithm>
@@ -324,6 +324,177 @@ int dk_sa_search(dk_ctx *ctx, const uint8_t *in, size_t n, const uint32_t *sa, c
     DK_TRY(sa_search_run(up, d_text, lay.device(up), d_sa, d_pat, p, nullptr, d_lo, d_hi));
     DK_HIP(ctx, hipMemcpyAsync(lo, d_lo, npat * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     DK_HIP(ctx, hipMemcpyAsync(hi, d_hi, npat * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    DK_TRY(up.sync());
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+// ---- matching statistics and super-maximal matches (csrc/sa_query.hip) ------------------------------------------------
+}  // extern "C"
+
+namespace {
+// the queries of a call on the device: their offsets and, in a pack, their blocks (8 bytes per query)
+struct Queries { const uint32_t *d_off = nullptr, *d_blk = nullptr; };
+int upload_queries(Upload &up, const Patterns &p, const uint32_t *query_block, const uint32_t *d_off, Queries &q) {
+    q.d_off = upload_offsets(up, p);
+    q.d_blk = query_block ? up.stage(query_block, p.count(), "query blocks") : nullptr;
+    return d_off && q.d_off && (!query_block || q.d_blk) ? DK_OK : up.failed();
+}
+// what the two device entries check in front of the queries themselves
+int check_match_call(dk_ctx *ctx, const uint8_t *d_in, Layout &lay, const uint32_t *d_sa, size_t max_len) {
+    if (!d_in || lay.null() || !d_sa) return ctx->fail(DK_E_ARG, "null pointer");
+    DK_TRY(lay.check(ctx));
+    if (max_len == 0) return ctx->fail(DK_E_ARG, "max_len is 0: a window holds one byte at least");
+    return DK_OK;
+}
+int check_match_outputs(dk_ctx *ctx, const void *query, const void *len, const void *lo, const void *hi) {
+    if (!query || !len) return ctx->fail(DK_E_ARG, "null pointer");
+    if (!lo != !hi) return ctx->fail(DK_E_ARG, "one of the two range arrays is null: both, or neither for the lengths alone");
+    return DK_OK;
+}
+int dev_sa_match(dk_ctx *ctx, const char *entry, const uint8_t *d_in, Layout &&lay, const uint32_t *d_sa, const uint8_t *d_query, size_t nq,
+                 const size_t *query_len, const uint32_t *query_block, size_t max_len, uint32_t *d_len, uint32_t *d_lo, uint32_t *d_hi) {
+    DK_TRY(begin_call(ctx, entry));
+    ScopedCall sc(ctx);
+    DK_TRY(check_match_call(ctx, d_in, lay, d_sa, max_len));
+    if (nq == 0) return DK_OK;
+    if (lay.packed() && !query_block) return ctx->fail(DK_E_ARG, "null pointer");
+    Timer t;
+    Patterns p;
+    DK_TRY(check_patterns(ctx, nq, query_len, query_block, lay.count(), p));
+    if (p.bytes() == 0) return DK_OK;
+    DK_TRY(check_match_outputs(ctx, d_query, d_len, d_lo, d_hi));
+    Upload up(ctx);
+    const uint32_t *d_off = lay.device(up);
+    Queries q;
+    DK_TRY(upload_queries(up, p, query_block, d_off, q));
+    DK_TRY(sa_match_device(ctx, d_in, d_off, d_sa, d_query, q.d_off, q.d_blk, nq, p.bytes(), max_len, d_len, d_lo, d_hi));
+    DK_TRY(up.sync());
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+int dev_sa_smems(dk_ctx *ctx, const char *entry, const uint8_t *d_in, Layout &&lay, const uint32_t *d_sa, const uint8_t *d_query, size_t nq,
+                 const size_t *query_len, const uint32_t *query_block, size_t min_len, size_t max_len, size_t max_hits, dk_sa_smem *d_hits,
+                 uint64_t *total) {
+    DK_TRY(begin_call(ctx, entry));
+    ScopedCall sc(ctx);
+    DK_TRY(check_match_call(ctx, d_in, lay, d_sa, max_len));
+    if (!total || (max_hits && !d_hits)) return ctx->fail(DK_E_ARG, "null pointer");
+    if (max_hits) DK_TRY(check_aligned(ctx, addr(d_hits), 16, "the match records are"));
+    if (nq == 0) {
+        *total = 0;
+        return DK_OK;
+    }
+    if (lay.packed() && !query_block) return ctx->fail(DK_E_ARG, "null pointer");
+    Timer t;
+    Patterns p;
+    DK_TRY(check_patterns(ctx, nq, query_len, query_block, lay.count(), p));
+    if (p.bytes() == 0) {
+        *total = 0;
+        return DK_OK;
+    }
+    if (!d_query) return ctx->fail(DK_E_ARG, "null pointer");
+    if (ws_round(4 * (lay.count() + 1)) + ws_round(4 * (nq + 1)) + (query_block ? ws_round(4 * nq) : 0) + sa_smems_workspace(p.bytes()) > ctx->ws_size)
+        return ctx->fail(DK_E_ARG, "%zu queries of %zu bytes do not fit the workspace (16 bytes per query byte)", nq, p.bytes());
+    Upload up(ctx);
+    const uint32_t *d_off = lay.device(up);
+    Queries q;
+    DK_TRY(upload_queries(up, p, query_block, d_off, q));
+    DK_TRY(sa_smems_device(ctx, d_in, d_off, d_sa, d_query, q.d_off, q.d_blk, nq, p.bytes(), min_len, max_len, max_hits, d_hits, total));
+    DK_TRY(up.sync());
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int dk_dev_sa_match(dk_ctx *ctx, const uint8_t *d_in, size_t n, const uint32_t *d_sa, const uint8_t *d_query, size_t nq, const size_t *query_len,
+                    size_t max_len, uint32_t *d_len, uint32_t *d_lo, uint32_t *d_hi) {
+    return dev_sa_match(ctx, "dk_dev_sa_match", d_in, Layout(&n), d_sa, d_query, nq, query_len, nullptr, max_len, d_len, d_lo, d_hi);
+}
+int dk_dev_sa_match_packed(dk_ctx *ctx, const uint8_t *d_in, size_t count, const size_t *n, const uint32_t *d_sa, const uint8_t *d_query, size_t nq,
+                           const size_t *query_len, const uint32_t *query_block, size_t max_len, uint32_t *d_len, uint32_t *d_lo, uint32_t *d_hi) {
+    return dev_sa_match(ctx, "dk_dev_sa_match_packed", d_in, Layout(count, n), d_sa, d_query, nq, query_len, query_block, max_len, d_len, d_lo, d_hi);
+}
+int dk_dev_sa_smems(dk_ctx *ctx, const uint8_t *d_in, size_t n, const uint32_t *d_sa, const uint8_t *d_query, size_t nq, const size_t *query_len,
+                    size_t min_len, size_t max_len, size_t max_hits, dk_sa_smem *d_hits, uint64_t *total) {
+    return dev_sa_smems(ctx, "dk_dev_sa_smems", d_in, Layout(&n), d_sa, d_query, nq, query_len, nullptr, min_len, max_len, max_hits, d_hits, total);
+}
+int dk_dev_sa_smems_packed(dk_ctx *ctx, const uint8_t *d_in, size_t count, const size_t *n, const uint32_t *d_sa, const uint8_t *d_query, size_t nq,
+                           const size_t *query_len, const uint32_t *query_block, size_t min_len, size_t max_len, size_t max_hits, dk_sa_smem *d_hits,
+                           uint64_t *total) {
+    return dev_sa_smems(ctx, "dk_dev_sa_smems_packed", d_in, Layout(count, n), d_sa, d_query, nq, query_len, query_block, min_len, max_len, max_hits,
+                        d_hits, total);
+}
+
+int dk_sa_match(dk_ctx *ctx, const uint8_t *in, size_t n, const uint32_t *sa, const uint8_t *query, size_t nq, const size_t *query_len, size_t max_len,
+                uint32_t *len, uint32_t *lo, uint32_t *hi) {
+    DK_TRY(begin_call(ctx, "dk_sa_match"));
+    ScopedCall sc(ctx);
+    Layout lay(&n);
+    DK_TRY(check_match_call(ctx, in, lay, sa, max_len));
+    if (nq == 0) return DK_OK;
+    Timer t;
+    Patterns p;
+    DK_TRY(check_patterns(ctx, nq, query_len, nullptr, 1, p));
+    const size_t Q = p.bytes();
+    if (Q == 0) return DK_OK;
+    DK_TRY(check_match_outputs(ctx, query, len, lo, hi));
+    // text n, SA 4 n, the two offsets of the block; then the queries, their offsets and the results
+    const size_t need = ws_round(n) + ws_round(4 * n) + 256 + ws_round(Q) + ws_round(4 * (nq + 1)) + (lo ? 3 : 1) * ws_round(4 * Q);
+    if (need > ctx->ws_size) return ctx->fail(DK_E_ARG, "%zu queries of %zu bytes and their statistics do not fit the workspace beside the block", nq, Q);
+    Upload up(ctx);
+    hipStream_t st = ctx->stream;
+    const uint8_t *d_text = up.stage(in, n, "text"), *d_query = up.stage(query, Q, "queries");
+    const uint32_t *d_sa = up.stage(sa, n, "suffix array");
+    uint32_t *d_len = ctx->ws_alloc<uint32_t>(Q), *d_lo = lo ? ctx->ws_alloc<uint32_t>(Q) : nullptr, *d_hi = lo ? ctx->ws_alloc<uint32_t>(Q) : nullptr;
+    if (!d_text || !d_query || !d_sa || !d_len || (lo && (!d_lo || !d_hi))) return up.failed();
+    const uint32_t *d_off = lay.device(up);
+    Queries q;
+    DK_TRY(upload_queries(up, p, nullptr, d_off, q));
+    DK_TRY(sa_match_device(ctx, d_text, d_off, d_sa, d_query, q.d_off, nullptr, nq, Q, max_len, d_len, d_lo, d_hi));
+    DK_HIP(ctx, hipMemcpyAsync(len, d_len, Q * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (lo) {
+        DK_HIP(ctx, hipMemcpyAsync(lo, d_lo, Q * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        DK_HIP(ctx, hipMemcpyAsync(hi, d_hi, Q * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
+    DK_TRY(up.sync());
+    ctx->stats.ms_total = t.ms();
+    return DK_OK;
+}
+
+int dk_sa_smems(dk_ctx *ctx, const uint8_t *in, size_t n, const uint32_t *sa, const uint8_t *query, size_t nq, const size_t *query_len, size_t min_len,
+                size_t max_len, size_t max_hits, dk_sa_smem *hits, uint64_t *total) {
+    DK_TRY(begin_call(ctx, "dk_sa_smems"));
+    ScopedCall sc(ctx);
+    Layout lay(&n);
+    DK_TRY(check_match_call(ctx, in, lay, sa, max_len));
+    if (!total || (max_hits && !hits)) return ctx->fail(DK_E_ARG, "null pointer");
+    *total = 0;
+    if (nq == 0) return DK_OK;
+    Timer t;
+    Patterns p;
+    DK_TRY(check_patterns(ctx, nq, query_len, nullptr, 1, p));
+    const size_t Q = p.bytes();
+    if (Q == 0) return DK_OK;
+    if (!query) return ctx->fail(DK_E_ARG, "null pointer");
+    // text n, SA 4 n, the two offsets of the block; the queries and their offsets; the stage's workspace; the records -- never more than positions
+    const size_t cap = std::min(max_hits, Q);
+    const size_t need = ws_round(n) + ws_round(4 * n) + 256 + ws_round(Q) + ws_round(4 * (nq + 1)) + sa_smems_workspace(Q) + ws_round(16 * cap);
+    if (need > ctx->ws_size)
+        return ctx->fail(DK_E_ARG, "%zu queries of %zu bytes and %zu match records do not fit the workspace beside the block", nq, Q, cap);
+    Upload up(ctx);
+    const uint8_t *d_text = up.stage(in, n, "text"), *d_query = up.stage(query, Q, "queries");
+    const uint32_t *d_sa = up.stage(sa, n, "suffix array");
+    dk_sa_smem *d_hits = cap ? ctx->ws_alloc<dk_sa_smem>(cap) : nullptr;
+    if (!d_text || !d_query || !d_sa || (cap && !d_hits)) return up.failed();
+    const uint32_t *d_off = lay.device(up);
+    Queries q;
+    DK_TRY(upload_queries(up, p, nullptr, d_off, q));
+    DK_TRY(sa_smems_device(ctx, d_text, d_off, d_sa, d_query, q.d_off, nullptr, nq, Q, min_len, max_len, cap, d_hits, total));
+    const size_t nhits = static_cast<size_t>(std::min<uint64_t>(*total, cap));
+    if (nhits) DK_HIP(ctx, hipMemcpyAsync(hits, d_hits, nhits * sizeof(dk_sa_smem), hipMemcpyDeviceToHost, ctx->stream));
     DK_TRY(up.sync());
     ctx->stats.ms_total = t.ms();
     return DK_OK;

@@ -49,7 +49,7 @@ enum KernelSlot : int {
     K_RADIX_SCATTER_TEXT,  // k_radix_scatter<false, true>: first pass, keys built from the text (13 B per pair)
     K_ISA_PARTITION,       // k_isa_init + k_isa_split<true> + k_isa_split<false> (inverse permutation through LDS windows)
     K_ISA_ASSEMBLE,        // k_isa_assemble
-    K_CHAIN,               // k_chain_extract + _ends + _tiles + _spine + _verdicts + _apply (pair chains; their sort is in the radix slots); k_sa_search*, k_fm_count, k_fm_locate, k_fm_extract, k_fm_find_*, k_fm_seam_*, k_fm_near_*
+    K_CHAIN,               // k_chain_extract + _ends + _tiles + _spine + _verdicts + _apply (pair chains; their sort is in the radix slots); k_sa_search*, k_sa_match*, k_sa_smem_*, k_fm_count, k_fm_locate, k_fm_extract, k_fm_find_*, k_fm_seam_*, k_fm_near_*
     K_PERIOD,              // k_period_first + _spine + _fill (next break of the block's dominant period, for the period round)
     K_SLOT_COUNT
 };
@@ -335,6 +335,17 @@ int sa_check_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, s
 // shortest: of the pattern lengths, which decide the kernels launched.  Enqueues only; takes no workspace.
 int sa_search_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, const uint32_t *d_sa, const uint8_t *d_pat, const uint32_t *d_pat_off,
                      const uint32_t *d_pat_blk, size_t npat, size_t longest, size_t shortest, uint32_t *d_lo, uint32_t *d_hi);
+// sa_match_device: query j = d_qry[d_q_off[j], d_q_off[j + 1]) against block d_q_blk[j] (null: block 0; checked by the
+// caller); for every position g < qbytes, d_len[g] = the longest prefix of its window (at most max_len bytes, inside its query) that occurs in the
+// block, d_lo[g] / d_hi[g] (both or neither) = sa_search_device's numbers for that prefix.  Enqueues only; takes no workspace.
+int sa_match_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, const uint32_t *d_sa, const uint8_t *d_qry, const uint32_t *d_q_off,
+                    const uint32_t *d_q_blk, size_t nq, size_t qbytes, size_t max_len, uint32_t *d_len, uint32_t *d_lo, uint32_t *d_hi);
+// sa_smems_device: the super-maximal matches of those statistics; *total_out (host) = their number, d_hits (16-byte aligned records {at, len, lo,
+// hi}, at = the position g) = the first min(total, max_hits) in rising order of at.  max_hits == 0: d_hits is not looked at.  Takes
+// sa_smems_workspace(qbytes) bytes (16 per query byte and a word per 1024, every ws_alloc rounded up) and releases them.  Synchronises.
+size_t sa_smems_workspace(size_t qbytes);
+int sa_smems_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, const uint32_t *d_sa, const uint8_t *d_qry, const uint32_t *d_q_off,
+                    const uint32_t *d_q_blk, size_t nq, size_t qbytes, size_t min_len, size_t max_len, size_t max_hits, void *d_hits, uint64_t *total_out);
 // fm_index.hip: the FM-index of a packed L and the backward search in it; a single block is a pack of one.
 // fm_index_words: 32-bit words of the index (host arithmetic).  fm_build_workspace: what fm_build_device takes, every ws_alloc rounded up.
 size_t fm_index_words(size_t total, size_t count);

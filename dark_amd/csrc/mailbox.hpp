@@ -107,6 +107,12 @@ struct Mail {
         uint64_t near_cut;          // fm_near_device only: k_fm_find_scan_b over the pairs' cut flags (the same plain store, a launch of its own in
                                     // every call): the pairs that stopped at the node limit; the host reads it with `total`, as one group
     } fm_find;
+
+    // ---- super-maximal matches on the suffix array (sa_query.hip: sa_smems_device) -------------------------------------------------------------------
+    struct SaMatch {
+        alignas(8) uint64_t total;  // k_sa_smem_scan_b: the flagged positions of all queries together (a plain store on every launch); the host reads
+                                    // it behind the scan
+    } sa_match;
 };
 static_assert(sizeof(Mail) <= 4096, "the mailbox is one page");
 static_assert((LIVE_RING & (LIVE_RING - 1)) == 0, "rounds index the ring with a mask");

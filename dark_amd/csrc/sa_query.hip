@@ -28,6 +28,18 @@
 // the suffix at lo does not start with P.
 // Containment for an sa that is no suffix array: an entry >= n_b is the empty suffix and the text is not read at it, every compare stops at
 // min(m, n_b - SA[slot]) whatever is "known", and every step shrinks the range: results are unspecified, but lo <= hi <= n_b.
+//
+// MATCHING STATISTICS.  For every position g of a batch of queries: the longest prefix of the window at g (at most
+// max_len bytes, never past its query's end) that occurs in the block, and the search's range of that prefix.  A lower-bound search of the
+// window ends between the two suffixes that share the most with it: the length is max(kl, kr), which the search above computes and drops.
+//   k_sa_match       a wave per position: the window cut to lane_max bytes, by the 64-ary lane search; then the bracket of the matched prefix,
+//                    a lower bound in front of the insertion slot and an upper bound behind it, from the bytes known at their borders
+//   k_sa_match_long  only the positions whose match ran through the cut (len == lane_max < m): inside the range of the lane_max-byte prefix,
+//                    lane_max bytes known, by the whole-wave compare and binary search.  The route is what MATCHED, not the window's length:
+//                    windows are max_len long, most matches a few dozen bytes, and a lane's compare stops at its first difference.
+//   k_sa_smem_mark   the super-maximal matches among them, a flag per position from len[g - 1] and len[g] inside one query;
+//   k_sa_smem_scan_a/b, k_sa_smem_emit   the exclusive scan of the flags over tiles of 1024 positions (no atomics: every run gives the same
+//                    bytes), the total to the mailbox, and the first min(total, max_hits) records {at, len, lo, hi}, a 16-byte store each.
 #include <algorithm>
 
 #include "context.hpp"
@@ -253,6 +265,148 @@ __device__ __forceinline__ void sq_search(const SqArgs &a) {
 __global__ __launch_bounds__(256) void k_sa_search(SqArgs a) { sq_search<false>(a); }
 __global__ __launch_bounds__(256) void k_sa_search_long(SqArgs a) { sq_search<true>(a); }
 
+// ---- matching statistics and super-maximal matches --------------------------------------------------------------------
+
+// Position g of the queries (back to back in qry; query j = [q_off[j], q_off[j + 1]), matched against block q_blk[j], null: block 0): its window
+// is the m = min(max_len, q_off[j + 1] - g) bytes from g on.  len[g] = the longest prefix of the window that occurs in the block, lo[g] / hi[g]
+// (both or neither) = what the search gives for that prefix.
+struct SmArgs {
+    const uint8_t *t; const uint32_t *sa, *off; const uint8_t *qry; const uint32_t *q_off, *q_blk; uint32_t nq, Q, max_len, lane_max; uint32_t *len, *lo, *hi;
+};
+struct SmWindow { uint32_t m, s, nb; };
+__device__ __forceinline__ SmWindow sm_window(const SmArgs &a, uint32_t g) {
+    const uint32_t j = seg_of(a.q_off, a.nq, g);  // (an empty query shares its offset with the next one: the largest j is the one that holds g)
+    const uint32_t left = a.q_off[j + 1] - g, b = a.q_blk ? a.q_blk[j] : 0u, s = a.off[b];
+    return SmWindow{left < a.max_len ? left : a.max_len, s, a.off[b + 1] - s};
+}
+
+// The window P of m bytes inside the slots [L, H), whose suffixes all start with the first `known` bytes of P (L = 0, H = n_b, known = 0: the
+// whole block).  One lower bound of P: the suffixes on either side of the insertion slot are the two that share the most with P, so the longest
+// prefix of P that occurs is max(kl, kr) bytes long (a border that never moved still holds `known`, which the other, moved in a range that is
+// not empty, reaches at least).  Then the bracket of that prefix: a lower bound in front of the slot where the left neighbour has all of it, an
+// upper bound behind the slot where the suffix at the slot has; both start from the bytes known at their borders.  For any array: a border
+// holds more than `known` only once it has moved, so L <= slot - 1 and slot + 1 <= H where they are used, and L <= lo <= hi <= H.
+struct SmOut { uint32_t len, lo, hi; };
+template <bool WAVE>
+__device__ __forceinline__ SmOut sm_position(const uint8_t *__restrict__ tb, const uint32_t *__restrict__ sab, uint32_t nb, const uint8_t *__restrict__ p,
+                                             uint32_t m, uint32_t L, uint32_t H, uint32_t known, uint32_t lane) {
+    SqRange g{L, H, known, known};
+    g = WAVE ? sq_bound_wave<false>(tb, sab, nb, p, m, g, lane) : sq_bound_lanes<false>(tb, sab, nb, p, m, g, lane);
+    const uint32_t slot = g.l, len = g.kl > g.kr ? g.kl : g.kr;
+    SmOut o{len, L, H};
+    if (len > known) {
+        o.lo = o.hi = slot;
+        if (g.kl == len) {
+            const SqRange x{L, slot - 1u, known, len};
+            o.lo = (WAVE ? sq_bound_wave<false>(tb, sab, nb, p, len, x, lane) : sq_bound_lanes<false>(tb, sab, nb, p, len, x, lane)).l;
+        }
+        if (g.kr == len) {
+            const SqRange x{slot + 1u, H, len, known};
+            o.hi = (WAVE ? sq_bound_wave<true>(tb, sab, nb, p, len, x, lane) : sq_bound_lanes<true>(tb, sab, nb, p, len, x, lane)).l;
+        }
+    }
+    return o;
+}
+
+// A wave per position, walked with a grid stride: the window cut to lane_max bytes, by the 64-ary lane search.  A match that runs through the
+// cut (len == lane_max < m) is finished by k_sa_match_long.
+__global__ __launch_bounds__(256) void k_sa_match(SmArgs a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * SQ_WAVES;
+    for (uint64_t g = static_cast<uint64_t>(blockIdx.x) * SQ_WAVES + (threadIdx.x >> 6); g < a.Q; g += nwaves) {
+        const SmWindow w = sm_window(a, static_cast<uint32_t>(g));
+        const uint32_t mc = w.m < a.lane_max ? w.m : a.lane_max;
+        const SmOut o = sm_position<false>(a.t + w.s, a.sa + w.s, w.nb, a.qry + g, mc, 0u, w.nb, 0u, lane);
+        if (lane == 0) {
+            a.len[g] = o.len;
+            if (a.lo) { a.lo[g] = o.lo; a.hi[g] = o.hi; }
+        }
+    }
+}
+
+// Only the positions whose match ran through the cut: a wave reads 64 lengths at a time and takes the marked ones in turn, each inside the
+// range of its lane_max-byte prefix (lo / hi of k_sa_match; without them the whole block, nothing known) by the whole-wave compare.
+__global__ __launch_bounds__(256) void k_sa_match_long(SmArgs a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * SQ_WAVES * 64u;
+    for (uint64_t base = (static_cast<uint64_t>(blockIdx.x) * SQ_WAVES + (threadIdx.x >> 6)) * 64u; base < a.Q; base += stride) {
+        uint64_t todo = __ballot(base + lane < a.Q && a.len[base + lane] == a.lane_max);
+        while (todo) {
+            const uint32_t g = static_cast<uint32_t>(base) + static_cast<uint32_t>(__builtin_ctzll(todo));
+            todo &= todo - 1u;
+            const SmWindow w = sm_window(a, g);
+            if (w.m <= a.lane_max) continue;  // (the window ended at the cut: len is final)
+            uint32_t L = 0, H = w.nb, known = 0;
+            if (a.lo) {
+                H = a.hi[g] < w.nb ? a.hi[g] : w.nb;
+                L = a.lo[g] < H ? a.lo[g] : H;
+                known = a.lane_max;
+            }
+            const SmOut o = sm_position<true>(a.t + w.s, a.sa + w.s, w.nb, a.qry + g, w.m, L, H, known, lane);
+            if (lane == 0) {
+                a.len[g] = o.len;
+                if (a.lo) { a.lo[g] = o.lo; a.hi[g] = o.hi; }
+            }
+        }
+    }
+}
+
+// The super-maximal matches: position g at offset i of its query is one when len[g] >= max(min_len, 1), the match one byte earlier does not
+// contain it (i == 0 or len[g - 1] <= len[g]), and it is not the continuation of a copy longer than max_len (both at the cap).
+constexpr uint32_t SM_TILE = 1024;  // positions per workgroup of the scan: 256 threads x 4
+__global__ __launch_bounds__(256) void k_sa_smem_mark(const uint32_t *__restrict__ len, const uint32_t *__restrict__ q_off, uint32_t nq, uint32_t Q, uint32_t min_len,
+                                                      uint32_t max_len, uint32_t *__restrict__ flag) {
+    const uint64_t g64 = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x;
+    if (g64 >= Q) return;
+    const uint32_t g = static_cast<uint32_t>(g64), l = len[g];
+    const bool first = g == q_off[seg_of(q_off, nq, g)];
+    const uint32_t prev = first ? 0u : len[g - 1];
+    flag[g] = l >= (min_len ? min_len : 1u) && prev <= l && !(!first && prev == max_len && l == max_len);
+}
+// the exclusive scan of the flags: a tile's sum, one workgroup over the sums (the grand total to the mailbox, a plain store on every launch) ...
+__device__ __forceinline__ uint4 sm_flags(const uint32_t *__restrict__ flag, uint32_t Q, uint64_t g0) {
+    if (g0 + 3u < Q) return *reinterpret_cast<const uint4 *>(flag + g0);  // (flag: a workspace allocation, 256-byte aligned; g0 a multiple of 4)
+    return uint4{g0 < Q ? flag[g0] : 0u, g0 + 1u < Q ? flag[g0 + 1u] : 0u, g0 + 2u < Q ? flag[g0 + 2u] : 0u, g0 + 3u < Q ? flag[g0 + 3u] : 0u};
+}
+__global__ __launch_bounds__(256) void k_sa_smem_scan_a(const uint32_t *__restrict__ flag, uint32_t Q, uint32_t *__restrict__ tile_sum) {
+    __shared__ uint32_t s_tmp[5];
+    const uint4 f = sm_flags(flag, Q, static_cast<uint64_t>(blockIdx.x) * SM_TILE + 4u * threadIdx.x);
+    uint32_t all;
+    block_excl_sum<4>(f.x + f.y + f.z + f.w, s_tmp, &all);
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = all;
+}
+__global__ __launch_bounds__(256) void k_sa_smem_scan_b(uint32_t *__restrict__ tile_sum, uint32_t ntiles, uint64_t *__restrict__ grand_total) {
+    __shared__ uint32_t s_tmp[5];
+    uint64_t run = 0;
+    for (uint32_t c = 0; c < ntiles; c += 256u) {  // (the same trip count for every thread)
+        const uint32_t i = c + threadIdx.x, v = i < ntiles ? tile_sum[i] : 0u;
+        uint32_t all;
+        const uint32_t ex = block_excl_sum<4>(v, s_tmp, &all);
+        if (i < ntiles) tile_sum[i] = static_cast<uint32_t>(run) + ex;  // (an exclusive offset is below the total, and that below 2^32)
+        run += all;
+    }
+    if (threadIdx.x == 0) *grand_total = run;
+}
+// ... and the records: flagged position g at place `before` of the list, while that is below nhits = min(total, max_hits); one 16-byte store
+__global__ __launch_bounds__(256) void k_sa_smem_emit(const uint32_t *__restrict__ flag, const uint32_t *__restrict__ len, const uint32_t *__restrict__ lo,
+                                                      const uint32_t *__restrict__ hi, uint32_t Q, const uint32_t *__restrict__ tile_sum, uint32_t nhits,
+                                                      uint4 *__restrict__ hits) {
+    __shared__ uint32_t s_tmp[5];
+    const uint32_t tile_at = tile_sum[blockIdx.x];
+    if (tile_at >= nhits) return;  // (the whole workgroup: the list is cut in front of this tile)
+    const uint64_t g0 = static_cast<uint64_t>(blockIdx.x) * SM_TILE + 4u * threadIdx.x;
+    const uint4 f = sm_flags(flag, Q, g0);
+    const uint32_t fl[4] = {f.x, f.y, f.z, f.w};
+    uint32_t at = tile_at + block_excl_sum<4>(f.x + f.y + f.z + f.w, s_tmp, nullptr);
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; ++k) {
+        if (!fl[k]) continue;
+        const uint32_t g = static_cast<uint32_t>(g0) + k;
+        if (at < nhits) hits[at] = uint4{g, len[g], lo[g], hi[g]};
+        ++at;
+    }
+}
+
 }  // namespace
 
 int sa_check_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, size_t count, size_t total, const uint32_t *d_sa, uint32_t *h_words) {
@@ -299,6 +453,67 @@ int sa_search_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, 
         k_sa_search_long<<<dim3(grid), dim3(64 * SQ_WAVES), 0, st>>>(a);
     }
     DK_HIP(ctx, hipGetLastError());
+    return DK_OK;
+}
+
+int sa_match_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, const uint32_t *d_sa, const uint8_t *d_qry, const uint32_t *d_q_off,
+                    const uint32_t *d_q_blk, size_t nq, size_t qbytes, size_t max_len, uint32_t *d_len, uint32_t *d_lo, uint32_t *d_hi) {
+    hipStream_t st = ctx->stream;
+    // (the border is the search's, and so is its knob: a match that reaches it goes on in k_sa_match_long, whatever the window's length)
+    const uint32_t lane_max = static_cast<uint32_t>(std::max(0, std::min(1 << 20, DK_KNOB("DK_SA_SEARCH_LANE_MAX", SA_SEARCH_LANE_MAX))));
+    const uint32_t cap = static_cast<uint32_t>(std::min<size_t>(max_len, 0xFFFFFFFFull));
+    const SmArgs a{d_text, d_sa, d_off, d_qry, d_q_off, d_q_blk, static_cast<uint32_t>(nq), static_cast<uint32_t>(qbytes), cap, lane_max, d_len, d_lo, d_hi};
+    {
+        // per position three searches of about three steps of 64 slots and 64 short compares; the three results
+        LaunchScope ls(ctx, K_CHAIN, qbytes * (9.0 * 64 * 20 + 12.0));
+        const unsigned grid = static_cast<unsigned>(std::min<size_t>(div_up(qbytes, SQ_WAVES), 1u << 20));
+        k_sa_match<<<dim3(grid), dim3(64 * SQ_WAVES), 0, st>>>(a);
+    }
+    if (cap > lane_max) {
+        LaunchScope ls(ctx, K_CHAIN, 4.0 * qbytes);  // the lengths read; what the marked positions compare is theirs alone
+        const unsigned grid = static_cast<unsigned>(std::min<size_t>(div_up(qbytes, 64 * SQ_WAVES), 1u << 20));
+        k_sa_match_long<<<dim3(grid), dim3(64 * SQ_WAVES), 0, st>>>(a);
+    }
+    DK_HIP(ctx, hipGetLastError());
+    return DK_OK;
+}
+
+size_t sa_smems_workspace(size_t qbytes) {
+    auto r = [](size_t b) { return (b + 255) & ~size_t(255); };
+    return 4 * r(4 * qbytes) + r(4 * div_up(qbytes, SM_TILE));
+}
+
+int sa_smems_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, const uint32_t *d_sa, const uint8_t *d_qry, const uint32_t *d_q_off,
+                    const uint32_t *d_q_blk, size_t nq, size_t qbytes, size_t min_len, size_t max_len, size_t max_hits, void *d_hits, uint64_t *total_out) {
+    hipStream_t st = ctx->stream;
+    const size_t ntiles = div_up(qbytes, SM_TILE), mark = ctx->ws_mark();
+    uint32_t *d_len = ctx->ws_alloc<uint32_t>(qbytes), *d_lo = ctx->ws_alloc<uint32_t>(qbytes), *d_hi = ctx->ws_alloc<uint32_t>(qbytes);
+    uint32_t *d_flag = ctx->ws_alloc<uint32_t>(qbytes), *tile_sum = ctx->ws_alloc<uint32_t>(ntiles);
+    if (!d_len || !d_lo || !d_hi || !d_flag || !tile_sum) return DK_E_NOMEM;
+    DK_TRY(sa_match_device(ctx, d_text, d_off, d_sa, d_qry, d_q_off, d_q_blk, nq, qbytes, max_len, d_len, d_lo, d_hi));
+    const uint32_t Q = static_cast<uint32_t>(qbytes), T = static_cast<uint32_t>(ntiles);
+    {
+        LaunchScope ls(ctx, K_CHAIN, 20.0 * qbytes);  // the lengths and the flags, the flags read twice more
+        k_sa_smem_mark<<<dim3(static_cast<unsigned>(div_up(qbytes, 256))), dim3(256), 0, st>>>(
+            d_len, d_q_off, static_cast<uint32_t>(nq), Q, static_cast<uint32_t>(std::min<size_t>(min_len, 0xFFFFFFFFull)),
+            static_cast<uint32_t>(std::min<size_t>(max_len, 0xFFFFFFFFull)), d_flag);
+        k_sa_smem_scan_a<<<dim3(T), dim3(256), 0, st>>>(d_flag, Q, tile_sum);
+        k_sa_smem_scan_b<<<dim3(1), dim3(256), 0, st>>>(tile_sum, T, &ctx->d_mail->sa_match.total);
+    }
+    DK_HIP(ctx, hipGetLastError());
+    DK_TRY(ctx->mail_read(&ctx->h_mail->sa_match.total));
+    const uint64_t all = ctx->h_mail->sa_match.total;
+    *total_out = all;
+    const size_t nhits = static_cast<size_t>(std::min<uint64_t>(all, max_hits));
+    if (nhits) {
+        {
+            LaunchScope ls(ctx, K_CHAIN, 4.0 * qbytes + 28.0 * nhits);
+            k_sa_smem_emit<<<dim3(T), dim3(256), 0, st>>>(d_flag, d_len, d_lo, d_hi, Q, tile_sum, static_cast<uint32_t>(nhits), static_cast<uint4 *>(d_hits));
+        }
+        DK_HIP(ctx, hipGetLastError());
+        DK_HIP(ctx, hipStreamSynchronize(st));
+    }
+    ctx->ws_release(mark);
     return DK_OK;
 }
 

@@ -145,6 +145,47 @@ public:
         for (size_t q = 0; q < patterns.size(); ++q) out.emplace_back(lo[q], hi[q]);
         return out;
     }
+    // The matching statistics of the queries against input (dk_sa_match), over the positions of the queries back to back: len[g] = the longest
+    // prefix of the window at g (at most max_len symbols, inside its query) that occurs in input, suffixes[lo[g] .. hi[g]) = where it does.
+    struct Matches { std::vector<uint32_t> len, lo, hi; };
+    Matches match(const std::vector<Symbol> &input, const std::vector<Suffix> &suffixes, const std::vector<std::vector<Symbol>> &queries, size_t max_len) {
+        if (input.size() != n_ || suffixes.size() != n_) throw Error(DK_E_ARG, "assertion failed: input.len() == self.n");
+        std::vector<size_t> lens;
+        std::vector<Symbol> bytes(1);  // (one byte so that data() is never null)
+        for (const auto &q : queries) {
+            lens.push_back(q.size());
+            bytes.insert(bytes.end(), q.begin(), q.end());
+        }
+        const size_t total = bytes.size() - 1;
+        Matches m{std::vector<uint32_t>(total + 1), std::vector<uint32_t>(total + 1), std::vector<uint32_t>(total + 1)};
+        int rc = dk_sa_match(ctx_.get(), input.data(), input.size(), suffixes.data(), bytes.data() + 1, queries.size(), lens.data(), max_len, m.len.data(),
+                             m.lo.data(), m.hi.data());
+        if (rc != DK_OK) throw Error(rc, ctx_.error());
+        m.len.resize(total);
+        m.lo.resize(total);
+        m.hi.resize(total);
+        return m;
+    }
+    // The super-maximal exact matches of at least min_len symbols (dk_sa_smems): hits = the first min(total, max_hits) records {at, len, lo, hi}
+    // in rising order of at, the offset into the queries back to back.  A copy longer than max_len is reported once, with len = max_len.
+    struct Smems { std::vector<dk_sa_smem> hits; uint64_t total = 0; };
+    Smems smems(const std::vector<Symbol> &input, const std::vector<Suffix> &suffixes, const std::vector<std::vector<Symbol>> &queries, size_t min_len,
+                size_t max_len, size_t max_hits = 65536) {
+        if (input.size() != n_ || suffixes.size() != n_) throw Error(DK_E_ARG, "assertion failed: input.len() == self.n");
+        std::vector<size_t> lens;
+        std::vector<Symbol> bytes(1);
+        for (const auto &q : queries) {
+            lens.push_back(q.size());
+            bytes.insert(bytes.end(), q.begin(), q.end());
+        }
+        Smems s;
+        s.hits.resize(std::min(max_hits, bytes.size() - 1) + 1);  // (never more records than positions)
+        int rc = dk_sa_smems(ctx_.get(), input.data(), input.size(), suffixes.data(), bytes.data() + 1, queries.size(), lens.data(), min_len, max_len,
+                             max_hits, s.hits.data(), &s.total);
+        if (rc != DK_OK) throw Error(rc, ctx_.error());
+        s.hits.resize(static_cast<size_t>(std::min<uint64_t>(s.total, max_hits)));
+        return s;
+    }
     detail::Ctx &context() { return ctx_; }  // plays reuse(): later stages share the device workspace through it
 private:
     detail::Ctx ctx_;

@@ -251,6 +251,45 @@ int dk_sa_search(dk_ctx *full_ctx, const uint8_t *in, size_t n, const uint32_t *
 int dk_dev_sa_search_packed(dk_ctx *full_ctx, const uint8_t *d_in, size_t count, const size_t *n, const uint32_t *d_sa,
                             const uint8_t *d_pat, size_t npat, const size_t *pat_len, const uint32_t *pat_block,
                             uint32_t *d_lo, uint32_t *d_hi);
+/* ---- matching statistics and super-maximal exact matches of query texts against a block (csrc/sa_query.hip) ----
+ * Which stretches of a query does the block already hold, and how long is each?  Text, suffix array and packs as for the search above; nq
+ * queries lie back to back in d_query, query j of query_len[j] bytes (HOST memory, as pat_len), for a pack matched against block query_block[j]
+ * (HOST).  Q = the sum of the lengths; a POSITION g in [0, Q) lies in query j at offset i, and its window is the m_g = min(max_len,
+ * query_len[j] - i) bytes from it on: a window never runs into the next query.
+ *   d_len[g] = the largest l <= m_g such that d_query[g, g + l) occurs in the block;
+ *   d_lo[g], d_hi[g] = what dk_dev_sa_search gives for that pattern of l bytes, local to the block (l == 0: [0, n_i)), so SA[lo, hi) are the
+ *   occurrences of the longest match and hi > lo.  d_lo and d_hi may BOTH be null: only the lengths are written.  Q entries each.
+ * A position g is reported as a super-maximal match (SMEM) when, with capped(g) meaning len[g] == max_len,
+ *   len[g] >= max(min_len, 1);   i == 0 or len[g - 1] <= len[g] (the match one byte earlier does not contain this one);   and not (i > 0 and
+ *   capped(g - 1) and capped(g)): a copy longer than max_len is reported once, at its first position, with len = max_len.
+ * Without a cap these are exactly the matches of a query that no other match of the same query contains.  The record's `at` is the position g,
+ * an offset into d_query; the caller maps it to (query, offset) through the lengths.  The first min(*total, max_hits) records are written in
+ * rising order of `at` (device records 16-byte aligned); *total (HOST, 64 bits) is complete when the list is cut; max_hits == 0 counts only
+ * and d_hits may be null.  Placement is by an exclusive scan of the flags: no atomics, the same bytes in every run, and nothing behind the
+ * last record written is touched.
+ * DK_E_ARG as for the search (nulls, n == 0, the pack checks, query_block[j] >= count, more than 2^32 - 1 query bytes, a decoder context),
+ * and for max_len == 0, exactly one of d_lo / d_hi null, records off their alignment, and what does not fit the workspace: the device forms of
+ * match take 8 bytes per query, those of smems 16 bytes per query byte more; the host forms upload text, array and queries beside that.
+ * max_len above 2^32 - 1 counts as 2^32 - 1.  nq == 0 or Q == 0 is DK_OK, writes nothing and gives *total = 0; empty queries among others
+ * are allowed.  The suffix array is TRUSTED, as in the search.  For any array: an entry >= n_i is the empty suffix and the text is not read
+ * at it, every compare stops at min(m_g, n_i - SA[slot]), every step shrinks its range; the results are then unspecified, but len[g] <= m_g
+ * and lo <= hi <= n_i, and nothing outside the text, the array, the queries and the outputs is touched. */
+typedef struct dk_sa_smem { uint32_t at, len, lo, hi; } dk_sa_smem; /* 16 bytes */
+int dk_dev_sa_match(dk_ctx *full_ctx, const uint8_t *d_in, size_t n, const uint32_t *d_sa, const uint8_t *d_query, size_t nq,
+                    const size_t *query_len, size_t max_len, uint32_t *d_len, uint32_t *d_lo, uint32_t *d_hi);
+int dk_dev_sa_match_packed(dk_ctx *full_ctx, const uint8_t *d_in, size_t count, const size_t *n, const uint32_t *d_sa, const uint8_t *d_query,
+                           size_t nq, const size_t *query_len, const uint32_t *query_block, size_t max_len,
+                           uint32_t *d_len, uint32_t *d_lo, uint32_t *d_hi);
+/* the same from and to host memory: text, array and queries are uploaded, the statistics downloaded */
+int dk_sa_match(dk_ctx *full_ctx, const uint8_t *in, size_t n, const uint32_t *sa, const uint8_t *query, size_t nq, const size_t *query_len,
+                size_t max_len, uint32_t *len, uint32_t *lo, uint32_t *hi);
+int dk_dev_sa_smems(dk_ctx *full_ctx, const uint8_t *d_in, size_t n, const uint32_t *d_sa, const uint8_t *d_query, size_t nq,
+                    const size_t *query_len, size_t min_len, size_t max_len, size_t max_hits, dk_sa_smem *d_hits, uint64_t *total);
+int dk_dev_sa_smems_packed(dk_ctx *full_ctx, const uint8_t *d_in, size_t count, const size_t *n, const uint32_t *d_sa, const uint8_t *d_query,
+                           size_t nq, const size_t *query_len, const uint32_t *query_block, size_t min_len, size_t max_len, size_t max_hits,
+                           dk_sa_smem *d_hits, uint64_t *total);
+int dk_sa_smems(dk_ctx *full_ctx, const uint8_t *in, size_t n, const uint32_t *sa, const uint8_t *query, size_t nq, const size_t *query_len,
+                size_t min_len, size_t max_len, size_t max_hits, dk_sa_smem *hits, uint64_t *total);
 /* ---- FM-index: count patterns in a BWT, without the text and without a suffix array (csrc/fm_index.hip) ----
  * Backward search on L itself.  The index is an opaque DEVICE buffer of dk_fm_index_bytes(total, count) bytes that the caller supplies (4-byte
  * aligned): checkpointed symbol counts of the pack every 1024 positions and 1040 bytes per block, about `total` bytes in all; with L itself

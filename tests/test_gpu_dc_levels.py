@@ -107,6 +107,22 @@ def pack_where(c, off, index):
         run % S.PDC_TILE // S.PDC_STEP, run // S.PDC_TILE // tpc, run // S.PDC_TILE % tpc)
 
 
+def check_pack(c, off, want, want_init, inits, ms, got, where):
+    """what a packed call returned (inits, ms) and left in the caller's arrays (got: dist, sym and, where given, rank, each over the range
+    pack_reference covers) against pack_reference's"""
+    assert ms == c["ms"], "%s: m of block %d" % (where, next(i for i in range(len(ms)) if ms[i] != c["ms"][i]))
+    got_init = np.array(inits)
+    bad = np.argwhere(got_init != want_init)
+    assert len(bad) == 0, "%s: init[%d] of block %d is %d, the oracle's %d" % (
+        where, bad[0][1], bad[0][0], got_init[bad[0][0], bad[0][1]], want_init[bad[0][0], bad[0][1]])
+    for key, g in got.items():
+        bad = np.flatnonzero(g != want[key])
+        if len(bad):
+            i = int(bad[0])
+            pytest.fail("%s: %s differs in %d entries, first at %d: got %d, want %d -- %s" % (
+                where, key, len(bad), i, int(g[i]), int(want[key][i]), pack_where(c, off, i)))
+
+
 @pytest.mark.parametrize("name", list(S.PACKS))
 def test_packed(pctx, orc, name):
     c = S.PACKS[name]()
@@ -120,20 +136,10 @@ def test_packed(pctx, orc, name):
         d_rank = torch.full((total,), GUARD8, dtype=torch.uint8, device="cuda") if with_rank else None
         inits, ms = pctx.dev_dc_encode_packed(d_bwt, sizes, d_dist, d_sym, d_rank)
         where = "pack %s, d_rank %s" % (name, "given" if with_rank else "None")
-        assert ms == c["ms"], "%s: m of block %d" % (where, next(i for i in range(len(ms)) if ms[i] != c["ms"][i]))
-        got_init = np.array(inits)
-        bad = np.argwhere(got_init != want_init)
-        assert len(bad) == 0, "%s: init[%d] of block %d is %d, the oracle's %d" % (
-            where, bad[0][1], bad[0][0], got_init[bad[0][0], bad[0][1]], want_init[bad[0][0], bad[0][1]])
         got = dict(dist=d_dist.cpu().numpy().view(np.uint32), sym=d_sym.cpu().numpy())
         if with_rank:
             got["rank"] = d_rank.cpu().numpy()
-        for key, g in got.items():
-            bad = np.flatnonzero(g != want[key])
-            if len(bad):
-                i = int(bad[0])
-                pytest.fail("%s: %s differs in %d entries, first at %d: got %d, want %d -- %s" % (
-                    where, key, len(bad), i, int(g[i]), int(want[key][i]), pack_where(c, off, i)))
+        check_pack(c, off, want, want_init, inits, ms, got, where)
 
 
 def oracle_stream(orc, model, t):

@@ -18,8 +18,6 @@ struct ScopedCall {
     ~ScopedCall() { if (c->profiling) c->prof_collect(); }
 };
 
-inline size_t ws_round(size_t bytes) { return (bytes + 255) & ~size_t(255); }  // what one ws_alloc of `bytes` takes
-
 inline int check_n(dk_ctx *ctx, size_t n) {
     if (n == 0) return ctx->fail(DK_E_ARG, "empty block (the reference panics at src/saca.rs:107)");
     if (n > ctx->max_n) return ctx->fail(DK_E_ARG, "block of %zu bytes exceeds the context capacity %zu", n, ctx->max_n);
@@ -32,6 +30,7 @@ inline int check_n(dk_ctx *ctx, size_t n) {
 // included.  So no such copy outlives its source, whatever fails behind it.
 // Where it stands: it owns nothing, so it is declared LAST among the host arrays of its scope (behind the Layout, the Patterns, the plan): it is
 // then destroyed, and has waited, before they are.  A helper that takes the guard by reference uploads only what its caller declared in front.
+// The views of context.hpp (PackView, FmView, ItemView) are filled through the guard, so they too are declared behind it.
 struct Upload {
     dk_ctx *c;
     bool pending = false;
@@ -115,13 +114,16 @@ public:
         uint32_t *d = up.c->ws_alloc<uint32_t>(2);
         return d && up.fill(d, 0) == DK_OK && up.fill(d + 1, off_[1]) == DK_OK ? d : nullptr;
     }
-    // the offsets and the anchor bases of the extract structure (fm_extract_bases) in one array of 2 count + 1 words:
-    // d_geo[0 .. count] = the offsets, d_geo + count + 1 = the base of every block
-    uint32_t *device_with_bases(Upload &up, uint32_t step) {
+    // the pack of `bytes` (text or L) as the query stages take it: device() beside the sizes.  view.d_off null: up.failed()
+    PackView view(Upload &up, const uint8_t *bytes) const { return PackView{bytes, device(up), count_, total()}; }
+    // the same for the stages that read fm.ext: the offsets and the anchor bases of the extract structure (fm_extract_bases, at fm.step) in one
+    // array of 2 count + 1 words, fm.L.d_off = its first count + 1, fm.d_abase = the rest.  fm.L.d_off null: up.failed()
+    void device_with_bases(Upload &up, FmView &fm) {
         geo_ = off_;
-        const std::vector<uint32_t> abase = fm_extract_bases(off_, step);
+        const std::vector<uint32_t> abase = fm_extract_bases(off_, fm.step);
         geo_.insert(geo_.end(), abase.begin(), abase.end() - 1);
-        return up.stage(geo_.data(), geo_.size(), "block offsets and anchor bases");
+        fm.L.d_off = up.stage(geo_.data(), geo_.size(), "block offsets and anchor bases");
+        fm.d_abase = fm.L.d_off ? fm.L.d_off + count_ + 1 : nullptr;
     }
 };
 

@@ -60,6 +60,13 @@ struct Patterns {
     size_t longest = 0, shortest = ~size_t(0);
     size_t count() const { return off.size() - 1; }
     size_t bytes() const { return off.back(); }
+    // the batch as the stages take it, d_bytes the items' bytes on the device: the offsets and, where the items name blocks, these go to the
+    // workspace (8 bytes per item).  view.d_off null: up.failed()
+    ItemView view(Upload &up, const uint8_t *d_bytes, const uint32_t *block = nullptr, const char *blocks_are = "pattern blocks") const {
+        ItemView v{d_bytes, up.stage(off.data(), off.size(), "pattern offsets"), nullptr, count(), bytes(), longest, shortest};
+        if (block && !(v.d_blk = up.stage(block, count(), blocks_are))) v.d_off = nullptr;
+        return v;
+    }
 };
 int check_patterns(dk_ctx *ctx, size_t npat, const size_t *pat_len, const uint32_t *pat_block, size_t count, Patterns &p) {
     if (!pat_len) return ctx->fail(DK_E_ARG, "null pointer");
@@ -76,21 +83,20 @@ int check_patterns(dk_ctx *ctx, size_t npat, const size_t *pat_len, const uint32
     }
     return DK_OK;
 }
-uint32_t *upload_offsets(Upload &up, const Patterns &p) { return up.stage(p.off.data(), p.off.size(), "pattern offsets"); }
 
 // The *_run helpers below upload through their caller's guard and run their stage; none of them adds a wait for the stream of its own.  Their
 // callers wait, once, behind whatever else they enqueue (sa_check_device has handed its words to the host: nothing is left to wait for).
 int lcp_run(Upload &up, const Layout &lay, const uint8_t *d_text, const uint32_t *d_sa, uint32_t *d_lcp) {
-    const uint32_t *d_off = lay.device(up);
-    return d_off ? lcp_device(up.c, d_text, d_off, lay.count(), lay.total(), d_sa, d_lcp) : up.failed();
+    const PackView text = lay.view(up, d_text);
+    return text.d_off ? lcp_device(up.c, text, d_sa, d_lcp) : up.failed();
 }
 // the three words of every block (sa_check_device) -> the first kind that failed and where; where = n_i for a block that is in order
 int sa_check_run(Upload &up, const Layout &lay, const uint8_t *d_text, const uint32_t *d_sa, uint32_t *verdict, uint32_t *where) {
     const std::vector<uint32_t> &off = lay.off();
-    const uint32_t *d_off = lay.device(up);
-    if (!d_off) return up.failed();
+    const PackView text = lay.view(up, d_text);
+    if (!text.d_off) return up.failed();
     std::vector<uint32_t> words(3 * lay.count());
-    DK_TRY(sa_check_device(up.c, d_text, d_off, lay.count(), lay.total(), d_sa, words.data()));
+    DK_TRY(sa_check_device(up.c, text, d_sa, words.data()));
     up.synchronised();  // (`words` has arrived)
     for (size_t i = 0; i < lay.count(); ++i) {
         const uint32_t *w = &words[3 * i];
@@ -99,19 +105,6 @@ int sa_check_run(Upload &up, const Layout &lay, const uint8_t *d_text, const uin
         where[i] = kind == DK_SA_OK ? off[i + 1] - off[i] : w[kind - 1];
     }
     return DK_OK;
-}
-// d_off: from lay.device(), null where that failed.  The patterns' offsets and, in a pack, their blocks go to the workspace (8 bytes per pattern).
-int sa_search_run(Upload &up, const uint8_t *d_text, const uint32_t *d_off, const uint32_t *d_sa, const uint8_t *d_pat, const Patterns &p,
-                  const uint32_t *pat_block, uint32_t *d_lo, uint32_t *d_hi) {
-    const uint32_t *d_pat_off = upload_offsets(up, p), *d_pat_blk = pat_block ? up.stage(pat_block, p.count(), "pattern blocks") : nullptr;
-    if (!d_off || !d_pat_off || (pat_block && !d_pat_blk)) return up.failed();
-    return sa_search_device(up.c, d_text, d_off, d_sa, d_pat, d_pat_off, d_pat_blk, p.count(), p.longest, p.shortest, d_lo, d_hi);
-}
-int fm_count_run(Upload &up, const uint8_t *d_bwt, const uint32_t *d_off, const Layout &lay, const void *d_index, const uint8_t *d_pat,
-                 const Patterns &p, const uint32_t *pat_block, uint32_t *d_lo, uint32_t *d_hi) {
-    const uint32_t *d_pat_off = upload_offsets(up, p), *d_pat_blk = pat_block ? up.stage(pat_block, p.count(), "pattern blocks") : nullptr;
-    if (!d_off || !d_pat_off || (pat_block && !d_pat_blk)) return up.failed();
-    return fm_count_device(up.c, d_bwt, d_off, lay.count(), lay.total(), d_index, d_pat, d_pat_off, d_pat_blk, p.count(), p.bytes(), d_lo, d_hi);
 }
 
 // ---- LCP arrays (csrc/lcp.hip) ----------------------------------------------------------------------
@@ -192,12 +185,12 @@ int dk_dev_suffix_array_packed_lcp(dk_ctx *ctx, const uint8_t *d_in, size_t coun
     DK_TRY(lay.check(ctx));
     Upload up(ctx);
     Timer t;
-    const uint32_t *d_off = lay.device(up);
+    const PackView text = lay.view(up, d_in);
     uint32_t *d_phi = ctx->ws_alloc<uint32_t>(lay.total());
-    if (!d_off || !d_phi) return up.failed();
+    if (!text.d_off || !d_phi) return up.failed();
     std::vector<std::pair<size_t, uint32_t>> fixed;
-    DK_TRY(packed_forward(ctx, d_in, lay.off(), d_off, nullptr, nullptr, &fixed, d_sa_out, d_phi));
-    DK_TRY(lcp_device(ctx, d_in, d_off, count, lay.total(), d_sa_out, d_lcp_out, d_phi));
+    DK_TRY(packed_forward(ctx, d_in, lay.off(), text.d_off, nullptr, nullptr, &fixed, d_sa_out, d_phi));
+    DK_TRY(lcp_device(ctx, text, d_sa_out, d_lcp_out, d_phi));
     DK_TRY(up.sync());
     ctx->stats.ms_total = t.ms();
     return DK_OK;
@@ -215,15 +208,15 @@ int dk_suffix_array_packed_lcp(dk_ctx *ctx, const uint8_t *in, size_t count, con
     const size_t total = lay.total();
     uint8_t *d_text = up.stage(in, total, "text");
     uint32_t *d_sa = ctx->ws_alloc<uint32_t>(total), *d_phi = ctx->ws_alloc<uint32_t>(total);
-    const uint32_t *d_off = lay.device(up);
-    if (!d_text || !d_sa || !d_phi || !d_off) return up.failed();
+    const PackView text = lay.view(up, d_text);
+    if (!d_text || !d_sa || !d_phi || !text.d_off) return up.failed();
     std::vector<std::pair<size_t, uint32_t>> fixed;
-    DK_TRY(packed_forward(ctx, d_text, lay.off(), d_off, nullptr, nullptr, &fixed, d_sa, d_phi));
+    DK_TRY(packed_forward(ctx, d_text, lay.off(), text.d_off, nullptr, nullptr, &fixed, d_sa, d_phi));
     // (after the sort and its guard: text, SA and Phi are 9 total, and a guarded block's sort 63.4 n_i with n_i <= 2^24 -- the constant term covers
     //  the 2.8 n_i by which a pack that is one such block would pass 69.6 total)
     uint32_t *d_lcp = ctx->ws_alloc<uint32_t>(total);
     if (!d_lcp) return DK_E_NOMEM;
-    DK_TRY(lcp_device(ctx, d_text, d_off, count, total, d_sa, d_lcp, d_phi));
+    DK_TRY(lcp_device(ctx, text, d_sa, d_lcp, d_phi));
     DK_HIP(ctx, hipMemcpyAsync(sa_out, d_sa, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     DK_HIP(ctx, hipMemcpyAsync(lcp_out, d_lcp, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     DK_TRY(up.sync());
@@ -259,7 +252,10 @@ int dev_sa_search(dk_ctx *ctx, const char *entry, const uint8_t *d_in, Layout &&
     DK_TRY(check_patterns(ctx, npat, pat_len, pat_block, lay.count(), p));
     if ((!d_pat && p.bytes()) || !d_lo || !d_hi) return ctx->fail(DK_E_ARG, "null pointer");
     Upload up(ctx);
-    DK_TRY(sa_search_run(up, d_in, lay.device(up), d_sa, d_pat, p, pat_block, d_lo, d_hi));
+    const PackView text = lay.view(up, d_in);
+    const ItemView pats = p.view(up, d_pat, pat_block);
+    if (!text.d_off || !pats.d_off) return up.failed();
+    DK_TRY(sa_search_device(ctx, text, d_sa, pats, d_lo, d_hi));
     DK_TRY(up.sync());
     ctx->stats.ms_total = t.ms();
     return DK_OK;
@@ -321,7 +317,10 @@ int dk_sa_search(dk_ctx *ctx, const uint8_t *in, size_t n, const uint32_t *sa, c
     const uint32_t *d_sa = up.stage(sa, n, "suffix array");
     uint32_t *d_lo = ctx->ws_alloc<uint32_t>(npat), *d_hi = ctx->ws_alloc<uint32_t>(npat);
     if (!d_text || !d_pat || !d_sa || !d_lo || !d_hi) return up.failed();
-    DK_TRY(sa_search_run(up, d_text, lay.device(up), d_sa, d_pat, p, nullptr, d_lo, d_hi));
+    const PackView text = lay.view(up, d_text);
+    const ItemView pats = p.view(up, d_pat);
+    if (!text.d_off || !pats.d_off) return up.failed();
+    DK_TRY(sa_search_device(ctx, text, d_sa, pats, d_lo, d_hi));
     DK_HIP(ctx, hipMemcpyAsync(lo, d_lo, npat * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     DK_HIP(ctx, hipMemcpyAsync(hi, d_hi, npat * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     DK_TRY(up.sync());
@@ -333,13 +332,6 @@ int dk_sa_search(dk_ctx *ctx, const uint8_t *in, size_t n, const uint32_t *sa, c
 }  // extern "C"
 
 namespace {
-// the queries of a call on the device: their offsets and, in a pack, their blocks (8 bytes per query)
-struct Queries { const uint32_t *d_off = nullptr, *d_blk = nullptr; };
-int upload_queries(Upload &up, const Patterns &p, const uint32_t *query_block, const uint32_t *d_off, Queries &q) {
-    q.d_off = upload_offsets(up, p);
-    q.d_blk = query_block ? up.stage(query_block, p.count(), "query blocks") : nullptr;
-    return d_off && q.d_off && (!query_block || q.d_blk) ? DK_OK : up.failed();
-}
 // what the two device entries check in front of the queries themselves
 int check_match_call(dk_ctx *ctx, const uint8_t *d_in, Layout &lay, const uint32_t *d_sa, size_t max_len) {
     if (!d_in || lay.null() || !d_sa) return ctx->fail(DK_E_ARG, "null pointer");
@@ -365,10 +357,10 @@ int dev_sa_match(dk_ctx *ctx, const char *entry, const uint8_t *d_in, Layout &&l
     if (p.bytes() == 0) return DK_OK;
     DK_TRY(check_match_outputs(ctx, d_query, d_len, d_lo, d_hi));
     Upload up(ctx);
-    const uint32_t *d_off = lay.device(up);
-    Queries q;
-    DK_TRY(upload_queries(up, p, query_block, d_off, q));
-    DK_TRY(sa_match_device(ctx, d_in, d_off, d_sa, d_query, q.d_off, q.d_blk, nq, p.bytes(), max_len, d_len, d_lo, d_hi));
+    const PackView text = lay.view(up, d_in);
+    const ItemView qry = p.view(up, d_query, query_block, "query blocks");
+    if (!text.d_off || !qry.d_off) return up.failed();
+    DK_TRY(sa_match_device(ctx, text, d_sa, qry, max_len, d_len, d_lo, d_hi));
     DK_TRY(up.sync());
     ctx->stats.ms_total = t.ms();
     return DK_OK;
@@ -397,10 +389,10 @@ int dev_sa_smems(dk_ctx *ctx, const char *entry, const uint8_t *d_in, Layout &&l
     if (ws_round(4 * (lay.count() + 1)) + ws_round(4 * (nq + 1)) + (query_block ? ws_round(4 * nq) : 0) + sa_smems_workspace(p.bytes()) > ctx->ws_size)
         return ctx->fail(DK_E_ARG, "%zu queries of %zu bytes do not fit the workspace (16 bytes per query byte)", nq, p.bytes());
     Upload up(ctx);
-    const uint32_t *d_off = lay.device(up);
-    Queries q;
-    DK_TRY(upload_queries(up, p, query_block, d_off, q));
-    DK_TRY(sa_smems_device(ctx, d_in, d_off, d_sa, d_query, q.d_off, q.d_blk, nq, p.bytes(), min_len, max_len, max_hits, d_hits, total));
+    const PackView text = lay.view(up, d_in);
+    const ItemView qry = p.view(up, d_query, query_block, "query blocks");
+    if (!text.d_off || !qry.d_off) return up.failed();
+    DK_TRY(sa_smems_device(ctx, text, d_sa, qry, min_len, max_len, HitSink{max_hits, d_hits, nullptr, total}));
     DK_TRY(up.sync());
     ctx->stats.ms_total = t.ms();
     return DK_OK;
@@ -450,10 +442,10 @@ int dk_sa_match(dk_ctx *ctx, const uint8_t *in, size_t n, const uint32_t *sa, co
     const uint32_t *d_sa = up.stage(sa, n, "suffix array");
     uint32_t *d_len = ctx->ws_alloc<uint32_t>(Q), *d_lo = lo ? ctx->ws_alloc<uint32_t>(Q) : nullptr, *d_hi = lo ? ctx->ws_alloc<uint32_t>(Q) : nullptr;
     if (!d_text || !d_query || !d_sa || !d_len || (lo && (!d_lo || !d_hi))) return up.failed();
-    const uint32_t *d_off = lay.device(up);
-    Queries q;
-    DK_TRY(upload_queries(up, p, nullptr, d_off, q));
-    DK_TRY(sa_match_device(ctx, d_text, d_off, d_sa, d_query, q.d_off, nullptr, nq, Q, max_len, d_len, d_lo, d_hi));
+    const PackView text = lay.view(up, d_text);
+    const ItemView qry = p.view(up, d_query);
+    if (!text.d_off || !qry.d_off) return up.failed();
+    DK_TRY(sa_match_device(ctx, text, d_sa, qry, max_len, d_len, d_lo, d_hi));
     DK_HIP(ctx, hipMemcpyAsync(len, d_len, Q * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     if (lo) {
         DK_HIP(ctx, hipMemcpyAsync(lo, d_lo, Q * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -489,10 +481,10 @@ int dk_sa_smems(dk_ctx *ctx, const uint8_t *in, size_t n, const uint32_t *sa, co
     const uint32_t *d_sa = up.stage(sa, n, "suffix array");
     dk_sa_smem *d_hits = cap ? ctx->ws_alloc<dk_sa_smem>(cap) : nullptr;
     if (!d_text || !d_query || !d_sa || (cap && !d_hits)) return up.failed();
-    const uint32_t *d_off = lay.device(up);
-    Queries q;
-    DK_TRY(upload_queries(up, p, nullptr, d_off, q));
-    DK_TRY(sa_smems_device(ctx, d_text, d_off, d_sa, d_query, q.d_off, nullptr, nq, Q, min_len, max_len, cap, d_hits, total));
+    const PackView text = lay.view(up, d_text);
+    const ItemView qry = p.view(up, d_query);
+    if (!text.d_off || !qry.d_off) return up.failed();
+    DK_TRY(sa_smems_device(ctx, text, d_sa, qry, min_len, max_len, HitSink{cap, d_hits, nullptr, total}));
     const size_t nhits = static_cast<size_t>(std::min<uint64_t>(*total, cap));
     if (nhits) DK_HIP(ctx, hipMemcpyAsync(hits, d_hits, nhits * sizeof(dk_sa_smem), hipMemcpyDeviceToHost, ctx->stream));
     DK_TRY(up.sync());
@@ -504,6 +496,21 @@ int dk_sa_smems(dk_ctx *ctx, const uint8_t *in, size_t n, const uint32_t *sa, co
 }  // extern "C"
 
 namespace {
+// What the host-pointer forms (dk_fm_count, _locate, _extract, _find) share: the block's L staged, its index allocated and built, beside it the
+// sampled structure asked for, the block's two offsets -> fm.  The builds take their workspace on top of what the caller holds by then.
+enum Sampled { JUST_INDEX, WITH_LOCATE, WITH_EXTRACT };
+int host_fm(Upload &up, const Layout &lay, const uint8_t *bwt, uint32_t origin, uint32_t step, Sampled sampled, FmView &fm) {
+    const size_t n = lay.total();
+    uint32_t *d_index = up.c->ws_alloc<uint32_t>(fm_index_words(n, 1));
+    uint32_t *d_loc = sampled == WITH_LOCATE ? up.c->ws_alloc<uint32_t>(fm_locate_words(n, 1, step)) : nullptr;
+    uint32_t *d_ext = sampled == WITH_EXTRACT ? up.c->ws_alloc<uint32_t>(fm_extract_words(n, 1, step)) : nullptr;
+    fm = FmView{lay.view(up, up.stage(bwt, n, "L")), d_index, d_loc, d_ext, step};
+    if (!fm.L.bytes || !fm.L.d_off || !d_index || (sampled == WITH_LOCATE && !d_loc) || (sampled == WITH_EXTRACT && !d_ext)) return up.failed();
+    DK_TRY(fm_build_device(up.c, fm.L.bytes, lay.off(), &origin, d_index));
+    if (d_loc) DK_TRY(fm_locate_build_device(up.c, fm.L.bytes, lay.off(), &origin, step, d_loc, false));
+    if (d_ext) DK_TRY(fm_extract_build_device(up.c, fm.L.bytes, lay.off(), &origin, step, d_ext, false));
+    return DK_OK;
+}
 int dev_fm_build(dk_ctx *ctx, const uint8_t *d_bwt, Layout &&lay, const uint32_t *origin, void *d_index) {
     DK_TRY(begin_call(ctx));
     ScopedCall sc(ctx);
@@ -530,7 +537,10 @@ int dev_fm_count(dk_ctx *ctx, const uint8_t *d_bwt, Layout &&lay, const void *d_
     DK_TRY(check_patterns(ctx, npat, pat_len, pat_block, lay.count(), p));
     if ((!d_pat && p.bytes()) || !d_lo || !d_hi) return ctx->fail(DK_E_ARG, "null pointer");
     Upload up(ctx);
-    DK_TRY(fm_count_run(up, d_bwt, lay.device(up), lay, d_index, d_pat, p, pat_block, d_lo, d_hi));
+    const FmView fm{lay.view(up, d_bwt), d_index};
+    const ItemView pats = p.view(up, d_pat, pat_block);
+    if (!fm.L.d_off || !pats.d_off) return up.failed();
+    DK_TRY(fm_count_device(ctx, fm, pats, d_lo, d_hi));
     DK_TRY(up.sync());
     ctx->stats.ms_total = t.ms();
     return DK_OK;
@@ -579,12 +589,14 @@ int dk_fm_count(dk_ctx *ctx, const uint8_t *bwt, size_t n, uint32_t origin, cons
     if (need > ctx->ws_size) return ctx->fail(DK_E_ARG, "%zu patterns of %zu bytes and their offsets do not fit the workspace beside L and its index", npat, p.bytes());
     Upload up(ctx);
     hipStream_t st = ctx->stream;
-    const uint8_t *d_bwt = up.stage(bwt, n, "L"), *d_pat = up.stage(pat, p.bytes(), "patterns");
-    uint32_t *d_index = ctx->ws_alloc<uint32_t>(index_words), *d_lo = ctx->ws_alloc<uint32_t>(npat), *d_hi = ctx->ws_alloc<uint32_t>(npat);
-    const uint32_t *d_off = lay.device(up);
-    if (!d_bwt || !d_pat || !d_index || !d_lo || !d_hi || !d_off) return up.failed();
-    DK_TRY(fm_build_device(ctx, d_bwt, lay.off(), &origin, d_index));
-    DK_TRY(fm_count_run(up, d_bwt, d_off, lay, d_index, d_pat, p, nullptr, d_lo, d_hi));
+    const uint8_t *d_pat = up.stage(pat, p.bytes(), "patterns");
+    uint32_t *d_lo = ctx->ws_alloc<uint32_t>(npat), *d_hi = ctx->ws_alloc<uint32_t>(npat);
+    if (!d_pat || !d_lo || !d_hi) return up.failed();
+    FmView fm;
+    DK_TRY(host_fm(up, lay, bwt, origin, 0, JUST_INDEX, fm));
+    const ItemView pats = p.view(up, d_pat);
+    if (!pats.d_off) return up.failed();
+    DK_TRY(fm_count_device(ctx, fm, pats, d_lo, d_hi));
     DK_HIP(ctx, hipMemcpyAsync(lo, d_lo, npat * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     DK_HIP(ctx, hipMemcpyAsync(hi, d_hi, npat * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     DK_TRY(up.sync());
@@ -627,9 +639,10 @@ int dev_fm_locate(dk_ctx *ctx, const uint8_t *d_bwt, Layout &&lay, const void *d
     if (lay.packed()) DK_TRY(check_blocks(ctx, pat_block, npat, lay.count(), "pattern"));
     Upload up(ctx);
     Timer t;
-    const uint32_t *d_off = lay.device(up), *d_blk = lay.packed() ? up.stage(pat_block, npat, "pattern blocks") : nullptr;
-    if (!d_off || (lay.packed() && !d_blk)) return up.failed();
-    DK_TRY(fm_locate_device(ctx, d_bwt, d_off, lay.count(), lay.total(), d_index, d_loc, step, d_lo, d_hi, d_blk, npat, max_hits, d_pos));
+    const FmView fm{lay.view(up, d_bwt), d_index, d_loc, nullptr, step};
+    const uint32_t *d_blk = lay.packed() ? up.stage(pat_block, npat, "pattern blocks") : nullptr;
+    if (!fm.L.d_off || (lay.packed() && !d_blk)) return up.failed();
+    DK_TRY(fm_locate_device(ctx, fm, d_lo, d_hi, d_blk, npat, max_hits, d_pos));
     DK_TRY(up.sync());
     ctx->stats.ms_total = t.ms();
     return DK_OK;
@@ -651,11 +664,11 @@ int dev_fm_extract(dk_ctx *ctx, const uint8_t *d_bwt, Layout &&lay, const void *
     Upload up(ctx);
     Timer t;
     // a pack: the offsets and the anchor bases in one array; a single block has the base 0 and needs none
-    const uint32_t *d_off = lay.packed() ? lay.device_with_bases(up, step) : lay.device(up);
+    FmView fm{lay.packed() ? PackView{d_bwt, nullptr, lay.count(), lay.total()} : lay.view(up, d_bwt), d_index, nullptr, d_ext, step};
+    if (lay.packed()) lay.device_with_bases(up, fm);
     const uint32_t *d_blk = lay.packed() ? up.stage(range_block, nrange, "range blocks") : nullptr;
-    if (!d_off || (lay.packed() && !d_blk)) return up.failed();
-    DK_TRY(fm_extract_device(ctx, d_bwt, d_off, lay.packed() ? d_off + lay.count() + 1 : nullptr, lay.count(), lay.total(), d_index, d_ext, step, d_pos,
-                             d_len, d_blk, nrange, max_len, d_out));
+    if (!fm.L.d_off || (lay.packed() && !d_blk)) return up.failed();
+    DK_TRY(fm_extract_device(ctx, fm, d_pos, d_len, d_blk, nrange, max_len, d_out));
     DK_TRY(up.sync());
     ctx->stats.ms_total = t.ms();
     return DK_OK;
@@ -720,15 +733,15 @@ int dk_fm_locate(dk_ctx *ctx, const uint8_t *bwt, size_t n, uint32_t origin, uin
                          npat, p.bytes(), max_hits);
     Upload up(ctx);
     hipStream_t st = ctx->stream;
-    const uint8_t *d_bwt = up.stage(bwt, n, "L"), *d_pat = up.stage(pat, p.bytes(), "patterns");
-    uint32_t *d_index = ctx->ws_alloc<uint32_t>(index_words), *d_loc = ctx->ws_alloc<uint32_t>(loc_words);
+    const uint8_t *d_pat = up.stage(pat, p.bytes(), "patterns");
     uint32_t *d_lo = ctx->ws_alloc<uint32_t>(npat), *d_hi = ctx->ws_alloc<uint32_t>(npat), *d_pos = ctx->ws_alloc<uint32_t>(nitems);
-    const uint32_t *d_off = lay.device(up);
-    if (!d_bwt || !d_pat || !d_index || !d_loc || !d_lo || !d_hi || !d_pos || !d_off) return up.failed();
-    DK_TRY(fm_build_device(ctx, d_bwt, lay.off(), &origin, d_index));
-    DK_TRY(fm_locate_build_device(ctx, d_bwt, lay.off(), &origin, step, d_loc, false));
-    DK_TRY(fm_count_run(up, d_bwt, d_off, lay, d_index, d_pat, p, nullptr, d_lo, d_hi));
-    DK_TRY(fm_locate_device(ctx, d_bwt, d_off, 1, n, d_index, d_loc, step, d_lo, d_hi, nullptr, npat, max_hits, d_pos));
+    if (!d_pat || !d_lo || !d_hi || !d_pos) return up.failed();
+    FmView fm;
+    DK_TRY(host_fm(up, lay, bwt, origin, step, WITH_LOCATE, fm));
+    const ItemView pats = p.view(up, d_pat);
+    if (!pats.d_off) return up.failed();
+    DK_TRY(fm_count_device(ctx, fm, pats, d_lo, d_hi));
+    DK_TRY(fm_locate_device(ctx, fm, d_lo, d_hi, nullptr, npat, max_hits, d_pos));
     DK_HIP(ctx, hipMemcpyAsync(lo, d_lo, npat * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     DK_HIP(ctx, hipMemcpyAsync(hi, d_hi, npat * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     DK_HIP(ctx, hipMemcpyAsync(pos, d_pos, nitems * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -767,17 +780,14 @@ int dk_fm_extract(dk_ctx *ctx, const uint8_t *bwt, size_t n, uint32_t origin, ui
     if (need > ctx->ws_size)
         return ctx->fail(DK_E_ARG, "%zu ranges of at most %zu bytes do not fit the workspace beside L, its index and the extract build", nrange, max_len);
     Upload up(ctx);
-    const uint8_t *d_bwt = up.stage(bwt, n, "L");
     uint8_t *d_out = ctx->ws_alloc<uint8_t>(nbytes);
-    uint32_t *d_index = ctx->ws_alloc<uint32_t>(index_words), *d_ext = ctx->ws_alloc<uint32_t>(ext_words);
     const uint32_t *d_pos = up.stage(pos, nrange, "positions");
     uint32_t *d_len = ctx->ws_alloc<uint32_t>(nrange);
-    const uint32_t *d_off = lay.device(up);
-    if (!d_bwt || !d_out || !d_index || !d_ext || !d_pos || !d_len || !d_off) return up.failed();
+    if (!d_out || !d_pos || !d_len) return up.failed();
     if (len) DK_TRY(up.copy(d_len, len, nrange * sizeof(uint32_t), "lengths"));
-    DK_TRY(fm_build_device(ctx, d_bwt, lay.off(), &origin, d_index));
-    DK_TRY(fm_extract_build_device(ctx, d_bwt, lay.off(), &origin, step, d_ext, false));
-    DK_TRY(fm_extract_device(ctx, d_bwt, d_off, nullptr, 1, n, d_index, d_ext, step, d_pos, len ? d_len : nullptr, nullptr, nrange, max_len, d_out));
+    FmView fm;
+    DK_TRY(host_fm(up, lay, bwt, origin, step, WITH_EXTRACT, fm));
+    DK_TRY(fm_extract_device(ctx, fm, d_pos, len ? d_len : nullptr, nullptr, nrange, max_len, d_out));
     DK_HIP(ctx, hipMemcpyAsync(out, d_out, nbytes, hipMemcpyDeviceToHost, ctx->stream));
     DK_TRY(up.sync());
     ctx->stats.ms_total = t.ms();
@@ -788,19 +798,24 @@ int dk_fm_extract(dk_ctx *ctx, const uint8_t *bwt, size_t n, uint32_t origin, ui
 }  // extern "C"
 
 namespace {
+// what dk_dev_fm_find* and dk_dev_fm_near* check in front of the patterns themselves
+int check_find_call(dk_ctx *ctx, const uint8_t *d_bwt, Layout &lay, const void *d_index, const void *d_loc, uint32_t step, size_t npat, const HitSink &out) {
+    if (!d_bwt || lay.null() || !d_index || (out.max_hits && !d_loc)) return ctx->fail(DK_E_ARG, "null pointer");
+    DK_TRY(check_index(ctx, d_index));
+    DK_TRY(lay.check(ctx));
+    if (!out.total_out) return ctx->fail(DK_E_ARG, "null pointer");
+    DK_TRY(check_step(ctx, step));
+    DK_TRY(check_records(ctx, npat, lay.count(), "%zu patterns in %zu blocks: more than DK_FM_FIND_MAX_PAIRS pairs", out.max_hits, out.d_hits, 16));
+    if (out.max_hits) DK_TRY(check_aligned(ctx, addr(d_loc), 4, LOCATE_IS));
+    return check_aligned(ctx, addr(out.d_occ), 4, "the occurrence matrix is");
+}
 int dev_fm_find(dk_ctx *ctx, const uint8_t *d_bwt, Layout &&lay, const void *d_index, const void *d_loc, uint32_t step, const uint8_t *d_pat, size_t npat,
                 const size_t *pat_len, size_t max_hits, dk_fm_hit *d_hits, uint32_t *d_occ, uint64_t *total) {
     DK_TRY(begin_call(ctx));
     ScopedCall sc(ctx);
-    if (!d_bwt || lay.null() || !d_index || (max_hits && !d_loc)) return ctx->fail(DK_E_ARG, "null pointer");
-    DK_TRY(check_index(ctx, d_index));
-    DK_TRY(lay.check(ctx));
+    const HitSink out{max_hits, d_hits, d_occ, total};
+    DK_TRY(check_find_call(ctx, d_bwt, lay, d_index, d_loc, step, npat, out));
     const size_t count = lay.count();
-    if (!total) return ctx->fail(DK_E_ARG, "null pointer");
-    DK_TRY(check_step(ctx, step));
-    DK_TRY(check_records(ctx, npat, count, "%zu patterns in %zu blocks: more than DK_FM_FIND_MAX_PAIRS pairs", max_hits, d_hits, 16));
-    if (max_hits) DK_TRY(check_aligned(ctx, addr(d_loc), 4, LOCATE_IS));
-    DK_TRY(check_aligned(ctx, addr(d_occ), 4, "the occurrence matrix is"));
     if (npat == 0) {
         *total = 0;
         return DK_OK;
@@ -814,9 +829,10 @@ int dev_fm_find(dk_ctx *ctx, const uint8_t *d_bwt, Layout &&lay, const void *d_i
         return ctx->fail(DK_E_ARG, "%zu patterns do not fit the workspace (16 bytes per pair)", npat);
     }
     Upload up(ctx);
-    const uint32_t *d_off = lay.device(up), *d_pat_off = upload_offsets(up, p);
-    if (!d_off || !d_pat_off) return up.failed();
-    DK_TRY(fm_find_device(ctx, d_bwt, d_off, count, lay.total(), d_index, d_loc, step, d_pat, d_pat_off, npat, p.bytes(), max_hits, d_hits, d_occ, total));
+    const FmView fm{lay.view(up, d_bwt), d_index, d_loc, nullptr, step};
+    const ItemView pats = p.view(up, d_pat);
+    if (!fm.L.d_off || !pats.d_off) return up.failed();
+    DK_TRY(fm_find_device(ctx, fm, pats, out));
     DK_TRY(up.sync());
     ctx->stats.ms_total = t.ms();
     return DK_OK;
@@ -863,22 +879,21 @@ int dk_fm_find(dk_ctx *ctx, const uint8_t *bwt, size_t n, uint32_t origin, uint3
         return ctx->fail(DK_E_ARG, "%zu patterns of %zu bytes do not fit the workspace beside L, its index and the locate build", npat, p.bytes());
     Upload up(ctx);
     hipStream_t st = ctx->stream;
-    const uint8_t *d_bwt = up.stage(bwt, n, "L"), *d_pat = up.stage(pat, p.bytes(), "patterns");
-    uint32_t *d_index = ctx->ws_alloc<uint32_t>(index_words), *d_loc = max_hits ? ctx->ws_alloc<uint32_t>(loc_words) : nullptr;
+    const uint8_t *d_pat = up.stage(pat, p.bytes(), "patterns");
     uint32_t *d_occ = ctx->ws_alloc<uint32_t>(npat);
-    const uint32_t *d_pat_off = upload_offsets(up, p), *d_off = lay.device(up);
-    if (!d_bwt || !d_pat || !d_index || (max_hits && !d_loc) || !d_occ || !d_pat_off || !d_off) return up.failed();
-    DK_TRY(fm_build_device(ctx, d_bwt, lay.off(), &origin, d_index));
-    if (max_hits) DK_TRY(fm_locate_build_device(ctx, d_bwt, lay.off(), &origin, step, d_loc, false));
+    const ItemView pats = p.view(up, d_pat);
+    if (!d_pat || !d_occ || !pats.d_off) return up.failed();
+    FmView fm;
+    DK_TRY(host_fm(up, lay, bwt, origin, step, max_hits ? WITH_LOCATE : JUST_INDEX, fm));
     // the count and the scan alone first: how many records there are decides what the records take
-    DK_TRY(fm_find_device(ctx, d_bwt, d_off, 1, n, d_index, nullptr, step, d_pat, d_pat_off, npat, p.bytes(), 0, nullptr, d_occ, total));
+    DK_TRY(fm_find_device(ctx, fm, pats, HitSink{0, nullptr, d_occ, total}));
     const size_t nhits = static_cast<size_t>(std::min<uint64_t>(*total, max_hits));
     if (nhits) {
         if (ctx->ws_used + ws_round(16 * nhits) + fm_find_workspace(npat) > ctx->ws_size)
             return ctx->fail(DK_E_ARG, "%zu hit records do not fit the workspace beside L, its index and the patterns", nhits);
         dk_fm_hit *d_hits = ctx->ws_alloc<dk_fm_hit>(nhits);
         if (!d_hits) return DK_E_NOMEM;
-        DK_TRY(fm_find_device(ctx, d_bwt, d_off, 1, n, d_index, d_loc, step, d_pat, d_pat_off, npat, p.bytes(), nhits, d_hits, nullptr, total));
+        DK_TRY(fm_find_device(ctx, fm, pats, HitSink{nhits, d_hits, nullptr, total}));
         DK_HIP(ctx, hipMemcpyAsync(hits, d_hits, nhits * sizeof(dk_fm_hit), hipMemcpyDeviceToHost, st));
     }
     if (occ) DK_HIP(ctx, hipMemcpyAsync(occ, d_occ, npat * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -930,11 +945,12 @@ int dev_fm_seams(dk_ctx *ctx, const uint8_t *d_bwt, Layout &&lay, const void *d_
         return ctx->fail(DK_E_ARG, "%zu patterns at %zu borders do not fit the workspace (a strip of %zu bytes, 52 bytes per block, 16 per pair)", npat,
                          count, pl.strip_len);
     Upload up(ctx);
-    const uint32_t *d_geo = lay.device_with_bases(up, step), *d_pat_off = upload_offsets(up, p);
-    if (!d_geo || !d_pat_off) return up.failed();
+    FmView fm{PackView{d_bwt, nullptr, count, lay.total()}, d_index, nullptr, d_ext, step};
+    lay.device_with_bases(up, fm);
+    const ItemView pats = p.view(up, d_pat);
+    if (!fm.L.d_off || !pats.d_off) return up.failed();
     up.covers_stage();  // (the stage uploads `pl`)
-    DK_TRY(fm_seams_device(ctx, d_bwt, d_geo, d_geo + count + 1, count, lay.total(), d_index, d_ext, step, d_prev, prev_len, pl, d_pat, d_pat_off, npat,
-                           p.bytes(), max_hits, d_hits, d_occ, total));
+    DK_TRY(fm_seams_device(ctx, fm, d_prev, prev_len, pl, pats, HitSink{max_hits, d_hits, d_occ, total}));
     DK_TRY(up.sync());
     ctx->stats.ms_total = t.ms();
     return DK_OK;
@@ -963,15 +979,9 @@ int dev_fm_near(dk_ctx *ctx, const uint8_t *d_bwt, Layout &&lay, const void *d_i
                 uint64_t *cut) {
     DK_TRY(begin_call(ctx));
     ScopedCall sc(ctx);
-    if (!d_bwt || lay.null() || !d_index || (max_hits && !d_loc)) return ctx->fail(DK_E_ARG, "null pointer");
-    DK_TRY(check_index(ctx, d_index));
-    DK_TRY(lay.check(ctx));
+    const HitSink out{max_hits, d_hits, d_occ, total};
+    DK_TRY(check_find_call(ctx, d_bwt, lay, d_index, d_loc, step, npat, out));
     const size_t count = lay.count();
-    if (!total) return ctx->fail(DK_E_ARG, "null pointer");
-    DK_TRY(check_step(ctx, step));
-    DK_TRY(check_records(ctx, npat, count, "%zu patterns in %zu blocks: more than DK_FM_FIND_MAX_PAIRS pairs", max_hits, d_hits, 16));
-    if (max_hits) DK_TRY(check_aligned(ctx, addr(d_loc), 4, LOCATE_IS));
-    DK_TRY(check_aligned(ctx, addr(d_occ), 4, "the occurrence matrix is"));
     if (k > DK_FM_NEAR_MAX_K) return ctx->fail(DK_E_ARG, "a budget of %u mismatches: more than DK_FM_NEAR_MAX_K", k);
     if (npat == 0) {
         *total = 0;
@@ -988,10 +998,10 @@ int dev_fm_near(dk_ctx *ctx, const uint8_t *d_bwt, Layout &&lay, const void *d_i
         return ctx->fail(DK_E_ARG, "%zu patterns do not fit the workspace (16 bytes per pair)", npat);
     }
     Upload up(ctx);
-    const uint32_t *d_off = lay.device(up), *d_pat_off = upload_offsets(up, p);
-    if (!d_off || !d_pat_off) return up.failed();
-    DK_TRY(fm_near_device(ctx, d_bwt, d_off, count, lay.total(), d_index, d_loc, step, d_cls, d_pat_off, npat, p.bytes(), k, node_limit, max_hits, d_hits,
-                          d_occ, total, cut));
+    const FmView fm{lay.view(up, d_bwt), d_index, d_loc, nullptr, step};
+    const ItemView cls = p.view(up, d_cls);
+    if (!fm.L.d_off || !cls.d_off) return up.failed();
+    DK_TRY(fm_near_device(ctx, fm, cls, k, node_limit, out, cut));
     DK_TRY(up.sync());
     ctx->stats.ms_total = t.ms();
     return DK_OK;
@@ -1020,7 +1030,7 @@ int dk_dbg_dev_fm_rank(dk_ctx *ctx, const uint8_t *d_bwt, size_t total, const vo
     DK_TRY(check_n(ctx, total));
     if (nq == 0) return DK_OK;
     if (!d_pos || !d_sym || !d_out || nq > 0xFFFFFFFEull) return ctx->fail(DK_E_ARG, "null pointer");
-    DK_TRY(fm_rank_device(ctx, d_bwt, total, d_index, d_pos, d_sym, nq, d_out));
+    DK_TRY(fm_rank_device(ctx, FmView{PackView{d_bwt, nullptr, 0, total}, d_index}, d_pos, d_sym, nq, d_out));
     DK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return DK_OK;
 }

@@ -1065,7 +1065,6 @@ int fm_extract_build_device(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector
 
 // ---- what the two inverses above take from the workspace (a decoder context is sized by these: abi.cpp decoder_workspace_bytes) ----------
 namespace {
-size_t ws_round(size_t bytes) { return (bytes + 255) & ~static_cast<size_t>(255); }
 // tile histograms, chunk sums, class starts and the successor table of `total` positions.  The chunk count itself is not monotone in the tile
 // count (257 tiles make 129 chunks, 256 tiles 256): min(tiles, IB_MAX_CHUNKS) bounds it and is.
 size_t ibwt_tables(size_t total) {

@@ -118,7 +118,7 @@ struct dk_ctx {
     int hip_ok(hipError_t e, const char *what) { return e == hipSuccess ? DK_OK : fail(DK_E_HIP, "%s: %s", what, hipGetErrorString(e)); }
 
     void ws_reset() { ws_used = 0; }
-    // 256-byte aligned bump allocation; returns nullptr (and records the error) when the workspace is exhausted
+    // 256-byte aligned bump allocation (dk::ws_round, below: what one takes); returns nullptr (and records the error) when the workspace is exhausted
     void *ws_alloc_bytes(size_t bytes);
     template <class T> T *ws_alloc(size_t count) { return static_cast<T *>(ws_alloc_bytes(count * sizeof(T))); }
     // the same for OPTIONAL buffers (a faster variant that can be done without): nullptr when it does not fit, no error recorded
@@ -136,6 +136,8 @@ struct dk_ctx {
 };
 
 namespace dk {
+
+inline size_t ws_round(size_t bytes) { return (bytes + 255) & ~size_t(255); }  // what one ws_alloc of `bytes` takes: the *_workspace functions' arithmetic
 
 #define DK_HIP(ctx, call)                                                                         \
     do {                                                                                          \
@@ -313,51 +315,61 @@ struct DbgPackedRound {
     uint64_t *keys; uint32_t *vals, *next_act, *guard;
 };
 int dbg_packed_round_device(dk_ctx *ctx, const DbgPackedRound &args, uint32_t out[8]);
-// lcp.hip: d_lcp[i] = common prefix of the suffixes at slots i - 1 and i of their block, 0 at a block's first slot; layout of
-// d_text / d_sa / d_lcp as in packed_sa_device (a single block: count = 1, d_off = {0, n}).  DK_E_ARG, with d_lcp untouched, for an entry of d_sa
-// outside its block.  Synchronises (the lists' counters are read back); ORs DK_ROUTE_LCP_* into stats.sa_route.  Takes 4 total + total / 1024
-// bytes of workspace and sizes its two lists from what is left; releases all of it.
+// ---- the views the query stages take: aggregates of device pointers and sizes, filled on the host by abi_query.cpp; they own nothing ------
+// PackView: `count` blocks back to back in `bytes` (text or L), block i at [d_off[i], d_off[i + 1]), d_off[count] = total, as in
+// packed_sa_device; a single block is a pack of one (d_off = {0, n}).
+struct PackView { const uint8_t *bytes; const uint32_t *d_off; size_t count, total; };
+// FmView: a packed L and what was built from it: the index (fm_build_device), the locate and the extract structure of sampling step `step`
+// (null where the stage reads none), d_abase = the blocks' anchor bases (fm_extract_bases; null: one block, base 0).
+struct FmView { PackView L; const void *index, *loc, *ext; uint32_t step; const uint32_t *d_abase; };
+// ItemView: `count` items -- patterns, queries, rows of byte classes -- back to back in `bytes`, item q at [d_off[q], d_off[q + 1]), d_off[count] =
+// nbytes, for block d_blk[q] (checked by the caller; null: block 0, or every block where the stage says so).  longest / shortest: of their lengths.
+struct ItemView { const uint8_t *bytes; const uint32_t *d_off, *d_blk; size_t count, nbytes, longest, shortest; };
+// HitSink: where a stage that lists hits leaves them: *total_out (host) = their number, d_hits (16-byte aligned records of 16 bytes) = the
+// first min(total, max_hits) of them (max_hits == 0: not looked at), d_occ (may be null) = the hits of every (item, block) pair.
+struct HitSink {
+    size_t max_hits; void *d_hits; uint32_t *d_occ; uint64_t *total_out;
+    size_t take(uint64_t total) const { *total_out = total; return static_cast<size_t>(total < max_hits ? total : max_hits); }  // -> records to write
+};
+// lcp.hip: d_lcp[i] = common prefix of the suffixes at slots i - 1 and i of their block, 0 at a block's first slot; d_sa /
+// d_lcp laid out as the text.  DK_E_ARG, with d_lcp untouched, for an entry of d_sa outside its block.  Synchronises (the lists' counters are
+// read back); ORs DK_ROUTE_LCP_* into stats.sa_route.  Takes 4 total + total / 1024 bytes of workspace and sizes its two lists from what is
+// left; releases all of it.
 // d_phi_ready (may be null; total words, the caller's): Phi as lcp_phi_from_rank_device / lcp_phi_block_device left it -- d_sa is not checked then.
-int lcp_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, size_t count, size_t total, const uint32_t *d_sa, uint32_t *d_lcp,
-               uint32_t *d_phi_ready = nullptr);
+int lcp_device(dk_ctx *ctx, const PackView &text, const uint32_t *d_sa, uint32_t *d_lcp, uint32_t *d_phi_ready = nullptr);
 // Phi of the whole pack from the packed sort's rank (the inverse suffix array) and the suffix arrays k_pk_emit wrote from it; the stretches of
 // guarded blocks hold nothing useful afterwards ...
 int lcp_phi_from_rank_device(dk_ctx *ctx, const uint32_t *d_rank, const uint32_t *d_sa, const uint32_t *d_off, size_t count, size_t total, uint32_t *d_phi);
 // ... and are redone here, one block's slots [lo, hi) at a time, from the suffix array the guard has written
 int lcp_phi_block_device(dk_ctx *ctx, const uint32_t *d_sa, const uint32_t *d_off, size_t count, size_t lo, size_t hi, uint32_t *d_phi);
-// sa_query.hip; layout of d_text / d_sa as in lcp_device.
+// sa_query.hip; d_sa laid out as the text.
 // sa_check_device: h_words (host, 3 count) = per block the lowest slot whose entry is outside the block, the lowest position no slot names, the lowest
 // slot whose suffix is not greater than the one in front of it; all ones: none.  The order is evaluated only for blocks without the first two.
 // Synchronises.  Takes 4 total + 12 count bytes of workspace and releases them.
-int sa_check_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, size_t count, size_t total, const uint32_t *d_sa, uint32_t *h_words);
-// sa_search_device: pattern q = d_pat[d_pat_off[q], d_pat_off[q + 1]) in block d_pat_blk[q] (d_pat_blk null: block 0; the caller has checked them);
-// d_lo[q] / d_hi[q] = slots of that block whose suffix, cut to the pattern's length, is smaller than / not greater than the pattern.  longest /
-// shortest: of the pattern lengths, which decide the kernels launched.  Enqueues only; takes no workspace.
-int sa_search_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, const uint32_t *d_sa, const uint8_t *d_pat, const uint32_t *d_pat_off,
-                     const uint32_t *d_pat_blk, size_t npat, size_t longest, size_t shortest, uint32_t *d_lo, uint32_t *d_hi);
-// sa_match_device: query j = d_qry[d_q_off[j], d_q_off[j + 1]) against block d_q_blk[j] (null: block 0; checked by the
-// caller); for every position g < qbytes, d_len[g] = the longest prefix of its window (at most max_len bytes, inside its query) that occurs in the
-// block, d_lo[g] / d_hi[g] (both or neither) = sa_search_device's numbers for that prefix.  Enqueues only; takes no workspace.
-int sa_match_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, const uint32_t *d_sa, const uint8_t *d_qry, const uint32_t *d_q_off,
-                    const uint32_t *d_q_blk, size_t nq, size_t qbytes, size_t max_len, uint32_t *d_len, uint32_t *d_lo, uint32_t *d_hi);
-// sa_smems_device: the super-maximal matches of those statistics; *total_out (host) = their number, d_hits (16-byte aligned records {at, len, lo,
-// hi}, at = the position g) = the first min(total, max_hits) in rising order of at.  max_hits == 0: d_hits is not looked at.  Takes
-// sa_smems_workspace(qbytes) bytes (16 per query byte and a word per 1024, every ws_alloc rounded up) and releases them.  Synchronises.
+int sa_check_device(dk_ctx *ctx, const PackView &text, const uint32_t *d_sa, uint32_t *h_words);
+// sa_search_device: d_lo[q] / d_hi[q] = slots of pattern q's block whose suffix, cut to the pattern's length, is smaller than / not greater than
+// the pattern.  The longest and the shortest length decide the kernels launched.  Enqueues only; takes no workspace.
+int sa_search_device(dk_ctx *ctx, const PackView &text, const uint32_t *d_sa, const ItemView &pat, uint32_t *d_lo, uint32_t *d_hi);
+// sa_match_device: for every position g < qry.nbytes, d_len[g] = the longest prefix of its window (at most max_len
+// bytes, inside its query) that occurs in the query's block, d_lo[g] / d_hi[g] (both or neither) = sa_search_device's numbers for that prefix.
+// Enqueues only; takes no workspace.
+int sa_match_device(dk_ctx *ctx, const PackView &text, const uint32_t *d_sa, const ItemView &qry, size_t max_len, uint32_t *d_len, uint32_t *d_lo, uint32_t *d_hi);
+// sa_smems_device: the super-maximal matches of those statistics, records {at, len, lo, hi} (at = the position g) in rising order of at;
+// out.d_occ is not looked at.  Takes sa_smems_workspace(qry.nbytes) bytes (16 per query byte and a word per 1024, every ws_alloc rounded
+// up) and releases them.  Synchronises.
 size_t sa_smems_workspace(size_t qbytes);
-int sa_smems_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, const uint32_t *d_sa, const uint8_t *d_qry, const uint32_t *d_q_off,
-                    const uint32_t *d_q_blk, size_t nq, size_t qbytes, size_t min_len, size_t max_len, size_t max_hits, void *d_hits, uint64_t *total_out);
+int sa_smems_device(dk_ctx *ctx, const PackView &text, const uint32_t *d_sa, const ItemView &qry, size_t min_len, size_t max_len, const HitSink &out);
 // fm_index.hip: the FM-index of a packed L and the backward search in it; a single block is a pack of one.
 // fm_index_words: 32-bit words of the index (host arithmetic).  fm_build_workspace: what fm_build_device takes, every ws_alloc rounded up.
 size_t fm_index_words(size_t total, size_t count);
 size_t fm_build_workspace(size_t total, size_t count);
 // off (host, count + 1) and origin (host, count; origin[i] < n_i checked by the caller) describe the pack.  Synchronises; releases its workspace.
 int fm_build_device(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector<uint32_t> &off, const uint32_t *origin, void *d_index);
-// patterns as in sa_search_device; d_lo[q] / d_hi[q] are the numbers sa_search_device gives.  Enqueues only; takes no workspace.
-int fm_count_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, const void *d_index, const uint8_t *d_pat,
-                    const uint32_t *d_pat_off, const uint32_t *d_pat_blk, size_t npat, size_t pat_bytes, uint32_t *d_lo, uint32_t *d_hi);
-// d_out[q] = occurrences of d_sym[q] in d_bwt[0, min(d_pos[q], total)), by the count kernel's rank.  Enqueues only.
-int fm_rank_device(dk_ctx *ctx, const uint8_t *d_bwt, size_t total, const void *d_index, const uint32_t *d_pos, const uint8_t *d_sym, size_t nq,
-                   uint32_t *d_out);
+// d_lo[q] / d_hi[q] are the numbers sa_search_device gives, by backward search in L.  Enqueues only; takes no workspace.
+int fm_count_device(dk_ctx *ctx, const FmView &fm, const ItemView &pat, uint32_t *d_lo, uint32_t *d_hi);
+// d_out[q] = occurrences of d_sym[q] in L[0, min(d_pos[q], total)), by the count kernel's rank: of fm, the bytes, the total and the index's
+// checkpoints are read and nothing else.  Enqueues only.
+int fm_rank_device(dk_ctx *ctx, const FmView &fm, const uint32_t *d_pos, const uint8_t *d_sym, size_t nq, uint32_t *d_out);
 // The locate structure of a packed L (bwt.hip builds it, fm_index.hip reads it): 32-bit words, over the whole pack.
 //   [0, 64) header | rows + 1 marks before each 1024-slot row | 32 rows mark bits | total / step + count samples, in slot order
 // step: a power of two in [1, 4096] (the caller's check).  Host arithmetic, and the one place that knows the layout.
@@ -377,26 +389,22 @@ int fm_locate_build_device(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector<
                            bool packed);
 size_t fm_locate_build_workspace(size_t total, size_t count);  // an upper bound of what it takes, every ws_alloc rounded up; host arithmetic
 // fm_index.hip: item (q, j), j < max_hits, of pattern q with the range [d_lo[q], d_hi[q]) in block d_pat_blk[q] (null: block 0):
-// d_pos[q * max_hits + j] = SA_b[lo + j], DK_FM_NO_HIT behind the range.  Enqueues only; takes no workspace.
-int fm_locate_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, const void *d_index, const void *d_loc,
-                     uint32_t step, const uint32_t *d_lo, const uint32_t *d_hi, const uint32_t *d_pat_blk, size_t npat, size_t max_hits, uint32_t *d_pos);
-// fm_index.hip: every pattern (d_pat / d_pat_off as for fm_count_device, no blocks) in every block.  Pair p = q * count + b:
-// d_occ[p] (may be null) = its occurrences; *total_out (host) = their sum; d_hits (16-byte aligned records {pattern, block, position, slot}) = the
-// first min(total, max_hits) hits in the order (q, b, slot), position as fm_locate_device gives it.  max_hits == 0: d_hits and d_loc are not looked
-// at.  Takes fm_find_workspace(npat * count) bytes (16 per pair and the chunk sums, every ws_alloc rounded up) and releases them.  Synchronises.
+// d_pos[q * max_hits + j] = SA_b[lo + j], DK_FM_NO_HIT behind the range.  Reads fm.loc.  Enqueues only; takes no workspace.
+int fm_locate_device(dk_ctx *ctx, const FmView &fm, const uint32_t *d_lo, const uint32_t *d_hi, const uint32_t *d_pat_blk, size_t npat, size_t max_hits,
+                     uint32_t *d_pos);
+// fm_index.hip: every pattern in every block (pat.d_blk is not looked at).  Pair p = q * count + b: out.d_occ[p] = its
+// occurrences; the records {pattern, block, position, slot} stand in the order (q, b, slot), position as fm_locate_device gives it.
+// out.max_hits == 0: fm.loc is not looked at either.  Takes fm_find_workspace(pat.count * count) bytes (16 per pair and the chunk sums, every
+// ws_alloc rounded up) and releases them.  Synchronises.
 size_t fm_find_workspace(size_t npairs);
-int fm_find_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, const void *d_index, const void *d_loc,
-                   uint32_t step, const uint8_t *d_pat, const uint32_t *d_pat_off, size_t npat, size_t pat_bytes, size_t max_hits, void *d_hits,
-                   uint32_t *d_occ, uint64_t *total_out);
-// fm_index.hip: every pattern in every block again, the pattern's positions byte classes (d_cls: 32 bytes per position,
-// the patterns back to back as d_pat_off says) and up to k of them missed.  d_occ, *total_out and the order of the pairs as for fm_find_device;
-// inside a pair the hits stand in the preorder of the search tree, of which at most node_limit nodes (0: DK_FM_NEAR_NODE_LIMIT) are visited.
-// *cut_out (host, may be null) = the pairs that stopped there.  d_hits: records {pattern, block, position, cost}.  Takes
-// fm_near_workspace(npat * count) bytes (16 per pair and two rows of chunk sums) and releases them.  Synchronises.
+int fm_find_device(dk_ctx *ctx, const FmView &fm, const ItemView &pat, const HitSink &out);
+// fm_index.hip: every pattern in every block again, the pattern's positions byte classes (cls.bytes: 32 bytes per
+// position, so cls.d_off counts positions) and up to k of them missed.  Pairs, out.d_occ and fm.loc as for fm_find_device; inside a pair the
+// hits stand in the preorder of the search tree, of which at most node_limit nodes (0: DK_FM_NEAR_NODE_LIMIT) are visited.  *cut_out (host,
+// may be null) = the pairs that stopped there.  Records {pattern, block, position, cost}.  Takes fm_near_workspace(cls.count * count) bytes
+// (16 per pair and two rows of chunk sums) and releases them.  Synchronises.
 size_t fm_near_workspace(size_t npairs);
-int fm_near_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, const void *d_index, const void *d_loc,
-                   uint32_t step, const uint8_t *d_cls, const uint32_t *d_pat_off, size_t npat, size_t pat_bytes, uint32_t k, uint32_t node_limit,
-                   size_t max_hits, void *d_hits, uint32_t *d_occ, uint64_t *total_out, uint64_t *cut_out);
+int fm_near_device(dk_ctx *ctx, const FmView &fm, const ItemView &cls, uint32_t k, uint32_t node_limit, const HitSink &out, uint64_t *cut_out);
 // The extract structure of a packed L (bwt.hip builds it, fm_index.hip reads it): 32-bit words, over the whole pack.
 //   [0, 64) header: magic, total, count, step, anchors | total / step + count anchors
 // Block b's anchors are the ceil(n_b / step) words from its anchor base, the sum of ceil(n_i / step) over the blocks in front of it: anchor k =
@@ -415,23 +423,20 @@ inline std::vector<uint32_t> fm_extract_bases(const std::vector<uint32_t> &off, 
 int fm_extract_build_device(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector<uint32_t> &off, const uint32_t *origin, uint32_t step, void *d_ext,
                             bool packed);
 // fm_index.hip: row q of d_out (nrange x max_len bytes, any alignment) = T_b[pos, pos + got) of block d_rng_blk[q] (null: block 0), where pos =
-// d_pos[q] and got = min(d_len[q] (null: max_len), max_len, n_b - pos), 0 for pos >= n_b; zeros behind.  d_abase: the blocks' anchor bases on the
-// device (null: one block, base 0).  Enqueues a memset of the rows and one kernel; takes no workspace.
-int fm_extract_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, const uint32_t *d_abase, size_t count, size_t total, const void *d_index,
-                      const void *d_ext, uint32_t step, const uint32_t *d_pos, const uint32_t *d_len, const uint32_t *d_rng_blk, size_t nrange,
-                      size_t max_len, uint8_t *d_out);
+// d_pos[q] and got = min(d_len[q] (null: max_len), max_len, n_b - pos), 0 for pos >= n_b; zeros behind.  Reads fm.ext and fm.d_abase.  Enqueues
+// a memset of the rows and one kernel; takes no workspace.
+int fm_extract_device(dk_ctx *ctx, const FmView &fm, const uint32_t *d_pos, const uint32_t *d_len, const uint32_t *d_rng_blk, size_t nrange, size_t max_len,
+                      uint8_t *d_out);
 // fm_index.hip: the matches that straddle the borders of a pack whose text is preceded by prev_len bytes d_prev.
 // fm_seam_plan lays out the edge strip for W = longest pattern - 1 (host arithmetic): words = 3 per block {strip offset of the block's first byte,
 // min(n_b, W), start of the contiguous run that reaches it}, then block, start, length and strip offset of each of the nrange <= 2 count - 1
-// extract ranges.  fm_seams_device fills the strip through k_fm_extract, counts, scans and emits as fm_find_device does: d_occ[q * count + b]
-// (may be null), *total_out (host), d_hits = the first min(total, max_hits) records {pattern, block, back, 0} in the order (q, b, back
-// descending).  Takes fm_seams_workspace bytes and releases them.  Synchronises.
+// extract ranges.  fm_seams_device fills the strip through k_fm_extract (fm.ext, fm.d_abase), counts, scans and emits as fm_find_device does:
+// pairs and out.d_occ as there, records {pattern, block, back, 0} in the order (q, b, back descending).  Takes fm_seams_workspace bytes and
+// releases them.  Synchronises.
 struct FmSeamPlan { std::vector<uint32_t> words; size_t nrange = 0, strip_len = 0, max_len = 1; };
 FmSeamPlan fm_seam_plan(const std::vector<uint32_t> &off, size_t prev_len, size_t W);
 size_t fm_seams_workspace(const FmSeamPlan &pl, size_t npairs);
-int fm_seams_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, const uint32_t *d_abase, size_t count, size_t total, const void *d_index,
-                    const void *d_ext, uint32_t step, const uint8_t *d_prev, size_t prev_len, const FmSeamPlan &pl, const uint8_t *d_pat,
-                    const uint32_t *d_pat_off, size_t npat, size_t pat_bytes, size_t max_hits, void *d_hits, uint32_t *d_occ, uint64_t *total_out);
+int fm_seams_device(dk_ctx *ctx, const FmView &fm, const uint8_t *d_prev, size_t prev_len, const FmSeamPlan &pl, const ItemView &pat, const HitSink &out);
 // packed_dc_device: the DC arrays of every block of a packed L.  compact: block i's entries at [rb_i, rb_i + m_i) (global run order, rb on the
 // device in d_rb[0 .. count], d_rb[count] = all runs); otherwise at [off_i, off_i + m_i).  d_m / d_flags: count words, d_init: count x 256.
 int packed_dc_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, bool compact, uint32_t *d_dist,

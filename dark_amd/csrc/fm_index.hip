@@ -807,12 +807,34 @@ __global__ __launch_bounds__(64 * FM_WAVES) void k_fm_near_locate(FmNearLocArgs 
     }
 }
 
+// ---- what the host stages share: the caller's structures carved, the pairs' geometry, the scan over the pairs ---------------------------------
+FmIndex fm_carve(const FmView &fm) { return fm_carve(const_cast<void *>(fm.index), fm.L.total, fm.L.count); }
+// the walk's record: the index and the locate structure fm.loc, sampled at fm.step
+FmWalk fm_walk(const FmView &fm, const FmIndex &ix) {
+    const FmLocate lc = fm_locate_carve(const_cast<void *>(fm.loc), fm.L.total, fm.L.count, fm.step);
+    return FmWalk{fm.L.bytes, ix.blocks, ix.base, ix.cp, lc.marks, lc.bits, lc.samples, static_cast<uint32_t>(fm.L.total),
+                  static_cast<uint32_t>(ceil_log2_u64(fm.step)), static_cast<uint32_t>(lc.nsamp)};
+}
+// the (pattern, block) pairs of find, near and seams, and their scan's shape: rows of FM_FIND_ROW pairs in nchunks chunks of rpc rows
+struct FmPairs { size_t npairs, rows, rpc, nchunks; };
+FmPairs fm_pairs(size_t npat, size_t count) {
+    const size_t npairs = npat * count, rows = div_up(npairs, FM_FIND_ROW), rpc = div_up(rows, FM_MAX_CHUNKS), nchunks = div_up(rows, rpc);
+    return FmPairs{npairs, rows, rpc, nchunks};
+}
+// k_fm_find_scan_a / _b / _c over d_cnt: *d_total (a field of the device mailbox) = the sum of all, d_offset[p] = the sum below pair p;
+// d_offset null: _a / _b alone, the total.  chunk_sum: FM_MAX_CHUNKS sums.  Enqueues inside the caller's bracket and opens none.
+void fm_scan_pairs(dk_ctx *ctx, const FmPairs &g, const uint32_t *d_cnt, uint64_t *chunk_sum, uint64_t *d_total, uint64_t *d_offset) {
+    const uint32_t P = static_cast<uint32_t>(g.npairs), R = static_cast<uint32_t>(g.rpc), C = static_cast<uint32_t>(g.nchunks);
+    k_fm_find_scan_a<<<dim3(C), dim3(256), 0, ctx->stream>>>(d_cnt, P, R, chunk_sum);
+    k_fm_find_scan_b<<<dim3(1), dim3(256), 0, ctx->stream>>>(chunk_sum, C, d_total);
+    if (d_offset) k_fm_find_scan_c<<<dim3(C), dim3(256), 0, ctx->stream>>>(d_cnt, P, R, chunk_sum, d_offset);
+}
+
 }  // namespace
 
 size_t fm_build_workspace(size_t total, size_t count) {
     const size_t rows = div_up(total, FM_BLOCK) + 1, rpc = div_up(rows, FM_MAX_CHUNKS), nchunks = div_up(rows, rpc);
-    auto r = [](size_t b) { return (b + 255) & ~size_t(255); };
-    return r(nchunks * 256 * 4) + r(4 * (count + 1)) + r(4 * count);
+    return ws_round(nchunks * 256 * 4) + ws_round(4 * (count + 1)) + ws_round(4 * count);
 }
 
 int fm_build_device(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector<uint32_t> &off, const uint32_t *origin, void *d_index) {
@@ -850,95 +872,80 @@ int fm_build_device(dk_ctx *ctx, const uint8_t *d_bwt, const std::vector<uint32_
     return DK_OK;
 }
 
-int fm_count_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, const void *d_index, const uint8_t *d_pat,
-                    const uint32_t *d_pat_off, const uint32_t *d_pat_blk, size_t npat, size_t pat_bytes, uint32_t *d_lo, uint32_t *d_hi) {
-    const FmIndex ix = fm_carve(const_cast<void *>(d_index), total, count);
-    const unsigned grid = static_cast<unsigned>(std::min<size_t>(div_up(npat, FM_WAVES), 1u << 20));
-    const FmArgs a{d_bwt, d_off, ix.blocks, ix.base, ix.cp, d_pat, d_pat_off, d_pat_blk, static_cast<uint32_t>(npat), static_cast<uint32_t>(total),
-                   static_cast<uint32_t>(count), d_lo, d_hi};
+int fm_count_device(dk_ctx *ctx, const FmView &fm, const ItemView &pat, uint32_t *d_lo, uint32_t *d_hi) {
+    const FmIndex ix = fm_carve(fm);
+    const unsigned grid = static_cast<unsigned>(std::min<size_t>(div_up(pat.count, FM_WAVES), 1u << 20));
+    const FmArgs a{fm.L.bytes, fm.L.d_off, ix.blocks, ix.base, ix.cp, pat.bytes, pat.d_off, pat.d_blk, static_cast<uint32_t>(pat.count),
+                   static_cast<uint32_t>(fm.L.total), static_cast<uint32_t>(fm.L.count), d_lo, d_hi};
     {
         // per step at most two gathered checkpoint words and two rows of L; the pattern bytes, the offsets and the two results
-        LaunchScope ls(ctx, K_CHAIN, 16.0 * npat + pat_bytes * (1.0 + 2.0 * (FM_BLOCK + 64)));
+        LaunchScope ls(ctx, K_CHAIN, 16.0 * pat.count + pat.nbytes * (1.0 + 2.0 * (FM_BLOCK + 64)));
         k_fm_count<<<dim3(grid), dim3(64 * FM_WAVES), 0, ctx->stream>>>(a);
     }
     DK_HIP(ctx, hipGetLastError());
     return DK_OK;
 }
 
-int fm_rank_device(dk_ctx *ctx, const uint8_t *d_bwt, size_t total, const void *d_index, const uint32_t *d_pos, const uint8_t *d_sym, size_t nq,
-                   uint32_t *d_out) {
-    const FmIndex ix = fm_carve(const_cast<void *>(d_index), total, 0);  // (the checkpoints lie in front of everything that depends on the count)
+int fm_rank_device(dk_ctx *ctx, const FmView &fm, const uint32_t *d_pos, const uint8_t *d_sym, size_t nq, uint32_t *d_out) {
+    const FmIndex ix = fm_carve(const_cast<void *>(fm.index), fm.L.total, 0);  // (the checkpoints lie in front of everything that depends on the count)
     const unsigned grid = static_cast<unsigned>(std::min<size_t>(div_up(nq, FM_WAVES), 1u << 20));
     {
         LaunchScope ls(ctx, K_CHAIN, nq * (9.0 + FM_BLOCK + 64));
-        k_fm_rank<<<dim3(grid), dim3(64 * FM_WAVES), 0, ctx->stream>>>(d_bwt, static_cast<uint32_t>(total), ix.cp, d_pos, d_sym, static_cast<uint32_t>(nq), d_out);
+        k_fm_rank<<<dim3(grid), dim3(64 * FM_WAVES), 0, ctx->stream>>>(fm.L.bytes, static_cast<uint32_t>(fm.L.total), ix.cp, d_pos, d_sym,
+                                                                       static_cast<uint32_t>(nq), d_out);
     }
     DK_HIP(ctx, hipGetLastError());
     return DK_OK;
 }
 
-int fm_locate_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, const void *d_index, const void *d_loc,
-                     uint32_t step, const uint32_t *d_lo, const uint32_t *d_hi, const uint32_t *d_pat_blk, size_t npat, size_t max_hits, uint32_t *d_pos) {
-    const FmIndex ix = fm_carve(const_cast<void *>(d_index), total, count);
-    const FmLocate lc = fm_locate_carve(const_cast<void *>(d_loc), total, count, step);
+int fm_locate_device(dk_ctx *ctx, const FmView &fm, const uint32_t *d_lo, const uint32_t *d_hi, const uint32_t *d_pat_blk, size_t npat, size_t max_hits,
+                     uint32_t *d_pos) {
+    const FmWalk w = fm_walk(fm, fm_carve(fm));
     const size_t nitems = npat * max_hits;
     const unsigned grid = static_cast<unsigned>(std::min<size_t>(div_up(nitems, FM_WAVES), 1u << 20));
-    const FmLocArgs a{d_bwt, d_off, ix.blocks, ix.base, ix.cp, lc.marks, lc.bits, lc.samples, d_lo, d_hi, d_pat_blk, static_cast<uint32_t>(npat),
-                      static_cast<uint32_t>(max_hits), static_cast<uint32_t>(total), static_cast<uint32_t>(ceil_log2_u64(step)),
-                      static_cast<uint32_t>(lc.nsamp), d_pos};
+    const FmLocArgs a{w.L, fm.L.d_off, w.blocks, w.base, w.cp, w.marks, w.bits, w.samples, d_lo, d_hi, d_pat_blk, static_cast<uint32_t>(npat),
+                      static_cast<uint32_t>(max_hits), w.total, w.step_shift, w.nsamp, d_pos};
     {
         // per item about step / 2 steps of a row of L, a row of mark words and a checkpoint word; the range, the sample and the result
-        LaunchScope ls(ctx, K_CHAIN, nitems * (20.0 + 0.5 * step * (FM_BLOCK + 128 + 64)));
+        LaunchScope ls(ctx, K_CHAIN, nitems * (20.0 + 0.5 * fm.step * (FM_BLOCK + 128 + 64)));
         k_fm_locate<<<dim3(grid), dim3(64 * FM_WAVES), 0, ctx->stream>>>(a);
     }
     DK_HIP(ctx, hipGetLastError());
     return DK_OK;
 }
 
-size_t fm_find_workspace(size_t npairs) {
-    auto r = [](size_t b) { return (b + 255) & ~size_t(255); };
-    return 2 * r(4 * npairs) + r(8 * npairs) + r(8 * FM_MAX_CHUNKS);
-}
+size_t fm_find_workspace(size_t npairs) { return 2 * ws_round(4 * npairs) + ws_round(8 * npairs) + ws_round(8 * FM_MAX_CHUNKS); }
 
-int fm_find_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, const void *d_index, const void *d_loc,
-                   uint32_t step, const uint8_t *d_pat, const uint32_t *d_pat_off, size_t npat, size_t pat_bytes, size_t max_hits, void *d_hits,
-                   uint32_t *d_occ, uint64_t *total_out) {
+int fm_find_device(dk_ctx *ctx, const FmView &fm, const ItemView &pat, const HitSink &out) {
     hipStream_t st = ctx->stream;
-    const FmIndex ix = fm_carve(const_cast<void *>(d_index), total, count);
-    const size_t npairs = npat * count, rows = div_up(npairs, FM_FIND_ROW), rpc = div_up(rows, FM_MAX_CHUNKS), nchunks = div_up(rows, rpc);
-    const size_t mark = ctx->ws_mark();
+    const FmIndex ix = fm_carve(fm);
+    const FmPairs g = fm_pairs(pat.count, fm.L.count);
+    const size_t npairs = g.npairs, count = fm.L.count, mark = ctx->ws_mark();
     uint32_t *d_lo = ctx->ws_alloc<uint32_t>(npairs), *d_cnt = ctx->ws_alloc<uint32_t>(npairs);
     uint64_t *d_offset = ctx->ws_alloc<uint64_t>(npairs), *chunk_sum = ctx->ws_alloc<uint64_t>(FM_MAX_CHUNKS);
     if (!d_lo || !d_cnt || !d_offset || !chunk_sum) return DK_E_NOMEM;
-    const uint32_t P = static_cast<uint32_t>(npairs), R = static_cast<uint32_t>(rpc);
     {
-        // per pair the count's traffic for its pattern (pat_bytes / npat on average), the three words written
-        LaunchScope ls(ctx, K_CHAIN, 20.0 * npairs + static_cast<double>(count) * pat_bytes * (1.0 + 2.0 * (FM_BLOCK + 64)));
-        const FmFindArgs a{d_bwt, d_off, ix.blocks, ix.base, ix.cp, d_pat, d_pat_off, static_cast<uint32_t>(npat), static_cast<uint32_t>(total),
-                           static_cast<uint32_t>(count), d_lo, d_cnt, d_occ};
+        // per pair the count's traffic for its pattern (pat.nbytes / pat.count on average), the three words written
+        LaunchScope ls(ctx, K_CHAIN, 20.0 * npairs + static_cast<double>(count) * pat.nbytes * (1.0 + 2.0 * (FM_BLOCK + 64)));
+        const FmFindArgs a{fm.L.bytes, fm.L.d_off, ix.blocks, ix.base, ix.cp, pat.bytes, pat.d_off, static_cast<uint32_t>(pat.count),
+                           static_cast<uint32_t>(fm.L.total), static_cast<uint32_t>(count), d_lo, d_cnt, out.d_occ};
         const unsigned grid = static_cast<unsigned>(std::min<size_t>(div_up(npairs, FM_WAVES), 1u << 20));
         k_fm_find_count<<<dim3(grid), dim3(64 * FM_WAVES), 0, st>>>(a);
     }
     {
         LaunchScope ls(ctx, K_CHAIN, 16.0 * npairs);  // occ read twice, the offsets written
-        k_fm_find_scan_a<<<dim3(static_cast<unsigned>(nchunks)), dim3(256), 0, st>>>(d_cnt, P, R, chunk_sum);
-        k_fm_find_scan_b<<<dim3(1), dim3(256), 0, st>>>(chunk_sum, static_cast<uint32_t>(nchunks), &ctx->d_mail->fm_find.total);
-        k_fm_find_scan_c<<<dim3(static_cast<unsigned>(nchunks)), dim3(256), 0, st>>>(d_cnt, P, R, chunk_sum, d_offset);
+        fm_scan_pairs(ctx, g, d_cnt, chunk_sum, &ctx->d_mail->fm_find.total, d_offset);
     }
     DK_HIP(ctx, hipGetLastError());
     DK_TRY(ctx->mail_read(&ctx->h_mail->fm_find.total));
-    const uint64_t all = ctx->h_mail->fm_find.total;
-    *total_out = all;
-    const size_t nhits = static_cast<size_t>(std::min<uint64_t>(all, max_hits));
+    const size_t nhits = out.take(ctx->h_mail->fm_find.total);
     if (nhits) {
-        const FmLocate lc = fm_locate_carve(const_cast<void *>(d_loc), total, count, step);
-        const FmFindLocArgs a{FmWalk{d_bwt, ix.blocks, ix.base, ix.cp, lc.marks, lc.bits, lc.samples, static_cast<uint32_t>(total),
-                                     static_cast<uint32_t>(ceil_log2_u64(step)), static_cast<uint32_t>(lc.nsamp)},
-                              d_off, d_lo, d_offset, P, static_cast<uint32_t>(count), static_cast<uint32_t>(nhits), static_cast<uint4 *>(d_hits)};
+        const FmFindLocArgs a{fm_walk(fm, ix), fm.L.d_off, d_lo, d_offset, static_cast<uint32_t>(npairs), static_cast<uint32_t>(count),
+                              static_cast<uint32_t>(nhits), static_cast<uint4 *>(out.d_hits)};
         const unsigned grid = static_cast<unsigned>(std::min<size_t>(div_up(nhits, FM_WAVES), 1u << 20));
         {
             // per hit four rounds of 64 offsets, the walk of k_fm_locate and the record
-            LaunchScope ls(ctx, K_CHAIN, nhits * (4.0 * 512 + 36.0 + 0.5 * step * (FM_BLOCK + 128 + 64)));
+            LaunchScope ls(ctx, K_CHAIN, nhits * (4.0 * 512 + 36.0 + 0.5 * fm.step * (FM_BLOCK + 128 + 64)));
             k_fm_find_locate<<<dim3(grid), dim3(64 * FM_WAVES), 0, st>>>(a);
         }
         DK_HIP(ctx, hipGetLastError());
@@ -948,59 +955,45 @@ int fm_find_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, siz
     return DK_OK;
 }
 
-size_t fm_near_workspace(size_t npairs) {
-    auto r = [](size_t b) { return (b + 255) & ~size_t(255); };
-    return 2 * r(4 * npairs) + r(8 * npairs) + 2 * r(8 * FM_MAX_CHUNKS);
-}
+size_t fm_near_workspace(size_t npairs) { return 2 * ws_round(4 * npairs) + ws_round(8 * npairs) + 2 * ws_round(8 * FM_MAX_CHUNKS); }
 
-int fm_near_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, size_t count, size_t total, const void *d_index, const void *d_loc,
-                   uint32_t step, const uint8_t *d_cls, const uint32_t *d_pat_off, size_t npat, size_t pat_bytes, uint32_t k, uint32_t node_limit,
-                   size_t max_hits, void *d_hits, uint32_t *d_occ, uint64_t *total_out, uint64_t *cut_out) {
+int fm_near_device(dk_ctx *ctx, const FmView &fm, const ItemView &cls, uint32_t k, uint32_t node_limit, const HitSink &out, uint64_t *cut_out) {
     hipStream_t st = ctx->stream;
-    const FmIndex ix = fm_carve(const_cast<void *>(d_index), total, count);
-    const size_t npairs = npat * count, rows = div_up(npairs, FM_FIND_ROW), rpc = div_up(rows, FM_MAX_CHUNKS), nchunks = div_up(rows, rpc);
-    const size_t mark = ctx->ws_mark();
+    const FmIndex ix = fm_carve(fm);
+    const FmPairs g = fm_pairs(cls.count, fm.L.count);
+    const size_t npairs = g.npairs, count = fm.L.count, mark = ctx->ws_mark();
     uint32_t *d_cnt = ctx->ws_alloc<uint32_t>(npairs), *d_cut = ctx->ws_alloc<uint32_t>(npairs);
     uint64_t *d_offset = ctx->ws_alloc<uint64_t>(npairs), *chunk_sum = ctx->ws_alloc<uint64_t>(FM_MAX_CHUNKS), *cut_sum = ctx->ws_alloc<uint64_t>(FM_MAX_CHUNKS);
     if (!d_cnt || !d_cut || !d_offset || !chunk_sum || !cut_sum) return DK_E_NOMEM;
-    const uint32_t P = static_cast<uint32_t>(npairs), R = static_cast<uint32_t>(rpc);
-    FmNearArgs a{d_bwt, d_off, ix.blocks, ix.base, ix.cp, d_cls, d_pat_off, static_cast<uint32_t>(npat), static_cast<uint32_t>(total),
+    FmNearArgs a{fm.L.bytes, fm.L.d_off, ix.blocks, ix.base, ix.cp, cls.bytes, cls.d_off, static_cast<uint32_t>(cls.count), static_cast<uint32_t>(fm.L.total),
                  static_cast<uint32_t>(count), static_cast<uint32_t>(ix.rows), k, node_limit ? node_limit : DK_FM_NEAR_NODE_LIMIT,
-                 d_cnt, d_cut, d_occ, d_offset, 0u, static_cast<uint4 *>(d_hits)};
+                 d_cnt, d_cut, out.d_occ, d_offset, 0u, static_cast<uint4 *>(out.d_hits)};
     const unsigned grid = static_cast<unsigned>(std::min<size_t>(div_up(npairs, FM_WAVES), 1u << 20));
     // What a pair's tree costs is the answer itself.  The bytes given are those of the one path a search without branching takes -- find's, with
     // 32 bytes of class per position -- so the slot's GB/s is a lower bound.
-    const double path_bytes = static_cast<double>(count) * pat_bytes * (32.0 + 2.0 * (FM_BLOCK + 64));
+    const double path_bytes = static_cast<double>(count) * cls.nbytes * (32.0 + 2.0 * (FM_BLOCK + 64));
     {
         LaunchScope ls(ctx, K_CHAIN, 20.0 * npairs + path_bytes);
         k_fm_near_count<<<dim3(grid), dim3(64 * FM_WAVES), 0, st>>>(a);
     }
     {
         LaunchScope ls(ctx, K_CHAIN, 24.0 * npairs);  // occ read twice, the cut flags once, the offsets written
-        k_fm_find_scan_a<<<dim3(static_cast<unsigned>(nchunks)), dim3(256), 0, st>>>(d_cnt, P, R, chunk_sum);
-        k_fm_find_scan_b<<<dim3(1), dim3(256), 0, st>>>(chunk_sum, static_cast<uint32_t>(nchunks), &ctx->d_mail->fm_find.total);
-        k_fm_find_scan_c<<<dim3(static_cast<unsigned>(nchunks)), dim3(256), 0, st>>>(d_cnt, P, R, chunk_sum, d_offset);
-        k_fm_find_scan_a<<<dim3(static_cast<unsigned>(nchunks)), dim3(256), 0, st>>>(d_cut, P, R, cut_sum);
-        k_fm_find_scan_b<<<dim3(1), dim3(256), 0, st>>>(cut_sum, static_cast<uint32_t>(nchunks), &ctx->d_mail->fm_find.near_cut);
+        fm_scan_pairs(ctx, g, d_cnt, chunk_sum, &ctx->d_mail->fm_find.total, d_offset);
+        fm_scan_pairs(ctx, g, d_cut, cut_sum, &ctx->d_mail->fm_find.near_cut, nullptr);
     }
     DK_HIP(ctx, hipGetLastError());
     DK_TRY(ctx->mail_read(&ctx->h_mail->fm_find));
-    const uint64_t all = ctx->h_mail->fm_find.total;
-    *total_out = all;
     if (cut_out) *cut_out = ctx->h_mail->fm_find.near_cut;
-    a.nhits = static_cast<uint32_t>(std::min<uint64_t>(all, max_hits));
+    a.nhits = static_cast<uint32_t>(out.take(ctx->h_mail->fm_find.total));
     if (a.nhits) {
-        const FmLocate lc = fm_locate_carve(const_cast<void *>(d_loc), total, count, step);
-        const FmNearLocArgs l{FmWalk{d_bwt, ix.blocks, ix.base, ix.cp, lc.marks, lc.bits, lc.samples, static_cast<uint32_t>(total),
-                                     static_cast<uint32_t>(ceil_log2_u64(step)), static_cast<uint32_t>(lc.nsamp)},
-                              d_off, static_cast<uint32_t>(count), a.nhits, static_cast<uint4 *>(d_hits)};
+        const FmNearLocArgs l{fm_walk(fm, ix), fm.L.d_off, static_cast<uint32_t>(count), a.nhits, static_cast<uint4 *>(out.d_hits)};
         {
             LaunchScope ls(ctx, K_CHAIN, 12.0 * npairs + path_bytes + 16.0 * a.nhits);  // the pairs' walks again, and the records
             k_fm_near_emit<<<dim3(grid), dim3(64 * FM_WAVES), 0, st>>>(a);
         }
         {
             // per record the walk of k_fm_locate; the record read, its position written
-            LaunchScope ls(ctx, K_CHAIN, a.nhits * (36.0 + 0.5 * step * (FM_BLOCK + 128 + 64)));
+            LaunchScope ls(ctx, K_CHAIN, a.nhits * (36.0 + 0.5 * fm.step * (FM_BLOCK + 128 + 64)));
             const unsigned lgrid = static_cast<unsigned>(std::min<size_t>(div_up(a.nhits, FM_WAVES), 1u << 20));
             k_fm_near_locate<<<dim3(lgrid), dim3(64 * FM_WAVES), 0, st>>>(l);
         }
@@ -1011,19 +1004,18 @@ int fm_near_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, siz
     return DK_OK;
 }
 
-int fm_extract_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, const uint32_t *d_abase, size_t count, size_t total, const void *d_index,
-                      const void *d_ext, uint32_t step, const uint32_t *d_pos, const uint32_t *d_len, const uint32_t *d_rng_blk, size_t nrange,
-                      size_t max_len, uint8_t *d_out) {
-    const FmIndex ix = fm_carve(const_cast<void *>(d_index), total, count);
-    const size_t per = div_up(max_len, step) + 1, nitems = nrange * per;  // the most chunks a range of max_len bytes can touch
+int fm_extract_device(dk_ctx *ctx, const FmView &fm, const uint32_t *d_pos, const uint32_t *d_len, const uint32_t *d_rng_blk, size_t nrange, size_t max_len,
+                      uint8_t *d_out) {
+    const FmIndex ix = fm_carve(fm);
+    const size_t per = div_up(max_len, fm.step) + 1, nitems = nrange * per;  // the most chunks a range of max_len bytes can touch
     const unsigned grid = static_cast<unsigned>(std::min<size_t>(div_up(nitems, FM_WAVES), 1u << 20));
-    const FmExtArgs a{d_bwt, d_off, d_abase, ix.blocks, ix.base, ix.cp, static_cast<const uint32_t *>(d_ext) + FM_EXT_HEADER, d_pos, d_len, d_rng_blk,
-                      static_cast<uint32_t>(nrange), static_cast<uint32_t>(max_len), static_cast<uint32_t>(per), static_cast<uint32_t>(total),
-                      static_cast<uint32_t>(ceil_log2_u64(step)), d_out};
+    const FmExtArgs a{fm.L.bytes, fm.L.d_off, fm.d_abase, ix.blocks, ix.base, ix.cp, static_cast<const uint32_t *>(fm.ext) + FM_EXT_HEADER, d_pos, d_len,
+                      d_rng_blk, static_cast<uint32_t>(nrange), static_cast<uint32_t>(max_len), static_cast<uint32_t>(per),
+                      static_cast<uint32_t>(fm.L.total), static_cast<uint32_t>(ceil_log2_u64(fm.step)), d_out};
     DK_HIP(ctx, hipMemsetAsync(d_out, 0, nrange * max_len, ctx->stream));  // the zeros behind every range: the kernel stores text bytes only
     {
         // per range its two words and its row, twice (zeros, bytes); per byte and per step / 2 bytes walked in vain a row of L and a checkpoint word
-        LaunchScope ls(ctx, K_CHAIN, nrange * (8.0 + 2.0 * max_len + (max_len + 0.5 * step) * (FM_BLOCK + 64)));
+        LaunchScope ls(ctx, K_CHAIN, nrange * (8.0 + 2.0 * max_len + (max_len + 0.5 * fm.step) * (FM_BLOCK + 64)));
         k_fm_extract<<<dim3(grid), dim3(64 * FM_WAVES), 0, ctx->stream>>>(a);
     }
     DK_HIP(ctx, hipGetLastError());
@@ -1063,56 +1055,48 @@ FmSeamPlan fm_seam_plan(const std::vector<uint32_t> &off, size_t prev_len, size_
 }
 
 size_t fm_seams_workspace(const FmSeamPlan &pl, size_t npairs) {
-    auto r = [](size_t b) { return (b + 255) & ~size_t(255); };
-    return r(std::max<size_t>(pl.strip_len, 1)) + r(4 * pl.words.size()) + r(4 * npairs) + r(8 * npairs) + r(8 * FM_MAX_CHUNKS);
+    return ws_round(std::max<size_t>(pl.strip_len, 1)) + ws_round(4 * pl.words.size()) + ws_round(4 * npairs) + ws_round(8 * npairs) + ws_round(8 * FM_MAX_CHUNKS);
 }
 
-int fm_seams_device(dk_ctx *ctx, const uint8_t *d_bwt, const uint32_t *d_off, const uint32_t *d_abase, size_t count, size_t total, const void *d_index,
-                    const void *d_ext, uint32_t step, const uint8_t *d_prev, size_t prev_len, const FmSeamPlan &pl, const uint8_t *d_pat,
-                    const uint32_t *d_pat_off, size_t npat, size_t pat_bytes, size_t max_hits, void *d_hits, uint32_t *d_occ, uint64_t *total_out) {
+int fm_seams_device(dk_ctx *ctx, const FmView &fm, const uint8_t *d_prev, size_t prev_len, const FmSeamPlan &pl, const ItemView &pat, const HitSink &out) {
     hipStream_t st = ctx->stream;
-    const FmIndex ix = fm_carve(const_cast<void *>(d_index), total, count);
-    const size_t npairs = npat * count, rows = div_up(npairs, FM_FIND_ROW), rpc = div_up(rows, FM_MAX_CHUNKS), nchunks = div_up(rows, rpc);
-    const size_t mark = ctx->ws_mark(), nr = pl.nrange;
+    const FmIndex ix = fm_carve(fm);
+    const FmPairs g = fm_pairs(pat.count, fm.L.count);
+    const size_t npairs = g.npairs, count = fm.L.count, mark = ctx->ws_mark(), nr = pl.nrange;
     uint8_t *strip = ctx->ws_alloc<uint8_t>(std::max<size_t>(pl.strip_len, 1));
     uint32_t *d_plan = ctx->ws_alloc<uint32_t>(pl.words.size()), *d_cnt = ctx->ws_alloc<uint32_t>(npairs);
     uint64_t *d_offset = ctx->ws_alloc<uint64_t>(npairs), *chunk_sum = ctx->ws_alloc<uint64_t>(FM_MAX_CHUNKS);
     if (!strip || !d_plan || !d_cnt || !d_offset || !chunk_sum) return DK_E_NOMEM;
     const uint32_t *d_geo = d_plan, *d_blk = d_plan + 3 * count, *d_pos = d_blk + nr, *d_len = d_pos + nr, *d_out_off = d_len + nr;
-    const uint32_t P = static_cast<uint32_t>(npairs), R = static_cast<uint32_t>(rpc);
     // (pl outlives the copy: mail_read below synchronises, and so does every caller on failure)
     DK_HIP(ctx, hipMemcpyAsync(d_plan, pl.words.data(), pl.words.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     DK_HIP(ctx, hipMemsetAsync(strip, 0, std::max<size_t>(pl.strip_len, 1), st));
     if (prev_len) DK_HIP(ctx, hipMemcpyAsync(strip, d_prev, prev_len, hipMemcpyDeviceToDevice, st));
     {
-        const size_t per = div_up(pl.max_len, step) + 1, nitems = nr * per;
-        const FmExtArgs e{d_bwt, d_off, d_abase, ix.blocks, ix.base, ix.cp, static_cast<const uint32_t *>(d_ext) + FM_EXT_HEADER, d_pos, d_len, d_blk,
-                          static_cast<uint32_t>(nr), static_cast<uint32_t>(pl.max_len), static_cast<uint32_t>(per), static_cast<uint32_t>(total),
-                          static_cast<uint32_t>(ceil_log2_u64(step)), strip, d_out_off};
+        const size_t per = div_up(pl.max_len, fm.step) + 1, nitems = nr * per;
+        const FmExtArgs e{fm.L.bytes, fm.L.d_off, fm.d_abase, ix.blocks, ix.base, ix.cp, static_cast<const uint32_t *>(fm.ext) + FM_EXT_HEADER, d_pos, d_len,
+                          d_blk, static_cast<uint32_t>(nr), static_cast<uint32_t>(pl.max_len), static_cast<uint32_t>(per),
+                          static_cast<uint32_t>(fm.L.total), static_cast<uint32_t>(ceil_log2_u64(fm.step)), strip, d_out_off};
         const unsigned grid = static_cast<unsigned>(std::min<size_t>(div_up(nitems, FM_WAVES), 1u << 20));
         // extract's traffic for the strip's bytes: per byte, and per step / 2 bytes walked in vain per range, a row of L and a checkpoint word
-        LaunchScope ls(ctx, K_CHAIN, 16.0 * nr + 2.0 * pl.strip_len + (static_cast<double>(pl.strip_len) + 0.5 * step * nr) * (FM_BLOCK + 64));
+        LaunchScope ls(ctx, K_CHAIN, 16.0 * nr + 2.0 * pl.strip_len + (static_cast<double>(pl.strip_len) + 0.5 * fm.step * nr) * (FM_BLOCK + 64));
         k_fm_extract<<<dim3(grid), dim3(64 * FM_WAVES), 0, st>>>(e);
     }
-    FmSeamArgs a{strip, d_geo, d_pat, d_pat_off, static_cast<uint32_t>(npat), static_cast<uint32_t>(count), static_cast<uint32_t>(pl.strip_len),
-                 d_cnt, d_occ, d_offset, 0u, static_cast<uint4 *>(d_hits)};
+    FmSeamArgs a{strip, d_geo, pat.bytes, pat.d_off, static_cast<uint32_t>(pat.count), static_cast<uint32_t>(count), static_cast<uint32_t>(pl.strip_len),
+                 d_cnt, out.d_occ, d_offset, 0u, static_cast<uint4 *>(out.d_hits)};
     const unsigned grid = static_cast<unsigned>(std::min<size_t>(div_up(npairs, FM_WAVES), 1u << 20));
     {
-        // per pair its three words, the pattern's first word per candidate (a mismatch ends a compare; pat_bytes / npat candidates at most) and occ
-        LaunchScope ls(ctx, K_CHAIN, 24.0 * npairs + 16.0 * static_cast<double>(count) * pat_bytes);
+        // per pair its three words, the pattern's first word per candidate (a mismatch ends a compare; pat.nbytes / pat.count candidates at most) and occ
+        LaunchScope ls(ctx, K_CHAIN, 24.0 * npairs + 16.0 * static_cast<double>(count) * pat.nbytes);
         k_fm_seam_count<<<dim3(grid), dim3(64 * FM_WAVES), 0, st>>>(a);
     }
     {
         LaunchScope ls(ctx, K_CHAIN, 16.0 * npairs);  // occ read twice, the offsets written
-        k_fm_find_scan_a<<<dim3(static_cast<unsigned>(nchunks)), dim3(256), 0, st>>>(d_cnt, P, R, chunk_sum);
-        k_fm_find_scan_b<<<dim3(1), dim3(256), 0, st>>>(chunk_sum, static_cast<uint32_t>(nchunks), &ctx->d_mail->fm_find.total);
-        k_fm_find_scan_c<<<dim3(static_cast<unsigned>(nchunks)), dim3(256), 0, st>>>(d_cnt, P, R, chunk_sum, d_offset);
+        fm_scan_pairs(ctx, g, d_cnt, chunk_sum, &ctx->d_mail->fm_find.total, d_offset);
     }
     DK_HIP(ctx, hipGetLastError());
     DK_TRY(ctx->mail_read(&ctx->h_mail->fm_find.total));
-    const uint64_t all = ctx->h_mail->fm_find.total;
-    *total_out = all;
-    a.nhits = static_cast<uint32_t>(std::min<uint64_t>(all, max_hits));
+    a.nhits = static_cast<uint32_t>(out.take(ctx->h_mail->fm_find.total));
     if (a.nhits) {
         {
             // per pair occ and its offset; per hit the pair's compare again and the record

@@ -318,10 +318,11 @@ int lcp_phi_block_device(dk_ctx *ctx, const uint32_t *d_sa, const uint32_t *d_of
     return DK_OK;
 }
 
-int lcp_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, size_t count, size_t total, const uint32_t *d_sa, uint32_t *d_lcp,
-               uint32_t *d_phi_ready) {
+int lcp_device(dk_ctx *ctx, const PackView &text, const uint32_t *d_sa, uint32_t *d_lcp, uint32_t *d_phi_ready) {
     hipStream_t st = ctx->stream;
-    const uint32_t cnt = static_cast<uint32_t>(count), T = static_cast<uint32_t>(total);
+    const uint8_t *d_text = text.bytes;
+    const size_t total = text.total;
+    const uint32_t cnt = static_cast<uint32_t>(text.count), T = static_cast<uint32_t>(total);
     const unsigned grid = static_cast<unsigned>(div_up(total, 256)), ntiles = static_cast<unsigned>(div_up(total, LCP_TILE));
     // (tuning build: the caps and the lists' capacity come from the environment -- tests send the same inputs down the other routes with them)
     const uint32_t lane_cap = static_cast<uint32_t>(std::max(16, std::min(1 << 20, DK_KNOB("DK_LCP_LANE_CAP", LCP_LANE_CAP))));
@@ -348,7 +349,7 @@ int lcp_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, size_t
     if (!d_phi_ready) {
         DK_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(phi), static_cast<int>(LCP_MARK), total, st));
         LaunchScope ls(ctx, K_BWT_GATHER, 12.0 * total);  // SA 4 n, a scattered 4-byte store per slot, the preset 4 n
-        k_lcp_phi<<<dim3(grid), dim3(256), 0, st>>>(d_sa, d_off, cnt, 0u, T, phi, d_mail);
+        k_lcp_phi<<<dim3(grid), dim3(256), 0, st>>>(d_sa, text.d_off, cnt, 0u, T, phi, d_mail);
     }
     DK_HIP(ctx, hipGetLastError());
     uint32_t passes = 0, route = 0;
@@ -357,11 +358,11 @@ int lcp_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, size_t
         if (passes) DK_TRY(ctx->mail_fill(&d_mail->lists, 0));
         {
             LaunchScope ls(ctx, K_CHAIN, 10.0 * total);  // phi read and written, T[p-1] and a line of text at q
-            k_lcp_measure<<<dim3(grid), dim3(256), 0, st>>>(d_text, d_off, cnt, T, phi, lane_cap, d_long, static_cast<uint32_t>(long_cap), d_mail, d_cnt);
+            k_lcp_measure<<<dim3(grid), dim3(256), 0, st>>>(d_text, text.d_off, cnt, T, phi, lane_cap, d_long, static_cast<uint32_t>(long_cap), d_mail, d_cnt);
         }
         {
             LaunchScope ls(ctx, K_CHAIN, 0.0);
-            k_lcp_wave<<<dim3(512), dim3(256), 0, st>>>(d_text, d_off, cnt, phi, d_long, static_cast<uint32_t>(long_cap), lane_cap, wave_cap, d_giant,
+            k_lcp_wave<<<dim3(512), dim3(256), 0, st>>>(d_text, text.d_off, cnt, phi, d_long, static_cast<uint32_t>(long_cap), lane_cap, wave_cap, d_giant,
                                                         static_cast<uint32_t>(giant_cap), d_mail, d_cnt);
         }
         DK_HIP(ctx, hipGetLastError());
@@ -400,7 +401,7 @@ int lcp_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, size_t
     }
     {
         LaunchScope ls(ctx, K_BWT_GATHER, 12.0 * total);  // SA 4 n, a gathered word per slot, LCP 4 n
-        k_lcp_gather<<<dim3(grid), dim3(256), 0, st>>>(d_sa, d_off, cnt, T, phi, d_lcp);
+        k_lcp_gather<<<dim3(grid), dim3(256), 0, st>>>(d_sa, text.d_off, cnt, T, phi, d_lcp);
     }
     DK_HIP(ctx, hipGetLastError());
     ctx->stats.sa_route |= route;

@@ -409,8 +409,9 @@ __global__ __launch_bounds__(256) void k_sa_smem_emit(const uint32_t *__restrict
 
 }  // namespace
 
-int sa_check_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, size_t count, size_t total, const uint32_t *d_sa, uint32_t *h_words) {
+int sa_check_device(dk_ctx *ctx, const PackView &text, const uint32_t *d_sa, uint32_t *h_words) {
     hipStream_t st = ctx->stream;
+    const size_t count = text.count, total = text.total;
     const uint32_t cnt = static_cast<uint32_t>(count), T = static_cast<uint32_t>(total);
     const unsigned grid = static_cast<unsigned>(div_up(total, 256));
     const size_t mark = ctx->ws_mark();
@@ -420,15 +421,15 @@ int sa_check_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, s
     DK_HIP(ctx, hipMemsetAsync(words, 0xFF, 3 * count * sizeof(uint32_t), st));
     {
         LaunchScope ls(ctx, K_BWT_GATHER, 12.0 * total);  // SA 4 n, a scattered 4-byte store per slot, the preset 4 n
-        k_sa_check_scatter<<<dim3(grid), dim3(256), 0, st>>>(d_sa, d_off, cnt, T, isa, words);
+        k_sa_check_scatter<<<dim3(grid), dim3(256), 0, st>>>(d_sa, text.d_off, cnt, T, isa, words);
     }
     {
         LaunchScope ls(ctx, K_BWT_GATHER, 4.0 * total);
-        k_sa_check_missing<<<dim3(grid), dim3(256), 0, st>>>(isa, d_off, cnt, T, words);
+        k_sa_check_missing<<<dim3(grid), dim3(256), 0, st>>>(isa, text.d_off, cnt, T, words);
     }
     {
         LaunchScope ls(ctx, K_BWT_GATHER, 18.0 * total);  // SA twice 8 n, two gathered bytes, two gathered words of isa (where the bytes are equal)
-        k_sa_check_order<<<dim3(grid), dim3(256), 0, st>>>(d_text, d_sa, d_off, cnt, T, isa, words);
+        k_sa_check_order<<<dim3(grid), dim3(256), 0, st>>>(text.bytes, d_sa, text.d_off, cnt, T, isa, words);
     }
     DK_HIP(ctx, hipGetLastError());
     DK_HIP(ctx, hipMemcpyAsync(h_words, words, 3 * count * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -437,32 +438,32 @@ int sa_check_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, s
     return DK_OK;
 }
 
-int sa_search_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, const uint32_t *d_sa, const uint8_t *d_pat, const uint32_t *d_pat_off,
-                     const uint32_t *d_pat_blk, size_t npat, size_t longest, size_t shortest, uint32_t *d_lo, uint32_t *d_hi) {
+int sa_search_device(dk_ctx *ctx, const PackView &text, const uint32_t *d_sa, const ItemView &pat, uint32_t *d_lo, uint32_t *d_hi) {
     hipStream_t st = ctx->stream;
     // (tuning build: DK_SA_SEARCH_LANE_MAX moves the border between the two kernels -- tests send short patterns down the long one with it)
     const uint32_t lane_max = static_cast<uint32_t>(std::max(0, std::min(1 << 20, DK_KNOB("DK_SA_SEARCH_LANE_MAX", SA_SEARCH_LANE_MAX))));
-    const unsigned grid = static_cast<unsigned>(std::min<size_t>(div_up(npat, SQ_WAVES), 1u << 20));
-    const SqArgs a{d_text, d_sa, d_off, d_pat, d_pat_off, d_pat_blk, static_cast<uint32_t>(npat), lane_max, d_lo, d_hi};
-    if (shortest <= lane_max) {
-        LaunchScope ls(ctx, K_CHAIN, 8.0 * npat);
+    const unsigned grid = static_cast<unsigned>(std::min<size_t>(div_up(pat.count, SQ_WAVES), 1u << 20));
+    const SqArgs a{text.bytes, d_sa, text.d_off, pat.bytes, pat.d_off, pat.d_blk, static_cast<uint32_t>(pat.count), lane_max, d_lo, d_hi};
+    if (pat.shortest <= lane_max) {
+        LaunchScope ls(ctx, K_CHAIN, 8.0 * pat.count);
         k_sa_search<<<dim3(grid), dim3(64 * SQ_WAVES), 0, st>>>(a);
     }
-    if (longest > lane_max) {
-        LaunchScope ls(ctx, K_CHAIN, 8.0 * npat);
+    if (pat.longest > lane_max) {
+        LaunchScope ls(ctx, K_CHAIN, 8.0 * pat.count);
         k_sa_search_long<<<dim3(grid), dim3(64 * SQ_WAVES), 0, st>>>(a);
     }
     DK_HIP(ctx, hipGetLastError());
     return DK_OK;
 }
 
-int sa_match_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, const uint32_t *d_sa, const uint8_t *d_qry, const uint32_t *d_q_off,
-                    const uint32_t *d_q_blk, size_t nq, size_t qbytes, size_t max_len, uint32_t *d_len, uint32_t *d_lo, uint32_t *d_hi) {
+int sa_match_device(dk_ctx *ctx, const PackView &text, const uint32_t *d_sa, const ItemView &qry, size_t max_len, uint32_t *d_len, uint32_t *d_lo, uint32_t *d_hi) {
     hipStream_t st = ctx->stream;
+    const size_t qbytes = qry.nbytes;
     // (the border is the search's, and so is its knob: a match that reaches it goes on in k_sa_match_long, whatever the window's length)
     const uint32_t lane_max = static_cast<uint32_t>(std::max(0, std::min(1 << 20, DK_KNOB("DK_SA_SEARCH_LANE_MAX", SA_SEARCH_LANE_MAX))));
     const uint32_t cap = static_cast<uint32_t>(std::min<size_t>(max_len, 0xFFFFFFFFull));
-    const SmArgs a{d_text, d_sa, d_off, d_qry, d_q_off, d_q_blk, static_cast<uint32_t>(nq), static_cast<uint32_t>(qbytes), cap, lane_max, d_len, d_lo, d_hi};
+    const SmArgs a{text.bytes, d_sa, text.d_off, qry.bytes, qry.d_off, qry.d_blk, static_cast<uint32_t>(qry.count), static_cast<uint32_t>(qbytes), cap, lane_max,
+                   d_len, d_lo, d_hi};
     {
         // per position three searches of about three steps of 64 slots and 64 short compares; the three results
         LaunchScope ls(ctx, K_CHAIN, qbytes * (9.0 * 64 * 20 + 12.0));
@@ -479,36 +480,33 @@ int sa_match_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, c
 }
 
 size_t sa_smems_workspace(size_t qbytes) {
-    auto r = [](size_t b) { return (b + 255) & ~size_t(255); };
-    return 4 * r(4 * qbytes) + r(4 * div_up(qbytes, SM_TILE));
+    return 4 * ws_round(4 * qbytes) + ws_round(4 * div_up(qbytes, SM_TILE));
 }
 
-int sa_smems_device(dk_ctx *ctx, const uint8_t *d_text, const uint32_t *d_off, const uint32_t *d_sa, const uint8_t *d_qry, const uint32_t *d_q_off,
-                    const uint32_t *d_q_blk, size_t nq, size_t qbytes, size_t min_len, size_t max_len, size_t max_hits, void *d_hits, uint64_t *total_out) {
+int sa_smems_device(dk_ctx *ctx, const PackView &text, const uint32_t *d_sa, const ItemView &qry, size_t min_len, size_t max_len, const HitSink &out) {
     hipStream_t st = ctx->stream;
+    const size_t qbytes = qry.nbytes;
     const size_t ntiles = div_up(qbytes, SM_TILE), mark = ctx->ws_mark();
     uint32_t *d_len = ctx->ws_alloc<uint32_t>(qbytes), *d_lo = ctx->ws_alloc<uint32_t>(qbytes), *d_hi = ctx->ws_alloc<uint32_t>(qbytes);
     uint32_t *d_flag = ctx->ws_alloc<uint32_t>(qbytes), *tile_sum = ctx->ws_alloc<uint32_t>(ntiles);
     if (!d_len || !d_lo || !d_hi || !d_flag || !tile_sum) return DK_E_NOMEM;
-    DK_TRY(sa_match_device(ctx, d_text, d_off, d_sa, d_qry, d_q_off, d_q_blk, nq, qbytes, max_len, d_len, d_lo, d_hi));
+    DK_TRY(sa_match_device(ctx, text, d_sa, qry, max_len, d_len, d_lo, d_hi));
     const uint32_t Q = static_cast<uint32_t>(qbytes), T = static_cast<uint32_t>(ntiles);
     {
         LaunchScope ls(ctx, K_CHAIN, 20.0 * qbytes);  // the lengths and the flags, the flags read twice more
         k_sa_smem_mark<<<dim3(static_cast<unsigned>(div_up(qbytes, 256))), dim3(256), 0, st>>>(
-            d_len, d_q_off, static_cast<uint32_t>(nq), Q, static_cast<uint32_t>(std::min<size_t>(min_len, 0xFFFFFFFFull)),
+            d_len, qry.d_off, static_cast<uint32_t>(qry.count), Q, static_cast<uint32_t>(std::min<size_t>(min_len, 0xFFFFFFFFull)),
             static_cast<uint32_t>(std::min<size_t>(max_len, 0xFFFFFFFFull)), d_flag);
         k_sa_smem_scan_a<<<dim3(T), dim3(256), 0, st>>>(d_flag, Q, tile_sum);
         k_sa_smem_scan_b<<<dim3(1), dim3(256), 0, st>>>(tile_sum, T, &ctx->d_mail->sa_match.total);
     }
     DK_HIP(ctx, hipGetLastError());
     DK_TRY(ctx->mail_read(&ctx->h_mail->sa_match.total));
-    const uint64_t all = ctx->h_mail->sa_match.total;
-    *total_out = all;
-    const size_t nhits = static_cast<size_t>(std::min<uint64_t>(all, max_hits));
+    const size_t nhits = out.take(ctx->h_mail->sa_match.total);
     if (nhits) {
         {
             LaunchScope ls(ctx, K_CHAIN, 4.0 * qbytes + 28.0 * nhits);
-            k_sa_smem_emit<<<dim3(T), dim3(256), 0, st>>>(d_flag, d_len, d_lo, d_hi, Q, tile_sum, static_cast<uint32_t>(nhits), static_cast<uint4 *>(d_hits));
+            k_sa_smem_emit<<<dim3(T), dim3(256), 0, st>>>(d_flag, d_len, d_lo, d_hi, Q, tile_sum, static_cast<uint32_t>(nhits), static_cast<uint4 *>(out.d_hits));
         }
         DK_HIP(ctx, hipGetLastError());
         DK_HIP(ctx, hipStreamSynchronize(st));

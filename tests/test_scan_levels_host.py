@@ -47,7 +47,9 @@ def test_constants_are_the_sources():
     assert S.SM_TRIP == 256 and "for (uint32_t c = 0; c < ntiles; c += 256u)" in saq and "k_sa_smem_scan_b<<<dim3(1), dim3(256), 0, st>>>" in saq
     # the drivers' arithmetic, as restated in fm_levels, find_levels and ibwt_levels
     assert "const size_t rows = ix.rows, rpc = div_up(rows, FM_MAX_CHUNKS), nchunks = div_up(rows, rpc);" in fmi
-    assert fmi.count("rows = div_up(npairs, FM_FIND_ROW), rpc = div_up(rows, FM_MAX_CHUNKS), nchunks = div_up(rows, rpc);") == 3
+    # (find, near and seams share fm_pairs: one place, and none of the three keeps arithmetic of its own)
+    assert fmi.count("rows = div_up(npairs, FM_FIND_ROW), rpc = div_up(rows, FM_MAX_CHUNKS), nchunks = div_up(rows, rpc);") == 1
+    assert fmi.count("const FmPairs g = fm_pairs(") == 3 and fmi.count("div_up(npairs, FM_FIND_ROW)") == 1
     assert "const size_t ntiles = div_up(total, IB_TILE), tpc = div_up(ntiles, IB_MAX_CHUNKS), nchunks = div_up(ntiles, tpc);" in bwt
     assert "const uint32_t stride = (phi - plo + 63u) >> 6" in fmi
 
